@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the PCG hot path (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,11 +11,16 @@ pcg_max_iter = 167, pcg_exit_tol = 1e-4) solved by ONE launch of the PCG kernel 
 ranks just get their own `batch` (weak scaling) and the only collectives are the barrier, the max-over-ranks of the time and the
 gather of the per-trajectory results (RCCL).  Inputs are synthetic (mpcgpu_amd.synth), built and resident in HBM before the timed region.
 
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.  `--full` adds everything else the benchmark
+measures after the timed region: the sustained leg, the side legs of tools/bench_legs.py (rooflines, producers, latencies, long
+horizons, double precision, ...) and the CPU baseline; `--full --no-extras` drops the side legs and keeps the other two.
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64): lambda (the
+solution, B x 14N per rank), pcg_iters and pcg_exit (per trajectory, gathered over the ranks); the inputs depend only on the arguments.
+
 Output (rank 0):
   * the LAST stdout line = ONE compact JSON object (< 6 KB, strict JSON, scalars first): metric / value / steps / ms_per_step / config /
     roofline / cpu_baseline — what the driver parses (`compact_line`, tests/test_bench_line.py holds its size);
-  * everything else — every side leg's full object — goes to `gpurun_out/bench_full.json` (`--full-json PATH`), never to stdout.
-The side legs live in tools/bench_legs.py; `--no-extras` runs the timed region only.
+  * with --full, everything else — every side leg's full object — goes to `bench_out/bench_full.json` (`--full-json PATH`), never to stdout.
 """
 from __future__ import annotations
 
@@ -187,6 +192,28 @@ def emit(full: dict, path: str | None):
     return line
 
 
+DUMP_LIMIT = 64 << 20     # bytes of .npy data one --dump-outputs run may write in all
+DUMP_SEED = 20260101      # fixed: the rows a too-large lambda is sampled down to are the same in every run
+
+
+def dump_outputs(d: str, lam: np.ndarray, iters: np.ndarray, exits: np.ndarray, rank: int, world: int):
+    """--dump-outputs: what a caller of the timed path receives after its last step.  Rank 0 writes the gathered per-trajectory
+    pcg_iters / pcg_exit (float64 / float32), every rank its own lambda shard (lambda.npy, lambda_rank<r>.npy when world > 1).  A lambda
+    beyond its share of DUMP_LIMIT is cut to a seeded sample of trajectories (rows listed in lambda_rows.npy)."""
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    lam = np.ascontiguousarray(lam, dtype=np.float32)
+    cap_rows = max(1, (DUMP_LIMIT - 16 * iters.size - (1 << 20)) // world // (lam[0].nbytes + 8))     # (+8: its entry in lambda_rows)
+    if lam.shape[0] > cap_rows:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(lam.shape[0], cap_rows, replace=False))
+        lam = lam[rows]
+        np.save(os.path.join(d, f"lambda_rows{sfx}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, f"lambda{sfx}.npy"), lam)
+    if rank == 0:
+        np.save(os.path.join(d, "pcg_iters.npy"), iters.astype(np.float64))
+        np.save(os.path.join(d, "pcg_exit.npy"), exits.astype(np.float32))
+
+
 def _free_port():
     import socket
     sk = socket.socket()
@@ -270,14 +297,19 @@ def main():
     ap.add_argument("--pcg-waves", type=int, default=0)
     ap.add_argument("--reg-rows", type=int, default=-1)
     ap.add_argument("--lds-rows", type=int, default=-2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the sustained leg, the side legs (tools/bench_legs.py) and the CPU baseline, and write "
+                         "the full record (--full-json); a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (lambda, pcg_iters, pcg_exit) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region (no side legs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no side legs (the sustained leg and the CPU baseline still run)")
     ap.add_argument("--profile-lean", action="store_true",
-                    help="for rocprofv3 passes: only the timed region + the two HBM roofline kernels, so that per-kernel averages are not "
+                    help="for rocprofv3 passes (implies --full): only the timed region + the two HBM roofline kernels, so that per-kernel averages are not "
                          "diluted by the batch-1 latency launches and the parity sample")
     ap.add_argument("--profile-mini", action="store_true",
-                    help="what the PMC passes execute: the timed region, the SpMV leg and the producer kernels (one launch shape each), nothing else")
+                    help="what the PMC passes execute (implies --full): the timed region, the SpMV leg and the producer kernels (one launch shape each), nothing else")
     ap.add_argument("--inrun-pmc", action="store_true",
                     help="OPT-IN: spawn two rocprofv3 --pmc child passes of this script for roofline.traffic (default: profiles/traffic.json, the committed passes)")
     ap.add_argument("--sustain-seconds", type=float, default=3.0, help="length of the sustained leg (back-to-back timed steps; 0 = skip)")
@@ -285,14 +317,21 @@ def main():
     ap.add_argument("--spmv-batch", type=int, default=4096, help="trajectories streamed by the SpMV roofline run (S = batch x 301 KB)")
     ap.add_argument("--storage", default="f32", choices=["f32", "f16"],
                     help="matrix storage of S/Pinv; f16 = BASELINE config 5's reduced-precision experiment (arithmetic stays fp32)")
-    ap.add_argument("--full-json", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"), help="where the full record goes ('' = nowhere)")
+    ap.add_argument("--full-json", default=None,
+                    help="where the full record goes ('' = nowhere; default: bench_out/bench_full.json with --full, nowhere without)")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="launcher / collective dry run (CPU test of the N > 1 flow, tests/test_bench_launcher.py): every rank runs the whole "
                          "distributed flow of this file with made-up iteration counts and NO solve; prints value = null")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.profile_mini:
         args.profile_lean = True
         args.no_cpu_baseline = True
+    if args.profile_lean:
+        args.full = True
+    if args.full_json is None:
+        args.full_json = os.path.join(ROOT, "bench_out", "bench_full.json") if args.full else ""
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # bare `python bench.py --gpus N`: this process becomes the launcher of N ranks (one per GPU, RCCL), it does not degrade to one rank
@@ -320,10 +359,10 @@ def main():
     max_iter = args.max_iter or synth.pcg_max_iter(N)
     cfg = pcg_config(pcg_exit_tol=args.exit_tol, pcg_max_iter=max_iter)
 
-    sol = PcgSolver(N, max_batch=max(B, args.spmv_batch if not args.no_extras else B), device=local_rank)
+    sol = PcgSolver(N, max_batch=max(B, args.spmv_batch if args.full and not args.no_extras else B), device=local_rank)
     d_S, d_P, d_g = L.build_inputs(sol, N, B, seed0, args.precond, dev, chunk=B if args.profile_lean else 128)      # (PMC passes: one launch shape per kernel)
     ns = min(32, B)
-    S_h, P_h, g_h = (t[:ns].cpu().numpy() for t in (d_S, d_P, d_g))     # host copies of the CPU-baseline sample
+    S_h, P_h, g_h = (t[:ns].cpu().numpy() if args.full else None for t in (d_S, d_P, d_g))     # host copies of the CPU-baseline sample
     d_lam = torch.zeros(B, 14 * N, device=dev)
     d_it = torch.zeros(B, dtype=torch.int32, device=dev)
     d_ex = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -390,6 +429,8 @@ def main():
 
     ms_per_step = 1e3 * t_all / args.steps
     value = iters_step_all / (t_all / args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_lam.cpu().numpy(), g_it.cpu().numpy(), g_ex.cpu().numpy(), rank, world)
 
     cx = types.SimpleNamespace(sol=sol, dev=dev, N=N, B=B, args=args, cfg=cfg, max_iter=max_iter, rank=rank, world=world, seed0=seed0,
                                d_S=d_S, d_P=d_P, d_g=d_g, d_lam=d_lam, d_it=d_it, d_ex=d_ex, run_solve=run_solve, it_host=it_host,
@@ -398,7 +439,7 @@ def main():
     # ---- sustained leg: the very same step back to back for >= --sustain-seconds (steady-state clocks; a 25 ms timed region is invisible
     # to a 5 s utilisation sampler) ----
     sustained = None
-    if args.sustain_seconds > 0 and not args.profile_lean:
+    if args.full and args.sustain_seconds > 0 and not args.profile_lean:
         n_chunk = max(8, int(0.25 / max(ms_per_step * 1e-3, 1e-5)))          # ~0.25 s of steps between two host synchronisations
         done, t_s0 = 0, time.perf_counter()
         D.barrier()
@@ -472,7 +513,7 @@ def main():
                 rr["valu_active_frac"] = tr["valu_active_frac"]      # SQ_ACTIVE_INST_VALU / (4 SIMDs x SQ_BUSY_CYCLES), same passes
         out["roofline_resident"] = rr
 
-    extras = not args.no_extras and args.storage == "f32"
+    extras = args.full and not args.no_extras and args.storage == "f32"
     lean, mini = args.profile_lean, args.profile_mini
     solo = rank == 0 and world == 1
     if extras:
@@ -514,7 +555,7 @@ def main():
         run_leg(out, "scaling_expectation", L.scaling_expectation, cx)
     if extras and rank == 0 and not lean:
         run_leg(out, "block_solve", L.block_solve, cx)
-    if solo and not args.no_cpu_baseline and not lean:
+    if solo and args.full and not args.no_cpu_baseline and not lean:
         cb = run_leg(out, "cpu_baseline", L.cpu_baseline, cx, args.cpu_seconds)
         if "value" in cb:
             cb["gpu_linsolves_per_sec"] = out["linsolves_per_sec"]

@@ -1,6 +1,6 @@
 """The side legs of bench.py (everything that is NOT the timed region): each takes the bench context `cx` (a SimpleNamespace made by
 bench.py: sol, dev, N, B, args, cfg, max_iter, the device arrays of the timed workload) and returns a dict for the FULL record
-(`gpurun_out/bench_full.json`).  bench.py picks a few scalars out of them for the one compact line the driver parses.
+(`bench_out/bench_full.json`); they run only with `bench.py --full`.  bench.py picks a few scalars out of them for the one compact line the driver parses.
 
 Every leg is wrapped by bench.py's `run_leg`: a failing leg is reported as {"error": ...} and never costs the headline line.
 Only `cpu_baseline`, `parity_sample` and nothing else here touch oracle/ (the checker), after the timed region, as DESIGN.md §4 allows.
