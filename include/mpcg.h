@@ -101,10 +101,12 @@ const char *mpcg_build_info(void);
 
 /* Handle = per-device solver context for fixed (state_size, knot_points).  Replaces the
  * per-call cudaMalloc of PCG scratch in sqpSolvePcg (include/pcg/sqp.cuh:116-135): the solver
- * needs no global scratch at all (r, p, upsilon live in LDS), the handle only caches launch
- * configuration and owns three device buffers: the hand-off cells of the cluster kernel (1 KiB per CU, allocated
- * here) and, from their first use on, the staging buffer of mpcg_form_schur and the sweep scratch of
- * mpcg_block_solve.  max_batch bounds `batch` of later calls.  device < 0 = current device.  One handle per
+ * needs no global scratch at all (r, p, upsilon live in LDS), the handle caches launch configuration and owns
+ * device buffers: allocated here, the hand-off cells of the float cluster kernel, the dispatch-order buffer of "sched_hint",
+ * the pinned word of the symmetry latch, the copy of d_lambda a cluster follow-up launch starts from (knot_points > 128)
+ * and, for handles with at most 8 MB of double iterates, the double cluster kernels' buffers (GRAPH CAPTURE); from their
+ * first use on, the staging buffers of mpcg_form_schur(_f64), the seam buffer of the chunk-walking Schur kernel and the
+ * sweep scratch of mpcg_block_solve.  max_batch bounds `batch` of later calls.  device < 0 = current device.  One handle per
  * (device, knot_points) and per concurrently used stream: calls on the same handle must not overlap on the host
  * side (launch knobs are chosen per call) and their device work must be ordered (one stream, or events) because
  * they share those buffers; different handles are independent. */
@@ -225,8 +227,9 @@ int mpcg_prep_csr(mpcg_handle *h, int32_t *d_col_ptr, int32_t *d_row_ind, void *
 int mpcg_bd_to_csr_lowertri(mpcg_handle *h, const float *d_S, float *d_val, float mult, uint32_t batch, void *stream);
 
 /* linsys_t = double (USE_DOUBLES=1, include/common/settings.cuh:41-49): the same solve, same semantics, in double
- * precision.  A functional path (S and Pinv are streamed every iteration), limited to knot_points <= 350 (iterate
- * vectors in LDS).  mpcg_pcg_solve_ref_f64 carries the reference kernel's 12 arguments for pcg<double, n, N>. */
+ * precision.  Register-resident kernels up to 512 knots with block-symmetric matrices (one CU up to 64 knots, clusters of
+ * CUs beyond; 256 otherwise), the streaming kernel (S and Pinv read every iteration, iterate vectors in LDS: knot_points
+ * <= 350) for "cluster" = 0 and the horizons between (Options: kernel selection).  mpcg_pcg_solve_ref_f64 carries the reference kernel's 12 arguments for pcg<double, n, N>. */
 int mpcg_pcg_solve_f64(mpcg_handle *h, const double *d_S, const double *d_Pinv, const double *d_gamma, double *d_lambda,
                        uint32_t batch, uint32_t max_iter, double exit_tol, mpcg_precond precond,
                        uint32_t *d_iters, uint8_t *d_max_iter_exit, void *stream);
@@ -317,38 +320,50 @@ int mpcg_ldl_solve(mpcg_ldl *l, const float *h_val, const float *h_gamma, float 
 int mpcg_qdldl_solve_schur(mpcg_handle *h, mpcg_ldl *l, const float *d_val, const float *d_gamma, float *d_lambda, void *stream);
 
 /* Options (tuning / experiments; defaults are chosen by mpcg_create from knot_points and per call from the batch).
- * Kernel selection of a float solve (state_size 14):
- *   "pcg_rpl" (-1 auto / 0 / 1): the row-per-lane kernel for knot_points <= 64 — a DPP row per knot, vectors in registers; automatic for
- *       knot_points <= 32 (below 2.5 trajectories per CU at 16 < knot_points <= 32; with "pcg_lqb" = 0 also for calls of at most one trajectory per CU up to 64); "rpl_waves" (its wavefronts per trajectory: 0 auto, 4, 8, 16);
- *   "pcg_lpk" (-1 auto / 0 / 1): the lane-pair-per-knot kernel, knot_points <= 128 — everything in registers, a matrix per wavefront; the automatic
- *       choice for fp16 storage only since round 6; = 1 forces it (and keeps the lane-quad kernel out);
- *   "pcg_lqb" (-1 auto / 0 / 1; round 6): the lane-quad-per-knot kernel, knot_points <= 128 — everything in registers, a QUARTER of both matrices
- *       in every wavefront, so that all wavefronts of a workgroup run every pass (two working wavefronts per SIMD).  It takes the lane-pair
- *       kernel's launches (same contract: block lower triangle, gated and fix-up launches, dispatch order); automatic, for both preconditioners, for 32 < knot_points <= 64
- *       at every batch, at 64 < knot_points <= 128, and — with workgroups of 32 knots, four per CU — for
- *       16 < knot_points <= 32 when the call brings at least 2.5 trajectories per CU (block-Jacobi calls run a build of their own); = 0 gives those calls back to the lane-pair kernel (and
- *       the row-per-lane / row-pair kernels their round-5 ranges), = 1 runs it wherever the lane-pair kernel would run;
- *   "cluster" (-1 auto / 0 off / G = 2..8 forced): workgroups (= CUs of one XCD) per trajectory of the clustered lane-pair kernel, automatic
- *       for knot_points > 128 (G = ceil(N / 128)).  Members exchange inner-product partials and boundary knots through the XCD's L2
- *       ("cluster_l2" = 0: always write-through), so all members of a cluster must be resident: the launch holds as many clusters as fit the
- *       chip and each draws trajectories from a queue (any batch = one launch).  A cluster that cannot make progress (a peer not resident:
- *       another stream holds its CU) gives up after a bounded spin and the follow-up launch of a single-workgroup kernel re-solves its
- *       trajectory ("cluster_fixup" = 0: no follow-up launch, d_iters = 0xFFFFFFFF and d_max_iter_exit = 2 for such a trajectory).  The
- *       follow-up launch warm-starts from the handle's own copy of d_lambda, made in front of the cluster launch: members that did finish such a
- *       trajectory have written their knots by then.  ("cluster_test_fail" = 1, tests only: one member gives up at its first write-back.)
- *       linsys_t = double (mpcg_pcg_solve_f64 / _ref_f64): knot_points <= 32 the row-per-lane kernel in double; beyond, with block-symmetric
- *       matrices (the latch), "pcg_lqk" (-1 auto / 0 / 1): the lane-quad-per-knot kernel — the lower block triangle of 64 knots in the registers of
- *       one CU (32 < knot_points <= 64, and 16 < knot_points <= 32 for calls of at least four trajectories per CU; = 1 forces it at any
- *       knot_points <= 64) — and for 64 < knot_points <= 512 its clustered form, G = ceil(N / 64) CUs per
- *       trajectory under the same "cluster" option and hand-off machinery; "pcg_lqk" = 0, a latch that says not symmetric or a capturing first
- *       call: the clustered row-per-lane kernel (32 < knot_points <= 256, G = ceil(N / 32) members, full block rows, all three block columns);
- *       "cluster" = 0 selects the streaming kernel, which is also the clusters' fix-up (up to 350 knots: beyond, its iterate vectors do not fit
- *       LDS and an abandoned trajectory is reported as with "cluster_fixup" = 0);
- *   otherwise (explicit pcg_* knobs, the fix-up launches, fp16 storage at N <= 36) the single-workgroup row-pair kernel: "pcg_waves" (4, 8 or 16
- *       wavefronts per trajectory workgroup), "pcg_reg_rows" (TRIPLES of block rows per matrix and wave kept in registers for the whole
- *       solve; only compiled (waves, rows) pairs are accepted at launch), "pcg_lds_rows" (triples per matrix and wave cached in LDS, -1 =
- *       what fits), "pcg_stream_bufs", "pcg_max_wg_per_cu", "lds_extra" (single-triple LDS slots beyond the uniform cache of the <.,.,1>
- *       kernels: -1 what fits, 0 none); "pcg16_*" = the same for fp16 storage.  Setting any pcg_* knob switches the automatic selection off.
+ * Kernel selection.  One row per branch of the launch plan (mpcg_pcg.hip: plan_f32, plan_f64; the measurements behind each row are there),
+ * tried top to bottom; "auto" = no pcg_* knob set (any pcg_* knob switches the automatic choices off), C = CUs of the device, B = the call's
+ * batch, family = "last_kernel_family".
+ *   float / fp16 storage (mpcg_pcg_solve, _ref, _f16):
+ *     state_size != 14                                                                   generic streaming kernel          3
+ *     fp32, N <= 64, "pcg_rpl" != 0, and "pcg_rpl" = 1 or (auto, "cluster" <= 0, "pcg_lpk" != 1, not the half build below, and
+ *       N <= 32 or B <= C with the lane-quad kernel not automatic)                         row-per-lane                      5
+ *     N <= 128, "pcg_lpk" != 0, and "pcg_lpk" = 1, or auto with "cluster" <= 0 and N > 36 (N > 32 where the lane-quad kernel is
+ *       automatic), or the half build: fp32, 16 < N <= 32, 2 B >= 5 C, auto, "pcg_rpl" != 1 — the lane-pair kernel      lane-pair         6
+ *       ... in its place, fp32, "pcg_lqb" = 1, or "pcg_lqb", "pcg_lpk", "pcg_rpl" all -1, auto, "cluster" <= 0        lane-quad         11
+ *     "cluster" = G, or auto with "cluster" = -1 and N > 128 (G = ceil(N / 128)); 2 <= G <= 8, G <= C, <= 128 knots per member
+ *                                                                                        clustered lane-pair               7
+ *     otherwise                                                                          row-pair (single workgroup)       0
+ *   the calls above with family 6, 7 or 11 read only the lower block triangle; while the handle does not know the caller's matrices to be
+ *   block-symmetric they run guarded, and once it knows they are not (BLOCK SYMMETRY):
+ *     fp32, N <= 64, "pcg_rpl" != 0                                                      row-per-lane                      5
+ *     otherwise                                                                          row-pair                          0
+ *   double (mpcg_pcg_solve_f64, _ref_f64):
+ *     N <= 64, "pcg_lqk" != 0, block-symmetric (the latch), and "pcg_lqk" = 1 or auto with "cluster" = -1 and N > 32 (or 16 < N and
+ *       B >= 4 C)                                                                          lane-quad (one CU)                9
+ *     N <= 32, "pcg_rpl" != 0, and "pcg_rpl" = 1 or auto                                 row-per-lane                      5
+ *     state_size != 14                                                                   generic streaming kernel          3
+ *     N > 32, "cluster" != 0, "pcg_lqk" != 0, block-symmetric, G = "cluster" or ceil(N / 64): 2 <= G <= 8, <= 64 knots per member
+ *                                                                                        clustered lane-quad               10
+ *     "cluster" != 0, G = "cluster" or ceil(N / 32): 2 <= G <= 8, <= 32 knots per member  clustered row-per-lane            8
+ *     otherwise (the iterate vectors in LDS: N <= 350; two block columns once the latch says block-symmetric)
+ *                                                                                        streaming                         3
+ *   Clustered kernels: G CUs of one XCD per trajectory; members exchange inner-product partials and boundary knots through the XCD's L2
+ *   ("cluster_l2" = 0: always write-through), so all members of a cluster must be resident: the launch holds as many clusters as fit the chip
+ *   and each draws trajectories from a queue (any batch = one launch).  A cluster that cannot make progress (a peer not resident: another
+ *   stream holds its CU) gives up after a bounded spin and a follow-up launch re-solves its trajectory — the lane-pair / lane-quad kernel up
+ *   to 128 knots, else the row-pair kernel (double: the streaming kernel) — warm-started from the handle's own copy of d_lambda made in front
+ *   of the cluster launch ("cluster_fixup" = 0, or a horizon the follow-up kernel cannot hold: no follow-up launch, d_iters = 0xFFFFFFFF and
+ *   d_max_iter_exit = 2 for such a trajectory; "cluster_test_fail" = 1, tests only: one member gives up at its first write-back).
+ *   Knobs of these rows: "rpl_waves" (row-per-lane wavefronts per trajectory: 0 auto, 4, 8, 16); the row-pair kernel's "pcg_waves" (4, 8 or
+ *   16 wavefronts per trajectory workgroup), "pcg_reg_rows" (TRIPLES of block rows per matrix and wave kept in registers for the whole
+ *   solve; only compiled (waves, rows) pairs are accepted at launch), "pcg_lds_rows" (triples per matrix and wave cached in LDS, -1 =
+ *   what fits), "pcg_stream_bufs", "pcg_max_wg_per_cu", "lds_extra" (single-triple LDS slots beyond the uniform cache of the <.,.,1>
+ *   kernels: -1 what fits, 0 none); "pcg16_*" = the same for fp16 storage.
+ *   The family depends on knot_points AND on the call's batch.  Families sum the inner products in different orders, so the SAME trajectory
+ *   solved alone and inside a large batch may differ in the last fp32 bits (and, near the tolerance, by an iteration); within one family
+ *   results are bitwise reproducible run to run and independent of batch composition.  Pin a family with "pcg_rpl" / "pcg_lpk" / "pcg_lqb" /
+ *   "rpl_waves" when bit-stability across batch sizes matters.  None of the residency knobs changes results within a lane-order family
+ *   (bitwise identical, tested).
  * "sched_hint" (0 / 1, default 1): an mpcg_pcg_solve call with more trajectories than CUs that runs a register-resident kernel dispatches its
  *       trajectories longest-expected-first, the expectation being the iteration counts the handle's previous call with the same batch size
  *       wrote to d_iters — warm-started solves leave the loop at very different iterations and the dispatch order decides how well the chip stays
@@ -371,13 +386,7 @@ int mpcg_qdldl_solve_schur(mpcg_handle *h, mpcg_ldl *l, const float *d_val, cons
  *       D2H read), "last_symmetry_violations", "num_cus", "pcg_resident" (1 if the single-workgroup configuration streams nothing inside the PCG
  *       loop), "last_schur_chunk" (block rows per chunk of the last mpcg_form_schur, 0 = the LDS kernels), "last_kernel_family" (kernel of the
  *       last solve: 0 single-workgroup row-pair, 3 generic, 5 row-per-lane, 6 lane-pair-per-knot, 7 clustered lane-pair, 8 clustered row-per-lane
- *       (double), 9 lane-quad-per-knot (double), 10 clustered lane-quad (double), 11 lane-quad-per-knot with both matrices per wavefront (float, round 6); 1, 2, 4 were kernels retired in round 4), "last_kernel_{waves,reg_rows,lds_rows,lds_extra,stream_bufs,cluster,lds_bytes}".
- * WHICH kernel family serves a call depends on knot_points AND, up to 32 knots, on the call's batch (N <= 32: row-per-lane kernel, 8 waves x 1 slot or 4 x 2 by batch; 16 < N <= 32:
- * the lane-quad kernel from 2.5 trajectories per CU; 32 < N <= 128: one kernel at every batch since round 6).  Families sum the inner products in different
- * orders, so the SAME trajectory solved alone and inside a large batch may differ in the last fp32 bits (and, near the tolerance, by an
- * iteration); within one family results are bitwise reproducible run to run and independent of batch composition.  Pin a family with
- * "pcg_rpl" / "pcg_lpk" / "pcg_lqb" / "rpl_waves" when bit-stability across batch sizes matters.  None of the residency knobs changes results within a
- * lane-order family (bitwise identical, tested). */
+ *       (double), 9 lane-quad-per-knot (double), 10 clustered lane-quad (double), 11 lane-quad-per-knot with both matrices per wavefront (float, round 6); 1, 2, 4 were kernels retired in round 4), "last_kernel_{waves,reg_rows,lds_rows,lds_extra,stream_bufs,cluster,lds_bytes}". */
 int mpcg_set_option(mpcg_handle *h, const char *key, int value);
 int mpcg_get_option(const mpcg_handle *h, const char *key, int *value);
 

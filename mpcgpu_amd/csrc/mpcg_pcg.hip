@@ -11,6 +11,8 @@
 #include "pcg_lqk_cluster_f64.hip.h"
 #include "pcg_f64.hip.h"
 
+#include <type_traits>
+
 using namespace mpcg;
 
 thread_local std::string mpcg_create_err;
@@ -63,7 +65,6 @@ static int stream_bufs_for(const mpcg_handle* h, const PcgKnobs& k, int nw, int 
 static void choose_auto(const mpcg_handle* h, PcgKnobs& k, uint32_t batch, int esz);
 static constexpr uint32_t kLqkMaxN = 64;      // linsys_t = double: knots one CU holds as lane quads (pcg_lqk_f64.hip.h)
 static constexpr uint32_t kCluster64MaxN = 64 * LQKC_MAX_G;      // linsys_t = double: the longest horizon a cluster kernel holds (eight members of 64 knots)
-static size_t default_launch_lds_bytes(uint32_t N, int num_cus);
 
 extern "C" {
 
@@ -125,7 +126,10 @@ static int launch_cluster_report(mpcg_handle* h, const unsigned long long* flags
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
-static size_t cluster64_alloc_words(const mpcg_handle* h);
+// the double cluster kernels' scratch: queue + flags + cells
+static size_t cluster64_alloc_words(const mpcg_handle* h) {
+    return CL_FLAG_STRIDE + (size_t)h->max_batch * CL_FLAG_STRIDE + (size_t)h->num_cus * RPLC_WG_WORDS + 16;
+}
 static constexpr size_t kEagerF64Bytes = (size_t)8 << 20;
 // the double cluster kernels' buffers: queue + flags + cells, and the double-sized copy of lambda0 their fix-up launch starts from.  Blocking
 // (hipMalloc): mpcg_create for small handles, "reserve_f64" = 1, or the first double cluster solve outside a capture.
@@ -147,22 +151,6 @@ static int reserve_f64(mpcg_handle* h) {
         h->lam_backup_bytes = bytes;
     }
     return MPCG_OK;
-}
-
-size_t mpcg_pcg_lds_bytes(uint32_t state_size, uint32_t knot_points) {
-    if (generic_shape_supported(state_size, knot_points)) return pcg_generic_lds_elems((int)knot_points, (int)state_size) * sizeof(float);
-    if (!shape_supported(state_size, knot_points)) return 0;
-    if (knot_points > kLpbMaxN && lds_bytes_for(knot_points, 16) > kLdsMax) return 0;
-    return default_launch_lds_bytes(knot_points, 256);
-}
-
-size_t mpcg_pcg_lds_bytes_f64(uint32_t state_size, uint32_t knot_points) {
-    if (!shape_supported(state_size, knot_points) && !generic_shape_supported(state_size, knot_points)) return 0;
-    if (state_size == NS && knot_points <= 32) return pcg_rpl_lds_floats((int)knot_points, knot_points <= 16 ? 4 : 8) * sizeof(double);   // row-per-lane kernel
-    if (state_size == NS && knot_points <= kLqkMaxN) return pcg_lqk_lds_doubles(8) * sizeof(double);                                   // lane-quad kernel (block-symmetric matrices: the reference's)
-    if (state_size == NS && knot_points <= kCluster64MaxN) return pcg_lqkc_lds_doubles() * sizeof(double);                             // a member of the clustered lane-quad kernel
-    const size_t b = pcg_generic_lds_elems((int)knot_points, (int)state_size) * sizeof(double);
-    return b <= kLdsMax ? b : 0;
 }
 
 int mpcg_create(mpcg_handle** out, int device, uint32_t state_size, uint32_t knot_points, uint32_t max_batch) {
@@ -455,33 +443,6 @@ static TrajLds traj_lds(const mpcg_handle* h, const PcgKnobs& k, int nw, int sb,
     return t;
 }
 
-template <int NW, int RT, int SB, typename MT>
-static int launch_pcg_t(mpcg_handle* h, const PcgKnobs& k, PcgArgs a, uint32_t batch, hipStream_t st, bool record) {
-    const TrajLds t = traj_lds(h, k, NW, SB, (int)sizeof(MT));
-    a.lds_rows = t.lt; a.lds_extra_s = t.extra_s; a.lds_extra_p = t.extra_p;
-    if (t.bytes > kLdsMax) return fail(h, MPCG_ERR_INVALID, "pcg_lds_rows does not fit 160 KiB of LDS");
-    auto kern = pcg_traj_kernel<NW, RT, SB, MT>;
-    if (t.bytes > 48 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.bytes));
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(NW * 64), t.bytes, st, a);
-    HIP_TRY(h, hipGetLastError());
-    if (record) h->last = LastKernel{FAM_TRAJ, NW, RT, t.lt, SB, 0, (int)t.bytes, t.extra_s + t.extra_p};
-    return MPCG_OK;
-}
-
-template <int NW, int RT, int SB, typename MT>
-static int occupancy_t(mpcg_handle* h, const PcgKnobs& k, int* blocks_per_cu) {
-    const TrajLds t = traj_lds(h, k, NW, SB, (int)sizeof(MT));
-    if (t.bytes > kLdsMax) return fail(h, MPCG_ERR_INVALID, "pcg_lds_rows does not fit 160 KiB of LDS");
-    auto kern = pcg_traj_kernel<NW, RT, SB, MT>;
-    if (t.bytes > 48 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.bytes));
-    HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, kern, NW * 64, t.bytes));
-    return MPCG_OK;
-}
-
 // Compiled (waves, register triples, stream buffers) variants.  X(NW, RT, SB)
 #define MPCG_PCG_VARIANTS(X)                                                              \
     X(16, 0, 2) X(8, 0, 2) X(4, 0, 2)                                                     \
@@ -502,6 +463,23 @@ static int stream_bufs_for(const mpcg_handle* h, const PcgKnobs& k, int nw, int 
     const bool all_resident = TT <= rt + lds_rows_for(h, k, nw, esz);
     if (k.stream_bufs >= 0) return (k.stream_bufs == 0 && !all_resident) ? 1 : k.stream_bufs;
     return all_resident ? 0 : -1;       // -1: any compiled SB > 0 (1 preferred)
+}
+
+// The compiled pcg_traj_kernel<waves, rt, SB> for the stream buffers `sb` asks (stream_bufs_for): the exact build, then a streaming one.
+// nullptr: none compiled.
+static const void* traj_variant(int waves, int rt, int sb, int esz, int* sb_out) {
+    for (int want : {sb, sb == 0 ? 1 : -2, sb <= 0 ? 2 : -2}) {
+        if (want == -2) continue;
+#define X(NW_, RT_, SB_)                                                                                   \
+        if (waves == NW_ && rt == RT_ && (want == SB_ || (want == -1 && SB_ > 0))) {                       \
+            *sb_out = SB_;                                                                                 \
+            return reinterpret_cast<const void*>(pcg_traj_kernel<NW_, RT_, SB_, MT>);                      \
+        }
+        if (esz == 4) { using MT = float; MPCG_PCG_VARIANTS(X) }
+        else { using MT = _Float16; MPCG_PCG_VARIANTS16(X) }
+#undef X
+    }
+    return nullptr;
 }
 
 // Automatic per-call configuration of the single-workgroup kernels (round-1 sweeps on MI355X: profiles/r01_tune11.txt,
@@ -533,30 +511,6 @@ static void choose_auto(const mpcg_handle* h, PcgKnobs& k, uint32_t batch, int e
     }
 }
 
-// ---- lane-pair-per-knot kernel (pcg_lpk.hip.h): everything register-resident, N <= 128 ----
-template <int NWR>
-static int launch_lpk_t(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st) {
-    const size_t lds = pcg_lpk_lds_floats(LpkLds<NWR>::NW) * sizeof(float);
-    auto kern = pcg_lpk_kernel<NWR>;
-    if (lds > 48 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(LpkLds<NWR>::NW * 64), lds, st, a);
-    HIP_TRY(h, hipGetLastError());
-    h->last = LastKernel{FAM_LPK, LpkLds<NWR>::NW, 0, 0, 0, 0, (int)lds, 0};
-    return MPCG_OK;
-}
-// ---- lane-quad-per-knot kernel, both matrices in every wavefront (pcg_lqb.hip.h): the lane-pair kernel's contract, two working wavefronts per SIMD ----
-template <int NMAXQ>
-static int launch_lqb_t(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st) {
-    const size_t lds = pcg_lqb_lds_floats(NMAXQ) * sizeof(float);
-    void (*kern)(PcgArgs) = a.pcols == 3 ? pcg_lqb_kernel<NMAXQ, true> : pcg_lqb_kernel<NMAXQ, false>;      // (SS / block-Jacobi builds)
-    if (lds > 48 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(NMAXQ * 4), lds, st, a);
-    HIP_TRY(h, hipGetLastError());
-    h->last = LastKernel{FAM_LQB, NMAXQ / 16, 0, 0, 0, 0, (int)lds, 0};
-    return MPCG_OK;
-}
 // The float lane-quad kernel takes the lane-pair kernel's launches (same contract: lower block triangle, gated / fix-up launches, dispatch order).
 // Automatic use ("pcg_lqb" = 1 / 0 forces / forbids, an explicit "pcg_lpk" = 1 keeps the lane-pair kernel; steady clocks, tools/_prof/lqb_ab.py,
 // lqb_n32.py, lqb_n32_forced.py; the first sweep: profiles/r06_lqb_policy.txt): WHEREVER the lane-pair kernel ran in fp32, both preconditioners
@@ -569,18 +523,10 @@ static int launch_lqb_t(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStr
 static bool lqb_auto(const mpcg_handle* h, int esz) { return esz == 4 && h->lqb == -1 && h->lpk == -1 && h->rpl != 1 && h->auto_cfg && h->cluster <= 0; }
 static bool use_lqb(const mpcg_handle* h, int esz) {
     if (esz != 4 || h->lqb == 0) return false;
-    return h->lqb == 1 || lqb_auto(h, esz);
+    return h->lqb == 1 || lqb_auto(h, esz);       // (quirk: "pcg_lqb" = 1 reaches only calls the lane-pair kernel takes without it: 36 < N, not 32 < N)
 }
-static int launch_lpk(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st) {
-    if (use_lqb(h, a.esz)) {
-        if (h->N <= 32) return launch_lqb_t<32>(h, a, batch, st);
-        return h->N <= 64 ? launch_lqb_t<64>(h, a, batch, st) : launch_lqb_t<128>(h, a, batch, st);
-    }
-    if (h->N <= 32) return launch_lpk_t<0>(h, a, batch, st);          // the half build: one wavefront per matrix, four workgroups per CU
-    return h->N <= 64 ? launch_lpk_t<1>(h, a, batch, st) : launch_lpk_t<2>(h, a, batch, st);
-}
-// Automatic use: 36 < N <= 128 (where the row-per-lane kernel has not taken the call).  Its per-lane work does not shrink with the horizon
-// (a lane pair per knot whatever N), so up to N = 36 — where the row-pair kernel <4,3,0> fits two trajectories per CU — that one stays
+// Lane-pair kernel, automatic use: 36 < N <= 128 (where the row-per-lane kernel has not taken the call).  Its per-lane work does not shrink with the
+// horizon (a lane pair per knot whatever N), so up to N = 36 — where the row-pair kernel <4,3,0> fits two trajectories per CU — that one stays
 // ahead in throughput (N=36: 292 vs 222 M it/s at batch 2048); beyond it the order flips (HISTORY.md §3.1c).
 // ... and, round 5, 16 < N <= 32 for calls of at least 2.5 trajectories per CU: the HALF build (one wavefront per matrix, 32 knots, four workgroups
 // per CU) takes 1.45-1.55 us per iteration for up to four trajectories per CU, the row-per-lane kernel 1.26 us for two, 2.1 for three, 2.5-2.7 for
@@ -590,44 +536,13 @@ static bool lpk_half(const mpcg_handle* h, int esz, uint32_t batch) {
 }
 static bool use_lpk(const mpcg_handle* h, int esz, uint32_t batch) {
     if ((esz != 4 && esz != 2) || h->N > kLpbMaxN || h->lpk == 0) return false;     // (fp16 storage: converted once at the load)
-    // (with the lane-quad kernel behind launch_lpk: from 33 knots, at every batch — it beats the row-pair kernel at 33..36 and the row-per-lane kernel's
-    //  latency-sized calls up to 64, use_lqb)
+    // (with the lane-quad kernel behind the lane-pair kernel's launches: from 33 knots, at every batch — it beats the row-pair kernel at 33..36 and
+    //  the row-per-lane kernel's latency-sized calls up to 64, use_lqb)
     return h->lpk == 1 || (h->auto_cfg && h->cluster <= 0 && h->N > (lqb_auto(h, esz) ? 32u : 36u)) || lpk_half(h, esz, batch);
 }
-
-// ---- row-per-lane kernel (pcg_rpl.hip.h): short horizons, NW wavefronts x RHO slots of four knots ----
-#define MPCG_RPL_VARIANTS(X) X(4, 1) X(4, 2) X(8, 1) X(8, 2) X(16, 1)
-template <int NW, int RHO, bool PC3>
-static int launch_rpl_t(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st) {
-    const size_t lds = pcg_rpl_lds_floats((int)h->N, NW) * sizeof(float);
-    hipLaunchKernelGGL((pcg_rpl_kernel<NW, RHO, PC3>), dim3(batch), dim3(NW * 64), lds, st, a);
-    HIP_TRY(h, hipGetLastError());
-    h->last = LastKernel{FAM_RPL, NW, RHO, 0, 0, 0, (int)lds, 0};
-    return MPCG_OK;
-}
-// (NW, RHO) of a call: NW RHO slots of four knots must cover the horizon.  Automatic (profiles/r02_rpl_quick.txt): N <= 16 four
-// wavefronts; N <= 32 eight wavefronts x one slot for a latency-sized call (at most one trajectory per CU), four x two slots for
-// throughput (N=32 SS 395 vs 376 M it/s, block-Jacobi 623 vs 484 M); N <= 64 eight x two.
-static void rpl_shape(const mpcg_handle* h, uint32_t batch, int* nw, int* rho) {
-    const int slots = ((int)h->N + 3) / 4;
-    int w = h->rpl_waves;
-    if (w == 0) w = slots <= 4 ? 4 : slots <= 8 ? (batch > (uint32_t)h->num_cus ? 4 : 8) : 8;
-    *nw = w;
-    *rho = (slots + w - 1) / w;
-}
-static int launch_rpl(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st) {
-    int nw, rho;
-    rpl_shape(h, batch, &nw, &rho);
-#define X(NW_, RHO_)                                                                                   \
-    if (nw == NW_ && rho == RHO_)                                                                      \
-        return a.pcols == 3 ? launch_rpl_t<NW_, RHO_, true>(h, a, batch, st) : launch_rpl_t<NW_, RHO_, false>(h, a, batch, st);
-    MPCG_RPL_VARIANTS(X)
-#undef X
-    return fail(h, MPCG_ERR_UNSUPPORTED, "row-per-lane kernel: no compiled (waves, slots) variant covers this horizon with rpl_waves");
-}
-// Automatic use (no explicit pcg_* knob): N <= 32 always (N=32: 0.150 vs 0.247 ms for one trajectory, 395 vs 277 M it/s at batch 2048;
-// N=16: 875 vs 317 M); 32 < N <= 64 for latency-sized calls only (N=64 one trajectory 0.248 vs 0.341 ms, but 170 vs 211 M it/s at
-// batch 2048, where the lane-pair / row-pair kernels stay ahead).
+// Row-per-lane kernel (pcg_rpl.hip.h), automatic use (no explicit pcg_* knob): N <= 32 always (N=32: 0.150 vs 0.247 ms for one trajectory, 395 vs
+// 277 M it/s at batch 2048; N=16: 875 vs 317 M); 32 < N <= 64 for latency-sized calls only (N=64 one trajectory 0.248 vs 0.341 ms, but 170 vs
+// 211 M it/s at batch 2048, where the lane-pair / row-pair kernels stay ahead).
 static bool use_rpl(const mpcg_handle* h, int esz, uint32_t batch) {
     if (esz != 4 || h->N > kRplMaxN || h->rpl == 0) return false;
     if (h->rpl == 1) return true;
@@ -636,118 +551,280 @@ static bool use_rpl(const mpcg_handle* h, int esz, uint32_t batch) {
     return h->auto_cfg && h->cluster <= 0 && (h->N <= 32 || (batch <= (uint32_t)h->num_cus && !lqb_auto(h, esz)));
 }
 
-static int launch_traj(mpcg_handle* h, const PcgKnobs& k, const PcgArgs& a, uint32_t batch, hipStream_t st, int esz, bool record);
-
-// ---- clustered lane-pair kernel (pcg_lpk_cluster.hip.h): G members x up to 128 knots, all blocks in registers ----
-// Members must be co-resident, which a plain launch cannot guarantee when another stream holds CUs: a member that waits longer than the
-// bounded spin gives up; every member that FINISHES a trajectory counts itself in that trajectory's flag, and the launch is followed by a
-// launch of a single-workgroup kernel in which only the trajectories whose count is not G run — the caller always gets a solved system.
-static int lpkc_members(const mpcg_handle* h) {
-    const int nmax = 128;
+// Members of a cluster: "cluster" = G forced, else ceil(N / nmax); 0 when the kernel cannot take the call (at most max_g members of at most
+// nmax knots, no more members than CUs or knots).
+static int cluster_members(const mpcg_handle* h, int nmax, int max_g) {
     const int G = h->cluster > 0 ? h->cluster : ((int)h->N + nmax - 1) / nmax;
-    if (G < 2 || G > LPBC_MAX_G || G > h->num_cus || G > (int)h->N) return 0;
+    if (G < 2 || G > max_g || G > h->num_cus || G > (int)h->N) return 0;
     if (((int)h->N + G - 1) / G > nmax) return 0;        // the largest member: ceil(N / G) knots
     return G;
 }
 // clusters the chip holds: the kernel pins cluster cl to XCD cl % 8 (all its members on one XCD, 32 CUs each), so residency is a
 // per-XCD count — 8 x floor(CUs of one XCD / G).  (Sized chip-wide, G = 3, 5, 6, 7 over-subscribed some XCDs by a member that could
 // not start while the persistent clusters held the CUs: its peers spun to the limit and the trajectories fell to the fix-up launch.)
-static uint32_t lpkc_resident_clusters(const mpcg_handle* h, int G) {
+static uint32_t cluster_resident(const mpcg_handle* h, int G) {
     const int xcd_slots = h->num_cus / 8;
     return h->num_cus >= 8 && xcd_slots >= G ? (uint32_t)(8 * (xcd_slots / G)) : (uint32_t)(h->num_cus / G);
 }
-// returns 1 when it does not apply.  One persistent launch for any batch: clusters draw trajectories from a queue.
-// scratch: [queue: one 128-byte line][flags: one line per trajectory of the call][cells: 1 KB per member of the launch] — what a call uses
-// is contiguous, so one small fill precedes every launch
-static int try_launch_cluster(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st, int esz, bool guarded = false) {
-    if (h->cluster == 0 || (esz != 4 && esz != 2)) return 1;
-    if (h->cluster < 0 && (!h->auto_cfg || h->N <= kLpbMaxN)) return 1;     // explicit pcg_* knobs, or a horizon one CU holds
-    constexpr int NWR = 2;
-    const int G = lpkc_members(h);
-    if (G == 0) return 1;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "batch exceeds max_batch");
-    const uint32_t resident = lpkc_resident_clusters(h, G);
-    const uint32_t clusters = batch < resident ? batch : resident;
-    const size_t lds = pcg_lpkc_lds_floats(4 * NWR) * sizeof(float);
-    void (*kern)(ClusterArgs) = pcg_lpkc_kernel<NWR>;
-    if (lds > 48 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PcgKnobs kf = h->k;
-    choose_auto(h, kf, 1, esz);
-    const bool fixup = h->cluster_fixup && (h->N <= kLpbMaxN || lds_bytes_for(h->N, kf.waves) <= kLdsMax);
-    ClusterArgs ca;
-    ca.kl_max = 64 * NWR;
-    ca.p = a;
-    ca.queue = h->cluster_scratch;
-    ca.fail_flags = ca.queue + CL_FLAG_STRIDE;
-    ca.scratch = ca.fail_flags + (size_t)batch * CL_FLAG_STRIDE;
-    ca.G = G;
-    ca.batch = (int)batch;
-    ca.clusters = (int)clusters;
-    ca.l2_handoff = h->cluster_l2;
-    ca.test_fail = h->cluster_test_fail;
-    // one launch in front: the queue counter, this call's flags and the cells of this launch zeroed (their tags restart at 1 every launch) and,
-    // when a fix-up launch follows, lambda0 copied for it
-    const size_t zw = CL_FLAG_STRIDE + (size_t)batch * CL_FLAG_STRIDE + (size_t)clusters * G * LPBC_WG_WORDS;
-    if (fixup) {
-        const int rc = launch_cluster_prologue(h, h->cluster_scratch, zw, a.lambda, (size_t)batch * h->N * NS * sizeof(float), st);
-        if (rc != MPCG_OK) return rc;
-    } else {
-        hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((zw + 255) / 256)), dim3(256), 0, st, h->cluster_scratch, zw);
-        HIP_TRY(h, hipGetLastError());
-    }
-    hipLaunchKernelGGL(kern, dim3(((clusters + 7) / 8) * 8 * (unsigned)G), dim3(NWR * 256), lds, st, ca);
-    HIP_TRY(h, hipGetLastError());
-    if (fixup) {
-        PcgArgs c = a;
-        c.redo_flags = ca.fail_flags;
-        c.redo_stride = CL_FLAG_STRIDE;
-        c.redo_skip = (unsigned)G;
-        // a GUARDED call (launch_guarded: the handle does not know yet whether the caller's matrices are block-symmetric) relies on this fix-up
-        // being a three-column kernel — every completion count is 0 after a gated exit — so it is never the lower-triangle lane-pair kernel
-        // then (a forced "cluster" = G at N <= 128), and gated exits are not counted as abandoned trajectories
-        c.redo_count = guarded ? nullptr : fixup_counter(h);
-        c.lam0 = static_cast<const float*>(h->lam_backup);     // (members that finished a trajectory their cluster did not have written their knots of lambda)
-        const int rc = h->N <= kLpbMaxN && !guarded ? launch_lpk(h, c, batch, st) : launch_traj(h, kf, c, batch, st, esz, /*record=*/false);
-        if (rc != MPCG_OK) return rc;
-    } else {
-        const int rc = launch_cluster_report(h, ca.fail_flags, G, batch, a.iters, a.max_iter_exit, st);
-        if (rc != MPCG_OK) return rc;
-    }
-    h->last = LastKernel{FAM_LPKC, 4 * NWR, 0, 0, 0, G, (int)lds, 0};
-    return MPCG_OK;
+
+// ---- the launch plan ------------------------------------------------------------------------------
+// Which kernel serves a call is decided here and nowhere else (include/mpcg.h, Options: one row of its kernel-selection table per branch of
+// plan_f32 / plan_f64).  Pure host code — no HIP call, no change to the handle — so mpcg_pcg_lds_bytes(_f64) plan on a handle of the stack
+// without a GPU.  The launch paths, mpcg_check_pcg_occupancy and the dispatch-order hint all read the plan.
+
+// One kernel launch (grid 0: one workgroup per trajectory), or why there is none (rc != MPCG_OK: the call fails with err where it would launch)
+struct Launch {
+    const void* kern = nullptr;
+    unsigned grid = 0, block = 0;
+    size_t lds = 0;
+    int lds_rows = 0, extra_s = 0, extra_p = 0;     // pcg_traj_kernel: its LDS layout (PcgArgs::lds_rows, lds_extra_s, lds_extra_p)
+    int rc = MPCG_OK;
+    const char* err = nullptr;
+};
+struct PcgPlan {
+    Launch k;
+    LastKernel last;            // what "last_kernel_*" reports after the call
+    bool lower = false;         // reads only the lower block triangle: the latch (float: its own predicate, see plan_f32) / guard applies
+    bool check = false;         // float: "check_symmetry" verifies this call first (its own predicate, see plan_f32)
+    bool order = false;         // a call with more trajectories than CUs is followed by the dispatch-order kernel (sched_order_kernel)
+    // clustered kernels (G > 0): the persistent launch holds min(batch, resident) clusters
+    int G = 0;
+    uint32_t resident = 0;
+    int member_words = 0;       // hand-off cells per member (u64 words)
+    int lam_esz = 0;            // element size of lambda (4: float, the float scratch; 8: double, the double kernels' scratch)
+    bool fixup = false;         // trajectories whose cluster gave up are re-solved by `fix` (gated on the completion counts), else reported
+    Launch fix;
+    int fix_lower = 0;          // double: PcgArgs64::lower of the fix-up (the streaming kernel)
+};
+enum Cols { LOWER, GATED, FULL, FALLBACK };   // a lower-triangle kernel allowed / allowed but gated by the guard / three columns / the guard's fallback
+
+static Launch unsupported(int rc, const char* err) { Launch L; L.rc = rc; L.err = err; return L; }
+template <typename K>
+static Launch make_launch(K* kern, unsigned block, size_t lds, unsigned grid = 0) {
+    Launch L;
+    L.kern = reinterpret_cast<const void*>(kern); L.grid = grid; L.block = block; L.lds = lds;
+    return L;
 }
 
-static int launch_traj(mpcg_handle* h, const PcgKnobs& k, const PcgArgs& a, uint32_t batch, hipStream_t st, int esz, bool record) {
+static Launch plan_traj(const mpcg_handle* h, const PcgKnobs& k, int esz, LastKernel* last) {
     const int waves = esz == 2 ? k.waves16 : k.waves;
     const int rt = esz == 2 ? k.reg_rows16 : k.reg_rows;
-    const int sb = stream_bufs_for(h, k, waves, esz);
-    for (int want : {sb, sb == 0 ? 1 : -2, sb <= 0 ? 2 : -2}) {     // exact, then fall back to a streaming build
-        if (want == -2) continue;
-        if (esz == 4) {
-#define X(NW_, RT_, SB_)                                                                       \
-            if (waves == NW_ && rt == RT_ && (want == SB_ || (want == -1 && SB_ > 0)))             \
-                return launch_pcg_t<NW_, RT_, SB_, float>(h, k, a, batch, st, record);
-            MPCG_PCG_VARIANTS(X)
+    int sb = 0;
+    const void* kern = traj_variant(waves, rt, stream_bufs_for(h, k, waves, esz), esz, &sb);
+    if (!kern) return unsupported(MPCG_ERR_UNSUPPORTED, "no compiled kernel variant for this (pcg_waves, pcg_reg_rows, pcg_stream_bufs)");
+    const TrajLds t = traj_lds(h, k, waves, sb, esz);
+    Launch L;
+    L.kern = kern; L.block = waves * 64; L.lds = t.bytes;
+    L.lds_rows = t.lt; L.extra_s = t.extra_s; L.extra_p = t.extra_p;
+    if (t.bytes > kLdsMax) { L.rc = MPCG_ERR_INVALID; L.err = "pcg_lds_rows does not fit 160 KiB of LDS"; }
+    *last = LastKernel{FAM_TRAJ, waves, rt, t.lt, sb, 0, (int)t.bytes, t.extra_s + t.extra_p};
+    return L;
+}
+// (NW, RHO) of a row-per-lane call: NW RHO slots of four knots must cover the horizon.  Automatic (profiles/r02_rpl_quick.txt): N <= 16 four
+// wavefronts; N <= 32 eight wavefronts x one slot for a latency-sized call (at most one trajectory per CU), four x two slots for
+// throughput (N=32 SS 395 vs 376 M it/s, block-Jacobi 623 vs 484 M); N <= 64 eight x two.
+#define MPCG_RPL_VARIANTS(X) X(4, 1) X(4, 2) X(8, 1) X(8, 2) X(16, 1)
+static Launch plan_rpl(const mpcg_handle* h, uint32_t batch, int pcols, LastKernel* last) {
+    const int slots = ((int)h->N + 3) / 4;
+    int nw = h->rpl_waves;
+    if (nw == 0) nw = slots <= 4 ? 4 : slots <= 8 ? (batch > (uint32_t)h->num_cus ? 4 : 8) : 8;
+    const int rho = (slots + nw - 1) / nw;
+    const size_t lds = pcg_rpl_lds_floats((int)h->N, nw) * sizeof(float);
+    *last = LastKernel{FAM_RPL, nw, rho, 0, 0, 0, (int)lds, 0};
+#define X(NW_, RHO_) \
+    if (nw == NW_ && rho == RHO_) return make_launch(pcols == 3 ? pcg_rpl_kernel<NW_, RHO_, true> : pcg_rpl_kernel<NW_, RHO_, false>, NW_ * 64, lds);
+    MPCG_RPL_VARIANTS(X)
 #undef X
-        } else {
-#define X(NW_, RT_, SB_)                                                                       \
-            if (waves == NW_ && rt == RT_ && (want == SB_ || (want == -1 && SB_ > 0)))             \
-                return launch_pcg_t<NW_, RT_, SB_, _Float16>(h, k, a, batch, st, record);
-            MPCG_PCG_VARIANTS16(X)
-#undef X
-        }
+    return unsupported(MPCG_ERR_UNSUPPORTED, "row-per-lane kernel: no compiled (waves, slots) variant covers this horizon with rpl_waves");
+}
+// lane-pair kernel (pcg_lpk.hip.h; N <= 32: the half build, one wavefront per matrix, four workgroups per CU), or the lane-quad kernel in its place
+static Launch plan_lpk(const mpcg_handle* h, int esz, int pcols, LastKernel* last) {
+    if (use_lqb(h, esz)) {
+        const int nq = h->N <= 32 ? 32 : h->N <= 64 ? 64 : 128;
+        const size_t lds = pcg_lqb_lds_floats(nq) * sizeof(float);
+        *last = LastKernel{FAM_LQB, nq / 16, 0, 0, 0, 0, (int)lds, 0};
+        const bool pc3 = pcols == 3;         // (SS / block-Jacobi builds)
+        if (nq == 32) return make_launch(pc3 ? pcg_lqb_kernel<32, true> : pcg_lqb_kernel<32, false>, 128, lds);
+        if (nq == 64) return make_launch(pc3 ? pcg_lqb_kernel<64, true> : pcg_lqb_kernel<64, false>, 256, lds);
+        return make_launch(pc3 ? pcg_lqb_kernel<128, true> : pcg_lqb_kernel<128, false>, 512, lds);
     }
-    return fail(h, MPCG_ERR_UNSUPPORTED, "no compiled kernel variant for this (pcg_waves, pcg_reg_rows, pcg_stream_bufs)");
+    const int nw = h->N <= 32 ? LpkLds<0>::NW : h->N <= 64 ? LpkLds<1>::NW : LpkLds<2>::NW;
+    const size_t lds = pcg_lpk_lds_floats(nw) * sizeof(float);
+    *last = LastKernel{FAM_LPK, nw, 0, 0, 0, 0, (int)lds, 0};
+    return make_launch(h->N <= 32 ? pcg_lpk_kernel<0> : h->N <= 64 ? pcg_lpk_kernel<1> : pcg_lpk_kernel<2>, nw * 64, lds);
+}
+// the generic streaming kernel (pcg_f64.hip.h): state_size != 14 (NFIX = 0) in float and double; the double path's streaming kernel (NFIX = 14)
+template <typename T, int NFIX>
+static Launch plan_generic(const mpcg_handle* h, LastKernel* last) {
+    const size_t lds = pcg_generic_lds_elems((int)h->N, (int)h->n) * sizeof(T);
+    const int nthr = pcg_generic_threads((int)h->N, (int)h->n);
+    *last = LastKernel{FAM_GENERIC, nthr / 64, 0, 0, 2, 0, (int)lds, 0};
+    if (lds > kLdsMax) return unsupported(MPCG_ERR_UNSUPPORTED, "generic / double-precision kernel: the iterate vectors do not fit 160 KiB of LDS");
+    return make_launch(nthr == F64_THREADS_WIDE ? pcg_generic_kernel<T, NFIX, F64_THREADS_WIDE> : pcg_generic_kernel<T, NFIX, F64_THREADS>, nthr, lds);
 }
 
-// Kernel selection of one solve:
-//   1. row-per-lane kernel: fp32, N <= 32 (N <= 64 for latency-sized calls), automatic configuration (or "pcg_rpl" = 1);
-//   2. lane-pair kernel: fp32, 36 < N <= 128, automatic configuration (or "pcg_lpk" = 1);
-//   3. clustered lane-pair kernel: forced ("cluster" = G), or automatic configuration and a horizon one CU cannot hold;
-//   4. single-workgroup kernel <waves, reg_rows, stream_bufs> — the handle's knobs, adjusted per call by the
-//      automatic policy unless the caller set any pcg_* knob.
-static int launch_generic_f32(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st);
+// float / fp16 storage.  In order: the generic kernel (state_size != 14); the row-per-lane kernel (use_rpl); the lane-pair / lane-quad kernel
+// (use_lpk); the clustered lane-pair kernel ("cluster" = G forced, or automatic knobs and a horizon one CU cannot hold); pcg_traj_kernel with the
+// handle's knobs, chosen per call (choose_auto) unless the caller set a pcg_* knob.  Three columns (a call whose matrices are not known to be
+// block-symmetric): the row-per-lane kernel up to 64 knots, else pcg_traj_kernel.
+static PcgPlan plan_f32(const mpcg_handle* h, uint32_t batch, int esz, int pcols, Cols cols) {
+    PcgPlan p;
+    const uint32_t N = h->N;
+    if (h->generic) { p.k = plan_generic<float, 0>(h, &p.last); return p; }     // (fp16 storage: refused by mpcg_pcg_solve_f16)
+    PcgKnobs k = h->k;
+    if (cols == FULL || cols == FALLBACK) {
+        if (esz == 4 && N <= kRplMaxN && h->rpl != 0) { p.k = plan_rpl(h, batch, pcols, &p.last); p.order = true; return p; }   // full block rows in registers
+        if (h->auto_cfg || cols == FALLBACK) choose_auto(h, k, batch, esz);   // (quirk: the guard's fallback picks its knobs even under explicit pcg_* knobs)
+        p.k = plan_traj(h, k, esz, &p.last);
+        return p;
+    }
+    if (use_rpl(h, esz, batch)) { p.k = plan_rpl(h, batch, pcols, &p.last); p.order = true; return p; }      // (an explicit "pcg_lpk" = 1 wins over the automatic choice of this one)
+    // the kernels below read only the left + diagonal block columns (mpcg.h "Block symmetry"): the predicates of the check and of the latch
+    p.check = use_lpk(h, esz, batch) || (h->cluster != 0 && (h->cluster > 0 || N > kLpbMaxN));                // (quirk: without the auto_cfg test of `lower`)
+    p.lower = use_lpk(h, esz, batch) || (h->cluster != 0 && (h->cluster > 0 || (h->auto_cfg && N > kLpbMaxN)));   // (quirk: also when cluster_members refuses G)
+    if (use_lpk(h, esz, batch)) { p.k = plan_lpk(h, esz, pcols, &p.last); p.order = true; return p; }
+    p.G = h->cluster == 0 || (h->cluster < 0 && (!h->auto_cfg || N <= kLpbMaxN)) ? 0 : cluster_members(h, 128, LPBC_MAX_G);
+    if (p.G) {
+        // G CUs per trajectory, 128 knots per member in registers (pcg_lpk_cluster.hip.h); the fix-up: the lane-pair kernel's launch up to
+        // 128 knots — a GATED call's fix-up must read all three columns (every completion count is 0 after a gated exit: ADVICE r04) — else
+        // pcg_traj_kernel with the knobs of a batch-1 call (quirk: whatever the call's batch and auto_cfg)
+        p.resident = cluster_resident(h, p.G);
+        p.member_words = LPBC_WG_WORDS; p.lam_esz = sizeof(float);
+        p.k = make_launch(pcg_lpkc_kernel<2>, 512, pcg_lpkc_lds_floats(8) * sizeof(float));
+        p.last = LastKernel{FAM_LPKC, 8, 0, 0, 0, p.G, (int)p.k.lds, 0};
+        PcgKnobs kf = h->k;
+        choose_auto(h, kf, 1, esz);
+        p.fixup = h->cluster_fixup && (N <= kLpbMaxN || lds_bytes_for(N, kf.waves) <= kLdsMax);
+        LastKernel unused;
+        p.fix = N <= kLpbMaxN && cols != GATED ? plan_lpk(h, esz, pcols, &unused) : plan_traj(h, kf, esz, &unused);
+        p.order = true;
+        return p;
+    }
+    if (h->auto_cfg) choose_auto(h, k, batch, esz);
+    p.k = plan_traj(h, k, esz, &p.last);
+    return p;
+}
+
+// double (linsys_t = double).  lower_ok: the latch says the caller's matrices are block-symmetric (the lane-quad kernels need it).
+static constexpr uint32_t kRplMaxN64 = 32;
+static PcgPlan plan_f64(const mpcg_handle* h, uint32_t batch, int pcols, bool lower_ok) {
+    PcgPlan p;
+    const uint32_t N = h->N;
+    // 32 < N <= 64 (or "pcg_lqk" = 1 at any N <= 64): the lane-quad kernel of one CU (pcg_lqk_f64.hip.h).  Also 16 < N <= 32 when the call brings at
+    // least four trajectories per CU: two 32-knot workgroups per CU take 4.2 us per iteration of 1,024 trajectories at every such N and 30-39 us to
+    // start, the row-per-lane kernel 4.4 us and 38-64 us — 40-iteration solves of 1,024 trajectories: 200-205 against 218-246 us
+    // (tools/_prof/f64_fixed_cost.py); below that batch the row-per-lane kernel's 1.0-1.1 us per iteration of ONE trajectory wins (1.7).
+    const bool lqk_short = N > 16 && batch >= 4u * (uint32_t)h->num_cus;
+    if (lower_ok && !h->generic && N <= kLqkMaxN && h->lqk != 0 && (h->lqk == 1 || (h->auto_cfg && (N > kRplMaxN64 || lqk_short) && h->cluster < 0))) {
+        const int nw = N <= 32 ? 4 : 8;
+        const size_t lds = pcg_lqk_lds_doubles(nw) * sizeof(double);
+        p.k = make_launch(nw == 4 ? pcg_lqk_f64_kernel<1> : pcg_lqk_f64_kernel<2>, nw * 64, lds);
+        p.last = LastKernel{FAM_LQK64, nw, 0, 0, 0, 0, (int)lds, 0};
+        p.lower = true;
+        return p;
+    }
+    // N <= 32 (the real-time horizon): the row-per-lane kernel in double, one slot per wavefront
+    if (!h->generic && N <= kRplMaxN64 && h->rpl != 0 && (h->rpl == 1 || h->auto_cfg)) {
+        const int nw = N <= 16 ? 4 : 8;
+        const size_t lds = pcg_rpl_lds_floats((int)N, nw) * sizeof(double);
+        const bool pc3 = pcols == 3;
+        p.k = nw == 4 ? make_launch(pc3 ? pcg_rpl_kernel_f64<4, 1, true> : pcg_rpl_kernel_f64<4, 1, false>, 256, lds)
+                      : make_launch(pc3 ? pcg_rpl_kernel_f64<8, 1, true> : pcg_rpl_kernel_f64<8, 1, false>, 512, lds);
+        p.last = LastKernel{FAM_RPL, nw, 1, 0, 0, 0, (int)lds, 0};
+        return p;
+    }
+    if (h->generic) { p.k = plan_generic<double, 0>(h, &p.last); return p; }
+    LastKernel unused;
+    p.fix = plan_generic<double, 14>(h, &unused);          // the clusters' fix-up: the streaming kernel
+    // 64 < N <= 512, block-symmetric matrices: the lane-quad kernel across G = ceil(N / 64) CUs of one XCD (pcg_lqk_cluster_f64.hip.h)
+    p.G = lower_ok && N > kRplMaxN64 && h->cluster != 0 && h->lqk != 0 ? cluster_members(h, 64, LQKC_MAX_G) : 0;
+    if (p.G) {
+        p.k = make_launch(pcg_lqkc_f64_kernel<2>, 512, pcg_lqkc_lds_doubles() * sizeof(double));
+        p.last = LastKernel{FAM_LQKC64, 8, 0, 0, 0, p.G, (int)p.k.lds, 0};
+        p.member_words = LQKC_WG_WORDS;
+        p.lower = true;
+        // (the fix-up is the streaming kernel, two block columns (the latch says symmetric): beyond the horizon whose iterate vectors fit its LDS
+        //  — N = 350 in double — an abandoned trajectory is reported, d_iters = 0xFFFFFFFF / d_max_iter_exit = 2, as with "cluster_fixup" = 0)
+        p.fix_lower = 1;
+    } else {
+        // 32 < N <= 256: the row-per-lane kernel across G = ceil(N / 32) CUs of one XCD, full block rows of S and Pinv in registers
+        // (pcg_rpl_cluster_f64.hip.h; "cluster" = 0: the streaming kernel below)
+        p.G = h->cluster != 0 ? cluster_members(h, RPLC_KMAX, RPLC_MAX_G) : 0;
+        if (!p.G) { p.k = plan_generic<double, 14>(h, &p.last); p.fix = Launch(); return p; }
+        p.k = make_launch(pcols == 3 ? pcg_rplc_f64_kernel<true> : pcg_rplc_f64_kernel<false>, RPLC_NW * 64, pcg_rplc_lds_doubles() * sizeof(double));
+        p.last = LastKernel{FAM_RPLC64, RPLC_NW, 0, 0, 0, p.G, (int)p.k.lds, 0};
+        p.member_words = RPLC_WG_WORDS;
+    }
+    p.resident = cluster_resident(h, p.G);
+    p.lam_esz = sizeof(double);
+    p.fixup = h->cluster_fixup && p.fix.rc == MPCG_OK;
+    return p;
+}
+
+// ---- launching a plan -------------------------------------------------------------------------------
+// hipFuncSetAttribute when the launch needs more than 48 KiB of LDS, the launch (grid 0: `batch` workgroups), the error check
+static int launch(mpcg_handle* h, const Launch& L, void* arg, uint32_t batch, hipStream_t st) {
+    if (L.rc != MPCG_OK) return fail(h, L.rc, L.err);
+    if (L.lds > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(L.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    void* args[] = {arg};
+    (void)hipLaunchKernel(L.kern, dim3(L.grid ? L.grid : batch), dim3(L.block), args, L.lds, st);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
+static int launch_args(mpcg_handle* h, const Launch& L, PcgArgs a, uint32_t batch, hipStream_t st) {
+    a.lds_rows = L.lds_rows; a.lds_extra_s = L.extra_s; a.lds_extra_p = L.extra_p;
+    return launch(h, L, &a, batch, st);
+}
+template <typename T>
+static int launch_args(mpcg_handle* h, const Launch& L, PcgArgsG<T> a, uint32_t batch, hipStream_t st) {
+    a.n = (int)h->n;
+    return launch(h, L, &a, batch, st);
+}
+
+// A clustered launch (pcg_lpkc_kernel, pcg_rplc_f64_kernel, pcg_lqkc_f64_kernel): one persistent launch for any batch, clusters draw trajectories
+// from a queue.  Members must be co-resident, which a plain launch cannot guarantee when another stream holds CUs: a member that waits longer
+// than the bounded spin gives up; every member that FINISHES a trajectory counts itself in that trajectory's flag, and the launch is followed by
+// the fix-up launch, in which only the trajectories whose count is not G run — the caller always gets a solved system ("cluster_fixup" = 0, or
+// no fix-up that fits: the report of those trajectories instead).
+// Scratch: [queue: one 128-byte line][flags: one line per trajectory of the call][cells of the launch] — what a call uses is contiguous, so one
+// small fill precedes every launch (with lambda0 copied for the fix-up when one follows).  count_fixups: the fix-up adds to "cluster_fixups"
+// (not behind a gated launch, whose gated exits are no abandoned trajectories).
+template <typename CA, typename A>
+static int launch_cluster(mpcg_handle* h, const PcgPlan& p, const A& a, uint32_t batch, hipStream_t st, bool count_fixups) {
+    unsigned long long* words = p.lam_esz == sizeof(double) ? h->cluster64_scratch : h->cluster_scratch;
+    const uint32_t clusters = batch < p.resident ? batch : p.resident;
+    CA ca;
+    if constexpr (std::is_same<CA, ClusterArgs>::value) ca.kl_max = 128;
+    ca.p = a;
+    ca.queue = words;
+    ca.fail_flags = ca.queue + CL_FLAG_STRIDE;
+    ca.scratch = ca.fail_flags + (size_t)batch * CL_FLAG_STRIDE;
+    ca.G = p.G; ca.batch = (int)batch; ca.clusters = (int)clusters; ca.l2_handoff = h->cluster_l2;
+    ca.test_fail = h->cluster_test_fail;
+    const size_t zw = CL_FLAG_STRIDE + (size_t)batch * CL_FLAG_STRIDE + (size_t)clusters * p.G * p.member_words;
+    if (p.fixup) {
+        const int rc = launch_cluster_prologue(h, words, zw, a.lambda, (size_t)batch * h->N * NS * p.lam_esz, st);
+        if (rc != MPCG_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((zw + 255) / 256)), dim3(256), 0, st, words, zw);
+        HIP_TRY(h, hipGetLastError());
+    }
+    { const int rc = launch(h, p.k, &ca, ((clusters + 7) / 8) * 8 * (unsigned)p.G, st); if (rc != MPCG_OK) return rc; }
+    if (!p.fixup) return launch_cluster_report(h, ca.fail_flags, p.G, batch, a.iters, a.max_iter_exit, st);
+    A c = a;
+    c.redo_flags = ca.fail_flags; c.redo_stride = CL_FLAG_STRIDE; c.redo_skip = (unsigned)p.G;
+    c.redo_count = count_fixups ? fixup_counter(h) : nullptr;
+    c.lam0 = static_cast<decltype(c.lam0)>(h->lam_backup);     // (members that finished a trajectory their cluster did not have written their knots of lambda)
+    if constexpr (std::is_same<A, PcgArgs64>::value) c.lower = p.fix_lower;
+    return launch_args(h, p.fix, c, batch, st);
+}
+// the planned launch(es); h->last on success.  (A cluster's launch size: its resident clusters, whatever `batch`.)
+template <typename CA, typename A>
+static int launch_plan(mpcg_handle* h, const PcgPlan& p, const A& a, uint32_t batch, hipStream_t st, bool count_fixups = true) {
+    const int rc = p.G ? launch_cluster<CA>(h, p, a, batch, st, count_fixups) : launch_args(h, p.k, a, batch, st);
+    if (rc == MPCG_OK) h->last = p.last;
+    return rc;
+}
 
 // Tolerance of the block-symmetry checks: block pairs (k, right) / (k+1, left) that differ by more than 1 % of their largest entry.  The
 // reference's construction gives 0 for S; its symmetric-stair Pinv[k,right] / Pinv[k+1,left] are the same triple product associated two ways
@@ -789,7 +866,9 @@ static int symmetry_violations(mpcg_handle* h, const PcgArgs& a, uint32_t batch,
 //   a three-column kernel, gated the other way: runs only if the flag is set
 //   (clustered kernel: its own fix-up launch is that kernel — every completion count is 0 after a gated exit)
 // and, outside graph capture, an asynchronous copy of the flag to pinned host memory + an event that sym_poll() queries on later calls.
-static int launch_guarded(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st) {
+// Returns 1 when the plan has no lower-triangle kernel after all (the check kernels have run: the caller falls through).
+static int launch_guarded(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st, bool* order) {
+    const PcgPlan p = plan_f32(h, batch, a.esz, a.pcols, GATED);
     unsigned long long* flag = fixup_counter(h) + 9;
     const long items = (long)batch * ((long)h->N - 1);
     const unsigned blocks = (unsigned)((items + 3) / 4);
@@ -797,30 +876,17 @@ static int launch_guarded(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipS
     if (a.pcols == 3) h->sym_pinv_guarded = true;
     launch_symmetry_check(h, a, batch, st, blocks, nullptr, flag);
     HIP_TRY(h, hipGetLastError());
-    PcgArgs p = a;
-    p.redo_flags = flag; p.redo_stride = 0; p.redo_skip = 1; p.redo_count = nullptr;         // skip if the flag is 1
-    bool need_fallback = true;
-    int rc;
-    const int esz = a.esz;
-    if (use_lpk(h, esz, batch)) rc = launch_lpk(h, p, batch, st);
-    else {
-        rc = try_launch_cluster(h, p, batch, st, esz, /*guarded=*/true);
-        if (rc == 1) return 1;                                                                // (does not apply: the caller falls through)
-        need_fallback = !h->cluster_fixup;
-    }
-    if (rc != MPCG_OK) return rc;
-    const LastKernel primary = h->last;
-    if (need_fallback) {
+    const int fam = p.last.family;
+    if (fam != FAM_LPK && fam != FAM_LQB && fam != FAM_LPKC) return 1;
+    PcgArgs g = a;
+    g.redo_flags = flag; g.redo_stride = 0; g.redo_skip = 1; g.redo_count = nullptr;         // skip if the flag is 1
+    { const int rc = launch_plan<ClusterArgs>(h, p, g, batch, st, /*count_fixups=*/false); if (rc != MPCG_OK) return rc; }
+    *order = p.order;
+    if (fam != FAM_LPKC || !h->cluster_fixup) {
         PcgArgs f = a;
         f.redo_flags = flag; f.redo_stride = 0; f.redo_skip = 0; f.redo_count = nullptr;     // skip if the flag is 0
-        if (esz == 4 && h->N <= kRplMaxN && h->rpl != 0) rc = launch_rpl(h, f, batch, st);   // full block rows in registers
-        else {
-            PcgKnobs k = h->k;
-            choose_auto(h, k, batch, esz);
-            rc = launch_traj(h, k, f, batch, st, esz, /*record=*/false);
-        }
+        const int rc = launch_args(h, plan_f32(h, batch, a.esz, a.pcols, FALLBACK).k, f, batch, st);
         if (rc != MPCG_OK) return rc;
-        h->last = primary;
     }
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (!h->sym_pending && hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) {
@@ -833,220 +899,48 @@ static int launch_guarded(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipS
     return MPCG_OK;
 }
 
-static int launch_pcg(mpcg_handle* h, const PcgArgs& a_in, uint32_t batch, hipStream_t st, int esz) {
+// One float / fp16 solve.  *order: the launched plan asks for the dispatch-order kernel.
+static int launch_pcg(mpcg_handle* h, const PcgArgs& a_in, uint32_t batch, hipStream_t st, int esz, bool* order) {
     HIP_TRY(h, hipSetDevice(h->device));
     PcgArgs a = a_in;
     a.esz = esz;
-    if (h->generic) {
-        if (esz != 4) return fail(h, MPCG_ERR_UNSUPPORTED, "fp16 matrix storage exists for state_size = 14 only");
-        return launch_generic_f32(h, a, batch, st);
+    PcgPlan p = plan_f32(h, batch, esz, a.pcols, LOWER);
+    *order = false;
+    if (h->generic) {      // state_size != 14: the PcgArgs of the tuned path re-packed for the generic kernel
+        PcgArgsG<float> g;
+        g.S = static_cast<const float*>(a.S); g.Pinv = static_cast<const float*>(a.Pinv); g.gamma = a.gamma; g.lambda = a.lambda;
+        g.r_out = a.r_out; g.p_out = a.p_out; g.iters = a.iters; g.max_iter_exit = a.max_iter_exit;
+        g.N = a.N; g.max_iter = a.max_iter; g.exit_tol = a.exit_tol; g.pcols = a.pcols;
+        const int rc = launch_args(h, p.k, g, batch, st);
+        if (rc == MPCG_OK) h->last = p.last;
+        return rc;
     }
-    if (use_rpl(h, esz, batch)) return launch_rpl(h, a, batch, st);      // (an explicit "pcg_lpk" = 1 wins over the automatic choice of this one)
-    // "check_symmetry" (debug, off by default): the kernels below read only the left + diagonal block columns (mpcg.h "Block symmetry").
-    // Verify the precondition on this call's matrices; a call that violates it is solved by a kernel that reads all three columns.
-    bool lower_ok = true;
-    h->last_sym_violations = 0;
-    if (h->check_symmetry && (use_lpk(h, esz, batch) || (h->cluster != 0 && (h->cluster > 0 || h->N > kLpbMaxN)))) {
-        int v = 0;
-        const int rc = symmetry_violations(h, a, batch, st, &v);
-        if (rc != MPCG_OK) return rc;
-        h->last_sym_violations = v;
-        lower_ok = v == 0;
-    } else if (a.redo_flags == nullptr && (use_lpk(h, esz, batch) || (h->cluster != 0 && (h->cluster > 0 || (h->auto_cfg && h->N > kLpbMaxN))))) {
-        // the symmetry latch (see launch_guarded): no synchronisation, no per-solve D2H
-        sym_poll(h, st, true);
-        { const int rc = sym_prepare(h, a.pcols, st); if (rc != MPCG_OK) return rc; }
-        if (h->sym_state == 2) lower_ok = false;
-        else if (h->sym_state == 0) {
-            const int rc = launch_guarded(h, a, batch, st);
-            if (rc != 1) return rc;
+    if (p.last.family != FAM_RPL) {
+        // "check_symmetry" (debug, off by default): the kernels below read only the left + diagonal block columns (mpcg.h "Block symmetry").
+        // Verify the precondition on this call's matrices; a call that violates it is solved by a kernel that reads all three columns.
+        bool lower_ok = true;
+        h->last_sym_violations = 0;
+        if (h->check_symmetry && p.check) {
+            int v = 0;
+            const int rc = symmetry_violations(h, a, batch, st, &v);
+            if (rc != MPCG_OK) return rc;
+            h->last_sym_violations = v;
+            lower_ok = v == 0;
+        } else if (p.lower) {
+            // the symmetry latch (see launch_guarded): no synchronisation, no per-solve D2H
+            sym_poll(h, st, true);
+            { const int rc = sym_prepare(h, a.pcols, st); if (rc != MPCG_OK) return rc; }
+            if (h->sym_state == 2) lower_ok = false;
+            else if (h->sym_state == 0) {
+                const int rc = launch_guarded(h, a, batch, st, order);
+                if (rc != 1) return rc;
+            }
         }
+        if (!lower_ok) p = plan_f32(h, batch, esz, a.pcols, FULL);
     }
-    if (lower_ok) {
-        if (use_lpk(h, esz, batch)) return launch_lpk(h, a, batch, st);
-        const int rc = try_launch_cluster(h, a, batch, st, esz);
-        if (rc != 1) return rc;
-    } else if (esz == 4 && h->N <= kRplMaxN && h->rpl != 0) {
-        return launch_rpl(h, a, batch, st);              // full block rows in registers
-    }
-    PcgKnobs k = h->k;
-    if (h->auto_cfg) choose_auto(h, k, batch, esz);
-    return launch_traj(h, k, a, batch, st, esz, /*record=*/true);
-}
-
-static int occupancy(mpcg_handle* h, const PcgKnobs& k, int* per_cu) {
-    const int sb = stream_bufs_for(h, k, k.waves, 4);
-    for (int want : {sb, sb == 0 ? 1 : -2, sb <= 0 ? 2 : -2}) {
-        if (want == -2) continue;
-#define X(NW_, RT_, SB_) \
-        if (k.waves == NW_ && k.reg_rows == RT_ && (want == SB_ || (want == -1 && SB_ > 0))) \
-            return occupancy_t<NW_, RT_, SB_, float>(h, k, per_cu);
-        MPCG_PCG_VARIANTS(X)
-#undef X
-    }
-    return fail(h, MPCG_ERR_UNSUPPORTED, "no compiled kernel variant for this (pcg_waves, pcg_reg_rows, pcg_stream_bufs)");
-}
-
-// LDS bytes of the launch a default-configured batch-1 solve makes (what pcgSharedMemSize stands for)
-static size_t default_launch_lds_bytes(uint32_t N, int num_cus) {
-    if (N <= 32) return pcg_rpl_lds_floats((int)N, N <= 16 ? 4 : 8) * sizeof(float);           // row-per-lane kernel (a batch-1 call)
-    if (N <= kLpbMaxN) return pcg_lqb_lds_floats(N <= 64 ? 64 : 128) * sizeof(float);  // lane-quad kernel
-    mpcg_handle tmp;
-    tmp.N = N; tmp.n = NS; tmp.num_cus = num_cus;
-    if (lpkc_members(&tmp) > 0) return pcg_lpkc_lds_floats(8) * sizeof(float);          // clustered lane-pair kernel
-    choose_auto(&tmp, tmp.k, 1, 4);                                                     // (beyond 8 x 128 knots: the single-workgroup streaming kernel)
-    const int sb = stream_bufs_for(&tmp, tmp.k, tmp.k.waves, 4);
-    return traj_lds(&tmp, tmp.k, tmp.k.waves, sb == 0 ? 0 : 1, 4).bytes;
-}
-
-template <typename T, int NFIX>
-static int launch_generic(mpcg_handle* h, PcgArgsG<T> a, uint32_t batch, void* stream) {
-    HIP_TRY(h, hipSetDevice(h->device));
-    a.n = (int)h->n;
-    const size_t lds = pcg_generic_lds_elems((int)h->N, (int)h->n) * sizeof(T);
-    if (lds > kLdsMax) return fail(h, MPCG_ERR_UNSUPPORTED, "generic / double-precision kernel: the iterate vectors do not fit 160 KiB of LDS");
-    const int nthr = pcg_generic_threads((int)h->N, (int)h->n);
-    void (*kern)(PcgArgsG<T>) = nthr == F64_THREADS_WIDE ? pcg_generic_kernel<T, NFIX, F64_THREADS_WIDE> : pcg_generic_kernel<T, NFIX, F64_THREADS>;
-    if (lds > 48 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(nthr), lds, static_cast<hipStream_t>(stream), a);
-    HIP_TRY(h, hipGetLastError());
-    h->last = LastKernel{3, nthr / 64, 0, 0, 2, 0, (int)lds, 0};      // family 3 = generic streaming kernel
-    return MPCG_OK;
-}
-// double precision, N <= 32 (the real-time horizon): the row-per-lane kernel in double, one slot per wavefront
-static constexpr uint32_t kRplMaxN64 = 32;
-template <int NW, bool PC3>
-static int launch_rpl_f64_t(mpcg_handle* h, const PcgArgs64& a, uint32_t batch, hipStream_t st) {
-    const size_t lds = pcg_rpl_lds_floats((int)h->N, NW) * sizeof(double);
-    hipLaunchKernelGGL((pcg_rpl_kernel_f64<NW, 1, PC3>), dim3(batch), dim3(NW * 64), lds, st, a);
-    HIP_TRY(h, hipGetLastError());
-    h->last = LastKernel{FAM_RPL, NW, 1, 0, 0, 0, (int)lds, 0};
-    return MPCG_OK;
-}
-// ---- linsys_t = double, 32 < N <= 256: the row-per-lane kernel across G = ceil(N / 32) CUs of one XCD (pcg_rpl_cluster_f64.hip.h) ----
-// Same launch shape as the clustered lane-pair kernel (persistent clusters pinned to XCDs, one fill of queue + flags + cells in front, a fix-up
-// launch behind: here the streaming kernel, gated on the completion counts).  Returns 1 when it does not apply.
-static int rplc64_members(const mpcg_handle* h) {
-    const int G = h->cluster > 0 ? h->cluster : ((int)h->N + RPLC_KMAX - 1) / RPLC_KMAX;
-    if (G < 2 || G > RPLC_MAX_G || G > h->num_cus || G > (int)h->N) return 0;
-    if (((int)h->N + G - 1) / G > RPLC_KMAX) return 0;
-    return G;
-}
-static size_t cluster64_alloc_words(const mpcg_handle* h) {
-    return CL_FLAG_STRIDE + (size_t)h->max_batch * CL_FLAG_STRIDE + (size_t)h->num_cus * RPLC_WG_WORDS + 16;
-}
-template <typename T, int NFIX>
-static int launch_generic(mpcg_handle* h, PcgArgsG<T> a, uint32_t batch, void* stream);
-static int try_launch_cluster_f64(mpcg_handle* h, const PcgArgs64& a, uint32_t batch, hipStream_t st) {
-    if (h->cluster == 0 || h->generic) return 1;
-    const int G = rplc64_members(h);
-    if (G == 0) return 1;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "batch exceeds max_batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->cluster64_scratch || (h->cluster_fixup && h->lam_backup_bytes < (size_t)h->max_batch * h->N * NS * sizeof(double))) {
-        // (mpcg_create made them for handles with <= 8 MB of double iterates; "reserve_f64" = 1 makes them ahead of a capture)
-        { const int rc = alloc_allowed(h, st, "mpcg_pcg_solve_f64 (or set \"reserve_f64\" = 1 first)"); if (rc != MPCG_OK) return rc; }
-        { const int rc = reserve_f64(h); if (rc != MPCG_OK) return rc; }
-    }
-    const uint32_t resident = lpkc_resident_clusters(h, G);
-    const uint32_t clusters = batch < resident ? batch : resident;
-    const size_t lds = pcg_rplc_lds_doubles() * sizeof(double);
-    void (*kern)(ClusterArgs64) = a.pcols == 3 ? pcg_rplc_f64_kernel<true> : pcg_rplc_f64_kernel<false>;
-    if (lds > 48 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ClusterArgs64 ca;
-    ca.p = a;
-    ca.queue = h->cluster64_scratch;
-    ca.fail_flags = ca.queue + CL_FLAG_STRIDE;
-    ca.scratch = ca.fail_flags + (size_t)batch * CL_FLAG_STRIDE;
-    ca.G = G; ca.batch = (int)batch; ca.clusters = (int)clusters; ca.l2_handoff = h->cluster_l2;
-    ca.test_fail = h->cluster_test_fail;
-    const size_t zw = CL_FLAG_STRIDE + (size_t)batch * CL_FLAG_STRIDE + (size_t)clusters * G * RPLC_WG_WORDS;
-    if (h->cluster_fixup) {
-        const int rc = launch_cluster_prologue(h, h->cluster64_scratch, zw, a.lambda, (size_t)batch * h->N * NS * sizeof(double), st);
-        if (rc != MPCG_OK) return rc;
-    } else {
-        hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((zw + 255) / 256)), dim3(256), 0, st, h->cluster64_scratch, zw);
-        HIP_TRY(h, hipGetLastError());
-    }
-    hipLaunchKernelGGL(kern, dim3(((clusters + 7) / 8) * 8 * (unsigned)G), dim3(RPLC_NW * 64), lds, st, ca);
-    HIP_TRY(h, hipGetLastError());
-    if (h->cluster_fixup) {                             // trajectories whose cluster gave up: the streaming kernel, all three block columns
-        PcgArgs64 c = a;
-        c.lower = 0;
-        c.redo_flags = ca.fail_flags; c.redo_stride = CL_FLAG_STRIDE; c.redo_skip = (unsigned long long)G;
-        c.redo_count = fixup_counter(h);
-        c.lam0 = static_cast<const double*>(h->lam_backup);
-        const int rc = launch_generic<double, 14>(h, c, batch, st);
-        if (rc != MPCG_OK) return rc;
-    } else {
-        const int rc = launch_cluster_report(h, ca.fail_flags, G, batch, a.iters, a.max_iter_exit, st);
-        if (rc != MPCG_OK) return rc;
-    }
-    h->last = LastKernel{FAM_RPLC64, RPLC_NW, 0, 0, 0, G, (int)lds, 0};
-    return MPCG_OK;
-}
-
-// ---- linsys_t = double, 64 < N <= 512, block-symmetric matrices: the lane-quad kernel across G = ceil(N / 64) CUs of one XCD (pcg_lqk_cluster_f64.hip.h).
-// Launch shape, scratch and fix-up of try_launch_cluster_f64.  Returns 1 when it does not apply.
-static int lqkc_members(const mpcg_handle* h) {
-    const int nmax = 64;
-    const int G = h->cluster > 0 ? h->cluster : ((int)h->N + nmax - 1) / nmax;
-    if (G < 2 || G > LQKC_MAX_G || G > h->num_cus || G > (int)h->N) return 0;
-    if (((int)h->N + G - 1) / G > nmax) return 0;
-    return G;
-}
-static int try_launch_cluster_lqk_f64(mpcg_handle* h, const PcgArgs64& a, uint32_t batch, hipStream_t st) {
-    if (h->cluster == 0 || h->generic || h->lqk == 0) return 1;
-    const int G = lqkc_members(h);
-    if (G == 0) return 1;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "batch exceeds max_batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->cluster64_scratch || (h->cluster_fixup && h->lam_backup_bytes < (size_t)h->max_batch * h->N * NS * sizeof(double))) {
-        // (mpcg_create made them for handles with <= 8 MB of double iterates; "reserve_f64" = 1 makes them ahead of a capture)
-        { const int rc = alloc_allowed(h, st, "mpcg_pcg_solve_f64 (or set \"reserve_f64\" = 1 first)"); if (rc != MPCG_OK) return rc; }
-        { const int rc = reserve_f64(h); if (rc != MPCG_OK) return rc; }
-    }
-    const uint32_t resident = lpkc_resident_clusters(h, G);
-    const uint32_t clusters = batch < resident ? batch : resident;
-    const size_t lds = pcg_lqkc_lds_doubles() * sizeof(double);
-    void (*kern)(ClusterArgs64) = pcg_lqkc_f64_kernel<2>;
-    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ClusterArgs64 ca;
-    ca.p = a;
-    ca.queue = h->cluster64_scratch;
-    ca.fail_flags = ca.queue + CL_FLAG_STRIDE;
-    ca.scratch = ca.fail_flags + (size_t)batch * CL_FLAG_STRIDE;
-    ca.G = G; ca.batch = (int)batch; ca.clusters = (int)clusters; ca.l2_handoff = h->cluster_l2;
-    ca.test_fail = h->cluster_test_fail;
-    const size_t zw = CL_FLAG_STRIDE + (size_t)batch * CL_FLAG_STRIDE + (size_t)clusters * G * LQKC_WG_WORDS;
-    // (the fix-up is the streaming kernel: beyond the horizon whose iterate vectors fit its LDS — N = 350 in double — an abandoned trajectory is
-    //  reported, d_iters = 0xFFFFFFFF / d_max_iter_exit = 2, as with "cluster_fixup" = 0)
-    const bool fixup = h->cluster_fixup && pcg_generic_lds_elems((int)h->N, (int)h->n) * sizeof(double) <= kLdsMax;
-    if (fixup) {
-        const int rc = launch_cluster_prologue(h, h->cluster64_scratch, zw, a.lambda, (size_t)batch * h->N * NS * sizeof(double), st);
-        if (rc != MPCG_OK) return rc;
-    } else {
-        hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((zw + 255) / 256)), dim3(256), 0, st, h->cluster64_scratch, zw);
-        HIP_TRY(h, hipGetLastError());
-    }
-    hipLaunchKernelGGL(kern, dim3(((clusters + 7) / 8) * 8 * (unsigned)G), dim3(512), lds, st, ca);
-    HIP_TRY(h, hipGetLastError());
-    if (fixup) {                                        // trajectories whose cluster gave up: the streaming kernel (two block columns: the latch says symmetric)
-        PcgArgs64 c = a;
-        c.lower = 1;
-        c.redo_flags = ca.fail_flags; c.redo_stride = CL_FLAG_STRIDE; c.redo_skip = (unsigned long long)G;
-        c.redo_count = fixup_counter(h);
-        c.lam0 = static_cast<const double*>(h->lam_backup);
-        const int rc = launch_generic<double, 14>(h, c, batch, st);
-        if (rc != MPCG_OK) return rc;
-    } else {
-        const int rc = launch_cluster_report(h, ca.fail_flags, G, batch, a.iters, a.max_iter_exit, st);
-        if (rc != MPCG_OK) return rc;
-    }
-    h->last = LastKernel{FAM_LQKC64, 8, 0, 0, 0, G, (int)lds, 0};
-    return MPCG_OK;
+    const int rc = launch_plan<ClusterArgs>(h, p, a, batch, st);
+    *order = rc == MPCG_OK && p.order;
+    return rc;
 }
 
 // The double kernels that read only the left + diagonal block columns use the float path's latch (mpcg.h, BLOCK SYMMETRY): a handle that does not
@@ -1079,118 +973,68 @@ static int f64_symmetry_latch(mpcg_handle* h, const PcgArgs64& a, uint32_t batch
                     "runs kernels that read all three block columns (include/mpcg.h, BLOCK SYMMETRY)";
     return MPCG_OK;
 }
-// linsys_t = double, N <= 64: a lane quad per knot, the lower block triangle in the registers of ONE CU (pcg_lqk_f64.hip.h)
-template <int NWR>
-static int launch_lqk_f64_t(mpcg_handle* h, const PcgArgs64& a, uint32_t batch, hipStream_t st) {
-    const size_t lds = pcg_lqk_lds_doubles(4 * NWR) * sizeof(double);
-    void (*kern)(PcgArgs64) = pcg_lqk_f64_kernel<NWR>;
-    if (lds > 48 * 1024)
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(NWR * 256), lds, st, a);
-    HIP_TRY(h, hipGetLastError());
-    h->last = LastKernel{FAM_LQK64, 4 * NWR, 0, 0, 0, 0, (int)lds, 0};
-    return MPCG_OK;
-}
 
 static int launch_f64(mpcg_handle* h, PcgArgs64 a, uint32_t batch, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // 32 < N <= 64 (or "pcg_lqk" = 1 at any N <= 64): the lane-quad kernel, once the latch says the matrices are block-symmetric.  Also 16 < N <= 32
-    // when the call brings at least four trajectories per CU: two 32-knot workgroups per CU take 4.2 us per iteration of 1,024 trajectories at
-    // every such N and 30-39 us to start, the row-per-lane kernel 4.4 us and 38-64 us — 40-iteration solves of 1,024 trajectories: 200-205 against
-    // 218-246 us (tools/_prof/f64_fixed_cost.py); below that batch the row-per-lane kernel's 1.0-1.1 us per iteration of ONE trajectory wins (1.7).
-    const bool lqk_short = h->N > 16 && batch >= 4u * (uint32_t)h->num_cus;
-    if (!h->generic && h->N <= kLqkMaxN && h->lqk != 0 && (h->lqk == 1 || (h->auto_cfg && (h->N > kRplMaxN64 || lqk_short) && h->cluster < 0))) {
+    HIP_TRY(h, hipSetDevice(h->device));
+    PcgPlan p = plan_f64(h, batch, a.pcols, true);
+    if (p.lower) {         // the lane-quad kernels: once the latch says the matrices are block-symmetric
         const int rc = f64_symmetry_latch(h, a, batch, st);
         if (rc != MPCG_OK) return rc;
-        if (h->sym_state == 1) {
-            HIP_TRY(h, hipSetDevice(h->device));
-            return h->N <= 32 ? launch_lqk_f64_t<1>(h, a, batch, st) : launch_lqk_f64_t<2>(h, a, batch, st);
-        }
+        if (h->sym_state != 1) p = plan_f64(h, batch, a.pcols, false);
     }
-    if (!h->generic && h->N <= kRplMaxN64 && h->rpl != 0 && (h->rpl == 1 || h->auto_cfg)) {
-        HIP_TRY(h, hipSetDevice(h->device));
-        if (h->N <= 16) return a.pcols == 3 ? launch_rpl_f64_t<4, true>(h, a, batch, st) : launch_rpl_f64_t<4, false>(h, a, batch, st);
-        return a.pcols == 3 ? launch_rpl_f64_t<8, true>(h, a, batch, st) : launch_rpl_f64_t<8, false>(h, a, batch, st);
-    }
-    if (h->generic) return launch_generic<double, 0>(h, a, batch, stream);
-    // 64 < N <= 512, block-symmetric matrices: lane-quad clusters of ceil(N / 64) CUs
-    if (h->N > kRplMaxN64 && h->cluster != 0 && h->lqk != 0 && lqkc_members(h) > 0) {
-        const int rcl = f64_symmetry_latch(h, a, batch, st);
-        if (rcl != MPCG_OK) return rcl;
-        if (h->sym_state == 1) {
-            const int rc = try_launch_cluster_lqk_f64(h, a, batch, st);
-            if (rc != 1) return rc;
-        }
-    }
-    {   // 32 < N <= 256: clusters of ceil(N / 32) CUs keep full block rows of S and Pinv in registers ("cluster" = 0: the streaming kernel below)
-        const int rc = try_launch_cluster_f64(h, a, batch, st);
-        if (rc != 1) return rc;
-    }
-    // The streaming kernel reads a third less when it may take block (k, right) from block (k+1, left) (mpcg.h, BLOCK SYMMETRY)
-    {
+    if (p.last.family == FAM_GENERIC && !h->generic) {
+        // the streaming kernel reads a third less when it may take block (k, right) from block (k+1, left) (mpcg.h, BLOCK SYMMETRY)
         const int rc = f64_symmetry_latch(h, a, batch, st);
         if (rc != MPCG_OK) return rc;
+        a.lower = h->sym_state == 1 ? 1 : 0;
     }
-    a.lower = h->sym_state == 1 ? 1 : 0;
-    return launch_generic<double, 14>(h, a, batch, stream);
+    if (p.G && (!h->cluster64_scratch || (h->cluster_fixup && h->lam_backup_bytes < (size_t)h->max_batch * h->N * NS * sizeof(double)))) {
+        // (mpcg_create made them for handles with <= 8 MB of double iterates; "reserve_f64" = 1 makes them ahead of a capture)
+        { const int rc = alloc_allowed(h, st, "mpcg_pcg_solve_f64 (or set \"reserve_f64\" = 1 first)"); if (rc != MPCG_OK) return rc; }
+        { const int rc = reserve_f64(h); if (rc != MPCG_OK) return rc; }
+    }
+    return launch_plan<ClusterArgs64>(h, p, a, batch, st);
 }
-// state_size != 14, float: the PcgArgs of the tuned path re-packed for the generic kernel
-static int launch_generic_f32(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st) {
-    PcgArgsG<float> g;
-    g.S = static_cast<const float*>(a.S); g.Pinv = static_cast<const float*>(a.Pinv); g.gamma = a.gamma; g.lambda = a.lambda;
-    g.r_out = a.r_out; g.p_out = a.p_out; g.iters = a.iters; g.max_iter_exit = a.max_iter_exit;
-    g.N = a.N; g.max_iter = a.max_iter; g.exit_tol = a.exit_tol; g.pcols = a.pcols;
-    return launch_generic<float, 0>(h, g, batch, st);
+
+// The plan of a default-configured batch-1 call (256 CUs) on a handle of the stack: no GPU needed
+static PcgPlan default_plan(uint32_t n, uint32_t N, bool f64) {
+    mpcg_handle tmp;
+    tmp.n = n; tmp.N = N; tmp.num_cus = 256; tmp.max_batch = 1;
+    tmp.generic = generic_shape_supported(n, N);
+    return f64 ? plan_f64(&tmp, 1, 3, true) : plan_f32(&tmp, 1, 4, 3, LOWER);
 }
 
 
 extern "C" {
 
+// LDS bytes of the launch a default-configured batch-1 solve makes (what pcgSharedMemSize stands for)
+size_t mpcg_pcg_lds_bytes(uint32_t state_size, uint32_t knot_points) {
+    if (!generic_shape_supported(state_size, knot_points) &&
+        (!shape_supported(state_size, knot_points) || (knot_points > kLpbMaxN && lds_bytes_for(knot_points, 16) > kLdsMax)))
+        return 0;
+    return default_plan(state_size, knot_points, false).k.lds;
+}
+
+size_t mpcg_pcg_lds_bytes_f64(uint32_t state_size, uint32_t knot_points) {     // (lane-quad kernels: block-symmetric matrices, the reference's)
+    if (!shape_supported(state_size, knot_points) && !generic_shape_supported(state_size, knot_points)) return 0;
+    const PcgPlan p = default_plan(state_size, knot_points, true);
+    return p.k.rc == MPCG_OK ? p.k.lds : 0;
+}
+
 // Resident trajectories of the configuration a throughput-sized call (batch = max_batch) would launch.
 int mpcg_check_pcg_occupancy(mpcg_handle* h, uint32_t* resident_trajectories) {
     if (!h || !resident_trajectories) return MPCG_ERR_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
-    int per_cu = 0;
-    if (h->generic) {
-        const size_t lds = pcg_generic_lds_elems((int)h->N, (int)h->n) * sizeof(float);
-        const int nthr = pcg_generic_threads((int)h->N, (int)h->n);
-        void (*kern)(PcgArgsG<float>) = nthr == F64_THREADS_WIDE ? pcg_generic_kernel<float, 0, F64_THREADS_WIDE> : pcg_generic_kernel<float, 0, F64_THREADS>;
-        if (lds > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, nthr, lds));
-    } else if (use_rpl(h, 4, h->max_batch)) {
-        // mirrors launch_pcg for a throughput-sized call (batch = max_batch): the row-per-lane kernel in the shape that call would take
-        int nw, rho;
-        rpl_shape(h, h->max_batch, &nw, &rho);
-        const size_t lds = pcg_rpl_lds_floats((int)h->N, nw) * sizeof(float);
-#define X(NW_, RHO_) if (nw == NW_ && rho == RHO_) HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pcg_rpl_kernel<NW_, RHO_, true>, NW_ * 64, lds));
-        MPCG_RPL_VARIANTS(X)
-#undef X
-    } else if (use_lpk(h, 4, h->max_batch) && use_lqb(h, 4)) {
-        const int nmax = h->N <= 32 ? 32 : h->N <= 64 ? 64 : 128;
-        const size_t lds = pcg_lqb_lds_floats(nmax) * sizeof(float);
-        const void* kern = nmax == 32 ? reinterpret_cast<const void*>(pcg_lqb_kernel<32, true>) : nmax == 64 ? reinterpret_cast<const void*>(pcg_lqb_kernel<64, true>) : reinterpret_cast<const void*>(pcg_lqb_kernel<128, true>);
-        HIP_TRY(h, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (nmax == 32) HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pcg_lqb_kernel<32, true>, 128, lds));
-        else if (nmax == 64) HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pcg_lqb_kernel<64, true>, 256, lds));
-        else HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pcg_lqb_kernel<128, true>, 512, lds));
-    } else if (use_lpk(h, 4, h->max_batch)) {
-        const size_t lds = pcg_lpk_lds_floats(h->N <= 32 ? 2 : h->N <= 64 ? 4 : 8) * sizeof(float);
-        if (h->N <= 32) HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pcg_lpk_kernel<0>, 128, lds));
-        else if (h->N <= 64) HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pcg_lpk_kernel<1>, 256, lds));
-        else {
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(pcg_lpk_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pcg_lpk_kernel<2>, 512, lds));
-        }
-    } else if (h->cluster != 0 && (h->cluster > 0 || (h->auto_cfg && h->N > kLpbMaxN)) && lpkc_members(h) > 0) {
-        // clustered kernel (the condition of try_launch_cluster): resident CLUSTERS = trajectories in flight, the count the launch itself uses
-        *resident_trajectories = lpkc_resident_clusters(h, lpkc_members(h));
+    const PcgPlan p = plan_f32(h, h->max_batch, 4, 3, LOWER);
+    if (p.G) {      // clustered kernel: resident CLUSTERS = trajectories in flight, the count the launch itself uses
+        *resident_trajectories = p.resident;
         return MPCG_OK;
-    } else {
-        PcgKnobs k = h->k;
-        if (h->auto_cfg) choose_auto(h, k, h->max_batch, 4);
-        const int rc = occupancy(h, k, &per_cu);
-        if (rc != MPCG_OK) return rc;
     }
+    if (p.k.rc != MPCG_OK) return fail(h, p.k.rc, p.k.err);
+    if (p.k.lds > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(p.k.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.k.lds));
+    int per_cu = 0;
+    HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p.k.kern, (int)p.k.block, p.k.lds));
     if (per_cu < 1) return fail(h, MPCG_ERR_UNSUPPORTED, "PCG workgroup does not fit on a CU");
     *resident_trajectories = (uint32_t)per_cu * (uint32_t)h->num_cus;
     return MPCG_OK;
@@ -1218,8 +1062,9 @@ int mpcg_pcg_solve(mpcg_handle* h, const float* d_S, const float* d_Pinv, const 
     // counts for the same batch (pcg_kernels.hip.h: sched_order_kernel).  A scheduling hint only: no result depends on it.
     const bool hinted = h->sched_hint && !h->generic && batch > (uint32_t)h->num_cus;
     if (hinted) { a.order = h->sched_order; a.order_tag = batch; }       // (used only if the stored permutation was made for this batch: sched_pick)
-    const int rc = launch_pcg(h, a, batch, static_cast<hipStream_t>(stream), 4);
-    if (rc == MPCG_OK && hinted && (h->last.family == FAM_LPK || h->last.family == FAM_LQB || h->last.family == FAM_LPKC || h->last.family == FAM_RPL)) {
+    bool order = false;
+    const int rc = launch_pcg(h, a, batch, static_cast<hipStream_t>(stream), 4, &order);
+    if (rc == MPCG_OK && hinted && order) {
         hipLaunchKernelGGL(sched_order_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), d_iters, (int)batch, h->sched_order);
         HIP_TRY(h, hipGetLastError());
     }
@@ -1242,7 +1087,8 @@ int mpcg_pcg_solve_ref(mpcg_handle* h, float* d_S, float* d_Pinv, float* d_gamma
     a.r_out = d_r; a.p_out = d_p;
     a.iters = d_pcg_iters; a.max_iter_exit = d_pcg_exit;
     a.N = (int)h->N; a.max_iter = (int)pcg_max_iter; a.exit_tol = pcg_exit_tol; a.pcols = 3; a.lds_rows = 0;
-    return launch_pcg(h, a, 1, static_cast<hipStream_t>(stream), 4);
+    bool order;
+    return launch_pcg(h, a, 1, static_cast<hipStream_t>(stream), 4, &order);
 }
 
 int mpcg_bt_spmv(mpcg_handle* h, const float* d_M, const float* d_x, float* d_y, uint32_t batch, int cols, void* stream) {
@@ -1316,7 +1162,8 @@ int mpcg_pcg_solve_f16(mpcg_handle* h, const uint16_t* d_S16, const uint16_t* d_
     a.r_out = nullptr; a.p_out = nullptr;
     a.iters = d_iters; a.max_iter_exit = d_max_iter_exit;
     a.N = (int)h->N; a.max_iter = (int)max_iter; a.exit_tol = exit_tol; a.pcols = (int)precond; a.lds_rows = 0;
-    return launch_pcg(h, a, batch, static_cast<hipStream_t>(stream), 2);
+    bool order;
+    return launch_pcg(h, a, batch, static_cast<hipStream_t>(stream), 2, &order);
 }
 
 int mpcg_pcg_solve_f64(mpcg_handle* h, const double* d_S, const double* d_Pinv, const double* d_gamma, double* d_lambda,
