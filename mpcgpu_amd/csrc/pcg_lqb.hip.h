@@ -27,8 +27,9 @@
 // Inner product without the assembled vector, from the partial sums themselves (no weights, no duplicates): x^T M x = sum over lanes of
 // x_k[piece g] . (ypart + its L part) — the coupling term x_{k-1}^T (L^T x_k) taken as x_k^T (L x_{k-1}) from the direct product.
 // Block-Jacobi (Pinv without off-diagonal blocks) is a build of its own, PC3 = false: no L sub-block of Pinv in registers, no z, a shorter epilogue.
-// Measured (steady clocks, tools/_prof/lqb_ab.py; lane-pair kernel in brackets): N = 128 SS 1.58 (1.62) us per iteration of one trajectory, 6.31 (6.54) per
-// 1024; block-Jacobi 1.29 (1.34); N = 64, two independent workgroups per CU: 1.03 (1.44), 3.02 (3.71); DESIGN.md §3.2b for where an iteration goes.
+// Measured (steady clocks, tools/_prof/lqb_ab.py; lane-pair kernel in brackets): N = 128 SS 1.49 (1.62) us per iteration of one trajectory, 5.98 (6.54) per
+// 1024 — 1.58 and 6.32 before the stage priorities (LQB_PHASE below); block-Jacobi 1.21 (1.35), 4.86 (5.52) per 1024; N = 64, two independent workgroups
+// per CU: 1.02 (1.44), 2.98 (3.71); DESIGN.md §3.2b for where an iteration goes.
 //
 // Reads only the left + diagonal block columns (include/mpcg.h, BLOCK SYMMETRY), like the lane-pair kernel; same PCG, same exit rule, same
 // outputs (include/pcg/sqp.cuh:137-150); another summation order, so results agree with it to the fp32 band, not bit for bit.
@@ -272,6 +273,16 @@ __device__ __forceinline__ void lqb_epilogue_y(float& part, LqbPiece& fin, const
 //  outside [2^-100, 2^100]: two more live registers, N = 64 one trajectory 1.07 -> 1.14 us per iteration, N = 128 unchanged.)
 // PC3: the preconditioner has off-diagonal blocks (SS); false = block-Jacobi — a build of its own, so that the SS build carries nothing of it (as a
 // wave-uniform branch inside one build the second epilogue cost the SS path 4-7 %: tools/_prof/lqb_ab.py).
+// Issue priority by the work a wavefront has LEFT in its pass (128 knots: the two wavefronts of a SIMD belong to ONE trajectory and meet at the same
+// barrier).  The SIMD arbitrates by age: left alone, the older wavefront wins every packed-FMA slot, is done with its whole pass first, and the younger
+// one runs what is left of its FMAs and its epilogue ALONE, at one instruction per 4 clocks, half of the VALU pipe idle — 200 clocks per pass in front
+// of the barrier.  With s_setprio 3 / 2 / 1 / 0 at the transposed product / direct L / direct D / epilogue the wavefront that is BEHIND wins the slot:
+// the lead changes hands at every stage, the two are never further apart than one stage, and the epilogue of one co-issues with the last FMAs of
+// the other.  No value changes (same instructions, same operands: tests/test_gpu_lqb_bits.py).  __builtin_amdgcn_sched_barrier keeps a stage's
+// instructions on their side of the s_setprio (it is no scheduling boundary of its own).  N = 128 SS batch 1024: 6.32 -> 5.98 us per iteration,
+// block-Jacobi 5.06 -> 4.86 (tools/_prof/lqb_ab.py; profiles/r08_lqb_ab.txt).  Not at 64 / 32 knots: the wavefronts of a SIMD are independent
+// workgroups there, no barrier joins them.
+#define LQB_PHASE(p) do { if constexpr (NW == 8) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(p); __builtin_amdgcn_sched_barrier(0); } } while (0)
 template <int NMAXQ, bool PC3>
 __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
     typedef LqbLds<NMAXQ> L;
@@ -406,6 +417,7 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
     // dead once the L columns are done: x^T M x = sum x_k[piece g] . (ypart + L-part of ypart).
     auto pass = [&](auto hasl_tag, const LqbSub& D, const LqbSub& Lb, const LqbPiece& mine, int TOUT, float* red, const f2* park, int pb) {
         constexpr bool hasL = decltype(hasl_tag)::value;
+        LQB_PHASE(3);
         const LqbPiece xg = lqb_quad<LQB_QP_XG>(mine);
         MPCG_STAMP(pb + 1);
         LqbPiece ypart, zpart;
@@ -437,6 +449,7 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
                 zpart.s = fmaf(Lb.e, xg.s, lqb_hsum(zt[2]));
             }
             // direct, off-diagonal block: L x_{k-1}[piece h]
+            LQB_PHASE(2);
             const LqbPiece xm = lqb_quad<LQB_QP_XM>(mine);
 #pragma unroll
             for (int rp = 0; rp < 3; ++rp) acc[rp] = Lb.A[rp][0] * bc(xm, std::integral_constant<int, 0>{});
@@ -461,6 +474,7 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
             y6 = 0.f; ds = 0.f; dd = f2{0.f, 0.f}; zpart.s = 0.f;
         }
         // direct, diagonal block: D x_k[piece h]; the pairs parked in LDS are requested here (volatile: in program order) and used last
+        LQB_PHASE(1);
         const LqbPiece xh = lqb_quad<LQB_QP_XH>(mine);
         f2 pk_[NPK > 0 ? NPK : 1];
 #pragma unroll
@@ -485,6 +499,7 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
         dd = __builtin_elementwise_fma(ypart.p[1], xg.p[1], dd);
         dd = __builtin_elementwise_fma(ypart.p[2], xg.p[2], dd);
         MPCG_STAMP(pb + 2);
+        LQB_PHASE(0);
         float part = fmaf(ypart.s, xg.s, ds) + lqb_hsum(dd);
         LqbPiece fin;
         if constexpr (hasL) lqb_epilogue(part, fin, ypart, zpart, diag_mask);
@@ -598,6 +613,7 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
     LQB_PSTAMP(6);
     MPCG_WG_STAMP(1);
 #undef LQB_PSTAMP
+#undef LQB_PHASE
 }
 
 }  // namespace mpcg
