@@ -3,8 +3,11 @@
 // compiled against the shim headers and libmpcg_hip.so.  Checks on the CPU that the step satisfies the
 // regularised KKT conditions:  (G + rho I) dz + C^T lambda = g   and   C dz = c.
 //   hipcc --offload-arch=gfx950 -O2 -Iinclude/gbd_pcg_compat -Iinclude/mpcgpu_compat examples/sqp_linsys_chain.cpp -Lmpcgpu_amd -lmpcg_hip
+//   sqp_linsys_chain [--direct] [--state n --control m]     another robot's shape, 1 <= m <= n (default 14 x 7); the pcg<> launch is a
+//   template in the state size, as in the reference, so without --direct n is one of the sizes instantiated in pcg_kernel_for below
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -20,10 +23,32 @@ typedef double T;             // pcg<double, n, N> and compute_dz<double>; the s
 typedef float T;
 #endif
 
+template <uint32_t NS> static void* pcg_of() { return (void*)pcg<T, NS, KNOT_POINTS>; }
+static void* pcg_kernel_for(uint32_t state_size) {
+    switch (state_size) {
+        case 4: return pcg_of<4>();
+        case 6: return pcg_of<6>();
+        case 12: return pcg_of<12>();
+        case 13: return pcg_of<13>();
+        case STATE_SIZE: return pcg_of<STATE_SIZE>();
+        case 32: return pcg_of<32>();
+        default: return nullptr;
+    }
+}
+
 int main(int argc, char** argv) {
-    const bool use_direct = argc > 1 && std::string(argv[1]) == "--direct";   // block_solve_schur instead of pcg<>
-    const uint32_t state_size = STATE_SIZE, control_size = 7, knot_points = KNOT_POINTS;
-    const int n = 14, m = 7, N = KNOT_POINTS, nn = n * n, mm = m * m, nm = n * m;
+    bool use_direct = false;                                               // block_solve_schur instead of pcg<>
+    uint32_t state_size = STATE_SIZE, control_size = 7;
+    for (int i = 1; i < argc; ++i) {
+        const std::string arg = argv[i];
+        if (arg == "--direct") use_direct = true;
+        else if (arg == "--state" && i + 1 < argc) state_size = (uint32_t)atoi(argv[++i]);
+        else if (arg == "--control" && i + 1 < argc) control_size = (uint32_t)atoi(argv[++i]);
+        else { fprintf(stderr, "usage: %s [--direct] [--state n --control m]\n", argv[0]); return 2; }
+    }
+    if (state_size < 1 || state_size > 64 || control_size < 1 || control_size > state_size) { fprintf(stderr, "1 <= control <= state <= 64\n"); return 2; }
+    const uint32_t knot_points = KNOT_POINTS;
+    const int n = (int)state_size, m = (int)control_size, N = KNOT_POINTS, nn = n * n, mm = m * m, nm = n * m;
     const size_t Gsz = (size_t)(nn + mm) * N - mm, Csz = (size_t)(nn + nm) * (N - 1), gsz = (size_t)(n + m) * N - m;
     const T rho = 0.5f;
     std::vector<T> G(Gsz, 0.f), C(Csz), g(gsz), c(n * N), Graw;
@@ -69,7 +94,8 @@ int main(int argc, char** argv) {
     pcg_config<T> config;
     config.pcg_exit_tol = sizeof(T) == 8 ? (T)1e-26 : (T)1e-12;
     config.pcg_max_iter = 1000;
-    void* pcg_kernel = (void*)pcg<T, STATE_SIZE, KNOT_POINTS>;
+    void* pcg_kernel = pcg_kernel_for(state_size);
+    if (!pcg_kernel && !use_direct) { fprintf(stderr, "no pcg<> instantiation for state size %u: add one to pcg_kernel_for, or use --direct\n", state_size); return 2; }
     uint32_t pcg_iters, *d_pcg_iters;
     bool pcg_exit, *d_pcg_exit;
     gpuErrchk(hipMalloc(&d_pcg_iters, sizeof(uint32_t)));

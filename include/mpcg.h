@@ -110,11 +110,17 @@ const char *mpcg_build_info(void);
  * (device, knot_points) and per concurrently used stream: calls on the same handle must not overlap on the host
  * side (launch knobs are chosen per call) and their device work must be ordered (one stream, or events) because
  * they share those buffers; different handles are independent. */
-/* state_size = 14 (IIWA-14) is the tuned specialisation and the only one every entry point supports.  Any other
- * 1 <= state_size <= 64 gets a handle whose PCG entry points (mpcg_pcg_solve, mpcg_pcg_solve_ref, mpcg_pcg_solve_f64,
- * mpcg_pcg_solve_ref_f64, mpcg_pcg_lds_bytes, mpcg_check_pcg_occupancy) run a generic, functional kernel (matrices streamed
- * every iteration; "last_kernel_family" = 3) — same layouts with n x n blocks, same semantics; the other entry points
- * return MPCG_ERR_UNSUPPORTED on such a handle. */
+/* state_size = 14 (IIWA-14) with control_size = 7 is the tuned specialisation.  Any other 1 <= state_size <= 64 gets a handle that
+ * serves, with n x n blocks in the same layouts and with the same semantics:
+ *   - the PCG entry points (mpcg_pcg_solve, mpcg_pcg_solve_ref, mpcg_pcg_solve_f64, mpcg_pcg_solve_ref_f64, mpcg_pcg_lds_bytes,
+ *     mpcg_check_pcg_occupancy) through a generic, functional kernel (matrices streamed every iteration; "last_kernel_family" = 3);
+ *   - mpcg_form_schur(_f64), mpcg_compute_dz(_f64), mpcg_block_solve, mpcg_prep_csr and mpcg_bd_to_csr_lowertri through run-time-dimension
+ *     kernels (operands in LDS; the same operation order as the tuned ones, i.e. the same bits as the reference arithmetic restated on the
+ *     CPU), for any 1 <= control_size <= state_size — also control_size != 7 on a 14-state handle.  control_size = 0 or > state_size is
+ *     MPCG_ERR_INVALID.  mpcg_form_schur(_f64) needs one block row's operands, 6 n^2 + 2 n m + 2 m^2 + 12 n + 4 m elements, in 160 KiB of
+ *     LDS: every m <= n <= 32 in both precisions (and e.g. 40 x 10); beyond that it returns MPCG_ERR_UNSUPPORTED.  The others serve every
+ *     such handle.  batch x knot_points < 2^31.
+ * mpcg_bt_spmv, mpcg_pcg_solve_f16, mpcg_generate_kkt and mpcg_probe_hbm_read return MPCG_ERR_UNSUPPORTED on a handle with state_size != 14. */
 int mpcg_create(mpcg_handle **out, int device, uint32_t state_size, uint32_t knot_points, uint32_t max_batch);
 int mpcg_destroy(mpcg_handle *h);
 const char *mpcg_last_error(const mpcg_handle *h);   /* h may be NULL: last error of mpcg_create */
@@ -204,9 +210,13 @@ int mpcg_pcg_solve_f16(mpcg_handle *h,
  * precond = MPCG_PRECOND_JACOBI skips the symmetric-stair completion (:9-137): the off-diagonal
  * blocks of d_Pinv are then left untouched.  The first call allocates a handle-owned staging buffer
  * of max_batch * sizeof(G) (hipMalloc — not stream-ordered); later calls are purely stream-ordered.
+ * Any 1 <= control_size <= state_size (mpcg_create): other shapes than 14 x 7 run the run-time-dimension kernels, whose staging buffer is
+ * sized from the largest control_size the handle has seen — a later call with a larger one re-allocates it (after a device synchronisation,
+ * refused inside a stream capture like every first call).
  *
  * mpcg_compute_dz replaces compute_dz(state_size, control_size, knot_points, d_Ginv_dense, d_C_dense,
- * d_g, d_lambda, d_dz) (include/common/dz.cuh:124-136), batched; d_dz [batch][(n+m)N - m]. */
+ * d_g, d_lambda, d_dz) (include/common/dz.cuh:124-136), batched; d_dz [batch][(n+m)N - m].  Any 1 <= control_size <= state_size <= 64;
+ * pure stream work from the first call on. */
 int mpcg_form_schur(mpcg_handle *h, uint32_t control_size, float *d_G_dense, const float *d_C_dense,
                     const float *d_g, const float *d_c, float *d_S, float *d_Pinv, float *d_gamma,
                     float rho, uint32_t batch, mpcg_precond precond, void *stream);
@@ -222,7 +232,7 @@ int mpcg_compute_dz(mpcg_handle *h, uint32_t control_size, const float *d_Ginv_d
  * (include/qdldl/linsys_setup.cuh:339-351) from a bd-layout S: per trajectory [nnz] floats = mult * (left
  * block, then lower triangle of the diagonal block, row by row).  With the S of mpcg_form_schur (already
  * negated) mult = +1 reproduces the reference's numbers; gamma is shared by both paths.  The CPU LDL^T that consumes
- * them: the reference's own qdldl, or mpcg_ldl_* / mpcg_qdldl_solve_schur below. */
+ * them: the reference's own qdldl, or mpcg_ldl_* / mpcg_qdldl_solve_schur below.  Both serve every state size a handle can have. */
 int mpcg_prep_csr(mpcg_handle *h, int32_t *d_col_ptr, int32_t *d_row_ind, void *stream);
 int mpcg_bd_to_csr_lowertri(mpcg_handle *h, const float *d_S, float *d_val, float mult, uint32_t batch, void *stream);
 
@@ -240,7 +250,8 @@ int mpcg_pcg_solve_ref_f64(mpcg_handle *h, double *d_S, double *d_Pinv, double *
 
 /* The steps either side of the solve for linsys_t = double: mpcg_form_schur / mpcg_compute_dz with every float replaced by double (same
  * layouts, same side effects, same preconditioner choices).  Functional twins — one wavefront per knot, operands in LDS — in the float
- * path's operation order: bit-identical to the oracle's double instantiation (tests/test_gpu_f64.py). */
+ * path's operation order: bit-identical to the oracle's double instantiation (tests/test_gpu_f64.py).  Shapes other than 14 x 7: as the float
+ * entry points (tests/test_gpu_generic_producers.py). */
 int mpcg_form_schur_f64(mpcg_handle *h, uint32_t control_size, double *d_G_dense, const double *d_C_dense,
                         const double *d_g, const double *d_c, double *d_S, double *d_Pinv, double *d_gamma,
                         double rho, uint32_t batch, mpcg_precond precond, void *stream);
@@ -256,8 +267,10 @@ int mpcg_compute_dz_f64(mpcg_handle *h, uint32_t control_size, const double *d_G
  * Block LU without pivoting, pivot blocks eliminated by the reference's Gauss-Jordan scheme; four trajectories per
  * wavefront, serial in the knot index — the throughput solver for batches (1/50 of the flops of 167 PCG iterations),
  * while mpcg_pcg_solve keeps warm starts and the tolerance knob.  fp32 at cond ~1e5: relative error ~3e-4.
- * Scratch (max_batch x N x 210 floats) is owned by the handle; the first call allocates it, later calls are pure
- * stream work (capturable into a graph). */
+ * state_size != 14: one workgroup per trajectory with Delta_k, [U_k | y_k] and L_k in LDS, the same operation order and bits; every
+ * state size a handle can have.  Float only.
+ * Scratch (max_batch x N x (n^2 + n) floats; 210 per knot at n = 14) is owned by the handle; the first call allocates it, later calls are
+ * pure stream work (capturable into a graph). */
 int mpcg_block_solve(mpcg_handle* h, const float* d_S, const float* d_gamma, float* d_lambda, uint32_t batch,
                      void* stream);
 
@@ -373,7 +386,9 @@ int mpcg_qdldl_solve_schur(mpcg_handle *h, mpcg_ldl *l, const float *d_val, cons
  *       kernel closes the seams between chunks; 0: the LDS kernels; same bits), "schur_chunk" (block rows per chunk: 0 = by call size, from one
  *       row per chunk for a single trajectory to 16 at 1024 x 128 knots; 1..2048 forced; same bits), "dz_dpp" (1: mpcg_compute_dz with four knots
  *       per wavefront, 0: one workgroup per knot; same bits), "block_solve_wide" (mpcg_block_solve: 1 one trajectory per wavefront, 0 four, -1 by
- *       batch size; same bits), "kkt_analytic" (mpcg_generate_kkt: 1 = the analytic gradient recursion of the inverse dynamics, the default;
+ *       batch size; same bits), "producers_generic" (0 / 1, default 0; 1: on a 14 x 7 handle mpcg_form_schur(_f64), mpcg_compute_dz(_f64) and
+ *       mpcg_block_solve run the run-time-dimension kernels every other shape gets — same bits, the A/B switch of tests and timings;
+ *       "last_schur_chunk" then reads 0), "kkt_analytic" (mpcg_generate_kkt: 1 = the analytic gradient recursion of the inverse dynamics, the default;
  *       0 = one-sided float64 differences, the checker), "kkt_f32" (round 6; 1 = the analytic kernel with every recursion in float — linsys_t's own
  *       arithmetic, as the reference's GRiD<float> — and TWO knots per lane in packed float: outputs within 5e-6 of the float64 restatement (relative to max(1, |block|); worst of 1024 windows: 4e-6) instead of
  *       2e-7, 1.6x faster than the default on throughput-sized calls (0.204 against 0.330 ms per 1024 x 127 knots; a single trajectory: 20 against 16 us —

@@ -5,4 +5,6 @@ This package is the thin host-side mirror of the reference's interface for that 
 """
 from .solver import PcgSolver, Plant, QdldlSolver, pcg_config, pcgSharedMemSize  # noqa: F401
 
-__all__ = ["PcgSolver", "Plant", "QdldlSolver", "pcg_config", "pcgSharedMemSize"]
+LdlSolver = QdldlSolver     # (the host LDL^T twin under its shorter name)
+
+__all__ = ["PcgSolver", "Plant", "QdldlSolver", "LdlSolver", "pcg_config", "pcgSharedMemSize"]

@@ -1,7 +1,8 @@
 // mpcg_handle.hpp — what the translation units of libmpcg_hip.so share: the handle behind include/mpcg.h, the error convention, the HIP_TRY
 // macro.  The library is four translation units over this header (Makefile: every csrc/*.hip is compiled on its own and linked once):
 //   mpcg_pcg.hip        handle / options / the PCG launch policy and entry points (pcg_*.hip.h kernels)
-//   mpcg_producers.hip  Schur + preconditioner formation, dz recovery, CSR emitter, block-tridiagonal direct solve (schur_*.hip.h, block_solve.hip.h)
+//   mpcg_producers.hip  Schur + preconditioner formation, dz recovery, CSR emitter, block-tridiagonal direct solve (schur_*.hip.h, block_solve.hip.h;
+//                       any other (state_size, control_size) than 14 x 7: schur_generic.hip.h)
 //   mpcg_plant.hip      the robot as data + KKT block assembly (kkt_plant.hip.h)
 //   mpcg_ldl.hip        the host LDL^T twin of the reference's QDLDL path (ldl_host.hpp)
 // Every kernel header is included by exactly one of them (their non-template kernels have external linkage).
@@ -53,6 +54,7 @@ struct mpcg_handle {
     int kkt_f32 = 0;          // mpcg_generate_kkt: 1 = the analytic kernel in float arithmetic (linsys_t's own, as the reference's GRiD<float>); 0 = float64 inside
     int dz_dpp = 1;           // 1: four-knots-per-wavefront dz recovery (schur_walk.hip.h), 0: the one-workgroup-per-knot LDS kernel
     int last_schur_chunk = 0; //   what the last mpcg_form_schur used (0: the LDS kernels)
+    int producers_generic = 0; // 1: form_schur(_f64), compute_dz(_f64) and block_solve of a (14, 7) call run the run-time-dimension kernels (schur_generic.hip.h) every other shape gets
     void* seam_qinv = nullptr;       // schur_walk: one Q^-1 per chunk seam (float or double; ensure_seam_buffer)
     size_t seam_qinv_bytes = 0;
     int cluster = -1;         // workgroups per trajectory of the clustered lane-pair kernel (pcg_lpk_cluster.hip.h): 0 off, -1 auto (N > 128), G > 0 forced
@@ -81,11 +83,11 @@ struct mpcg_handle {
     size_t lam_backup_bytes = 0;
     unsigned long long* cluster64_scratch = nullptr;   // the clustered row-per-lane kernel in double (pcg_rpl_cluster_f64.hip.h): queue | flags | cells, first use
     bool auto_cfg = true;     // launch knobs still at mpcg_create's choice (any valid pcg_* set_option clears this)
-    bool generic = false;     // state_size != 14: only the PCG entry points work, through pcg_generic_kernel
+    bool generic = false;     // state_size != 14: PCG through pcg_generic_kernel, producers / dz / block solve / CSR through schur_generic.hip.h
     int spmv_blocks_per_cu = 3;    // (sweep at 4096 trajectories = 1.2 GB of S, a true HBM stream: profiles/r04_spmv.txt; until round 4: 4)
     int spmv_mfma = 0;        // 1 = the MFMA experiment kernel for mpcg_bt_spmv
-    float* block_scratch = nullptr;  // W_k, z_k of mpcg_block_solve: max_batch x N x 210 floats (first call)
-    float* ginv_scratch = nullptr;   // staging for the in-place G <- G^-1 of mpcg_form_schur
+    float* block_scratch = nullptr;  // W_k, z_k of mpcg_block_solve: max_batch x N x (n^2 + n) floats (first call)
+    float* ginv_scratch = nullptr;   // staging for the in-place G <- G^-1 of mpcg_form_schur: max_batch x ((n^2 + m^2) N - m^2), m the largest control_size seen
     size_t ginv_scratch_floats = 0;
     double* ginv_scratch_f64 = nullptr;   // the same for mpcg_form_schur_f64
     size_t ginv_scratch_f64_elems = 0;

@@ -49,8 +49,9 @@ static void sym_poll(mpcg_handle* h, hipStream_t st = nullptr, bool have_stream 
     }
 }
 
-// n = 14 is the tuned specialisation (every entry point); any other 1 <= n <= 64 is served by the generic PCG kernel only
-// (mpcg_pcg_solve / _ref / _f64: pcg_generic_kernel, pcg_f64.hip.h), as long as its iterate vectors fit the LDS.
+// n = 14 is the tuned specialisation (every entry point); any other 1 <= n <= 64 is served by the generic PCG kernel
+// (mpcg_pcg_solve / _ref / _f64: pcg_generic_kernel, pcg_f64.hip.h), as long as its iterate vectors fit the LDS, and by the
+// run-time-dimension producers of schur_generic.hip.h (mpcg_producers.hip).
 static bool shape_supported(uint32_t n, uint32_t N) { return n == (uint32_t)NS && N >= 2 && N <= 2048; }
 static bool generic_shape_supported(uint32_t n, uint32_t N) {
     return n >= 1 && n <= 64 && n != (uint32_t)NS && N >= 2 && N <= 2048 && pcg_generic_lds_elems((int)N, (int)n) * sizeof(float) <= 160 * 1024;
@@ -159,7 +160,7 @@ int mpcg_create(mpcg_handle** out, int device, uint32_t state_size, uint32_t kno
     const bool generic = generic_shape_supported(state_size, knot_points);
     if (!generic && (!shape_supported(state_size, knot_points) || lds_bytes_for(knot_points, 16) > kLdsMax))
         return fail(nullptr, MPCG_ERR_UNSUPPORTED,
-                    "mpcg_create: state_size = 14 (tuned; every entry point) or 1..64 (generic PCG kernel only), 2 <= knot_points, "
+                    "mpcg_create: state_size = 14 (tuned; every entry point) or 1..64 (run-time-dimension kernels), 2 <= knot_points, "
                     "and the iterate vectors must fit 160 KiB of LDS");
     if (max_batch == 0) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_create: max_batch is 0");
     int ndev = 0;
@@ -308,6 +309,7 @@ int mpcg_set_option(mpcg_handle* h, const char* key, int value) {
     if (!strcmp(key, "schur_dpp")) { h->schur_dpp = value ? 1 : 0; return MPCG_OK; }
     if (!strcmp(key, "schur_chunk")) { if (value < 0 || value > 2048) return fail(h, MPCG_ERR_INVALID, "schur_chunk must be 0 (auto) or 1..2048 block rows"); h->schur_chunk = value; return MPCG_OK; }
     if (!strcmp(key, "dz_dpp")) { h->dz_dpp = value ? 1 : 0; return MPCG_OK; }
+    if (!strcmp(key, "producers_generic")) { h->producers_generic = value ? 1 : 0; return MPCG_OK; }
     if (!strcmp(key, "kkt_analytic")) { h->kkt_analytic = value ? 1 : 0; return MPCG_OK; }
     if (!strcmp(key, "kkt_f32")) { h->kkt_f32 = value == 2 ? 2 : value ? 1 : 0; return MPCG_OK; }
     if (!strcmp(key, "sched_hint")) { h->sched_hint = value ? 1 : 0; return MPCG_OK; }
@@ -345,6 +347,7 @@ int mpcg_get_option(const mpcg_handle* h, const char* key, int* value) {
     if (!strcmp(key, "schur_chunk")) { *value = h->schur_chunk; return MPCG_OK; }
     if (!strcmp(key, "last_schur_chunk")) { *value = h->last_schur_chunk; return MPCG_OK; }
     if (!strcmp(key, "dz_dpp")) { *value = h->dz_dpp; return MPCG_OK; }
+    if (!strcmp(key, "producers_generic")) { *value = h->producers_generic; return MPCG_OK; }
     if (!strcmp(key, "kkt_analytic")) { *value = h->kkt_analytic; return MPCG_OK; }
     if (!strcmp(key, "kkt_f32")) { *value = h->kkt_f32; return MPCG_OK; }
     if (!strcmp(key, "sched_hint")) { *value = h->sched_hint; return MPCG_OK; }

@@ -1,6 +1,7 @@
 // mpcg_producers.hip — C ABI (include/mpcg.h) of the steps either side of the solve: Schur + preconditioner formation, dz
 // recovery (float and linsys_t = double), the CSR emitter of the QDLDL path and the block-tridiagonal direct solve, over the gfx950 kernels
-// in schur_kernels.hip.h / schur_walk.hip.h / schur_walk_f64.hip.h / block_solve.hip.h.
+// in schur_kernels.hip.h / schur_walk.hip.h / schur_walk_f64.hip.h / block_solve.hip.h (the tuned 14 x 7 shape) and schur_generic.hip.h
+// (every other 1 <= control_size <= state_size <= 64, and 14 x 7 under option "producers_generic").
 #include "mpcg_handle.hpp"
 #ifndef MPCG_DZ64_CAPMUL
 #define MPCG_DZ64_CAPMUL 4      // (grid cap of compute_dz_dpp_f64_kernel in units of 64 workgroups per CU; tools/_prof/dz64_ab.py)
@@ -9,6 +10,7 @@
 #include "schur_walk.hip.h"
 #include "schur_walk_f64.hip.h"
 #include "block_solve.hip.h"
+#include "schur_generic.hip.h"
 
 using namespace mpcg;
 
@@ -34,11 +36,84 @@ static int ensure_seam_buffer(mpcg_handle* h, size_t chunks_needed, size_t elem_
     return MPCG_OK;
 }
 
+// ---- the run-time-dimension route (schur_generic.hip.h): any 1 <= control_size <= state_size, (14, 7) only under "producers_generic" ----
+static constexpr size_t kGenLdsMax = 160 * 1024;       // LDS of one CU: what one workgroup's operands may occupy
+
+static inline bool gen_route(const mpcg_handle* h, uint32_t control_size) { return h->generic || control_size != 7 || h->producers_generic; }
+static inline int gen_threads(int n) { return n <= 16 ? 64 : 256; }      // one wavefront up to n = 16; beyond, an n^2 update is >= 4 elements per lane of one
+// workgroups of a grid-stride launch: what the LDS kernels of the 14 x 7 path use (64 per CU), fewer when the LDS holds fewer per CU
+static inline unsigned gen_grid(const mpcg_handle* h, long items, size_t lds_bytes) {
+    const long per_cu = std::min<long>(64, std::max<long>(1, (long)(kGenLdsMax / std::max<size_t>(lds_bytes, 1))));
+    return (unsigned)std::max<long>(1, std::min<long>(items, (long)h->num_cus * per_cu));
+}
+static int gen_check_control(mpcg_handle* h, const char* fn, uint32_t control_size) {
+    if (control_size == 0 || control_size > h->n)
+        return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": control_size must be between 1 and state_size (the n x m workspaces of the formation assume m <= n)");
+    return MPCG_OK;
+}
+template <typename K>
+static int gen_raise_lds(mpcg_handle* h, K kern, size_t lds_bytes) {      // (as the PCG launches: beyond 48 KiB of dynamic LDS the kernel's limit is raised first)
+    if (lds_bytes > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    return MPCG_OK;
+}
+// the G^-1 staging buffer of the generic formation, max_batch x ((n^2 + m^2) N - m^2) elements: grows with the largest control_size seen,
+// outside a stream capture only (an earlier call's kernels may still use the old one: synchronise before it goes)
+template <typename T>
+static int gen_ensure_staging(mpcg_handle* h, T** buf, size_t* have, size_t need, hipStream_t st, const char* fn) {
+    if (*have >= need) return MPCG_OK;
+    { const int rc = alloc_allowed(h, st, fn); if (rc != MPCG_OK) return rc; }
+    if (*buf) {
+        HIP_TRY(h, hipDeviceSynchronize());
+        HIP_TRY(h, hipFree(*buf));
+    }
+    *buf = nullptr; *have = 0;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(buf), need * sizeof(T)));
+    *have = need;
+    return MPCG_OK;
+}
+
+template <typename T>
+static int form_schur_generic(mpcg_handle* h, const char* fn, uint32_t control_size, T* d_G, const T* d_C, const T* d_g, const T* d_c, T* d_S, T* d_Pinv,
+                              T* d_gamma, T rho, uint32_t batch, mpcg_precond precond, T** staging, size_t* staging_elems, hipStream_t st) {
+    const int n = (int)h->n, m = (int)control_size, N = (int)h->N;
+    const size_t lds = gen::form_lds_elems(n, m) * sizeof(T), lds2 = gen::complete_lds_elems(n) * sizeof(T);
+    if (lds > kGenLdsMax)
+        return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": the operands of one block row (" + std::to_string(lds) + " bytes at state_size " + std::to_string(n) +
+                    ", control_size " + std::to_string(m) + ") exceed the LDS limit of 160 KiB (6 n^2 + 2 n m + 2 m^2 + 12 n + 4 m elements)");
+    const size_t Gsz = (size_t)(n * n + m * m) * N - (size_t)m * m;
+    { const int rc = gen_ensure_staging(h, staging, staging_elems, Gsz * h->max_batch, st, fn); if (rc != MPCG_OK) return rc; }
+    h->last_schur_chunk = 0;
+    SchurArgsT<T> a;
+    a.G = d_G; a.C = d_C; a.g = d_g; a.c = d_c; a.S = d_S; a.Pinv = d_Pinv; a.gamma = d_gamma;
+    a.Ginv_scratch = *staging; a.Ginv_out = d_G;
+    a.rho = rho; a.n = n; a.m = m; a.N = N; a.batch = (int)batch; a.ss = precond == MPCG_PRECOND_SS; a.pinv = precond != MPCG_PRECOND_NONE;
+    a.k0_only = 0;
+    const long items = (long)batch * N;
+    const int nt = gen_threads(n);
+    { const int rc = gen_raise_lds(h, gen::form_schur_kernel<T>, lds); if (rc != MPCG_OK) return rc; }
+    hipLaunchKernelGGL(gen::form_schur_kernel<T>, dim3(gen_grid(h, items, lds)), dim3(nt), lds, st, a);
+    HIP_TRY(h, hipGetLastError());
+    { const int rc = gen_raise_lds(h, gen::complete_ss_kernel<T>, lds2); if (rc != MPCG_OK) return rc; }
+    hipLaunchKernelGGL(gen::complete_ss_kernel<T>, dim3(gen_grid(h, items, lds2)), dim3(nt), lds2, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
+
+template <typename T>
+static int compute_dz_generic(mpcg_handle* h, uint32_t control_size, const T* d_Ginv, const T* d_C, const T* d_g, const T* d_lambda, T* d_dz, uint32_t batch,
+                              hipStream_t st) {
+    DzArgsT<T> a{d_Ginv, d_C, d_g, d_lambda, d_dz, (int)h->n, (int)control_size, (int)h->N, (int)batch};
+    const int w = (int)h->n + (int)control_size, nt = w <= 64 ? 64 : 128, kpw = nt / w;
+    const long groups = ((long)batch * h->N + kpw - 1) / kpw;
+    hipLaunchKernelGGL(gen::compute_dz_kernel<T>, dim3(gen_grid(h, groups, 0)), dim3(nt), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
+
 extern "C" {
 
 int mpcg_block_solve(mpcg_handle* h, const float* d_S, const float* d_gamma, float* d_lambda, uint32_t batch, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
-    if (h->generic) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_block_solve: state_size = 14 only (other state sizes: PCG entry points through the generic kernel)");
     if (!d_S || !d_gamma || !d_lambda) return fail(h, MPCG_ERR_INVALID, "mpcg_block_solve: null device pointer");
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_block_solve: batch exceeds max_batch");
@@ -48,7 +123,15 @@ int mpcg_block_solve(mpcg_handle* h, const float* d_S, const float* d_gamma, flo
     }
     if (!h->block_scratch)
         HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->block_scratch),
-                             (size_t)h->max_batch * h->N * (14 * 14 + 14) * sizeof(float)));       // W_k (14 x 14) + z_k per knot
+                             (size_t)h->max_batch * h->N * ((size_t)h->n * h->n + h->n) * sizeof(float)));       // W_k (n x n) + z_k per knot
+    if (h->generic || h->producers_generic) {         // any state size: one workgroup per trajectory, operands in LDS (schur_generic.hip.h)
+        gen::BlockSolveGenArgs ga{d_S, d_gamma, d_lambda, h->block_scratch, (int)h->n, (int)h->N, (int)batch};
+        const size_t lds = gen::block_solve_lds_elems((int)h->n) * sizeof(float);
+        { const int rc = gen_raise_lds(h, gen::bt_block_solve_kernel, lds); if (rc != MPCG_OK) return rc; }
+        hipLaunchKernelGGL(gen::bt_block_solve_kernel, dim3(batch), dim3(gen_threads((int)h->n)), lds, static_cast<hipStream_t>(stream), ga);
+        HIP_TRY(h, hipGetLastError());
+        return MPCG_OK;
+    }
     BlockSolveArgs a;
     a.S = d_S; a.gamma = d_gamma; a.lambda = d_lambda; a.work = h->block_scratch; a.N = (int)h->N; a.batch = (int)batch;
     // few trajectories: one per wavefront (columns dealt over the four DPP rows, ~2.5x shorter critical path);
@@ -65,16 +148,18 @@ int mpcg_form_schur(mpcg_handle* h, uint32_t control_size, float* d_G_dense, con
                     const float* d_c, float* d_S, float* d_Pinv, float* d_gamma, float rho, uint32_t batch,
                     mpcg_precond precond, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
-    if (h->generic) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_form_schur: state_size = 14 only (other state sizes: PCG entry points through the generic kernel)");
     if (!d_G_dense || !d_C_dense || !d_g || !d_c || !d_S || (!d_Pinv && precond != MPCG_PRECOND_NONE) || !d_gamma)
         return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur: null device pointer");
-    if (control_size != 7) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_form_schur: control_size must be 7 (IIWA-14)");
+    { const int rc = gen_check_control(h, "mpcg_form_schur", control_size); if (rc != MPCG_OK) return rc; }
     if (precond != MPCG_PRECOND_NONE && precond != MPCG_PRECOND_JACOBI && precond != MPCG_PRECOND_SS)
         return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur: bad preconditioner");
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur: batch exceeds max_batch");
     if ((uint64_t)batch * h->N >= (1ull << 31)) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_form_schur: batch * knot_points must stay below 2^31");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (gen_route(h, control_size))
+        return form_schur_generic<float>(h, "mpcg_form_schur", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, rho, batch, precond,
+                                         &h->ginv_scratch, &h->ginv_scratch_floats, static_cast<hipStream_t>(stream));
     const int n = (int)h->n, m = (int)control_size, N = (int)h->N;
     const size_t Gsz = (size_t)(n * n + m * m) * N - m * m;
     // Register-resident formation (schur_walk.hip.h): a 16-lane row walks a chunk of L consecutive block rows, a second kernel closes the
@@ -141,13 +226,13 @@ int mpcg_form_schur(mpcg_handle* h, uint32_t control_size, float* d_G_dense, con
 int mpcg_compute_dz(mpcg_handle* h, uint32_t control_size, const float* d_Ginv_dense, const float* d_C_dense,
                     const float* d_g, const float* d_lambda, float* d_dz, uint32_t batch, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
-    if (h->generic) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_compute_dz: state_size = 14 only (other state sizes: PCG entry points through the generic kernel)");
     if (!d_Ginv_dense || !d_C_dense || !d_g || !d_lambda || !d_dz)
         return fail(h, MPCG_ERR_INVALID, "mpcg_compute_dz: null device pointer");
-    if (control_size != 7) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_compute_dz: control_size must be 7 (IIWA-14)");
+    { const int rc = gen_check_control(h, "mpcg_compute_dz", control_size); if (rc != MPCG_OK) return rc; }
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_dz: batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (gen_route(h, control_size)) return compute_dz_generic<float>(h, control_size, d_Ginv_dense, d_C_dense, d_g, d_lambda, d_dz, batch, static_cast<hipStream_t>(stream));
     DzArgs a{d_Ginv_dense, d_C_dense, d_g, d_lambda, d_dz, (int)h->n, (int)control_size, (int)h->N, (int)batch};
     long blocks = (long)batch * h->N;
     const long cap = (long)h->num_cus * 64;
@@ -172,16 +257,18 @@ int mpcg_form_schur_f64(mpcg_handle* h, uint32_t control_size, double* d_G_dense
                         const double* d_c, double* d_S, double* d_Pinv, double* d_gamma, double rho, uint32_t batch,
                         mpcg_precond precond, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
-    if (h->generic) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_form_schur_f64: state_size = 14 only (other state sizes: PCG entry points through the generic kernel)");
     if (!d_G_dense || !d_C_dense || !d_g || !d_c || !d_S || (!d_Pinv && precond != MPCG_PRECOND_NONE) || !d_gamma)
         return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur_f64: null device pointer");
-    if (control_size != 7) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_form_schur_f64: control_size must be 7 (IIWA-14)");
+    { const int rc = gen_check_control(h, "mpcg_form_schur_f64", control_size); if (rc != MPCG_OK) return rc; }
     if (precond != MPCG_PRECOND_NONE && precond != MPCG_PRECOND_JACOBI && precond != MPCG_PRECOND_SS)
         return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur_f64: bad preconditioner");
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur_f64: batch exceeds max_batch");
     if ((uint64_t)batch * h->N >= (1ull << 31)) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_form_schur_f64: batch * knot_points must stay below 2^31");     // (as mpcg_form_schur: the LDS kernels index knots with int)
     HIP_TRY(h, hipSetDevice(h->device));
+    if (gen_route(h, control_size))
+        return form_schur_generic<double>(h, "mpcg_form_schur_f64", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, rho, batch, precond,
+                                          &h->ginv_scratch_f64, &h->ginv_scratch_f64_elems, static_cast<hipStream_t>(stream));
     const int n = (int)h->n, m = (int)control_size, N = (int)h->N;
     const size_t Gsz = (size_t)(n * n + m * m) * N - m * m;
     // Round 5: the register-resident formation in double (schur_walk_f64.hip.h) — the float path's design, chunk policy and seam buffer; its
@@ -244,13 +331,13 @@ int mpcg_form_schur_f64(mpcg_handle* h, uint32_t control_size, double* d_G_dense
 int mpcg_compute_dz_f64(mpcg_handle* h, uint32_t control_size, const double* d_Ginv_dense, const double* d_C_dense,
                         const double* d_g, const double* d_lambda, double* d_dz, uint32_t batch, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
-    if (h->generic) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_compute_dz_f64: state_size = 14 only (other state sizes: PCG entry points through the generic kernel)");
     if (!d_Ginv_dense || !d_C_dense || !d_g || !d_lambda || !d_dz)
         return fail(h, MPCG_ERR_INVALID, "mpcg_compute_dz_f64: null device pointer");
-    if (control_size != 7) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_compute_dz_f64: control_size must be 7 (IIWA-14)");
+    { const int rc = gen_check_control(h, "mpcg_compute_dz_f64", control_size); if (rc != MPCG_OK) return rc; }
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_dz_f64: batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
+    if (gen_route(h, control_size)) return compute_dz_generic<double>(h, control_size, d_Ginv_dense, d_C_dense, d_g, d_lambda, d_dz, batch, static_cast<hipStream_t>(stream));
     DzArgsT<double> a{d_Ginv_dense, d_C_dense, d_g, d_lambda, d_dz, (int)h->n, (int)control_size, (int)h->N, (int)batch};
     long blocks = (long)batch * h->N;
     const long cap = (long)h->num_cus * 64;
@@ -272,7 +359,6 @@ int mpcg_compute_dz_f64(mpcg_handle* h, uint32_t control_size, const double* d_G
 
 int mpcg_prep_csr(mpcg_handle* h, int32_t* d_col_ptr, int32_t* d_row_ind, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
-    if (h->generic) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_prep_csr: state_size = 14 only (other state sizes: PCG entry points through the generic kernel)");
     if (!d_col_ptr || !d_row_ind) return fail(h, MPCG_ERR_INVALID, "mpcg_prep_csr: null device pointer");
     HIP_TRY(h, hipSetDevice(h->device));
     hipLaunchKernelGGL(prep_csr_kernel, dim3(h->N), dim3(SCH_THREADS), 0, static_cast<hipStream_t>(stream), (int)h->n, (int)h->N,
@@ -283,7 +369,6 @@ int mpcg_prep_csr(mpcg_handle* h, int32_t* d_col_ptr, int32_t* d_row_ind, void* 
 
 int mpcg_bd_to_csr_lowertri(mpcg_handle* h, const float* d_S, float* d_val, float mult, uint32_t batch, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
-    if (h->generic) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_bd_to_csr_lowertri: state_size = 14 only (other state sizes: PCG entry points through the generic kernel)");
     if (!d_S || !d_val) return fail(h, MPCG_ERR_INVALID, "mpcg_bd_to_csr_lowertri: null device pointer");
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_bd_to_csr_lowertri: batch exceeds max_batch");

@@ -1,0 +1,420 @@
+// schur_generic.hip.h — the steps either side of the PCG for ANY state and control size (1 <= m <= n <= 64), gfx950 HIP:
+//   gen::form_schur_kernel + gen::complete_ss_kernel   (G, C, g, c, rho) -> (S, Pinv, gamma), G <- G^-1
+//   gen::compute_dz_kernel                             dz = G^-1 (g - C^T lambda)
+//   gen::bt_block_solve_kernel                         block-tridiagonal direct solve of S lambda = gamma (float)
+// Semantics, operation order and therefore BITS are those of schur_kernels.hip.h / block_solve.hip.h (contraction off, sequential inner
+// products, pivot-free Gauss-Jordan: pivot row scaled by 1 / pivot, then eliminated from every other row); only the dimensions are
+// run-time values and the operands live in DYNAMIC LDS sized from (n, m).  The tuned 14 x 7 kernels stay what (14, 7) runs by default;
+// option "producers_generic" = 1 sends that shape here too (the A/B switch of the tests).
+//
+// Mapping.  A workgroup of blockDim.x = 64 (n <= 16) or 256 threads owns one block row (formation, completion), a few knots (dz) or one
+// trajectory (block solve).  Over an operand with `rows` rows a thread keeps ONE row r = tid % rows and walks the columns c0, c0 + cs, ...
+// (cs = blockDim.x / rows; the blockDim.x % rows lanes left over idle): the integer division by a run-time dimension happens once per
+// kernel, not once per element, and every bulk LDS access is unit-stride over the lanes — A[r + t * rows] is consecutive (lanes of another
+// column repeat the address: a broadcast), B[t + c * n] is one address per column group, the transposed operand B[c + t * k] of the
+// transB products is consecutive in c.  So power-of-two n (power-of-two column strides) costs nothing there and the leading dimensions
+// are NOT padded; padding them would put 2-way conflicts into exactly these bulk accesses (r + c * (n + 1) wraps the 32 banks inside a
+// half-wave).  The two strided accesses that remain: the pivot row of the Gauss-Jordan step (n elements per pivot, against 2 n^2 in the
+// update) and the transposition of phi, which walks the columns skewed by the row ((q + r) mod n) so that read and write both spread
+// over the banks.
+#pragma once
+#include "schur_kernels.hip.h"
+
+namespace mpcg {
+namespace gen {
+
+#pragma clang fp contract(off)
+
+struct Lane { int r, c0, cs; };      // this thread's row, first column and column step over an operand with `rows` rows (idle: c0 beyond any column)
+__device__ __forceinline__ Lane lane_of(int rows) {
+    Lane l;
+    l.cs = (int)blockDim.x / rows;
+    l.r = (int)threadIdx.x % rows;
+    l.c0 = (int)threadIdx.x / rows;
+    if (l.c0 >= l.cs) l.c0 = 1 << 20;
+    return l;
+}
+
+template <typename T>
+__device__ __forceinline__ void g_copy(int cnt, const T* src, T* dst, T mult = (T)1) {
+    for (int e = threadIdx.x; e < cnt; e += blockDim.x) dst[e] = src[e] * mult;
+}
+// C[m x k] = mult * (A[m x n] * B[n x k]) (column-major); TB: B stored k x n.  Sequential over n.  l = lane_of(m).
+template <bool TB, typename T>
+__device__ __forceinline__ void g_gemm(const Lane l, int m, int n, int k, const T* A, const T* B, T* C, T mult = (T)1) {
+    for (int c = l.c0; c < k; c += l.cs) {
+        T acc = 0;
+#pragma unroll 4
+        for (int t = 0; t < n; ++t) acc += A[l.r + t * m] * (TB ? B[c + t * k] : B[t + c * n]);
+        C[l.r + c * m] = acc * mult;
+    }
+}
+template <typename T>
+__device__ __forceinline__ void g_matvec(int rows, int cols, const T* M, const T* v, T* out) {
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) {
+        T acc = 0;
+        for (int c = 0; c < cols; ++c) acc += M[r + c * rows] * v[c];
+        out[r] = acc;
+    }
+}
+// one Gauss-Jordan step on [A | I] (pivot piv < n): scratch sc = {scaled pivot row of A, of I, pivot column}, filled by g_gj_pivot
+template <typename T>
+__device__ __forceinline__ void g_gj_pivot(int n, int piv, int c, const T* A, const T* I, T* sc) {
+    const T pinv = (T)1 / A[piv + piv * n];
+    sc[c] = A[piv + c * n] * pinv;
+    sc[n + c] = I[piv + c * n] * pinv;
+    sc[2 * n + c] = A[c + piv * n];
+}
+template <typename T>
+__device__ __forceinline__ void g_gj_update(const Lane l, int n, int piv, T* A, T* I, const T* sc) {
+    const T f = sc[2 * n + l.r];
+    for (int c = l.c0; c < n; c += l.cs) {
+        const int e = l.r + c * n;
+        if (l.r == piv) { A[e] = sc[c]; I[e] = sc[n + c]; }
+        else { A[e] -= f * sc[c]; I[e] -= f * sc[n + c]; }
+    }
+}
+// Gauss-Jordan on [A | I] without pivoting: A destroyed, Ainv out.  scr: 3 n.  Ends on a barrier.
+template <typename T>
+__device__ __forceinline__ void g_invert(const Lane l, int n, T* A, T* Ainv, T* scr) {
+    for (int e = threadIdx.x; e < n * n; e += blockDim.x) Ainv[e] = (T)0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += blockDim.x) Ainv[i + i * n] = (T)1;
+    __syncthreads();
+    for (int piv = 0; piv < n; ++piv) {
+        for (int c = threadIdx.x; c < n; c += blockDim.x) g_gj_pivot(n, piv, c, A, Ainv, scr);
+        __syncthreads();
+        g_gj_update(l, n, piv, A, Ainv, scr);
+        __syncthreads();
+    }
+}
+// The three inversions of a block row (Q_k, Q_{k+1}: n x n; R_k: m x m, m <= n) advanced in lock-step, as w_invert3: the arithmetic of
+// three g_invert calls per element, a third of the barriers.  m = n is the boundary case (every pivot step touches all three).
+// scr: 3 (2 n + m).  Ends on a barrier.
+template <typename T>
+__device__ __forceinline__ void g_invert3(const Lane ln, const Lane lm, int n, T* A1, T* I1, T* A2, T* I2, int m, T* A3, T* I3, T* scr) {
+    const int nn = n * n, mm = m * m;
+    for (int e = threadIdx.x; e < 2 * nn + mm; e += blockDim.x) {
+        if (e < nn) I1[e] = (T)0;
+        else if (e < 2 * nn) I2[e - nn] = (T)0;
+        else I3[e - 2 * nn] = (T)0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * n + m; i += blockDim.x) {
+        if (i < n) I1[i + i * n] = (T)1;
+        else if (i < 2 * n) I2[(i - n) + (i - n) * n] = (T)1;
+        else I3[(i - 2 * n) + (i - 2 * n) * m] = (T)1;
+    }
+    __syncthreads();
+    T* s1 = scr;
+    T* s2 = s1 + 3 * n;
+    T* s3 = s2 + 3 * n;
+    for (int piv = 0; piv < n; ++piv) {
+        for (int c = threadIdx.x; c < 2 * n + m; c += blockDim.x) {
+            if (c < n) g_gj_pivot(n, piv, c, A1, I1, s1);
+            else if (c < 2 * n) g_gj_pivot(n, piv, c - n, A2, I2, s2);
+            else if (piv < m) g_gj_pivot(m, piv, c - 2 * n, A3, I3, s3);
+        }
+        __syncthreads();
+        g_gj_update(ln, n, piv, A1, I1, s1);
+        g_gj_update(ln, n, piv, A2, I2, s2);
+        if (piv < m) g_gj_update(lm, m, piv, A3, I3, s3);
+        __syncthreads();
+    }
+}
+
+// LDS working set of the formation kernel in elements: Qk Qki Qp Qpi Ak phi (n x n), Bk BR (n x m), Rk Rki (m x m), six n-vectors
+// (gam v1 v2 qk qp + one spare), rk, the Gauss-Jordan scratch 3 (2 n + m).  theta, theta^-1 and phi^T reuse the blocks the inversions destroyed.
+__host__ __device__ constexpr size_t form_lds_elems(int n, int m) {
+    return (size_t)6 * n * n + (size_t)2 * n * m + (size_t)2 * m * m + (size_t)6 * n + m + (size_t)3 * (2 * n + m);
+}
+__host__ __device__ constexpr size_t complete_lds_elems(int n) { return (size_t)6 * n * n; }
+
+// block row k of trajectory b: S[k,0], S[k,1], S[k-1,2], Pinv[k,1], gamma[k]; inverses -> staging buffer (form_schur_kernel of schur_kernels.hip.h)
+template <typename T>
+__global__ __launch_bounds__(256) void form_schur_kernel(SchurArgsT<T> a) {
+    extern __shared__ __align__(16) unsigned char gen_smem[];
+    T* sm = reinterpret_cast<T*>(gen_smem);
+    const int n = a.n, m = a.m, N = a.N;
+    const int nn = n * n, mm = m * m, nm = n * m;
+    const int Gset = nn + mm, Cset = nn + nm, gset = n + m;
+    const size_t Gsz = (size_t)Gset * N - mm, Csz = (size_t)Cset * (N - 1), gsz = (size_t)gset * N - m;
+    T *Qk = sm, *Qki = Qk + nn, *Qp = Qki + nn, *Qpi = Qp + nn, *Ak = Qpi + nn, *phi = Ak + nn, *Bk = phi + nn, *BR = Bk + nm,
+      *Rk = BR + nm, *Rki = Rk + mm, *gam = Rki + mm, *v1 = gam + n, *v2 = v1 + n, *qk = v2 + n, *qp = qk + n, *rk = qp + 2 * n, *scr = rk + m;
+    T *theta = Qk, *thetaInv = Qp, *phiT = Ak;               // (free once the inversions / the theta products are through)
+    const int nt = blockDim.x, tid = threadIdx.x;
+    const Lane ln = lane_of(n), lm = lane_of(m);
+
+    for (long item = blockIdx.x; item < (long)a.batch * N; item += gridDim.x) {
+        const int b = (int)(item / N), k = (int)(item % N);
+        const T* G = a.G + (size_t)b * Gsz;
+        const T* C = a.C + (size_t)b * Csz;
+        const T* g = a.g + (size_t)b * gsz;
+        const T* c = a.c + (size_t)b * n * N;
+        T* S = a.S + (size_t)b * 3 * nn * N;
+        T* P = a.Pinv + (size_t)b * 3 * nn * N;
+        T* gamma = a.gamma + (size_t)b * n * N;
+        T* Gs = a.Ginv_scratch + (size_t)b * Gsz;
+        __syncthreads();
+        if (k == 0) {
+            g_copy(nn, G, Qk);
+            g_copy(n, g, qk);
+            __syncthreads();
+            for (int i = tid; i < n; i += nt) Qk[i + i * n] += a.rho;
+            __syncthreads();
+            if (a.pinv) g_copy(nn, Qk, P + nn, (T)-1);                   // Pinv[0,1] = -(Q0 + rho I)
+            __syncthreads();
+            g_invert(ln, n, Qk, Qki, scr);
+            g_copy(nn, Qki, S + nn, (T)-1);                              // S[0,1] = -Q0^-1
+            g_matvec(n, n, Qki, qk, v1);
+            __syncthreads();
+            for (int i = tid; i < n; i += nt) gamma[i] = -v1[i];
+            continue;
+        }
+        g_copy(nn, C + (size_t)(k - 1) * Cset, Ak);
+        g_copy(nm, C + (size_t)(k - 1) * Cset + nn, Bk);
+        g_copy(nn, G + (size_t)(k - 1) * Gset, Qk);
+        g_copy(mm, G + (size_t)(k - 1) * Gset + nn, Rk);
+        g_copy(nn, G + (size_t)k * Gset, Qp);
+        g_copy(n, g + (size_t)(k - 1) * gset, qk);
+        g_copy(m, g + (size_t)(k - 1) * gset + n, rk);
+        g_copy(n, g + (size_t)k * gset, qp);
+        __syncthreads();
+        for (int i = tid; i < n; i += nt) { Qk[i + i * n] += a.rho; Qp[i + i * n] += a.rho; }
+        for (int i = tid; i < m; i += nt) Rk[i + i * m] += a.rho;
+        __syncthreads();
+        g_invert3(ln, lm, n, Qk, Qki, Qp, Qpi, m, Rk, Rki, scr);
+        g_gemm<false>(ln, n, n, n, Ak, Qki, phi);                        // phi = Abar Qi
+        g_gemm<false>(ln, n, m, m, Bk, Rki, BR);                         // Bbar Ri
+        g_matvec(n, n, Qpi, qp, gam);
+        __syncthreads();
+        for (int i = tid; i < n; i += nt) gam[i] -= c[(size_t)k * n + i];
+        g_matvec(n, n, phi, qk, v1);
+        g_matvec(n, m, BR, rk, v2);
+        __syncthreads();
+        for (int i = tid; i < n; i += nt) gam[i] += v2[i] + v1[i];
+        // theta = phi Abar^T, += Qpi, += (Bbar Ri) Bbar^T: one thread owns element (r, c) of all three terms, so the two products stay in
+        // registers; S[k,0] = -phi and S[k,1] = -theta leave from here (theta itself lands in the block the inversion of Q_k destroyed)
+        {
+            T* S0 = S + (size_t)k * 3 * nn;
+            for (int cc = ln.c0; cc < n; cc += ln.cs) {
+                T acc = 0, acc2 = 0;
+#pragma unroll 4
+                for (int t = 0; t < n; ++t) acc += phi[ln.r + t * n] * Ak[cc + t * n];
+#pragma unroll 4
+                for (int t = 0; t < m; ++t) acc2 += BR[ln.r + t * n] * Bk[cc + t * n];
+                const int e = ln.r + cc * n;
+                T th = acc;
+                th += Qpi[e];
+                th += acc2;
+                theta[e] = th;
+                S0[e] = phi[e] * (T)-1;
+                S0[nn + e] = th * (T)-1;
+            }
+        }
+        __syncthreads();
+        for (int q = ln.c0; q < n; q += ln.cs) {                           // phi^T, columns skewed by the row
+            int j = q + ln.r;
+            if (j >= n) j -= n;
+            phiT[ln.r + j * n] = phi[j + ln.r * n];
+        }
+        for (int i = tid; i < n; i += nt) gamma[(size_t)k * n + i] = -gam[i];
+        g_copy(nn, Qki, Gs + (size_t)(k - 1) * Gset);                    // G <- G^-1 (via the staging buffer)
+        g_copy(mm, Rki, Gs + (size_t)(k - 1) * Gset + nn);
+        if (k == N - 1) g_copy(nn, Qpi, Gs + (size_t)k * Gset);
+        __syncthreads();
+        g_copy(nn, phiT, S + (size_t)(k - 1) * 3 * nn + 2 * nn, (T)-1);   // S[k-1,2] = -phi^T
+        if (a.pinv) {
+            g_invert(ln, n, theta, thetaInv, scr);
+            g_copy(nn, thetaInv, P + (size_t)k * 3 * nn + nn, (T)-1);     // Pinv[k,1]
+        }
+    }
+}
+
+// symmetric-stair completion + publication of G^-1 (complete_ss_kernel of schur_kernels.hip.h).  phi_{k+1}^T enters its product as the
+// transposed operand (B stored k x n): the same sums in the same order as a transposed load followed by a plain product.
+template <typename T>
+__global__ __launch_bounds__(256) void complete_ss_kernel(SchurArgsT<T> a) {
+    extern __shared__ __align__(16) unsigned char gen_smem[];
+    T* sm = reinterpret_cast<T*>(gen_smem);
+    const int n = a.n, m = a.m, N = a.N, nn = n * n, mm = m * m;
+    const int Gset = nn + mm;
+    const size_t Gsz = (size_t)Gset * N - mm;
+    T *Dk = sm, *Dm = Dk + nn, *Dp = Dm + nn, *L = Dp + nn, *Rn = L + nn, *t1 = Rn + nn;
+    const Lane ln = lane_of(n);
+    for (long item = blockIdx.x; item < (long)a.batch * N; item += gridDim.x) {
+        const int b = (int)(item / N), k = (int)(item % N);
+        const T* S = a.S + (size_t)b * 3 * nn * N;
+        T* P = a.Pinv + (size_t)b * 3 * nn * N;
+        const int cnt = (k < N - 1) ? Gset : nn;
+        g_copy(cnt, a.Ginv_scratch + (size_t)b * Gsz + (size_t)k * Gset, a.Ginv_out + (size_t)b * Gsz + (size_t)k * Gset);
+        if (!a.ss) continue;
+        __syncthreads();
+        g_copy(nn, P + (size_t)k * 3 * nn + nn, Dk);
+        if (k > 0) {
+            g_copy(nn, S + (size_t)k * 3 * nn, L);
+            g_copy(nn, P + (size_t)(k - 1) * 3 * nn + nn, Dm);
+        }
+        if (k < N - 1) {
+            g_copy(nn, S + (size_t)(k + 1) * 3 * nn, Rn);                // phi_{k+1} as stored
+            g_copy(nn, P + (size_t)(k + 1) * 3 * nn + nn, Dp);
+        }
+        __syncthreads();
+        if (k > 0) {
+            g_gemm<false>(ln, n, n, n, Dk, L, t1);
+            __syncthreads();
+            g_gemm<false>(ln, n, n, n, t1, Dm, P + (size_t)k * 3 * nn, (T)-1);              // Pinv[k,0]
+            __syncthreads();
+        }
+        if (k < N - 1) {
+            g_gemm<true>(ln, n, n, n, Dk, Rn, t1);
+            __syncthreads();
+            g_gemm<false>(ln, n, n, n, t1, Dp, P + (size_t)k * 3 * nn + 2 * nn, (T)-1);     // Pinv[k,2]
+        }
+    }
+}
+
+// dz recovery (compute_dz_kernel of schur_kernels.hip.h): one lane per element of dz_k, blockDim.x / (n + m) knots per workgroup
+// (every output is one sequential inner product, so a knot cannot use more than n + m lanes).  blockDim.x >= n + m.
+template <typename T>
+__global__ __launch_bounds__(128) void compute_dz_kernel(DzArgsT<T> a) {
+    __shared__ T sm[128];
+    const int n = a.n, m = a.m, N = a.N, nn = n * n, mm = m * m, nm = n * m, w = n + m;
+    const size_t Gsz = (size_t)(nn + mm) * N - mm, Csz = (size_t)(nn + nm) * (N - 1), gsz = (size_t)w * N - m;
+    const int kpw = (int)blockDim.x / w;                                  // knots per workgroup
+    const int slot = (int)threadIdx.x / w, i = (int)threadIdx.x % w;
+    T* tv = sm + slot * w;                                                // [0, n): state part, [n, n + m): control part
+    const long total = (long)a.batch * N, groups = (total + kpw - 1) / kpw;
+    for (long grp = blockIdx.x; grp < groups; grp += gridDim.x) {
+        const long item = grp * kpw + slot;
+        const bool live = slot < kpw && item < total;
+        const int b = live ? (int)(item / N) : 0, k = live ? (int)(item % N) : 0;
+        const T* Qi = a.Ginv + (size_t)b * Gsz + (size_t)k * (nn + mm);
+        const T* Ck = a.C + (size_t)b * Csz + (size_t)k * (nn + nm);
+        const T* gk = a.g + (size_t)b * gsz + (size_t)k * w;
+        const T* lam = a.lambda + (size_t)b * n * N;
+        T* dz = a.dz + (size_t)b * gsz + (size_t)k * w;
+        const bool ctl = i >= n;                                          // control rows exist for k < N - 1 only
+        const bool on = live && (!ctl || k != N - 1);
+        __syncthreads();
+        if (on) {
+            T acc = 0;
+            if (k != N - 1) {
+                const T* col = Ck + (size_t)i * n;                        // column i of [Abar | Bbar]
+                const T* ln = lam + (size_t)(k + 1) * n;
+                for (int t = 0; t < n; ++t) acc += col[t] * ln[t];
+            }
+            tv[i] = ctl ? gk[i] - acc : gk[i] - (lam[(size_t)k * n + i] + acc);
+        }
+        __syncthreads();
+        if (on) {
+            T acc = 0;
+            if (!ctl) for (int c = 0; c < n; ++c) acc += Qi[i + c * n] * tv[c];
+            else for (int c = 0; c < m; ++c) acc += Qi[nn + (i - n) + c * m] * tv[n + c];
+            dz[i] = acc;
+        }
+    }
+}
+
+// Block-tridiagonal direct solve for any n (bt_block_solve_kernel of block_solve.hip.h): one workgroup per trajectory, serial in the
+// knot index.  Delta_k, [U_k | y_k] (double-buffered: the eliminated block is W_k, the next knot's operand), L_k in LDS; the L W product
+// stays in registers (thread (r, c) owns Delta(r, c)).  W_k, z_k -> work for the back substitution.
+//   Delta_0 = D_0, y_0 = gamma_0;  k >= 1: Delta_k = D_k - L_k W_{k-1}, y_k = gamma_k - L_k z_{k-1};  [Delta_k | U_k y_k] -> [I | W_k z_k] by one
+//   Gauss-Jordan elimination (columns at or left of the pivot untouched);  lambda_{N-1} = z_{N-1}, lambda_k = z_k - W_k lambda_{k+1}.
+struct BlockSolveGenArgs {
+    const float* S; const float* gamma; float* lambda; float* work;       // work: [batch][N][n * n + n]
+    int n; int N; int batch;
+};
+__host__ __device__ constexpr size_t block_solve_lds_elems(int n) { return (size_t)4 * n * n + (size_t)5 * n + 4; }
+
+__global__ __launch_bounds__(256) void bt_block_solve_kernel(BlockSolveGenArgs a) {
+    typedef float T;
+    extern __shared__ __align__(16) unsigned char gen_smem[];
+    T* sm = reinterpret_cast<T*>(gen_smem);
+    const int n = a.n, N = a.N, nn = n * n, WS = nn + n;
+    T *Delta = sm, *Lb = Delta + nn, *cur = Lb + nn, *prev = cur + nn, *y = prev + nn, *zp = y + n, *prowD = zp + n, *prowB = prowD + n,
+      *pcol = prowB + n, *py = pcol + n;
+    const int nt = blockDim.x, tid = threadIdx.x;
+    const Lane ln = lane_of(n);
+    for (long b = blockIdx.x; b < a.batch; b += gridDim.x) {
+        const T* S = a.S + (size_t)b * 3 * nn * N;
+        const T* gamma = a.gamma + (size_t)b * n * N;
+        T* lambda = a.lambda + (size_t)b * n * N;
+        T* work = a.work + (size_t)b * N * WS;
+        for (int k = 0; k < N; ++k) {
+            const T* blk = S + (size_t)k * 3 * nn;
+            __syncthreads();
+            g_copy(nn, blk + nn, Delta);
+            if (k < N - 1) g_copy(nn, blk + 2 * nn, cur);
+            else for (int e = tid; e < nn; e += nt) cur[e] = (T)0;          // the last block row carries y only
+            if (k > 0) g_copy(nn, blk, Lb);
+            for (int i = tid; i < n; i += nt) y[i] = gamma[(size_t)k * n + i];
+            __syncthreads();
+            if (k > 0) {
+                for (int c = ln.c0; c < n; c += ln.cs) {                   // Delta = D - L W_{k-1}
+                    T acc = 0;
+#pragma unroll 4
+                    for (int t = 0; t < n; ++t) acc += Lb[ln.r + t * n] * prev[t + c * n];
+                    const int e = ln.r + c * n;
+                    Delta[e] = Delta[e] - acc;
+                }
+                for (int r = tid; r < n; r += nt) {                        // y -= L z_{k-1}
+                    T acc = 0;
+                    for (int c = 0; c < n; ++c) acc += Lb[r + c * n] * zp[c];
+                    y[r] = y[r] - acc;
+                }
+                __syncthreads();
+            }
+            for (int piv = 0; piv < n; ++piv) {
+                const int right = n - piv - 1;                             // columns of Delta still alive
+                for (int c = tid; c < n; c += nt) {
+                    const T pinv = (T)1 / Delta[piv + piv * n];
+                    if (c > piv) prowD[c] = Delta[piv + c * n] * pinv;
+                    prowB[c] = cur[piv + c * n] * pinv;
+                    pcol[c] = Delta[c + piv * n];
+                    if (c == 0) py[0] = y[piv] * pinv;
+                }
+                __syncthreads();
+                const T f = pcol[ln.r];
+                const bool isp = ln.r == piv;
+                for (int cc = ln.c0; cc < right + n + 1; cc += ln.cs) {
+                    if (cc < right) {
+                        const int c = piv + 1 + cc, e = ln.r + c * n;
+                        Delta[e] = isp ? prowD[c] : Delta[e] - f * prowD[c];
+                    } else if (cc < right + n) {
+                        const int c = cc - right, e = ln.r + c * n;
+                        cur[e] = isp ? prowB[c] : cur[e] - f * prowB[c];
+                    } else {
+                        y[ln.r] = isp ? py[0] : y[ln.r] - f * py[0];
+                    }
+                }
+                __syncthreads();
+            }
+            for (int i = tid; i < n; i += nt) { const T z = y[i]; work[(size_t)k * WS + nn + i] = z; zp[i] = z; }
+            if (k < N - 1) g_copy(nn, cur, work + (size_t)k * WS);
+            T* sw = cur; cur = prev; prev = sw;
+        }
+        // back substitution: lambda_{N-1} = z_{N-1} (still in zp); W_k staged through LDS by the whole workgroup, one lane per row
+        T *la = y, *lb = prowD;
+        __syncthreads();
+        for (int i = tid; i < n; i += nt) { la[i] = zp[i]; lambda[(size_t)(N - 1) * n + i] = zp[i]; }
+        for (int k = N - 2; k >= 0; --k) {
+            g_copy(nn, work + (size_t)k * WS, Lb);
+            __syncthreads();
+            for (int r = tid; r < n; r += nt) {
+                T acc = 0;
+                for (int c = 0; c < n; ++c) acc += Lb[r + c * n] * la[c];
+                const T v = work[(size_t)k * WS + nn + r] - acc;
+                lb[r] = v;
+                lambda[(size_t)k * n + r] = v;
+            }
+            __syncthreads();
+            T* sw = la; la = lb; lb = sw;
+        }
+    }
+}
+
+#pragma clang fp contract(fast)
+
+}  // namespace gen
+}  // namespace mpcg

@@ -120,14 +120,17 @@ class QdldlSolver:
 
 class PcgSolver:
     """One handle per (device, state_size, knot_points).  `solve` is the batched hot path,
-    `solve_ref` the reference's single-trajectory 12-argument launch."""
+    `solve_ref` the reference's single-trajectory 12-argument launch.  `control_size` is the default of
+    `form_schur` / `compute_dz` / `generate_kkt` (None: 7, the IIWA-14's)."""
 
-    def __init__(self, knot_points: int, max_batch: int = 1, state_size: int = STATE_SIZE, device: int | None = None):
+    def __init__(self, knot_points: int, max_batch: int = 1, state_size: int = STATE_SIZE, device: int | None = None,
+                 control_size: int | None = None):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError("mpcgpu_amd.PcgSolver needs a HIP device (no CPU fallback)")
         self.device = torch.cuda.current_device() if device is None else int(device)
         self.n, self.N, self.max_batch = int(state_size), int(knot_points), int(max_batch)
+        self.control_size = CONTROL_SIZE if control_size is None else int(control_size)
         h = C.c_void_p()
         rc = self.lib.mpcg_create(C.byref(h), self.device, self.n, self.N, self.max_batch)
         if rc != _lib.MPCG_OK:
@@ -270,11 +273,11 @@ class PcgSolver:
         return lam
 
     def form_schur(self, G_dense, C_dense, g, c, rho: float, precond: str = "ss", S=None, Pinv=None, gamma=None,
-                   control_size: int = CONTROL_SIZE):
+                   control_size: int | None = None):
         """form_schur_system (include/pcg/linsys_setup.cuh:620-656), batched.  G_dense is overwritten by
         its block inverses (the reference's side effect).  Returns (S, Pinv, gamma) device tensors."""
         B = c.shape[0] if c.dim() > 1 else 1
-        n, m, N = self.n, control_size, self.N
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
         dt = c.dtype                                           # float32, or float64 = linsys_t double (mpcg_form_schur_f64)
         if dt not in (torch.float32, torch.float64):
             raise TypeError("form_schur: float32 or float64 tensors")
@@ -295,11 +298,11 @@ class PcgSolver:
         return S, Pinv, gamma
 
     def generate_kkt(self, plant: "Plant", eePos_traj, xs, xu, timestep: float, qd_cost: float, r_cost: float,
-                     control_size: int = CONTROL_SIZE):
+                     control_size: int | None = None):
         """generate_kkt_submatrices (include/common/kkt.cuh:22-163), batched: eePos_traj [B, 6N], xs [B, n], xu [B, (n+m)N - m]
         -> (G_dense, C_dense, g, c) device tensors in the layouts form_schur consumes."""
         B = xu.shape[0] if xu.dim() > 1 else 1
-        n, m, N = self.n, control_size, self.N
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
         self._chk(eePos_traj, B * 6 * N, torch.float32, "eePos_traj")
         self._chk(xs, B * n, torch.float32, "xs")
         self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
@@ -312,10 +315,10 @@ class PcgSolver:
                                                float(r_cost), _ptr(G), _ptr(Cd), _ptr(g), _ptr(c), B, _stream()))
         return G, Cd, g, c
 
-    def compute_dz(self, Ginv_dense, C_dense, g, lam, dz=None, control_size: int = CONTROL_SIZE):
+    def compute_dz(self, Ginv_dense, C_dense, g, lam, dz=None, control_size: int | None = None):
         """compute_dz (include/common/dz.cuh:124-136), batched."""
         B = lam.shape[0] if lam.dim() > 1 else 1
-        n, m, N = self.n, control_size, self.N
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
         dt = lam.dtype                                         # float32, or float64 = linsys_t double (mpcg_compute_dz_f64)
         if dt not in (torch.float32, torch.float64):
             raise TypeError("compute_dz: float32 or float64 tensors")
