@@ -1,0 +1,163 @@
+// sqp_batched_iiwa.cpp — a BATCHED SQP iteration that never leaves the device, over the C ABI alone (include/mpcg.h): for B windows of the reference's
+// precomputed trajectory (mpcgpu_amd/data/iiwa_traj_0_0.f32, perturbed as in mpcsim_iiwa_demo.cpp) K iterations of
+//     mpcg_generate_kkt -> mpcg_form_schur (SS) -> mpcg_pcg_solve -> mpcg_compute_dz -> mpcg_compute_merit (8 step sizes -1 / 2^p) -> mpcg_line_search_step
+// — the stages of include/pcg/sqp.cuh:190-353 of the reference, whose line search runs eight cooperative launches, a device synchronisation and a
+// read-back per iteration for ONE trajectory.  Here nothing synchronises inside an iteration: the merit of every trajectory and iteration and the
+// accepted exponents wait in device buffers and are read once at the end.  rho stays at its initial value (it is one scalar per mpcg_form_schur
+// call; the reference's adaptation, sqp.cuh:304-320, belongs to a caller that reads d_step back — mpcgpu_compat::use_mpcg_line_search does).
+// Prints one JSON line; exits 0 only if every trajectory's merit went down.
+//   hipcc --offload-arch=gfx950 -O2 -Iinclude examples/sqp_batched_iiwa.cpp -Lmpcgpu_amd -lmpcg_hip
+//   sqp_batched_iiwa [--batch 8] [--knots 32] [--iters 4] [--mu 10] [--rho 1e-3]
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "mpcg.h"
+
+static const int n = 14, m = 7, ROWW = 27, ROWS = 400;      // a row of the data file: x (14), u (7), end-effector pose (6)
+
+#define HIP_OK(expr)                                                                                         \
+    do {                                                                                                     \
+        hipError_t e_ = (expr);                                                                              \
+        if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #expr, hipGetErrorString(e_)); exit(1); }       \
+    } while (0)
+#define MPCG_OK_OR_DIE(h, expr)                                                                              \
+    do {                                                                                                     \
+        if ((expr) != MPCG_OK) { fprintf(stderr, "%s: %s\n", #expr, mpcg_last_error(h)); exit(1); }          \
+    } while (0)
+
+static std::vector<float> load_rows(const std::string& exe) {
+    const std::string dir = exe.substr(0, exe.find_last_of('/') + 1);
+    for (const std::string& p : {dir + "../mpcgpu_amd/data/iiwa_traj_0_0.f32", std::string("mpcgpu_amd/data/iiwa_traj_0_0.f32")}) {
+        if (FILE* f = fopen(p.c_str(), "rb")) {
+            std::vector<float> v((size_t)ROWS * ROWW);
+            const size_t got = fread(v.data(), sizeof(float), v.size(), f);
+            fclose(f);
+            if (got == v.size()) return v;
+        }
+    }
+    fprintf(stderr, "cannot read mpcgpu_amd/data/iiwa_traj_0_0.f32\n");
+    exit(1);
+}
+
+template <typename T>
+static T* dalloc(size_t count) {
+    T* p = nullptr;
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)));
+    HIP_OK(hipMemset(p, 0, count * sizeof(T)));
+    return p;
+}
+
+int main(int argc, char** argv) {
+    int B = 8, N = 32, K = 4;
+    float mu = 10.f, rho = 1e-3f;
+    for (int i = 1; i + 1 < argc; i += 2) {
+        if (!strcmp(argv[i], "--batch")) B = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--knots")) N = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--iters")) K = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--mu")) mu = (float)atof(argv[i + 1]);
+        else if (!strcmp(argv[i], "--rho")) rho = (float)atof(argv[i + 1]);
+        else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
+    }
+    if (B < 1 || N < 2 || N + 1 > ROWS || K < 1) { fprintf(stderr, "need batch >= 1, 2 <= knots < %d, iters >= 1\n", ROWS); return 2; }
+    const float dt = 1.0f / 64, qd_cost = 1e-4f, r_cost = N == 64 ? 1e-3f : 1e-4f;      // include/common/settings.cuh:84-94
+    const size_t L = (size_t)(n + m) * N - m;
+    const std::vector<float> rows = load_rows(argv[0]);
+
+    // B windows spread over the file; the measured state is off the plan and the plan is off the dynamics (mpcsim_iiwa_demo.cpp)
+    std::vector<float> xu((size_t)B * L), goals((size_t)B * 6 * N), xs((size_t)B * n);
+    unsigned s = 99u;
+    auto rnd = [&s]() { s = s * 1664525u + 1013904223u; return ((s >> 8) & 0xffff) / 65536.0f - 0.5f; };
+    for (int b = 0; b < B; ++b) {
+        const int t0 = (int)(((long)b * 37) % (ROWS - N));
+        float* w = &xu[(size_t)b * L];
+        for (int k = 0; k < N; ++k) {
+            const float* r = &rows[(size_t)(t0 + k) * ROWW];
+            for (int i = 0; i < n; ++i) w[(size_t)k * (n + m) + i] = r[i];
+            if (k < N - 1) for (int i = 0; i < m; ++i) w[(size_t)k * (n + m) + n + i] = r[n + i];
+            for (int i = 0; i < 6; ++i) goals[((size_t)b * N + k) * 6 + i] = r[n + m + i];
+        }
+        for (int i = 0; i < n; ++i) xs[(size_t)b * n + i] = w[i] + 0.04f * rnd();
+        for (size_t e = n; e < L; ++e) w[e] += 0.02f * rnd();
+    }
+
+    mpcg_handle* h = nullptr;
+    mpcg_plant* plant = nullptr;
+    if (mpcg_create(&h, -1, n, (uint32_t)N, (uint32_t)B) != MPCG_OK) { fprintf(stderr, "mpcg_create: %s\n", mpcg_last_error(nullptr)); return 1; }
+    if (mpcg_plant_create_iiwa14(&plant, -1) != MPCG_OK) { fprintf(stderr, "mpcg_plant_create_iiwa14: %s\n", mpcg_last_error(nullptr)); return 1; }
+
+    const size_t nn = n * n, mm = m * m, nm = n * m;
+    float* d_xu = dalloc<float>((size_t)B * L);
+    float* d_goals = dalloc<float>(goals.size());
+    float* d_xs = dalloc<float>(xs.size());
+    float* d_G = dalloc<float>((size_t)B * ((nn + mm) * N - mm));
+    float* d_C = dalloc<float>((size_t)B * (nn + nm) * (N - 1));
+    float* d_g = dalloc<float>((size_t)B * L);
+    float* d_c = dalloc<float>((size_t)B * n * N);
+    float* d_S = dalloc<float>((size_t)B * 3 * nn * N);
+    float* d_Pinv = dalloc<float>((size_t)B * 3 * nn * N);
+    float* d_gamma = dalloc<float>((size_t)B * n * N);
+    float* d_lambda = dalloc<float>((size_t)B * n * N);
+    float* d_dz = dalloc<float>((size_t)B * L);
+    float* d_merit = dalloc<float>((size_t)B * 8);
+    float* d_merit_ref = dalloc<float>(B);
+    float* d_merit_hist = dalloc<float>((size_t)(K + 1) * B);
+    int32_t* d_step_hist = dalloc<int32_t>((size_t)K * B);
+    uint32_t* d_iters = dalloc<uint32_t>(B);
+    uint8_t* d_exit = dalloc<uint8_t>(B);
+    HIP_OK(hipMemcpy(d_xu, xu.data(), xu.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_goals, goals.data(), goals.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_xs, xs.data(), xs.size() * sizeof(float), hipMemcpyHostToDevice));
+
+    hipStream_t st;
+    HIP_OK(hipStreamCreate(&st));
+    float steps[8];
+    for (int p = 0; p < 8; ++p) steps[p] = -1.0f / (float)(1 << p);          // alpha = -1 / 2^p (include/common/merit.cuh:47)
+    const float zero = 0.f;
+    // the merit of the start iterate: the reference's compute_merit (include/pcg/sqp.cuh:171-187) — with the initial-state term, like the eight trials
+    MPCG_OK_OR_DIE(h, mpcg_compute_merit(h, plant, m, dt, d_goals, d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, (uint32_t)B, st));
+    HIP_OK(hipMemcpyAsync(d_merit_hist, d_merit_ref, B * sizeof(float), hipMemcpyDeviceToDevice, st));
+    for (int it = 0; it < K; ++it) {                                          // no host synchronisation in here
+        MPCG_OK_OR_DIE(h, mpcg_generate_kkt(h, plant, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, st));
+        MPCG_OK_OR_DIE(h, mpcg_form_schur(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, rho, (uint32_t)B, MPCG_PRECOND_SS, st));
+        MPCG_OK_OR_DIE(h, mpcg_pcg_solve(h, d_S, d_Pinv, d_gamma, d_lambda, (uint32_t)B, 3000, 1e-7f, MPCG_PRECOND_SS, d_iters, d_exit, st));
+        MPCG_OK_OR_DIE(h, mpcg_compute_dz(h, m, d_G, d_C, d_g, d_lambda, d_dz, (uint32_t)B, st));
+        MPCG_OK_OR_DIE(h, mpcg_compute_merit(h, plant, m, dt, d_goals, d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, (uint32_t)B, st));
+        MPCG_OK_OR_DIE(h, mpcg_line_search_step(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step_hist + (size_t)it * B, (uint32_t)B, st));
+        HIP_OK(hipMemcpyAsync(d_merit_hist + (size_t)(it + 1) * B, d_merit_ref, B * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    std::vector<float> hist((size_t)(K + 1) * B);
+    std::vector<int32_t> expo((size_t)K * B);
+    HIP_OK(hipMemcpy(hist.data(), d_merit_hist, hist.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(expo.data(), d_step_hist, expo.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+
+    bool ok = true;
+    for (int b = 0; b < B; ++b) ok = ok && std::isfinite(hist[(size_t)K * B + b]) && hist[(size_t)K * B + b] < hist[b];
+    printf("{\"batch\": %d, \"knots\": %d, \"iters\": %d, \"mu\": %g, \"rho\": %g, \"merit\": [", B, N, K, (double)mu, (double)rho);
+    for (int b = 0; b < B; ++b) {
+        printf("%s[", b ? ", " : "");
+        for (int it = 0; it <= K; ++it) printf("%s%.9g", it ? ", " : "", (double)hist[(size_t)it * B + b]);
+        printf("]");
+    }
+    printf("], \"exponents\": [");
+    for (int b = 0; b < B; ++b) {
+        printf("%s[", b ? ", " : "");
+        for (int it = 0; it < K; ++it) printf("%s%d", it ? ", " : "", expo[(size_t)it * B + b]);
+        printf("]");
+    }
+    printf("], \"ok\": %s}\n", ok ? "true" : "false");
+
+    for (void* p : {(void*)d_xu, (void*)d_goals, (void*)d_xs, (void*)d_G, (void*)d_C, (void*)d_g, (void*)d_c, (void*)d_S, (void*)d_Pinv, (void*)d_gamma,
+                    (void*)d_lambda, (void*)d_dz, (void*)d_merit, (void*)d_merit_ref, (void*)d_merit_hist, (void*)d_step_hist, (void*)d_iters, (void*)d_exit})
+        HIP_OK(hipFree(p));
+    HIP_OK(hipStreamDestroy(st));
+    mpcg_plant_destroy(plant);
+    mpcg_destroy(h);
+    return ok ? 0 : 1;
+}

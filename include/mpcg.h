@@ -41,7 +41,7 @@
  *     passed as void* (NULL = default stream).  Calls are stream-ordered and never synchronise.
  *   - batched entry points take `batch` independent trajectories stored back to back.
  *   - GRAPH CAPTURE.  Every compute entry point is pure stream work and may be captured into a hipGraph.  What the float PCG entry points need
- *     is allocated by mpcg_create; mpcg_form_schur(_f64), mpcg_block_solve and a FORCED "cluster" on a horizon the automatic policy gives to one
+ *     is allocated by mpcg_create; mpcg_form_schur(_f64), mpcg_block_solve, mpcg_compute_merit and a FORCED "cluster" on a horizon the automatic policy gives to one
  *     CU allocate a handle-owned work buffer at their first call (hipMalloc is not stream work): make that call once outside the capture — a
  *     first call on a capturing stream returns MPCG_ERR_INVALID with a message and leaves the capture intact.  linsys_t = double beyond 32
  *     knots (mpcg_pcg_solve_f64 / _ref_f64: cluster kernels with a queue + flags buffer and a double-sized copy of lambda0): mpcg_create makes
@@ -105,8 +105,8 @@ const char *mpcg_build_info(void);
  * device buffers: allocated here, the hand-off cells of the float cluster kernel, the dispatch-order buffer of "sched_hint",
  * the pinned word of the symmetry latch, the copy of d_lambda a cluster follow-up launch starts from (knot_points > 128)
  * and, for handles with at most 8 MB of double iterates, the double cluster kernels' buffers (GRAPH CAPTURE); from their
- * first use on, the staging buffers of mpcg_form_schur(_f64), the seam buffer of the chunk-walking Schur kernel and the
- * sweep scratch of mpcg_block_solve.  max_batch bounds `batch` of later calls.  device < 0 = current device.  One handle per
+ * first use on, the staging buffers of mpcg_form_schur(_f64), the seam buffer of the chunk-walking Schur kernel, the
+ * sweep scratch of mpcg_block_solve and the point-merit scratch of mpcg_compute_merit.  max_batch bounds `batch` of later calls.  device < 0 = current device.  One handle per
  * (device, knot_points) and per concurrently used stream: calls on the same handle must not overlap on the host
  * side (launch knobs are chosen per call) and their device work must be ordered (one stream, or events) because
  * they share those buffers; different handles are independent. */
@@ -120,7 +120,7 @@ const char *mpcg_build_info(void);
  *     MPCG_ERR_INVALID.  mpcg_form_schur(_f64) needs one block row's operands, 6 n^2 + 2 n m + 2 m^2 + 12 n + 4 m elements, in 160 KiB of
  *     LDS: every m <= n <= 32 in both precisions (and e.g. 40 x 10); beyond that it returns MPCG_ERR_UNSUPPORTED.  The others serve every
  *     such handle.  batch x knot_points < 2^31.
- * mpcg_bt_spmv, mpcg_pcg_solve_f16, mpcg_generate_kkt and mpcg_probe_hbm_read return MPCG_ERR_UNSUPPORTED on a handle with state_size != 14. */
+ * mpcg_bt_spmv, mpcg_pcg_solve_f16, mpcg_generate_kkt, mpcg_compute_merit and mpcg_probe_hbm_read return MPCG_ERR_UNSUPPORTED on a handle with state_size != 14. */
 int mpcg_create(mpcg_handle **out, int device, uint32_t state_size, uint32_t knot_points, uint32_t max_batch);
 int mpcg_destroy(mpcg_handle *h);
 const char *mpcg_last_error(const mpcg_handle *h);   /* h may be NULL: last error of mpcg_create */
@@ -310,6 +310,51 @@ int mpcg_plant_destroy(mpcg_plant *p);
 int mpcg_generate_kkt(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size, float timestep, const float *d_eePos_traj,
                       const float *d_xs, const float *d_xu, float qd_cost, float r_cost, float *d_G_dense, float *d_C_dense,
                       float *d_g, float *d_c, uint32_t batch, void *stream);
+
+/* ---- the stage behind dz: merit function and line search on the device ----
+ * mpcg_compute_merit replaces the eight cooperative launches of ls_gato_compute_merit (include/common/merit.cuh:16-94, launched at
+ * include/pcg/sqp.cuh:264-282) and compute_merit (merit.cuh:99-143), batched over trajectories AND step sizes in one call: for trajectory b and
+ * step size a, at the trial iterate z = xu_b + step_sizes[a] * dz_b,
+ *   d_merit[b][a] = sum_{k<N} J_k + mu ( sum_{k<N-1} | x_{k+1} - (x_k + dt [qd_k ; qdd_k]) |_1  +  [d_xs given] | x_0 - xs_b |_1 )
+ *   J_k = 1/2 |ee(q_k) - goal_k[0:3]|^2 + 1/2 qd_cost |qd_k|^2 + [k < N-1] 1/2 r_cost |u_k|^2
+ * with the plant functions the reference calls (gato_plant::trackingcost, include/dynamics/iiwa/iiwa_eepos_plant.cuh:242-290; integratorError
+ * with the Euler integrator, include/common/integrator.cuh; forward dynamics of the mpcg_plant without gravity, as mpcg_generate_kkt).  The last
+ * knot's cost is evaluated at its own state x_{N-1} against goal_{N-1} (merit.cuh:62) — not at x_{N-2} as the KKT stage's _lastblock does.
+ * The initial-state term is what ls_gato_compute_merit adds in its last block (merit.cuh:68-77); the reference's compute_merit, which gives
+ * the merit the line search compares against, leaves it out (:133-135): d_xs = NULL reproduces that.  Pass the same d_xs for both and all
+ * numbers of a line search are the same function.
+ *   step_sizes   HOST array of num_steps (1 .. MPCG_MAX_STEP_SIZES) values, copied into the launch (a captured graph keeps them); the
+ *                reference's are -1 / 2^p (merit.cuh:47).  d_dz may be NULL if every step size is 0.
+ *   d_merit      [batch][num_steps] floats
+ * The trial iterate is formed in float with ONE rounding, fmaf(step, dz, xu) — with step 0 it is xu exactly — and everything behind it runs
+ * in float64 (csrc/merit_plant.hip.h: the KKT kernel's round 0, a 16-lane group per (trajectory, step size, knot)); option "kkt_f32" does not
+ * affect it.  Every sum has a fixed order (no atomics — the reference's atomicAdd is not reproduced): results are bitwise reproducible and a
+ * number depends neither on the rest of the batch nor on the other step sizes of the call.  state_size 14 / control_size 7 only
+ * (MPCG_ERR_UNSUPPORTED otherwise).  The first call allocates a handle-owned scratch of max_batch x 16 x knot_points doubles (hipMalloc — not
+ * stream work: GRAPH CAPTURE above); later calls are pure stream work.
+ *
+ * mpcg_line_search_step is the reference's step selection and update (include/pcg/sqp.cuh:292-301, 317, 332-338, 352), per trajectory b:
+ *   best = d_merit_ref[b]; p = -1;  for i in 0 .. num_steps-1: if (d_merit[b][i] < best) { best = d_merit[b][i]; p = i; }
+ * (strict: the first of equals wins, a value equal to d_merit_ref is no improvement, a NaN never wins), then d_step[b] = p and, if p >= 0,
+ * d_merit_ref[b] = best and every element xu = fmaf(step_sizes[p], dz, xu) — the very float mpcg_compute_merit evaluated, so the merit of the new
+ * iterate at step size 0 IS the new d_merit_ref, bit for bit.  p = -1 leaves d_xu and d_merit_ref untouched.  No dynamics: every handle shape,
+ * any 1 <= control_size <= state_size; d_dz, d_xu [batch][(n+m)N - m].  Pure stream work from the first call on.  The rho adaptation of
+ * sqp.cuh:304-320 stays with the caller (rho is one scalar per mpcg_form_schur call); d_step is what it needs.
+ *
+ * Both calls:  MPCG_ERR_INVALID      a null required pointer; num_steps 0 or > MPCG_MAX_STEP_SIZES; batch > max_batch; d_dz == NULL with a
+ *                                    non-zero step size; a plant on another device than the handle's; control_size 0 or > state_size (step)
+ *              MPCG_ERR_UNSUPPORTED  mpcg_compute_merit on anything but state_size 14 / control_size 7
+ *              MPCG_OK               batch == 0: nothing is launched */
+#define MPCG_MAX_STEP_SIZES 16
+int mpcg_compute_merit(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size, float timestep,
+                       const float *d_eePos_traj, const float *d_xs /* may be NULL */, const float *d_xu,
+                       const float *d_dz /* may be NULL if every step size is 0 */,
+                       const float *step_sizes /* HOST, num_steps values, copied into the launch */, uint32_t num_steps,
+                       float mu, float qd_cost, float r_cost, float *d_merit /* [batch][num_steps] */,
+                       uint32_t batch, void *stream);
+int mpcg_line_search_step(mpcg_handle *h, uint32_t control_size, const float *d_merit, const float *step_sizes, uint32_t num_steps,
+                          float *d_merit_ref /* [batch] in/out */, const float *d_dz, float *d_xu /* in/out */,
+                          int32_t *d_step /* [batch] out */, uint32_t batch, void *stream);
 
 /* ---- LINSYS_SOLVE == 0 as a selectable solver: the reference's CPU LDL^T path ----
  * The reference's second linear-system path factors the (negated) Schur matrix on the HOST with QDLDL

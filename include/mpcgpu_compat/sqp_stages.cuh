@@ -1,16 +1,19 @@
-// sqp_stages.cuh — plug points for the stages of MPCGPU's SQP / MPC loop that are OUTSIDE this library's scope
-// (KKT assembly with the robot dynamics, merit / line search, plant simulation + horizon
-// shift).  The shim versions of sqpSolvePcg / sqpSolveQdldl / simulateMPC (include/pcg/sqp.cuh, include/qdldl/sqp.cuh,
-// include/mpcsim.cuh of THIS repo) keep the reference's names, argument lists and return tuples and run the
-// linear-system section on libmpcg_hip; wherever the reference calls one of its own out-of-scope kernels they call the
-// function registered here.  A maintainer porting MPCGPU registers thin wrappers around the reference's kernels
-// (generate_kkt_submatrices, ls_gato_compute_merit + the alpha / rho logic of include/pcg/sqp.cuh:265-353,
-// simple_simulate + just_shift); examples/mpcsim_shim_demo.cpp registers a synthetic convex problem.
+// sqp_stages.cuh — plug points for the stages of MPCGPU's SQP / MPC loop around the linear-system section (KKT
+// assembly with the robot dynamics, merit / line search, plant simulation + horizon shift).  The shim versions of sqpSolvePcg / sqpSolveQdldl /
+// simulateMPC (include/pcg/sqp.cuh, include/qdldl/sqp.cuh, include/mpcsim.cuh of THIS repo) keep the reference's names, argument lists and
+// return tuples and run the linear-system section on libmpcg_hip; wherever the reference calls one of those stages' kernels they call the
+// function registered here.  Two of the three are in the library now and register themselves: use_mpcg_generate_kkt (mpcg_generate_kkt) and
+// use_mpcg_line_search (mpcg_compute_merit + mpcg_line_search_step with the alpha / rho logic of include/pcg/sqp.cuh:264-353) for the IIWA-14;
+// the plant simulation + horizon shift (simple_simulate + just_shift) stays outside the library.  A maintainer porting MPCGPU with another
+// robot registers thin wrappers around the reference's kernels instead; examples/mpcsim_shim_demo.cpp registers a synthetic convex problem.
 #pragma once
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <functional>
+#include <memory>
+#include <type_traits>
 
 #ifndef CONST_UPDATE_FREQ
 #define CONST_UPDATE_FREQ 1      // include/common/settings.cuh:56-58
@@ -20,6 +23,8 @@
 #endif
 
 namespace mpcgpu_compat {
+
+inline void require_stage(bool present, const char* which);
 
 template <typename T>
 struct sqp_stages {
@@ -53,7 +58,8 @@ inline sqp_stages<T>& stages() {
 }
 
 // The library's own generate_kkt_submatrices (mpcg_generate_kkt: IIWA-14 dynamics, tracking cost, Euler integrator on the device) as the
-// generate_kkt stage — the default when an mpcg_plant is supplied; merit function / line search and the plant simulation stay plug points.
+// generate_kkt stage — the default when an mpcg_plant is supplied; use_mpcg_line_search below adds the merit function / line search, the plant
+// simulation stays a plug point.
 // qd_cost / r_cost: QD_COST / R_COST of include/common/settings.cuh:84-94.  Needs gbd_pcg_compat/gpu_pcg.cuh (handle cache) before this header.
 #ifdef MPCG_H
 template <typename T>
@@ -66,6 +72,67 @@ inline void use_mpcg_generate_kkt(mpcg_plant* plant, float qd_cost, float r_cost
         if (mpcg_generate_kkt(h, static_cast<const mpcg_plant*>(d_dynMem_const), control_size, timestep, d_eePos_traj, d_xs, d_xu, qd_cost, r_cost,
                               d_G_dense, d_C_dense, d_g, d_c, 1, /*stream*/ nullptr) != MPCG_OK)
             mpcg_compat::die("generate_kkt_submatrices", h);
+    };
+}
+
+// The library's own line search as the globalize_and_step stage: include/pcg/sqp.cuh:264-353 of the reference over mpcg_compute_merit (the eight
+// step sizes alpha = -1 / 2^p in ONE call instead of eight cooperative launches on eight streams) and mpcg_line_search_step (selection :292-301 and
+// the saxpy :317, 332-338 on the device), a 4-byte read-back of the chosen exponent, and the drho / rho / rho_max / rho_reset logic of :304-320 with
+// the reference's constants (include/common/settings.cuh:185-196).  mu: 10 in the reference (sqp.cuh:51); timestep as handed to sqpSolve*.
+// Register a generate_kkt stage FIRST (use_mpcg_generate_kkt): this wraps it to remember the goals and d_xs of the current call, which the
+// stage's signature does not carry.  merit_ref is evaluated at the first SQP iteration of a call (sqp.cuh:171-187) and carried afterwards (:352).
+// The reference compares the eight trial merits of ls_gato_compute_merit, which include the initial-state term |x_0 - x_s|_1
+// (include/common/merit.cuh:68-77), against an initial merit from compute_merit, which leaves it out (:133-135) — two different functions, and a
+// step that does not move x_0 can never win by that term.  Here d_xs is passed to all nine evaluations: one function.
+template <typename T>
+inline void use_mpcg_line_search(float mu, float qd_cost, float r_cost, float timestep) {
+    static_assert(std::is_same<T, float>::value, "use_mpcg_line_search: mpcg_compute_merit / mpcg_line_search_step are float entry points");
+    struct ls_state {
+        T *d_goal = nullptr, *d_xs = nullptr;
+        float* d_buf = nullptr;          // merit[8], merit_ref, step: 40 bytes that live as long as the process (the stage table is a static)
+        T drho = 1;
+    };
+    auto s = std::make_shared<ls_state>();
+    auto& st = stages<T>();
+    require_stage((bool)st.generate_kkt, "generate_kkt (register it before use_mpcg_line_search)");
+    auto kkt = st.generate_kkt;
+    st.generate_kkt = [s, kkt](uint32_t state_size, uint32_t control_size, uint32_t knot_points, T* d_G_dense, T* d_C_dense, T* d_g, T* d_c,
+                               void* d_dynMem_const, float dt, T* d_eePos_traj, T* d_xs, T* d_xu) {
+        s->d_goal = d_eePos_traj; s->d_xs = d_xs;
+        kkt(state_size, control_size, knot_points, d_G_dense, d_C_dense, d_g, d_c, d_dynMem_const, dt, d_eePos_traj, d_xs, d_xu);
+    };
+    st.globalize_and_step = [s, mu, qd_cost, r_cost, timestep](uint32_t state_size, uint32_t control_size, uint32_t knot_points, T* d_xu, T* d_dz, T& rho,
+                                                                T rho_reset, uint32_t sqp_iter) -> bool {
+        const T rho_factor = 1.2f, rho_max = 10.f, rho_min = 1e-3f;            // include/common/settings.cuh:185-196
+        mpcg_handle* h = mpcg_compat::handle_for(state_size, knot_points);
+        const mpcg_plant* plant = static_cast<const mpcg_plant*>(stages<T>().dynmem);
+        if (!s->d_buf && hipMalloc(reinterpret_cast<void**>(&s->d_buf), 10 * sizeof(float)) != hipSuccess) mpcg_compat::die("use_mpcg_line_search: hipMalloc", h);
+        float *d_merit = s->d_buf, *d_merit_ref = s->d_buf + 8;
+        int32_t* d_step = reinterpret_cast<int32_t*>(s->d_buf + 9);
+        float steps[8];
+        for (int p = 0; p < 8; ++p) steps[p] = -1.0f / (float)(1 << p);       // alpha sign (include/common/merit.cuh:47)
+        if (sqp_iter == 0) {                                                   // (:86, :171-187)
+            s->drho = 1;
+            const float zero = 0.f;
+            if (mpcg_compute_merit(h, plant, control_size, timestep, s->d_goal, s->d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, 1,
+                                   /*stream*/ nullptr) != MPCG_OK)
+                mpcg_compat::die("compute_merit", h);
+        }
+        if (mpcg_compute_merit(h, plant, control_size, timestep, s->d_goal, s->d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, 1, nullptr) != MPCG_OK)
+            mpcg_compat::die("ls_gato_compute_merit", h);                      // (:264-282)
+        if (mpcg_line_search_step(h, control_size, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step, 1, nullptr) != MPCG_OK)
+            mpcg_compat::die("line_search_step", h);                           // (:292-301, :317, :332-338, :352)
+        int32_t p = -1;
+        if (hipMemcpy(&p, d_step, sizeof(p), hipMemcpyDeviceToHost) != hipSuccess) mpcg_compat::die("use_mpcg_line_search: hipMemcpy", h);
+        if (p < 0) {                                                           // line search failure (:304-315)
+            s->drho = std::max(s->drho * rho_factor, rho_factor);
+            rho = std::max(rho * s->drho, rho_min);
+            if (rho > rho_max) { rho = rho_reset; return false; }
+            return true;
+        }
+        s->drho = std::min(s->drho / rho_factor, 1 / rho_factor);              // (:319-320)
+        rho = std::max(rho * s->drho, rho_min);
+        return true;
     };
 }
 #endif

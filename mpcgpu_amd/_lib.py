@@ -19,6 +19,7 @@ MPCG_ERR_NOMEM = -4
 MPCG_PRECOND_NONE = 0
 MPCG_PRECOND_JACOBI = 1
 MPCG_PRECOND_SS = 3
+MPCG_MAX_STEP_SIZES = 16
 
 # every symbol include/mpcg.h declares: (name, restype, argtypes)
 _f32p = C.c_void_p   # device pointers travel as integers
@@ -58,6 +59,10 @@ SYMBOLS = {
     "mpcg_plant_destroy": (C.c_int, [C.c_void_p]),
     "mpcg_generate_kkt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_compute_merit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_line_search_step": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_ldl_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
     "mpcg_ldl_destroy": (C.c_int, [C.c_void_p]),
     "mpcg_ldl_pattern": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),

@@ -27,6 +27,8 @@ DEMO_BINS = {1: _ex("mpcsim_shim_demo_pcg"), 0: _ex("mpcsim_shim_demo_qdldl")}
 IIWA_DEMO_BINS = {1: _ex("mpcsim_iiwa_demo_pcg"), 0: _ex("mpcsim_iiwa_demo_qdldl")}
 MULTI_BIN = _ex("multi_gpu_pcg")
 UTILS_BIN = _ex("bd_utils_probe")
+SQP_BATCHED_BIN = _ex("sqp_batched_iiwa")
+LINE_SEARCH_STAGE_BIN = _ex("sqp_line_search_stage")
 
 
 def sources():
@@ -132,6 +134,18 @@ def build_utils_probe(force: bool = False, verbose: bool = False) -> str:
     """Instantiates store_block_bd / load_block_bd / gato_memcpy of include/gbd_pcg_compat/utils.cuh in a kernel."""
     _build_bins([UTILS_BIN], force, verbose)
     return UTILS_BIN
+
+
+def build_sqp_batched(force: bool = False, verbose: bool = False) -> str:
+    """A batched SQP iteration that stays on the device: KKT -> Schur -> PCG -> dz -> merit -> line-search step over the C ABI."""
+    _build_bins([SQP_BATCHED_BIN], force, verbose)
+    return SQP_BATCHED_BIN
+
+
+def build_line_search_stage(force: bool = False, verbose: bool = False) -> str:
+    """sqpSolvePcg over the shim headers with the library's KKT and line-search stages registered (use_mpcg_line_search)."""
+    _build_bins([LINE_SEARCH_STAGE_BIN], force, verbose)
+    return LINE_SEARCH_STAGE_BIN
 
 
 def build_all(force: bool = False, verbose: bool = False) -> str:

@@ -3,7 +3,7 @@
 //   mpcg_pcg.hip        handle / options / the PCG launch policy and entry points (pcg_*.hip.h kernels)
 //   mpcg_producers.hip  Schur + preconditioner formation, dz recovery, CSR emitter, block-tridiagonal direct solve (schur_*.hip.h, block_solve.hip.h;
 //                       any other (state_size, control_size) than 14 x 7: schur_generic.hip.h)
-//   mpcg_plant.hip      the robot as data + KKT block assembly (kkt_plant.hip.h)
+//   mpcg_plant.hip      the robot as data + KKT block assembly (kkt_plant.hip.h), merit function + line-search step (merit_plant.hip.h)
 //   mpcg_ldl.hip        the host LDL^T twin of the reference's QDLDL path (ldl_host.hpp)
 // Every kernel header is included by exactly one of them (their non-template kernels have external linkage).
 #pragma once
@@ -91,6 +91,7 @@ struct mpcg_handle {
     size_t ginv_scratch_floats = 0;
     double* ginv_scratch_f64 = nullptr;   // the same for mpcg_form_schur_f64
     size_t ginv_scratch_f64_elems = 0;
+    double* merit_scratch = nullptr;   // point merits of mpcg_compute_merit: max_batch x 16 x N doubles (first call)
     std::string err;
 };
 

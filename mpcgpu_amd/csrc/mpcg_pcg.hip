@@ -234,6 +234,7 @@ int mpcg_destroy(mpcg_handle* h) {
         if (h->sym_event) (void)hipEventDestroy(h->sym_event);
         if (h->sym_host) (void)hipHostFree(h->sym_host);
         if (h->ginv_scratch_f64) (void)hipFree(h->ginv_scratch_f64);
+        if (h->merit_scratch) (void)hipFree(h->merit_scratch);
         if (h->cluster_scratch) (void)hipFree(h->cluster_scratch);
         if (h->cluster64_scratch) (void)hipFree(h->cluster64_scratch);
         if (h->sched_order) (void)hipFree(h->sched_order);

@@ -1,7 +1,9 @@
 // mpcg_plant.hip — C ABI (include/mpcg.h) of the producer of the path's inputs: the robot as data (mpcg_plant) and the KKT block assembly
-// mpcg_generate_kkt over the gfx950 kernel in kkt_plant.hip.h.
+// mpcg_generate_kkt over the gfx950 kernel in kkt_plant.hip.h; the stage behind dz — mpcg_compute_merit and
+// mpcg_line_search_step over merit_plant.hip.h.
 #include "mpcg_handle.hpp"
 #include "kkt_plant.hip.h"
+#include "merit_plant.hip.h"
 
 using namespace mpcg;
 
@@ -223,6 +225,66 @@ int mpcg_generate_kkt(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_
         hipLaunchKernelGGL((generate_kkt_kernel<true, float>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), f);
     } else if (h->kkt_analytic) hipLaunchKernelGGL((generate_kkt_kernel<true, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
     else hipLaunchKernelGGL((generate_kkt_kernel<false, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
+
+// ---- merit function and line search (merit_plant.hip.h) ----
+static int check_steps(mpcg_handle* h, const char* who, const float* step_sizes, uint32_t num_steps) {
+    if (!step_sizes) return fail(h, MPCG_ERR_INVALID, std::string(who) + ": null step_sizes");
+    if (num_steps == 0 || num_steps > (uint32_t)MPCG_MAX_STEP_SIZES) return fail(h, MPCG_ERR_INVALID, std::string(who) + ": num_steps must be 1..16 (MPCG_MAX_STEP_SIZES)");
+    return MPCG_OK;
+}
+
+int mpcg_compute_merit(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float timestep, const float* d_eePos_traj, const float* d_xs,
+                       const float* d_xu, const float* d_dz, const float* step_sizes, uint32_t num_steps, float mu, float qd_cost, float r_cost,
+                       float* d_merit, uint32_t batch, void* stream) {
+    static_assert(MERIT_MAX_STEPS == MPCG_MAX_STEP_SIZES, "scratch row stride");
+    if (!h || !plant) return MPCG_ERR_INVALID;
+    if (!d_eePos_traj || !d_xu || !d_merit) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_merit: null device pointer");
+    { const int rc = check_steps(h, "mpcg_compute_merit", step_sizes, num_steps); if (rc != MPCG_OK) return rc; }
+    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_compute_merit: state_size 14 / control_size 7 (IIWA-14) only");
+    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_merit: plant and handle live on different devices");
+    MeritArgs a;
+    bool moved = false;
+    for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) { a.alpha[i] = i < num_steps ? step_sizes[i] : 0.f; moved = moved || a.alpha[i] != 0.f; }
+    if (moved && !d_dz) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_merit: d_dz may be NULL only if every step size is 0");
+    if (batch == 0) return MPCG_OK;
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_merit: batch exceeds max_batch");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!h->merit_scratch) {                      // first call only (not stream-ordered: hipMalloc)
+        { const int rc = alloc_allowed(h, st, "mpcg_compute_merit"); if (rc != MPCG_OK) return rc; }
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->merit_scratch), (size_t)h->max_batch * MERIT_MAX_STEPS * h->N * sizeof(double)));
+    }
+    a.plant = plant->d; a.eePos_traj = d_eePos_traj; a.xs = d_xs; a.xu = d_xu; a.dz = d_dz; a.point = h->merit_scratch;
+    a.N = (int)h->N; a.batch = (int)batch; a.A = (int)num_steps;
+    a.dt = timestep; a.mu = mu; a.qd_cost = qd_cost; a.r_cost = r_cost;
+    long blocks = ((long)batch * num_steps * h->N + KKT_ITEMS - 1) / KKT_ITEMS;      // one wavefront per KKT_ITEMS (trajectory, step size, knot) items
+    const long cap = (long)h->num_cus * 32;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(merit_points_kernel, dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    const int rows = (int)(batch * num_steps);
+    hipLaunchKernelGGL(merit_sum_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
+
+int mpcg_line_search_step(mpcg_handle* h, uint32_t control_size, const float* d_merit, const float* step_sizes, uint32_t num_steps,
+                          float* d_merit_ref, const float* d_dz, float* d_xu, int32_t* d_step, uint32_t batch, void* stream) {
+    if (!h) return MPCG_ERR_INVALID;
+    if (!d_merit || !d_merit_ref || !d_dz || !d_xu || !d_step) return fail(h, MPCG_ERR_INVALID, "mpcg_line_search_step: null device pointer");
+    { const int rc = check_steps(h, "mpcg_line_search_step", step_sizes, num_steps); if (rc != MPCG_OK) return rc; }
+    if (control_size == 0 || control_size > h->n) return fail(h, MPCG_ERR_INVALID, "mpcg_line_search_step: control_size must be 1..state_size");
+    if (batch == 0) return MPCG_OK;
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_line_search_step: batch exceeds max_batch");
+    HIP_TRY(h, hipSetDevice(h->device));
+    StepArgs a;
+    a.merit = d_merit; a.merit_ref = d_merit_ref; a.dz = d_dz; a.xu = d_xu; a.step = d_step; a.A = (int)num_steps;
+    a.len = (size_t)(h->n + control_size) * h->N - control_size;
+    for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) a.alpha[i] = i < num_steps ? step_sizes[i] : 0.f;
+    hipLaunchKernelGGL(line_search_step_kernel, dim3(batch), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }

@@ -121,7 +121,7 @@ class QdldlSolver:
 class PcgSolver:
     """One handle per (device, state_size, knot_points).  `solve` is the batched hot path,
     `solve_ref` the reference's single-trajectory 12-argument launch.  `control_size` is the default of
-    `form_schur` / `compute_dz` / `generate_kkt` (None: 7, the IIWA-14's)."""
+    `form_schur` / `compute_dz` / `generate_kkt` / `compute_merit` / `line_search_step` (None: 7, the IIWA-14's)."""
 
     def __init__(self, knot_points: int, max_batch: int = 1, state_size: int = STATE_SIZE, device: int | None = None,
                  control_size: int | None = None):
@@ -332,6 +332,49 @@ class PcgSolver:
         fn = self.lib.mpcg_compute_dz if dt == torch.float32 else self.lib.mpcg_compute_dz_f64
         self._check(fn(self._h, m, _ptr(Ginv_dense), _ptr(C_dense), _ptr(g), _ptr(lam), _ptr(dz), B, _stream()))
         return dz
+
+    @staticmethod
+    def _steps(step_sizes):
+        """The HOST array of step sizes both line-search calls take (copied into the launch)."""
+        vals = [float(v) for v in step_sizes]
+        return (C.c_float * len(vals))(*vals), len(vals)
+
+    def compute_merit(self, plant: "Plant", eePos_traj, xs, xu, dz, step_sizes, timestep: float, mu: float, qd_cost: float,
+                      r_cost: float, merit=None, control_size: int | None = None):
+        """ls_gato_compute_merit / compute_merit (include/common/merit.cuh:16-143), batched over trajectories and step sizes:
+        merit [B, A] float of the trial iterates xu + step_sizes[a] * dz.  xs = None: no initial-state term (the reference's compute_merit);
+        dz = None is allowed when every step size is 0."""
+        B = xu.shape[0] if xu.dim() > 1 else 1
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        arr, A = self._steps(step_sizes)
+        self._chk(eePos_traj, B * 6 * N, torch.float32, "eePos_traj")
+        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
+        if xs is not None:
+            self._chk(xs, B * n, torch.float32, "xs")
+        if dz is not None:
+            self._chk(dz, B * ((n + m) * N - m), torch.float32, "dz")
+        if merit is None:
+            merit = torch.empty(B, A, device=xu.device)
+        self._chk(merit, B * A, torch.float32, "merit")
+        self._check(self.lib.mpcg_compute_merit(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), _ptr(dz), arr, A,
+                                                float(mu), float(qd_cost), float(r_cost), _ptr(merit), B, _stream()))
+        return merit
+
+    def line_search_step(self, merit, step_sizes, merit_ref, dz, xu, step=None, control_size: int | None = None):
+        """The step selection and update of include/pcg/sqp.cuh:292-301, 317, 332-338, 352 per trajectory: the first strictly smallest merit below
+        merit_ref wins; xu and merit_ref are updated in place.  Returns the chosen index per trajectory (int32 [B], -1: no step)."""
+        B = merit_ref.numel()
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        arr, A = self._steps(step_sizes)
+        self._chk(merit, B * A, torch.float32, "merit")
+        self._chk(merit_ref, B, torch.float32, "merit_ref")
+        self._chk(dz, B * ((n + m) * N - m), torch.float32, "dz")
+        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
+        if step is None:
+            step = torch.empty(B, dtype=torch.int32, device=xu.device)
+        self._chk(step, B, torch.int32, "step")
+        self._check(self.lib.mpcg_line_search_step(self._h, m, _ptr(merit), arr, A, _ptr(merit_ref), _ptr(dz), _ptr(xu), _ptr(step), B, _stream()))
+        return step
 
     def csr_nnz(self) -> int:
         """nnz of the lower triangle (include/qdldl/sqp.cuh:148)."""
