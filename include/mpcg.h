@@ -428,12 +428,15 @@ int mpcg_qdldl_solve_schur(mpcg_handle *h, mpcg_ldl *l, const float *d_val, cons
  *       filled: -25..35 % on such batches; a scheduling hint only, no result depends on it; one extra ~3 us kernel behind each such solve.
  * "check_symmetry" (debug, 0/1: see BLOCK SYMMETRY above).
  * Around the solve: "schur_dpp" (1: mpcg_form_schur's register-resident formation — a 16-lane DPP row walks a chunk of consecutive block rows, a second
- *       kernel closes the seams between chunks; 0: the LDS kernels; same bits), "schur_chunk" (block rows per chunk: 0 = by call size, from one
- *       row per chunk for a single trajectory to 16 at 1024 x 128 knots; 1..2048 forced; same bits), "dz_dpp" (1: mpcg_compute_dz with four knots
- *       per wavefront, 0: one workgroup per knot; same bits), "block_solve_wide" (mpcg_block_solve: 1 one trajectory per wavefront, 0 four, -1 by
- *       batch size; same bits), "producers_generic" (0 / 1, default 0; 1: on a 14 x 7 handle mpcg_form_schur(_f64), mpcg_compute_dz(_f64) and
- *       mpcg_block_solve run the run-time-dimension kernels every other shape gets — same bits, the A/B switch of tests and timings;
- *       "last_schur_chunk" then reads 0), "kkt_analytic" (mpcg_generate_kkt: 1 = the analytic gradient recursion of the inverse dynamics, the default;
+ *       kernel closes the seams between chunks; 0: the LDS kernels, one workgroup per block row; same bits), "schur_chunk" (block rows per
+ *       chunk: 0 = by call size, from one row per chunk for a single trajectory to 16 at 1024 x 128 knots; 1..2048 forced; same bits), "dz_dpp"
+ *       (1: mpcg_compute_dz with four knots per wavefront, 0: the LDS kernel, one lane per element of dz; same bits), "block_solve_wide"
+ *       (mpcg_block_solve: 1 one trajectory per wavefront, 0 four, -1 by batch size; same bits), "producers_generic" (0 / 1, default 0; 1: on a
+ *       14 x 7 handle mpcg_form_schur(_f64), mpcg_compute_dz(_f64) and mpcg_block_solve run the run-time-dimension kernels every other shape
+ *       gets — same bits, the A/B switch of tests and timings; "last_schur_chunk" then reads 0).  The library has ONE set of LDS kernels, the
+ *       run-time-dimension ones: for formation and dz, "producers_generic" = 1 and "schur_dpp" = "dz_dpp" = 0 run the same kernels (the two
+ *       differ in mpcg_block_solve only, which "schur_dpp" / "dz_dpp" leave register-resident); a 14 x 7 call too large for the 31-bit byte
+ *       offsets of the register-resident kernels (from 913 k knots in float, 456 k in double) runs them as well.  "kkt_analytic" (mpcg_generate_kkt: 1 = the analytic gradient recursion of the inverse dynamics, the default;
  *       0 = one-sided float64 differences, the checker), "kkt_f32" (round 6; 1 = the analytic kernel with every recursion in float — linsys_t's own
  *       arithmetic, as the reference's GRiD<float> — and TWO knots per lane in packed float: outputs within 5e-6 of the float64 restatement (relative to max(1, |block|); worst of 1024 windows: 4e-6) instead of
  *       2e-7, 1.6x faster than the default on throughput-sized calls (0.204 against 0.330 ms per 1024 x 127 knots; a single trajectory: 20 against 16 us —

@@ -46,15 +46,15 @@ struct mpcg_handle {
     int lqk = -1;             // lane-quad-per-knot kernel in double (pcg_lqk_f64.hip.h, N <= 64): -1 auto (32 < N <= 64 once the latch says block-symmetric), 0 off, 1 forced
     int lpk = -1;             // lane-pair-per-knot kernel (pcg_lpk.hip.h, N <= 128): -1 auto (36 < N <= 128 beyond the row-per-lane kernel's calls), 0 off, 1 forced
     int block_solve_wide = -1; // mpcg_block_solve: one trajectory per wavefront (1), four (0), by batch size (-1)
-    int schur_dpp = 1;        // 1: register-resident Schur formation (schur_walk.hip.h: the chunk-walking kernel + its seam kernel), 0: the LDS versions
+    int schur_dpp = 1;        // 1: register-resident Schur formation (schur_walk.hip.h: the chunk-walking kernel + its seam kernel), 0: the LDS kernels (schur_generic.hip.h)
     int sched_hint = 1;       // dispatch the trajectories of a large call longest-expected-first, predicted by the previous call's iteration counts (sched_order_kernel)
     uint32_t* sched_order = nullptr;   // [1 + max_batch] {batch it was made for, dispatch order}: written after every hinted solve, checked on the device
     int schur_chunk = 0;      //   block rows per chunk of the walking kernel: 0 auto (by call size), 1..2048 forced
     int kkt_analytic = 1;     // mpcg_generate_kkt: 1 = analytic gradient recursion of the inverse dynamics (as the reference's GRiD code), 0 = one-sided float64 differences (the checker)
     int kkt_f32 = 0;          // mpcg_generate_kkt: 1 = the analytic kernel in float arithmetic (linsys_t's own, as the reference's GRiD<float>); 0 = float64 inside
-    int dz_dpp = 1;           // 1: four-knots-per-wavefront dz recovery (schur_walk.hip.h), 0: the one-workgroup-per-knot LDS kernel
+    int dz_dpp = 1;           // 1: four-knots-per-wavefront dz recovery (schur_walk.hip.h), 0: the LDS kernel (schur_generic.hip.h)
     int last_schur_chunk = 0; //   what the last mpcg_form_schur used (0: the LDS kernels)
-    int producers_generic = 0; // 1: form_schur(_f64), compute_dz(_f64) and block_solve of a (14, 7) call run the run-time-dimension kernels (schur_generic.hip.h) every other shape gets
+    int producers_generic = 0; // 1: form_schur(_f64), compute_dz(_f64) and block_solve of a (14, 7) call run the run-time-dimension kernels (schur_generic.hip.h) every other shape gets (formation and dz: what "schur_dpp" / "dz_dpp" = 0 run too)
     void* seam_qinv = nullptr;       // schur_walk: one Q^-1 per chunk seam (float or double; ensure_seam_buffer)
     size_t seam_qinv_bytes = 0;
     int cluster = -1;         // workgroups per trajectory of the clustered lane-pair kernel (pcg_lpk_cluster.hip.h): 0 off, -1 auto (N > 128), G > 0 forced

@@ -1,16 +1,17 @@
 // mpcg_producers.hip — C ABI (include/mpcg.h) of the steps either side of the solve: Schur + preconditioner formation, dz
-// recovery (float and linsys_t = double), the CSR emitter of the QDLDL path and the block-tridiagonal direct solve, over the gfx950 kernels
-// in schur_kernels.hip.h / schur_walk.hip.h / schur_walk_f64.hip.h / block_solve.hip.h (the tuned 14 x 7 shape) and schur_generic.hip.h
-// (every other 1 <= control_size <= state_size <= 64, and 14 x 7 under option "producers_generic").
+// recovery (float and linsys_t = double), the CSR emitter of the QDLDL path and the block-tridiagonal direct solve.  Two sets of gfx950
+// kernels serve them: the register-resident ones of schur_walk.hip.h / schur_walk_f64.hip.h / block_solve.hip.h (the tuned 14 x 7 shape,
+// the default there) and the run-time-dimension LDS kernels of schur_generic.hip.h (every other 1 <= control_size <= state_size <= 64; at
+// 14 x 7 under "schur_dpp" / "dz_dpp" = 0 or "producers_generic" = 1, and for calls beyond the register-resident kernels' 31-bit offsets).
+// Formation and dz have ONE host path each, form_schur_impl<T> and compute_dz_impl<T>; ProducerTraits<T> holds what float and double differ in.
 #include "mpcg_handle.hpp"
 #ifndef MPCG_DZ64_CAPMUL
 #define MPCG_DZ64_CAPMUL 4      // (grid cap of compute_dz_dpp_f64_kernel in units of 64 workgroups per CU; tools/_prof/dz64_ab.py)
 #endif
-#include "schur_kernels.hip.h"
+#include "schur_generic.hip.h"
 #include "schur_walk.hip.h"
 #include "schur_walk_f64.hip.h"
 #include "block_solve.hip.h"
-#include "schur_generic.hip.h"
 
 using namespace mpcg;
 
@@ -36,12 +37,12 @@ static int ensure_seam_buffer(mpcg_handle* h, size_t chunks_needed, size_t elem_
     return MPCG_OK;
 }
 
-// ---- the run-time-dimension route (schur_generic.hip.h): any 1 <= control_size <= state_size, (14, 7) only under "producers_generic" ----
+// ---- the LDS route (schur_generic.hip.h): any 1 <= control_size <= state_size; at (14, 7) whatever does not run register-resident ----
 static constexpr size_t kGenLdsMax = 160 * 1024;       // LDS of one CU: what one workgroup's operands may occupy
 
 static inline bool gen_route(const mpcg_handle* h, uint32_t control_size) { return h->generic || control_size != 7 || h->producers_generic; }
 static inline int gen_threads(int n) { return n <= 16 ? 64 : 256; }      // one wavefront up to n = 16; beyond, an n^2 update is >= 4 elements per lane of one
-// workgroups of a grid-stride launch: what the LDS kernels of the 14 x 7 path use (64 per CU), fewer when the LDS holds fewer per CU
+// workgroups of a grid-stride launch: 64 per CU, fewer when the LDS holds fewer per CU
 static inline unsigned gen_grid(const mpcg_handle* h, long items, size_t lds_bytes) {
     const long per_cu = std::min<long>(64, std::max<long>(1, (long)(kGenLdsMax / std::max<size_t>(lds_bytes, 1))));
     return (unsigned)std::max<long>(1, std::min<long>(items, (long)h->num_cus * per_cu));
@@ -56,12 +57,12 @@ static int gen_raise_lds(mpcg_handle* h, K kern, size_t lds_bytes) {      // (as
     if (lds_bytes > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     return MPCG_OK;
 }
-// the G^-1 staging buffer of the generic formation, max_batch x ((n^2 + m^2) N - m^2) elements: grows with the largest control_size seen,
+// the G^-1 staging buffer of the LDS formation, max_batch x ((n^2 + m^2) N - m^2) elements: grows with the largest control_size seen,
 // outside a stream capture only (an earlier call's kernels may still use the old one: synchronise before it goes)
 template <typename T>
-static int gen_ensure_staging(mpcg_handle* h, T** buf, size_t* have, size_t need, hipStream_t st, const char* fn) {
+static int gen_ensure_staging(mpcg_handle* h, T** buf, size_t* have, size_t need, hipStream_t st, const std::string& what) {
     if (*have >= need) return MPCG_OK;
-    { const int rc = alloc_allowed(h, st, fn); if (rc != MPCG_OK) return rc; }
+    { const int rc = alloc_allowed(h, st, what.c_str()); if (rc != MPCG_OK) return rc; }
     if (*buf) {
         HIP_TRY(h, hipDeviceSynchronize());
         HIP_TRY(h, hipFree(*buf));
@@ -72,23 +73,50 @@ static int gen_ensure_staging(mpcg_handle* h, T** buf, size_t* have, size_t need
     return MPCG_OK;
 }
 
+// What the float and the double producers differ in: the register-resident kernels and their argument struct, the handle's staging buffer
+// (one per type) and the grid cap of the dz kernel.
+template <typename T> struct ProducerTraits;
+template <> struct ProducerTraits<float> {
+    typedef sw::WalkArgs WalkArgs;
+    static constexpr auto walk_kernel = sw::schur_walk_kernel, seam_kernel = sw::schur_seam_kernel;
+    static constexpr auto dz_dpp_kernel = sw::compute_dz_dpp_kernel;
+    static constexpr auto staging = &mpcg_handle::ginv_scratch;
+    static constexpr auto staging_elems = &mpcg_handle::ginv_scratch_floats;
+    static constexpr long dz_capmul = 4;
+};
+template <> struct ProducerTraits<double> {
+    typedef sw64::WalkArgs64 WalkArgs;
+    static constexpr auto walk_kernel = sw64::schur_walk_f64_kernel, seam_kernel = sw64::schur_seam_f64_kernel;
+    static constexpr auto dz_dpp_kernel = sw64::compute_dz_dpp_f64_kernel;
+    static constexpr auto staging = &mpcg_handle::ginv_scratch_f64;
+    static constexpr auto staging_elems = &mpcg_handle::ginv_scratch_f64_elems;
+    // (126 VGPRs, four wavefronts per SIMD against the float kernel's seven: capped at 1 the 1024 x 128 call ran two quads per workgroup,
+    //  0.1165-0.1175 ms against 0.1126-0.1128 with the float kernel's cap, tools/_prof/dz64_ab.py)
+    static constexpr long dz_capmul = MPCG_DZ64_CAPMUL;
+};
+
+// The register-resident kernels address every array through a buffer resource with 31-bit byte offsets; the largest array per knot is S
+// for the formation (3 n^2 elements) and C for dz (n^2 + n m).  Calls beyond run the LDS kernels, which index with size_t.
+static constexpr uint64_t schur_bytes_per_knot(int n, size_t elem) { return (uint64_t)3 * n * n * elem; }
+static constexpr uint64_t dz_bytes_per_knot(int n, int m, size_t elem) { return (uint64_t)(n * n + n * m) * elem; }
+static_assert(schur_bytes_per_knot(14, 4) == 2352 && schur_bytes_per_knot(14, 8) == 4704, "913 k knots per call in float, 456 k in double");
+static_assert(dz_bytes_per_knot(14, 7, 4) == 1176 && dz_bytes_per_knot(14, 7, 8) == 2352, "");
+
+// The LDS formation: one workgroup per block row, G^-1 through a handle-owned staging buffer (the second kernel publishes it).
+// fn: the entry point's name, why: what sent a (14, 7) call here — both for the refusal of a first call inside a stream capture.
 template <typename T>
-static int form_schur_generic(mpcg_handle* h, const char* fn, uint32_t control_size, T* d_G, const T* d_C, const T* d_g, const T* d_c, T* d_S, T* d_Pinv,
-                              T* d_gamma, T rho, uint32_t batch, mpcg_precond precond, T** staging, size_t* staging_elems, hipStream_t st) {
-    const int n = (int)h->n, m = (int)control_size, N = (int)h->N;
+static int form_schur_lds(mpcg_handle* h, const char* fn, const char* why, SchurArgsT<T> a, hipStream_t st) {
+    typedef ProducerTraits<T> Tr;
+    const int n = a.n, m = a.m, N = a.N;
+    h->last_schur_chunk = 0;
     const size_t lds = gen::form_lds_elems(n, m) * sizeof(T), lds2 = gen::complete_lds_elems(n) * sizeof(T);
     if (lds > kGenLdsMax)
         return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": the operands of one block row (" + std::to_string(lds) + " bytes at state_size " + std::to_string(n) +
                     ", control_size " + std::to_string(m) + ") exceed the LDS limit of 160 KiB (6 n^2 + 2 n m + 2 m^2 + 12 n + 4 m elements)");
     const size_t Gsz = (size_t)(n * n + m * m) * N - (size_t)m * m;
-    { const int rc = gen_ensure_staging(h, staging, staging_elems, Gsz * h->max_batch, st, fn); if (rc != MPCG_OK) return rc; }
-    h->last_schur_chunk = 0;
-    SchurArgsT<T> a;
-    a.G = d_G; a.C = d_C; a.g = d_g; a.c = d_c; a.S = d_S; a.Pinv = d_Pinv; a.gamma = d_gamma;
-    a.Ginv_scratch = *staging; a.Ginv_out = d_G;
-    a.rho = rho; a.n = n; a.m = m; a.N = N; a.batch = (int)batch; a.ss = precond == MPCG_PRECOND_SS; a.pinv = precond != MPCG_PRECOND_NONE;
-    a.k0_only = 0;
-    const long items = (long)batch * N;
+    { const int rc = gen_ensure_staging(h, &(h->*Tr::staging), &(h->*Tr::staging_elems), Gsz * h->max_batch, st, std::string(fn) + why); if (rc != MPCG_OK) return rc; }
+    a.Ginv_scratch = h->*Tr::staging;
+    const long items = (long)a.batch * N;
     const int nt = gen_threads(n);
     { const int rc = gen_raise_lds(h, gen::form_schur_kernel<T>, lds); if (rc != MPCG_OK) return rc; }
     hipLaunchKernelGGL(gen::form_schur_kernel<T>, dim3(gen_grid(h, items, lds)), dim3(nt), lds, st, a);
@@ -99,13 +127,99 @@ static int form_schur_generic(mpcg_handle* h, const char* fn, uint32_t control_s
     return MPCG_OK;
 }
 
+// Register-resident formation (schur_walk.hip.h, schur_walk_f64.hip.h; 14 x 7): a 16-lane row walks a chunk of L consecutive block rows, a
+// second kernel closes the seams between chunks.  L trades parallelism against seam work: as long as a call has fewer than ~6 wavefronts of
+// four chunks per CU the chunks are made shorter (L = 1: every row a seam — one trajectory of the MPC loop's own call; 16 at 1024 x 128 knots).
 template <typename T>
-static int compute_dz_generic(mpcg_handle* h, uint32_t control_size, const T* d_Ginv, const T* d_C, const T* d_g, const T* d_lambda, T* d_dz, uint32_t batch,
-                              hipStream_t st) {
-    DzArgsT<T> a{d_Ginv, d_C, d_g, d_lambda, d_dz, (int)h->n, (int)control_size, (int)h->N, (int)batch};
-    const int w = (int)h->n + (int)control_size, nt = w <= 64 ? 64 : 128, kpw = nt / w;
-    const long groups = ((long)batch * h->N + kpw - 1) / kpw;
+static int form_schur_walk(mpcg_handle* h, const SchurArgsT<T>& a, hipStream_t st) {
+    typedef ProducerTraits<T> Tr;
+    int wL = h->schur_chunk;
+    if (wL <= 0) {
+        const long rows = (long)a.batch * (a.N - 1), want = (long)h->num_cus * 6 * 4;
+        wL = 1;
+        while (wL < 16 && rows / (2 * wL) >= want) wL *= 2;
+    }
+    const int wchunks = (a.N - 1 + wL - 1) / wL;
+    // seam buffer: one Q^-1 per chunk (ensure_seam_buffer: sized once for every automatic chunk length of this handle)
+    { const int rc = ensure_seam_buffer(h, (size_t)a.batch * wchunks, sizeof(T), st); if (rc != MPCG_OK) return rc; }
+    typename Tr::WalkArgs w;
+    w.s = a;                                     // (Ginv_scratch stays null: G^-1 is written in place)
+    w.seam_qinv = static_cast<T*>(h->seam_qinv); w.L = wL; w.chunks = wchunks;
+    h->last_schur_chunk = wL;
+    const long capw = (long)h->num_cus * 64;
+    long bw = ((long)a.batch * wchunks + 3) / 4;
+    if (bw > capw) bw = capw;
+    hipLaunchKernelGGL(Tr::walk_kernel, dim3((unsigned)bw), dim3(64), 0, st, w);
+    HIP_TRY(h, hipGetLastError());
+    if (wchunks > 1) {
+        long bs = ((long)a.batch * (wchunks - 1) + 3) / 4;
+        if (bs > capw) bs = capw;
+        hipLaunchKernelGGL(Tr::seam_kernel, dim3((unsigned)bs), dim3(64), 0, st, w);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return MPCG_OK;
+}
+
+// mpcg_form_schur and mpcg_form_schur_f64 (fn: the entry point's name, for its messages).  Same arithmetic order in float and double and on
+// either route: bit-identical to the oracle's instantiation for T.
+template <typename T>
+static int form_schur_impl(mpcg_handle* h, const char* fn, uint32_t control_size, T* d_G, const T* d_C, const T* d_g, const T* d_c, T* d_S, T* d_Pinv,
+                           T* d_gamma, T rho, uint32_t batch, mpcg_precond precond, void* stream) {
+    if (!h) return MPCG_ERR_INVALID;
+    if (!d_G || !d_C || !d_g || !d_c || !d_S || (!d_Pinv && precond != MPCG_PRECOND_NONE) || !d_gamma)
+        return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    { const int rc = gen_check_control(h, fn, control_size); if (rc != MPCG_OK) return rc; }
+    if (precond != MPCG_PRECOND_NONE && precond != MPCG_PRECOND_JACOBI && precond != MPCG_PRECOND_SS)
+        return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": bad preconditioner");
+    if (batch == 0) return MPCG_OK;
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
+    if ((uint64_t)batch * h->N >= (1ull << 31)) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": batch * knot_points must stay below 2^31");    // (the kernels keep a knot's index in an int)
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SchurArgsT<T> a;
+    a.G = d_G; a.C = d_C; a.g = d_g; a.c = d_c; a.S = d_S; a.Pinv = d_Pinv; a.gamma = d_gamma;
+    a.Ginv_scratch = nullptr; a.Ginv_out = d_G;
+    a.rho = rho; a.n = (int)h->n; a.m = (int)control_size; a.N = (int)h->N; a.batch = (int)batch;
+    a.ss = precond == MPCG_PRECOND_SS; a.pinv = precond != MPCG_PRECOND_NONE;
+    a.k0_only = 0;
+    if (gen_route(h, control_size)) return form_schur_lds<T>(h, fn, "", a, st);
+    if (!h->schur_dpp) return form_schur_lds<T>(h, fn, " (\"schur_dpp\" = 0)", a, st);
+    if ((uint64_t)batch * h->N * schur_bytes_per_knot(a.n, sizeof(T)) >= (1ull << 31))
+        return form_schur_lds<T>(h, fn, " (a call beyond the 31-bit offsets of the register-resident kernels)", a, st);
+    return form_schur_walk<T>(h, a, st);
+}
+
+// The LDS dz recovery: one lane per element of dz_k, a few knots per workgroup.
+template <typename T>
+static int compute_dz_lds(mpcg_handle* h, const DzArgsT<T>& a, hipStream_t st) {
+    const int w = a.n + a.m, nt = w <= 64 ? 64 : 128, kpw = nt / w;
+    const long groups = ((long)a.batch * a.N + kpw - 1) / kpw;
     hipLaunchKernelGGL(gen::compute_dz_kernel<T>, dim3(gen_grid(h, groups, 0)), dim3(nt), 0, st, a);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
+
+// mpcg_compute_dz and mpcg_compute_dz_f64
+template <typename T>
+static int compute_dz_impl(mpcg_handle* h, const char* fn, uint32_t control_size, const T* d_Ginv, const T* d_C, const T* d_g, const T* d_lambda, T* d_dz,
+                           uint32_t batch, void* stream) {
+    typedef ProducerTraits<T> Tr;
+    if (!h) return MPCG_ERR_INVALID;
+    if (!d_Ginv || !d_C || !d_g || !d_lambda || !d_dz) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    { const int rc = gen_check_control(h, fn, control_size); if (rc != MPCG_OK) return rc; }
+    if (batch == 0) return MPCG_OK;
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const DzArgsT<T> a{d_Ginv, d_C, d_g, d_lambda, d_dz, (int)h->n, (int)control_size, (int)h->N, (int)batch};
+    const uint64_t knots = (uint64_t)batch * h->N;
+    if (gen_route(h, control_size) || !h->dz_dpp || h->N < 2 || knots * dz_bytes_per_knot(a.n, a.m, sizeof(T)) >= (1ull << 31))
+        return compute_dz_lds<T>(h, a, st);
+    // four knots per wavefront (schur_walk.hip.h, schur_walk_f64.hip.h): grid-stride over quads of knots
+    const long cap = (long)h->num_cus * 64 * Tr::dz_capmul;
+    long bq = ((long)knots + 3) / 4;
+    if (bq > cap) bq = cap;
+    hipLaunchKernelGGL(Tr::dz_dpp_kernel, dim3((unsigned)bq), dim3(64), 0, st, a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
@@ -147,214 +261,24 @@ int mpcg_block_solve(mpcg_handle* h, const float* d_S, const float* d_gamma, flo
 int mpcg_form_schur(mpcg_handle* h, uint32_t control_size, float* d_G_dense, const float* d_C_dense, const float* d_g,
                     const float* d_c, float* d_S, float* d_Pinv, float* d_gamma, float rho, uint32_t batch,
                     mpcg_precond precond, void* stream) {
-    if (!h) return MPCG_ERR_INVALID;
-    if (!d_G_dense || !d_C_dense || !d_g || !d_c || !d_S || (!d_Pinv && precond != MPCG_PRECOND_NONE) || !d_gamma)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur: null device pointer");
-    { const int rc = gen_check_control(h, "mpcg_form_schur", control_size); if (rc != MPCG_OK) return rc; }
-    if (precond != MPCG_PRECOND_NONE && precond != MPCG_PRECOND_JACOBI && precond != MPCG_PRECOND_SS)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur: bad preconditioner");
-    if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur: batch exceeds max_batch");
-    if ((uint64_t)batch * h->N >= (1ull << 31)) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_form_schur: batch * knot_points must stay below 2^31");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (gen_route(h, control_size))
-        return form_schur_generic<float>(h, "mpcg_form_schur", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, rho, batch, precond,
-                                         &h->ginv_scratch, &h->ginv_scratch_floats, static_cast<hipStream_t>(stream));
-    const int n = (int)h->n, m = (int)control_size, N = (int)h->N;
-    const size_t Gsz = (size_t)(n * n + m * m) * N - m * m;
-    // Register-resident formation (schur_walk.hip.h): a 16-lane row walks a chunk of L consecutive block rows, a second kernel closes the
-    // seams between chunks.  L trades parallelism against seam work: as long as a call has fewer than ~6 wavefronts of four chunks per
-    // CU the chunks are made shorter (L = 1: every row a seam — one trajectory of the MPC loop's own call; 16 at 1024 x 128 knots).
-    // (Its kernels address every array through a buffer resource with 31-bit byte offsets: 2,352 B of S per knot => below 913 k knots.)
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (h->schur_dpp && (uint64_t)batch * N * 2352u < (1ull << 31)) {
-        int wL = h->schur_chunk;
-        if (wL <= 0) {
-            const long rows = (long)batch * (N - 1), want = (long)h->num_cus * 6 * 4;
-            wL = 1;
-            while (wL < 16 && rows / (2 * wL) >= want) wL *= 2;
-        }
-        const int wchunks = (N - 1 + wL - 1) / wL;
-        // seam buffer: one Q^-1 per chunk (ensure_seam_buffer: sized once for every automatic chunk length of this handle)
-        { const int rc_ = ensure_seam_buffer(h, (size_t)batch * wchunks, sizeof(float), st); if (rc_ != MPCG_OK) return rc_; }
-        sw::WalkArgs w;
-        w.s.G = d_G_dense; w.s.C = d_C_dense; w.s.g = d_g; w.s.c = d_c; w.s.S = d_S; w.s.Pinv = d_Pinv; w.s.gamma = d_gamma;
-        w.s.Ginv_scratch = nullptr; w.s.Ginv_out = d_G_dense;
-        w.s.rho = rho; w.s.n = n; w.s.m = m; w.s.N = N; w.s.batch = (int)batch; w.s.ss = precond == MPCG_PRECOND_SS; w.s.pinv = precond != MPCG_PRECOND_NONE;
-        w.s.k0_only = 0;
-        w.seam_qinv = static_cast<float*>(h->seam_qinv); w.L = wL; w.chunks = wchunks;
-        h->last_schur_chunk = wL;
-        const long capw = (long)h->num_cus * 64;
-        long bw = ((long)batch * wchunks + 3) / 4;
-        if (bw > capw) bw = capw;
-        hipLaunchKernelGGL(sw::schur_walk_kernel, dim3((unsigned)bw), dim3(64), 0, st, w);
-        HIP_TRY(h, hipGetLastError());
-        if (wchunks > 1) {
-            long bs = ((long)batch * (wchunks - 1) + 3) / 4;
-            if (bs > capw) bs = capw;
-            hipLaunchKernelGGL(sw::schur_seam_kernel, dim3((unsigned)bs), dim3(64), 0, st, w);
-            HIP_TRY(h, hipGetLastError());
-        }
-        return MPCG_OK;
-    }
-    h->last_schur_chunk = 0;
-    // the LDS kernels (schur_kernels.hip.h; option "schur_dpp" = 0, and calls beyond the 31-bit offsets above): one wavefront per knot,
-    // G^-1 through a handle-owned staging buffer
-    const size_t need = Gsz * h->max_batch;
-    if (h->ginv_scratch_floats < need) {          // first call only (not stream-ordered: hipMalloc)
-        { const int rc = alloc_allowed(h, st, "mpcg_form_schur (\"schur_dpp\" = 0)"); if (rc != MPCG_OK) return rc; }
-        if (h->ginv_scratch) HIP_TRY(h, hipFree(h->ginv_scratch));
-        h->ginv_scratch = nullptr; h->ginv_scratch_floats = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->ginv_scratch), need * sizeof(float)));
-        h->ginv_scratch_floats = need;
-    }
-    SchurArgs a;
-    a.G = d_G_dense; a.C = d_C_dense; a.g = d_g; a.c = d_c; a.S = d_S; a.Pinv = d_Pinv; a.gamma = d_gamma;
-    a.Ginv_scratch = h->ginv_scratch; a.Ginv_out = d_G_dense;
-    a.rho = rho; a.n = n; a.m = m; a.N = N; a.batch = (int)batch; a.ss = precond == MPCG_PRECOND_SS; a.pinv = precond != MPCG_PRECOND_NONE;
-    a.k0_only = 0;
-    long blocks = (long)batch * N;
-    const long cap = (long)h->num_cus * 64;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((form_schur_kernel<14, 7>), dim3((unsigned)blocks), dim3(SCH_THREADS), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    hipLaunchKernelGGL((complete_ss_kernel<14, 7>), dim3((unsigned)blocks), dim3(SCH_THREADS), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    return MPCG_OK;
+    return form_schur_impl<float>(h, "mpcg_form_schur", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, rho, batch, precond, stream);
 }
 
 int mpcg_compute_dz(mpcg_handle* h, uint32_t control_size, const float* d_Ginv_dense, const float* d_C_dense,
                     const float* d_g, const float* d_lambda, float* d_dz, uint32_t batch, void* stream) {
-    if (!h) return MPCG_ERR_INVALID;
-    if (!d_Ginv_dense || !d_C_dense || !d_g || !d_lambda || !d_dz)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_compute_dz: null device pointer");
-    { const int rc = gen_check_control(h, "mpcg_compute_dz", control_size); if (rc != MPCG_OK) return rc; }
-    if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_dz: batch exceeds max_batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (gen_route(h, control_size)) return compute_dz_generic<float>(h, control_size, d_Ginv_dense, d_C_dense, d_g, d_lambda, d_dz, batch, static_cast<hipStream_t>(stream));
-    DzArgs a{d_Ginv_dense, d_C_dense, d_g, d_lambda, d_dz, (int)h->n, (int)control_size, (int)h->N, (int)batch};
-    long blocks = (long)batch * h->N;
-    const long cap = (long)h->num_cus * 64;
-    if (blocks > cap) blocks = cap;
-    if (h->dz_dpp && h->N >= 2 && (uint64_t)batch * h->N * 1176u < (1ull << 31)) {     // (31-bit byte offsets into C)
-        long b4 = ((long)batch * h->N + 3) / 4;
-        if (b4 > cap * 4) b4 = cap * 4;
-        hipLaunchKernelGGL(sw::compute_dz_dpp_kernel, dim3((unsigned)b4), dim3(64), 0, static_cast<hipStream_t>(stream), a);
-    } else {
-        hipLaunchKernelGGL((compute_dz_kernel<14, 7>), dim3((unsigned)blocks), dim3(SCH_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return MPCG_OK;
+    return compute_dz_impl<float>(h, "mpcg_compute_dz", control_size, d_Ginv_dense, d_C_dense, d_g, d_lambda, d_dz, batch, stream);
 }
 
-
-// ---- linsys_t = double (USE_DOUBLES = 1, include/common/settings.cuh:41-49): the steps either side of the solve in double precision.
-// Round 5: the walking formation and the four-knots-per-wavefront dz recovery in double (schur_walk_f64.hip.h); options "schur_dpp" / "dz_dpp"
-// = 0 select the one-wavefront-per-knot LDS kernels of schur_kernels.hip.h instantiated for double.  Same arithmetic order as the float path,
-// bit-identical to the oracle's double instantiation either way. ----
+// linsys_t = double (USE_DOUBLES = 1, include/common/settings.cuh:41-49): the steps either side of the solve in double precision
 int mpcg_form_schur_f64(mpcg_handle* h, uint32_t control_size, double* d_G_dense, const double* d_C_dense, const double* d_g,
                         const double* d_c, double* d_S, double* d_Pinv, double* d_gamma, double rho, uint32_t batch,
                         mpcg_precond precond, void* stream) {
-    if (!h) return MPCG_ERR_INVALID;
-    if (!d_G_dense || !d_C_dense || !d_g || !d_c || !d_S || (!d_Pinv && precond != MPCG_PRECOND_NONE) || !d_gamma)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur_f64: null device pointer");
-    { const int rc = gen_check_control(h, "mpcg_form_schur_f64", control_size); if (rc != MPCG_OK) return rc; }
-    if (precond != MPCG_PRECOND_NONE && precond != MPCG_PRECOND_JACOBI && precond != MPCG_PRECOND_SS)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur_f64: bad preconditioner");
-    if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_form_schur_f64: batch exceeds max_batch");
-    if ((uint64_t)batch * h->N >= (1ull << 31)) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_form_schur_f64: batch * knot_points must stay below 2^31");     // (as mpcg_form_schur: the LDS kernels index knots with int)
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (gen_route(h, control_size))
-        return form_schur_generic<double>(h, "mpcg_form_schur_f64", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, rho, batch, precond,
-                                          &h->ginv_scratch_f64, &h->ginv_scratch_f64_elems, static_cast<hipStream_t>(stream));
-    const int n = (int)h->n, m = (int)control_size, N = (int)h->N;
-    const size_t Gsz = (size_t)(n * n + m * m) * N - m * m;
-    // Round 5: the register-resident formation in double (schur_walk_f64.hip.h) — the float path's design, chunk policy and seam buffer; its
-    // buffer resources carry 31-bit byte offsets: 4,704 B of S per knot => below 456 k knots per call (beyond: the LDS kernels).
-    if (h->schur_dpp && (uint64_t)batch * N * 4704u < (1ull << 31)) {
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        int wL = h->schur_chunk;
-        if (wL <= 0) {
-            const long rows = (long)batch * (N - 1), want = (long)h->num_cus * 6 * 4;
-            wL = 1;
-            while (wL < 16 && rows / (2 * wL) >= want) wL *= 2;
-        }
-        const int wchunks = (N - 1 + wL - 1) / wL;
-        { const int rc_ = ensure_seam_buffer(h, (size_t)batch * wchunks, sizeof(double), st); if (rc_ != MPCG_OK) return rc_; }
-        sw64::WalkArgs64 w;
-        w.s.G = d_G_dense; w.s.C = d_C_dense; w.s.g = d_g; w.s.c = d_c; w.s.S = d_S; w.s.Pinv = d_Pinv; w.s.gamma = d_gamma;
-        w.s.Ginv_scratch = nullptr; w.s.Ginv_out = d_G_dense;
-        w.s.rho = rho; w.s.n = n; w.s.m = m; w.s.N = N; w.s.batch = (int)batch; w.s.ss = precond == MPCG_PRECOND_SS; w.s.pinv = precond != MPCG_PRECOND_NONE;
-        w.s.k0_only = 0;
-        w.seam_qinv = static_cast<double*>(h->seam_qinv); w.L = wL; w.chunks = wchunks;
-        h->last_schur_chunk = wL;
-        const long capw = (long)h->num_cus * 64;
-        long bw = ((long)batch * wchunks + 3) / 4;
-        if (bw > capw) bw = capw;
-        hipLaunchKernelGGL(sw64::schur_walk_f64_kernel, dim3((unsigned)bw), dim3(64), 0, st, w);
-        HIP_TRY(h, hipGetLastError());
-        if (wchunks > 1) {
-            long bs = ((long)batch * (wchunks - 1) + 3) / 4;
-            if (bs > capw) bs = capw;
-            hipLaunchKernelGGL(sw64::schur_seam_f64_kernel, dim3((unsigned)bs), dim3(64), 0, st, w);
-            HIP_TRY(h, hipGetLastError());
-        }
-        return MPCG_OK;
-    }
-    h->last_schur_chunk = 0;
-    const size_t need = Gsz * h->max_batch;
-    if (h->ginv_scratch_f64_elems < need) {       // first call only (not stream-ordered: hipMalloc)
-        { const int rc = alloc_allowed(h, static_cast<hipStream_t>(stream), "mpcg_form_schur_f64 (\"schur_dpp\" = 0)"); if (rc != MPCG_OK) return rc; }
-        if (h->ginv_scratch_f64) HIP_TRY(h, hipFree(h->ginv_scratch_f64));
-        h->ginv_scratch_f64 = nullptr; h->ginv_scratch_f64_elems = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->ginv_scratch_f64), need * sizeof(double)));
-        h->ginv_scratch_f64_elems = need;
-    }
-    SchurArgsT<double> a;
-    a.G = d_G_dense; a.C = d_C_dense; a.g = d_g; a.c = d_c; a.S = d_S; a.Pinv = d_Pinv; a.gamma = d_gamma;
-    a.Ginv_scratch = h->ginv_scratch_f64; a.Ginv_out = d_G_dense;
-    a.rho = rho; a.n = n; a.m = m; a.N = N; a.batch = (int)batch; a.ss = precond == MPCG_PRECOND_SS; a.pinv = precond != MPCG_PRECOND_NONE;
-    a.k0_only = 0;
-    long blocks = (long)batch * N;
-    const long cap = (long)h->num_cus * 64;
-    if (blocks > cap) blocks = cap;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL((form_schur_kernel<14, 7, double>), dim3((unsigned)blocks), dim3(SCH_THREADS), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    hipLaunchKernelGGL((complete_ss_kernel<14, 7, double>), dim3((unsigned)blocks), dim3(SCH_THREADS), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
-    return MPCG_OK;
+    return form_schur_impl<double>(h, "mpcg_form_schur_f64", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, rho, batch, precond, stream);
 }
 
 int mpcg_compute_dz_f64(mpcg_handle* h, uint32_t control_size, const double* d_Ginv_dense, const double* d_C_dense,
                         const double* d_g, const double* d_lambda, double* d_dz, uint32_t batch, void* stream) {
-    if (!h) return MPCG_ERR_INVALID;
-    if (!d_Ginv_dense || !d_C_dense || !d_g || !d_lambda || !d_dz)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_compute_dz_f64: null device pointer");
-    { const int rc = gen_check_control(h, "mpcg_compute_dz_f64", control_size); if (rc != MPCG_OK) return rc; }
-    if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_dz_f64: batch exceeds max_batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (gen_route(h, control_size)) return compute_dz_generic<double>(h, control_size, d_Ginv_dense, d_C_dense, d_g, d_lambda, d_dz, batch, static_cast<hipStream_t>(stream));
-    DzArgsT<double> a{d_Ginv_dense, d_C_dense, d_g, d_lambda, d_dz, (int)h->n, (int)control_size, (int)h->N, (int)batch};
-    long blocks = (long)batch * h->N;
-    const long cap = (long)h->num_cus * 64;
-    if (h->dz_dpp && h->N >= 2 && (uint64_t)batch * h->N * 2352u < (1ull << 31)) {      // four knots per wavefront (schur_walk_f64.hip.h); 31-bit byte offsets into C
-        // (grid-stride over quads of knots, capped like the float kernel at 4 x cap one-wavefront workgroups.  Round 5 capped this one at cap —
-        //  126 VGPRs, four wavefronts per SIMD against the float kernel's seven — which left the 1024 x 128 call two quads per workgroup:
-        //  0.1165-0.1175 ms against 0.1126-0.1128 with the float kernel's cap, tools/_prof/dz64_ab.py)
-        long bq = (blocks + 3) / 4;
-        if (bq > cap * MPCG_DZ64_CAPMUL) bq = cap * MPCG_DZ64_CAPMUL;
-        hipLaunchKernelGGL(sw64::compute_dz_dpp_f64_kernel, dim3((unsigned)bq), dim3(64), 0, static_cast<hipStream_t>(stream), a);
-        HIP_TRY(h, hipGetLastError());
-        return MPCG_OK;
-    }
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((compute_dz_kernel<14, 7, double>), dim3((unsigned)blocks), dim3(SCH_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    HIP_TRY(h, hipGetLastError());
-    return MPCG_OK;
+    return compute_dz_impl<double>(h, "mpcg_compute_dz_f64", control_size, d_Ginv_dense, d_C_dense, d_g, d_lambda, d_dz, batch, stream);
 }
 
 int mpcg_prep_csr(mpcg_handle* h, int32_t* d_col_ptr, int32_t* d_row_ind, void* stream) {

@@ -1,11 +1,22 @@
 // schur_generic.hip.h — the steps either side of the PCG for ANY state and control size (1 <= m <= n <= 64), gfx950 HIP:
 //   gen::form_schur_kernel + gen::complete_ss_kernel   (G, C, g, c, rho) -> (S, Pinv, gamma), G <- G^-1
-//   gen::compute_dz_kernel                             dz = G^-1 (g - C^T lambda)
+//        replaces form_S_gamma_Pinv_kernel / form_schur_system (include/pcg/linsys_setup.cuh:565-656)
+//   gen::compute_dz_kernel                             dz = G^-1 (g - C^T lambda)      replaces compute_dz (include/common/dz.cuh:3-136)
 //   gen::bt_block_solve_kernel                         block-tridiagonal direct solve of S lambda = gamma (float)
-// Semantics, operation order and therefore BITS are those of schur_kernels.hip.h / block_solve.hip.h (contraction off, sequential inner
-// products, pivot-free Gauss-Jordan: pivot row scaled by 1 / pivot, then eliminated from every other row); only the dimensions are
-// run-time values and the operands live in DYNAMIC LDS sized from (n, m).  The tuned 14 x 7 kernels stay what (14, 7) runs by default;
-// option "producers_generic" = 1 sends that shape here too (the A/B switch of the tests).
+// and, ahead of them, what every producer kernel of the library shares: the argument structs of formation and dz (the register-resident
+// kernels of schur_walk.hip.h / schur_walk_f64.hip.h take the same ones) and the two CSR kernels of the QDLDL path.
+//
+// Arithmetic follows the reference operation for operation and is written with contraction OFF, sequential inner products and pivot-free
+// Gauss-Jordan (pivot row scaled by 1 / pivot, then eliminated from every other row), so that it is BIT-IDENTICAL to the C oracle
+// (oracle/mpcg_oracle_impl.inc, built with -ffp-contract=off) — the parity tests compare bits, not tolerances.  The dimensions are run-time
+// values and the operands live in DYNAMIC LDS sized from (n, m).  These are the library's only LDS producers: every shape other than 14 x 7
+// runs them, and 14 x 7 — whose default is the register-resident kernels — runs them under "schur_dpp" / "dz_dpp" = 0, under
+// "producers_generic" = 1 and for calls beyond the register-resident kernels' 31-bit byte offsets.
+//
+// The reference runs both halves of the Schur formation in one cooperative kernel with a grid sync between them (:600); a kernel boundary
+// (~1.5 us on this chip) is cheaper than any grid barrier, so they are two launches here.  The reference also overwrites G with its block
+// inverses while other blocks may still be reading the raw blocks (row k writes slot k-1 which row k-1 reads, :321 vs :372 — a benign race
+// there); here the first kernel writes the inverses to a staging buffer and the second copies them into G.
 //
 // Mapping.  A workgroup of blockDim.x = 64 (n <= 16) or 256 threads owns one block row (formation, completion), a few knots (dz) or one
 // trajectory (block solve).  Over an operand with `rows` rows a thread keeps ONE row r = tid % rows and walks the columns c0, c0 + cs, ...
@@ -18,12 +29,68 @@
 // update) and the transposition of phi, which walks the columns skewed by the row ((q + r) mod n) so that read and write both spread
 // over the banks.
 #pragma once
-#include "schur_kernels.hip.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace mpcg {
-namespace gen {
+
+constexpr int SCH_THREADS = 64;      // workgroup of the CSR kernels
+
+template <typename T>
+struct SchurArgsT {
+    const T* G; const T* C; const T* g; const T* c;
+    T* S; T* Pinv; T* gamma; T* Ginv_scratch; T* Ginv_out;
+    T rho; int n; int m; int N; int batch; int ss;
+    int pinv;                 // 0: S and gamma only (no Pinv block is computed or written)
+    int k0_only;              // reserved, always 0 (no kernel reads it; it stays so that the kernel arguments keep their offsets)
+};
+typedef SchurArgsT<float> SchurArgs;
+
+template <typename T>
+struct DzArgsT { const T* Ginv; const T* C; const T* g; const T* lambda; T* dz; int n; int m; int N; int batch; };
+typedef DzArgsT<float> DzArgs;
 
 #pragma clang fp contract(off)
+
+// ---- CSR side of the QDLDL twin ----
+// prep_csr_kernel: pattern of the lower triangle of a symmetric block-tridiagonal matrix, exactly
+// include/utils/csr.cuh:40-73 (row (k,i) holds (k>0)*n + i+1 entries, first column (k>0)*(k-1)*n).
+__global__ __launch_bounds__(SCH_THREADS) void prep_csr_kernel(int n, int N, int* col_ptr, int* row_ind) {
+    const int brow = n * n + (n * (n + 1)) / 2;
+    for (int k = blockIdx.x; k < N; k += gridDim.x)
+        for (int row = threadIdx.x; row < n; row += SCH_THREADS) {
+            if (k == 0 && row == 0) col_ptr[0] = 0;
+            const int tri = ((row + 1) * row) / 2;
+            const int off = (k > 0) * ((n + 1) * n) / 2 + (k > 0) * (k - 1) * brow + (k > 0) * row * n + tri;
+            const int len = (k > 0) * n + row + 1;
+            col_ptr[k * n + row + 1] = off + len;
+            for (int c = 0; c < len; ++c) row_ind[off + c] = (k > 0) * (k - 1) * n + c;
+        }
+}
+// values: what form_schur_qdl_kernel leaves in d_val (include/qdldl/linsys_setup.cuh:12-336 via
+// store_block_csr_lowertri, include/utils/csr.cuh:9-36), gathered from the bd-layout S that
+// mpcg_form_schur produced: left block S[k,0] then the lower triangle of S[k,1], scaled by mult.
+struct CsrArgs { const float* S; float* val; float mult; int n; int N; int batch; };
+__global__ __launch_bounds__(SCH_THREADS) void bd_to_csr_kernel(CsrArgs a) {
+    const int n = a.n, N = a.N, nn = n * n;
+    const int brow = nn + (n * (n + 1)) / 2;
+    const size_t nnz = (size_t)(N - 1) * nn + (size_t)N * ((n * (n + 1)) / 2);
+    for (long item = blockIdx.x; item < (long)a.batch * N; item += gridDim.x) {
+        const int b = (int)(item / N), k = (int)(item % N);
+        const float* Sk = a.S + ((size_t)b * N + k) * 3 * nn;
+        float* val = a.val + (size_t)b * nnz;
+        const int per_row_max = n + n;
+        for (int e = threadIdx.x; e < n * per_row_max; e += SCH_THREADS) {
+            const int row = e / per_row_max, c = e % per_row_max;
+            const int tri = ((row + 1) * row) / 2;
+            const int off = (k > 0) * ((n + 1) * n) / 2 + (k > 0) * (k - 1) * brow + (k > 0) * row * n + tri;
+            if (k > 0 && c < n) val[off + c] = a.mult * Sk[row + c * n];                               // left block
+            else if (c >= n && c - n <= row) val[off + (k > 0) * n + (c - n)] = a.mult * Sk[nn + row + (c - n) * n];   // diagonal block
+        }
+    }
+}
+
+namespace gen {
 
 struct Lane { int r, c0, cs; };      // this thread's row, first column and column step over an operand with `rows` rows (idle: c0 beyond any column)
 __device__ __forceinline__ Lane lane_of(int rows) {
@@ -88,8 +155,8 @@ __device__ __forceinline__ void g_invert(const Lane l, int n, T* A, T* Ainv, T* 
         __syncthreads();
     }
 }
-// The three inversions of a block row (Q_k, Q_{k+1}: n x n; R_k: m x m, m <= n) advanced in lock-step, as w_invert3: the arithmetic of
-// three g_invert calls per element, a third of the barriers.  m = n is the boundary case (every pivot step touches all three).
+// The three inversions of a block row (Q_k, Q_{k+1}: n x n; R_k: m x m, m <= n) advanced in lock-step (the reference inverts them together too:
+// invertMatrix<T>(dimA, dimB, dimC, ...), include/utils/matrix.cuh): the arithmetic of three g_invert calls per element, a third of the barriers.  m = n is the boundary case (every pivot step touches all three).
 // scr: 3 (2 n + m).  Ends on a barrier.
 template <typename T>
 __device__ __forceinline__ void g_invert3(const Lane ln, const Lane lm, int n, T* A1, T* I1, T* A2, T* I2, int m, T* A3, T* I3, T* scr) {
@@ -130,7 +197,7 @@ __host__ __device__ constexpr size_t form_lds_elems(int n, int m) {
 }
 __host__ __device__ constexpr size_t complete_lds_elems(int n) { return (size_t)6 * n * n; }
 
-// block row k of trajectory b: S[k,0], S[k,1], S[k-1,2], Pinv[k,1], gamma[k]; inverses -> staging buffer (form_schur_kernel of schur_kernels.hip.h)
+// block row k of trajectory b: S[k,0], S[k,1], S[k-1,2], Pinv[k,1], gamma[k]; inverses -> staging buffer (linsys_setup.cuh:139-562)
 template <typename T>
 __global__ __launch_bounds__(256) void form_schur_kernel(SchurArgsT<T> a) {
     extern __shared__ __align__(16) unsigned char gen_smem[];
@@ -231,7 +298,7 @@ __global__ __launch_bounds__(256) void form_schur_kernel(SchurArgsT<T> a) {
     }
 }
 
-// symmetric-stair completion + publication of G^-1 (complete_ss_kernel of schur_kernels.hip.h).  phi_{k+1}^T enters its product as the
+// symmetric-stair completion + publication of G^-1 (linsys_setup.cuh:9-137).  phi_{k+1}^T enters its product as the
 // transposed operand (B stored k x n): the same sums in the same order as a transposed load followed by a plain product.
 template <typename T>
 __global__ __launch_bounds__(256) void complete_ss_kernel(SchurArgsT<T> a) {
@@ -274,7 +341,7 @@ __global__ __launch_bounds__(256) void complete_ss_kernel(SchurArgsT<T> a) {
     }
 }
 
-// dz recovery (compute_dz_kernel of schur_kernels.hip.h): one lane per element of dz_k, blockDim.x / (n + m) knots per workgroup
+// dz recovery (include/common/dz.cuh:3-121: dz_x = Qi (q - lambda_k - Abar^T lambda_{k+1}), dz_u = Ri (r - Bbar^T lambda_{k+1})): one lane per element of dz_k, blockDim.x / (n + m) knots per workgroup
 // (every output is one sequential inner product, so a knot cannot use more than n + m lanes).  blockDim.x >= n + m.
 template <typename T>
 __global__ __launch_bounds__(128) void compute_dz_kernel(DzArgsT<T> a) {

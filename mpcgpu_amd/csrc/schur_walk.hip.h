@@ -27,7 +27,7 @@
 #include <stdint.h>
 #include <type_traits>
 
-#include "schur_kernels.hip.h"
+#include "schur_generic.hip.h"
 
 namespace mpcg {
 namespace sw {

@@ -23,7 +23,7 @@ def dev(a):
 def test_form_schur_bit_exact_vs_oracle(orc, N, precond, formation):
     """The register-resident formation (schur_walk.hip.h: chunk-walking kernel + seam kernel) with L block rows per chunk — auto: what a
     call of this size gets by itself (L = 1 here: every row a seam), 16 (one chunk up to N = 17, eight at N = 128), 5 (ragged last chunk, many
-    seams), 1 — and the LDS kernels of schur_kernels.hip.h ("schur_dpp" = 0).  All the oracle's bits."""
+    seams), 1 — and the LDS kernels of schur_generic.hip.h ("schur_dpp" = 0).  All the oracle's bits."""
     from mpcgpu_amd import PcgSolver
     B = 5                                             # (a wavefront of four chunks straddles trajectories)
     k = synth.make_kkt(N, B, 555 + N)
@@ -113,7 +113,7 @@ def test_form_schur_formations_agree_at_throughput_sized_batches():
 @pytest.mark.parametrize("dz_dpp", [1, 0])
 @pytest.mark.parametrize("N", [2, 3, 9, 128])
 def test_compute_dz_bit_exact_vs_oracle(orc, N, dz_dpp):
-    """dz_dpp = 1: the four-knots-per-wavefront kernel (round 4, default), 0: the one-workgroup-per-knot LDS kernel."""
+    """dz_dpp = 1: the four-knots-per-wavefront kernel (round 4, default), 0: the LDS kernel of schur_generic.hip.h."""
     from mpcgpu_amd import PcgSolver
     B = 3
     k = synth.make_kkt(N, B, 77 + N)
@@ -129,6 +129,40 @@ def test_compute_dz_bit_exact_vs_oracle(orc, N, dz_dpp):
     Ginv = dG.cpu().numpy()
     for b in range(B):
         np.testing.assert_array_equal(dz[b], orc.compute_dz(Ginv[b], C[b], g[b], lam[b], N))
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_producer_routes_switched_on_one_handle_give_the_same_bits(dtype):
+    """The routing of formation and dz at 14 x 7, switched back and forth on ONE handle (shared staging and seam buffers): "schur_dpp" =
+    "dz_dpp" = 0 and "producers_generic" = 1 both run the LDS kernels of schur_generic.hip.h ("last_schur_chunk" 0), the default the
+    register-resident ones (one row per chunk here).  S, Pinv, gamma, G^-1 and dz bit for bit the same, unwritten slots (NaN) included."""
+    from mpcgpu_amd import PcgSolver
+    N, B = 3, 5
+    tdt = torch.float32 if dtype == np.float32 else torch.float64
+    k = synth.make_kkt(N, B, 2718)
+    G, C, g, c = synth.pack_kkt_dense(k, dtype)
+    lam = dev(np.random.default_rng(3).normal(size=(B, n * N)).astype(dtype))
+    sol = PcgSolver(N, max_batch=B)
+    outs, chunks = [], []
+    for opts in ({"schur_dpp": 0, "dz_dpp": 0, "producers_generic": 0}, {"schur_dpp": 1, "dz_dpp": 1, "producers_generic": 1},
+                 {"schur_dpp": 1, "dz_dpp": 1, "producers_generic": 0}):
+        for key, v in opts.items():
+            sol.set_option(key, v)
+        dG = dev(G)
+        S = torch.full((B, 3 * n * n * N), float("nan"), device="cuda", dtype=tdt)
+        P = torch.full((B, 3 * n * n * N), float("nan"), device="cuda", dtype=tdt)
+        gam = torch.full((B, n * N), float("nan"), device="cuda", dtype=tdt)
+        dz = torch.full((B, (n + m) * N - m), float("nan"), device="cuda", dtype=tdt)
+        sol.form_schur(dG, dev(C), dev(g), dev(c), 1e-3, "ss", S=S, Pinv=P, gamma=gam)
+        chunks.append(sol.get_option("last_schur_chunk"))
+        sol.compute_dz(dG, dev(C), dev(g), lam, dz=dz)
+        torch.cuda.synchronize()
+        outs.append([t.cpu().numpy() for t in (S, P, gam, dG, dz)])
+    assert chunks == [0, 0, 1], chunks
+    assert np.isnan(outs[0][0]).any() and not np.isnan(outs[0][0]).all() and not np.isnan(outs[0][4]).any()
+    for other in outs[1:]:
+        for a0, a1 in zip(outs[0], other):
+            np.testing.assert_array_equal(a0, a1)
 
 
 def test_kkt_to_step_pipeline_vs_float64_kkt_solve(orc):

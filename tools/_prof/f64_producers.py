@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""linsys_t = double: mpcg_form_schur_f64 / mpcg_compute_dz_f64 (the round-1 LDS kernels instantiated for double) at B x N knots."""
+"""linsys_t = double: mpcg_form_schur_f64 / mpcg_compute_dz_f64 at B x N knots."""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -2,12 +2,16 @@
 """Time the steps either side of the solve at any (state_size, control_size):  time_producers.py [--state n] [--control m] [--knots N] [--batch B]
 [--generic] [--json] — mpcg_form_schur (symmetric stair), mpcg_compute_dz and mpcg_block_solve, each with its rate on the shape's own
 algorithmic HBM bytes (formation: G, C, g, c in, S, Pinv, gamma, G^-1 out; dz: G^-1, C, g, lambda in, dz out; block solve: S, gamma in,
-lambda out).  At 14 x 7 three routes are timed: the default (register-resident) kernels, the compile-time LDS kernels ("schur_dpp" = "dz_dpp"
-= 0) and, with --generic, the run-time-dimension kernels of schur_generic.hip.h ("producers_generic" = 1) every other shape runs anyway."""
-import argparse, json, os, sys
+lambda out).  At 14 x 7 the default (register-resident) kernels are timed and, with --generic, the run-time-dimension LDS kernels of
+schur_generic.hip.h ("producers_generic" = 1) every other shape runs anyway (for formation and dz also what "schur_dpp" = "dz_dpp" = 0 runs).
+Every figure is the median of seven timed calls behind 50 ms of back-to-back calls."""
+import argparse, json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from mpcgpu_amd import _lib as _L
+if os.environ.get("AB_LIB"):                      # A/B against another build of the library
+    _L.LIB_PATH = os.environ["AB_LIB"]
 from mpcgpu_amd import PcgSolver, synth
 
 ap = argparse.ArgumentParser()
@@ -44,6 +48,10 @@ lam = torch.randn(B, n * N, device="cuda"); dz = torch.empty(B, (n + m) * N - m,
 
 
 def t(fn, restore=False, reps=9):
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.05:           # back-to-back warm-up: the clocks are up before anything is timed
+        fn()
+        torch.cuda.synchronize()
     ts = []
     for _ in range(reps):
         if restore:
@@ -58,7 +66,7 @@ nn, mm, nm = n * n, m * m, n * m
 model = {"form_schur": 4 * (9 * nn + 2 * mm + nm + 3 * n + m), "compute_dz": 4 * (2 * nn + mm + nm + 3 * n + 2 * m), "block_solve": 4 * (3 * nn + 2 * n)}
 routes = [("default", {})]
 if tuned:
-    routes = [("default", {"schur_dpp": 1, "dz_dpp": 1, "producers_generic": 0}), ("lds", {"schur_dpp": 0, "dz_dpp": 0, "producers_generic": 0})]
+    routes = [("default", {"schur_dpp": 1, "dz_dpp": 1, "producers_generic": 0})]
     if a.generic:
         routes.append(("generic", {"producers_generic": 1}))
 for route, opts in routes:
