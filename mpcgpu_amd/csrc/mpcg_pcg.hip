@@ -78,7 +78,7 @@ const char* mpcg_build_info(void) {
 // device scratch of the clustered kernel: [queue line][flags: one 128-byte line per trajectory of the CALL, up to max_batch][cells: 1 KB
 // per member of the launch, up to two members per CU]
 static size_t cluster_alloc_words(const mpcg_handle* h) {
-    return (size_t)2 * h->num_cus * LPBC_WG_WORDS + CL_FLAG_STRIDE + (size_t)h->max_batch * CL_FLAG_STRIDE
+    return (size_t)2 * h->num_cus * LPKC_WG_WORDS + CL_FLAG_STRIDE + (size_t)h->max_batch * CL_FLAG_STRIDE
            + 16;                         // + one line for the "cluster_fixups" counter (never re-zeroed by a launch)
 }
 static unsigned long long* fixup_counter(const mpcg_handle* h) { return h->cluster_scratch + cluster_alloc_words(h) - 16; }
@@ -687,13 +687,13 @@ static PcgPlan plan_f32(const mpcg_handle* h, uint32_t batch, int esz, int pcols
     p.check = use_lpk(h, esz, batch) || (h->cluster != 0 && (h->cluster > 0 || N > kLpbMaxN));                // (quirk: without the auto_cfg test of `lower`)
     p.lower = use_lpk(h, esz, batch) || (h->cluster != 0 && (h->cluster > 0 || (h->auto_cfg && N > kLpbMaxN)));   // (quirk: also when cluster_members refuses G)
     if (use_lpk(h, esz, batch)) { p.k = plan_lpk(h, esz, pcols, &p.last); p.order = true; return p; }
-    p.G = h->cluster == 0 || (h->cluster < 0 && (!h->auto_cfg || N <= kLpbMaxN)) ? 0 : cluster_members(h, 128, LPBC_MAX_G);
+    p.G = h->cluster == 0 || (h->cluster < 0 && (!h->auto_cfg || N <= kLpbMaxN)) ? 0 : cluster_members(h, 128, LPKC_MAX_G);
     if (p.G) {
         // G CUs per trajectory, 128 knots per member in registers (pcg_lpk_cluster.hip.h); the fix-up: the lane-pair kernel's launch up to
         // 128 knots — a GATED call's fix-up must read all three columns (every completion count is 0 after a gated exit: ADVICE r04) — else
         // pcg_traj_kernel with the knobs of a batch-1 call (quirk: whatever the call's batch and auto_cfg)
         p.resident = cluster_resident(h, p.G);
-        p.member_words = LPBC_WG_WORDS; p.lam_esz = sizeof(float);
+        p.member_words = LPKC_WG_WORDS; p.lam_esz = sizeof(float);
         p.k = make_launch(pcg_lpkc_kernel<2>, 512, pcg_lpkc_lds_floats(8) * sizeof(float));
         p.last = LastKernel{FAM_LPKC, 8, 0, 0, 0, p.G, (int)p.k.lds, 0};
         PcgKnobs kf = h->k;

@@ -708,74 +708,6 @@ __global__ __launch_bounds__(NW * 64, (RT == 0 ? 4 : (NW == 4 && RT <= 3 ? 2 : N
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Shared by the clustered kernel (pcg_lpk_cluster.hip.h: G workgroups on G CUs solve ONE trajectory) and its host side: the scratch
-// of epoch-tagged hand-off cells and completion flags.  Hand-off = the R2 recipe of cdna_hip_programming.md §6 G16: {epoch, value}
-// granules written with one relaxed agent-scope store and polled with relaxed agent-scope loads — the tag is the flag, no fences;
-// every spin is bounded.  (Rounds 1-2 had two more clustered kernels on this machinery — a row-triple one here and a lane-per-block one;
-// both retired in round 4, HISTORY.md.)
-// ------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-// "This cluster gave up" flags: one per trajectory of the launch, each in a 128-byte line of its own at the FRONT of the
-// scratch buffer, read by the fix-up launch with agent-scope loads.  They must not share a line with the polled cells: a
-// plainly cached copy of such a line (left in some XCD's L2 by the fix-up kernel) made the next graph replay's pollers
-// read last run's epochs and time out.
-constexpr int CL_FLAG_STRIDE = 16;       // u64 words between flags
-// A poll is one sc1 load + s_sleep (25-70 ns): 2^16 polls = 1.5-4.5 ms.  Members of a launch are dispatched within a
-// microsecond of each other on a free GPU, so a wait this long means a peer is not resident (another stream holds its
-// CU): the member gives up and the host-side fix-up launch re-solves the trajectory with the single-workgroup kernel.
-constexpr unsigned CL_SPIN_LIMIT = 1u << 16;
-
-struct ClusterArgs {
-    int kl_max;                              // knots of the largest member
-    PcgArgs p;
-    unsigned long long* scratch;         // [clusters * G][LPBC_WG_WORDS] hand-off cells, zeroed before the launch
-    unsigned long long* fail_flags;      // [batch][CL_FLAG_STRIDE], zeroed before the launch: count of members that finished the trajectory
-    int G;
-    unsigned long long* queue = nullptr; // next trajectory to hand out (zeroed before the launch)
-    int batch = 0;                       // trajectories of the call
-    int clusters = 0;                    // clusters of the launch (the grid holds 8 ceil(clusters / 8) of them)
-    int l2_handoff = 1;                  // 1 = hand-offs through the XCD's L2 when all members of a cluster share an XCD (verified in the kernel)
-    int test_fail = 0;                   // tests only ("cluster_test_fail"): the last member of cluster 0 gives up at the write-back of its first trajectory
-};
-
-// Zero-fill of the cluster scratch (flags + hand-off cells) in front of every cluster launch.  A kernel of our own
-// rather than hipMemsetAsync: captured into a hipGraph next to other fills, the memset NODE replayed with another
-// node's fill value (ROCm 7.2; observed 7168 = the element count of a neighbouring tensor fill) — harmless for the
-// epoch-tagged cells, fatal for the flags.
-__global__ __launch_bounds__(256) void zero_words_kernel(unsigned long long* p, size_t count) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < count) p[i] = 0ull;
-}
-// Behind a cluster launch that NO fix-up launch follows ("cluster_fixup" = 0, or a horizon the fix-up kernel cannot hold): every trajectory
-// whose completion count is short of G is REPORTED here — d_iters = 0xFFFFFFFF, d_max_iter_exit = 2 — whatever the members themselves stored.
-// A member that gives up writes that pair itself, but member 0 may still pass its last hand-off (the failed peer published before it timed
-// out) and store a valid-looking count over it, and a cluster that gives up stops drawing from the queue: trajectories it would have drawn
-// get no store at all.  The completion counts know both.
-__global__ __launch_bounds__(256) void cluster_report_kernel(const unsigned long long* flags, int stride, unsigned long long G, int batch,
-                                                             uint32_t* iters, uint8_t* max_iter_exit) {
-    const int b = (int)blockIdx.x * 256 + (int)threadIdx.x;
-    if (b >= batch) return;
-    if (__hip_atomic_load(flags + (size_t)b * stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != G) {
-        iters[b] = 0xFFFFFFFFu;
-        max_iter_exit[b] = 2;
-    }
-}
-// The same fill + the handle's copy of the caller's lambda ([batch][N][n], n32 dwords): what a fix-up launch warm-starts from (PcgArgs::lam0).
-// One launch in front of every cluster launch.
-__global__ __launch_bounds__(256) void cluster_prologue_kernel(unsigned long long* p, size_t count, const uint32_t* src, uint32_t* dst, size_t n32) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-    for (size_t j = i; j < count; j += stride) p[j] = 0ull;
-    if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0) {
-        typedef unsigned u4v __attribute__((ext_vector_type(4)));
-        const size_t n4 = n32 / 4;
-        for (size_t j = i; j < n4; j += stride) reinterpret_cast<u4v*>(dst)[j] = reinterpret_cast<const u4v*>(src)[j];
-        for (size_t j = 4 * n4 + i; j < n32; j += stride) dst[j] = src[j];
-    } else {
-        for (size_t j = i; j < n32; j += stride) dst[j] = src[j];
-    }
-}
-
 // The symmetry latch / the "check_symmetry" debug option: the lane-pair kernels read only the left and diagonal block
 // columns of S and Pinv and use L_{k+1}^T where the reference's kernel reads block (k, right).  One wavefront per (trajectory,
 // k < N-1): counts the pairs whose blocks differ by more than rel_tol x the largest entry of the pair,

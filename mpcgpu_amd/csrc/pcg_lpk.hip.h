@@ -265,6 +265,26 @@ __device__ __forceinline__ void lpk_load_blocks_lds(rsrc_t M, int kfirst, int ke
     }
 }
 
+// Sum of a value over the 64 lanes of a wavefront, one fixed order: within each row of 16 by DPP row shifts, then the four rows.
+__device__ __forceinline__ float lpk_wave_fold(float part) {
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_shl:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "s_nop 1"
+        : "+v"(part));
+    const int pb = __builtin_bit_cast(int, part);
+    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, 16));
+    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, 32));
+    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, 48));
+    return ((part + r1) + r2) + r3;
+}
+
 template <int NWR>
 __global__ __launch_bounds__(NWR ? NWR * 256 : 128, 2) void pcg_lpk_kernel(PcgArgs a) {
     typedef LpkLds<NWR> L;
@@ -343,24 +363,9 @@ __global__ __launch_bounds__(NWR ? NWR * 256 : 128, 2) void pcg_lpk_kernel(PcgAr
 #ifdef MPCG_PROF
     bool prof_on = false;
 #endif
-    auto wave_fold = [&](float part) -> float {
-        asm volatile(
-            "s_nop 1\n\t"
-            "v_add_f32_dpp %0, %0, %0 row_shl:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "s_nop 1\n\t"
-            "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "s_nop 1\n\t"
-            "v_add_f32_dpp %0, %0, %0 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "s_nop 1\n\t"
-            "v_add_f32_dpp %0, %0, %0 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "s_nop 1"
-            : "+v"(part));
-        const int pb = __builtin_bit_cast(int, part);
-        const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, 16));
-        const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, 32));
-        const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, 48));
-        return ((part + r1) + r2) + r3;
-    };
+    // (a lambda of this kernel's own in front of lpk_wave_fold: `half` below captures it, and without that capture the compiler numbers this
+    //  kernel's registers differently — same instructions, another allocation; kept so that this kernel stays the code that was measured)
+    auto wave_fold = [&](float part) -> float { return lpk_wave_fold(part); };
     // sum of the NW/2 wave partials of one inner product (the waves of one matrix), same order in every thread: deterministic
     auto sum_red = [&](const float* red) -> float {
         if constexpr (NW == 8) {

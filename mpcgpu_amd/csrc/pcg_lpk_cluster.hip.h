@@ -1,9 +1,9 @@
 // pcg_lpk_cluster.hip.h — the lane-pair-per-knot PCG kernel (pcg_lpk.hip.h) for horizons one CU cannot hold (round 3): G workgroups on
 // G CUs of one XCD solve ONE trajectory, each with up to 64 NWR consecutive knots of S and Pinv in its register file.  Successor of
-// pcg_lpbc_kernel (pcg_lpb_cluster.hip.h), whose hand-off machinery — epoch-tagged granules in the XCD's L2, persistent clusters drawing
-// trajectories from a queue, bounded spins + completion counts + fix-up launch — it reuses unchanged; what changes is everything between
-// two hand-offs, which was 70 % of an iteration (profiles/r02_lpbc_phases.txt: passes 2 x 2,300 ticks, part-vector sums and vector updates
-// 2 x 1,200, against 900 + 1,600 of polling).
+// round 2's lane-per-block cluster kernel (retired in round 4), whose hand-off machinery — epoch-tagged granules in the XCD's L2, persistent
+// clusters drawing trajectories from a queue, bounded spins + completion counts + fix-up launch: the cluster runtime, pcg_cluster.hip.h — it
+// reuses unchanged; what changes is everything between two hand-offs, which was 70 % of an iteration there (profiles/r02_lpbc_phases.txt:
+// passes 2 x 2,300 ticks, part-vector sums and vector updates 2 x 1,200, against 900 + 1,600 of polling).
 //
 // Decomposition.  Member g owns knots [k0, k1) with the lane-pair mapping of pcg_lpk_kernel (a knot = two adjacent lanes per matrix, 147
 // packed FMAs per lane and pass, iterate vectors carried in registers, the reader rebuilds its operand).  A half-iteration of a member needs
@@ -15,61 +15,24 @@
 // as soon as the transposed product is done, mid-pass), the wave partials as 8-byte granules.  The hand-off is polled by a wave of the
 // matrix that sits the pass out, which therefore starts polling while the pass still runs; it drops the neighbours' vectors into the halo
 // slots of the local T / Z vectors (slot 0 and slot KL + 1), folds the partials, and ONE barrier ends the exchange.  Two hand-offs and two
-// barriers per PCG iteration, nothing else: no part vectors, no element-wise phases (pcg_lpbc_kernel: two hand-offs and four barriers).
+// barriers per PCG iteration, nothing else: no part vectors, no element-wise phases (the retired kernel: two hand-offs and four barriers).
 #pragma once
 #include "pcg_lpk.hip.h"
+#include "pcg_cluster.hip.h"
 
 namespace mpcg {
 
-// ---- hand-off cells in the cluster scratch (round 2's machinery, kept from the retired clustered lane-per-block kernel) ----
-constexpr int LPBC_MAX_G = 8;              // members: G x NW wave partials are polled by the 64 lanes of one wave
-constexpr int LPBC_WG_WORDS = 128;         // u64 words of hand-off cells per member (1 KB)
-// Cells of one member: two alternating exchange slots, each = NW 8-byte granules {tag, wave partial} (words 0..7) and three groups of
-// five 16-byte granules {tag, v0, v1, v2} — 14 values each: yD and yL of the last own knot (for the right neighbour), t (for the left one).
-constexpr int LPBC_SLOT_V = 0, LPBC_SLOT_E = 40;
-constexpr int LPBC_W_YD = 8, LPBC_W_YL = 18, LPBC_W_T = 28;
-constexpr int LPBC_SLOT_T = 120;                     // leader only: {sequence number, trajectory index} of the cluster's current trajectory
-constexpr int LPBC_SLOT_X = 121;                     // every member, once per launch: {1, XCC id} (the same-XCD check)
-
-// Granule accesses in the "uniform 64-bit base (SGPR pair) + 32-bit lane byte offset" addressing form, spelled out: left to
-// the compiler, the per-lane addresses of the two exchange slots become 64-bit VGPR pointers that are hoisted out of the PCG
-// loop — four registers this kernel does not have; they spill, and the publishing wave reloads its store address from scratch
-// right in front of every hand-off.  (s_nop 4: the base may just have been written by a v_readlane — an SGPR spill reload — and a
-// VMEM instruction reading a VALU-written SGPR needs 5 wait states; the compiler's hazard recogniser does not look into asm.)
-// sc1 = agent scope (write-through store / L2-coherent load), as __hip_atomic_*(relaxed, agent).
-// WORD = compile-time word index inside the member's block of cells: the instruction's immediate offset, so that the two exchange
-// slots and the hand-out word share ONE base register pair.
-template <int WORD>
-__device__ __forceinline__ void granule_store(gu64* sbase, unsigned byte_off, unsigned long long v) {
-    asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %2 offset:%3 sc1" : : "v"(byte_off), "v"(v), "s"(sbase), "n"(8 * WORD) : "memory");
-}
-// The same store WITHOUT sc1: the granule stays in this XCD's L2, where a poller on the same XCD finds it (its sc1 load bypasses
-// only L1) without the round trip to the memory side that a write-through store forces on both.  Only valid when the whole
-// cluster sits on one XCD, which the members verify at start-up (pcg_lpbc_kernel: `same_xcd`).
-template <int WORD>
-__device__ __forceinline__ void granule_store_l2(gu64* sbase, unsigned byte_off, unsigned long long v) {
-    asm volatile("s_nop 4\n\tglobal_store_dwordx2 %0, %1, %2 offset:%3" : : "v"(byte_off), "v"(v), "s"(sbase), "n"(8 * WORD) : "memory");
-}
-template <int WORD>
-__device__ __forceinline__ unsigned long long granule_load(const gu64* sbase, unsigned byte_off) {
-    unsigned long long x;
-    asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %1, %2 offset:%3 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(x) : "v"(byte_off), "s"(sbase), "n"(8 * WORD) : "memory");
-    return x;
-}
-
-// 16-byte granules {tag, v0, v1, v2}: one dwordx4 store / load (observed untorn on gfx950, MI355X_MICROARCH.md "R2's granule"), three
-// values per fabric / L2 transaction instead of one.  L2 = without sc1 (see granule_store_l2).
-template <int WORD, bool L2>
-__device__ __forceinline__ void granule_store16(gu64* sbase, unsigned byte_off, f4 v) {
-    if constexpr (L2) asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 offset:%3\n\ts_nop 1" : : "v"(byte_off), "v"(v), "s"(sbase), "n"(8 * WORD) : "memory");
-    else asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 offset:%3 sc1\n\ts_nop 1" : : "v"(byte_off), "v"(v), "s"(sbase), "n"(8 * WORD) : "memory");
-}
-__device__ __forceinline__ f4 granule_load16(const gu64* sbase, unsigned byte_off) {
-    f4 x;
-    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(x) : "v"(byte_off), "s"(sbase) : "memory");
-    return x;
-}
-
+// ---- hand-off cells of one member in the cluster scratch ----
+constexpr int LPKC_MAX_G = 8;              // members: G x NW wave partials are polled by the 64 lanes of one wave
+constexpr int LPKC_WG_WORDS = 128;         // u64 words of hand-off cells per member (1 KB)
+// Two alternating exchange slots (LPKC_SLOT_V / LPKC_SLOT_E), each = NW/2 wave partials (words 0..3: 8-byte granules {value, tag}) and two
+// groups of five 16-byte granules {tag, v0, v1, v2}: T of the last own knot (for the right neighbour), Z of the first (for the left one).
+// Granule q of a group carries entries (0,1,2) (3,4,5) (6,7,-) (8,9,10) (11,12,13) of the 14-vector: q = 0..2 come from lane 0 of the
+// knot's pair, q = 3, 4 from lane 1.
+constexpr int LPKC_SLOT_V = 0, LPKC_SLOT_E = 40;
+constexpr int LPKC_W_T = 8, LPKC_W_Z = 18;
+constexpr int LPKC_SLOT_T = 120;                     // leader only: {trajectory index, sequence number} of the cluster's current trajectory
+constexpr int LPKC_SLOT_X = 121;                     // every member, once per launch: {XCC id, 1} (the same-XCD check)
 
 // LDS: the lane-pair kernel's seven pair-major vectors (knot slot 0 = the left halo knot k0 - 1, slots 1..KL = own knots, slot KL + 1 = the
 // right halo knot k1) | broadcast cell | hand-off tables (5 x 64 ints) | parked matrix pairs.
@@ -82,12 +45,6 @@ template <int NWR> struct LpkcLds {
     __host__ __device__ static constexpr int at(int s, int i) { return 2 * ((i >> 1) * KN + s) + (i & 1); }
 };
 __host__ __device__ constexpr size_t pcg_lpkc_lds_floats(int NW) { return NW == 4 ? (size_t)LpkcLds<1>::TOTAL : (size_t)LpkcLds<2>::TOTAL; }
-
-// Cells of one member (LPBC_WG_WORDS u64 words): two alternating exchange slots (LPBC_SLOT_V / LPBC_SLOT_E), each = NW/2 wave partials
-// (words 0..3: {tag, value}) and two groups of five 16-byte granules: T of the last own knot (for the right neighbour), Z of the first
-// (for the left one).  Granule q of a group carries entries (0,1,2) (3,4,5) (6,7,-) (8,9,10) (11,12,13) of the 14-vector: q = 0..2 come
-// from lane 0 of the knot's pair, q = 3, 4 from lane 1.  Words LPBC_SLOT_T / LPBC_SLOT_X as in pcg_lpbc_kernel.
-constexpr int LPKC_W_T = 8, LPKC_W_Z = 18;
 
 template <int NWR>
 __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) {
@@ -102,22 +59,20 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int G = ca.G;
-    // members of a cluster share an XCD (see pcg_lpbc_kernel): workgroup b = 8 j + x holds member j % G of cluster 8 (j / G) + x
     const unsigned nclusters = (unsigned)ca.clusters;
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int g = jx % G;
-    const int cl = (jx / G) * 8 + xcd;
-    if ((unsigned)cl >= nclusters) return;
+    const ClusterPlace pl = cluster_place(G, nclusters);
+    if (!pl.member) return;
+    const int g = pl.g, cl = pl.cl;
     // gate of the symmetry latch (mpcg_pcg.hip: launch_guarded): every member reads the same word and leaves at once when it says the
     // matrices are not block-symmetric — no trajectory is drawn, every completion count stays 0, and the fix-up launch solves them all
     if (a.redo_flags && __hip_atomic_load(a.redo_flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.redo_skip) return;
-    const int k0 = (int)(((long)g * N) / G), k1 = (int)(((long)(g + 1) * N) / G);
+    const int k0 = cluster_first_knot(g, N, G), k1 = cluster_first_knot(g + 1, N, G);
     const int KL = k1 - k0;                             // own knots (launcher: 1 <= KL <= NMAX)
     float* bc = lds + L::BC;                            // [0] cluster-wide sum, [1] sticky timeout flag, [2] trajectory index (int)
 
     const size_t mstride = (size_t)N * ROWF, vstride = (size_t)N * NS;
-    gu64* my_words = (gu64*)ca.scratch + ((size_t)cl * G + g) * LPBC_WG_WORDS;
-    gu64* cl_words = (gu64*)ca.scratch + (size_t)cl * G * LPBC_WG_WORDS;
+    gu64* my_words = (gu64*)ca.scratch + ((size_t)cl * G + g) * LPKC_WG_WORDS;
+    gu64* cl_words = (gu64*)ca.scratch + (size_t)cl * G * LPKC_WG_WORDS;
 
     // ---- role of this wave, knot and column half of this lane (pcg_lpk_kernel's mapping; i = knot inside the member, slot i + 1) ----
     const bool isP = w >= NWM;
@@ -134,24 +89,6 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
     f2 Md[7][7], Ml[7][7];
     f2* const park = reinterpret_cast<f2*>(lds + L::MX) + tid;
 
-    auto wave_fold = [&](float part) -> float {
-        asm volatile(
-            "s_nop 1\n\t"
-            "v_add_f32_dpp %0, %0, %0 row_shl:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "s_nop 1\n\t"
-            "v_add_f32_dpp %0, %0, %0 row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "s_nop 1\n\t"
-            "v_add_f32_dpp %0, %0, %0 row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "s_nop 1\n\t"
-            "v_add_f32_dpp %0, %0, %0 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "s_nop 1"
-            : "+v"(part));
-        const int pb = __builtin_bit_cast(int, part);
-        const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, 16));
-        const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, 32));
-        const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pb, 48));
-        return ((part + r1) + r2) + r3;
-    };
 #ifdef MPCG_PROF
     bool prof_on = false;
 #endif
@@ -212,7 +149,7 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
     auto half = [&](auto mode_tag, auto slot, const Fetch& f, const Vec& old, float c, int TOUT, int ZOUT) -> Vec {
         constexpr int MODE = decltype(mode_tag)::value;
         constexpr int base = decltype(slot)::value;
-        [[maybe_unused]] constexpr int pb = base == LPBC_SLOT_V ? 0 : 8;     // (stamp numbers of the -DMPCG_PROF build)
+        [[maybe_unused]] constexpr int pb = base == LPKC_SLOT_V ? 0 : 8;     // (stamp numbers of the -DMPCG_PROF build)
         MPCG_STAMP(pb + 0);
         const unsigned ep = epoch + 1;                      // tag of the hand-off that follows this pass
         f2 xk[7];
@@ -319,9 +256,9 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
         d0 = __builtin_elementwise_fma(o.v[2], me.v[2], d0);
         const f2 d3 = o.v[3] * me.v[3];
         const f2 dd = d0 + d1;
-        const float part = wave_fold(((dd.x + dd.y) + (h ? 0.f : d3.x + d3.y)) + cterm);
+        const float part = lpk_wave_fold(((dd.x + dd.y) + (h ? 0.f : d3.x + d3.y)) + cterm);
         if (lane == 0) {
-            const unsigned long long gran = ((unsigned long long)ep << 32) | __builtin_bit_cast(unsigned, part);
+            const unsigned long long gran = granule_of(__builtin_bit_cast(unsigned, part), ep);
             if (same_xcd) granule_store_l2<base>(my_words, 8u * (unsigned)wl, gran);
             else granule_store<base>(my_words, 8u * (unsigned)wl, gran);
         }
@@ -329,14 +266,14 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
         return Vec{me, om};
     };
 
-    using SlotV = std::integral_constant<int, LPBC_SLOT_V>;
-    using SlotE = std::integral_constant<int, LPBC_SLOT_E>;
+    using SlotV = std::integral_constant<int, LPKC_SLOT_V>;
+    using SlotE = std::integral_constant<int, LPKC_SLOT_E>;
     // The one hand-off of a half.  `poller`: this wave polls (a wave of the matrix that sits the half out — it starts while the pass still
     // runs).  TV / ZV: the local vectors whose halo slots receive the neighbours' T and Z.  withZ: the pass produced z (false: block-Jacobi Pinv pass).
     // Returns the cluster-wide inner product.
     auto exchange = [&](auto slot, bool poller, int TV, int ZV, bool withZ) -> float {
         constexpr int base = decltype(slot)::value;
-        [[maybe_unused]] constexpr int pb = base == LPBC_SLOT_V ? 0 : 8;
+        [[maybe_unused]] constexpr int pb = base == LPKC_SLOT_V ? 0 : 8;
         ++epoch;
         MPCG_STAMP(pb + 2);
         if (poller) {
@@ -352,7 +289,7 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
 #ifdef MPCG_CG_EMULATE
             // TIMING EXPERIMENT ONLY (tools/_prof/cg_emulate.py; wrong numerics): what a single-reduction (Chronopoulos-Gear) recurrence could
             // save at best without overlapping — its hand-off after the Pinv pass carries the neighbours' halo only: no partials polled, nothing folded
-            const bool wantp = base != LPBC_SLOT_E && pbyte != 0xFFFFFFFFu;
+            const bool wantp = base != LPKC_SLOT_E && pbyte != 0xFFFFFFFFu;
 #else
             const bool wantp = pbyte != 0xFFFFFFFFu;
 #endif
@@ -382,9 +319,9 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
                 if (d2 >= 0) dv[d2] = xv.w;
             }
 #ifdef MPCG_CG_EMULATE
-            const float tot = base == LPBC_SLOT_E ? 1.0f : wave_fold(wantp ? __builtin_bit_cast(float, (unsigned)x) : 0.f);
+            const float tot = base == LPKC_SLOT_E ? 1.0f : lpk_wave_fold(wantp ? __builtin_bit_cast(float, (unsigned)x) : 0.f);
 #else
-            const float tot = wave_fold(wantp ? __builtin_bit_cast(float, (unsigned)x) : 0.f);
+            const float tot = lpk_wave_fold(wantp ? __builtin_bit_cast(float, (unsigned)x) : 0.f);
 #endif
             if (ln == 0) { bc[(epoch & 1u) ? 3 : 0] = tot; if (spins >= CL_SPIN_LIMIT) bc[1] = 1.f; }
             MPCG_STAMP(pb + 4);
@@ -401,45 +338,29 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
     if (tid < 64) {
         const int l = tid;
         int* tab = reinterpret_cast<int*>(lds + L::TAB) + l;
-        tab[0] = l < G * NWM ? 8 * ((l / NWM) * LPBC_WG_WORDS + l % NWM) : -1;
+        tab[0] = l < G * NWM ? 8 * ((l / NWM) * LPKC_WG_WORDS + l % NWM) : -1;
         // 16-byte granule q of: lanes 32..36 T of member g - 1 (into slot 0), lanes 40..44 Z of member g + 1 (into slot KL + 1)
         const bool isT = l >= 32 && l < 37, isZ = l >= 40 && l < 45;
         const int q = isT ? l - 32 : l - 40;
         const bool have = isT ? g > 0 : (isZ && g < G - 1);
         const int src_m = isT ? g - 1 : g + 1;
-        tab[64] = have ? 8 * (src_m * LPBC_WG_WORDS + (isT ? LPKC_W_T : LPKC_W_Z) + 2 * q) : -1;
+        tab[64] = have ? 8 * (src_m * LPKC_WG_WORDS + (isT ? LPKC_W_T : LPKC_W_Z) + 2 * q) : -1;
         const int e0 = q == 0 ? 0 : q == 1 ? 3 : q == 2 ? 6 : q == 3 ? 8 : 11;        // first entry of granule q
         const int sl = isT ? 0 : KL + 1;
         tab[128] = L::at(sl, e0);
         tab[192] = L::at(sl, e0 + 1);
         tab[256] = q == 2 ? -1 : L::at(sl, e0 + 2);
     }
-    // ---- are all members of this cluster on one XCD? (pcg_lpbc_kernel) ----
+    // ---- are all members of this cluster on one XCD? ----
     if (w == 0) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 0xf;
-        if (lane == 0) granule_store<LPBC_SLOT_X>(my_words, 0u, (1ull << 32) | xcc);
-        unsigned long long x = 0;
-        unsigned spins = 0;
-        bool ok;
-        do {
-            ok = true;
-            if (lane < G) {
-                x = granule_load<LPBC_SLOT_X>(cl_words, 8u * (unsigned)(lane * LPBC_WG_WORDS));
-                ok = (unsigned)(x >> 32) == 1u;
-            }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-        } while (++spins < (CL_SPIN_LIMIT >> 4));
-        const bool all_same = __all(lane >= G || ((unsigned)(x >> 32) == 1u && (unsigned)x == xcc));
+        const bool all_same = cluster_on_one_xcd<LPKC_SLOT_X, LPKC_WG_WORDS>(my_words, cl_words, lane, G);
         if (lane == 0) reinterpret_cast<int*>(bc)[2] = all_same ? 1 : 0;
     }
     lds_barrier();
     same_xcd = reinterpret_cast<const int*>(bc)[2] != 0 && ca.l2_handoff != 0;
     lds_barrier();
     for (;;) {
-        // ---- next trajectory of this cluster (pcg_lpbc_kernel: own index first, then the leader draws from the queue) ----
+        // ---- next trajectory of this cluster (own index first, then the leader draws from the queue) ----
         ++seq;
         if (seq > 1) {
             if ((unsigned)ca.batch <= nclusters) break;
@@ -449,20 +370,12 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
                     if (lane == 0) {
                         kargp_t k_q = kp;
                         asm volatile("" : "+s"(k_q));
-                        bn = (int)nclusters + (int)__hip_atomic_fetch_add(k_q->queue, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (same_xcd) granule_store_l2<LPBC_SLOT_T>(my_words, 0u, ((unsigned long long)seq << 32) | (unsigned)bn);
-                        else granule_store<LPBC_SLOT_T>(my_words, 0u, ((unsigned long long)seq << 32) | (unsigned)bn);
+                        bn = cluster_hand_out<LPKC_SLOT_T>(k_q, my_words, seq, nclusters, same_xcd);
                     }
                 } else {
-                    unsigned long long x = 0;
-                    unsigned spins = 0;
-                    do {
-                        x = granule_load<LPBC_SLOT_T>(cl_words, 0u);
-                        if ((unsigned)(x >> 32) == seq) break;
-                        __builtin_amdgcn_s_sleep(1);
-                    } while (++spins < CL_SPIN_LIMIT);
-                    bn = (int)(unsigned)x;
-                    if (spins >= CL_SPIN_LIMIT && lane == 0) bc[1] = 1.f;
+                    const ClusterDraw d = cluster_await_trajectory<LPKC_SLOT_T>(cl_words, seq);
+                    bn = d.index;
+                    if (d.timed_out && lane == 0) bc[1] = 1.f;
                 }
                 if (lane == 0) reinterpret_cast<int*>(bc)[2] = bn;
             }
@@ -567,7 +480,7 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
         asm volatile("" : "+s"(k_out));
         if (ca.test_fail && cl == 0 && g == G - 1 && seq == 1) failed = true;      // ("cluster_test_fail": a member that gives up when its peers are past their last hand-off)
         if (failed) {
-            if (tid == 0) { k_out->p.iters[b] = 0xFFFFFFFFu; k_out->p.max_iter_exit[b] = 2; }
+            cluster_report_abandoned(k_out, b, tid);
             break;
         }
         {
@@ -585,13 +498,7 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
                 }
             }
         }
-        if (tid == 0) {
-            if (g == 0) {
-                k_out->p.iters[b] = iters;
-                k_out->p.max_iter_exit[b] = (uint8_t)max_iter_exit;
-            }
-            __hip_atomic_fetch_add(k_out->fail_flags + (size_t)b * CL_FLAG_STRIDE, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        cluster_finish(k_out, b, g == 0, tid, iters, max_iter_exit);
         lds_barrier();                                      // LDS is restaged for the next trajectory
     }
 }

@@ -1,6 +1,7 @@
 // pcg_lqk_cluster_f64.hip.h — the lane-quad-per-knot kernel in double (pcg_lqk_f64.hip.h) for horizons one CU cannot hold: G = ceil(N / 64)
 // workgroups on G CUs of one XCD solve ONE trajectory, each with up to 64 consecutive knots of the lower block triangle of S and Pinv in its
-// register file.  The double twin of pcg_lpkc_kernel (pcg_lpk_cluster.hip.h), whose decomposition and hand-off machinery it takes over:
+// register file.  The double twin of pcg_lpkc_kernel (pcg_lpk_cluster.hip.h), whose decomposition it takes over, on the same cluster runtime
+// (pcg_cluster.hip.h):
 //   * member g owns knots [k0, k1); LDS knot slot 0 = the replica knot k0 - 1 (its operand entries are rebuilt by the lanes of knot k0), slots
 //     1..KL = own knots, slot KL + 1 = the right halo knot k1;
 //   * a half-iteration needs from outside T[k0 - 1] (the LEFT member's merged rows of its last knot), Z[k1] (the RIGHT member's z = L_k1^T x_k1
@@ -13,12 +14,12 @@
 // diagonal block columns: launched when the handle's latch says block-symmetric.
 #pragma once
 #include "pcg_lqk_f64.hip.h"
-#include "pcg_rpl_cluster_f64.hip.h"
+#include "pcg_cluster.hip.h"
 
 namespace mpcg {
 
 // Cells of one member, u64 words: two exchange slots of 64 words — [0, 8) four wave partials, [8, 36) T of the last own knot (14 granules, for
-// the right neighbour), [36, 64) Z of the first own knot (for the left one) — then {sequence number, trajectory} (leader) and {1, XCC id}.
+// the right neighbour), [36, 64) Z of the first own knot (for the left one) — then {trajectory, sequence number} (leader) and {XCC id, 1}.
 constexpr int LQKC_WG_WORDS = 144;
 constexpr int LQKC_SLOT_V = 0, LQKC_SLOT_E = 64, LQKC_W_T = 8, LQKC_W_Z = 36;
 constexpr int LQKC_SLOT_T = 128, LQKC_SLOT_X = 130;
@@ -57,13 +58,11 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int G = ca.G;
-    // members of a cluster share an XCD (pcg_lpkc_kernel): workgroup b = 8 j + x holds member j % G of cluster 8 (j / G) + x
     const unsigned nclusters = (unsigned)ca.clusters;
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int gm = jx % G;
-    const int cl = (jx / G) * 8 + xcd;
-    if ((unsigned)cl >= nclusters) return;
-    const int k0 = (int)(((long)gm * N) / G), k1 = (int)(((long)(gm + 1) * N) / G);
+    const ClusterPlace pl = cluster_place(G, nclusters);
+    if (!pl.member) return;
+    const int gm = pl.g, cl = pl.cl;
+    const int k0 = cluster_first_knot(gm, N, G), k1 = cluster_first_knot(gm + 1, N, G);
     const int KL = k1 - k0;                             // own knots (launcher: 1 <= KL <= NMAX)
     real* bc = lds + L::BC;                             // [0] / [3] cluster-wide sum of even / odd hand-offs, [1] sticky timeout flag, [2] trajectory index / same-XCD (int)
 
@@ -139,21 +138,17 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
         const int e3 = ISZ ? 6 + hh : 6 + gg;
         const bool pub3 = ISZ ? gg == hh : hh == 0;
         const int h = hh, g = gg;
-        auto gran = [&](real v) -> f4 {
-            const unsigned long long bits = __builtin_bit_cast(unsigned long long, v);
-            return f4{__builtin_bit_cast(float, (unsigned)bits), __builtin_bit_cast(float, (unsigned)(bits >> 32)), __builtin_bit_cast(float, ep), 0.f};
-        };
         const unsigned o0 = 16u * (unsigned)(8 * h + g);
         if (same_xcd) {
-            granule_store16<WORD, true>(my_words, o0, gran(v0));
-            granule_store16<WORD + 4, true>(my_words, o0, gran(v1));
-            granule_store16<WORD + 8, true>(my_words, o0, gran(v2));
-            if (pub3) granule_store16<WORD, true>(my_words, 16u * (unsigned)e3, gran(v3));
+            granule_store16<WORD, true>(my_words, o0, granule_of(v0, ep));
+            granule_store16<WORD + 4, true>(my_words, o0, granule_of(v1, ep));
+            granule_store16<WORD + 8, true>(my_words, o0, granule_of(v2, ep));
+            if (pub3) granule_store16<WORD, true>(my_words, 16u * (unsigned)e3, granule_of(v3, ep));
         } else {
-            granule_store16<WORD, false>(my_words, o0, gran(v0));
-            granule_store16<WORD + 4, false>(my_words, o0, gran(v1));
-            granule_store16<WORD + 8, false>(my_words, o0, gran(v2));
-            if (pub3) granule_store16<WORD, false>(my_words, 16u * (unsigned)e3, gran(v3));
+            granule_store16<WORD, false>(my_words, o0, granule_of(v0, ep));
+            granule_store16<WORD + 4, false>(my_words, o0, granule_of(v1, ep));
+            granule_store16<WORD + 8, false>(my_words, o0, granule_of(v2, ep));
+            if (pub3) granule_store16<WORD, false>(my_words, 16u * (unsigned)e3, granule_of(v3, ep));
         }
     };
 
@@ -267,8 +262,7 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
         const real d3 = o.v[3] * me.v[3];
         const real part = rpl_wave_fold((d0 + (h ? real(0) : d3)) + cterm);
         if (lane == 0) {
-            const unsigned long long bits = __builtin_bit_cast(unsigned long long, part);
-            const f4 gr = {__builtin_bit_cast(float, (unsigned)bits), __builtin_bit_cast(float, (unsigned)(bits >> 32)), __builtin_bit_cast(float, ep), 0.f};
+            const f4 gr = granule_of(part, ep);
             if (same_xcd) granule_store16<base, true>(my_words, 16u * (unsigned)wl, gr);
             else granule_store16<base, false>(my_words, 16u * (unsigned)wl, gr);
         }
@@ -294,7 +288,6 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
             const bool isZ = ln >= 48;
             const bool wantp = pbyte != 0xFFFFFFFFu;
             const bool wantv = vbyte != 0xFFFFFFFFu && (withZ || !isZ);
-            typedef unsigned u4 __attribute__((ext_vector_type(4)));
             u4 xp = {0u, 0u, 0u, 0u}, xv = {0u, 0u, 0u, 0u};
             unsigned spins = 0;
             bool ok;
@@ -309,8 +302,8 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
                 if (__all(ok)) break;
                 __builtin_amdgcn_s_sleep(1);
             } while (++spins < CL_SPIN_LIMIT);
-            if (wantv) (lds + (isZ ? ZV : TV))[dst] = __builtin_bit_cast(real, ((unsigned long long)xv.y << 32) | (unsigned long long)xv.x);
-            const real partial = __builtin_bit_cast(real, ((unsigned long long)xp.y << 32) | (unsigned long long)xp.x);
+            if (wantv) (lds + (isZ ? ZV : TV))[dst] = granule_value(xv);
+            const real partial = granule_value(xp);
             const real tot = rpl_wave_fold(wantp ? partial : real(0));
             if (ln == 0) { bc[(epoch & 1u) ? 3 : 0] = tot; if (spins >= CL_SPIN_LIMIT) bc[1] = 1.0; }
         }
@@ -333,25 +326,9 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
         tab[64] = have ? 8 * (src_m * LQKC_WG_WORDS + (isT ? LQKC_W_T : LQKC_W_Z) + 2 * e) : -1;
         tab[128] = have ? L::at(isT ? 0 : KL + 1, e) : 0;
     }
-    // ---- are all members of this cluster on one XCD? (pcg_lpkc_kernel) ----
+    // ---- are all members of this cluster on one XCD? ----
     if (w == 0) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 0xf;
-        if (lane == 0) granule_store<LQKC_SLOT_X>(my_words, 0u, (1ull << 32) | xcc);
-        unsigned long long x = 0;
-        unsigned spins = 0;
-        bool ok;
-        do {
-            ok = true;
-            if (lane < G) {
-                x = granule_load<LQKC_SLOT_X>(cl_words, 8u * (unsigned)(lane * LQKC_WG_WORDS));
-                ok = (unsigned)(x >> 32) == 1u;
-            }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-        } while (++spins < (CL_SPIN_LIMIT >> 4));
-        const bool all_same = __all(lane >= G || ((unsigned)(x >> 32) == 1u && (unsigned)x == xcc));
+        const bool all_same = cluster_on_one_xcd<LQKC_SLOT_X, LQKC_WG_WORDS>(my_words, cl_words, lane, G);
         if (lane == 0) reinterpret_cast<int*>(bc + 2)[0] = all_same ? 1 : 0;
     }
     lds_barrier();
@@ -366,20 +343,12 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
                 int bn = 0;
                 if (gm == 0) {
                     if (lane == 0) {
-                        bn = (int)nclusters + (int)__hip_atomic_fetch_add(kp->queue, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (same_xcd) granule_store_l2<LQKC_SLOT_T>(my_words, 0u, ((unsigned long long)seq << 32) | (unsigned)bn);
-                        else granule_store<LQKC_SLOT_T>(my_words, 0u, ((unsigned long long)seq << 32) | (unsigned)bn);
+                        bn = cluster_hand_out<LQKC_SLOT_T>(kp, my_words, seq, nclusters, same_xcd);
                     }
                 } else {
-                    unsigned long long x = 0;
-                    unsigned spins = 0;
-                    do {
-                        x = granule_load<LQKC_SLOT_T>(cl_words, 0u);
-                        if ((unsigned)(x >> 32) == seq) break;
-                        __builtin_amdgcn_s_sleep(1);
-                    } while (++spins < CL_SPIN_LIMIT);
-                    bn = (int)(unsigned)x;
-                    if (spins >= CL_SPIN_LIMIT && lane == 0) bc[1] = 1.0;
+                    const ClusterDraw d = cluster_await_trajectory<LQKC_SLOT_T>(cl_words, seq);
+                    bn = d.index;
+                    if (d.timed_out && lane == 0) bc[1] = 1.0;
                 }
                 if (lane == 0) reinterpret_cast<int*>(bc + 2)[0] = bn;
             }
@@ -472,7 +441,7 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
         //      from the handle's copy of lambda0) ----
         if (ca.test_fail && cl == 0 && gm == G - 1 && seq == 1) failed = true;
         if (failed) {
-            if (tid == 0) { kp->p.iters[b] = 0xFFFFFFFFu; kp->p.max_iter_exit[b] = 2; }
+            cluster_report_abandoned(kp, b, tid);
             break;
         }
         for (int e = tid; e < KL * NS; e += NTHR) {
@@ -486,10 +455,7 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
                 kp->p.p_out[ge] = pv;
             }
         }
-        if (tid == 0) {
-            if (gm == 0) { kp->p.iters[b] = iters; kp->p.max_iter_exit[b] = (uint8_t)max_iter_exit; }
-            __hip_atomic_fetch_add(kp->fail_flags + (size_t)b * CL_FLAG_STRIDE, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        cluster_finish(kp, b, gm == 0, tid, iters, max_iter_exit);
         lds_barrier();                                      // LDS is restaged for the next trajectory
     }
 }

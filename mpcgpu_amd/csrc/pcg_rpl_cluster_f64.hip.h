@@ -7,34 +7,25 @@
 // type, and its data flow across a member boundary is small: what a pass needs from outside is entry i of the operand at the two neighbouring
 // knots, which the reader REBUILDS from two published vectors (x_nb = fma(c, B[nb], A[nb]) — the owner's own operation, hence its bits).
 // So a member publishes, after each of the two passes of an iteration, the two vectors of its first and last knot (2 x 14 doubles to each
-// side) and its wave partials; ONE hand-off per pass, as in pcg_lpkc_kernel, whose machinery this kernel reuses unchanged: epoch-tagged
+// side) and its wave partials; ONE hand-off per pass, as in pcg_lpkc_kernel, on the same cluster runtime (pcg_cluster.hip.h): epoch-tagged
 // 16-byte granules {value, tag} published straight from registers into the XCD's L2 (members pinned to one XCD, verified at start-up;
 // write-through otherwise), two alternating exchange slots, persistent clusters drawing trajectories from a queue, bounded spins +
 // completion counts + a fix-up launch (here: the streaming kernel) for a cluster that could not make progress.
 // Reads all three block columns (no symmetry contract).  Same PCG, same exit rule, same outputs as every other kernel.
 #pragma once
 #include "pcg_rpl.hip.h"
-#include "pcg_lpk_cluster.hip.h"
+#include "pcg_cluster.hip.h"
 
 namespace mpcg {
 
 // Cells of one member, u64 words: two exchange slots of 128 words — [0, 16) NW = 8 wave partials, [16, 72) the group for the LEFT neighbour
 // (vector 0 / vector 1 x 14 entries of the first own knot), [72, 128) the group for the RIGHT neighbour (last own knot); every granule 16 bytes
-// {value lo, value hi, tag, 0} — then {sequence number, trajectory} of the cluster's current trajectory (leader) and {1, XCC id}.
+// {value lo, value hi, tag, 0} — then {trajectory, sequence number} of the cluster's current trajectory (leader) and {XCC id, 1}.
 constexpr int RPLC_WG_WORDS = 272;
 constexpr int RPLC_SLOT = 128, RPLC_W_L = 16, RPLC_W_R = 72;
 constexpr int RPLC_SLOT_T = 256, RPLC_SLOT_X = 258;
 constexpr int RPLC_NW = 8, RPLC_KMAX = 32;          // wavefronts per member; knots per member (four per wavefront)
 constexpr int RPLC_MAX_G = 8;                       // G x NW <= 64 partials polled by one wavefront
-
-struct ClusterArgs64 {
-    PcgArgs64 p;
-    unsigned long long* scratch;         // [clusters * G][RPLC_WG_WORDS] hand-off cells, zeroed before the launch
-    unsigned long long* fail_flags;      // [batch][CL_FLAG_STRIDE], zeroed before the launch: members that finished the trajectory
-    unsigned long long* queue;           // next trajectory to hand out (zeroed before the launch)
-    int G, batch, clusters, l2_handoff;
-    int test_fail = 0;                   // tests only ("cluster_test_fail"): the last member of cluster 0 gives up at the write-back of its first trajectory
-};
 
 // LDS (doubles): six vectors [KL + 2][14] with a halo knot either side | 64 partials of the cluster | {timeout flag, trajectory index, same-XCD}
 __host__ __device__ constexpr size_t pcg_rplc_lds_doubles() { return 6 * r4((size_t)(RPLC_KMAX + 2) * NS) + 64 + 8; }
@@ -50,13 +41,11 @@ __global__ __launch_bounds__(RPLC_NW * 64, 2) void pcg_rplc_f64_kernel(ClusterAr
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // members of a cluster share an XCD (pcg_lpkc_kernel): workgroup b = 8 j + x holds member j % G of cluster 8 (j / G) + x
     const unsigned nclusters = (unsigned)ca.clusters;
-    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
-    const int g = jx % G;
-    const int cl = (jx / G) * 8 + xcd;
-    if ((unsigned)cl >= nclusters) return;
-    const int k0 = (int)(((long)g * N) / G), k1 = (int)(((long)(g + 1) * N) / G);
+    const ClusterPlace pl = cluster_place(G, nclusters);
+    if (!pl.member) return;
+    const int g = pl.g, cl = pl.cl;
+    const int k0 = cluster_first_knot(g, N, G), k1 = cluster_first_knot(g + 1, N, G);
     const int KL = k1 - k0;                             // own knots (launcher: 1 <= KL <= 32)
     constexpr int VS = (int)r4((size_t)(RPLC_KMAX + 2) * NS);
     real* xp0 = lds;                                    // local knot kl at (kl + 1) * NS; slot 0 / KL + 1 = the neighbours' boundary knots
@@ -86,23 +75,7 @@ __global__ __launch_bounds__(RPLC_NW * 64, 2) void pcg_rplc_f64_kernel(ClusterAr
     // ---- are all members of this cluster on one XCD? ----
     if (tid == 0) { bc[0] = 0.0; }
     if (w == 0) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 0xf;
-        if (lane == 0) granule_store<RPLC_SLOT_X>(my_words, 0u, (1ull << 32) | xcc);
-        unsigned long long x = 0;
-        unsigned spins = 0;
-        bool ok;
-        do {
-            ok = true;
-            if (lane < G) {
-                x = granule_load<RPLC_SLOT_X>(cl_words, 8u * (unsigned)(lane * RPLC_WG_WORDS));
-                ok = (unsigned)(x >> 32) == 1u;
-            }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-        } while (++spins < (CL_SPIN_LIMIT >> 4));
-        const bool all_same = __all(lane >= G || ((unsigned)(x >> 32) == 1u && (unsigned)x == xcc));
+        const bool all_same = cluster_on_one_xcd<RPLC_SLOT_X, RPLC_WG_WORDS>(my_words, cl_words, lane, G);
         if (lane == 0) reinterpret_cast<int*>(bc)[4] = all_same ? 1 : 0;
     }
     lds_barrier();
@@ -114,13 +87,9 @@ __global__ __launch_bounds__(RPLC_NW * 64, 2) void pcg_rplc_f64_kernel(ClusterAr
     auto exchange = [&](real* bufA, real va, real* bufB, real vb, real wave_part) -> real {
         ++epoch;
         const unsigned sb = (epoch & 1u) * (unsigned)RPLC_SLOT;           // word offset of this hand-off's slot
-        auto gran = [&](real v) -> f4 {
-            const unsigned long long bits = __builtin_bit_cast(unsigned long long, v);
-            return f4{__builtin_bit_cast(float, (unsigned)bits), __builtin_bit_cast(float, (unsigned)(bits >> 32)), __builtin_bit_cast(float, epoch), 0.f};
-        };
         auto put = [&](unsigned word, real v) {
-            if (same_xcd) granule_store16<0, true>(my_words, 8u * (sb + word), gran(v));
-            else granule_store16<0, false>(my_words, 8u * (sb + word), gran(v));
+            if (same_xcd) granule_store16<0, true>(my_words, 8u * (sb + word), granule_of(v, epoch));
+            else granule_store16<0, false>(my_words, 8u * (sb + word), granule_of(v, epoch));
         };
         if (lane == 0) put(2u * (unsigned)w, wave_part);
         if (first) { put(RPLC_W_L + 2u * (unsigned)ii, va); put(RPLC_W_L + 2u * (unsigned)(14 + ii), vb); }
@@ -134,7 +103,6 @@ __global__ __launch_bounds__(RPLC_NW * 64, 2) void pcg_rplc_f64_kernel(ClusterAr
             const bool fromL = lane < 32;
             const bool wantv = e < 28 && (fromL ? g > 0 : g < G - 1);
             const unsigned vbyte = 8u * ((unsigned)(fromL ? g - 1 : g + 1) * RPLC_WG_WORDS + sb + (fromL ? RPLC_W_R : RPLC_W_L) + 2u * (unsigned)e);
-            typedef unsigned u4 __attribute__((ext_vector_type(4)));
             u4 xp_ = {0u, 0u, 0u, 0u}, xv_ = {0u, 0u, 0u, 0u};
             unsigned spins = 0;
             const unsigned pb_ = wantp ? pbyte : 0u, vb_ = wantv ? vbyte : 0u;
@@ -149,8 +117,7 @@ __global__ __launch_bounds__(RPLC_NW * 64, 2) void pcg_rplc_f64_kernel(ClusterAr
                 if (__all(ok)) break;
                 __builtin_amdgcn_s_sleep(1);
             } while (++spins < CL_SPIN_LIMIT);
-            const real halo = __builtin_bit_cast(real, ((unsigned long long)xv_.y << 32) | (unsigned long long)xv_.x);
-            const real partial = __builtin_bit_cast(real, ((unsigned long long)xp_.y << 32) | (unsigned long long)xp_.x);
+            const real halo = granule_value(xv_), partial = granule_value(xp_);
             if (wantv) {
                 real* dst = e < 14 ? bufA : bufB;
                 dst[(fromL ? 0 : KL + 1) * NS + (e < 14 ? e : e - 14)] = halo;
@@ -159,13 +126,6 @@ __global__ __launch_bounds__(RPLC_NW * 64, 2) void pcg_rplc_f64_kernel(ClusterAr
             // the same in every member (lane l = member l / NW, wave l % NW), one value for the workgroup
             const real tot_ = rpl_wave_fold(wantp ? partial : real(0));
             if (lane == 0) { red[epoch & 1u] = tot_; if (spins >= CL_SPIN_LIMIT) bc[0] = 1.0; }
-#ifdef RPLC_DEBUG
-            if (spins >= CL_SPIN_LIMIT) {
-                double* d = ca.p.lambda + g * 256 + lane * 4;
-                d[0] = (double)xp_.z; d[1] = (double)xv_.z;
-                d[2] = (double)epoch; d[3] = (wantp ? 1.0 : 0.0) + (wantv ? 2.0 : 0.0) + (same_xcd ? 4.0 : 0.0);
-            }
-#endif
         }
         lds_barrier();
         if (bc[0] != 0.0) failed = true;
@@ -186,20 +146,12 @@ __global__ __launch_bounds__(RPLC_NW * 64, 2) void pcg_rplc_f64_kernel(ClusterAr
                 int bn = 0;
                 if (g == 0) {
                     if (lane == 0) {
-                        bn = (int)nclusters + (int)__hip_atomic_fetch_add(kp->queue, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (same_xcd) granule_store_l2<RPLC_SLOT_T>(my_words, 0u, ((unsigned long long)seq << 32) | (unsigned)bn);
-                        else granule_store<RPLC_SLOT_T>(my_words, 0u, ((unsigned long long)seq << 32) | (unsigned)bn);
+                        bn = cluster_hand_out<RPLC_SLOT_T>(kp, my_words, seq, nclusters, same_xcd);
                     }
                 } else {
-                    unsigned long long x = 0;
-                    unsigned spins = 0;
-                    do {
-                        x = granule_load<RPLC_SLOT_T>(cl_words, 0u);
-                        if ((unsigned)(x >> 32) == seq) break;
-                        __builtin_amdgcn_s_sleep(1);
-                    } while (++spins < CL_SPIN_LIMIT);
-                    bn = (int)(unsigned)x;
-                    if (spins >= CL_SPIN_LIMIT && lane == 0) bc[0] = 1.0;
+                    const ClusterDraw d = cluster_await_trajectory<RPLC_SLOT_T>(cl_words, seq);
+                    bn = d.index;
+                    if (d.timed_out && lane == 0) bc[0] = 1.0;
                 }
                 if (lane == 0) reinterpret_cast<int*>(bc)[2] = bn;
             }
@@ -327,7 +279,7 @@ __global__ __launch_bounds__(RPLC_NW * 64, 2) void pcg_rplc_f64_kernel(ClusterAr
             //      from the handle's copy of lambda0 — its peers may be past their last hand-off and have written their knots) ----
             if (ca.test_fail && cl == 0 && g == G - 1 && seq == 1) failed = true;
             if (failed) {
-                if (tid == 0) { kp->p.iters[b] = 0xFFFFFFFFu; kp->p.max_iter_exit[b] = 2; }
+                cluster_report_abandoned(kp, b, tid);
                 break;
             }
             if (act) {
@@ -336,10 +288,7 @@ __global__ __launch_bounds__(RPLC_NW * 64, 2) void pcg_rplc_f64_kernel(ClusterAr
                 if (kp->p.r_out) kp->p.r_out[e] = r;
                 if (kp->p.p_out) kp->p.p_out[e] = p;
             }
-            if (tid == 0) {
-                if (g == 0) { kp->p.iters[b] = iters; kp->p.max_iter_exit[b] = (uint8_t)max_iter_exit; }
-                __hip_atomic_fetch_add(kp->fail_flags + (size_t)b * CL_FLAG_STRIDE, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            cluster_finish(kp, b, g == 0, tid, iters, max_iter_exit);
         }
         lds_barrier();                                      // LDS is restaged for the next trajectory
     }
