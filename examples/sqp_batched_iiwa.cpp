@@ -3,11 +3,14 @@
 //     mpcg_generate_kkt -> mpcg_form_schur (SS) -> mpcg_pcg_solve -> mpcg_compute_dz -> mpcg_compute_merit (8 step sizes -1 / 2^p) -> mpcg_line_search_step
 // — the stages of include/pcg/sqp.cuh:190-353 of the reference, whose line search runs eight cooperative launches, a device synchronisation and a
 // read-back per iteration for ONE trajectory.  Here nothing synchronises inside an iteration: the merit of every trajectory and iteration and the
-// accepted exponents wait in device buffers and are read once at the end.  rho stays at its initial value (it is one scalar per mpcg_form_schur
-// call; the reference's adaptation, sqp.cuh:304-320, belongs to a caller that reads d_step back — mpcgpu_compat::use_mpcg_line_search does).
+// accepted exponents wait in device buffers and are read once at the end.  Without --adapt-rho, rho stays at its initial value (one scalar per
+// mpcg_form_schur call).  With it every trajectory carries its own rho, drho and "finished" flag in device memory: mpcg_form_schur_rhov reads the
+// rho vector and mpcg_line_search_step_rho applies the reference's adaptation (sqp.cuh:304-320: a failed line search multiplies drho and rho by
+// 1.2, a success divides them, rho > 10 gives the trajectory up and resets rho) — still without a synchronisation inside an iteration; the JSON line
+// then also carries "rho_final", "drho_final" and "done" per trajectory.
 // Prints one JSON line; exits 0 only if every trajectory's merit went down.
 //   hipcc --offload-arch=gfx950 -O2 -Iinclude examples/sqp_batched_iiwa.cpp -Lmpcgpu_amd -lmpcg_hip
-//   sqp_batched_iiwa [--batch 8] [--knots 32] [--iters 4] [--mu 10] [--rho 1e-3]
+//   sqp_batched_iiwa [--batch 8] [--knots 32] [--iters 4] [--mu 10] [--rho 1e-3] [--adapt-rho]
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -56,7 +59,10 @@ static T* dalloc(size_t count) {
 int main(int argc, char** argv) {
     int B = 8, N = 32, K = 4;
     float mu = 10.f, rho = 1e-3f;
-    for (int i = 1; i + 1 < argc; i += 2) {
+    bool adapt = false;
+    for (int i = 1; i < argc; i += 2) {
+        if (!strcmp(argv[i], "--adapt-rho")) { adapt = true; --i; continue; }
+        if (i + 1 >= argc) break;
         if (!strcmp(argv[i], "--batch")) B = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--knots")) N = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--iters")) K = atoi(argv[i + 1]);
@@ -110,6 +116,15 @@ int main(int argc, char** argv) {
     int32_t* d_step_hist = dalloc<int32_t>((size_t)K * B);
     uint32_t* d_iters = dalloc<uint32_t>(B);
     uint8_t* d_exit = dalloc<uint8_t>(B);
+    // --adapt-rho: the per-trajectory state of the rho adaptation (rho = the initial value, drho = 1, nobody finished)
+    float* d_rho = dalloc<float>(B);
+    float* d_drho = dalloc<float>(B);
+    uint8_t* d_done = dalloc<uint8_t>(B);
+    {
+        const std::vector<float> rho0((size_t)B, rho), one((size_t)B, 1.0f);
+        HIP_OK(hipMemcpy(d_rho, rho0.data(), B * sizeof(float), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_drho, one.data(), B * sizeof(float), hipMemcpyHostToDevice));
+    }
     HIP_OK(hipMemcpy(d_xu, xu.data(), xu.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_goals, goals.data(), goals.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_xs, xs.data(), xs.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -124,11 +139,14 @@ int main(int argc, char** argv) {
     HIP_OK(hipMemcpyAsync(d_merit_hist, d_merit_ref, B * sizeof(float), hipMemcpyDeviceToDevice, st));
     for (int it = 0; it < K; ++it) {                                          // no host synchronisation in here
         MPCG_OK_OR_DIE(h, mpcg_generate_kkt(h, plant, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, st));
-        MPCG_OK_OR_DIE(h, mpcg_form_schur(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, rho, (uint32_t)B, MPCG_PRECOND_SS, st));
+        if (adapt) MPCG_OK_OR_DIE(h, mpcg_form_schur_rhov(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_rho, (uint32_t)B, MPCG_PRECOND_SS, st));
+        else MPCG_OK_OR_DIE(h, mpcg_form_schur(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, rho, (uint32_t)B, MPCG_PRECOND_SS, st));
         MPCG_OK_OR_DIE(h, mpcg_pcg_solve(h, d_S, d_Pinv, d_gamma, d_lambda, (uint32_t)B, 3000, 1e-7f, MPCG_PRECOND_SS, d_iters, d_exit, st));
         MPCG_OK_OR_DIE(h, mpcg_compute_dz(h, m, d_G, d_C, d_g, d_lambda, d_dz, (uint32_t)B, st));
         MPCG_OK_OR_DIE(h, mpcg_compute_merit(h, plant, m, dt, d_goals, d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, (uint32_t)B, st));
-        MPCG_OK_OR_DIE(h, mpcg_line_search_step(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step_hist + (size_t)it * B, (uint32_t)B, st));
+        if (adapt) MPCG_OK_OR_DIE(h, mpcg_line_search_step_rho(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step_hist + (size_t)it * B, d_rho, d_drho, d_done,
+                                                               1.2f, 1e-3f, 10.f, rho, (uint32_t)B, st));
+        else MPCG_OK_OR_DIE(h, mpcg_line_search_step(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step_hist + (size_t)it * B, (uint32_t)B, st));
         HIP_OK(hipMemcpyAsync(d_merit_hist + (size_t)(it + 1) * B, d_merit_ref, B * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     HIP_OK(hipStreamSynchronize(st));
@@ -151,10 +169,24 @@ int main(int argc, char** argv) {
         for (int it = 0; it < K; ++it) printf("%s%d", it ? ", " : "", expo[(size_t)it * B + b]);
         printf("]");
     }
+    if (adapt) {
+        std::vector<float> rho_f(B), drho_f(B);
+        std::vector<uint8_t> done_f(B);
+        HIP_OK(hipMemcpy(rho_f.data(), d_rho, B * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(drho_f.data(), d_drho, B * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(done_f.data(), d_done, B * sizeof(uint8_t), hipMemcpyDeviceToHost));
+        printf("], \"rho_final\": [");
+        for (int b = 0; b < B; ++b) printf("%s%.9g", b ? ", " : "", (double)rho_f[b]);
+        printf("], \"drho_final\": [");
+        for (int b = 0; b < B; ++b) printf("%s%.9g", b ? ", " : "", (double)drho_f[b]);
+        printf("], \"done\": [");
+        for (int b = 0; b < B; ++b) printf("%s%d", b ? ", " : "", (int)done_f[b]);
+    }
     printf("], \"ok\": %s}\n", ok ? "true" : "false");
 
     for (void* p : {(void*)d_xu, (void*)d_goals, (void*)d_xs, (void*)d_G, (void*)d_C, (void*)d_g, (void*)d_c, (void*)d_S, (void*)d_Pinv, (void*)d_gamma,
-                    (void*)d_lambda, (void*)d_dz, (void*)d_merit, (void*)d_merit_ref, (void*)d_merit_hist, (void*)d_step_hist, (void*)d_iters, (void*)d_exit})
+                    (void*)d_lambda, (void*)d_dz, (void*)d_merit, (void*)d_merit_ref, (void*)d_merit_hist, (void*)d_step_hist, (void*)d_iters, (void*)d_exit,
+                    (void*)d_rho, (void*)d_drho, (void*)d_done})
         HIP_OK(hipFree(p));
     HIP_OK(hipStreamDestroy(st));
     mpcg_plant_destroy(plant);

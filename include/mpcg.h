@@ -214,12 +214,23 @@ int mpcg_pcg_solve_f16(mpcg_handle *h,
  * sized from the largest control_size the handle has seen — a later call with a larger one re-allocates it (after a device synchronisation,
  * refused inside a stream capture like every first call).
  *
+ * mpcg_form_schur_rhov is mpcg_form_schur with ONE RHO PER TRAJECTORY, read from device memory: trajectory b is formed with d_rho[b] (d_rho
+ * [batch] floats).  Everything else — layouts, side effects, preconditioner choices, routing between the register-resident and the
+ * run-time-dimension kernels, "schur_chunk", the handle-owned buffers and what a first call inside a stream capture is refused for — is
+ * mpcg_form_schur's; the additions are the same instructions, so a trajectory's outputs are bit for bit those of the scalar call with
+ * rho = d_rho[b].  Because rho is read when the kernel RUNS, a captured graph of the call follows whatever mpcg_line_search_step_rho (below) has
+ * written into d_rho since.  d_rho is device data and is NOT validated: a non-positive or NaN entry gives that trajectory what the scalar call would
+ * give for it, nothing else.  MPCG_ERR_INVALID for d_rho == NULL.
+ *
  * mpcg_compute_dz replaces compute_dz(state_size, control_size, knot_points, d_Ginv_dense, d_C_dense,
  * d_g, d_lambda, d_dz) (include/common/dz.cuh:124-136), batched; d_dz [batch][(n+m)N - m].  Any 1 <= control_size <= state_size <= 64;
  * pure stream work from the first call on. */
 int mpcg_form_schur(mpcg_handle *h, uint32_t control_size, float *d_G_dense, const float *d_C_dense,
                     const float *d_g, const float *d_c, float *d_S, float *d_Pinv, float *d_gamma,
                     float rho, uint32_t batch, mpcg_precond precond, void *stream);
+int mpcg_form_schur_rhov(mpcg_handle *h, uint32_t control_size, float *d_G_dense, const float *d_C_dense,
+                         const float *d_g, const float *d_c, float *d_S, float *d_Pinv, float *d_gamma,
+                         const float *d_rho /* [batch] */, uint32_t batch, mpcg_precond precond, void *stream);
 int mpcg_compute_dz(mpcg_handle *h, uint32_t control_size, const float *d_Ginv_dense,
                     const float *d_C_dense, const float *d_g, const float *d_lambda, float *d_dz,
                     uint32_t batch, void *stream);
@@ -251,10 +262,13 @@ int mpcg_pcg_solve_ref_f64(mpcg_handle *h, double *d_S, double *d_Pinv, double *
 /* The steps either side of the solve for linsys_t = double: mpcg_form_schur / mpcg_compute_dz with every float replaced by double (same
  * layouts, same side effects, same preconditioner choices).  Functional twins — one wavefront per knot, operands in LDS — in the float
  * path's operation order: bit-identical to the oracle's double instantiation (tests/test_gpu_f64.py).  Shapes other than 14 x 7: as the float
- * entry points (tests/test_gpu_generic_producers.py). */
+ * entry points (tests/test_gpu_generic_producers.py).  mpcg_form_schur_rhov_f64: mpcg_form_schur_rhov in double, d_rho [batch] doubles. */
 int mpcg_form_schur_f64(mpcg_handle *h, uint32_t control_size, double *d_G_dense, const double *d_C_dense,
                         const double *d_g, const double *d_c, double *d_S, double *d_Pinv, double *d_gamma,
                         double rho, uint32_t batch, mpcg_precond precond, void *stream);
+int mpcg_form_schur_rhov_f64(mpcg_handle *h, uint32_t control_size, double *d_G_dense, const double *d_C_dense,
+                             const double *d_g, const double *d_c, double *d_S, double *d_Pinv, double *d_gamma,
+                             const double *d_rho /* [batch] */, uint32_t batch, mpcg_precond precond, void *stream);
 int mpcg_compute_dz_f64(mpcg_handle *h, uint32_t control_size, const double *d_Ginv_dense,
                         const double *d_C_dense, const double *d_g, const double *d_lambda, double *d_dz,
                         uint32_t batch, void *stream);
@@ -338,11 +352,26 @@ int mpcg_generate_kkt(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_
  * (strict: the first of equals wins, a value equal to d_merit_ref is no improvement, a NaN never wins), then d_step[b] = p and, if p >= 0,
  * d_merit_ref[b] = best and every element xu = fmaf(step_sizes[p], dz, xu) — the very float mpcg_compute_merit evaluated, so the merit of the new
  * iterate at step size 0 IS the new d_merit_ref, bit for bit.  p = -1 leaves d_xu and d_merit_ref untouched.  No dynamics: every handle shape,
- * any 1 <= control_size <= state_size; d_dz, d_xu [batch][(n+m)N - m].  Pure stream work from the first call on.  The rho adaptation of
- * sqp.cuh:304-320 stays with the caller (rho is one scalar per mpcg_form_schur call); d_step is what it needs.
+ * any 1 <= control_size <= state_size; d_dz, d_xu [batch][(n+m)N - m].  Pure stream work from the first call on.
  *
- * Both calls:  MPCG_ERR_INVALID      a null required pointer; num_steps 0 or > MPCG_MAX_STEP_SIZES; batch > max_batch; d_dz == NULL with a
- *                                    non-zero step size; a plant on another device than the handle's; control_size 0 or > state_size (step)
+ * mpcg_line_search_step_rho is that step followed by the reference's rho adaptation (include/pcg/sqp.cuh:304-320), with rho, its growth
+ * factor drho and a "finished" flag as device state per trajectory — d_rho is the vector mpcg_form_schur_rhov reads, so a batched SQP iteration
+ * adapts rho without reading anything back, and one captured iteration replays for a whole solve.  Per trajectory b:
+ *   d_done[b] != 0:  d_step[b] = MPCG_STEP_FROZEN and NOTHING else is written (d_xu, d_merit_ref, d_rho, d_drho, d_done stay as they are).  Any
+ *                    non-zero value freezes: the caller may set the flag itself, e.g. on convergence.
+ *   otherwise:       p, d_step, d_merit_ref and d_xu exactly as mpcg_line_search_step (the same code), then in float, one rounding per
+ *                    operation, correctly rounded divisions:
+ *                      p <  0 (no step):  drho = fmaxf(drho * rho_factor, rho_factor);        rho = fmaxf(rho * drho, rho_min);
+ *                                         if (rho > rho_max) { rho = rho_reset; d_done[b] = 1; }     (the reference gives the solve up)
+ *                      p >= 0:            drho = fminf(drho / rho_factor, 1.0f / rho_factor);  rho = fmaxf(rho * drho, rho_min)
+ * The reference's constants: rho_factor 1.2, rho_min 1e-3, rho_max 10, rho_reset the caller's.  Finished trajectories are not compacted away:
+ * the other stages keep computing them (wasted work, never wrong — this call no longer changes them).  d_rho, d_drho are device data and
+ * are not validated.  Pure stream work from the first call on.
+ *
+ * All three calls:  MPCG_ERR_INVALID      a null required pointer; num_steps 0 or > MPCG_MAX_STEP_SIZES; batch > max_batch; d_dz == NULL with a
+ *                                    non-zero step size; a plant on another device than the handle's; control_size 0 or > state_size (step);
+ *                                    mpcg_line_search_step_rho: d_rho, d_drho or d_done NULL, a parameter that is not finite,
+ *                                    rho_factor <= 1, rho_min <= 0, rho_max < rho_min
  *              MPCG_ERR_UNSUPPORTED  mpcg_compute_merit on anything but state_size 14 / control_size 7
  *              MPCG_OK               batch == 0: nothing is launched */
 #define MPCG_MAX_STEP_SIZES 16
@@ -355,6 +384,12 @@ int mpcg_compute_merit(mpcg_handle *h, const mpcg_plant *plant, uint32_t control
 int mpcg_line_search_step(mpcg_handle *h, uint32_t control_size, const float *d_merit, const float *step_sizes, uint32_t num_steps,
                           float *d_merit_ref /* [batch] in/out */, const float *d_dz, float *d_xu /* in/out */,
                           int32_t *d_step /* [batch] out */, uint32_t batch, void *stream);
+#define MPCG_STEP_FROZEN (-2)
+int mpcg_line_search_step_rho(mpcg_handle *h, uint32_t control_size, const float *d_merit, const float *step_sizes, uint32_t num_steps,
+                              float *d_merit_ref /* [batch] in/out */, const float *d_dz, float *d_xu /* in/out */,
+                              int32_t *d_step /* [batch] out */, float *d_rho /* [batch] in/out */, float *d_drho /* [batch] in/out */,
+                              uint8_t *d_done /* [batch] in/out */, float rho_factor, float rho_min, float rho_max, float rho_reset,
+                              uint32_t batch, void *stream);
 
 /* ---- LINSYS_SOLVE == 0 as a selectable solver: the reference's CPU LDL^T path ----
  * The reference's second linear-system path factors the (negated) Schur matrix on the HOST with QDLDL

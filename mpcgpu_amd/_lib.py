@@ -20,6 +20,7 @@ MPCG_PRECOND_NONE = 0
 MPCG_PRECOND_JACOBI = 1
 MPCG_PRECOND_SS = 3
 MPCG_MAX_STEP_SIZES = 16
+MPCG_STEP_FROZEN = -2
 
 # every symbol include/mpcg.h declares: (name, restype, argtypes)
 _f32p = C.c_void_p   # device pointers travel as integers
@@ -43,9 +44,13 @@ SYMBOLS = {
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mpcg_form_schur": (C.c_int, [C.c_void_p, C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float,
                                   C.c_uint32, C.c_int, C.c_void_p]),
+    "mpcg_form_schur_rhov": (C.c_int, [C.c_void_p, C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                       C.c_uint32, C.c_int, C.c_void_p]),
     "mpcg_compute_dz": (C.c_int, [C.c_void_p, C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_uint32, C.c_void_p]),
     "mpcg_form_schur_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_double, C.c_uint32, C.c_int, C.c_void_p]),
+    "mpcg_form_schur_rhov_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "mpcg_compute_dz_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_prep_csr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mpcg_bd_to_csr_lowertri": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_float, C.c_uint32, C.c_void_p]),
@@ -63,6 +68,9 @@ SYMBOLS = {
                                      C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_line_search_step": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_line_search_step_rho": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
+                                            C.c_uint32, C.c_void_p]),
     "mpcg_ldl_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
     "mpcg_ldl_destroy": (C.c_int, [C.c_void_p]),
     "mpcg_ldl_pattern": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),

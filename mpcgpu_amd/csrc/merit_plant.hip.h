@@ -21,6 +21,7 @@
 // knot): results are bitwise reproducible and independent of the rest of the batch and of the other step sizes of the call.
 // LDS per wavefront: the KKT kernel's item records (4 x 840 B) + 11 recursion records per item (4 x 3,256 B) = 16,384 B — its budget exactly.
 #pragma once
+#include <type_traits>
 #include "kkt_plant.hip.h"
 #pragma clang fp contract(fast)
 
@@ -203,8 +204,30 @@ struct StepArgs {
     float alpha[MERIT_MAX_STEPS];
 };
 
-__global__ __launch_bounds__(256) void line_search_step_kernel(StepArgs a) {
+// mpcg_line_search_step_rho: the same selection and update, then the rho adaptation of sqp.cuh:304-320 per trajectory, in float with one rounding
+// per operation (nothing here can contract: no product feeds an addition) and correctly rounded divisions:
+//   p < 0 :  drho = max(drho * f, f);      rho = max(rho * drho, rho_min);  rho > rho_max: rho = rho_reset, done = 1
+//   p >= 0:  drho = min(drho / f, 1 / f);  rho = max(rho * drho, rho_min)
+// A trajectory with done != 0 on entry is frozen: step = STEP_FROZEN and nothing else is written.
+struct StepRhoArgs : StepArgs {
+    float* rho;                          // [batch] in/out
+    float* drho;                         // [batch] in/out
+    uint8_t* done;                       // [batch] in/out
+    float factor, rho_min, rho_max, rho_reset;
+};
+constexpr int32_t STEP_FROZEN = -2;      // MPCG_STEP_FROZEN
+
+// SA = StepArgs: mpcg_line_search_step; SA = StepRhoArgs: mpcg_line_search_step_rho — one selection, one update
+template <class SA = StepArgs>
+__global__ __launch_bounds__(256) void line_search_step_kernel(SA a) {
+    constexpr bool RHO = std::is_same<SA, StepRhoArgs>::value;
     const size_t b = blockIdx.x;
+    if constexpr (RHO) {
+        if (a.done[b] != 0) {                                // (uniform; nobody in this workgroup writes done before the barrier below)
+            if (threadIdx.x == 0) a.step[b] = STEP_FROZEN;
+            return;
+        }
+    }
     float best = a.merit_ref[b], al = 0.f;
     int p = -1;
 #pragma unroll
@@ -217,6 +240,18 @@ __global__ __launch_bounds__(256) void line_search_step_kernel(StepArgs a) {
     if (threadIdx.x == 0) {
         a.step[b] = p;
         if (p >= 0) a.merit_ref[b] = best;
+        if constexpr (RHO) {
+            float rho = a.rho[b], drho = a.drho[b];
+            if (p < 0) {
+                drho = fmaxf(__fmul_rn(drho, a.factor), a.factor);
+                rho = fmaxf(__fmul_rn(rho, drho), a.rho_min);
+                if (rho > a.rho_max) { rho = a.rho_reset; a.done[b] = 1; }
+            } else {
+                drho = fminf(__fdiv_rn(drho, a.factor), __fdiv_rn(1.0f, a.factor));
+                rho = fmaxf(__fmul_rn(rho, drho), a.rho_min);
+            }
+            a.rho[b] = rho; a.drho[b] = drho;
+        }
     }
     if (p < 0) return;
     const float* dz = a.dz + b * a.len;

@@ -1,6 +1,7 @@
 // mpcg_plant.hip — C ABI (include/mpcg.h) of the producer of the path's inputs: the robot as data (mpcg_plant) and the KKT block assembly
 // mpcg_generate_kkt over the gfx950 kernel in kkt_plant.hip.h; the stage behind dz — mpcg_compute_merit and
 // mpcg_line_search_step over merit_plant.hip.h.
+#include <cmath>
 #include "mpcg_handle.hpp"
 #include "kkt_plant.hip.h"
 #include "merit_plant.hip.h"
@@ -271,22 +272,47 @@ int mpcg_compute_merit(mpcg_handle* h, const mpcg_plant* plant, uint32_t control
     return MPCG_OK;
 }
 
-int mpcg_line_search_step(mpcg_handle* h, uint32_t control_size, const float* d_merit, const float* step_sizes, uint32_t num_steps,
-                          float* d_merit_ref, const float* d_dz, float* d_xu, int32_t* d_step, uint32_t batch, void* stream) {
+// mpcg_line_search_step and mpcg_line_search_step_rho: one host path (fn: the entry point's name; rho: null for the former)
+static int line_search_step_impl(mpcg_handle* h, const char* fn, uint32_t control_size, const float* d_merit, const float* step_sizes, uint32_t num_steps,
+                                 float* d_merit_ref, const float* d_dz, float* d_xu, int32_t* d_step, const StepRhoArgs* rho, uint32_t batch, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
-    if (!d_merit || !d_merit_ref || !d_dz || !d_xu || !d_step) return fail(h, MPCG_ERR_INVALID, "mpcg_line_search_step: null device pointer");
-    { const int rc = check_steps(h, "mpcg_line_search_step", step_sizes, num_steps); if (rc != MPCG_OK) return rc; }
-    if (control_size == 0 || control_size > h->n) return fail(h, MPCG_ERR_INVALID, "mpcg_line_search_step: control_size must be 1..state_size");
+    if (!d_merit || !d_merit_ref || !d_dz || !d_xu || !d_step || (rho && (!rho->rho || !rho->drho || !rho->done)))
+        return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    { const int rc = check_steps(h, fn, step_sizes, num_steps); if (rc != MPCG_OK) return rc; }
+    if (control_size == 0 || control_size > h->n) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": control_size must be 1..state_size");
+    if (rho) {
+        if (!std::isfinite(rho->factor) || !std::isfinite(rho->rho_min) || !std::isfinite(rho->rho_max) || !std::isfinite(rho->rho_reset))
+            return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": rho_factor, rho_min, rho_max and rho_reset must be finite");
+        if (!(rho->factor > 1.0f) || !(rho->rho_min > 0.0f) || rho->rho_max < rho->rho_min)
+            return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": needs rho_factor > 1, rho_min > 0 and rho_max >= rho_min");
+    }
     if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_line_search_step: batch exceeds max_batch");
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
-    StepArgs a;
+    StepRhoArgs ra{};
+    if (rho) ra = *rho;
+    StepArgs& a = ra;
     a.merit = d_merit; a.merit_ref = d_merit_ref; a.dz = d_dz; a.xu = d_xu; a.step = d_step; a.A = (int)num_steps;
     a.len = (size_t)(h->n + control_size) * h->N - control_size;
     for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) a.alpha[i] = i < num_steps ? step_sizes[i] : 0.f;
-    hipLaunchKernelGGL(line_search_step_kernel, dim3(batch), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    if (rho) hipLaunchKernelGGL(line_search_step_kernel<StepRhoArgs>, dim3(batch), dim3(256), 0, static_cast<hipStream_t>(stream), ra);
+    else hipLaunchKernelGGL(line_search_step_kernel<StepArgs>, dim3(batch), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
+}
+
+int mpcg_line_search_step(mpcg_handle* h, uint32_t control_size, const float* d_merit, const float* step_sizes, uint32_t num_steps,
+                          float* d_merit_ref, const float* d_dz, float* d_xu, int32_t* d_step, uint32_t batch, void* stream) {
+    return line_search_step_impl(h, "mpcg_line_search_step", control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, nullptr, batch, stream);
+}
+
+int mpcg_line_search_step_rho(mpcg_handle* h, uint32_t control_size, const float* d_merit, const float* step_sizes, uint32_t num_steps,
+                              float* d_merit_ref, const float* d_dz, float* d_xu, int32_t* d_step, float* d_rho, float* d_drho, uint8_t* d_done,
+                              float rho_factor, float rho_min, float rho_max, float rho_reset, uint32_t batch, void* stream) {
+    static_assert(STEP_FROZEN == MPCG_STEP_FROZEN, "the frozen code of the header");
+    StepRhoArgs r{};
+    r.rho = d_rho; r.drho = d_drho; r.done = d_done; r.factor = rho_factor; r.rho_min = rho_min; r.rho_max = rho_max; r.rho_reset = rho_reset;
+    return line_search_step_impl(h, "mpcg_line_search_step_rho", control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, &r, batch, stream);
 }
 
 }  // extern "C"

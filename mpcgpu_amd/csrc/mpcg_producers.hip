@@ -78,7 +78,9 @@ static int gen_ensure_staging(mpcg_handle* h, T** buf, size_t* have, size_t need
 template <typename T> struct ProducerTraits;
 template <> struct ProducerTraits<float> {
     typedef sw::WalkArgs WalkArgs;
-    static constexpr auto walk_kernel = sw::schur_walk_kernel, seam_kernel = sw::schur_seam_kernel;
+    typedef sw::WalkArgsV WalkArgsV;
+    static constexpr auto walk_kernel = sw::schur_walk_kernel<sw::WalkArgs>, seam_kernel = sw::schur_seam_kernel;
+    static constexpr auto walk_kernel_rhov = sw::schur_walk_kernel<sw::WalkArgsV>;
     static constexpr auto dz_dpp_kernel = sw::compute_dz_dpp_kernel;
     static constexpr auto staging = &mpcg_handle::ginv_scratch;
     static constexpr auto staging_elems = &mpcg_handle::ginv_scratch_floats;
@@ -86,7 +88,9 @@ template <> struct ProducerTraits<float> {
 };
 template <> struct ProducerTraits<double> {
     typedef sw64::WalkArgs64 WalkArgs;
-    static constexpr auto walk_kernel = sw64::schur_walk_f64_kernel, seam_kernel = sw64::schur_seam_f64_kernel;
+    typedef sw64::WalkArgs64V WalkArgsV;
+    static constexpr auto walk_kernel = sw64::schur_walk_f64_kernel<sw64::WalkArgs64>, seam_kernel = sw64::schur_seam_f64_kernel;
+    static constexpr auto walk_kernel_rhov = sw64::schur_walk_f64_kernel<sw64::WalkArgs64V>;
     static constexpr auto dz_dpp_kernel = sw64::compute_dz_dpp_f64_kernel;
     static constexpr auto staging = &mpcg_handle::ginv_scratch_f64;
     static constexpr auto staging_elems = &mpcg_handle::ginv_scratch_f64_elems;
@@ -104,8 +108,9 @@ static_assert(dz_bytes_per_knot(14, 7, 4) == 1176 && dz_bytes_per_knot(14, 7, 8)
 
 // The LDS formation: one workgroup per block row, G^-1 through a handle-owned staging buffer (the second kernel publishes it).
 // fn: the entry point's name, why: what sent a (14, 7) call here — both for the refusal of a first call inside a stream capture.
+// a.rho_v set: the per-trajectory instantiation of the formation kernel; the completion kernel never sees rho.
 template <typename T>
-static int form_schur_lds(mpcg_handle* h, const char* fn, const char* why, SchurArgsT<T> a, hipStream_t st) {
+static int form_schur_lds(mpcg_handle* h, const char* fn, const char* why, SchurArgsVT<T> a, hipStream_t st) {
     typedef ProducerTraits<T> Tr;
     const int n = a.n, m = a.m, N = a.N;
     h->last_schur_chunk = 0;
@@ -118,11 +123,17 @@ static int form_schur_lds(mpcg_handle* h, const char* fn, const char* why, Schur
     a.Ginv_scratch = h->*Tr::staging;
     const long items = (long)a.batch * N;
     const int nt = gen_threads(n);
-    { const int rc = gen_raise_lds(h, gen::form_schur_kernel<T>, lds); if (rc != MPCG_OK) return rc; }
-    hipLaunchKernelGGL(gen::form_schur_kernel<T>, dim3(gen_grid(h, items, lds)), dim3(nt), lds, st, a);
+    const SchurArgsT<T>& as = a;
+    if (a.rho_v) {
+        { const int rc = gen_raise_lds(h, gen::form_schur_kernel<T, SchurArgsVT<T>>, lds); if (rc != MPCG_OK) return rc; }
+        hipLaunchKernelGGL((gen::form_schur_kernel<T, SchurArgsVT<T>>), dim3(gen_grid(h, items, lds)), dim3(nt), lds, st, a);
+    } else {
+        { const int rc = gen_raise_lds(h, gen::form_schur_kernel<T>, lds); if (rc != MPCG_OK) return rc; }
+        hipLaunchKernelGGL(gen::form_schur_kernel<T>, dim3(gen_grid(h, items, lds)), dim3(nt), lds, st, as);
+    }
     HIP_TRY(h, hipGetLastError());
     { const int rc = gen_raise_lds(h, gen::complete_ss_kernel<T>, lds2); if (rc != MPCG_OK) return rc; }
-    hipLaunchKernelGGL(gen::complete_ss_kernel<T>, dim3(gen_grid(h, items, lds2)), dim3(nt), lds2, st, a);
+    hipLaunchKernelGGL(gen::complete_ss_kernel<T>, dim3(gen_grid(h, items, lds2)), dim3(nt), lds2, st, as);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
@@ -131,7 +142,7 @@ static int form_schur_lds(mpcg_handle* h, const char* fn, const char* why, Schur
 // second kernel closes the seams between chunks.  L trades parallelism against seam work: as long as a call has fewer than ~6 wavefronts of
 // four chunks per CU the chunks are made shorter (L = 1: every row a seam — one trajectory of the MPC loop's own call; 16 at 1024 x 128 knots).
 template <typename T>
-static int form_schur_walk(mpcg_handle* h, const SchurArgsT<T>& a, hipStream_t st) {
+static int form_schur_walk(mpcg_handle* h, const SchurArgsVT<T>& a, hipStream_t st) {
     typedef ProducerTraits<T> Tr;
     int wL = h->schur_chunk;
     if (wL <= 0) {
@@ -142,14 +153,17 @@ static int form_schur_walk(mpcg_handle* h, const SchurArgsT<T>& a, hipStream_t s
     const int wchunks = (a.N - 1 + wL - 1) / wL;
     // seam buffer: one Q^-1 per chunk (ensure_seam_buffer: sized once for every automatic chunk length of this handle)
     { const int rc = ensure_seam_buffer(h, (size_t)a.batch * wchunks, sizeof(T), st); if (rc != MPCG_OK) return rc; }
-    typename Tr::WalkArgs w;
+    typename Tr::WalkArgsV wv;
+    typename Tr::WalkArgs& w = wv;               // (what the scalar walking kernel and the seam kernel take)
     w.s = a;                                     // (Ginv_scratch stays null: G^-1 is written in place)
     w.seam_qinv = static_cast<T*>(h->seam_qinv); w.L = wL; w.chunks = wchunks;
+    wv.rho_v = a.rho_v;
     h->last_schur_chunk = wL;
     const long capw = (long)h->num_cus * 64;
     long bw = ((long)a.batch * wchunks + 3) / 4;
     if (bw > capw) bw = capw;
-    hipLaunchKernelGGL(Tr::walk_kernel, dim3((unsigned)bw), dim3(64), 0, st, w);
+    if (a.rho_v) hipLaunchKernelGGL(Tr::walk_kernel_rhov, dim3((unsigned)bw), dim3(64), 0, st, wv);
+    else hipLaunchKernelGGL(Tr::walk_kernel, dim3((unsigned)bw), dim3(64), 0, st, w);
     HIP_TRY(h, hipGetLastError());
     if (wchunks > 1) {
         long bs = ((long)a.batch * (wchunks - 1) + 3) / 4;
@@ -160,13 +174,17 @@ static int form_schur_walk(mpcg_handle* h, const SchurArgsT<T>& a, hipStream_t s
     return MPCG_OK;
 }
 
-// mpcg_form_schur and mpcg_form_schur_f64 (fn: the entry point's name, for its messages).  Same arithmetic order in float and double and on
-// either route: bit-identical to the oracle's instantiation for T.
+// One rho per call, or one per trajectory in device memory (the _rhov entry points; never validated: device data)
+template <typename T>
+struct RhoArg { T scalar; const T* vec; bool per_traj; };
+
+// mpcg_form_schur(_rhov) and mpcg_form_schur(_rhov)_f64 (fn: the entry point's name, for its messages).  Same arithmetic order in float and
+// double, on either route and for either form of rho: bit-identical to the oracle's instantiation for T.
 template <typename T>
 static int form_schur_impl(mpcg_handle* h, const char* fn, uint32_t control_size, T* d_G, const T* d_C, const T* d_g, const T* d_c, T* d_S, T* d_Pinv,
-                           T* d_gamma, T rho, uint32_t batch, mpcg_precond precond, void* stream) {
+                           T* d_gamma, RhoArg<T> rho, uint32_t batch, mpcg_precond precond, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
-    if (!d_G || !d_C || !d_g || !d_c || !d_S || (!d_Pinv && precond != MPCG_PRECOND_NONE) || !d_gamma)
+    if (!d_G || !d_C || !d_g || !d_c || !d_S || (!d_Pinv && precond != MPCG_PRECOND_NONE) || !d_gamma || (rho.per_traj && !rho.vec))
         return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
     { const int rc = gen_check_control(h, fn, control_size); if (rc != MPCG_OK) return rc; }
     if (precond != MPCG_PRECOND_NONE && precond != MPCG_PRECOND_JACOBI && precond != MPCG_PRECOND_SS)
@@ -176,10 +194,10 @@ static int form_schur_impl(mpcg_handle* h, const char* fn, uint32_t control_size
     if ((uint64_t)batch * h->N >= (1ull << 31)) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": batch * knot_points must stay below 2^31");    // (the kernels keep a knot's index in an int)
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    SchurArgsT<T> a;
+    SchurArgsVT<T> a;
     a.G = d_G; a.C = d_C; a.g = d_g; a.c = d_c; a.S = d_S; a.Pinv = d_Pinv; a.gamma = d_gamma;
     a.Ginv_scratch = nullptr; a.Ginv_out = d_G;
-    a.rho = rho; a.n = (int)h->n; a.m = (int)control_size; a.N = (int)h->N; a.batch = (int)batch;
+    a.rho = rho.per_traj ? (T)0 : rho.scalar; a.rho_v = rho.per_traj ? rho.vec : nullptr; a.n = (int)h->n; a.m = (int)control_size; a.N = (int)h->N; a.batch = (int)batch;
     a.ss = precond == MPCG_PRECOND_SS; a.pinv = precond != MPCG_PRECOND_NONE;
     a.k0_only = 0;
     if (gen_route(h, control_size)) return form_schur_lds<T>(h, fn, "", a, st);
@@ -261,7 +279,13 @@ int mpcg_block_solve(mpcg_handle* h, const float* d_S, const float* d_gamma, flo
 int mpcg_form_schur(mpcg_handle* h, uint32_t control_size, float* d_G_dense, const float* d_C_dense, const float* d_g,
                     const float* d_c, float* d_S, float* d_Pinv, float* d_gamma, float rho, uint32_t batch,
                     mpcg_precond precond, void* stream) {
-    return form_schur_impl<float>(h, "mpcg_form_schur", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, rho, batch, precond, stream);
+    return form_schur_impl<float>(h, "mpcg_form_schur", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, {rho, nullptr, false}, batch, precond, stream);
+}
+
+int mpcg_form_schur_rhov(mpcg_handle* h, uint32_t control_size, float* d_G_dense, const float* d_C_dense, const float* d_g,
+                         const float* d_c, float* d_S, float* d_Pinv, float* d_gamma, const float* d_rho, uint32_t batch,
+                         mpcg_precond precond, void* stream) {
+    return form_schur_impl<float>(h, "mpcg_form_schur_rhov", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, {0.f, d_rho, true}, batch, precond, stream);
 }
 
 int mpcg_compute_dz(mpcg_handle* h, uint32_t control_size, const float* d_Ginv_dense, const float* d_C_dense,
@@ -273,7 +297,13 @@ int mpcg_compute_dz(mpcg_handle* h, uint32_t control_size, const float* d_Ginv_d
 int mpcg_form_schur_f64(mpcg_handle* h, uint32_t control_size, double* d_G_dense, const double* d_C_dense, const double* d_g,
                         const double* d_c, double* d_S, double* d_Pinv, double* d_gamma, double rho, uint32_t batch,
                         mpcg_precond precond, void* stream) {
-    return form_schur_impl<double>(h, "mpcg_form_schur_f64", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, rho, batch, precond, stream);
+    return form_schur_impl<double>(h, "mpcg_form_schur_f64", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, {rho, nullptr, false}, batch, precond, stream);
+}
+
+int mpcg_form_schur_rhov_f64(mpcg_handle* h, uint32_t control_size, double* d_G_dense, const double* d_C_dense, const double* d_g,
+                             const double* d_c, double* d_S, double* d_Pinv, double* d_gamma, const double* d_rho, uint32_t batch,
+                             mpcg_precond precond, void* stream) {
+    return form_schur_impl<double>(h, "mpcg_form_schur_rhov_f64", control_size, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, {0.0, d_rho, true}, batch, precond, stream);
 }
 
 int mpcg_compute_dz_f64(mpcg_handle* h, uint32_t control_size, const double* d_Ginv_dense, const double* d_C_dense,

@@ -45,6 +45,12 @@ struct SchurArgsT {
     int k0_only;              // reserved, always 0 (no kernel reads it; it stays so that the kernel arguments keep their offsets)
 };
 typedef SchurArgsT<float> SchurArgs;
+// The per-trajectory form (mpcg_form_schur_rhov): trajectory b is formed with rho_v[b]; `rho` of the base is not read.  The scalar kernels take
+// the base, so their arguments keep their offsets.
+template <typename T>
+struct SchurArgsVT : SchurArgsT<T> { const T* rho_v; };
+template <typename T> __device__ __forceinline__ T rho_of(const SchurArgsT<T>& a, int) { return a.rho; }
+template <typename T> __device__ __forceinline__ T rho_of(const SchurArgsVT<T>& a, int b) { return a.rho_v[b]; }
 
 template <typename T>
 struct DzArgsT { const T* Ginv; const T* C; const T* g; const T* lambda; T* dz; int n; int m; int N; int batch; };
@@ -198,8 +204,9 @@ __host__ __device__ constexpr size_t form_lds_elems(int n, int m) {
 __host__ __device__ constexpr size_t complete_lds_elems(int n) { return (size_t)6 * n * n; }
 
 // block row k of trajectory b: S[k,0], S[k,1], S[k-1,2], Pinv[k,1], gamma[k]; inverses -> staging buffer (linsys_setup.cuh:139-562)
-template <typename T>
-__global__ __launch_bounds__(256) void form_schur_kernel(SchurArgsT<T> a) {
+// A: SchurArgsT<T> (one rho per call) or SchurArgsVT<T> (one per trajectory) — the same body, rho read through rho_of
+template <typename T, typename A = SchurArgsT<T>>
+__global__ __launch_bounds__(256) void form_schur_kernel(A a) {
     extern __shared__ __align__(16) unsigned char gen_smem[];
     T* sm = reinterpret_cast<T*>(gen_smem);
     const int n = a.n, m = a.m, N = a.N;
@@ -222,12 +229,13 @@ __global__ __launch_bounds__(256) void form_schur_kernel(SchurArgsT<T> a) {
         T* P = a.Pinv + (size_t)b * 3 * nn * N;
         T* gamma = a.gamma + (size_t)b * n * N;
         T* Gs = a.Ginv_scratch + (size_t)b * Gsz;
+        const T rho = rho_of(a, b);
         __syncthreads();
         if (k == 0) {
             g_copy(nn, G, Qk);
             g_copy(n, g, qk);
             __syncthreads();
-            for (int i = tid; i < n; i += nt) Qk[i + i * n] += a.rho;
+            for (int i = tid; i < n; i += nt) Qk[i + i * n] += rho;
             __syncthreads();
             if (a.pinv) g_copy(nn, Qk, P + nn, (T)-1);                   // Pinv[0,1] = -(Q0 + rho I)
             __syncthreads();
@@ -247,8 +255,8 @@ __global__ __launch_bounds__(256) void form_schur_kernel(SchurArgsT<T> a) {
         g_copy(m, g + (size_t)(k - 1) * gset + n, rk);
         g_copy(n, g + (size_t)k * gset, qp);
         __syncthreads();
-        for (int i = tid; i < n; i += nt) { Qk[i + i * n] += a.rho; Qp[i + i * n] += a.rho; }
-        for (int i = tid; i < m; i += nt) Rk[i + i * m] += a.rho;
+        for (int i = tid; i < n; i += nt) { Qk[i + i * n] += rho; Qp[i + i * n] += rho; }
+        for (int i = tid; i < m; i += nt) Rk[i + i * m] += rho;
         __syncthreads();
         g_invert3(ln, lm, n, Qk, Qki, Qp, Qpi, m, Rk, Rki, scr);
         g_gemm<false>(ln, n, n, n, Ak, Qki, phi);                        // phi = Abar Qi

@@ -435,13 +435,19 @@ struct WalkArgs {
     int L;                  // block rows per chunk
     int chunks;             // ceil((N - 1) / L) >= 1
 };
+// mpcg_form_schur_rhov: one rho per trajectory.  The scalar kernel takes the base, so its arguments keep their offsets.
+struct WalkArgsV : WalkArgs { const float* rho_v; };     // [batch]
 
 // One 16-lane row = one chunk: block rows k0 = 1 + j L ... k1 - 1 of trajectory b; chunk 0 also emits block row 0 (linsys_setup.cuh:152-277),
 // which needs nothing but Q_0.  Four chunks per wavefront, in lock-step.  (Host: every array below 2^31 bytes.)
+// WA = WalkArgs: s.rho for every trajectory.  WA = WalkArgsV: the item's trajectory b — one per 16-lane row — reads rho_v[b] once per item,
+// through a buffer resource like every other operand (dead rows redo item `items - 1`: a valid index); the additions are the same.
 #ifndef SW_WAVES
 #define SW_WAVES 2         // launch bound: wavefronts per SIMD the register allocation aims at
 #endif
-__global__ __launch_bounds__(64, SW_WAVES) void schur_walk_kernel(WalkArgs w) {
+template <class WA = WalkArgs>
+__global__ __launch_bounds__(64, SW_WAVES) void schur_walk_kernel(WA w) {
+    constexpr bool RHOV = std::is_same<WA, WalkArgsV>::value;
     constexpr int n = 14, m = 7;
     constexpr uint32_t nn = n * n, mm = m * m, nm = n * m;
     constexpr uint32_t Gset = nn + mm, Cset = nn + nm, gset = n + m;
@@ -470,6 +476,9 @@ __global__ __launch_bounds__(64, SW_WAVES) void schur_walk_kernel(WalkArgs w) {
         // byte offsets of trajectory b
         const uint32_t oG = b * Gsz * 4u, oC = b * Csz * 4u, og = b * gsz * 4u, oc = b * (uint32_t)(n * N) * 4u, oS = b * (3u * nn * (uint32_t)N) * 4u;
         const bool st14 = live && r14;
+        float rho;
+        if constexpr (RHOV) rho = bld(make_rsrc(w.rho_v, (size_t)B * 4), b * 4u);
+        else rho = a.rho;
 
         // ---- prologue: (Q_{k0-1} + rho I)^-1; for chunk 0 that is block row 0 ----
         f2 Qi[np(n)];          // carried: (Q_{k-1} + rho I)^-1
@@ -477,7 +486,7 @@ __global__ __launch_bounds__(64, SW_WAVES) void schur_walk_kernel(WalkArgs w) {
         {
             f2 Qa[np(n)];
             load_rows<n>(Qa, rG, oG + (uint32_t)(k0 - 1) * Gset * 4u, n, lr);
-            add_rho<n>(Qa, lr, a.rho);
+            add_rho<n>(Qa, lr, rho);
 #pragma unroll
             for (int q = 0; q < np(n); ++q) Tm[q] = Qa[q];
             const bool first = j == 0;
@@ -535,8 +544,8 @@ __global__ __launch_bounds__(64, SW_WAVES) void schur_walk_kernel(WalkArgs w) {
             const int lr_s = lane_s & 15;
             lds_f* slot = stage + (lane_s >> 4) * SW_SLOT;
 #endif
-            add_rho<n>(Qp, lr, a.rho);
-            add_rho<m>(Rk, lr, a.rho);
+            add_rho<n>(Qp, lr, rho);
+            add_rho<m>(Rk, lr, rho);
             f2 Qpi[np(n)], Rki[np(m)];
             SW_FENCE();
 #if SW_PAIR

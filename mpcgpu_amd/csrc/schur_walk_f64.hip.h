@@ -165,10 +165,15 @@ struct WalkArgs64 {
     int L;                  // block rows per chunk
     int chunks;             // ceil((N - 1) / L) >= 1
 };
+// mpcg_form_schur_rhov_f64: one rho per trajectory (as sw::WalkArgsV)
+struct WalkArgs64V : WalkArgs64 { const double* rho_v; };     // [batch]
 
 // One 16-lane row = one chunk: block rows k0 = 1 + j L ... k1 - 1 of trajectory b; chunk 0 also emits block row 0.  Four chunks per
 // wavefront, in lock-step.  (Host: every array below 2^31 bytes.)
-__global__ __launch_bounds__(64, 1) void schur_walk_f64_kernel(WalkArgs64 w) {
+// WA = WalkArgs64: s.rho for every trajectory; WA = WalkArgs64V: rho_v[b] of the item's trajectory, read once per item.
+template <class WA = WalkArgs64>
+__global__ __launch_bounds__(64, 1) void schur_walk_f64_kernel(WA w) {
+    constexpr bool RHOV = std::is_same<WA, WalkArgs64V>::value;
     constexpr int n = 14, m = 7;
     constexpr uint32_t nn = n * n, mm = m * m, nm = n * m, E = 8;
     constexpr uint32_t Gset = nn + mm, Cset = nn + nm, gset = n + m;
@@ -194,6 +199,9 @@ __global__ __launch_bounds__(64, 1) void schur_walk_f64_kernel(WalkArgs64 w) {
         const int k1 = (k0 + L < N) ? k0 + L : N;
         const uint32_t oG = b * Gsz * E, oC = b * Csz * E, og = b * gsz * E, oc = b * (uint32_t)(n * N) * E, oS = b * (3u * nn * (uint32_t)N) * E;
         const bool st14 = live && r14;
+        double rho;
+        if constexpr (RHOV) rho = bld(make_rsrc(w.rho_v, (size_t)B * E), b * E);
+        else rho = a.rho;
 
         // ---- prologue: (Q_{k0-1} + rho I)^-1; for chunk 0 that is block row 0 (linsys_setup.cuh:152-277) ----
         double Qi[n];          // carried: (Q_{k-1} + rho I)^-1
@@ -201,7 +209,7 @@ __global__ __launch_bounds__(64, 1) void schur_walk_f64_kernel(WalkArgs64 w) {
         {
             double Qa[n];
             load_rows<n>(Qa, rG, oG + (uint32_t)(k0 - 1) * Gset * E, n, lr);
-            add_rho<n>(Qa, lr, a.rho);
+            add_rho<n>(Qa, lr, rho);
 #pragma unroll
             for (int q = 0; q < n; ++q) Tm[q] = Qa[q];
             const bool first = j == 0;
@@ -240,8 +248,8 @@ __global__ __launch_bounds__(64, 1) void schur_walk_f64_kernel(WalkArgs64 w) {
             const bool on14 = st14 && rowl;
             const bool on7 = live && r7 && rowl;
             const uint32_t oGk = oG + (k - 1) * Gset * E, oSk = oS + k * 3u * nn * E;
-            add_rho<n>(Qp, lr, a.rho);
-            add_rho<m>(Rk, lr, a.rho);
+            add_rho<n>(Qp, lr, rho);
+            add_rho<m>(Rk, lr, rho);
             double Qpi[n], Rki[m];
             SW64_FENCE();
             invert<n>(Qp, Qpi, lr);                                                               // :356-368
@@ -304,6 +312,10 @@ __global__ __launch_bounds__(64, 1) void schur_walk_f64_kernel(WalkArgs64 w) {
             have_tm = true;
             // next row's A / B only now: requested any earlier they would be live across the symmetric-stair products, the register peak of a row
             // (130 doubles); the two inversions at the head of the next row hide their latency
+            // rho_v[b] again for the next row (a cached 8-byte load) rather than a double carried across the row's register peak: with it carried the
+            // kernel needs 4 registers more than its scalar twin, reloaded 22 fewer.  Requested AHEAD of A / B, so that the next row's wait for it
+            // leaves their loads in flight.
+            if constexpr (RHOV) rho = bld(make_rsrc(w.rho_v, (size_t)B * E), b * E);
             load_AB(kn);
         }
     }

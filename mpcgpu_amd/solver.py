@@ -272,10 +272,12 @@ class PcgSolver:
         self._check(self.lib.mpcg_block_solve(self._h, _ptr(S), _ptr(gamma), _ptr(lam), B, _stream()))
         return lam
 
-    def form_schur(self, G_dense, C_dense, g, c, rho: float, precond: str = "ss", S=None, Pinv=None, gamma=None,
+    def form_schur(self, G_dense, C_dense, g, c, rho, precond: str = "ss", S=None, Pinv=None, gamma=None,
                    control_size: int | None = None):
         """form_schur_system (include/pcg/linsys_setup.cuh:620-656), batched.  G_dense is overwritten by
-        its block inverses (the reference's side effect).  Returns (S, Pinv, gamma) device tensors."""
+        its block inverses (the reference's side effect).  Returns (S, Pinv, gamma) device tensors.
+        rho: a Python float (one value for the call), or a device tensor [B] of the operands' dtype — one value per trajectory, read
+        when the kernels run (mpcg_form_schur_rhov; what line_search_step_rho adapts)."""
         B = c.shape[0] if c.dim() > 1 else 1
         n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
         dt = c.dtype                                           # float32, or float64 = linsys_t double (mpcg_form_schur_f64)
@@ -293,8 +295,14 @@ class PcgSolver:
         self._chk(Pinv, B * 3 * n * n * N, dt, "Pinv")
         self._chk(gamma, B * n * N, dt, "gamma")
         pc = {"ss": _lib.MPCG_PRECOND_SS, "jacobi": _lib.MPCG_PRECOND_JACOBI, "none": _lib.MPCG_PRECOND_NONE}[precond]
-        fn = self.lib.mpcg_form_schur if dt == torch.float32 else self.lib.mpcg_form_schur_f64
-        self._check(fn(self._h, m, _ptr(G_dense), _ptr(C_dense), _ptr(g), _ptr(c), _ptr(S), _ptr(Pinv), _ptr(gamma), float(rho), B, pc, _stream()))
+        if isinstance(rho, torch.Tensor):
+            self._chk(rho, B, dt, "rho")
+            fn = self.lib.mpcg_form_schur_rhov if dt == torch.float32 else self.lib.mpcg_form_schur_rhov_f64
+            rho_arg = _ptr(rho)
+        else:
+            fn = self.lib.mpcg_form_schur if dt == torch.float32 else self.lib.mpcg_form_schur_f64
+            rho_arg = float(rho)
+        self._check(fn(self._h, m, _ptr(G_dense), _ptr(C_dense), _ptr(g), _ptr(c), _ptr(S), _ptr(Pinv), _ptr(gamma), rho_arg, B, pc, _stream()))
         return S, Pinv, gamma
 
     def generate_kkt(self, plant: "Plant", eePos_traj, xs, xu, timestep: float, qd_cost: float, r_cost: float,
@@ -374,6 +382,29 @@ class PcgSolver:
             step = torch.empty(B, dtype=torch.int32, device=xu.device)
         self._chk(step, B, torch.int32, "step")
         self._check(self.lib.mpcg_line_search_step(self._h, m, _ptr(merit), arr, A, _ptr(merit_ref), _ptr(dz), _ptr(xu), _ptr(step), B, _stream()))
+        return step
+
+    def line_search_step_rho(self, merit, step_sizes, merit_ref, dz, xu, rho, drho, done, rho_factor: float = 1.2, rho_min: float = 1e-3,
+                             rho_max: float = 10.0, rho_reset: float = 1e-3, step=None, control_size: int | None = None):
+        """line_search_step followed by the rho adaptation of include/pcg/sqp.cuh:304-320 with device state per trajectory: rho, drho (float32
+        [B]) and done (uint8 [B]) are updated in place; a trajectory with done != 0 is frozen (step = MPCG_STEP_FROZEN, nothing else written).
+        `rho` is the tensor form_schur takes: nothing is read back inside an SQP loop."""
+        B = merit_ref.numel()
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        arr, A = self._steps(step_sizes)
+        self._chk(merit, B * A, torch.float32, "merit")
+        self._chk(merit_ref, B, torch.float32, "merit_ref")
+        self._chk(dz, B * ((n + m) * N - m), torch.float32, "dz")
+        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
+        self._chk(rho, B, torch.float32, "rho")
+        self._chk(drho, B, torch.float32, "drho")
+        self._chk(done, B, torch.uint8, "done")
+        if step is None:
+            step = torch.empty(B, dtype=torch.int32, device=xu.device)
+        self._chk(step, B, torch.int32, "step")
+        self._check(self.lib.mpcg_line_search_step_rho(self._h, m, _ptr(merit), arr, A, _ptr(merit_ref), _ptr(dz), _ptr(xu), _ptr(step),
+                                                       _ptr(rho), _ptr(drho), _ptr(done), float(rho_factor), float(rho_min), float(rho_max),
+                                                       float(rho_reset), B, _stream()))
         return step
 
     def csr_nnz(self) -> int:

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Time the steps either side of the solve at any (state_size, control_size):  time_producers.py [--state n] [--control m] [--knots N] [--batch B]
-[--generic] [--json] — mpcg_form_schur (symmetric stair), mpcg_compute_dz and mpcg_block_solve, each with its rate on the shape's own
+[--generic] [--rho-vector] [--json] — mpcg_form_schur (symmetric stair), mpcg_compute_dz and mpcg_block_solve, each with its rate on the shape's own
 algorithmic HBM bytes (formation: G, C, g, c in, S, Pinv, gamma, G^-1 out; dz: G^-1, C, g, lambda in, dz out; block solve: S, gamma in,
 lambda out).  At 14 x 7 the default (register-resident) kernels are timed and, with --generic, the run-time-dimension LDS kernels of
 schur_generic.hip.h ("producers_generic" = 1) every other shape runs anyway (for formation and dz also what "schur_dpp" = "dz_dpp" = 0 runs).
-Every figure is the median of seven timed calls behind 50 ms of back-to-back calls."""
+Every figure is the median of seven timed calls behind 50 ms of back-to-back calls.
+--rho-vector times the formation alone, float and double: mpcg_form_schur(_f64) with a scalar rho against mpcg_form_schur_rhov(_f64) with a device
+vector of the same value, ALTERNATED call by call in one process behind a common warm-up — median and min-max of seven calls each."""
 import argparse, json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,6 +22,7 @@ ap.add_argument("--control", type=int, default=7)
 ap.add_argument("--knots", type=int, default=128)
 ap.add_argument("--batch", type=int, default=1024)
 ap.add_argument("--generic", action="store_true", help="14 x 7 only: also time the run-time-dimension kernels")
+ap.add_argument("--rho-vector", action="store_true", help="formation only: the scalar entry against the rho-vector entry, alternated, float and double")
 ap.add_argument("--hbm-tbs", type=float, default=8.0, help="HBM bandwidth the achieved fraction refers to (TB/s)")
 ap.add_argument("--json", action="store_true")
 a = ap.parse_args()
@@ -61,6 +64,37 @@ def t(fn, restore=False, reps=9):
         e0.record(); fn(); e1.record(); torch.cuda.synchronize(); ts.append(e0.elapsed_time(e1))
     return float(np.median(ts[2:])) * 1e3            # us
 
+
+def rho_vector_ab():
+    for dt in (torch.float32, torch.float64):
+        Gd, Cd, gd, cd = (x.to(dt) for x in (G0, C, g, c))
+        G0d = Gd.clone()
+        Sd = torch.zeros(B, 3 * n * n * N, device="cuda", dtype=dt); Pd = torch.zeros_like(Sd); gmd = torch.empty(B, n * N, device="cuda", dtype=dt)
+        vec = torch.full((B,), 1e-3, device="cuda", dtype=dt)
+        calls = {"scalar": lambda: sol.form_schur(Gd, Cd, gd, cd, 1e-3, "ss", S=Sd, Pinv=Pd, gamma=gmd),
+                 "vector": lambda: sol.form_schur(Gd, Cd, gd, cd, vec, "ss", S=Sd, Pinv=Pd, gamma=gmd)}
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < 0.1:            # common warm-up, both entries
+            for fn in calls.values():
+                fn()
+            torch.cuda.synchronize()
+        ts = {k: [] for k in calls}
+        for _ in range(7):
+            for k, fn in calls.items():
+                Gd.copy_(G0d)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); fn(); e1.record(); torch.cuda.synchronize(); ts[k].append(e0.elapsed_time(e1) * 1e3)
+        for k, v in ts.items():
+            rec = {"state": n, "control": m, "knots": N, "batch": B, "dtype": str(dt).split(".")[1], "rho": k, "step": "form_schur", "chunk": sol.get_option("last_schur_chunk"),
+                   "median_us": round(float(np.median(v)), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2)}
+            print(json.dumps(rec) if a.json else "(%2d,%2d) %4d x %-4d %-8s rho %-7s form_schur  median %9.1f us  (min %.1f, max %.1f)"
+                  % (n, m, B, N, rec["dtype"], k, rec["median_us"], rec["min_us"], rec["max_us"]))
+
+
+if a.rho_vector:
+    rho_vector_ab()
+    sys.exit(0)
 
 nn, mm, nm = n * n, m * m, n * m
 model = {"form_schur": 4 * (9 * nn + 2 * mm + nm + 3 * n + m), "compute_dz": 4 * (2 * nn + mm + nm + 3 * n + 2 * m), "block_solve": 4 * (3 * nn + 2 * n)}
