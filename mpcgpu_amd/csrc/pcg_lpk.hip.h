@@ -285,6 +285,188 @@ __device__ __forceinline__ float lpk_wave_fold(float part) {
     return ((part + r1) + r2) + r3;
 }
 
+// ---- lane helpers of the two lane-pair kernels (pcg_lpk_kernel, pcg_lpkc_kernel).  Float indices inside a vector, K2 = floats between consecutive
+// row pairs: register slots 0..2 -> pairs 4h + s: bA + K2 s | slot 3 -> pair 3: b0 + 3 K2   (slots 4..6 = the partner lane's pairs: by DPP, never
+// from LDS);  knot k - 1: subtract 2; knot k + 1: add 2
+struct LpkOwn { f2 v[4]; };
+struct LpkVec { LpkOwn k, m; };                                // a lane's copy of a vector: its own row pairs of knot k and of knot k-1
+struct LpkFetch { f2 t[4], z[4], gt[4], gz[4]; };
+// own entries (register slots 0..3) of knot k + dk of the vector at float offset X
+template <int K2>
+__device__ __forceinline__ LpkOwn lpk_load_own(const float* lds, int bA, int b0, int X, int dk) {
+    const float* x = lds + X + 2 * dk;
+    LpkOwn o;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) o.v[s] = *reinterpret_cast<const f2*>(x + bA + K2 * s);
+    o.v[3] = *reinterpret_cast<const f2*>(x + b0 + 3 * K2);
+    return o;
+}
+template <int K2>
+__device__ __forceinline__ void lpk_store_own(float* lds, int bA, int b0, int X, const LpkOwn& o) {
+    float* x = lds + X;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) *reinterpret_cast<f2*>(x + bA + K2 * s) = o.v[s];
+    *reinterpret_cast<f2*>(x + b0 + 3 * K2) = o.v[3];
+}
+// The operand loads of a half-iteration, requested as soon as the barrier in front of it is passed — BEFORE the scalar of the update
+// (alpha / beta: LDS read of the partials, three adds, a 13-instruction IEEE division, the exit test) is worked out: that chain is
+// ~300 cycles of dependent latency and the loads do not depend on it.  Own row pairs (register slots 0..3) of knot k and of knot k-1
+// of the two published vectors the operand is formed from: 16 volatile ds_read_b64.
+template <int K2>
+__device__ __forceinline__ LpkFetch lpk_fetch(const float* lds, int bA, int b0, int T, int Z) {
+    const float* xt = lds + T;
+    const float* xz = lds + Z + 2;
+    LpkFetch f;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) { f.t[s] = lds_ld64(xt + bA + K2 * s); f.z[s] = lds_ld64(xz + bA + K2 * s); }
+    f.t[3] = lds_ld64(xt + b0 + 3 * K2); f.z[3] = lds_ld64(xz + b0 + 3 * K2);
+#pragma unroll
+    for (int s = 0; s < 3; ++s) { f.gt[s] = lds_ld64(xt - 2 + bA + K2 * s); f.gz[s] = lds_ld64(xz - 2 + bA + K2 * s); }
+    f.gt[3] = lds_ld64(xt - 2 + b0 + 3 * K2); f.gz[3] = lds_ld64(xz - 2 + b0 + 3 * K2);
+    return f;
+}
+
+// One half-iteration of a wave's matrix, shared by the two lane-pair kernels.  `old` = the lane's register copy of the vector being updated (r or p).
+//   MODE 0: the operand is `old` as it stands (setup product S lambda0);
+//   MODE 1: operand = old - c (T + Z<<1)          (Pinv half: r_new, c = alpha; setup: c = 1)
+//   MODE 2: operand = (T + Z<<1) + c old          (S half: p_new, c = beta; first iteration: c = 0)
+// (block-Jacobi: the Pinv waves never write ZP, it stays zero.)  The lane forms its OWN row pairs of the operand for knot k and for
+// knot k-1, takes the other three pairs of knot k from the partner lane's registers (DPP) and runs the pass.  What the two kernels do
+// differently with the three results of a pass they do themselves:
+//   on_z(z2, z6)    z = L_k^T x_k, this lane's columns (three pairs + column 6 + h): to knot k-1's slot of the z vector   (clustered: the first own knot's also to the left member)
+//   on_rows(o)      the merged own row pairs: to knot k's slot of the T vector                                            (clustered: the last own knot's also to the right member)
+//   on_part(part)   the wavefront's share of x^T M x, the same in every lane                                              (red[wl], or a granule)
+// (single-CU: every lane stores — a lane beyond the horizon holds all-zero blocks, its products and its z are exact zeros and its knot slots
+//  exist, NMAX + 4 of them: three exec-mask branches less per half-iteration; a cluster member: only the lanes of own knots, its right halo
+//  slot must stay untouched.)  Returns the operand (= the updated vector) for the next half.
+// PB >= 0: the -DMPCG_PROF build stamps PB + 1 (operand in place), PB + 2 (transposed product done), PB + 3 (direct products done) — the single-CU
+// kernel's interior stamps; the clustered kernel passes -1 (its own PB + 1, PB + 2 mean something else, tools/_prof/lpkc_phases.py).  That
+// build alone hands MPCG_STAMP's names over as trailing arguments.
+#ifdef MPCG_PROF
+#define LPK_PROF_PARAMS , bool prof_on, int lane, int w
+#define LPK_PROF_ARGS , prof_on, lane, w
+#else
+#define LPK_PROF_PARAMS
+#define LPK_PROF_ARGS
+#endif
+template <int MODE, class L, int NTHR, int PB, class OnZ, class OnRows, class OnPart>
+__device__ __forceinline__ LpkVec lpk_half(const f2 (&Md)[7][7], const f2 (&Ml)[7][7], const f2* park, int h, bool hasL, const LpkFetch& f, const LpkVec& old, float c,
+                                           OnZ&& on_z, OnRows&& on_rows, OnPart&& on_part LPK_PROF_PARAMS) {
+    f2 xk[7];
+    LpkOwn om;                                               // knot k-1, own entries
+    if constexpr (MODE == 0) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { xk[s] = old.k.v[s]; om.v[s] = old.m.v[s]; }
+    } else {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { const f2 u = f.t[s] + f.z[s]; xk[s] = MODE == 1 ? old.k.v[s] - c * u : u + c * old.k.v[s]; }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { const f2 u = f.gt[s] + f.gz[s]; om.v[s] = MODE == 1 ? old.m.v[s] - c * u : u + c * old.m.v[s]; }
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) xk[4 + s] = f2{dpp_partner(xk[s].x), dpp_partner(xk[s].y)};
+    LpkOwn me;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) me.v[s] = xk[s];
+    if constexpr (PB >= 0) MPCG_STAMP(PB + 1);
+    f2 acc[7];
+    float cterm = 0.f;
+    const float xk6 = h ? xk[3].y : xk[3].x;
+#if defined(MPCG_ABLATE_LPK) && (MPCG_ABLATE_LPK & 1)     // (timing experiments only, tools/lpk_ablate.sh: results are wrong with any bit set)
+    if (false) {
+#else
+    if (hasL) {
+#endif
+        // transposed: z[j] = sum over row pairs of L[pair][column j] (.) x_k[pair]; four + three independent chains (register budget)
+        f2 z2[3];
+        float z6;
+        {
+            f2 t[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = Ml[0][j] * xk[0];
+#pragma unroll
+            for (int s = 1; s < 7; ++s)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) t[j] = __builtin_elementwise_fma(Ml[s][j], xk[s], t[j]);
+            z2[0] = f2{t[0].x + t[0].y, t[1].x + t[1].y};
+            z2[1] = f2{t[2].x + t[2].y, t[3].x + t[3].y};
+        }
+        {
+            f2 t[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) t[j] = Ml[0][4 + j] * xk[0];
+#pragma unroll
+            for (int s = 1; s < 7; ++s)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) t[j] = __builtin_elementwise_fma(Ml[s][4 + j], xk[s], t[j]);
+            z2[2] = f2{t[0].x + t[0].y, t[1].x + t[1].y};
+            z6 = t[2].x + t[2].y;
+        }
+        const float xm6 = h ? om.v[3].y : om.v[3].x;        // x_{k-1} at this lane's seventh column (entry 6 + h)
+        on_z(z2, z6);
+        // second copy of the coupling term of the inner product: x_{k-1}^T (L_k^T x_k), own columns
+        f2 ct = z2[0] * om.v[0];
+        ct = __builtin_elementwise_fma(z2[1], om.v[1], ct);
+        ct = __builtin_elementwise_fma(z2[2], om.v[2], ct);
+        cterm = fmaf(z6, xm6, ct.x + ct.y);
+        if constexpr (PB >= 0) MPCG_STAMP(PB + 2);
+        // direct, off-diagonal columns: acc = L[:, c_j] x_{k-1}[c_j]
+#pragma unroll
+        for (int s = 0; s < 7; ++s) acc[s] = Ml[s][0] * f2{om.v[0].x, om.v[0].x};
+#pragma unroll
+        for (int j = 1; j < 6; ++j) {
+            const float xs = (j & 1) ? om.v[j >> 1].y : om.v[j >> 1].x;
+#pragma unroll
+            for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Ml[s][j], f2{xs, xs}, acc[s]);
+        }
+#pragma unroll
+        for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Ml[s][6], f2{xm6, xm6}, acc[s]);
+#pragma unroll
+        for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Md[s][0], f2{xk[0].x, xk[0].x}, acc[s]);
+    } else {
+#pragma unroll
+        for (int s = 0; s < 7; ++s) acc[s] = Md[s][0] * f2{xk[0].x, xk[0].x};
+    }
+    // (the parked pairs — rows 4..6 of the diagonal block's seventh column — are requested here, volatile = in program order, and consumed by
+    //  the last FMAs of the pass)
+    f2 pk_[L::NPARK];
+#pragma unroll
+    for (int i = 0; i < L::NPARK; ++i) pk_[i] = lds_ld64(reinterpret_cast<const float*>(park + i * NTHR));
+    // direct, diagonal columns
+#if !(defined(MPCG_ABLATE_LPK) && (MPCG_ABLATE_LPK & 2))
+#pragma unroll
+    for (int j = 1; j < 6; ++j) {
+        const float xs = (j & 1) ? xk[j >> 1].y : xk[j >> 1].x;
+#pragma unroll
+        for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Md[s][j], f2{xs, xs}, acc[s]);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) acc[s] = __builtin_elementwise_fma(Md[s][6], f2{xk6, xk6}, acc[s]);
+#pragma unroll
+    for (int i = 0; i < L::NPARK; ++i) acc[4 + i] = __builtin_elementwise_fma(pk_[i], f2{xk6, xk6}, acc[4 + i]);
+#endif
+    if constexpr (PB >= 0) MPCG_STAMP(PB + 3);
+    // merge the two column halves: own slot s + the partner's slot (4, 5, 6, 3)[s]
+    LpkOwn o;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const f2 oth = acc[s < 3 ? s + 4 : 3];
+        o.v[s] = f2{acc[s].x + dpp_partner(oth.x), acc[s].y + dpp_partner(oth.y)};
+    }
+    on_rows(o);
+    // inner product share: x_k . (D x_k + L x_{k-1}) over this lane's OWN rows (lane 1's slot 3 duplicates lane 0's: weight 0) + the coupling copy
+    f2 d0 = o.v[0] * me.v[0], d1 = o.v[1] * me.v[1];
+    d0 = __builtin_elementwise_fma(o.v[2], me.v[2], d0);
+    const f2 d3 = o.v[3] * me.v[3];
+    const f2 dd = d0 + d1;
+#if defined(MPCG_ABLATE_LPK) && (MPCG_ABLATE_LPK & 4)
+    on_part(((dd.x + dd.y) + (h ? 0.f : d3.x + d3.y)) + cterm);
+#else
+    on_part(lpk_wave_fold(((dd.x + dd.y) + (h ? 0.f : d3.x + d3.y)) + cterm));
+#endif
+    return LpkVec{me, om};
+}
+
 template <int NWR>
 __global__ __launch_bounds__(NWR ? NWR * 256 : 128, 2) void pcg_lpk_kernel(PcgArgs a) {
     typedef LpkLds<NWR> L;
@@ -363,9 +545,6 @@ __global__ __launch_bounds__(NWR ? NWR * 256 : 128, 2) void pcg_lpk_kernel(PcgAr
 #ifdef MPCG_PROF
     bool prof_on = false;
 #endif
-    // (a lambda of this kernel's own in front of lpk_wave_fold: `half` below captures it, and without that capture the compiler numbers this
-    //  kernel's registers differently — same instructions, another allocation; kept so that this kernel stays the code that was measured)
-    auto wave_fold = [&](float part) -> float { return lpk_wave_fold(part); };
     // sum of the NW/2 wave partials of one inner product (the waves of one matrix), same order in every thread: deterministic
     auto sum_red = [&](const float* red) -> float {
         if constexpr (NW == 8) {
@@ -378,174 +557,31 @@ __global__ __launch_bounds__(NWR ? NWR * 256 : 128, 2) void pcg_lpk_kernel(PcgAr
             return red[0];
         }
     };
-    struct Own { f2 v[4]; };
-    // own entries (register slots 0..3) of knot k + dk of the vector at float offset X
-    auto load_own = [&](int X, int dk) -> Own {
-        const float* x = lds + X + 2 * dk;
-        Own o;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) o.v[s] = *reinterpret_cast<const f2*>(x + bA + K2 * s);
-        o.v[3] = *reinterpret_cast<const f2*>(x + b0 + 3 * K2);
-        return o;
-    };
-    // (no `k < N` predicate: a lane beyond the horizon holds all-zero blocks — its products, its z and its copies of the vectors are exact
-    //  zeros, and its knot slots exist (NMAX + 4 of them) — so it may write them; three exec-mask branches less per half-iteration)
-    auto store_own = [&](int X, const Own& o) {
-        float* x = lds + X;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) *reinterpret_cast<f2*>(x + bA + K2 * s) = o.v[s];
-        *reinterpret_cast<f2*>(x + b0 + 3 * K2) = o.v[3];
-    };
-
-    // The operand loads of a half-iteration, requested as soon as the barrier in front of it is passed — BEFORE the scalar of the update
-    // (alpha / beta: LDS read of the partials, three adds, a 13-instruction IEEE division, the exit test) is worked out: that chain is
-    // ~300 cycles of dependent latency and the loads do not depend on it.  Own row pairs (register slots 0..3) of knot k and of knot k-1
-    // of the two published vectors the operand is formed from: 16 volatile ds_read_b64.
-    struct Fetch { f2 t[4], z[4], gt[4], gz[4]; };
-    auto fetch = [&](int T, int Z) -> Fetch {
-        const float* xt = lds + T;
-        const float* xz = lds + Z + 2;
-        Fetch f;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) { f.t[s] = lds_ld64(xt + bA + K2 * s); f.z[s] = lds_ld64(xz + bA + K2 * s); }
-        f.t[3] = lds_ld64(xt + b0 + 3 * K2); f.z[3] = lds_ld64(xz + b0 + 3 * K2);
-#pragma unroll
-        for (int s = 0; s < 3; ++s) { f.gt[s] = lds_ld64(xt - 2 + bA + K2 * s); f.gz[s] = lds_ld64(xz - 2 + bA + K2 * s); }
-        f.gt[3] = lds_ld64(xt - 2 + b0 + 3 * K2); f.gz[3] = lds_ld64(xz - 2 + b0 + 3 * K2);
-        return f;
-    };
-    struct Vec { Own k, m; };                                  // a lane's copy of a vector: its own row pairs of knot k and of knot k-1
-
-    // One half-iteration of this wave's matrix.  `old` = the lane's register copy of the vector being updated (r or p).
-    //   MODE 0: the operand is `old` as it stands (setup product S lambda0);
-    //   MODE 1: operand = old - c (T + Z<<1)          (Pinv half: r_new, c = alpha; setup: c = 1)
-    //   MODE 2: operand = (T + Z<<1) + c old          (S half: p_new, c = beta; first iteration: c = 0)
-    // (block-Jacobi: the Pinv waves never write ZP, it stays zero.)  The lane forms its OWN row pairs of the operand for knot k and for
-    // knot k-1, takes the other three pairs of knot k from the partner lane's registers (DPP), runs the pass, publishes the merged own
-    // row pairs to TOUT and z to ZOUT, the wave's share of x^T M x to red[wl].  Returns the operand (= the updated vector) for the next half.
-    auto half = [&](auto mode_tag, const Fetch& f, const Vec& old, float c, int TOUT, int ZOUT, float* red, int pb) -> Vec {
-        constexpr int MODE = decltype(mode_tag)::value;
+    typedef LpkOwn Own;
+    typedef LpkFetch Fetch;
+    typedef LpkVec Vec;
+    auto load_own = [&](int X, int dk) -> Own { return lpk_load_own<K2>(lds, bA, b0, X, dk); };
+    auto store_own = [&](int X, const Own& o) { lpk_store_own<K2>(lds, bA, b0, X, o); };
+    auto fetch = [&](int T, int Z) -> Fetch { return lpk_fetch<K2>(lds, bA, b0, T, Z); };
+    // One half-iteration of this wave's matrix (lpk_half): every lane stores its z to ZOUT and its merged rows to TOUT, the wave's share of
+    // x^T M x goes to red[wl].  pb: stamp numbers of the -DMPCG_PROF build.
+    auto half = [&](auto mode_tag, const Fetch& f, const Vec& old, float c, int TOUT, int ZOUT, float* red, auto pb_tag) -> Vec {
+        [[maybe_unused]] constexpr int pb = decltype(pb_tag)::value;
         MPCG_STAMP(pb + 0);
-        f2 xk[7];
-        Own om;                                                  // knot k-1, own entries
-        if constexpr (MODE == 0) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { xk[s] = old.k.v[s]; om.v[s] = old.m.v[s]; }
-        } else {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { const f2 u = f.t[s] + f.z[s]; xk[s] = MODE == 1 ? old.k.v[s] - c * u : u + c * old.k.v[s]; }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { const f2 u = f.gt[s] + f.gz[s]; om.v[s] = MODE == 1 ? old.m.v[s] - c * u : u + c * old.m.v[s]; }
-        }
-#pragma unroll
-        for (int s = 0; s < 3; ++s) xk[4 + s] = f2{dpp_partner(xk[s].x), dpp_partner(xk[s].y)};
-        Own me;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) me.v[s] = xk[s];
-        MPCG_STAMP(pb + 1);
-        f2 acc[7];
-        float cterm = 0.f;
-        const float xk6 = h ? xk[3].y : xk[3].x;
-#if defined(MPCG_ABLATE_LPK) && (MPCG_ABLATE_LPK & 1)     // (timing experiments only, tools/lpk_ablate.sh: results are wrong with any bit set)
-        if (false) {
-#else
-        if (hasL) {
-#endif
-            // transposed: z[j] = sum over row pairs of L[pair][column j] (.) x_k[pair]; four + three independent chains (register budget)
-            f2 z2[3];
-            float z6;
-            {
-                f2 t[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) t[j] = Ml[0][j] * xk[0];
-#pragma unroll
-                for (int s = 1; s < 7; ++s)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) t[j] = __builtin_elementwise_fma(Ml[s][j], xk[s], t[j]);
-                z2[0] = f2{t[0].x + t[0].y, t[1].x + t[1].y};
-                z2[1] = f2{t[2].x + t[2].y, t[3].x + t[3].y};
-            }
-            {
-                f2 t[3];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) t[j] = Ml[0][4 + j] * xk[0];
-#pragma unroll
-                for (int s = 1; s < 7; ++s)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) t[j] = __builtin_elementwise_fma(Ml[s][4 + j], xk[s], t[j]);
-                z2[2] = f2{t[0].x + t[0].y, t[1].x + t[1].y};
-                z6 = t[2].x + t[2].y;
-            }
-            const float xm6 = h ? om.v[3].y : om.v[3].x;        // x_{k-1} at this lane's seventh column (entry 6 + h)
-            {                                                    // z belongs to knot k-1's vector: entries of this lane's columns
+        const Vec x = lpk_half<decltype(mode_tag)::value, L, NTHR, pb>(Md, Ml, park, h, hasL, f, old, c,
+            [&](const f2 (&z2)[3], float z6) {                   // z belongs to knot k-1's vector: entries of this lane's columns
                 float* zo = lds + ZOUT;
 #pragma unroll
                 for (int s = 0; s < 3; ++s) *reinterpret_cast<f2*>(zo + bA + K2 * s) = z2[s];
                 zo[b0 + 3 * K2 + h] = z6;
-            }
-            // second copy of the coupling term of the inner product: x_{k-1}^T (L_k^T x_k), own columns
-            f2 ct = z2[0] * om.v[0];
-            ct = __builtin_elementwise_fma(z2[1], om.v[1], ct);
-            ct = __builtin_elementwise_fma(z2[2], om.v[2], ct);
-            cterm = fmaf(z6, xm6, ct.x + ct.y);
-            MPCG_STAMP(pb + 2);
-            // direct, off-diagonal columns: acc = L[:, c_j] x_{k-1}[c_j]
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = Ml[s][0] * f2{om.v[0].x, om.v[0].x};
-#pragma unroll
-            for (int j = 1; j < 6; ++j) {
-                const float xs = (j & 1) ? om.v[j >> 1].y : om.v[j >> 1].x;
-#pragma unroll
-                for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Ml[s][j], f2{xs, xs}, acc[s]);
-            }
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Ml[s][6], f2{xm6, xm6}, acc[s]);
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Md[s][0], f2{xk[0].x, xk[0].x}, acc[s]);
-        } else {
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = Md[s][0] * f2{xk[0].x, xk[0].x};
-        }
-        // (the parked pairs are requested here, volatile = in program order, and consumed by the last FMAs of the pass)
-        f2 pk_[L::NPARK];
-#pragma unroll
-        for (int i = 0; i < L::NPARK; ++i) pk_[i] = lds_ld64(reinterpret_cast<const float*>(park + i * NTHR));
-        // direct, diagonal columns
-#if !(defined(MPCG_ABLATE_LPK) && (MPCG_ABLATE_LPK & 2))
-#pragma unroll
-        for (int j = 1; j < 6; ++j) {
-            const float xs = (j & 1) ? xk[j >> 1].y : xk[j >> 1].x;
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Md[s][j], f2{xs, xs}, acc[s]);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc[s] = __builtin_elementwise_fma(Md[s][6], f2{xk6, xk6}, acc[s]);
-#pragma unroll
-        for (int i = 0; i < L::NPARK; ++i) acc[4 + i] = __builtin_elementwise_fma(pk_[i], f2{xk6, xk6}, acc[4 + i]);
-#endif
-        MPCG_STAMP(pb + 3);
-        // merge the two column halves: own slot s + the partner's slot (4, 5, 6, 3)[s]
-        Own o;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const f2 oth = acc[s < 3 ? s + 4 : 3];
-            o.v[s] = f2{acc[s].x + dpp_partner(oth.x), acc[s].y + dpp_partner(oth.y)};
-        }
-        store_own(TOUT, o);
-        // inner product share: x_k . (D x_k + L x_{k-1}) over this lane's OWN rows (lane 1's slot 3 duplicates lane 0's: weight 0) + the coupling copy
-        f2 d0 = o.v[0] * me.v[0], d1 = o.v[1] * me.v[1];
-        d0 = __builtin_elementwise_fma(o.v[2], me.v[2], d0);
-        const f2 d3 = o.v[3] * me.v[3];
-        const f2 dd = d0 + d1;
-#if defined(MPCG_ABLATE_LPK) && (MPCG_ABLATE_LPK & 4)
-        const float part = ((dd.x + dd.y) + (h ? 0.f : d3.x + d3.y)) + cterm;
-#else
-        const float part = wave_fold(((dd.x + dd.y) + (h ? 0.f : d3.x + d3.y)) + cterm);
-#endif
-        if (lane == 0) red[wl] = part;
+            },
+            [&](const Own& o) { store_own(TOUT, o); },
+            [&](float part) { if (lane == 0) red[wl] = part; } LPK_PROF_ARGS);
         MPCG_STAMP(pb + 4);
-        return Vec{me, om};
+        return x;
     };
+    using Pb0 = std::integral_constant<int, 0>;
+    using Pb8 = std::integral_constant<int, 8>;
 
     // The S waves and the Pinv waves run the same barrier sequence through two SEPARATE code paths (the role is wave-uniform).
     uint32_t iters = 0;
@@ -559,11 +595,11 @@ __global__ __launch_bounds__(NWR ? NWR * 256 : 128, 2) void pcg_lpk_kernel(PcgAr
         Vec x;                                                   // S waves: p;  Pinv waves: r
         x.k = load_own(P ? L::R0 : L::P0, 0);
         x.m = load_own(P ? L::R0 : L::P0, -1);
-        if constexpr (!P) (void)half(std::integral_constant<int, 0>{}, f, x, 0.f, L::US, L::ZS, red_v, 0);
+        if constexpr (!P) (void)half(std::integral_constant<int, 0>{}, f, x, 0.f, L::US, L::ZS, red_v, Pb0{});
         lds_barrier();
         if constexpr (P) {
             f = fetch(L::US, L::ZS);
-            x = half(std::integral_constant<int, 1>{}, f, x, 1.f, L::RT, L::ZP, red_e, 8);
+            x = half(std::integral_constant<int, 1>{}, f, x, 1.f, L::RT, L::ZP, red_e, Pb8{});
         }
         lds_barrier();
         if constexpr (!P) f = fetch(L::RT, L::ZP);
@@ -579,7 +615,7 @@ __global__ __launch_bounds__(NWR ? NWR * 256 : 128, 2) void pcg_lpk_kernel(PcgAr
 #endif
                 if constexpr (!P) {
                     // p = r~ + beta p ; upsilon = S p ; v = p . upsilon
-                    x = half(std::integral_constant<int, 2>{}, f, x, beta, L::US, L::ZS, red_v, 0);
+                    x = half(std::integral_constant<int, 2>{}, f, x, beta, L::US, L::ZS, red_v, Pb0{});
                     MPCG_STAMP(5);
                     lds_barrier();
                     MPCG_STAMP(6);
@@ -601,7 +637,7 @@ __global__ __launch_bounds__(NWR ? NWR * 256 : 128, 2) void pcg_lpk_kernel(PcgAr
                     // alpha = eta / v ; r -= alpha upsilon ; r~ = Pinv r ; eta' = r . r~
                     f = fetch(L::US, L::ZS);
                     const float alpha = uniform(eta / sum_red(red_v));
-                    x = half(std::integral_constant<int, 1>{}, f, x, alpha, L::RT, L::ZP, red_e, 8);
+                    x = half(std::integral_constant<int, 1>{}, f, x, alpha, L::RT, L::ZP, red_e, Pb8{});
                     MPCG_STAMP(14);
                     lds_barrier();
                     MPCG_STAMP(15);

@@ -96,37 +96,14 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
     unsigned epoch = 0, seq = 0;
     bool failed = false;
 
-    struct Own { f2 v[4]; };
-    auto load_own = [&](int X, int dk) -> Own {
-        const float* x = lds + X + 2 * dk;
-        Own o;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) o.v[s] = *reinterpret_cast<const f2*>(x + bA + K2 * s);
-        o.v[3] = *reinterpret_cast<const f2*>(x + b0 + 3 * K2);
-        return o;
-    };
+    typedef LpkOwn Own;
+    typedef LpkFetch Fetch;
+    typedef LpkVec Vec;
+    auto load_own = [&](int X, int dk) -> Own { return lpk_load_own<K2>(lds, bA, b0, X, dk); };
     auto store_own = [&](int X, const Own& o) {
-        if (valid) {
-            float* x = lds + X;
-#pragma unroll
-            for (int s = 0; s < 3; ++s) *reinterpret_cast<f2*>(x + bA + K2 * s) = o.v[s];
-            *reinterpret_cast<f2*>(x + b0 + 3 * K2) = o.v[3];
-        }
+        if (valid) lpk_store_own<K2>(lds, bA, b0, X, o);      // (slot KL + 1 is the right halo: lanes beyond the member's knots must not write)
     };
-    struct Fetch { f2 t[4], z[4], gt[4], gz[4]; };
-    auto fetch = [&](int T, int Z) -> Fetch {
-        const float* xt = lds + T;
-        const float* xz = lds + Z + 2;
-        Fetch f;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) { f.t[s] = lds_ld64(xt + bA + K2 * s); f.z[s] = lds_ld64(xz + bA + K2 * s); }
-        f.t[3] = lds_ld64(xt + b0 + 3 * K2); f.z[3] = lds_ld64(xz + b0 + 3 * K2);
-#pragma unroll
-        for (int s = 0; s < 3; ++s) { f.gt[s] = lds_ld64(xt - 2 + bA + K2 * s); f.gz[s] = lds_ld64(xz - 2 + bA + K2 * s); }
-        f.gt[3] = lds_ld64(xt - 2 + b0 + 3 * K2); f.gz[3] = lds_ld64(xz - 2 + b0 + 3 * K2);
-        return f;
-    };
-    struct Vec { Own k, m; };
+    auto fetch = [&](int T, int Z) -> Fetch { return lpk_fetch<K2>(lds, bA, b0, T, Z); };
     // 14 values of a knot's lane pair as 16-byte granules of the group at word WORD: this lane's slots 0..2 -> two granules (entries
     // 0..5 / 8..13), lane 0 one more: {slot 3 (entries 6, 7), 0}.  Called by both lanes of the knot.
     auto publish_pair = [&](auto word_tag, unsigned ep, f2 s0, f2 s1, f2 s2, f2 s3) {
@@ -145,125 +122,42 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
         }
     };
 
-    // One half-iteration of this wave's matrix (pcg_lpk_kernel::half) + the publishing of what the neighbours and the reduction need.
+    // One half-iteration of this wave's matrix (lpk_half) + the publishing of what the neighbours and the reduction need.
     auto half = [&](auto mode_tag, auto slot, const Fetch& f, const Vec& old, float c, int TOUT, int ZOUT) -> Vec {
-        constexpr int MODE = decltype(mode_tag)::value;
         constexpr int base = decltype(slot)::value;
         [[maybe_unused]] constexpr int pb = base == LPKC_SLOT_V ? 0 : 8;     // (stamp numbers of the -DMPCG_PROF build)
         MPCG_STAMP(pb + 0);
         const unsigned ep = epoch + 1;                      // tag of the hand-off that follows this pass
-        f2 xk[7];
-        Own om;
-        if constexpr (MODE == 0) {
+        const Vec x = lpk_half<decltype(mode_tag)::value, L, NTHR, -1>(Md, Ml, park, h, hasL, f, old, c,
+            [&](const f2 (&z2)[3], float z6) {
+                if (valid) {
+                    float* zo = lds + ZOUT;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) { xk[s] = old.k.v[s]; om.v[s] = old.m.v[s]; }
-        } else {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { const f2 u = f.t[s] + f.z[s]; xk[s] = MODE == 1 ? old.k.v[s] - c * u : u + c * old.k.v[s]; }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { const f2 u = f.gt[s] + f.gz[s]; om.v[s] = MODE == 1 ? old.m.v[s] - c * u : u + c * old.m.v[s]; }
-        }
-#pragma unroll
-        for (int s = 0; s < 3; ++s) xk[4 + s] = f2{dpp_partner(xk[s].x), dpp_partner(xk[s].y)};
-        Own me;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) me.v[s] = xk[s];
-        f2 acc[7];
-        float cterm = 0.f;
-        const float xk6 = h ? xk[3].y : xk[3].x;
-        if (hasL) {
-            f2 z2[3];
-            float z6;
-            {
-                f2 t[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) t[j] = Ml[0][j] * xk[0];
-#pragma unroll
-                for (int s = 1; s < 7; ++s)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) t[j] = __builtin_elementwise_fma(Ml[s][j], xk[s], t[j]);
-                z2[0] = f2{t[0].x + t[0].y, t[1].x + t[1].y};
-                z2[1] = f2{t[2].x + t[2].y, t[3].x + t[3].y};
-            }
-            {
-                f2 t[3];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) t[j] = Ml[0][4 + j] * xk[0];
-#pragma unroll
-                for (int s = 1; s < 7; ++s)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) t[j] = __builtin_elementwise_fma(Ml[s][4 + j], xk[s], t[j]);
-                z2[2] = f2{t[0].x + t[0].y, t[1].x + t[1].y};
-                z6 = t[2].x + t[2].y;
-            }
-            const float xm6 = h ? om.v[3].y : om.v[3].x;
-            if (valid) {
-                float* zo = lds + ZOUT;
-#pragma unroll
-                for (int s = 0; s < 3; ++s) *reinterpret_cast<f2*>(zo + bA + K2 * s) = z2[s];
-                // (slot 3, entry h: b0 + 3 K2 + h, formed from bA on the spot — as a lane constant of its own it was the one VGPR the kernel
-                //  spilled: a scratch reload + wait in front of this store in every pass)
-                //  (h = lane & 1, re-read from the hardware lane count so that nothing of it lives across the pass.)
-                int ln6;
-                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln6));
-                zo[bA + ((ln6 & 1) ? 1 - K2 : 3 * K2)] = z6;
-            }
-            // z of the first own knot is the LEFT member's missing part: published now, half a pass before the hand-off
-            if (valid && i == 0 && g > 0) publish_pair(std::integral_constant<int, base + LPKC_W_Z>{}, ep, z2[0], z2[1], z2[2], f2{z6, dpp_partner(z6)});
-            f2 ct = z2[0] * om.v[0];
-            ct = __builtin_elementwise_fma(z2[1], om.v[1], ct);
-            ct = __builtin_elementwise_fma(z2[2], om.v[2], ct);
-            cterm = fmaf(z6, xm6, ct.x + ct.y);
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = Ml[s][0] * f2{om.v[0].x, om.v[0].x};
-#pragma unroll
-            for (int j = 1; j < 6; ++j) {
-                const float xs = (j & 1) ? om.v[j >> 1].y : om.v[j >> 1].x;
-#pragma unroll
-                for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Ml[s][j], f2{xs, xs}, acc[s]);
-            }
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Ml[s][6], f2{xm6, xm6}, acc[s]);
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Md[s][0], f2{xk[0].x, xk[0].x}, acc[s]);
-        } else {
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = Md[s][0] * f2{xk[0].x, xk[0].x};
-        }
-        f2 pk_[L::NPARK];
-#pragma unroll
-        for (int q = 0; q < L::NPARK; ++q) pk_[q] = lds_ld64(reinterpret_cast<const float*>(park + q * NTHR));
-#pragma unroll
-        for (int j = 1; j < 6; ++j) {
-            const float xs = (j & 1) ? xk[j >> 1].y : xk[j >> 1].x;
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = __builtin_elementwise_fma(Md[s][j], f2{xs, xs}, acc[s]);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc[s] = __builtin_elementwise_fma(Md[s][6], f2{xk6, xk6}, acc[s]);
-#pragma unroll
-        for (int q = 0; q < L::NPARK; ++q) acc[4 + q] = __builtin_elementwise_fma(pk_[q], f2{xk6, xk6}, acc[4 + q]);
-        Own o;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const f2 oth = acc[s < 3 ? s + 4 : 3];
-            o.v[s] = f2{acc[s].x + dpp_partner(oth.x), acc[s].y + dpp_partner(oth.y)};
-        }
-        store_own(TOUT, o);
-        // the merged rows of the last own knot are the RIGHT member's T[k0 - 1]
-        if (valid && i == KL - 1 && g < G - 1) publish_pair(std::integral_constant<int, base + LPKC_W_T>{}, ep, o.v[0], o.v[1], o.v[2], o.v[3]);
-        f2 d0 = o.v[0] * me.v[0], d1 = o.v[1] * me.v[1];
-        d0 = __builtin_elementwise_fma(o.v[2], me.v[2], d0);
-        const f2 d3 = o.v[3] * me.v[3];
-        const f2 dd = d0 + d1;
-        const float part = lpk_wave_fold(((dd.x + dd.y) + (h ? 0.f : d3.x + d3.y)) + cterm);
-        if (lane == 0) {
-            const unsigned long long gran = granule_of(__builtin_bit_cast(unsigned, part), ep);
-            if (same_xcd) granule_store_l2<base>(my_words, 8u * (unsigned)wl, gran);
-            else granule_store<base>(my_words, 8u * (unsigned)wl, gran);
-        }
+                    for (int s = 0; s < 3; ++s) *reinterpret_cast<f2*>(zo + bA + K2 * s) = z2[s];
+                    // (slot 3, entry h: b0 + 3 K2 + h, formed from bA on the spot — as a lane constant of its own it was the one VGPR the kernel
+                    //  spilled: a scratch reload + wait in front of this store in every pass)
+                    //  (h = lane & 1, re-read from the hardware lane count so that nothing of it lives across the pass.)
+                    int ln6;
+                    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln6));
+                    zo[bA + ((ln6 & 1) ? 1 - K2 : 3 * K2)] = z6;
+                }
+                // z of the first own knot is the LEFT member's missing part: published now, half a pass before the hand-off
+                if (valid && i == 0 && g > 0) publish_pair(std::integral_constant<int, base + LPKC_W_Z>{}, ep, z2[0], z2[1], z2[2], f2{z6, dpp_partner(z6)});
+            },
+            [&](const Own& o) {
+                store_own(TOUT, o);
+                // the merged rows of the last own knot are the RIGHT member's T[k0 - 1]
+                if (valid && i == KL - 1 && g < G - 1) publish_pair(std::integral_constant<int, base + LPKC_W_T>{}, ep, o.v[0], o.v[1], o.v[2], o.v[3]);
+            },
+            [&](float part) {
+                if (lane == 0) {
+                    const unsigned long long gran = granule_of(__builtin_bit_cast(unsigned, part), ep);
+                    if (same_xcd) granule_store_l2<base>(my_words, 8u * (unsigned)wl, gran);
+                    else granule_store<base>(my_words, 8u * (unsigned)wl, gran);
+                }
+            } LPK_PROF_ARGS);
         MPCG_STAMP(pb + 1);
-        return Vec{me, om};
+        return x;
     };
 
     using SlotV = std::integral_constant<int, LPKC_SLOT_V>;

@@ -29,16 +29,12 @@ constexpr int LQKC_MAX_G = 8;                       // G x 4 wave partials polle
 #define LQKC_NPARK 10     // (the hand-off state — epoch, cell addresses, tables — takes the registers the single-CU kernel still had: more of D_k waits in LDS)
 #endif
 // LDS (doubles): the lane-quad kernel's seven pair-major vectors | broadcast cell (4) | hand-off tables (3 x 64 ints) | parked matrix values
-template <int NWR> struct LqkcLds {
-    typedef LqkLds<NWR> B;
-    static constexpr int NMAX = B::NMAX, NW = B::NW, KN = B::KN, VS = B::VS;
-    static constexpr int P0 = 0, R0 = VS, US = 2 * VS, ZS = 3 * VS, RT = 4 * VS, ZP = 5 * VS, LAM = 6 * VS, BC = 7 * VS, TAB = BC + 4, MX = TAB + 3 * 32,
-                         NPARK = LQKC_NPARK, TOTAL = MX + NPARK * NW * 64;
-    // parked matrix values: the LAST NPARK entries of D_k in the order the pass consumes them (column-major: entry 7 j + s)
-    __host__ __device__ static constexpr bool parked(int s, int j) { return 7 * j + s >= 49 - NPARK; }
-    __host__ __device__ static constexpr int pidx(int s, int j) { return 7 * j + s - (49 - NPARK); }
+template <int NWR> struct LqkcLds : LqkLds<NWR, LQKC_NPARK> {
+    typedef LqkLds<NWR, LQKC_NPARK> B;                 // (its parking rule, parked / pidx, with this kernel's NPARK)
+    static constexpr int NW = B::NW, VS = B::VS, NPARK = B::NPARK;
+    static constexpr int BC = 7 * VS, TAB = BC + 4, MX = TAB + 3 * 32, TOTAL = MX + NPARK * NW * 64;
     // double index of entry i of knot slot s inside a vector
-    __host__ __device__ static constexpr int at(int s, int i) { return 2 * ((i >> 1) * KN + s) + (i & 1); }
+    __host__ __device__ static constexpr int at(int s, int i) { return 2 * ((i >> 1) * B::KN + s) + (i & 1); }
 };
 __host__ __device__ constexpr size_t pcg_lqkc_lds_doubles() { return (size_t)LqkcLds<2>::TOTAL; }
 
@@ -88,43 +84,14 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
     unsigned epoch = 0, seq = 0;
     bool failed = false;
 
-    struct Own { real v[4]; };
-    auto load_own = [&](int X, int dk) -> Own {
-        const real* x = lds + X + 2 * dk;
-        Own o;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) o.v[s] = x[bA + K2 * s];
-        o.v[3] = x[b0 + 3 * K2];
-        return o;
-    };
+    typedef LqkOwn Own;
+    typedef LqkFetch Fetch;
+    typedef LqkVec Vec;
+    auto load_own = [&](int X, int dk) -> Own { return lqk_load_own<K2>(lds, bA, b0, X, dk); };
     auto store_own = [&](int X, const Own& o) {
-        if (valid) {                                           // (slot KL + 1 is the right halo: lanes beyond the member's knots must not write)
-            real* x = lds + X;
-#pragma unroll
-            for (int s = 0; s < 3; ++s) x[bA + K2 * s] = o.v[s];
-            x[b0 + 3 * K2] = o.v[3];
-        }
+        if (valid) lqk_store_own<K2>(lds, bA, b0, X, o);      // (slot KL + 1 is the right halo: lanes beyond the member's knots must not write)
     };
-    struct Fetch { real t[4], z[4], gt[4], gz[4]; };
-    auto fetch = [&](int T, int Z) -> Fetch {
-        const real* xt = lds + T;
-        const real* xz = lds + Z + 2;
-        Fetch f;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) { f.t[s] = lqk_ld(xt + bA + K2 * s); f.z[s] = lqk_ld(xz + bA + K2 * s); }
-        f.t[3] = lqk_ld(xt + b0 + 3 * K2); f.z[3] = lqk_ld(xz + b0 + 3 * K2);
-#pragma unroll
-        for (int s = 0; s < 3; ++s) { f.gt[s] = lqk_ld(xt - 2 + bA + K2 * s); f.gz[s] = lqk_ld(xz - 2 + bA + K2 * s); }
-        f.gt[3] = lqk_ld(xt - 2 + b0 + 3 * K2); f.gz[3] = lqk_ld(xz - 2 + b0 + 3 * K2);
-        return f;
-    };
-    struct Vec { Own k, m; };
-    auto col = [&](const real (&v)[4], auto jt) -> real {
-        constexpr int J = decltype(jt)::value;
-        if constexpr (J == 6) return lqk_quad<LQK_QP_B6>(v[3]);
-        else if constexpr ((J & 1) == 0) return lqk_quad<LQK_QP_B0>(v[J >> 1]);
-        else return lqk_quad<LQK_QP_B1>(v[J >> 1]);
-    };
+    auto fetch = [&](int T, int Z) -> Fetch { return lqk_fetch<K2>(lds, bA, b0, T, Z); };
     // 14 entries of a knot held by its quad -> the 14 granules of the group at word WORD: this lane's v0..v2 are entries 8h + 2s + g, `v3` is
     // entry e3 of the lanes for which pub3 holds (T: own slot 3 = entry 6 + g, lanes h = 0; Z: column 6 = entry 6 + h, lanes g = h)
     auto publish_quad = [&](auto word_tag, auto isz_tag, unsigned ep, real v0, real v1, real v2, real v3) {
@@ -152,121 +119,33 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
         }
     };
 
-    // One half-iteration of this wave's matrix (pcg_lqk_f64_kernel::half) + the publishing of what the neighbours and the reduction need.
+    // One half-iteration of this wave's matrix (lqk_half) + the publishing of what the neighbours and the reduction need.
     auto half = [&](auto mode_tag, auto slot, const Fetch& f, const Vec& old, real c, int TOUT, int ZOUT) -> Vec {
-        constexpr int MODE = decltype(mode_tag)::value;
         constexpr int base = decltype(slot)::value;
         const unsigned ep = epoch + 1;                      // tag of the hand-off that follows this pass
-        real xk[7];
-        Own om;
-        if constexpr (MODE == 0) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { xk[s] = old.k.v[s]; om.v[s] = old.m.v[s]; }
-        } else {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { const real u = f.t[s] + f.z[s]; xk[s] = MODE == 1 ? old.k.v[s] - c * u : u + c * old.k.v[s]; }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { const real u = f.gt[s] + f.gz[s]; om.v[s] = MODE == 1 ? old.m.v[s] - c * u : u + c * old.m.v[s]; }
-        }
-#pragma unroll
-        for (int s = 0; s < 3; ++s) xk[4 + s] = lqk_quad<LQK_QP_H>(xk[s]);
-        Own me;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) me.v[s] = xk[s];
-        real acc[7];
-        real cterm = real(0);
-        const real xk6 = col(me.v, std::integral_constant<int, 6>{});
-        if (hasL) {
-            real z[7];
-            {
-                real t[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) t[j] = Ml[0][j] * xk[0];
-#pragma unroll
-                for (int s = 1; s < 7; ++s)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) t[j] = fma(Ml[s][j], xk[s], t[j]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) z[j] = t[j] + lqk_quad<LQK_QP_G>(t[j]);
-            }
-            {
-                real t[3];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) t[j] = Ml[0][4 + j] * xk[0];
-#pragma unroll
-                for (int s = 1; s < 7; ++s)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) t[j] = fma(Ml[s][4 + j], xk[s], t[j]);
-#pragma unroll
-                for (int j = 0; j < 3; ++j) z[4 + j] = t[j] + lqk_quad<LQK_QP_G>(t[j]);
-            }
-            const real zg0 = g ? z[1] : z[0], zg1 = g ? z[3] : z[2], zg2 = g ? z[5] : z[4];     // this lane's columns of parity g
-            if (valid) {
-                real* zo = lds + ZOUT;
-                zo[bA] = zg0; zo[bA + K2] = zg1; zo[bA + 2 * K2] = zg2;
-                if (g == h) zo[b0 + 3 * K2] = z[6];
-            }
-            // z of the first own knot is the LEFT member's missing part: published now, half a pass before the hand-off
-            if (valid && i == 0 && gm > 0) publish_quad(std::integral_constant<int, base + LQKC_W_Z>{}, std::true_type{}, ep, zg0, zg1, zg2, z[6]);
-            real ct = zg0 * om.v[0];
-            ct = fma(zg1, om.v[1], ct);
-            ct = fma(zg2, om.v[2], ct);
-            cterm = g == h ? fma(z[6], om.v[3], ct) : ct;
-            {
-                const real x0 = col(om.v, std::integral_constant<int, 0>{});
-#pragma unroll
-                for (int s = 0; s < 7; ++s) acc[s] = Ml[s][0] * x0;
-            }
-            SFor14<8>::run([&](auto jt) {                       // j = 1 .. 6
-                constexpr int J = decltype(jt)::value - 7;
-                const real xs = col(om.v, std::integral_constant<int, J>{});
-#pragma unroll
-                for (int s = 0; s < 7; ++s) acc[s] = fma(Ml[s][J], xs, acc[s]);
+        return lqk_half<decltype(mode_tag)::value, L, NTHR>(Md, Ml, park, h, g, hasL, f, old, c,
+            [&](const real (&z)[7]) {
+                const real zg0 = g ? z[1] : z[0], zg1 = g ? z[3] : z[2], zg2 = g ? z[5] : z[4];     // this lane's columns of parity g
+                if (valid) {
+                    real* zo = lds + ZOUT;
+                    zo[bA] = zg0; zo[bA + K2] = zg1; zo[bA + 2 * K2] = zg2;
+                    if (g == h) zo[b0 + 3 * K2] = z[6];
+                }
+                // z of the first own knot is the LEFT member's missing part: published now, half a pass before the hand-off
+                if (valid && i == 0 && gm > 0) publish_quad(std::integral_constant<int, base + LQKC_W_Z>{}, std::true_type{}, ep, zg0, zg1, zg2, z[6]);
+            },
+            [&](const Own& o) {
+                store_own(TOUT, o);
+                // the merged rows of the last own knot are the RIGHT member's T[k0 - 1]
+                if (valid && i == KL - 1 && gm < G - 1) publish_quad(std::integral_constant<int, base + LQKC_W_T>{}, std::false_type{}, ep, o.v[0], o.v[1], o.v[2], o.v[3]);
+            },
+            [&](real part) {
+                if (lane == 0) {
+                    const f4 gr = granule_of(part, ep);
+                    if (same_xcd) granule_store16<base, true>(my_words, 16u * (unsigned)wl, gr);
+                    else granule_store16<base, false>(my_words, 16u * (unsigned)wl, gr);
+                }
             });
-            {
-                const real x0 = col(me.v, std::integral_constant<int, 0>{});
-#pragma unroll
-                for (int s = 0; s < 7; ++s) acc[s] = fma(Md[s][0], x0, acc[s]);
-            }
-        } else {
-            const real x0 = col(me.v, std::integral_constant<int, 0>{});
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = Md[s][0] * x0;
-        }
-        real pk_[L::NPARK];
-#pragma unroll
-        for (int q = 0; q < L::NPARK; ++q) pk_[q] = lqk_ld(park + q * NTHR);
-        SFor14<9>::run([&](auto jt) {                           // j = 1 .. 5
-            constexpr int J = decltype(jt)::value - 8;
-            const real xs = col(me.v, std::integral_constant<int, J>{});
-            SFor14<7>::run([&](auto st) {
-                constexpr int S = decltype(st)::value - 7;
-                if constexpr (L::parked(S, J)) acc[S] = fma(pk_[L::pidx(S, J)], xs, acc[S]);
-                else acc[S] = fma(Md[S][J], xs, acc[S]);
-            });
-        });
-        SFor14<7>::run([&](auto st) {
-            constexpr int S = decltype(st)::value - 7;
-            if constexpr (L::parked(S, 6)) acc[S] = fma(pk_[L::pidx(S, 6)], xk6, acc[S]);
-            else acc[S] = fma(Md[S][6], xk6, acc[S]);
-        });
-        Own o;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) o.v[s] = acc[s] + lqk_quad<LQK_QP_H>(acc[s < 3 ? s + 4 : 3]);
-        store_own(TOUT, o);
-        // the merged rows of the last own knot are the RIGHT member's T[k0 - 1]
-        if (valid && i == KL - 1 && gm < G - 1) publish_quad(std::integral_constant<int, base + LQKC_W_T>{}, std::false_type{}, ep, o.v[0], o.v[1], o.v[2], o.v[3]);
-        real d0 = o.v[0] * me.v[0];
-        d0 = fma(o.v[1], me.v[1], d0);
-        d0 = fma(o.v[2], me.v[2], d0);
-        const real d3 = o.v[3] * me.v[3];
-        const real part = rpl_wave_fold((d0 + (h ? real(0) : d3)) + cterm);
-        if (lane == 0) {
-            const f4 gr = granule_of(part, ep);
-            if (same_xcd) granule_store16<base, true>(my_words, 16u * (unsigned)wl, gr);
-            else granule_store16<base, false>(my_words, 16u * (unsigned)wl, gr);
-        }
-        return Vec{me, om};
     };
 
     using SlotV = std::integral_constant<int, LQKC_SLOT_V>;
@@ -369,8 +248,7 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
             lqk_load_blocks(M, k0 + i_st, h_st, g_st, valid, valid && k0 + i_st > 0 && hasL, Md, Ml);
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0)
-#pragma unroll
-        for (int q = 0; q < L::NPARK; ++q) park[q * NTHR] = Md[(49 - L::NPARK + q) % 7][(49 - L::NPARK + q) / 7];
+        lqk_park<L, NTHR>(park, Md);
         // ---- stage: everything <- 0, then P0 <- lambda0, lambda <- lambda0, R0 <- gamma for the own knots AND the replica knot k0 - 1 ----
         for (int e = tid; e < L::BC; e += NTHR) lds[e] = real(0);
         lds_barrier();

@@ -30,15 +30,18 @@ namespace mpcg {
 // consecutive knots read 16 consecutive doubles = 32 banks, the h = 1 lanes read row pair q + 4 = 8 KN doubles further = 16 KN banks:
 // KN = 2 (mod 4) puts them on the other 32 banks.
 #ifndef LQK_NPARK
-#define LQK_NPARK 5      // matrix values per lane parked in LDS (the last column of D_k, rows 7 - NPARK .. 6 of the lane's slots): no scratch
+#define LQK_NPARK 5      // matrix values per lane parked in LDS (LqkLds::parked: the end of the last column of D_k): no scratch
 #endif
-template <int NWR> struct LqkLds {
+template <int NWR, int NPARK_ = LQK_NPARK> struct LqkLds {
     static constexpr int NMAX = 32 * NWR, NW = 4 * NWR;
     static constexpr int KN = NMAX + 2;
     static_assert(KN % 4 == 2, "row pairs q and q + 4 must sit 32 banks apart");
     static constexpr int VS = 7 * KN * 2;                      // doubles per vector
-    static constexpr int P0 = 0, R0 = VS, US = 2 * VS, ZS = 3 * VS, RT = 4 * VS, ZP = 5 * VS, LAM = 6 * VS, RED = 7 * VS, MX = RED + NW, NPARK = LQK_NPARK,
+    static constexpr int P0 = 0, R0 = VS, US = 2 * VS, ZS = 3 * VS, RT = 4 * VS, ZP = 5 * VS, LAM = 6 * VS, RED = 7 * VS, MX = RED + NW, NPARK = NPARK_,
                          TOTAL = MX + NPARK * NW * 64;
+    // parked matrix values: the LAST NPARK entries of D_k in the order the pass consumes them (column-major: entry 7 j + s); NPARK = 5: Md[2..6][6]
+    __host__ __device__ static constexpr bool parked(int s, int j) { return 7 * j + s >= 49 - NPARK; }
+    __host__ __device__ static constexpr int pidx(int s, int j) { return 7 * j + s - (49 - NPARK); }
     __host__ __device__ static constexpr int at(int k, int i) { return 2 * ((i >> 1) * KN + k + 1) + (i & 1); }
 };
 __host__ __device__ constexpr size_t pcg_lqk_lds_doubles(int NW) { return NW == 4 ? (size_t)LqkLds<1>::TOTAL : (size_t)LqkLds<2>::TOTAL; }
@@ -97,6 +100,174 @@ __device__ __forceinline__ void lqk_load_blocks(rsrc_t M, int k, int h, int g, b
     }
 }
 
+// ---- lane helpers of the two lane-quad kernels (pcg_lqk_f64_kernel, pcg_lqkc_f64_kernel).  Double indices inside a vector, K2 = doubles between
+// consecutive row pairs: register slots 0..2 -> pairs 4h + s, element g: bA + K2 s | slot 3 -> pair 3: b0 + 3 K2;  knot k - 1: subtract 2, knot k + 1: add 2
+struct LqkOwn { double v[4]; };
+struct LqkVec { LqkOwn k, m; };                                // a lane's copy of a vector: its own entries of knot k and of knot k-1
+struct LqkFetch { double t[4], z[4], gt[4], gz[4]; };
+// own entries (register slots 0..3, this lane's row of each pair) of knot k + dk of the vector at double offset X
+template <int K2>
+__device__ __forceinline__ LqkOwn lqk_load_own(const double* lds, int bA, int b0, int X, int dk) {
+    const double* x = lds + X + 2 * dk;
+    LqkOwn o;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) o.v[s] = x[bA + K2 * s];
+    o.v[3] = x[b0 + 3 * K2];
+    return o;
+}
+template <int K2>
+__device__ __forceinline__ void lqk_store_own(double* lds, int bA, int b0, int X, const LqkOwn& o) {
+    double* x = lds + X;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) x[bA + K2 * s] = o.v[s];
+    x[b0 + 3 * K2] = o.v[3];
+}
+// The operand loads of a half-iteration, requested as soon as the barrier in front of it is passed — before the scalar of the update is
+// worked out.  Own entries (slots 0..3) of knot k and of knot k-1 of the two published vectors the operand is formed from: 16 ds_read_b64.
+template <int K2>
+__device__ __forceinline__ LqkFetch lqk_fetch(const double* lds, int bA, int b0, int T, int Z) {
+    const double* xt = lds + T;
+    const double* xz = lds + Z + 2;
+    LqkFetch f;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) { f.t[s] = lqk_ld(xt + bA + K2 * s); f.z[s] = lqk_ld(xz + bA + K2 * s); }
+    f.t[3] = lqk_ld(xt + b0 + 3 * K2); f.z[3] = lqk_ld(xz + b0 + 3 * K2);
+#pragma unroll
+    for (int s = 0; s < 3; ++s) { f.gt[s] = lqk_ld(xt - 2 + bA + K2 * s); f.gz[s] = lqk_ld(xz - 2 + bA + K2 * s); }
+    f.gt[3] = lqk_ld(xt - 2 + b0 + 3 * K2); f.gz[3] = lqk_ld(xz - 2 + b0 + 3 * K2);
+    return f;
+}
+// entry of column J (of this lane's seven) of a vector whose own slots are v: slot J >> 1, element J & 1 — from the g lane that holds it
+template <int J>
+__device__ __forceinline__ double lqk_col(const double (&v)[4]) {
+    if constexpr (J == 6) return lqk_quad<LQK_QP_B6>(v[3]);                                       // entry 6 + h: pair 3, element h
+    else if constexpr ((J & 1) == 0) return lqk_quad<LQK_QP_B0>(v[J >> 1]);
+    else return lqk_quad<LQK_QP_B1>(v[J >> 1]);
+}
+// park the values the pass uses last (L::parked) in LDS, [value][thread]; lqk_half fetches them back inside the pass
+template <class L, int NTHR>
+__device__ __forceinline__ void lqk_park(double* park, const double (&Md)[7][7]) {
+#pragma unroll
+    for (int q = 0; q < L::NPARK; ++q) park[q * NTHR] = Md[(49 - L::NPARK + q) % 7][(49 - L::NPARK + q) / 7];
+}
+
+// One half-iteration of a wave's matrix, shared by the two lane-quad kernels.  `old` = the lane's register copy of the vector being updated.
+//   MODE 0: the operand is `old` as it stands (setup product S lambda0);
+//   MODE 1: operand = old - c (T + Z<<1)          (Pinv half: r_new, c = alpha; setup: c = 1)
+//   MODE 2: operand = (T + Z<<1) + c old          (S half: p_new, c = beta; first iteration: c = 0)
+// Everything the two kernels have in common; what they do differently with the three results of a pass they do themselves:
+//   on_z(z)         z = L_k^T x_k, this lane's seven columns: to knot k-1's slot of the z vector     (clustered: the first own knot's also to the left member)
+//   on_rows(o)      the merged own rows: to knot k's slot of the T vector                             (clustered: the last own knot's also to the right member)
+//   on_part(part)   the wavefront's share of x^T M x, the same in every lane                          (red[wl], or a granule)
+// (single-CU: every lane stores — a lane beyond the horizon holds all-zero blocks, its products and its z are exact zeros and its knot slots
+//  exist; a cluster member: only the lanes of own knots, its right halo slot must stay untouched.)
+// Returns the operand (= the updated vector) for the next half.
+template <int MODE, class L, int NTHR, class OnZ, class OnRows, class OnPart>
+__device__ __forceinline__ LqkVec lqk_half(const double (&Md)[7][7], const double (&Ml)[7][7], const double* park, int h, int g,
+                                           bool hasL, const LqkFetch& f, const LqkVec& old, double c, OnZ&& on_z, OnRows&& on_rows, OnPart&& on_part) {
+    typedef double real;
+    real xk[7];                                              // x_k at this lane's row of all seven pairs (slots 4..6: the h-partner's own)
+    LqkOwn om;                                               // knot k-1, own entries
+    if constexpr (MODE == 0) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { xk[s] = old.k.v[s]; om.v[s] = old.m.v[s]; }
+    } else {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { const real u = f.t[s] + f.z[s]; xk[s] = MODE == 1 ? old.k.v[s] - c * u : u + c * old.k.v[s]; }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) { const real u = f.gt[s] + f.gz[s]; om.v[s] = MODE == 1 ? old.m.v[s] - c * u : u + c * old.m.v[s]; }
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) xk[4 + s] = lqk_quad<LQK_QP_H>(xk[s]);
+    LqkOwn me;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) me.v[s] = xk[s];
+    real acc[7];
+    real cterm = real(0);
+    const real xk6 = lqk_col<6>(me.v);
+    if (hasL) {
+        // transposed: z[j] = sum over rows of L[row][column j] x_k[row]; this lane's seven rows, the other seven from the g-partner
+        real z[7];
+        {
+            real t[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = Ml[0][j] * xk[0];
+#pragma unroll
+            for (int s = 1; s < 7; ++s)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) t[j] = fma(Ml[s][j], xk[s], t[j]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z[j] = t[j] + lqk_quad<LQK_QP_G>(t[j]);
+        }
+        {
+            real t[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) t[j] = Ml[0][4 + j] * xk[0];
+#pragma unroll
+            for (int s = 1; s < 7; ++s)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) t[j] = fma(Ml[s][4 + j], xk[s], t[j]);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) z[4 + j] = t[j] + lqk_quad<LQK_QP_G>(t[j]);
+        }
+        // z belongs to knot k-1's vector: column j = (slot j >> 1, element j & 1) — this lane stores element g (+ entry 6 + h = pair 3, element h, in the lane g == h)
+        on_z(z);
+        // second copy of the coupling term of the inner product, x_{k-1}^T (L_k^T x_k): this lane's own columns of parity g (+ column 6 in the lane g == h)
+        real ct = (g ? z[1] : z[0]) * om.v[0];
+        ct = fma(g ? z[3] : z[2], om.v[1], ct);
+        ct = fma(g ? z[5] : z[4], om.v[2], ct);
+        cterm = g == h ? fma(z[6], om.v[3], ct) : ct;
+        // direct, off-diagonal columns: acc = L[:, c_j] x_{k-1}[c_j]
+        {
+            const real x0 = lqk_col<0>(om.v);
+#pragma unroll
+            for (int s = 0; s < 7; ++s) acc[s] = Ml[s][0] * x0;
+        }
+        SFor14<8>::run([&](auto jt) {                       // j = 1 .. 6
+            constexpr int J = decltype(jt)::value - 7;
+            const real xs = lqk_col<J>(om.v);
+#pragma unroll
+            for (int s = 0; s < 7; ++s) acc[s] = fma(Ml[s][J], xs, acc[s]);
+        });
+        {
+            const real x0 = lqk_col<0>(me.v);
+#pragma unroll
+            for (int s = 0; s < 7; ++s) acc[s] = fma(Md[s][0], x0, acc[s]);
+        }
+    } else {
+        const real x0 = lqk_col<0>(me.v);
+#pragma unroll
+        for (int s = 0; s < 7; ++s) acc[s] = Md[s][0] * x0;
+    }
+    // (the parked values are requested here, volatile = in program order, and consumed by the last FMAs of the pass)
+    real pk_[L::NPARK];
+#pragma unroll
+    for (int q = 0; q < L::NPARK; ++q) pk_[q] = lqk_ld(park + q * NTHR);
+    // direct, diagonal columns
+    SFor14<8>::run([&](auto jt) {                           // j = 1 .. 6
+        constexpr int J = decltype(jt)::value - 7;
+        real xs;
+        if constexpr (J == 6) xs = xk6; else xs = lqk_col<J>(me.v);
+        SFor14<7>::run([&](auto st) {
+            constexpr int S = decltype(st)::value - 7;
+            if constexpr (L::parked(S, J)) acc[S] = fma(pk_[L::pidx(S, J)], xs, acc[S]);
+            else acc[S] = fma(Md[S][J], xs, acc[S]);
+        });
+    });
+    // merge the two column halves: own slot s + the h-partner's slot (4, 5, 6, 3)[s]
+    LqkOwn o;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) o.v[s] = acc[s] + lqk_quad<LQK_QP_H>(acc[s < 3 ? s + 4 : 3]);
+    on_rows(o);
+    // inner product share: x_k . (D x_k + L x_{k-1}) over this lane's OWN rows (lane h = 1's slot 3 duplicates h = 0's: weight 0) + the coupling copy
+    real d0 = o.v[0] * me.v[0];
+    d0 = fma(o.v[1], me.v[1], d0);
+    d0 = fma(o.v[2], me.v[2], d0);
+    const real d3 = o.v[3] * me.v[3];
+    on_part(rpl_wave_fold((d0 + (h ? real(0) : d3)) + cterm));
+    return LqkVec{me, om};
+}
+
 template <int NWR>
 __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqk_f64_kernel(PcgArgs64 a) {
     typedef LqkLds<NWR> L;
@@ -138,13 +309,12 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqk_f64_kernel(PcgArgs64 a) 
         const rsrc_t M = make_rsrc(static_cast<const char*>(static_cast<const void*>(isP ? a.Pinv : a.S)) + (size_t)b * mstride * 8, (uint32_t)(mstride * 8));
         lqk_load_blocks(M, k, h, g, valid, valid && k > 0 && hasL, Md, Ml);
     }
-    // park the values the pass uses last (the diagonal block's seventh column, slots 7 - NPARK .. 6) in LDS; they are fetched back inside the pass
+    // park the values the pass uses last (the end of the diagonal block's seventh column) in LDS; they are fetched back inside the pass
     // (the register file holds 196 matrix registers + the working set of a half-iteration only just: left to the compiler the overflow goes to
     // SCRATCH, whose reloads cost global-memory latency in every pass — pcg_lpk_kernel)
     real* const park = lds + L::MX + tid;
     __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0)
-#pragma unroll
-    for (int i = 0; i < L::NPARK; ++i) park[i * NTHR] = Md[7 - L::NPARK + i][6];
+    lqk_park<L, NTHR>(park, Md);
 
     // ---- stage vectors: P0 <- lambda0 (operand of the setup product), lambda <- lambda0, R0 <- gamma, everything else (pads included) <- 0 ----
     for (int e = tid; e < L::RED; e += NTHR) lds[e] = real(0);
@@ -163,159 +333,23 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqk_f64_kernel(PcgArgs64 a) 
         if constexpr (NW == 8) return ((red[0] + red[1]) + red[2]) + red[3];
         else return red[0] + red[1];
     };
-    struct Own { real v[4]; };
-    // own entries (register slots 0..3, this lane's row of each pair) of knot k + dk of the vector at double offset X
-    auto load_own = [&](int X, int dk) -> Own {
-        const real* x = lds + X + 2 * dk;
-        Own o;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) o.v[s] = x[bA + K2 * s];
-        o.v[3] = x[b0 + 3 * K2];
-        return o;
-    };
-    // (no `k < N` predicate: a lane beyond the horizon holds all-zero blocks — its products, its z and its copies of the vectors are exact
-    //  zeros, and its knot slots exist — so it may write them)
-    auto store_own = [&](int X, const Own& o) {
-        real* x = lds + X;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) x[bA + K2 * s] = o.v[s];
-        x[b0 + 3 * K2] = o.v[3];
-    };
-    // The operand loads of a half-iteration, requested as soon as the barrier in front of it is passed — before the scalar of the update is
-    // worked out.  Own entries (slots 0..3) of knot k and of knot k-1 of the two published vectors the operand is formed from: 16 ds_read_b64.
-    struct Fetch { real t[4], z[4], gt[4], gz[4]; };
-    auto fetch = [&](int T, int Z) -> Fetch {
-        const real* xt = lds + T;
-        const real* xz = lds + Z + 2;
-        Fetch f;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) { f.t[s] = lqk_ld(xt + bA + K2 * s); f.z[s] = lqk_ld(xz + bA + K2 * s); }
-        f.t[3] = lqk_ld(xt + b0 + 3 * K2); f.z[3] = lqk_ld(xz + b0 + 3 * K2);
-#pragma unroll
-        for (int s = 0; s < 3; ++s) { f.gt[s] = lqk_ld(xt - 2 + bA + K2 * s); f.gz[s] = lqk_ld(xz - 2 + bA + K2 * s); }
-        f.gt[3] = lqk_ld(xt - 2 + b0 + 3 * K2); f.gz[3] = lqk_ld(xz - 2 + b0 + 3 * K2);
-        return f;
-    };
-    struct Vec { Own k, m; };                                  // a lane's copy of a vector: its own entries of knot k and of knot k-1
-    // entry of column j (of this lane's seven) of a vector whose own slots are v: slot j >> 1, element j & 1 — from the g lane that holds it
-    auto col = [&](const real (&v)[4], auto jt) -> real {
-        constexpr int J = decltype(jt)::value;
-        if constexpr (J == 6) return lqk_quad<LQK_QP_B6>(v[3]);                                       // entry 6 + h: pair 3, element h
-        else if constexpr ((J & 1) == 0) return lqk_quad<LQK_QP_B0>(v[J >> 1]);
-        else return lqk_quad<LQK_QP_B1>(v[J >> 1]);
-    };
-
-    // One half-iteration of this wave's matrix (pcg_lpk_kernel::half).  `old` = the lane's register copy of the vector being updated.
-    //   MODE 0: the operand is `old` as it stands (setup product S lambda0);
-    //   MODE 1: operand = old - c (T + Z<<1)          (Pinv half: r_new, c = alpha; setup: c = 1)
-    //   MODE 2: operand = (T + Z<<1) + c old          (S half: p_new, c = beta; first iteration: c = 0)
+    typedef LqkOwn Own;
+    typedef LqkFetch Fetch;
+    typedef LqkVec Vec;
+    auto load_own = [&](int X, int dk) -> Own { return lqk_load_own<K2>(lds, bA, b0, X, dk); };
+    auto store_own = [&](int X, const Own& o) { lqk_store_own<K2>(lds, bA, b0, X, o); };
+    auto fetch = [&](int T, int Z) -> Fetch { return lqk_fetch<K2>(lds, bA, b0, T, Z); };
+    // One half-iteration of this wave's matrix (lqk_half): every lane stores its z and its rows, the wave's partial goes to red[wl]
     auto half = [&](auto mode_tag, const Fetch& f, const Vec& old, real c, int TOUT, int ZOUT, real* red) -> Vec {
-        constexpr int MODE = decltype(mode_tag)::value;
-        real xk[7];                                              // x_k at this lane's row of all seven pairs (slots 4..6: the h-partner's own)
-        Own om;                                                  // knot k-1, own entries
-        if constexpr (MODE == 0) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { xk[s] = old.k.v[s]; om.v[s] = old.m.v[s]; }
-        } else {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { const real u = f.t[s] + f.z[s]; xk[s] = MODE == 1 ? old.k.v[s] - c * u : u + c * old.k.v[s]; }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) { const real u = f.gt[s] + f.gz[s]; om.v[s] = MODE == 1 ? old.m.v[s] - c * u : u + c * old.m.v[s]; }
-        }
-#pragma unroll
-        for (int s = 0; s < 3; ++s) xk[4 + s] = lqk_quad<LQK_QP_H>(xk[s]);
-        Own me;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) me.v[s] = xk[s];
-        real acc[7];
-        real cterm = real(0);
-        const real xk6 = col(me.v, std::integral_constant<int, 6>{});
-        if (hasL) {
-            // transposed: z[j] = sum over rows of L[row][column j] x_k[row]; this lane's seven rows, the other seven from the g-partner
-            real z[7];
-            {
-                real t[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) t[j] = Ml[0][j] * xk[0];
-#pragma unroll
-                for (int s = 1; s < 7; ++s)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) t[j] = fma(Ml[s][j], xk[s], t[j]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) z[j] = t[j] + lqk_quad<LQK_QP_G>(t[j]);
-            }
-            {
-                real t[3];
-#pragma unroll
-                for (int j = 0; j < 3; ++j) t[j] = Ml[0][4 + j] * xk[0];
-#pragma unroll
-                for (int s = 1; s < 7; ++s)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) t[j] = fma(Ml[s][4 + j], xk[s], t[j]);
-#pragma unroll
-                for (int j = 0; j < 3; ++j) z[4 + j] = t[j] + lqk_quad<LQK_QP_G>(t[j]);
-            }
-            {                                                    // z belongs to knot k-1's vector: column j = (slot j >> 1, element j & 1) — this lane stores element g
+        return lqk_half<decltype(mode_tag)::value, L, NTHR>(Md, Ml, park, h, g, hasL, f, old, c,
+            [&](const real (&z)[7]) {                            // column j = (slot j >> 1, element j & 1) — this lane stores element g
                 real* zo = lds + ZOUT;
 #pragma unroll
                 for (int s = 0; s < 3; ++s) zo[bA + K2 * s] = g ? z[2 * s + 1] : z[2 * s];
                 if (g == h) zo[b0 + 3 * K2] = z[6];              // entry 6 + h = pair 3, element h
-            }
-            // second copy of the coupling term of the inner product, x_{k-1}^T (L_k^T x_k): this lane's own columns of parity g (+ column 6 in the lane g == h)
-            real ct = (g ? z[1] : z[0]) * om.v[0];
-            ct = fma(g ? z[3] : z[2], om.v[1], ct);
-            ct = fma(g ? z[5] : z[4], om.v[2], ct);
-            cterm = g == h ? fma(z[6], om.v[3], ct) : ct;
-            // direct, off-diagonal columns: acc = L[:, c_j] x_{k-1}[c_j]
-            {
-                const real x0 = col(om.v, std::integral_constant<int, 0>{});
-#pragma unroll
-                for (int s = 0; s < 7; ++s) acc[s] = Ml[s][0] * x0;
-            }
-            SFor14<8>::run([&](auto jt) {                       // j = 1 .. 6
-                constexpr int J = decltype(jt)::value - 7;
-                const real xs = col(om.v, std::integral_constant<int, J>{});
-#pragma unroll
-                for (int s = 0; s < 7; ++s) acc[s] = fma(Ml[s][J], xs, acc[s]);
-            });
-            {
-                const real x0 = col(me.v, std::integral_constant<int, 0>{});
-#pragma unroll
-                for (int s = 0; s < 7; ++s) acc[s] = fma(Md[s][0], x0, acc[s]);
-            }
-        } else {
-            const real x0 = col(me.v, std::integral_constant<int, 0>{});
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = Md[s][0] * x0;
-        }
-        // (the parked values are requested here, volatile = in program order, and consumed by the last FMAs of the pass)
-        real pk_[L::NPARK];
-#pragma unroll
-        for (int i = 0; i < L::NPARK; ++i) pk_[i] = lqk_ld(park + i * NTHR);
-        // direct, diagonal columns
-        SFor14<9>::run([&](auto jt) {                           // j = 1 .. 5
-            constexpr int J = decltype(jt)::value - 8;
-            const real xs = col(me.v, std::integral_constant<int, J>{});
-#pragma unroll
-            for (int s = 0; s < 7; ++s) acc[s] = fma(Md[s][J], xs, acc[s]);
-        });
-#pragma unroll
-        for (int s = 0; s < 7 - L::NPARK; ++s) acc[s] = fma(Md[s][6], xk6, acc[s]);
-#pragma unroll
-        for (int i = 0; i < L::NPARK; ++i) acc[7 - L::NPARK + i] = fma(pk_[i], xk6, acc[7 - L::NPARK + i]);
-        // merge the two column halves: own slot s + the h-partner's slot (4, 5, 6, 3)[s]
-        Own o;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) o.v[s] = acc[s] + lqk_quad<LQK_QP_H>(acc[s < 3 ? s + 4 : 3]);
-        store_own(TOUT, o);
-        // inner product share: x_k . (D x_k + L x_{k-1}) over this lane's OWN rows (lane h = 1's slot 3 duplicates h = 0's: weight 0) + the coupling copy
-        real d0 = o.v[0] * me.v[0];
-        d0 = fma(o.v[1], me.v[1], d0);
-        d0 = fma(o.v[2], me.v[2], d0);
-        const real d3 = o.v[3] * me.v[3];
-        const real part = rpl_wave_fold((d0 + (h ? real(0) : d3)) + cterm);
-        if (lane == 0) red[wl] = part;
-        return Vec{me, om};
+            },
+            [&](const Own& o) { store_own(TOUT, o); },
+            [&](real part) { if (lane == 0) red[wl] = part; });
     };
 
     // The S waves and the Pinv waves run the same barrier sequence through two SEPARATE code paths (the role is wave-uniform).

@@ -3,8 +3,9 @@
 the instruction text per demangled kernel name, addresses and absolute branch targets stripped.  Prints the kernels that differ, were
 added or were removed; exit status 1 if a kernel present in both differs.  A kernel that changed its NAME between the builds (it became a
 template, say) is compared as a pair with --rename 'OLD NAME=NEW NAME' (demangled, as printed under removed / added; repeatable).
-   python tools/_prof/diff_kernels.py old/libmpcg_hip.so new/libmpcg_hip.so [--rename 'old=new' ...]"""
-import os, re, shutil, subprocess, sys, tempfile
+--opcodes: under each kernel that differs, the opcodes whose counts changed (old -> new; DPP forms counted apart, as opcode_dpp).
+   python tools/_prof/diff_kernels.py old/libmpcg_hip.so new/libmpcg_hip.so [--opcodes] [--rename 'old=new' ...]"""
+import collections, os, re, shutil, subprocess, sys, tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
@@ -38,6 +39,10 @@ def kernels(lib):
     return out
 
 
+def opcodes(ins):
+    return collections.Counter(l.split()[0] + ("_dpp" if re.search(r"quad_perm|row_|wave_", l) and not l.split()[0].endswith("_dpp") else "") for l in ins if not l.endswith(":"))
+
+
 old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
 for i, a in enumerate(sys.argv):
     if a == "--rename":
@@ -51,6 +56,9 @@ for title, names in (("removed", sorted(set(old) - set(new))), ("added", sorted(
     print(f"{title}: {len(names)}")
     for k in names:
         print("   ", k, f"({len(old[k])} -> {len(new[k])} instructions)" if title == "DIFFER" else "")
+        if title == "DIFFER" and "--opcodes" in sys.argv:
+            ho, hn = opcodes(old[k]), opcodes(new[k])
+            print("        " + ("; ".join(f"{op} {ho[op]} -> {hn[op]}" for op in sorted(set(ho) | set(hn)) if ho[op] != hn[op]) or "(every opcode count unchanged: order or registers only)"))
 print(f"identical: {len(common) - len(differ)} of {len(common)} common kernels, {sum(len(old[k]) for k in common)} instructions;"
       f" library size {os.path.getsize(sys.argv[1])} -> {os.path.getsize(sys.argv[2])} bytes")
 sys.exit(1 if differ else 0)
