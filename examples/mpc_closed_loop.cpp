@@ -1,0 +1,207 @@
+// mpc_closed_loop.cpp — the MPC loop closed on the device.  Two runs on the reference's precomputed trajectory (mpcgpu_amd/data/iiwa_traj_0_0.f32):
+//   1. simulateMPC (the reference's entry point, include/mpcsim.cuh:147) over THIS repo's shim headers with ALL THREE library stages registered:
+//      mpcgpu_compat::use_mpcg_generate_kkt, use_mpcg_line_search and use_mpcg_simulate_and_shift (mpcg_simulate + mpcg_advance_horizon with the
+//      host bookkeeping of include/mpcsim.cuh:280-352) — no stage is a host callback of the program's own.  The plant is integrated at 0.2 ms under
+//      the PREVIOUS plan's controls, as the reference does; a fixed number of SQP iterations per control update of 2,000 us.
+//   2. a batched run over the C ABI alone: B windows, U control updates, per update K iterations of the six SQP calls (rho per trajectory on the
+//      device), then mpcg_simulate under the previous plan and mpcg_advance_horizon — the host decides WHEN to shift from the clock bookkeeping, which
+//      is the same for every trajectory, so nothing synchronises inside an update; tracking errors wait in a device buffer and are read at the end.
+// Prints one JSON line; exits 0 only if every tracking error is finite and every trajectory shifted the expected number of times.
+//   hipcc --offload-arch=gfx950 -O2 -DLINSYS_SOLVE=1 -Iinclude examples/mpc_closed_loop.cpp -Lmpcgpu_amd -lmpcg_hip
+//   mpc_closed_loop [--batch 4] [--knots 16] [--updates 17] [--iters 1] [--mpc-steps 16]
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#define STATE_SIZE 14
+#define KNOT_POINTS 32
+#define PCG_MAX_ITER 3000
+#include "mpcsim.cuh"
+
+typedef float T;
+static const int n = 14, m = 7, ROWW = 27, ROWS = 400;      // a row of the data file: x (14), u (7), end-effector pose (6)
+
+#define MPCG_OK_OR_DIE(h, expr)                                                                              \
+    do {                                                                                                     \
+        if ((expr) != MPCG_OK) { fprintf(stderr, "%s: %s\n", #expr, mpcg_last_error(h)); exit(1); }          \
+    } while (0)
+
+static std::vector<T> load_rows(const std::string& exe) {
+    const std::string dir = exe.substr(0, exe.find_last_of('/') + 1);
+    for (const std::string& p : {dir + "../mpcgpu_amd/data/iiwa_traj_0_0.f32", std::string("mpcgpu_amd/data/iiwa_traj_0_0.f32")}) {
+        if (FILE* f = fopen(p.c_str(), "rb")) {
+            std::vector<T> v((size_t)ROWS * ROWW);
+            const size_t got = fread(v.data(), sizeof(T), v.size(), f);
+            fclose(f);
+            if (got == v.size()) return v;
+        }
+    }
+    fprintf(stderr, "cannot read mpcgpu_amd/data/iiwa_traj_0_0.f32\n");
+    exit(1);
+}
+
+template <typename V>
+static V* to_device(const std::vector<V>& v) {
+    V* p = nullptr;
+    gpuErrchk(hipMalloc(reinterpret_cast<void**>(&p), v.size() * sizeof(V)));
+    gpuErrchk(hipMemcpy(p, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice));
+    return p;
+}
+template <typename V>
+static V* dalloc(size_t count) { return to_device(std::vector<V>(count, V(0))); }
+
+// The clock bookkeeping of include/mpcsim.cuh:294-347 for a constant simulation period: does update `u` (from 0) shift the horizon?
+struct ShiftClock {
+    double since = 0, timestep;
+    bool shifted = false;
+    explicit ShiftClock(double dt) : timestep(dt) {}
+    bool update(double sim_us) {
+        since += sim_us * 1e-6;
+        const bool shift = !shifted && since > (double)(T)(1 * timestep);      // SHIFT_THRESHOLD
+        if (shift) shifted = true;
+        if (since > timestep) { shifted = false; since = std::fmod(since, timestep); }
+        return shift;
+    }
+};
+
+int main(int argc, char** argv) {
+    int B = 4, N = 16, U = 17, K = 1, mpc_steps = 16;
+    for (int i = 1; i + 1 < argc; i += 2) {
+        if (!strcmp(argv[i], "--batch")) B = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--knots")) N = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--updates")) U = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--iters")) K = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--mpc-steps")) mpc_steps = atoi(argv[i + 1]);
+        else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
+    }
+    if (B < 1 || N < 2 || N > 128 || U < 1 || K < 1 || mpc_steps < 1) { fprintf(stderr, "need batch >= 1, 2 <= knots <= 128, updates, iters, mpc-steps >= 1\n"); return 2; }
+    const float dt = 1.0f / 64, qd_cost = 1e-4f, mu = 10.f;                  // include/common/settings.cuh:84-94, include/pcg/sqp.cuh:51
+    const double period_us = 2000;                                            // SIMULATION_PERIOD
+    const std::vector<T> rows = load_rows(argv[0]);
+    std::vector<T> plan((size_t)ROWS * (n + m)), plan_goals((size_t)ROWS * 6);
+    for (int t = 0; t < ROWS; ++t) {
+        memcpy(&plan[(size_t)t * (n + m)], &rows[(size_t)t * ROWW], (n + m) * sizeof(T));
+        memcpy(&plan_goals[(size_t)t * 6], &rows[(size_t)t * ROWW + n + m], 6 * sizeof(T));
+    }
+    unsigned seed = 99u;
+    auto rnd = [&seed]() { seed = seed * 1664525u + 1013904223u; return ((seed >> 8) & 0xffff) / 65536.0f - 0.5f; };
+    mpcg_plant* plant = nullptr;
+    if (mpcg_plant_create_iiwa14(&plant, -1) != MPCG_OK) { fprintf(stderr, "mpcg_plant_create_iiwa14: %s\n", mpcg_last_error(nullptr)); return 1; }
+    T* d_plan = to_device(plan);
+    T* d_plan_goals = to_device(plan_goals);
+
+    // ---- 1. simulateMPC with the three library stages (single trajectory, KNOT_POINTS knots) ----
+    std::vector<linsys_t> mpc_errors;
+    {
+        const float r_cost = KNOT_POINTS == 64 ? 1e-3f : 1e-4f;
+        mpcgpu_compat::use_mpcg_generate_kkt<T>(plant, qd_cost, r_cost);
+        mpcgpu_compat::use_mpcg_line_search<T>(mu, qd_cost, r_cost, dt);
+        mpcgpu_compat::use_mpcg_simulate_and_shift<T>(d_plan, d_plan_goals, ROWS, dt, period_us, (uint32_t)mpc_steps);
+        auto& st = mpcgpu_compat::stages<T>();
+        st.sqp_max_iter = 2;
+        st.const_update_freq = false;         // a fixed number of SQP iterations per update (the wall-clock time box would make the run depend on the machine)
+        std::vector<T> xs0(plan.begin(), plan.begin() + n);
+        for (int i = 0; i < n; ++i) xs0[i] += 0.04f * rnd();                 // the measured state is off the plan
+        T* d_xs = to_device(xs0);
+        auto res = simulateMPC<T, toplevel_return_type>(n, m, KNOT_POINTS, ROWS, dt, d_plan_goals, d_plan, d_xs, 0, 0, 0, (T)1e-7, std::string("mpc_closed_loop"));
+        mpc_errors = std::get<1>(res);
+        gpuErrchk(hipFree(d_xs));
+    }
+
+    // ---- 2. B windows through U control updates over the C ABI, nothing synchronises inside an update ----
+    const int TS = N + 24;                                                    // rows of a trajectory's own plan
+    if (TS > ROWS) { fprintf(stderr, "knots too large for the data file\n"); return 2; }
+    const float r_cost = N == 64 ? 1e-3f : 1e-4f;
+    const size_t L = (size_t)(n + m) * N - m, nn = n * n, mm = m * m, nm = n * m;
+    std::vector<T> bplan((size_t)B * TS * (n + m)), bgoals((size_t)B * TS * 6), xu((size_t)B * L), goals((size_t)B * 6 * N), xs((size_t)B * n);
+    for (int b = 0; b < B; ++b) {
+        const int t0 = (int)(((long)b * 37) % (ROWS - TS));
+        memcpy(&bplan[(size_t)b * TS * (n + m)], &plan[(size_t)t0 * (n + m)], (size_t)TS * (n + m) * sizeof(T));
+        memcpy(&bgoals[(size_t)b * TS * 6], &plan_goals[(size_t)t0 * 6], (size_t)TS * 6 * sizeof(T));
+        memcpy(&xu[(size_t)b * L], &plan[(size_t)t0 * (n + m)], L * sizeof(T));
+        memcpy(&goals[(size_t)b * 6 * N], &plan_goals[(size_t)t0 * 6], (size_t)6 * N * sizeof(T));
+        for (int i = 0; i < n; ++i) xs[(size_t)b * n + i] = xu[(size_t)b * L + i] + 0.04f * rnd();
+    }
+    mpcg_handle* h = nullptr;
+    if (mpcg_create(&h, -1, n, (uint32_t)N, (uint32_t)B) != MPCG_OK) { fprintf(stderr, "mpcg_create: %s\n", mpcg_last_error(nullptr)); return 1; }
+    T *d_bplan = to_device(bplan), *d_bgoals = to_device(bgoals), *d_xu = to_device(xu), *d_xu_old = to_device(xu), *d_goals = to_device(goals), *d_xs = to_device(xs);
+    T* d_G = dalloc<T>((size_t)B * ((nn + mm) * N - mm));
+    T* d_C = dalloc<T>((size_t)B * (nn + nm) * (N - 1));
+    T *d_g = dalloc<T>((size_t)B * L), *d_c = dalloc<T>((size_t)B * n * N), *d_S = dalloc<T>((size_t)B * 3 * nn * N), *d_Pinv = dalloc<T>((size_t)B * 3 * nn * N);
+    T *d_gamma = dalloc<T>((size_t)B * n * N), *d_lambda = dalloc<T>((size_t)B * n * N), *d_dz = dalloc<T>((size_t)B * L), *d_merit = dalloc<T>((size_t)B * 8);
+    T *d_merit_ref = dalloc<T>(B), *d_eePos = dalloc<T>((size_t)B * 3), *d_err = dalloc<T>(B), *d_err_hist = dalloc<T>((size_t)U * B);
+    T *d_rho = to_device(std::vector<T>((size_t)B, 1e-3f)), *d_drho = dalloc<T>(B), *d_ones = to_device(std::vector<T>((size_t)B, 1.0f));
+    int32_t *d_step = dalloc<int32_t>(B), *d_offset = dalloc<int32_t>(B), *d_done = dalloc<int32_t>(B);
+    uint32_t* d_iters = dalloc<uint32_t>(B);
+    uint8_t *d_exit = dalloc<uint8_t>(B), *d_gave_up = dalloc<uint8_t>(B);
+    hipStream_t s;
+    gpuErrchk(hipStreamCreate(&s));
+    float steps[8];
+    for (int p = 0; p < 8; ++p) steps[p] = -1.0f / (float)(1 << p);
+    const float zero = 0.f;
+    ShiftClock clock(dt);
+    double prev_us = 0;
+    int shifts = 0;
+    for (int u = 0; u < U; ++u) {                                             // no host synchronisation in here
+        // one SQP call (include/pcg/sqp.cuh): x_s = x_0 of the iterate, drho = 1, merit of the start iterate, K iterations
+        gpuErrchk(hipMemcpyAsync(d_drho, d_ones, B * sizeof(T), hipMemcpyDeviceToDevice, s));
+        gpuErrchk(hipMemsetAsync(d_gave_up, 0, B, s));
+        MPCG_OK_OR_DIE(h, mpcg_compute_merit(h, plant, m, dt, d_goals, d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, (uint32_t)B, s));
+        for (int it = 0; it < K; ++it) {
+            MPCG_OK_OR_DIE(h, mpcg_generate_kkt(h, plant, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, s));
+            MPCG_OK_OR_DIE(h, mpcg_form_schur_rhov(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_rho, (uint32_t)B, MPCG_PRECOND_SS, s));
+            MPCG_OK_OR_DIE(h, mpcg_pcg_solve(h, d_S, d_Pinv, d_gamma, d_lambda, (uint32_t)B, PCG_MAX_ITER, 1e-7f, MPCG_PRECOND_SS, d_iters, d_exit, s));
+            MPCG_OK_OR_DIE(h, mpcg_compute_dz(h, m, d_G, d_C, d_g, d_lambda, d_dz, (uint32_t)B, s));
+            MPCG_OK_OR_DIE(h, mpcg_compute_merit(h, plant, m, dt, d_goals, d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, (uint32_t)B, s));
+            MPCG_OK_OR_DIE(h, mpcg_line_search_step_rho(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step, d_rho, d_drho, d_gave_up, 1.2f, 1e-3f, 10.f, 1e-3f,
+                                                        (uint32_t)B, s));
+        }
+        // the plant runs under the PREVIOUS plan for one period, offset by the previous period (include/mpcsim.cuh:288-291, :352)
+        MPCG_OK_OR_DIE(h, mpcg_simulate(h, plant, m, d_xs, d_xu_old, dt, prev_us, period_us, 2e-4f, d_eePos, (uint32_t)B, s));
+        gpuErrchk(hipMemcpyAsync(d_xu_old, d_xu, (size_t)B * L * sizeof(T), hipMemcpyDeviceToDevice, s));
+        const bool shift = clock.update(period_us);
+        MPCG_OK_OR_DIE(h, mpcg_advance_horizon(h, m, shift ? 1 : 0, d_xu, d_lambda, d_goals, d_xs, d_eePos, d_bplan, d_bgoals, (uint32_t)TS, (uint32_t)TS, 0,
+                                               d_offset, d_done, d_err, (uint32_t)B, s));
+        if (shift) {
+            gpuErrchk(hipMemcpyAsync(d_err_hist + (size_t)shifts * B, d_err, B * sizeof(T), hipMemcpyDeviceToDevice, s));
+            ++shifts;
+        }
+        prev_us = period_us;
+    }
+    gpuErrchk(hipStreamSynchronize(s));
+    std::vector<T> err((size_t)U * B), xs_end((size_t)B * n);
+    std::vector<int32_t> offset(B);
+    gpuErrchk(hipMemcpy(err.data(), d_err_hist, err.size() * sizeof(T), hipMemcpyDeviceToHost));
+    gpuErrchk(hipMemcpy(offset.data(), d_offset, B * sizeof(int32_t), hipMemcpyDeviceToHost));
+    gpuErrchk(hipMemcpy(xs_end.data(), d_xs, xs_end.size() * sizeof(T), hipMemcpyDeviceToHost));
+
+    bool ok = (int)mpc_errors.size() == mpc_steps;
+    for (linsys_t e : mpc_errors) ok = ok && std::isfinite((double)e);
+    for (int i = 0; i < shifts * B; ++i) ok = ok && std::isfinite((double)err[i]);
+    for (T x : xs_end) ok = ok && std::isfinite((double)x);
+    for (int b = 0; b < B; ++b) ok = ok && offset[b] == shifts;
+    printf("{\"batch\": %d, \"knots\": %d, \"updates\": %d, \"iters\": %d, \"expected_shifts\": %d, \"shifts\": [", B, N, U, K, shifts);
+    for (int b = 0; b < B; ++b) printf("%s%d", b ? ", " : "", offset[b]);
+    printf("], \"tracking_errors\": [");
+    for (int i = 0; i < shifts; ++i) {
+        printf("%s[", i ? ", " : "");
+        for (int b = 0; b < B; ++b) printf("%s%.9g", b ? ", " : "", (double)err[(size_t)i * B + b]);
+        printf("]");
+    }
+    printf("], \"simulate_mpc\": {\"knots\": %d, \"control_updates\": %zu, \"tracking_errors\": [", KNOT_POINTS, mpc_errors.size());
+    for (size_t i = 0; i < mpc_errors.size(); ++i) printf("%s%.9g", i ? ", " : "", (double)mpc_errors[i]);
+    printf("]}, \"ok\": %s}\n", ok ? "true" : "false");
+
+    for (void* p : {(void*)d_plan, (void*)d_plan_goals, (void*)d_bplan, (void*)d_bgoals, (void*)d_xu, (void*)d_xu_old, (void*)d_goals, (void*)d_xs, (void*)d_G, (void*)d_C,
+                    (void*)d_g, (void*)d_c, (void*)d_S, (void*)d_Pinv, (void*)d_gamma, (void*)d_lambda, (void*)d_dz, (void*)d_merit, (void*)d_merit_ref, (void*)d_eePos,
+                    (void*)d_err, (void*)d_err_hist, (void*)d_rho, (void*)d_drho, (void*)d_ones, (void*)d_step, (void*)d_offset, (void*)d_done, (void*)d_iters,
+                    (void*)d_exit, (void*)d_gave_up})
+        gpuErrchk(hipFree(p));
+    gpuErrchk(hipStreamDestroy(s));
+    mpcg_plant_destroy(plant);
+    mpcg_destroy(h);
+    return ok ? 0 : 1;
+}

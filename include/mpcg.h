@@ -391,6 +391,58 @@ int mpcg_line_search_step_rho(mpcg_handle *h, uint32_t control_size, const float
                               uint8_t *d_done /* [batch] in/out */, float rho_factor, float rho_min, float rho_max, float rho_reset,
                               uint32_t batch, void *stream);
 
+/* ---- plant simulation and horizon shift: the step between two SQP solves of the MPC loop (csrc/sim_plant.hip.h) ----
+ * What simulateMPC does once per control update (reference include/mpcsim.cuh:288-348), batched, on the device, nothing read back.  Float, state_size
+ * 14 / control_size 7 only (MPCG_ERR_UNSUPPORTED otherwise); both calls are pure stream work from the first call on (capturable).
+ *
+ * mpcg_simulate is simple_simulate (include/common/integrator.cuh:295-325) for the whole batch and all substeps in ONE launch: every trajectory's
+ * plant state d_xs[b] is integrated over sim_time_us under the controls of the plan d_xu[b] (the reference passes d_xu_old, the PREVIOUS plan).
+ * The schedule is evaluated in IEEE double:  ss = (double)sim_step, toff = time_offset_us * 1e-6, sim = sim_time_us * 1e-6;
+ *   S = (uint32)(sim / ss) full substeps of dt = ss; substep s applies u of knot idx_s = (uint32)((toff + s * ss) / timestep);
+ *   then one remainder substep of dt = (float)fmod(sim, ss) with the control of the LAST full substep (the reference does not recompute the index
+ *   there, :322-324), or of (uint32)(toff / timestep) if S = 0.  A remainder of exactly 0 is not run: sim_time_us = 0 leaves d_xs bitwise unchanged.
+ * A substep is explicit Euler from the old values, q += dt qd, qd += dt qdd, qdd = forward dynamics of the mpcg_plant without gravity in float64
+ * (the arithmetic of mpcg_generate_kkt's integrator defect).  Substeps are gated on their number, never on time accumulated in float.
+ * Two deliberate departures from the reference:
+ *   - the state is carried in float64 across the substeps of a call and rounded to float ONCE, on store; the reference rounds after every substep
+ *     (its T is float).  d_xs and the controls are read as float and widened.
+ *   - a control index beyond the last control, idx > knot_points - 2, is clamped to knot_points - 2; the reference reads past its buffer there.
+ * d_eePos (may be NULL): [batch][3], the end-effector position of the NEW state, float64 inside, rounded once (what mpcg_advance_horizon takes).
+ * Results are bitwise reproducible and a trajectory's do not depend on the rest of the batch (no atomics).
+ *   MPCG_ERR_INVALID   a null required pointer; sim_step <= 0, timestep <= 0, a negative time, a non-finite argument; more than
+ *                      MPCG_SIM_MAX_SUBSTEPS full substeps (sim / ss >= 65537); batch > max_batch; a plant on another device.  Nothing is written.
+ *
+ * mpcg_advance_horizon is the rest of the control update (include/mpcsim.cuh:300-348), one workgroup per trajectory, dynamics-free, every source
+ * read before it is overwritten.  A trajectory whose d_done[b] is non-zero on entry is FROZEN: nothing of it is written (as MPCG_STEP_FROZEN).
+ *   shift = 0:  d_xu[b][0:14] = d_xs[b] (:348) and nothing else; only d_xu and d_xs are required (d_done is honoured if given).
+ *   shift = 1, per trajectory, in the reference's order:
+ *     d_tracking_error[b] = (|ee0 - goal[0]| + |ee1 - goal[1]|) + |ee2 - goal[2]| in float, in that order, d_eePos[b] against knot 0 of the
+ *       UNSHIFTED goals (:303-306);
+ *     d_traj_offset[b] += 1 (:310);
+ *     just_shift of d_xu (integrator.cuh:258-263: knots 1..N-1 move to 0..N-2, the last moved knot carries no control); its tail u_{N-2}, x_{N-1}:
+ *       if traj_offset + N < traj_steps, the 21 plan values at (n+m) * (traj_offset + xu_fill_lead) - m.  With xu_fill_lead = 0 that is :316
+ *       literally — a quirk of the reference: its goal fill uses plan row traj_offset + N - 1, its xu fill does not.  A caller who wants the
+ *       aligned row passes xu_fill_lead = N - 1.  Otherwise (:320-322) the final plan position, zero velocity, zero last control;
+ *     just_shift(6, 0, N) of d_eePos_goal, its last knot from plan row traj_offset + N - 1, or traj_steps - 1 in the else branch (:326-334);
+ *     just_shift(14, 0, N) of d_lambda: the last knot of lambda keeps its value (:337-338);
+ *     the :348 copy; d_done[b] = 1 when traj_offset reaches traj_steps (:252).
+ *   The plan: d_xu_traj traj_steps rows of n + m floats, d_eePos_traj traj_steps rows of 6; traj_batch_stride = 0: one plan shared by the batch,
+ *   otherwise trajectory b's plan starts traj_batch_stride rows behind trajectory b-1's (>= traj_steps).  d_traj_offset is device data: a value
+ *   that is no row of the plan takes the else branch.
+ *   MPCG_ERR_INVALID   shift > 1; a null required pointer (shift = 1: every array, d_eePos included); traj_steps = 0; xu_fill_lead > N - 1;
+ *                      0 < traj_batch_stride < traj_steps; batch > max_batch.  Nothing is written. */
+#define MPCG_SIM_MAX_SUBSTEPS 65536
+int mpcg_simulate(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size,
+                  float *d_xs /* [batch][14] in/out */, const float *d_xu /* [batch][(n+m)N - m] */,
+                  double timestep, double time_offset_us, double sim_time_us, float sim_step /* reference: 2e-4f */,
+                  float *d_eePos /* [batch][3] or NULL */, uint32_t batch, void *stream);
+int mpcg_advance_horizon(mpcg_handle *h, uint32_t control_size, uint32_t shift,
+                         float *d_xu, float *d_lambda, float *d_eePos_goal /* in/out */,
+                         const float *d_xs /* [batch][14] */, const float *d_eePos /* [batch][3]; needed when shift = 1 */,
+                         const float *d_xu_traj, const float *d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride,
+                         uint32_t xu_fill_lead, int32_t *d_traj_offset, int32_t *d_done /* [batch] in/out */,
+                         float *d_tracking_error /* [batch] out */, uint32_t batch, void *stream);
+
 /* ---- LINSYS_SOLVE == 0 as a selectable solver: the reference's CPU LDL^T path ----
  * The reference's second linear-system path factors the (negated) Schur matrix on the HOST with QDLDL
  * (include/qdldl/sqp.cuh: pattern prep_csr :164 + QDLDL_etree :193 once per SQP call; per SQP iteration D2H(values,

@@ -2,14 +2,16 @@
 // assembly with the robot dynamics, merit / line search, plant simulation + horizon shift).  The shim versions of sqpSolvePcg / sqpSolveQdldl /
 // simulateMPC (include/pcg/sqp.cuh, include/qdldl/sqp.cuh, include/mpcsim.cuh of THIS repo) keep the reference's names, argument lists and
 // return tuples and run the linear-system section on libmpcg_hip; wherever the reference calls one of those stages' kernels they call the
-// function registered here.  Two of the three are in the library now and register themselves: use_mpcg_generate_kkt (mpcg_generate_kkt) and
-// use_mpcg_line_search (mpcg_compute_merit + mpcg_line_search_step with the alpha / rho logic of include/pcg/sqp.cuh:264-353) for the IIWA-14;
-// the plant simulation + horizon shift (simple_simulate + just_shift) stays outside the library.  A maintainer porting MPCGPU with another
-// robot registers thin wrappers around the reference's kernels instead; examples/mpcsim_shim_demo.cpp registers a synthetic convex problem.
+// function registered here.  All three are in the library now and register themselves for the IIWA-14: use_mpcg_generate_kkt (mpcg_generate_kkt),
+// use_mpcg_line_search (mpcg_compute_merit + mpcg_line_search_step with the alpha / rho logic of include/pcg/sqp.cuh:264-353) and
+// use_mpcg_simulate_and_shift (mpcg_simulate + mpcg_advance_horizon with the host bookkeeping of include/mpcsim.cuh:280-352).  A maintainer porting
+// MPCGPU with another robot registers thin wrappers around the reference's kernels instead; examples/mpcsim_shim_demo.cpp registers a synthetic
+// convex problem.
 #pragma once
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <algorithm>
 #include <functional>
 #include <memory>
@@ -20,6 +22,9 @@
 #endif
 #ifndef SQP_MAX_TIME_US
 #define SQP_MAX_TIME_US 2000     // include/common/settings.cuh:161-163
+#endif
+#ifndef SIMULATION_PERIOD
+#define SIMULATION_PERIOD 2000   // include/common/settings.cuh:70-72 [us]
 #endif
 
 namespace mpcgpu_compat {
@@ -58,8 +63,8 @@ inline sqp_stages<T>& stages() {
 }
 
 // The library's own generate_kkt_submatrices (mpcg_generate_kkt: IIWA-14 dynamics, tracking cost, Euler integrator on the device) as the
-// generate_kkt stage — the default when an mpcg_plant is supplied; use_mpcg_line_search below adds the merit function / line search, the plant
-// simulation stays a plug point.
+// generate_kkt stage — the default when an mpcg_plant is supplied; use_mpcg_line_search below adds the merit function / line search,
+// use_mpcg_simulate_and_shift the plant simulation and the horizon shift.
 // qd_cost / r_cost: QD_COST / R_COST of include/common/settings.cuh:84-94.  Needs gbd_pcg_compat/gpu_pcg.cuh (handle cache) before this header.
 #ifdef MPCG_H
 template <typename T>
@@ -133,6 +138,73 @@ inline void use_mpcg_line_search(float mu, float qd_cost, float r_cost, float ti
         s->drho = std::min(s->drho / rho_factor, 1 / rho_factor);              // (:319-320)
         rho = std::max(rho * s->drho, rho_min);
         return true;
+    };
+}
+// The library's own plant simulation and horizon shift as the simulate_and_shift stage: include/mpcsim.cuh:280-352 of the reference over
+// mpcg_simulate (simple_simulate: all substeps of a control update in ONE launch) and mpcg_advance_horizon (tracking error, just_shift, tail fills,
+// start-state copy on the device), with the reference's host bookkeeping: the plant runs under the PREVIOUS plan (d_xu_old, :288-291) for
+// simulation_time = SIMULATION_PERIOD under const_update_freq, else the SQP solve time (:280-284), offset by the previous simulation time
+// (prev_simulation_time, :352); time_since_timestep accumulates and the horizon shifts once it passes shift_threshold (SHIFT_THRESHOLD = one
+// timestep, include/common/settings.cuh:66-68), `shifted` holding the next shift back until a whole timestep has passed (:297, :343-347).
+// One 4-byte read-back per shifting control update: the tracking error the stage returns (updates that do not shift return the last one).
+//   d_xu_traj, d_eePos_traj, traj_steps   the precomputed plan simulateMPC was given: traj_steps rows of state_size + control_size / of 6
+//   simulation_period_us                  > 0: that constant period (CONST_UPDATE_FREQ); 0: the SQP solve time; < 0: by stages<T>().const_update_freq
+//   max_control_updates                   > 0: `done` after that many updates (a demo's bound); 0: only when the plan is used up (:252)
+//   xu_fill_lead                          0: the reference's source row of the xu tail (:316); knot_points - 1: the row its goal fill uses
+// Needs an mpcg_plant in stages<T>().dynmem (use_mpcg_generate_kkt).
+template <typename T>
+inline void use_mpcg_simulate_and_shift(const T* d_xu_traj, const T* d_eePos_traj, uint32_t traj_steps, float timestep, double simulation_period_us = -1,
+                                        uint32_t max_control_updates = 0, uint32_t xu_fill_lead = 0, float sim_step = 2e-4f) {
+    static_assert(std::is_same<T, float>::value, "use_mpcg_simulate_and_shift: mpcg_simulate / mpcg_advance_horizon are float entry points");
+    struct sim_state {
+        T* d_xu_old = nullptr;           // the plan the plant runs under: the previous update's d_xu (:185-192, :291)
+        float* d_buf = nullptr;          // eePos[3], tracking error, traj_offset, done: 24 bytes that live as long as the process
+        double prev_simulation_time = 0, time_since_timestep = 0;
+        bool shifted = false;
+        uint32_t traj_offset = 0, updates = 0;
+        T tracking_error = 0;
+    };
+    auto s = std::make_shared<sim_state>();
+    auto& st = stages<T>();
+    st.simulate_and_shift = [=](uint32_t state_size, uint32_t control_size, uint32_t knot_points, T* d_xs, T* d_xu, T* d_lambda, T* d_eePos_goal,
+                                double sqp_solve_time_us, bool& done) -> T {
+        mpcg_handle* h = mpcg_compat::handle_for(state_size, knot_points);
+        const mpcg_plant* plant = static_cast<const mpcg_plant*>(stages<T>().dynmem);
+        const size_t traj_len = (size_t)(state_size + control_size) * knot_points - control_size;
+        if (!s->d_buf) {
+            if (hipMalloc(reinterpret_cast<void**>(&s->d_buf), 6 * sizeof(float)) != hipSuccess || hipMemset(s->d_buf, 0, 6 * sizeof(float)) != hipSuccess ||
+                hipMalloc(reinterpret_cast<void**>(&s->d_xu_old), traj_len * sizeof(T)) != hipSuccess ||
+                hipMemcpy(s->d_xu_old, d_xu_traj, traj_len * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess)      // (:192)
+                mpcg_compat::die("use_mpcg_simulate_and_shift: hipMalloc", h);
+        }
+        float *d_eePos = s->d_buf, *d_err = s->d_buf + 3;
+        int32_t *d_offset = reinterpret_cast<int32_t*>(s->d_buf + 4), *d_done = reinterpret_cast<int32_t*>(s->d_buf + 5);
+        const double period = simulation_period_us < 0 ? (stages<T>().const_update_freq ? (double)SIMULATION_PERIOD : 0.0) : simulation_period_us;
+        const double simulation_time = period > 0 ? period : sqp_solve_time_us;                                       // (:280-284)
+        if (mpcg_simulate(h, plant, control_size, d_xs, s->d_xu_old, timestep, s->prev_simulation_time, simulation_time, sim_step, d_eePos, 1,
+                          /*stream*/ nullptr) != MPCG_OK)
+            mpcg_compat::die("simple_simulate", h);                                                                   // (:288)
+        if (hipMemcpyAsync(s->d_xu_old, d_xu, traj_len * sizeof(T), hipMemcpyDeviceToDevice, nullptr) != hipSuccess)  // (:291)
+            mpcg_compat::die("use_mpcg_simulate_and_shift: hipMemcpy", h);
+        s->time_since_timestep += simulation_time * 1e-6;
+        const T shift_threshold = 1 * timestep;                                                                      // SHIFT_THRESHOLD
+        const bool shift = !s->shifted && s->time_since_timestep > shift_threshold;                                   // (:297)
+        if (mpcg_advance_horizon(h, control_size, shift ? 1 : 0, d_xu, d_lambda, d_eePos_goal, d_xs, d_eePos, d_xu_traj, d_eePos_traj, traj_steps, 0,
+                                 xu_fill_lead, d_offset, d_done, d_err, 1, nullptr) != MPCG_OK)
+            mpcg_compat::die("just_shift", h);                                                                        // (:300-348)
+        if (shift) {
+            if (hipMemcpy(&s->tracking_error, d_err, sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) mpcg_compat::die("use_mpcg_simulate_and_shift: hipMemcpy", h);
+            ++s->traj_offset;
+            s->shifted = true;
+        }
+        if (s->time_since_timestep > timestep) {                                                                      // (:343-347)
+            s->shifted = false;
+            s->time_since_timestep = std::fmod(s->time_since_timestep, (double)timestep);
+        }
+        s->prev_simulation_time = simulation_time;                                                                    // (:352)
+        ++s->updates;
+        done = s->traj_offset >= traj_steps || (max_control_updates && s->updates >= max_control_updates);            // (:252)
+        return s->tracking_error;
     };
 }
 #endif

@@ -1,9 +1,9 @@
 // include/mpcsim.cuh (shim) — simulateMPC with the reference's name, argument list and return tuple (reference
 // include/mpcsim.cuh:146-150, :421-425) and the reference's compile-time solver switch (:21-25): LINSYS_SOLVE == 1 ->
-// sqpSolvePcg (this repo's include/pcg/sqp.cuh), otherwise sqpSolveQdldl (include/qdldl/sqp.cuh).  The MPC loop body
-// that is outside this library's scope — plant simulation, tracking error, horizon shift (:288-341) — is the
-// simulate_and_shift plug point of mpcgpu_compat/sqp_stages.cuh.  lambda is owned here and warm-starts every SQP call
-// (:186, :190, :267), as in the reference.
+// sqpSolvePcg (this repo's include/pcg/sqp.cuh), otherwise sqpSolveQdldl (include/qdldl/sqp.cuh).  The rest of the MPC loop
+// body — plant simulation, tracking error, horizon shift (:288-348) — is the simulate_and_shift plug point of
+// mpcgpu_compat/sqp_stages.cuh; the library's own stage for it is use_mpcg_simulate_and_shift (mpcg_simulate +
+// mpcg_advance_horizon).  lambda is owned here and warm-starts every SQP call (:186, :190, :267), as in the reference.
 #pragma once
 #include <cstdint>
 #include <string>

@@ -21,6 +21,7 @@ MPCG_PRECOND_JACOBI = 1
 MPCG_PRECOND_SS = 3
 MPCG_MAX_STEP_SIZES = 16
 MPCG_STEP_FROZEN = -2
+MPCG_SIM_MAX_SUBSTEPS = 65536
 
 # every symbol include/mpcg.h declares: (name, restype, argtypes)
 _f32p = C.c_void_p   # device pointers travel as integers
@@ -71,6 +72,10 @@ SYMBOLS = {
     "mpcg_line_search_step_rho": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
                                             C.c_uint32, C.c_void_p]),
+    "mpcg_simulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_float,
+                                C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_advance_horizon": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_ldl_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
     "mpcg_ldl_destroy": (C.c_int, [C.c_void_p]),
     "mpcg_ldl_pattern": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),

@@ -29,6 +29,7 @@ MULTI_BIN = _ex("multi_gpu_pcg")
 UTILS_BIN = _ex("bd_utils_probe")
 SQP_BATCHED_BIN = _ex("sqp_batched_iiwa")
 LINE_SEARCH_STAGE_BIN = _ex("sqp_line_search_stage")
+MPC_CLOSED_LOOP_BIN = _ex("mpc_closed_loop")
 
 
 def sources():
@@ -146,6 +147,12 @@ def build_line_search_stage(force: bool = False, verbose: bool = False) -> str:
     """sqpSolvePcg over the shim headers with the library's KKT and line-search stages registered (use_mpcg_line_search)."""
     _build_bins([LINE_SEARCH_STAGE_BIN], force, verbose)
     return LINE_SEARCH_STAGE_BIN
+
+
+def build_mpc_closed_loop(force: bool = False, verbose: bool = False) -> str:
+    """simulateMPC over the shim headers with all three library stages (use_mpcg_simulate_and_shift), and a batched MPC run over the C ABI."""
+    _build_bins([MPC_CLOSED_LOOP_BIN], force, verbose)
+    return MPC_CLOSED_LOOP_BIN
 
 
 def build_all(force: bool = False, verbose: bool = False) -> str:

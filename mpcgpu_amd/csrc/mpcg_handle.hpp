@@ -3,7 +3,8 @@
 //   mpcg_pcg.hip        handle / options / the PCG launch policy and entry points (pcg_*.hip.h kernels)
 //   mpcg_producers.hip  Schur + preconditioner formation, dz recovery, CSR emitter, block-tridiagonal direct solve (schur_*.hip.h, block_solve.hip.h;
 //                       any other (state_size, control_size) than 14 x 7: schur_generic.hip.h)
-//   mpcg_plant.hip      the robot as data + KKT block assembly (kkt_plant.hip.h), merit function + line-search step (merit_plant.hip.h)
+//   mpcg_plant.hip      the robot as data + KKT block assembly (kkt_plant.hip.h), merit function + line-search step (merit_plant.hip.h),
+//                       plant simulation + horizon shift (sim_plant.hip.h)
 //   mpcg_ldl.hip        the host LDL^T twin of the reference's QDLDL path (ldl_host.hpp)
 // Every kernel header is included by exactly one of them (their non-template kernels have external linkage).
 #pragma once

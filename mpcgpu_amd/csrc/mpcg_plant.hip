@@ -1,10 +1,11 @@
 // mpcg_plant.hip — C ABI (include/mpcg.h) of the producer of the path's inputs: the robot as data (mpcg_plant) and the KKT block assembly
 // mpcg_generate_kkt over the gfx950 kernel in kkt_plant.hip.h; the stage behind dz — mpcg_compute_merit and
-// mpcg_line_search_step over merit_plant.hip.h.
+// mpcg_line_search_step over merit_plant.hip.h; the step between two SQP solves — mpcg_simulate and mpcg_advance_horizon over sim_plant.hip.h.
 #include <cmath>
 #include "mpcg_handle.hpp"
 #include "kkt_plant.hip.h"
 #include "merit_plant.hip.h"
+#include "sim_plant.hip.h"
 
 using namespace mpcg;
 
@@ -313,6 +314,59 @@ int mpcg_line_search_step_rho(mpcg_handle* h, uint32_t control_size, const float
     StepRhoArgs r{};
     r.rho = d_rho; r.drho = d_drho; r.done = d_done; r.factor = rho_factor; r.rho_min = rho_min; r.rho_max = rho_max; r.rho_reset = rho_reset;
     return line_search_step_impl(h, "mpcg_line_search_step_rho", control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, &r, batch, stream);
+}
+
+// ---- plant simulation and horizon shift: the step between two SQP solves (sim_plant.hip.h) ----
+int mpcg_simulate(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float* d_xs, const float* d_xu, double timestep, double time_offset_us,
+                  double sim_time_us, float sim_step, float* d_eePos, uint32_t batch, void* stream) {
+    static_assert(SIM_MAX_SUBSTEPS == MPCG_SIM_MAX_SUBSTEPS, "the cap of the header");
+    if (!h || !plant) return MPCG_ERR_INVALID;
+    if (!d_xs || !d_xu) return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: null device pointer");
+    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_simulate: state_size 14 / control_size 7 (IIWA-14) only");
+    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: plant and handle live on different devices");
+    if (!std::isfinite(timestep) || !std::isfinite(time_offset_us) || !std::isfinite(sim_time_us) || !std::isfinite(sim_step))
+        return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: timestep, time_offset_us, sim_time_us and sim_step must be finite");
+    if (!(sim_step > 0.f) || !(timestep > 0.0) || time_offset_us < 0.0 || sim_time_us < 0.0)
+        return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: needs sim_step > 0, timestep > 0, time_offset_us >= 0 and sim_time_us >= 0");
+    // the schedule of simple_simulate (include/common/integrator.cuh:301-322), in double
+    const double ss = (double)sim_step, toff = time_offset_us * 1e-6, sim = sim_time_us * 1e-6;
+    const double full = sim / ss;
+    if (!(full < (double)SIM_MAX_SUBSTEPS + 1.0)) return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: more than 65536 substeps (MPCG_SIM_MAX_SUBSTEPS) in one call");
+    if (batch == 0) return MPCG_OK;
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: batch exceeds max_batch");
+    HIP_TRY(h, hipSetDevice(h->device));
+    SimArgs a;
+    a.plant = plant->d; a.xs = d_xs; a.xu = d_xu; a.eePos = d_eePos;
+    a.N = (int)h->N; a.batch = (int)batch;
+    a.S = (unsigned)full; a.ss = ss; a.toff = toff; a.timestep = timestep;
+    a.rem = (double)(float)fmod(sim, ss);
+    hipLaunchKernelGGL(simulate_kernel, dim3((batch + KKT_ITEMS - 1) / KKT_ITEMS), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
+
+int mpcg_advance_horizon(mpcg_handle* h, uint32_t control_size, uint32_t shift, float* d_xu, float* d_lambda, float* d_eePos_goal, const float* d_xs,
+                         const float* d_eePos, const float* d_xu_traj, const float* d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride,
+                         uint32_t xu_fill_lead, int32_t* d_traj_offset, int32_t* d_done, float* d_tracking_error, uint32_t batch, void* stream) {
+    if (!h) return MPCG_ERR_INVALID;
+    if (shift > 1) return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: shift must be 0 or 1");
+    if (!d_xu || !d_xs) return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: null device pointer");
+    if (shift && !d_eePos) return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: shift = 1 needs d_eePos (the end-effector position mpcg_simulate wrote)");
+    if (shift && (!d_lambda || !d_eePos_goal || !d_xu_traj || !d_eePos_traj || !d_traj_offset || !d_done || !d_tracking_error))
+        return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: null device pointer (shift = 1 needs every array)");
+    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_advance_horizon: state_size 14 / control_size 7 (IIWA-14) only");
+    if (shift && (traj_steps == 0 || xu_fill_lead > h->N - 1 || (traj_batch_stride != 0 && traj_batch_stride < traj_steps)))
+        return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: needs traj_steps >= 1, xu_fill_lead <= knot_points - 1 and traj_batch_stride 0 or >= traj_steps");
+    if (batch == 0) return MPCG_OK;
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: batch exceeds max_batch");
+    HIP_TRY(h, hipSetDevice(h->device));
+    AdvanceArgs a;
+    a.xu = d_xu; a.lambda = d_lambda; a.goal = d_eePos_goal; a.xs = d_xs; a.eePos = d_eePos; a.xu_traj = d_xu_traj; a.goal_traj = d_eePos_traj;
+    a.traj_offset = d_traj_offset; a.done = d_done; a.tracking_error = d_tracking_error;
+    a.n = h->n; a.m = control_size; a.N = h->N; a.traj_steps = traj_steps; a.traj_stride = traj_batch_stride; a.lead = xu_fill_lead; a.shift = shift;
+    hipLaunchKernelGGL(advance_horizon_kernel, dim3(batch), dim3(ADV_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,240 @@
+// sim_plant.hip.h — the step between two SQP solves of the MPC loop, batched: the HIP twin of simple_simulate (reference
+// include/common/integrator.cuh:295-325: sim_time / 2e-4 launches of one 32-thread block and a remainder launch) as ONE launch for the whole batch and
+// all substeps, and of the tracking error, just_shift, the tail fills and the start-state copy of simulateMPC (include/mpcsim.cuh:300-348: one
+// cudaMemcpy per knot) as a second, dynamics-free kernel.
+//
+// simulate_kernel.  A substep is the explicit Euler step of the KKT kernel's integrator, q += dt qd, qd += dt qdd (both from the old values), qdd =
+// Minv (u - bias) without gravity, so the mapping is merit_points_kernel's: a 16-lane group per trajectory, four trajectories per wavefront; lanes
+// 0..6 the inertia-matrix columns and lane 7 the bias through rnea<double>, then lanes 0..6 the Cholesky solve (plant_qdd_lane: the merit kernel's
+// arithmetic).  The substeps are a loop INSIDE the kernel: q, qd and sin / cos wait in the item record in LDS between them.  The schedule is the reference's,
+// evaluated in IEEE double with one rounding per operation (no contraction: __dmul_rn / __dadd_rn / __ddiv_rn):
+//     S = (uint32)(sim / ss) full substeps of dt = ss (host);  substep s applies u of knot idx_s = (uint32)((toff + s ss) / timestep);
+//     then one substep of dt = (float)fmod(sim, ss) with the control of the LAST full substep — the reference does not recompute the index there
+//     (integrator.cuh:322-324) — or of (uint32)(toff / timestep) if S = 0.  A substep is gated on its NUMBER, never on accumulated time.
+// Two deliberate departures from the reference:
+//   * the state is carried in float64 across the substeps of a call and rounded to float ONCE, on store (the reference rounds after every substep:
+//     its T is float); the inputs are read as float and widened, as in the merit kernel;
+//   * a control index beyond the last control, idx > N - 2, is clamped to N - 2 (the reference reads past its buffer there).
+// A remainder of exactly 0 is not run (x + 0 f = x): sim_time 0 leaves the state as it is, bit for bit.
+// The pose sweeps (lanes 8..10) run ONCE, on the final state, and only when an end-effector output is asked for.  A group without a trajectory
+// recomputes the last one and writes nothing; no atomics; a trajectory's arithmetic depends on nothing but that trajectory.
+// LDS per wavefront: merit_points_kernel's (4 x 840 B item records + 4 x 11 recursion records of 296 B) = 16,384 B.
+//
+// advance_horizon_kernel.  One workgroup per trajectory; every value that moves is LOADED, then a barrier, then stored (the source and destination
+// regions of a shift overlap by one knot).  See include/mpcg.h for the order of operations.
+#pragma once
+#include "merit_plant.hip.h"
+#pragma clang fp contract(fast)
+
+namespace mpcg {
+
+constexpr unsigned SIM_MAX_SUBSTEPS = 65536;     // MPCG_SIM_MAX_SUBSTEPS
+
+// Lane l < PJ of a group, after round 0 (records of lanes 0..6 hold the inertia-matrix columns, lane 7's the bias): qdd_l = Minv_l . (u - bias) through the
+// Cholesky solve of the symmetrised M, redundantly factorised per lane.  This is merit_points_kernel's block (merit_plant.hip.h), statement for
+// statement.  It is restated here and not shared: with the block lifted into this function merit_points_kernel compiled to different instructions
+// (1,729 -> 1,697, tools/_prof/diff_kernels.py), and no existing kernel may change.
+__device__ __forceinline__ double plant_qdd_lane(KktLds<double>::vr* recs, KktLds<double>::item* I, const int l) {
+    typedef double R;
+    auto rec = [&](int j) -> KktLds<double>::vr* { return recs + j * RN_ROWS; };
+    R qdd = 0.0;
+    R Lm[PJ][PJ], rd[PJ];
+#pragma unroll
+    for (int i = 0; i < PJ; ++i)
+#pragma unroll
+        for (int jj = 0; jj <= i; ++jj) {
+            R sv = 0.5 * (rec(jj)[RN_TAU(i)] + rec(i)[RN_TAU(jj)]);
+#pragma unroll
+            for (int t = 0; t < jj; ++t) sv -= Lm[i][t] * Lm[jj][t];
+            if (i == jj) {
+                R y = __builtin_amdgcn_rsq(sv);
+                y = __builtin_elementwise_fma(y * 0.5, __builtin_elementwise_fma(-sv * y, y, 1.0), y);
+                y = __builtin_elementwise_fma(y * 0.5, __builtin_elementwise_fma(-sv * y, y, 1.0), y);
+                rd[i] = y;
+                Lm[i][i] = sv * y;
+            }
+            else Lm[i][jj] = sv * rd[jj];
+        }
+    R y[PJ];
+#pragma unroll
+    for (int i = 0; i < PJ; ++i) {
+        R sv = (i == l) ? 1.0 : 0.0;
+#pragma unroll
+        for (int t = 0; t < i; ++t) sv -= Lm[i][t] * y[t];
+        y[i] = sv * rd[i];
+    }
+#pragma unroll
+    for (int i = PJ - 1; i >= 0; --i) {
+        R sv = y[i];
+#pragma unroll
+        for (int t = i + 1; t < PJ; ++t) sv -= Lm[t][i] * y[t];
+        y[i] = sv * rd[i];
+    }
+#pragma unroll
+    for (int i = 0; i < PJ; ++i) qdd += y[i] * (I->U[i] - rec(PJ)[RN_TAU(i)]);      // bias_i = tau_i of lane 7
+    return qdd;
+}
+
+// End-effector position from the three pose sweeps of lanes 8..10 (kkt_plant.hip.h: [W_i ; V_i] = [R e_i ; R (e_i x p)])
+__device__ __forceinline__ void plant_ee_pos(KktLds<double>::vr* recs, double& ee0, double& ee1, double& ee2) {
+    typedef double R;
+    auto rec = [&](int j) -> KktLds<double>::vr* { return recs + j * RN_ROWS; };
+    R W1[3], W2[3], V0[3], V1[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        W1[r] = rec(PJ + 2)[RN_AW + r]; W2[r] = rec(PJ + 3)[RN_AW + r];
+        V0[r] = rec(PJ + 1)[RN_AU + r]; V1[r] = rec(PJ + 2)[RN_AU + r];
+    }
+    ee0 = -(W2[0] * V1[0] + W2[1] * V1[1] + W2[2] * V1[2]);
+    ee1 = W2[0] * V0[0] + W2[1] * V0[1] + W2[2] * V0[2];
+    ee2 = -(W1[0] * V0[0] + W1[1] * V0[1] + W1[2] * V0[2]);
+}
+
+struct SimArgs {
+    const PlantDev* plant;
+    float* xs;                           // [batch][n] in/out
+    const float* xu;                     // [batch][(n+m)N - m]
+    float* eePos;                        // [batch][3] or NULL
+    int N, batch;
+    unsigned S;                          // full substeps
+    double ss, toff, timestep;           // substep, time offset, knot spacing [s]
+    double rem;                          // the remainder substep, (double)(float)fmod(sim, ss); 0: none
+};
+
+__global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgs a) {
+    typedef double R;
+    typedef KktLds<R>::vr kkt_lds_vd;
+    typedef KktLds<R>::item kkt_lds_item;
+    typedef PlantC<R>::creal creal;
+    constexpr int n = 2 * PJ, m = PJ;
+    __shared__ KktItemLds<R> sI[KKT_ITEMS];
+    __shared__ R sF[KKT_ITEMS][KKT_R0 * RN_ROWS];
+    static_assert(sizeof(KktItemLds<R>) * KKT_ITEMS + sizeof(R) * KKT_ITEMS * KKT_R0 * RN_ROWS <= 16384, "the merit kernel's LDS budget");
+    const int lane = threadIdx.x, gi = lane / KKT_GL, l = lane - gi * KKT_GL;
+    kkt_lds_item* I = (kkt_lds_item*)&sI[gi];
+    kkt_lds_vd* recs = (kkt_lds_vd*)&sF[gi][0];
+    kkt_lds_vd* fl = recs + (l < KKT_R0 ? l : 0) * RN_ROWS;
+    const PlantC<R> P{reinterpret_cast<creal*>(reinterpret_cast<unsigned long long>(a.plant))};
+    const long b0 = (long)blockIdx.x * KKT_ITEMS + gi;
+    const bool live = b0 < a.batch;                          // (a group without a trajectory recomputes the last one — it shares this wavefront — and writes nothing)
+    const size_t b = live ? (size_t)b0 : (size_t)a.batch - 1;
+    const float* xu = a.xu + b * ((size_t)(n + m) * a.N - m);
+    float* xs = a.xs + b * n;
+    const unsigned last = (unsigned)a.N - 2;                 // the last knot that has a control
+    auto knot_of = [&](double t) -> unsigned {               // (uint32)(t / timestep), clamped to the last control; one rounding per operation
+        const double v = __ddiv_rn(t, a.timestep);
+        return v >= (double)last ? last : (unsigned)v;
+    };
+    if (l < n) I->Xq[l] = (double)xs[l];
+    unsigned idx = knot_of(a.toff);
+    const unsigned steps = a.S + (a.rem != 0.0 ? 1u : 0u), rounds = steps + (a.eePos ? 1u : 0u);
+    for (unsigned k = 0; k < rounds; ++k) {
+        const bool step = k < steps;                         // the last round of a call with an end-effector output: the pose sweeps on the final state
+        double dt = a.rem;
+        if (k < a.S) { idx = knot_of(__dadd_rn(a.toff, __dmul_rn((double)k, a.ss))); dt = a.ss; }
+        if (l < m) {
+            if (step) I->U[l] = (double)xu[(size_t)idx * (n + m) + n + l];
+            double sn, cs;
+            kkt_sincos(I->Xq[l], sn, cs);
+            I->Sc[0][l] = sn;
+            I->Sc[1][l] = cs;
+        }
+        __syncthreads();
+        // ---- round 0 of the KKT kernel: lanes 0..6 ID(q, 0, e_l), lane 7 ID(q, qd, 0); in the pose round lanes 8..10 instead ----
+        if (l < KKT_R0 && (step ? l <= PJ : l > PJ)) {
+            R a6w[3], a6u[3];
+            RneaTask<R> t;
+            t.sj = -1; t.pj = -1; t.qdscale = (l == PJ) ? 1.0 : 0.0; t.knot_qdd = false; t.unit = l < PJ ? l : -1; t.base = l > PJ ? l - PJ - 1 : -1;
+            rnea<R>(P, fl, I, t, a6w, a6u);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) { fl[RN_AW + r] = a6w[r]; fl[RN_AU + r] = a6u[r]; }
+        }
+        __syncthreads();
+        if (step && l < PJ) {                                // lanes 0..6: qdd_l, then joint l's Euler step from the old values
+            const R qdd = plant_qdd_lane(recs, I, l);
+            const R q = I->Xq[l], qd = I->Xq[PJ + l];
+            I->Xq[l] = q + dt * qd;
+            I->Xq[PJ + l] = qd + dt * qdd;
+        }
+        __syncthreads();
+    }
+    if (a.eePos && live && l < 3) {
+        R ee0, ee1, ee2;
+        plant_ee_pos(recs, ee0, ee1, ee2);
+        a.eePos[b * 3 + l] = (float)(l == 0 ? ee0 : (l == 1 ? ee1 : ee2));
+    }
+    if (live && l < n) xs[l] = (float)I->Xq[l];             // the one rounding of the call
+}
+
+struct AdvanceArgs {
+    float* xu; float* lambda; float* goal;                  // [batch][(n+m)N - m], [batch][n N], [batch][6 N] in/out
+    const float* xs;                                        // [batch][n]
+    const float* eePos;                                     // [batch][3] (shift = 1)
+    const float* xu_traj; const float* goal_traj;           // the plan: traj_steps rows of (n + m) / 6
+    int32_t* traj_offset; int32_t* done;                    // [batch] in/out
+    float* tracking_error;                                  // [batch] out
+    uint32_t n, m, N, traj_steps, traj_stride, lead, shift;
+};
+
+// Every element of the three iterates gets its new value from ONE source element (new_xu, new_goal, lambda[e + n]).  A shift moves values DOWN, so
+// a sweep in ascending chunks of ADV_THREADS x ADV_KEEP elements — load the chunk's sources into registers, barrier, store, barrier — never reads
+// an element that was already overwritten: what a store destroys is the source of an element of the same or an earlier chunk.
+constexpr int ADV_THREADS = 256, ADV_KEEP = 8;
+template <class F>
+__device__ __forceinline__ void advance_sweep(float* dst, const size_t count, F&& value) {
+    float v[ADV_KEEP];
+    for (size_t c0 = 0; c0 < count; c0 += (size_t)ADV_THREADS * ADV_KEEP) {
+#pragma unroll
+        for (int i = 0; i < ADV_KEEP; ++i) { const size_t e = c0 + (size_t)i * ADV_THREADS + threadIdx.x; v[i] = e < count ? value(e) : 0.f; }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < ADV_KEEP; ++i) { const size_t e = c0 + (size_t)i * ADV_THREADS + threadIdx.x; if (e < count) dst[e] = v[i]; }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(ADV_THREADS) void advance_horizon_kernel(AdvanceArgs a) {
+    const size_t b = blockIdx.x;
+    const uint32_t n = a.n, m = a.m, N = a.N, nm = n + m, t = threadIdx.x;
+    const size_t len = (size_t)nm * N - m;
+    float* xu = a.xu + b * len;
+    const float* xs = a.xs + b * n;
+    if (a.done && a.done[b] != 0) return;                    // frozen (uniform; done is written behind the barriers below)
+    if (!a.shift) {                                          // mpcsim.cuh:348 alone
+        for (uint32_t e = t; e < n; e += ADV_THREADS) xu[e] = xs[e];
+        return;
+    }
+    float* lam = a.lambda + b * (size_t)n * N;
+    float* goal = a.goal + b * (size_t)6 * N;
+    const float* xut = a.xu_traj + b * (size_t)a.traj_stride * nm;
+    const float* gt = a.goal_traj + b * (size_t)a.traj_stride * 6;
+    const uint32_t off = (uint32_t)a.traj_offset[b] + 1;     // (:310; a value that is no row of the plan takes the else branch and reads the plan's last row)
+    const bool inside = off >= 1 && (uint64_t)off + N < a.traj_steps;    // (:314, :327)
+    float err = 0.f;
+    if (t == 0) {                                            // (:303-306) against knot 0 of the unshifted goals
+        const float* ee = a.eePos + b * 3;
+        err = __fadd_rn(__fadd_rn(fabsf(__fsub_rn(ee[0], goal[0])), fabsf(__fsub_rn(ee[1], goal[1]))), fabsf(__fsub_rn(ee[2], goal[2])));
+    }
+    // xu: x_0 from xs (:348, the last write of the reference); everything else below the last n + m elements from one knot up (just_shift: knots
+    // 0..N-3 whole, x_{N-2} <- x_{N-1} without a control, integrator.cuh:258-263); the last n + m elements u_{N-2}, x_{N-1} from the plan (:316) or
+    // the final plan position with zero velocity and zero control (:320-322).
+    advance_sweep(xu, len, [&](size_t e) -> float {
+        if (e < n) return xs[e];
+        if (e + nm < len) return xu[e + nm];
+        const uint32_t r = (uint32_t)(e + nm - len);         // 0..m-1: u_{N-2}; m..m+n-1: x_{N-1}
+        if (inside) return xut[(size_t)nm * (off + a.lead) - m + r];
+        return r >= m && r - m < n / 2 ? xut[(size_t)(a.traj_steps - 1) * nm + (r - m)] : 0.f;
+    });
+    advance_sweep(goal, (size_t)6 * N, [&](size_t e) -> float {      // (:326-334)
+        if (e + 6 < (size_t)6 * N) return goal[e + 6];
+        return gt[(size_t)(inside ? off + N - 1 : a.traj_steps - 1) * 6 + (e + 6 - (size_t)6 * N)];
+    });
+    advance_sweep(lam, (size_t)n * (N - 1), [&](size_t e) -> float { return lam[e + n]; });      // the last knot of lambda keeps its value (:337-338)
+    if (t == 0) {
+        a.tracking_error[b] = err;
+        a.traj_offset[b] = (int32_t)off;
+        if (off >= a.traj_steps) a.done[b] = 1;              // (:252)
+    }
+}
+
+}  // namespace mpcg

@@ -121,7 +121,7 @@ class QdldlSolver:
 class PcgSolver:
     """One handle per (device, state_size, knot_points).  `solve` is the batched hot path,
     `solve_ref` the reference's single-trajectory 12-argument launch.  `control_size` is the default of
-    `form_schur` / `compute_dz` / `generate_kkt` / `compute_merit` / `line_search_step` (None: 7, the IIWA-14's)."""
+    `form_schur` / `compute_dz` / `generate_kkt` / `compute_merit` / `line_search_step` / `simulate` / `advance_horizon` (None: 7, the IIWA-14's)."""
 
     def __init__(self, knot_points: int, max_batch: int = 1, state_size: int = STATE_SIZE, device: int | None = None,
                  control_size: int | None = None):
@@ -406,6 +406,56 @@ class PcgSolver:
                                                        _ptr(rho), _ptr(drho), _ptr(done), float(rho_factor), float(rho_min), float(rho_max),
                                                        float(rho_reset), B, _stream()))
         return step
+
+    def simulate(self, plant: "Plant", xs, xu, timestep: float, time_offset_us: float, sim_time_us: float, sim_step: float = 2e-4,
+                 eePos=None, control_size: int | None = None):
+        """simple_simulate (include/common/integrator.cuh:295-325), batched, one launch for all substeps: the plant states xs [B, n] are
+        integrated in place over sim_time_us under the controls of the plan xu [B, (n+m)N - m], starting time_offset_us into it.
+        eePos (optional, [B, 3]) receives the end-effector position of the new state — what advance_horizon(shift=1) takes."""
+        B = xs.shape[0] if xs.dim() > 1 else 1
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        self._chk(xs, B * n, torch.float32, "xs")
+        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
+        if eePos is not None:
+            self._chk(eePos, B * 3, torch.float32, "eePos")
+        self._check(self.lib.mpcg_simulate(self._h, plant._p, m, _ptr(xs), _ptr(xu), float(timestep), float(time_offset_us), float(sim_time_us),
+                                           float(sim_step), _ptr(eePos), B, _stream()))
+        return xs
+
+    def advance_horizon(self, shift: bool, xu, xs, lam=None, eePos_goal=None, eePos=None, xu_traj=None, eePos_traj=None, traj_offset=None,
+                        done=None, tracking_error=None, xu_fill_lead: int = 0, control_size: int | None = None):
+        """The rest of a control update (include/mpcsim.cuh:300-348) per trajectory.  shift=False: xu[:, :n] = xs only.  shift=True: tracking error,
+        traj_offset += 1, the one-knot shift of xu / eePos_goal / lam with their tails refilled from the plan, then the start-state copy; done
+        (int32 [B]) is set when a trajectory has used up its plan, and a trajectory with done != 0 on entry is frozen.
+        The plan: xu_traj [T, n+m] and eePos_traj [T, 6] shared by the batch, or [B, T, n+m] and [B, T, 6] per trajectory.
+        xu_fill_lead: 0 = the reference's source row of the xu tail, N - 1 = the row its goal fill uses."""
+        B = xs.shape[0] if xs.dim() > 1 else 1
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
+        self._chk(xs, B * n, torch.float32, "xs")
+        T = stride = 0
+        if shift:
+            for t, name in ((lam, "lam"), (eePos_goal, "eePos_goal"), (xu_traj, "xu_traj"), (eePos_traj, "eePos_traj"), (traj_offset, "traj_offset"),
+                            (done, "done"), (tracking_error, "tracking_error")):
+                if t is None:
+                    raise ValueError(f"advance_horizon(shift=True) needs {name}")
+            per_traj = xu_traj.dim() == 3
+            T = int(xu_traj.shape[-2])
+            stride = T if per_traj else 0
+            self._chk(lam, B * n * N, torch.float32, "lam")
+            self._chk(eePos_goal, B * 6 * N, torch.float32, "eePos_goal")
+            self._chk(xu_traj, (B if per_traj else 1) * T * (n + m), torch.float32, "xu_traj")
+            self._chk(eePos_traj, (B if per_traj else 1) * T * 6, torch.float32, "eePos_traj")
+            self._chk(traj_offset, B, torch.int32, "traj_offset")
+            self._chk(tracking_error, B, torch.float32, "tracking_error")
+            if eePos is not None:
+                self._chk(eePos, B * 3, torch.float32, "eePos")
+        if done is not None:
+            self._chk(done, B, torch.int32, "done")
+        self._check(self.lib.mpcg_advance_horizon(self._h, m, 1 if shift else 0, _ptr(xu), _ptr(lam), _ptr(eePos_goal), _ptr(xs), _ptr(eePos),
+                                                  _ptr(xu_traj), _ptr(eePos_traj), T, stride, int(xu_fill_lead), _ptr(traj_offset), _ptr(done),
+                                                  _ptr(tracking_error), B, _stream()))
+        return xu
 
     def csr_nnz(self) -> int:
         """nnz of the lower triangle (include/qdldl/sqp.cuh:148)."""
