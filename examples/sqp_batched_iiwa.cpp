@@ -7,10 +7,11 @@
 // mpcg_form_schur call).  With it every trajectory carries its own rho, drho and "finished" flag in device memory: mpcg_form_schur_rhov reads the
 // rho vector and mpcg_line_search_step_rho applies the reference's adaptation (sqp.cuh:304-320: a failed line search multiplies drho and rho by
 // 1.2, a success divides them, rho > 10 gives the trajectory up and resets rho) — still without a synchronisation inside an iteration; the JSON line
-// then also carries "rho_final", "drho_final" and "done" per trajectory.
+// then also carries "rho_final", "drho_final" and "done" per trajectory.  --merit-f32 sets option "merit_f32" = 1 on the handle: every mpcg_compute_merit
+// of the run evaluates its point merits in packed float (the reference's own arithmetic; merits within 1e-5 max(1, |merit|) of the default's).
 // Prints one JSON line; exits 0 only if every trajectory's merit went down.
 //   hipcc --offload-arch=gfx950 -O2 -Iinclude examples/sqp_batched_iiwa.cpp -Lmpcgpu_amd -lmpcg_hip
-//   sqp_batched_iiwa [--batch 8] [--knots 32] [--iters 4] [--mu 10] [--rho 1e-3] [--adapt-rho]
+//   sqp_batched_iiwa [--batch 8] [--knots 32] [--iters 4] [--mu 10] [--rho 1e-3] [--adapt-rho] [--merit-f32]
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -59,9 +60,10 @@ static T* dalloc(size_t count) {
 int main(int argc, char** argv) {
     int B = 8, N = 32, K = 4;
     float mu = 10.f, rho = 1e-3f;
-    bool adapt = false;
+    bool adapt = false, merit_f32 = false;
     for (int i = 1; i < argc; i += 2) {
         if (!strcmp(argv[i], "--adapt-rho")) { adapt = true; --i; continue; }
+        if (!strcmp(argv[i], "--merit-f32")) { merit_f32 = true; --i; continue; }
         if (i + 1 >= argc) break;
         if (!strcmp(argv[i], "--batch")) B = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--knots")) N = atoi(argv[i + 1]);
@@ -95,6 +97,7 @@ int main(int argc, char** argv) {
     mpcg_handle* h = nullptr;
     mpcg_plant* plant = nullptr;
     if (mpcg_create(&h, -1, n, (uint32_t)N, (uint32_t)B) != MPCG_OK) { fprintf(stderr, "mpcg_create: %s\n", mpcg_last_error(nullptr)); return 1; }
+    if (merit_f32) MPCG_OK_OR_DIE(h, mpcg_set_option(h, "merit_f32", 1));
     if (mpcg_plant_create_iiwa14(&plant, -1) != MPCG_OK) { fprintf(stderr, "mpcg_plant_create_iiwa14: %s\n", mpcg_last_error(nullptr)); return 1; }
 
     const size_t nn = n * n, mm = m * m, nm = n * m;

@@ -342,7 +342,14 @@ int mpcg_generate_kkt(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_
  *   d_merit      [batch][num_steps] floats
  * The trial iterate is formed in float with ONE rounding, fmaf(step, dz, xu) — with step 0 it is xu exactly — and everything behind it runs
  * in float64 (csrc/merit_plant.hip.h: the KKT kernel's round 0, a 16-lane group per (trajectory, step size, knot)); option "kkt_f32" does not
- * affect it.  Every sum has a fixed order (no atomics — the reference's atomicAdd is not reproduced): results are bitwise reproducible and a
+ * affect it — the merit has an option of its own: "merit_f32" = 1 (default 0) evaluates every point merit in PACKED FLOAT instead
+ * (csrc/merit_plant_f32.hip.h: the reference's own arithmetic, merit.cuh with T = float; two items per 16-lane group, the float trial iterate used
+ * as is, float model tables, sine / cosine in double and rounded; the seven lane shares of an item added in float, the knots of a row in
+ * double as before, in the same scratch), for every call of the handle whatever its size.  The option is read when the call is made (a captured
+ * graph keeps the build it was captured with); arguments, errors, the first-call allocation and mpcg_line_search_step(_rho) are the same, and
+ * "kkt_f32" and "merit_f32" are independent.  With it a merit is within 1e-5 of the float64 restatement relative to max(1, |merit|) — the tested
+ * limit; a numpy float32 restatement of the formula is within 2.5e-6 on the tests' inputs, the default within 5e-8 —, bitwise reproducible, independent of the batch and of the other step sizes all the same — which items share a
+ * lane group depends on the call, a half's arithmetic does not — and the accepted merit is still the merit of the new iterate bit for bit.  Every sum has a fixed order (no atomics — the reference's atomicAdd is not reproduced): results are bitwise reproducible and a
  * number depends neither on the rest of the batch nor on the other step sizes of the call.  state_size 14 / control_size 7 only
  * (MPCG_ERR_UNSUPPORTED otherwise).  The first call allocates a handle-owned scratch of max_batch x 16 x knot_points doubles (hipMalloc — not
  * stream work: GRAPH CAPTURE above); later calls are pure stream work.
@@ -529,7 +536,8 @@ int mpcg_qdldl_solve_schur(mpcg_handle *h, mpcg_ldl *l, const float *d_val, cons
  *       2e-7, 1.6x faster than the default on throughput-sized calls (0.204 against 0.330 ms per 1024 x 127 knots; a single trajectory: 20 against 16 us —
  *       the default is the one for latency-sized calls), a trajectory's results independent of the rest of the batch; 2 = the same arithmetic with one
  *       knot per lane (8 % faster than the default; differs from 1 by float rounding); 0, the default: float64 inside, results rounded to float on
- *       the way out), "nt_loads" / "spmv_blocks_per_cu" (mpcg_bt_spmv), "spmv_mfma" (the MFMA experiment kernel).
+ *       the way out), "merit_f32" (mpcg_compute_merit: 0, the default: float64 inside; 1: the point merits in packed float, two work items per
+ *       16-lane group — see mpcg_compute_merit; any other value is MPCG_ERR_INVALID; independent of "kkt_f32"), "nt_loads" / "spmv_blocks_per_cu" (mpcg_bt_spmv), "spmv_mfma" (the MFMA experiment kernel).
  * "assume_symmetric" (0 / 1), "symmetry_state" (read-only; 0 unknown, 1 block-symmetric, 2 violated): see BLOCK SYMMETRY above.
  * "reserve_f64" (= 1: allocate the double cluster kernels' buffers now; see GRAPH CAPTURE above).
  * Read-only: "cluster_fixups" (trajectories re-solved by fix-up launches since mpcg_create — each costs 1.5-4.5 ms of spinning; blocking 8-byte

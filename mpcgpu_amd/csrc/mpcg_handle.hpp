@@ -3,7 +3,7 @@
 //   mpcg_pcg.hip        handle / options / the PCG launch policy and entry points (pcg_*.hip.h kernels)
 //   mpcg_producers.hip  Schur + preconditioner formation, dz recovery, CSR emitter, block-tridiagonal direct solve (schur_*.hip.h, block_solve.hip.h;
 //                       any other (state_size, control_size) than 14 x 7: schur_generic.hip.h)
-//   mpcg_plant.hip      the robot as data + KKT block assembly (kkt_plant.hip.h), merit function + line-search step (merit_plant.hip.h),
+//   mpcg_plant.hip      the robot as data + KKT block assembly (kkt_plant.hip.h), merit function + line-search step (merit_plant.hip.h, merit_plant_f32.hip.h),
 //                       plant simulation + horizon shift (sim_plant.hip.h)
 //   mpcg_ldl.hip        the host LDL^T twin of the reference's QDLDL path (ldl_host.hpp)
 // Every kernel header is included by exactly one of them (their non-template kernels have external linkage).
@@ -53,6 +53,7 @@ struct mpcg_handle {
     int schur_chunk = 0;      //   block rows per chunk of the walking kernel: 0 auto (by call size), 1..2048 forced
     int kkt_analytic = 1;     // mpcg_generate_kkt: 1 = analytic gradient recursion of the inverse dynamics (as the reference's GRiD code), 0 = one-sided float64 differences (the checker)
     int kkt_f32 = 0;          // mpcg_generate_kkt: 1 = the analytic kernel in float arithmetic (linsys_t's own, as the reference's GRiD<float>); 0 = float64 inside
+    int merit_f32 = 0;        // mpcg_compute_merit: 1 = the point merits in packed float (merit_plant_f32.hip.h: the reference's own arithmetic, two items per lane group); 0 = float64 inside
     int dz_dpp = 1;           // 1: four-knots-per-wavefront dz recovery (schur_walk.hip.h), 0: the LDS kernel (schur_generic.hip.h)
     int last_schur_chunk = 0; //   what the last mpcg_form_schur used (0: the LDS kernels)
     int producers_generic = 0; // 1: form_schur(_f64), compute_dz(_f64) and block_solve of a (14, 7) call run the run-time-dimension kernels (schur_generic.hip.h) every other shape gets (formation and dz: what "schur_dpp" / "dz_dpp" = 0 run too)

@@ -313,6 +313,10 @@ int mpcg_set_option(mpcg_handle* h, const char* key, int value) {
     if (!strcmp(key, "producers_generic")) { h->producers_generic = value ? 1 : 0; return MPCG_OK; }
     if (!strcmp(key, "kkt_analytic")) { h->kkt_analytic = value ? 1 : 0; return MPCG_OK; }
     if (!strcmp(key, "kkt_f32")) { h->kkt_f32 = value == 2 ? 2 : value ? 1 : 0; return MPCG_OK; }
+    if (!strcmp(key, "merit_f32")) {
+        if (value != 0 && value != 1) return fail(h, MPCG_ERR_INVALID, "merit_f32 must be 0 (float64 inside) or 1 (packed float)");
+        h->merit_f32 = value; return MPCG_OK;
+    }
     if (!strcmp(key, "sched_hint")) { h->sched_hint = value ? 1 : 0; return MPCG_OK; }
     if (!strcmp(key, "cluster")) {
         if (value < -1 || value > 32) return fail(h, MPCG_ERR_INVALID, "cluster must be -1 (auto), 0 (off) or 1..32 workgroups per trajectory");
@@ -351,6 +355,7 @@ int mpcg_get_option(const mpcg_handle* h, const char* key, int* value) {
     if (!strcmp(key, "producers_generic")) { *value = h->producers_generic; return MPCG_OK; }
     if (!strcmp(key, "kkt_analytic")) { *value = h->kkt_analytic; return MPCG_OK; }
     if (!strcmp(key, "kkt_f32")) { *value = h->kkt_f32; return MPCG_OK; }
+    if (!strcmp(key, "merit_f32")) { *value = h->merit_f32; return MPCG_OK; }
     if (!strcmp(key, "sched_hint")) { *value = h->sched_hint; return MPCG_OK; }
     if (!strcmp(key, "spmv_blocks_per_cu")) { *value = h->spmv_blocks_per_cu; return MPCG_OK; }
     if (!strcmp(key, "spmv_mfma")) { *value = h->spmv_mfma; return MPCG_OK; }

@@ -1,10 +1,11 @@
 // mpcg_plant.hip — C ABI (include/mpcg.h) of the producer of the path's inputs: the robot as data (mpcg_plant) and the KKT block assembly
 // mpcg_generate_kkt over the gfx950 kernel in kkt_plant.hip.h; the stage behind dz — mpcg_compute_merit and
-// mpcg_line_search_step over merit_plant.hip.h; the step between two SQP solves — mpcg_simulate and mpcg_advance_horizon over sim_plant.hip.h.
+// mpcg_line_search_step over merit_plant.hip.h (the merit in packed float, "merit_f32": merit_plant_f32.hip.h); the step between two SQP solves — mpcg_simulate and mpcg_advance_horizon over sim_plant.hip.h.
 #include <cmath>
 #include "mpcg_handle.hpp"
 #include "kkt_plant.hip.h"
 #include "merit_plant.hip.h"
+#include "merit_plant_f32.hip.h"
 #include "sim_plant.hip.h"
 
 using namespace mpcg;
@@ -265,6 +266,18 @@ int mpcg_compute_merit(mpcg_handle* h, const mpcg_plant* plant, uint32_t control
     long blocks = ((long)batch * num_steps * h->N + KKT_ITEMS - 1) / KKT_ITEMS;      // one wavefront per KKT_ITEMS (trajectory, step size, knot) items
     const long cap = (long)h->num_cus * 32;
     if (blocks > cap) blocks = cap;
+    if (h->merit_f32) {                           // the reference's own arithmetic (merit.cuh, T = float): two items per lane group in packed float, whatever the size of the call
+        MeritArgsF32 f;
+        f.plant = plant->d32; f.eePos_traj = d_eePos_traj; f.xs = d_xs; f.xu = d_xu; f.dz = d_dz; f.point = h->merit_scratch;
+        f.N = a.N; f.batch = a.batch; f.A = a.A;
+        f.dt = timestep; f.mu = mu; f.qd_cost = qd_cost; f.r_cost = r_cost;
+        memcpy(f.alpha, a.alpha, sizeof(f.alpha));
+        // one wavefront per trip of 2 KKT_ITEMS items (no trip loop: merit_plant_f32.hip.h); at most max_batch x 16 x N / 8 of them, and a handle whose
+        // scratch of max_batch x 16 x N doubles could be allocated stays far below the 2^31 - 1 workgroups a grid dimension holds
+        const long pblocks = ((long)batch * num_steps * h->N + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
+        if (pblocks > 0x7fffffffL) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_merit: batch x num_steps x knot_points exceeds the grid");
+        hipLaunchKernelGGL(merit_points_f32_kernel, dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
+    } else
     hipLaunchKernelGGL(merit_points_kernel, dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
     HIP_TRY(h, hipGetLastError());
     const int rows = (int)(batch * num_steps);
