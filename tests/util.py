@@ -24,26 +24,27 @@ def rel_residual(S_bd, gamma, lam, N):
     return np.linalg.norm(g - Sd @ np.asarray(lam, np.float64)) / np.linalg.norm(g)
 
 
-def fp32_band(orc, S, Pinv, g, lam0, N, K, pc, ref64, trials=4):
+def fp32_band(orc, S, Pinv, g, lam0, N, K, pc, ref64, trials=4, n=14, vec="lam"):
     """Self-calibrating fp32 tolerance for a FIXED iteration count K: the largest distance from the
     float64 iterate reached by the CPU float32 restatement on (a) the same inputs and (b) inputs
     perturbed by one float32 ulp (relative 6e-8 gaussian) — i.e. what rounding-level noise does to
     fp32 CG on this system (cond ~1e5).  Any correct fp32 implementation with a different summation
-    order lands inside a small multiple of this band."""
+    order lands inside a small multiple of this band.  `n`: the state size (tests/generic_pcg_cases.py); `vec`: the vector
+    `ref64` is ("lam", or the "r" / "p" the 12-argument entries return)."""
     S = np.nan_to_num(np.asarray(S, np.float32))
     P = np.nan_to_num(np.asarray(Pinv, np.float32))
     g = np.asarray(g, np.float32)
     lam0 = np.asarray(lam0, np.float32)
-    band = relinf(orc.pcg(S, P, g, lam0, N, K, 0.0, pc)["lam"], ref64)
+    band = relinf(orc.pcg(S, P, g, lam0, N, K, 0.0, pc, n=n)[vec], ref64)
     rng = np.random.default_rng(K * 1000 + N)
     for _ in range(trials):
         Sp = (S.astype(np.float64) * (1 + 6e-8 * rng.standard_normal(S.shape))).astype(np.float32)
         gp = (g.astype(np.float64) * (1 + 6e-8 * rng.standard_normal(g.shape))).astype(np.float32)
-        band = max(band, relinf(orc.pcg(Sp, P, gp, lam0, N, K, 0.0, pc)["lam"], ref64))
+        band = max(band, relinf(orc.pcg(Sp, P, gp, lam0, N, K, 0.0, pc, n=n)[vec], ref64))
     return band
 
 
-def fp32_iters_band(orc, S, Pinv, g, lam0, N, max_iter, tol, pc, trials=8):
+def fp32_iters_band(orc, S, Pinv, g, lam0, N, max_iter, tol, pc, trials=8, n=14):
     """(lo, hi) of the iteration count the CPU float32 restatement needs on the same and on
     1-ulp-perturbed inputs.  With a tolerance exit the crossing iteration of fp32 CG is erratic
     (measured on the N=32 golden system: 174..201 against 172 in float64), so a fixed +-10 % around
@@ -52,12 +53,12 @@ def fp32_iters_band(orc, S, Pinv, g, lam0, N, max_iter, tol, pc, trials=8):
     P = np.nan_to_num(np.asarray(Pinv, np.float32))
     g = np.asarray(g, np.float32)
     lam0 = np.asarray(lam0, np.float32)
-    its = [orc.pcg(S, P, g, lam0, N, max_iter, tol, pc)["iters"]]
+    its = [orc.pcg(S, P, g, lam0, N, max_iter, tol, pc, n=n)["iters"]]
     rng = np.random.default_rng(N + max_iter)
     for _ in range(trials):
         Sp = (S.astype(np.float64) * (1 + 6e-8 * rng.standard_normal(S.shape))).astype(np.float32)
         gp = (g.astype(np.float64) * (1 + 6e-8 * rng.standard_normal(g.shape))).astype(np.float32)
-        its.append(orc.pcg(Sp, P, gp, lam0, N, max_iter, tol, pc)["iters"])
+        its.append(orc.pcg(Sp, P, gp, lam0, N, max_iter, tol, pc, n=n)["iters"])
     return min(its), max(its)
 
 
