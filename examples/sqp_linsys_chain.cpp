@@ -108,15 +108,10 @@ int main(int argc, char** argv) {
     // ---- include/pcg/sqp.cuh:207-259 ----
     form_schur_system<T>(state_size, control_size, knot_points, d_G_dense, d_C_dense, d_g, d_c, d_S, d_Pinv, d_gamma, rho);
     gpuErrchk(hipPeekAtLastError());
-    if (use_direct) {                                                      // the LINSYS_SOLVE == 0 twin, on the GPU
-#ifdef USE_DOUBLES
-        fprintf(stderr, "--direct: mpcg_block_solve is single precision\n");
-        return 2;
-#else
+    if (use_direct) {                                                      // the LINSYS_SOLVE == 0 twin, on the GPU (float or -DUSE_DOUBLES)
         block_solve_schur<T>(state_size, knot_points, d_S, d_gamma, d_lambda);
         pcg_iters = 0;
         pcg_exit = false;
-#endif
     } else {
         gpuErrchk(mpcgLaunchPcg(pcg_kernel, knot_points, PCG_NUM_THREADS, pcgKernelArgs, ppcg_kernel_smem_size));
         gpuErrchk(hipMemcpy(&pcg_iters, d_pcg_iters, sizeof(uint32_t), hipMemcpyDeviceToHost));

@@ -41,7 +41,7 @@
  *     passed as void* (NULL = default stream).  Calls are stream-ordered and never synchronise.
  *   - batched entry points take `batch` independent trajectories stored back to back.
  *   - GRAPH CAPTURE.  Every compute entry point is pure stream work and may be captured into a hipGraph.  What the float PCG entry points need
- *     is allocated by mpcg_create; mpcg_form_schur(_f64), mpcg_block_solve, mpcg_compute_merit and a FORCED "cluster" on a horizon the automatic policy gives to one
+ *     is allocated by mpcg_create; mpcg_form_schur(_f64), mpcg_block_solve(_f64), mpcg_compute_merit and a FORCED "cluster" on a horizon the automatic policy gives to one
  *     CU allocate a handle-owned work buffer at their first call (hipMalloc is not stream work): make that call once outside the capture — a
  *     first call on a capturing stream returns MPCG_ERR_INVALID with a message and leaves the capture intact.  linsys_t = double beyond 32
  *     knots (mpcg_pcg_solve_f64 / _ref_f64: cluster kernels with a queue + flags buffer and a double-sized copy of lambda0): mpcg_create makes
@@ -106,7 +106,7 @@ const char *mpcg_build_info(void);
  * the pinned word of the symmetry latch, the copy of d_lambda a cluster follow-up launch starts from (knot_points > 128)
  * and, for handles with at most 8 MB of double iterates, the double cluster kernels' buffers (GRAPH CAPTURE); from their
  * first use on, the staging buffers of mpcg_form_schur(_f64), the seam buffer of the chunk-walking Schur kernel, the
- * sweep scratch of mpcg_block_solve and the point-merit scratch of mpcg_compute_merit.  max_batch bounds `batch` of later calls.  device < 0 = current device.  One handle per
+ * sweep scratch of mpcg_block_solve, that of mpcg_block_solve_f64 and the point-merit scratch of mpcg_compute_merit.  max_batch bounds `batch` of later calls.  device < 0 = current device.  One handle per
  * (device, knot_points) and per concurrently used stream: calls on the same handle must not overlap on the host
  * side (launch knobs are chosen per call) and their device work must be ordered (one stream, or events) because
  * they share those buffers; different handles are independent. */
@@ -114,7 +114,7 @@ const char *mpcg_build_info(void);
  * serves, with n x n blocks in the same layouts and with the same semantics:
  *   - the PCG entry points (mpcg_pcg_solve, mpcg_pcg_solve_ref, mpcg_pcg_solve_f64, mpcg_pcg_solve_ref_f64, mpcg_pcg_lds_bytes,
  *     mpcg_check_pcg_occupancy) through a generic, functional kernel (matrices streamed every iteration; "last_kernel_family" = 3);
- *   - mpcg_form_schur(_f64), mpcg_compute_dz(_f64), mpcg_block_solve, mpcg_prep_csr and mpcg_bd_to_csr_lowertri through run-time-dimension
+ *   - mpcg_form_schur(_f64), mpcg_compute_dz(_f64), mpcg_block_solve(_f64), mpcg_prep_csr and mpcg_bd_to_csr_lowertri through run-time-dimension
  *     kernels (operands in LDS; the same operation order as the tuned ones, i.e. the same bits as the reference arithmetic restated on the
  *     CPU), for any 1 <= control_size <= state_size — also control_size != 7 on a 14-state handle.  control_size = 0 or > state_size is
  *     MPCG_ERR_INVALID.  mpcg_form_schur(_f64) needs one block row's operands, 6 n^2 + 2 n m + 2 m^2 + 12 n + 4 m elements, in 160 KiB of
@@ -282,11 +282,31 @@ int mpcg_compute_dz_f64(mpcg_handle *h, uint32_t control_size, const double *d_G
  * wavefront, serial in the knot index — the throughput solver for batches (1/50 of the flops of 167 PCG iterations),
  * while mpcg_pcg_solve keeps warm starts and the tolerance knob.  fp32 at cond ~1e5: relative error ~3e-4.
  * state_size != 14: one workgroup per trajectory with Delta_k, [U_k | y_k] and L_k in LDS, the same operation order and bits; every
- * state size a handle can have.  Float only.
+ * state size a handle can have.
  * Scratch (max_batch x N x (n^2 + n) floats; 210 per knot at n = 14) is owned by the handle; the first call allocates it, later calls are
- * pure stream work (capturable into a graph). */
+ * pure stream work (capturable into a graph).
+ * Option "block_solve_f64" = 1 (default 0; any other value is MPCG_ERR_INVALID; read when the call is made, so a captured graph keeps what it
+ * was captured with): float64 inside, float outputs — the same float d_S / d_gamma are widened on load (exact), the sweep and the back
+ * substitution run in double through the scratch of mpcg_block_solve_f64 (allocated by the first such call, as there), and lambda is rounded
+ * to float once, on store: the bits of the double sweep on the widened data, rounded.  A pivot-free block LU in float loses what the condition
+ * number takes; on the 128-knot iiwa systems of the tests (cond 1e7) the float sweep is at 2e-3 of max |lambda|, this one at 3e-5.  With 0
+ * nothing about the call changes. */
 int mpcg_block_solve(mpcg_handle* h, const float* d_S, const float* d_gamma, float* d_lambda, uint32_t batch,
                      void* stream);
+
+/* The same solve with linsys_t = double: reads d_S / d_gamma exactly as mpcg_form_schur_f64 left them (bd layout, stored negated, blocks
+ * (0, left) and (N-1, right) never read), d_lambda is output only; the same errors in the same order (null pointer: MPCG_ERR_INVALID;
+ * batch == 0: MPCG_OK, nothing launched; batch > max_batch: MPCG_ERR_INVALID).  The operation order of mpcg_block_solve with every
+ * operation in double: bit-identical to the reference arithmetic restated on the CPU in double.  state_size 14: one trajectory per
+ * wavefront, the columns of [Delta_k | U_k y_k] dealt over the four 16-lane DPP rows (csrc/block_solve_f64.hip.h) at EVERY batch size —
+ * the four-trajectories-per-wavefront layout is not built in double (its live set, ~100 doubles per lane, does not fit the register file
+ * without spilling), so "block_solve_wide" is ignored by this entry and by "block_solve_f64" = 1.  Every other state size (1..64), and 14
+ * under "producers_generic" = 1: the run-time-dimension LDS kernel in double (133,664 bytes of LDS at n = 64); same bits.
+ * Scratch: a second handle-owned buffer, max_batch x N x (n^2 + n) doubles, allocated by the first call of this entry or of
+ * mpcg_block_solve under "block_solve_f64" = 1 (refused on a capturing stream: GRAPH CAPTURE), freed by mpcg_destroy; the float solve's
+ * scratch is never resized, freed or shared, so a captured float solve stays valid.  Later calls are pure stream work. */
+int mpcg_block_solve_f64(mpcg_handle *h, const double *d_S, const double *d_gamma, double *d_lambda, uint32_t batch,
+                         void *stream);
 
 /* ---- the producer of the path's inputs: KKT block assembly ----
  * mpcg_generate_kkt replaces generate_kkt_submatrices<T><<<knot_points, KKT_THREADS, smem>>>(state_size, control_size, knot_points,
@@ -525,8 +545,10 @@ int mpcg_qdldl_solve_schur(mpcg_handle *h, mpcg_ldl *l, const float *d_val, cons
  *       kernel closes the seams between chunks; 0: the LDS kernels, one workgroup per block row; same bits), "schur_chunk" (block rows per
  *       chunk: 0 = by call size, from one row per chunk for a single trajectory to 16 at 1024 x 128 knots; 1..2048 forced; same bits), "dz_dpp"
  *       (1: mpcg_compute_dz with four knots per wavefront, 0: the LDS kernel, one lane per element of dz; same bits), "block_solve_wide"
- *       (mpcg_block_solve: 1 one trajectory per wavefront, 0 four, -1 by batch size; same bits), "producers_generic" (0 / 1, default 0; 1: on a
- *       14 x 7 handle mpcg_form_schur(_f64), mpcg_compute_dz(_f64) and mpcg_block_solve run the run-time-dimension kernels every other shape
+ *       (mpcg_block_solve: 1 one trajectory per wavefront, 0 four, -1 by batch size; same bits; not read by the double sweeps), "block_solve_f64"
+ *       (mpcg_block_solve: 0, the default: the float sweep; 1: float64 inside, lambda rounded to float on store — see mpcg_block_solve; any other
+ *       value is MPCG_ERR_INVALID), "producers_generic" (0 / 1, default 0; 1: on a
+ *       14 x 7 handle mpcg_form_schur(_f64), mpcg_compute_dz(_f64) and mpcg_block_solve(_f64) run the run-time-dimension kernels every other shape
  *       gets — same bits, the A/B switch of tests and timings; "last_schur_chunk" then reads 0).  The library has ONE set of LDS kernels, the
  *       run-time-dimension ones: for formation and dz, "producers_generic" = 1 and "schur_dpp" = "dz_dpp" = 0 run the same kernels (the two
  *       differ in mpcg_block_solve only, which "schur_dpp" / "dz_dpp" leave register-resident); a 14 x 7 call too large for the 31-bit byte

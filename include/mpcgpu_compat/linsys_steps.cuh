@@ -40,9 +40,13 @@ void compute_dz(uint32_t state_size, uint32_t control_size, uint32_t knot_points
 // The linear solve of the reference's other path (LINSYS_SOLVE == 0) — D2H(values, gamma), qdldl_solve_schur
 // (include/qdldl/sqp.cuh:22-49), H2D(lambda), timed as one region at include/qdldl/sqp.cuh:261-282 — as one GPU call on
 // the bd-layout S and gamma that form_schur_system left on the device: block-tridiagonal direct sweep, no host round trip.
+// linsys_t = float: mpcg_block_solve; double: mpcg_block_solve_f64.
 template <typename T>
 void block_solve_schur(uint32_t state_size, uint32_t knot_points, T* d_S, T* d_gamma, T* d_lambda) {
-    static_assert(std::is_same<T, float>::value, "mpcg_block_solve is single precision");
+    static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "linsys_t is float or double (include/common/settings.cuh:41-49)");
     mpcg_handle* h = mpcg_compat::handle_for(state_size, knot_points);
-    if (mpcg_block_solve(h, d_S, d_gamma, d_lambda, 1, /*stream*/ nullptr) != MPCG_OK) mpcg_compat::die("block_solve_schur", h);
+    int rc;
+    if constexpr (std::is_same<T, float>::value) rc = mpcg_block_solve(h, d_S, d_gamma, d_lambda, 1, /*stream*/ nullptr);
+    else rc = mpcg_block_solve_f64(h, d_S, d_gamma, d_lambda, 1, /*stream*/ nullptr);
+    if (rc != MPCG_OK) mpcg_compat::die("block_solve_schur", h);
 }

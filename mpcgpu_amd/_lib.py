@@ -59,6 +59,7 @@ SYMBOLS = {
                                      C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mpcg_pcg_solve_ref_f64": (C.c_int, [C.c_void_p] * 11 + [C.c_uint32, C.c_double, C.c_void_p]),
     "mpcg_block_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_block_solve_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_plant_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "mpcg_plant_create_iiwa14": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),

@@ -229,6 +229,7 @@ int mpcg_destroy(mpcg_handle* h) {
         (void)hipSetDevice(h->device);
         if (h->lam_backup) (void)hipFree(h->lam_backup);
         if (h->block_scratch) (void)hipFree(h->block_scratch);
+        if (h->block_scratch64) (void)hipFree(h->block_scratch64);
         if (h->ginv_scratch) (void)hipFree(h->ginv_scratch);
         if (h->seam_qinv) (void)hipFree(h->seam_qinv);
         if (h->sym_event) (void)hipEventDestroy(h->sym_event);
@@ -317,6 +318,10 @@ int mpcg_set_option(mpcg_handle* h, const char* key, int value) {
         if (value != 0 && value != 1) return fail(h, MPCG_ERR_INVALID, "merit_f32 must be 0 (float64 inside) or 1 (packed float)");
         h->merit_f32 = value; return MPCG_OK;
     }
+    if (!strcmp(key, "block_solve_f64")) {
+        if (value != 0 && value != 1) return fail(h, MPCG_ERR_INVALID, "block_solve_f64 must be 0 (the float sweep) or 1 (float64 inside)");
+        h->block_solve_f64 = value; return MPCG_OK;
+    }
     if (!strcmp(key, "sched_hint")) { h->sched_hint = value ? 1 : 0; return MPCG_OK; }
     if (!strcmp(key, "cluster")) {
         if (value < -1 || value > 32) return fail(h, MPCG_ERR_INVALID, "cluster must be -1 (auto), 0 (off) or 1..32 workgroups per trajectory");
@@ -356,6 +361,7 @@ int mpcg_get_option(const mpcg_handle* h, const char* key, int* value) {
     if (!strcmp(key, "kkt_analytic")) { *value = h->kkt_analytic; return MPCG_OK; }
     if (!strcmp(key, "kkt_f32")) { *value = h->kkt_f32; return MPCG_OK; }
     if (!strcmp(key, "merit_f32")) { *value = h->merit_f32; return MPCG_OK; }
+    if (!strcmp(key, "block_solve_f64")) { *value = h->block_solve_f64; return MPCG_OK; }
     if (!strcmp(key, "sched_hint")) { *value = h->sched_hint; return MPCG_OK; }
     if (!strcmp(key, "spmv_blocks_per_cu")) { *value = h->spmv_blocks_per_cu; return MPCG_OK; }
     if (!strcmp(key, "spmv_mfma")) { *value = h->spmv_mfma; return MPCG_OK; }

@@ -2,7 +2,7 @@
 //   gen::form_schur_kernel + gen::complete_ss_kernel   (G, C, g, c, rho) -> (S, Pinv, gamma), G <- G^-1
 //        replaces form_S_gamma_Pinv_kernel / form_schur_system (include/pcg/linsys_setup.cuh:565-656)
 //   gen::compute_dz_kernel                             dz = G^-1 (g - C^T lambda)      replaces compute_dz (include/common/dz.cuh:3-136)
-//   gen::bt_block_solve_kernel                         block-tridiagonal direct solve of S lambda = gamma (float)
+//   gen::bt_block_solve_kernel                         block-tridiagonal direct solve of S lambda = gamma (float, double, float storage / double sweep)
 // and, ahead of them, what every producer kernel of the library shares: the argument structs of formation and dz (the register-resident
 // kernels of schur_walk.hip.h / schur_walk_f64.hip.h take the same ones) and the two CSR kernels of the QDLDL path.
 //
@@ -396,14 +396,23 @@ __global__ __launch_bounds__(128) void compute_dz_kernel(DzArgsT<T> a) {
 // stays in registers (thread (r, c) owns Delta(r, c)).  W_k, z_k -> work for the back substitution.
 //   Delta_0 = D_0, y_0 = gamma_0;  k >= 1: Delta_k = D_k - L_k W_{k-1}, y_k = gamma_k - L_k z_{k-1};  [Delta_k | U_k y_k] -> [I | W_k z_k] by one
 //   Gauss-Jordan elimination (columns at or left of the pivot untouched);  lambda_{N-1} = z_{N-1}, lambda_k = z_k - W_k lambda_{k+1}.
-struct BlockSolveGenArgs {
-    const float* S; const float* gamma; float* lambda; float* work;       // work: [batch][N][n * n + n]
+// T: the type of the sweep (operands in LDS, work); ST: the storage type of S, gamma and lambda — T itself, or float under T = double: widened
+// on load (exact), lambda rounded once on store ("block_solve_f64" = 1).  LDS: block_solve_lds_elems(n) x sizeof(T).
+template <typename T, typename ST = T>
+struct BlockSolveGenArgsT {
+    const ST* S; const ST* gamma; ST* lambda; T* work;                    // work: [batch][N][n * n + n]
     int n; int N; int batch;
 };
+typedef BlockSolveGenArgsT<float> BlockSolveGenArgs;
 __host__ __device__ constexpr size_t block_solve_lds_elems(int n) { return (size_t)4 * n * n + (size_t)5 * n + 4; }
 
-__global__ __launch_bounds__(256) void bt_block_solve_kernel(BlockSolveGenArgs a) {
-    typedef float T;
+template <typename T, typename ST>
+__device__ __forceinline__ void g_widen(int cnt, const ST* src, T* dst) {
+    for (int e = threadIdx.x; e < cnt; e += blockDim.x) dst[e] = (T)src[e];
+}
+
+template <typename T, typename ST = T>
+__global__ __launch_bounds__(256) void bt_block_solve_kernel(BlockSolveGenArgsT<T, ST> a) {
     extern __shared__ __align__(16) unsigned char gen_smem[];
     T* sm = reinterpret_cast<T*>(gen_smem);
     const int n = a.n, N = a.N, nn = n * n, WS = nn + n;
@@ -412,18 +421,18 @@ __global__ __launch_bounds__(256) void bt_block_solve_kernel(BlockSolveGenArgs a
     const int nt = blockDim.x, tid = threadIdx.x;
     const Lane ln = lane_of(n);
     for (long b = blockIdx.x; b < a.batch; b += gridDim.x) {
-        const T* S = a.S + (size_t)b * 3 * nn * N;
-        const T* gamma = a.gamma + (size_t)b * n * N;
-        T* lambda = a.lambda + (size_t)b * n * N;
+        const ST* S = a.S + (size_t)b * 3 * nn * N;
+        const ST* gamma = a.gamma + (size_t)b * n * N;
+        ST* lambda = a.lambda + (size_t)b * n * N;
         T* work = a.work + (size_t)b * N * WS;
         for (int k = 0; k < N; ++k) {
-            const T* blk = S + (size_t)k * 3 * nn;
+            const ST* blk = S + (size_t)k * 3 * nn;
             __syncthreads();
-            g_copy(nn, blk + nn, Delta);
-            if (k < N - 1) g_copy(nn, blk + 2 * nn, cur);
+            g_widen(nn, blk + nn, Delta);
+            if (k < N - 1) g_widen(nn, blk + 2 * nn, cur);
             else for (int e = tid; e < nn; e += nt) cur[e] = (T)0;          // the last block row carries y only
-            if (k > 0) g_copy(nn, blk, Lb);
-            for (int i = tid; i < n; i += nt) y[i] = gamma[(size_t)k * n + i];
+            if (k > 0) g_widen(nn, blk, Lb);
+            for (int i = tid; i < n; i += nt) y[i] = (T)gamma[(size_t)k * n + i];
             __syncthreads();
             if (k > 0) {
                 for (int c = ln.c0; c < n; c += ln.cs) {                   // Delta = D - L W_{k-1}
@@ -472,7 +481,7 @@ __global__ __launch_bounds__(256) void bt_block_solve_kernel(BlockSolveGenArgs a
         // back substitution: lambda_{N-1} = z_{N-1} (still in zp); W_k staged through LDS by the whole workgroup, one lane per row
         T *la = y, *lb = prowD;
         __syncthreads();
-        for (int i = tid; i < n; i += nt) { la[i] = zp[i]; lambda[(size_t)(N - 1) * n + i] = zp[i]; }
+        for (int i = tid; i < n; i += nt) { la[i] = zp[i]; lambda[(size_t)(N - 1) * n + i] = (ST)zp[i]; }
         for (int k = N - 2; k >= 0; --k) {
             g_copy(nn, work + (size_t)k * WS, Lb);
             __syncthreads();
@@ -481,7 +490,7 @@ __global__ __launch_bounds__(256) void bt_block_solve_kernel(BlockSolveGenArgs a
                 for (int c = 0; c < n; ++c) acc += Lb[r + c * n] * la[c];
                 const T v = work[(size_t)k * WS + nn + r] - acc;
                 lb[r] = v;
-                lambda[(size_t)k * n + r] = v;
+                lambda[(size_t)k * n + r] = (ST)v;
             }
             __syncthreads();
             T* sw = la; la = lb; lb = sw;

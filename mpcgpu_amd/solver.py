@@ -261,15 +261,21 @@ class PcgSolver:
 
     def block_solve(self, S, gamma, lam=None):
         """Batched block-tridiagonal direct solve (the GPU counterpart of qdldl_solve_schur,
-        include/qdldl/sqp.cuh:22-49).  S: [B, 3*n*n*N], gamma: [B, n*N]; returns lambda [B, n*N]."""
+        include/qdldl/sqp.cuh:22-49).  S: [B, 3*n*n*N], gamma: [B, n*N]; returns lambda [B, n*N].
+        float32 tensors: mpcg_block_solve (option "block_solve_f64" = 1: the sweep in double, float in and out);
+        float64 tensors: mpcg_block_solve_f64 (linsys_t = double).  Mixed or other dtypes raise TypeError."""
         B = gamma.shape[0] if gamma.dim() > 1 else 1
         n, N = self.n, self.N
-        self._chk(S, B * 3 * n * n * N, torch.float32, "S")
-        self._chk(gamma, B * n * N, torch.float32, "gamma")
+        dt = gamma.dtype
+        if dt not in (torch.float32, torch.float64) or S.dtype != dt or (lam is not None and lam.dtype != dt):
+            raise TypeError("block_solve: S, gamma and lambda must all be float32 or all be float64")
+        self._chk(S, B * 3 * n * n * N, dt, "S")
+        self._chk(gamma, B * n * N, dt, "gamma")
         if lam is None:
-            lam = torch.empty(B, n * N, device=gamma.device)
-        self._chk(lam, B * n * N, torch.float32, "lambda")
-        self._check(self.lib.mpcg_block_solve(self._h, _ptr(S), _ptr(gamma), _ptr(lam), B, _stream()))
+            lam = torch.empty(B, n * N, device=gamma.device, dtype=dt)
+        self._chk(lam, B * n * N, dt, "lambda")
+        fn = self.lib.mpcg_block_solve if dt == torch.float32 else self.lib.mpcg_block_solve_f64
+        self._check(fn(self._h, _ptr(S), _ptr(gamma), _ptr(lam), B, _stream()))
         return lam
 
     def form_schur(self, G_dense, C_dense, g, c, rho, precond: str = "ss", S=None, Pinv=None, gamma=None,

@@ -1,0 +1,83 @@
+#!/usr/bin/env python3
+"""Time the block-tridiagonal direct solve in its three precisions on one handle in ONE process, alternated window by window:
+    float     mpcg_block_solve, "block_solve_f64" = 0 — the baseline (the float kernels, untouched by the double paths)
+    option    mpcg_block_solve, "block_solve_f64" = 1 — float S / gamma widened on load, the sweep in double, lambda rounded on store
+    f64       mpcg_block_solve_f64 — linsys_t = double
+Shapes: 1024 trajectories x 128 knots (the throughput call), one trajectory x 128 and one x 32 knots (the MPC loop's own call), state size 14.
+After 50 ms of back-to-back warm-up launches of all three: device events around `reps` back-to-back calls, medians of seven windows.
+Before the timing the three results are compared against the float64 result (relative to max |lambda|).  One JSON line per shape.
+No ratio is promised: a knot's elimination is a dependent chain of fp64 operations at half the fp32 issue rate, with twice the scratch
+traffic.  Needs an MI355X:
+    python tools/time_block_solve_f64.py [reps]
+(tools/time_block_solve.py is the older comparison of the float solve against PCG.)"""
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+from mpcgpu_amd import PcgSolver  # noqa: E402
+
+WINDOWS = 7
+
+
+def timed(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps * 1e3          # microseconds per call
+
+
+def main():
+    reps_arg = int(sys.argv[1]) if len(sys.argv) > 1 else 0
+    dev = torch.device("cuda", 0)
+    for N, B in ((128, 1024), (128, 1), (32, 1)):
+        reps = reps_arg or (200 if B == 1 else 20)
+        sol = PcgSolver(N, max_batch=B)
+        dS, _, dg = bench.build_inputs(sol, N, B, 0, "ss", dev)
+        dS64, dg64 = dS.double(), dg.double()
+        lam = torch.empty(B, 14 * N, device=dev)
+        lam64 = torch.empty(B, 14 * N, device=dev, dtype=torch.float64)
+
+        def call(which):
+            if which == "f64":
+                sol.block_solve(dS64, dg64, lam64)
+            else:
+                sol.set_option("block_solve_f64", 1 if which == "option" else 0)      # (read when the call is made)
+                sol.block_solve(dS, dg, lam)
+
+        names = ("float", "option", "f64")
+        out = {}
+        for w in names:
+            call(w)
+            torch.cuda.synchronize()
+            out[w] = (lam64 if w == "f64" else lam).cpu().numpy().astype(np.float64)
+        scale = np.abs(out["f64"]).max()
+        diff = {w: float(f"{np.abs(out[w] - out['f64']).max() / scale:.3g}") for w in ("float", "option")}
+        t0 = time.time()
+        while time.time() - t0 < 0.05:
+            for w in names:
+                call(w)
+            torch.cuda.synchronize()
+        rounds = []
+        for _ in range(WINDOWS):
+            rounds.append([timed(lambda: call(w), reps) for w in names])
+        med = [statistics.median(r[i] for r in rounds) for i in range(3)]
+        print(json.dumps({"knots": N, "batch": B, "reps": reps, "float_us": round(med[0], 2), "option_us": round(med[1], 2), "f64_us": round(med[2], 2),
+                          "option_over_float": round(med[1] / med[0], 3), "f64_over_float": round(med[2] / med[0], 3),
+                          "finite": bool(all(np.isfinite(v).all() for v in out.values())), "float_vs_f64": diff["float"], "option_vs_f64": diff["option"],
+                          "windows": [[round(v, 2) for v in r] for r in rounds]}), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
