@@ -298,7 +298,7 @@ int mpcg_block_solve(mpcg_handle* h, const float* d_S, const float* d_gamma, flo
  * (0, left) and (N-1, right) never read), d_lambda is output only; the same errors in the same order (null pointer: MPCG_ERR_INVALID;
  * batch == 0: MPCG_OK, nothing launched; batch > max_batch: MPCG_ERR_INVALID).  The operation order of mpcg_block_solve with every
  * operation in double: bit-identical to the reference arithmetic restated on the CPU in double.  state_size 14: one trajectory per
- * wavefront, the columns of [Delta_k | U_k y_k] dealt over the four 16-lane DPP rows (csrc/block_solve_f64.hip.h) at EVERY batch size —
+ * wavefront, the columns of [Delta_k | U_k y_k] dealt over the four 16-lane DPP rows (csrc/block_solve.hip.h) at EVERY batch size —
  * the four-trajectories-per-wavefront layout is not built in double (its live set, ~100 doubles per lane, does not fit the register file
  * without spilling), so "block_solve_wide" is ignored by this entry and by "block_solve_f64" = 1.  Every other state size (1..64), and 14
  * under "producers_generic" = 1: the run-time-dimension LDS kernel in double (133,664 bytes of LDS at n = 64); same bits.

@@ -13,7 +13,14 @@
 // four sweeping k = 0..N-1 in lock-step; W_k and z_k go through a global scratch of N x 210 floats per trajectory
 // for the back substitution.  ~1.7 k instructions per knot and wave, no LDS, no barriers; the sweep is serial in k
 // (that is what PCG avoids for ONE trajectory), so this is the throughput solver for batches: 1/50 of the flops of
-// 167 PCG iterations.  The test oracle restates the same operation order on the CPU: results are bit-identical in float (tested).
+// 167 PCG iterations.  The test oracle restates the same operation order on the CPU: results are bit-identical (tested).
+//
+// bt_block_solve_wide_kernel<CT, ST> is the same sweep with ONE trajectory per wavefront, in float or with the sweep in
+// DOUBLE (linsys_t = double, USE_DOUBLES = 1 of include/common/settings.cuh:41-49; and "float64 inside, float outputs"
+// for float callers).  CT is the sweep type — the scratch holds N x 210 CTs per trajectory — and ST the STORAGE type of
+// S, gamma and lambda: widened on load (exact) and rounded once on the store of lambda.  One body serves both
+// precisions, so the operation order the oracle pins bit for bit is written once; what float and double differ in is
+// the "float and double rows" section of dpp_rows.hip.h.
 #pragma once
 #include "dpp_rows.hip.h"
 
@@ -21,10 +28,37 @@ namespace mpcg {
 
 #pragma clang fp contract(off)
 
-struct BlockSolveArgs {
-    const float* S; const float* gamma; float* lambda; float* work;   // work: [batch][N][14*14 + 14]
+template <typename CT, typename ST = CT>
+struct BlockSolveArgsT {
+    const ST* S; const ST* gamma; ST* lambda; CT* work;    // work: [batch][N][14*14 + 14]
     int N; int batch;
 };
+typedef BlockSolveArgsT<float> BlockSolveArgs;
+
+// lambda_k = z_k - W_k lambda_{k+1} for k = N-2..0, from lam = lambda_{N-1} (stored by the caller): rows in lanes, the sum over all 14
+// columns in order, W_k and z_k prefetched one knot ahead from the scratch.  Lanes with `st` store.
+template <typename CT, typename ST>
+__device__ __forceinline__ void back_substitute(const CT* work, ST* lambda, int N, int lr, int lc, CT lam, bool st) {
+    using namespace sdpp;
+    constexpr int n = 14, nn = n * n, WS = nn + n;
+    CT Wn[n], zn = 0;
+    auto fetch_b = [&](int k) {
+#pragma unroll
+        for (int c = 0; c < n; ++c) Wn[c] = work[(size_t)k * WS + lc + c * n];
+        zn = work[(size_t)k * WS + nn + lc];
+    };
+    if (N >= 2) fetch_b(N - 2);
+    for (int k = N - 2; k >= 0; --k) {
+        CT Wk[n];
+#pragma unroll
+        for (int c = 0; c < n; ++c) Wk[c] = Wn[c];
+        const CT zk = zn;
+        if (k > 0) fetch_b(k - 1);
+        const CT v = matvec<n>(Wk, lam);
+        lam = zk - v;
+        if (st) lambda[(size_t)k * n + lr] = (ST)lam;
+    }
+}
 
 __global__ __launch_bounds__(64, 2) void bt_block_solve_kernel(BlockSolveArgs a) {
     using namespace sdpp;
@@ -80,91 +114,75 @@ __global__ __launch_bounds__(64, 2) void bt_block_solve_kernel(BlockSolveArgs a)
         if (k < N - 1) store_rows(W, work + (size_t)k * WS, n, lr, st, 1.f);
         zp = z;
     }
-    float lam = zp;                                        // lambda_{N-1} = z_{N-1}
-    if (st) lambda[(size_t)(N - 1) * n + lr] = lam;
-    float Wn[n], zn = 0.f;
-    auto fetch_b = [&](int k) {
-        load_rows(Wn, work + (size_t)k * WS, n, lr, true);
-        zn = work[(size_t)k * WS + nn + lc];
-    };
-    if (N >= 2) fetch_b(N - 2);
-    for (int k = N - 2; k >= 0; --k) {
-        float Wk[n];
-#pragma unroll
-        for (int c = 0; c < n; ++c) Wk[c] = Wn[c];
-        const float zk = zn;
-        if (k > 0) fetch_b(k - 1);
-        const float v = matvec<n>(Wk, lam);
-        lam = zk - v;
-        if (st) lambda[(size_t)k * n + lr] = lam;
-    }
+    if (st) lambda[(size_t)(N - 1) * n + lr] = zp;         // lambda_{N-1} = z_{N-1}
+    back_substitute(work, lambda, N, lr, lc, zp, st);
 }
 
-// ---- the same sweep for FEW trajectories: one trajectory per wavefront, the 29 columns of [Delta | U y] dealt
-// round-robin to the four 16-lane DPP rows (lane = 16 g + r holds row r of columns c = 4 j + g, j = 0..3, of Delta and
-// of U; g = 3 also carries y / z).  Per pivot one ds_bpermute moves the pivot column from its owner row to the other
-// three; everything else stays inside a row (row_newbcast).  Every entry goes through exactly the operations of the
-// narrow kernel above, so the results are bit-identical; ~0.9 k instead of ~2.3 k instructions per knot on the
-// critical path.  The back substitution sums over all 14 columns in order, so it runs in the narrow layout
-// (redundantly in the four rows). ----
-__global__ __launch_bounds__(64, 2) void bt_block_solve_wide_kernel(BlockSolveArgs a) {
+// ---- the same sweep for FEW trajectories, and the only layout built in double: one trajectory per wavefront, the 29 columns of
+// [Delta | U y] dealt round-robin to the four 16-lane DPP rows (lane = 16 g + r holds row r of columns c = 4 j + g, j = 0..3, of Delta and
+// of U; g = 3 also carries y / z).  Per pivot one bperm moves the pivot column from its owner row to the other three; everything else stays
+// inside a row (row_newbcast).  Every entry goes through exactly the operations of the narrow kernel above, so the results are
+// bit-identical; ~0.9 k instead of ~2.3 k instructions per knot on the critical path in float.  In double the live set is ~45 doubles per
+// lane (D, U, W: 4 each, L: 14, the prefetch: 23 in the storage type), which fits the register file with no scratch.  The back substitution
+// sums over all 14 columns in order, so it runs in the narrow layout (redundantly in the four rows). ----
+template <typename CT, typename ST>
+__global__ __launch_bounds__(64, 2) void bt_block_solve_wide_kernel(BlockSolveArgsT<CT, ST> a) {
     using namespace sdpp;
     constexpr int n = 14, nn = n * n, WS = nn + n, NSL = 4;
     const int N = a.N;
     const int lane = threadIdx.x, lr = lane & 15, g = lane >> 4;
     const bool r14 = lr < n;
-    const int lc = r14 ? lr : n - 1;
+    const int lc = r14 ? lr : n - 1;                       // lanes 14, 15 repeat row 13 and store nothing
     const size_t b = blockIdx.x;
-    const float* S = a.S + b * 3 * nn * N;
-    const float* gamma = a.gamma + b * n * N;
-    float* lambda = a.lambda + b * n * N;
-    float* work = a.work + b * (size_t)N * WS;
+    const ST* S = a.S + b * 3 * nn * N;
+    const ST* gamma = a.gamma + b * n * N;
+    ST* lambda = a.lambda + b * n * N;
+    CT* work = a.work + b * (size_t)N * WS;
     // this lane's columns: c_j = 4 j + g (clamped for addressing; slots with c_j >= 14 compute on duplicates, store nothing)
     int cj[NSL];
     bool cv[NSL];
 #pragma unroll
     for (int j = 0; j < NSL; ++j) { cv[j] = 4 * j + g < n; cj[j] = cv[j] ? 4 * j + g : n - 1; }
 
-    float W[NSL];                                          // this lane's columns of W_{k-1}
-    float zp = 0.f;                                        // z_{k-1}[lr] (meaningful in row g = 3)
+    CT W[NSL];                                             // this lane's columns of W_{k-1}
+    CT zp = 0;                                             // z_{k-1}[lr] (meaningful in row g = 3)
 #pragma unroll
-    for (int j = 0; j < NSL; ++j) W[j] = 0.f;
-    float Dn[NSL], Un[NSL], Ln[n], yn;
+    for (int j = 0; j < NSL; ++j) W[j] = 0;
+    // operands of the NEXT knot are requested before the current knot is eliminated (as in the narrow kernel), as stored: widened when the knot starts
+    ST Dn[NSL], Un[NSL], Ln[n], yn;
     auto fetch = [&](int k) {
-        const float* blk = S + (size_t)k * 3 * nn;
+        const ST* blk = S + (size_t)k * 3 * nn;
 #pragma unroll
         for (int j = 0; j < NSL; ++j) {
             Dn[j] = blk[nn + lc + cj[j] * n];
-            Un[j] = blk[2 * nn + lc + cj[j] * n];
+            Un[j] = blk[2 * nn + lc + cj[j] * n];         // (k = N-1: the never-written block, never used)
         }
 #pragma unroll
-        for (int c = 0; c < n; ++c) Ln[c] = blk[lc + c * n];
+        for (int c = 0; c < n; ++c) Ln[c] = blk[lc + c * n];   // (k = 0: likewise)
         yn = gamma[(size_t)k * n + lc];
     };
     fetch(0);
     for (int k = 0; k < N; ++k) {
-        float D[NSL], U[NSL], L[n];
+        CT D[NSL], U[NSL], L[n];
 #pragma unroll
-        for (int j = 0; j < NSL; ++j) { D[j] = Dn[j]; U[j] = (k < N - 1) ? Un[j] : 0.f; }
+        for (int j = 0; j < NSL; ++j) { D[j] = (CT)Dn[j]; U[j] = (k < N - 1) ? (CT)Un[j] : CT(0); }
 #pragma unroll
-        for (int c = 0; c < n; ++c) L[c] = Ln[c];
-        float y = yn;
+        for (int c = 0; c < n; ++c) L[c] = (CT)Ln[c];
+        CT y = (CT)yn;
         if (k + 1 < N) fetch(k + 1);
         if (k > 0) {
             // Delta = D - L W_{k-1} (own columns), y -= L z_{k-1}: sums over t = 0..13 in order, W / z from lane t of the row
-            float t[NSL];
+            CT t[NSL];
 #pragma unroll
-            for (int j = 0; j < NSL; ++j) t[j] = 0.f;
-            float v = 0.f;
+            for (int j = 0; j < NSL; ++j) t[j] = 0;
+            CT v = 0;
+            settle<CT>();
             SFor<0, n>::run([&](auto tc) {
                 constexpr int T = decltype(tc)::value;
+                if constexpr (T > 0) sched_fence<CT>();    // (double) term T's products start after term T-1's sums: five broadcasts in flight, not 70
 #pragma unroll
-                for (int j = 0; j < NSL; ++j) {
-                    const float p = L[T] * rbc<T>(W[j]);
-                    t[j] = t[j] + p;
-                }
-                const float pv = L[T] * rbc<T>(zp);
-                v = v + pv;
+                for (int j = 0; j < NSL; ++j) t[j] = t[j] + mulbc<T>(L[T], W[j]);
+                v = v + mulbc<T>(L[T], zp);
             });
 #pragma unroll
             for (int j = 0; j < NSL; ++j) D[j] = D[j] - t[j];
@@ -175,27 +193,41 @@ __global__ __launch_bounds__(64, 2) void bt_block_solve_wide_kernel(BlockSolveAr
             constexpr int P = decltype(pc_)::value;
             constexpr int GP = P % 4, JP = P / 4;
             // column P of Delta, from its owner row to every row (same lr)
-            const float pcol = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((GP * 16 + lr) * 4, __builtin_bit_cast(int, D[JP])));
-            const float pinv = 1.0f / rbc<P>(pcol);
+            const CT pcol = bperm((GP * 16 + lr) * 4, D[JP]);
+            settle<CT>();
+            const CT pinv = CT(1) / rbc<P>(pcol);
             const bool is_p = lr == P;
+            CT pa[NSL], pu[NSL];
+            // columns right of the pivot (slot JP: only in rows g > GP; the others recompute dead columns, which nobody reads again)
 #pragma unroll
-            for (int j = JP; j < NSL; ++j) {               // columns right of the pivot (slot JP: only in rows g > GP; the
-                const float pa = D[j] * pinv;              //  others recompute dead columns, which nobody reads again)
-                const float ta = pcol * rbc<P>(pa);
-                const float na = D[j] - ta;
-                D[j] = is_p ? pa : na;
+            for (int j = JP; j < NSL; ++j) pa[j] = D[j] * pinv;
+#pragma unroll
+            for (int j = 0; j < NSL; ++j) pu[j] = U[j] * pinv;
+            CT py = y * pinv;
+            // (double) pinned in front of the settle: a scaled entry whose only other reader is the pivot lane's select would otherwise be
+            // sunk behind the s_nop, next to its DPP reader
+#pragma unroll
+            for (int j = JP; j < NSL; ++j) pin(pa[j]);
+#pragma unroll
+            for (int j = 0; j < NSL; ++j) pin(pu[j]);
+            pin(py);
+            settle<CT>();
+#pragma unroll
+            for (int j = JP; j < NSL; ++j) {
+                const CT ta = mulbc<P>(pcol, pa[j]);
+                const CT na = D[j] - ta;
+                D[j] = is_p ? pa[j] : na;
             }
 #pragma unroll
             for (int j = 0; j < NSL; ++j) {
-                const float pu = U[j] * pinv;
-                const float tu = pcol * rbc<P>(pu);
-                const float nu = U[j] - tu;
-                U[j] = is_p ? pu : nu;
+                const CT tu = mulbc<P>(pcol, pu[j]);
+                const CT nu = U[j] - tu;
+                U[j] = is_p ? pu[j] : nu;
             }
-            const float py = y * pinv;
-            const float ty = pcol * rbc<P>(py);
-            const float ny = y - ty;
+            const CT ty = mulbc<P>(pcol, py);
+            const CT ny = y - ty;
             y = is_p ? py : ny;
+            sched_fence<CT>();
         });
         // U now holds W_k (own columns), y holds z_k (row g = 3)
 #pragma unroll
@@ -212,25 +244,13 @@ __global__ __launch_bounds__(64, 2) void bt_block_solve_wide_kernel(BlockSolveAr
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    float lam = work[(size_t)(N - 1) * WS + nn + lc];      // lambda_{N-1} = z_{N-1}
-    if (g == 0 && r14) lambda[(size_t)(N - 1) * n + lr] = lam;
-    float Wn[n], zn = 0.f;
-    auto fetch_b = [&](int k) {
-        load_rows(Wn, work + (size_t)k * WS, n, lr, true);
-        zn = work[(size_t)k * WS + nn + lc];
-    };
-    if (N >= 2) fetch_b(N - 2);
-    for (int k = N - 2; k >= 0; --k) {
-        float Wk[n];
-#pragma unroll
-        for (int c = 0; c < n; ++c) Wk[c] = Wn[c];
-        const float zk = zn;
-        if (k > 0) fetch_b(k - 1);
-        const float v = matvec<n>(Wk, lam);
-        lam = zk - v;
-        if (g == 0 && r14) lambda[(size_t)k * n + lr] = lam;
-    }
+    const CT lam = work[(size_t)(N - 1) * WS + nn + lc];   // lambda_{N-1} = z_{N-1}
+    if (g == 0 && r14) lambda[(size_t)(N - 1) * n + lr] = (ST)lam;
+    back_substitute(work, lambda, N, lr, lc, lam, g == 0 && r14);
 }
+// Built as <float, float> (mpcg_block_solve), <double, double> (mpcg_block_solve_f64) and <double, float> ("block_solve_f64" = 1).  The
+// four-per-wavefront layout of bt_block_solve_kernel would hold ~100 doubles per lane (200 VGPRs before temporaries) and is NOT built in
+// double: there the wide layout serves every batch, and "block_solve_wide" is not read.
 
 }  // namespace mpcg
 

@@ -1,7 +1,8 @@
 // dpp_rows.hip.h — rows-in-lanes primitives on 16-lane DPP rows (gfx950): four independent problems per wavefront, lane r < 14 of a
 // row holds ROW r of every 14x14 operand in registers, and what another row needs from row t of an operand is a `row_newbcast:t` DPP source
 // modifier on the multiply (verified on the chip: tools/_prof/dpp_probe.hip).  Used by the block-tridiagonal direct solver
-// (block_solve.hip.h).  (Rounds 2-3 ran the Schur formation on these as well; round 4's formation, schur_walk.hip.h, has its own
+// (block_solve.hip.h), in float and in double; what the two differ in is the section "float and double rows" below, which
+// schur_walk_f64.hip.h uses too.  (Rounds 2-3 ran the Schur formation on these as well; round 4's formation, schur_walk.hip.h, has its own
 // column-pair versions.)
 //
 // Contraction is OFF: every a*b+c is a rounded multiply followed by a rounded add, sequential over the contracted index, accumulators
@@ -17,10 +18,53 @@ namespace mpcg {
 
 namespace sdpp {
 
-// value held by lane L of this lane's 16-lane row
+// ---- float and double rows: the broadcast, a * bc(b), the wavefront-wide permute and the hazard idioms only double needs ----
+// value held by lane L of this lane's 16-lane row.  float: a DPP source modifier once the compiler folds it into the reader.
 template <int L>
 __device__ __forceinline__ float rbc(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150 + L, 0xf, 0xf, true));
+}
+// double: `v_mov_b64_dpp ... row_newbcast:L`, the only DPP control 64-bit operations have.  The compiler does not produce it (it splits a
+// 64-bit broadcast into two v_mov_b32_dpp), so it is assembler text, and the DPP read-after-VALU-write hazard is ours to keep: SW64_SETTLE().
+template <int L>
+__device__ __forceinline__ double rbc(double v) {
+    double r;
+    asm("v_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(v), "n"(L));
+    return r;
+}
+// a * (b held by lane L of this lane's 16-lane row), a rounded multiply.  (gfx950 has DPP forms of v_mov_b64 and v_fmac_f64 only —
+// v_mul_f64 / v_add_f64 are VOP3 — and the fused multiply-add is not what the oracle computes.)
+template <int L, typename T>
+__device__ __forceinline__ T mulbc(T a, T b) {
+    return a * rbc<L>(b);
+}
+// value held by lane `addr / 4` of the wavefront: one ds_bpermute in float, two 32-bit halves in double
+__device__ __forceinline__ float bperm(int addr, float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(addr, __builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ double bperm(int addr, double v) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)(uint32_t)u);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)(uint32_t)(u >> 32));
+    return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
+}
+#define SW64_FENCE() __builtin_amdgcn_sched_barrier(0)
+// Two wait states between the last VALU write of an operand and its first DPP read: nothing is scheduled across this point, and the s_nop 1
+// stands between whatever wrote the operands before it and the DPP multiplies behind it (verified on the built code: tools/check_dpp_hazards.py).
+#define SW64_SETTLE() do { SW64_FENCE(); asm volatile("s_nop 1"); SW64_FENCE(); } while (0)
+// The same three idioms for code written once for both types: nothing in float, where the compiler owns the DPP modifier and its hazard.
+template <typename T>
+__device__ __forceinline__ void sched_fence() {
+    if constexpr (std::is_same<T, double>::value) SW64_FENCE();
+}
+template <typename T>
+__device__ __forceinline__ void settle() {
+    if constexpr (std::is_same<T, double>::value) SW64_SETTLE();
+}
+// keeps the VALU write of v in front of this point (the launder idiom of schur_walk_f64.hip.h)
+template <typename T>
+__device__ __forceinline__ void pin(T& v) {
+    if constexpr (std::is_same<T, double>::value) asm volatile("" : "+v"(v));
 }
 
 // acc += a * (b held by lane L of this 16-lane row): rounded multiply through the DPP source modifier, rounded add
@@ -56,12 +100,13 @@ __device__ __forceinline__ void gemm_nn(const float (&A)[NI], const float (&B)[N
     });
 }
 // out[r] = sum_c M[r][c] * v[c]          v: element c in lane c
-template <int NC>
-__device__ __forceinline__ float matvec(const float (&M)[NC], float v) {
-    float acc = 0.f;
+template <int NC, typename T>
+__device__ __forceinline__ T matvec(const T (&M)[NC], T v) {
+    settle<T>();
+    T acc = 0;
     SFor<0, NC>::run([&](auto cc) {
         constexpr int Cc = decltype(cc)::value;
-        mac_bc<Cc>(acc, M[Cc], v);
+        acc = acc + mulbc<Cc>(M[Cc], v);
     });
     return acc;
 }

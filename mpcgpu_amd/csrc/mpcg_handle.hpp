@@ -1,7 +1,7 @@
 // mpcg_handle.hpp — what the translation units of libmpcg_hip.so share: the handle behind include/mpcg.h, the error convention, the HIP_TRY
 // macro.  The library is four translation units over this header (Makefile: every csrc/*.hip is compiled on its own and linked once):
 //   mpcg_pcg.hip        handle / options / the PCG launch policy and entry points (pcg_*.hip.h kernels)
-//   mpcg_producers.hip  Schur + preconditioner formation, dz recovery, CSR emitter, block-tridiagonal direct solve (schur_*.hip.h, block_solve.hip.h, block_solve_f64.hip.h;
+//   mpcg_producers.hip  Schur + preconditioner formation, dz recovery, CSR emitter, block-tridiagonal direct solve (schur_*.hip.h, block_solve.hip.h;
 //                       any other (state_size, control_size) than 14 x 7: schur_generic.hip.h)
 //   mpcg_plant.hip      the robot as data + KKT block assembly (kkt_plant.hip.h), merit function + line-search step (merit_plant.hip.h, merit_plant_f32.hip.h),
 //                       plant simulation + horizon shift (sim_plant.hip.h)
@@ -47,7 +47,7 @@ struct mpcg_handle {
     int lqk = -1;             // lane-quad-per-knot kernel in double (pcg_lqk_f64.hip.h, N <= 64): -1 auto (32 < N <= 64 once the latch says block-symmetric), 0 off, 1 forced
     int lpk = -1;             // lane-pair-per-knot kernel (pcg_lpk.hip.h, N <= 128): -1 auto (36 < N <= 128 beyond the row-per-lane kernel's calls), 0 off, 1 forced
     int block_solve_wide = -1; // mpcg_block_solve: one trajectory per wavefront (1), four (0), by batch size (-1)
-    int block_solve_f64 = 0;  // mpcg_block_solve: 1 = float S / gamma widened on load, the sweep in double (block_solve_f64.hip.h), lambda rounded once on store; 0 = the float sweep
+    int block_solve_f64 = 0;  // mpcg_block_solve: 1 = float S / gamma widened on load, the sweep in double (block_solve.hip.h), lambda rounded once on store; 0 = the float sweep
     int schur_dpp = 1;        // 1: register-resident Schur formation (schur_walk.hip.h: the chunk-walking kernel + its seam kernel), 0: the LDS kernels (schur_generic.hip.h)
     int sched_hint = 1;       // dispatch the trajectories of a large call longest-expected-first, predicted by the previous call's iteration counts (sched_order_kernel)
     uint32_t* sched_order = nullptr;   // [1 + max_batch] {batch it was made for, dispatch order}: written after every hinted solve, checked on the device
@@ -90,7 +90,7 @@ struct mpcg_handle {
     int spmv_blocks_per_cu = 3;    // (sweep at 4096 trajectories = 1.2 GB of S, a true HBM stream: profiles/r04_spmv.txt; until round 4: 4)
     int spmv_mfma = 0;        // 1 = the MFMA experiment kernel for mpcg_bt_spmv
     float* block_scratch = nullptr;  // W_k, z_k of mpcg_block_solve: max_batch x N x (n^2 + n) floats (first call)
-    double* block_scratch64 = nullptr;   // the same for mpcg_block_solve_f64 and "block_solve_f64" = 1, in doubles (their first call); block_scratch is never touched by them
+    double* block_scratch64 = nullptr;   // the same for the sweeps in double, mpcg_block_solve_f64 and "block_solve_f64" = 1 (their first call): block_solve_impl<CT, ...> picks by CT, neither buffer is shared
     float* ginv_scratch = nullptr;   // staging for the in-place G <- G^-1 of mpcg_form_schur: max_batch x ((n^2 + m^2) N - m^2), m the largest control_size seen
     size_t ginv_scratch_floats = 0;
     double* ginv_scratch_f64 = nullptr;   // the same for mpcg_form_schur_f64

@@ -1,9 +1,10 @@
 // mpcg_producers.hip — C ABI (include/mpcg.h) of the steps either side of the solve: Schur + preconditioner formation, dz
 // recovery (float and linsys_t = double), the CSR emitter of the QDLDL path and the block-tridiagonal direct solve.  Two sets of gfx950
-// kernels serve them: the register-resident ones of schur_walk.hip.h / schur_walk_f64.hip.h / block_solve.hip.h / block_solve_f64.hip.h (the tuned 14 x 7 shape,
+// kernels serve them: the register-resident ones of schur_walk.hip.h / schur_walk_f64.hip.h / block_solve.hip.h (the tuned 14 x 7 shape,
 // the default there) and the run-time-dimension LDS kernels of schur_generic.hip.h (every other 1 <= control_size <= state_size <= 64; at
 // 14 x 7 under "schur_dpp" / "dz_dpp" = 0 or "producers_generic" = 1, and for calls beyond the register-resident kernels' 31-bit offsets).
-// Formation and dz have ONE host path each, form_schur_impl<T> and compute_dz_impl<T>; ProducerTraits<T> holds what float and double differ in.
+// Formation, dz and the direct solve have ONE host path each, form_schur_impl<T>, compute_dz_impl<T> and block_solve_impl<CT, ST>; ProducerTraits<T>
+// holds what float and double differ in.
 #include "mpcg_handle.hpp"
 #ifndef MPCG_DZ64_CAPMUL
 #define MPCG_DZ64_CAPMUL 4      // (grid cap of compute_dz_dpp_f64_kernel in units of 64 workgroups per CU; tools/_prof/dz64_ab.py)
@@ -12,7 +13,6 @@
 #include "schur_walk.hip.h"
 #include "schur_walk_f64.hip.h"
 #include "block_solve.hip.h"
-#include "block_solve_f64.hip.h"
 
 using namespace mpcg;
 
@@ -85,6 +85,7 @@ template <> struct ProducerTraits<float> {
     static constexpr auto dz_dpp_kernel = sw::compute_dz_dpp_kernel;
     static constexpr auto staging = &mpcg_handle::ginv_scratch;
     static constexpr auto staging_elems = &mpcg_handle::ginv_scratch_floats;
+    static constexpr auto block_scratch = &mpcg_handle::block_scratch;
     static constexpr long dz_capmul = 4;
 };
 template <> struct ProducerTraits<double> {
@@ -95,6 +96,7 @@ template <> struct ProducerTraits<double> {
     static constexpr auto dz_dpp_kernel = sw64::compute_dz_dpp_f64_kernel;
     static constexpr auto staging = &mpcg_handle::ginv_scratch_f64;
     static constexpr auto staging_elems = &mpcg_handle::ginv_scratch_f64_elems;
+    static constexpr auto block_scratch = &mpcg_handle::block_scratch64;
     // (126 VGPRs, four wavefronts per SIMD against the float kernel's seven: capped at 1 the 1024 x 128 call ran two quads per workgroup,
     //  0.1165-0.1175 ms against 0.1126-0.1128 with the float kernel's cap, tools/_prof/dz64_ab.py)
     static constexpr long dz_capmul = MPCG_DZ64_CAPMUL;
@@ -243,33 +245,45 @@ static int compute_dz_impl(mpcg_handle* h, const char* fn, uint32_t control_size
     return MPCG_OK;
 }
 
-// The direct solve with the sweep in double: mpcg_block_solve_f64 (ST = double) and mpcg_block_solve under "block_solve_f64" = 1 (ST = float:
-// widened on load, lambda rounded once on store).  W_k, z_k go through block_scratch64, a buffer of its own: the float solve's block_scratch is
-// never resized, freed or shared — a float solve captured into a graph has that pointer baked in.
-template <typename ST>
-static int block_solve64_impl(mpcg_handle* h, const char* fn, const ST* d_S, const ST* d_gamma, ST* d_lambda, uint32_t batch, void* stream) {
+// The direct solve, ONE host path: CT is the sweep type, ST the storage type of S, gamma and lambda (CT = double, ST = float: widened on load,
+// lambda rounded once on store).  W_k, z_k go through block_scratch (CT = float) or block_scratch64 (CT = double), two buffers of their own,
+// each allocated on its first use: neither is ever resized, freed or shared — a solve captured into a graph has its pointer baked in.
+template <typename CT, typename ST>
+static int block_solve_impl(mpcg_handle* h, const char* fn, const ST* d_S, const ST* d_gamma, ST* d_lambda, uint32_t batch, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
     if (!d_S || !d_gamma || !d_lambda) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!h->block_scratch64) {                    // first call only (not stream-ordered: hipMalloc)
+    CT*& work = h->*ProducerTraits<CT>::block_scratch;
+    if (!work) {                                  // first call only (not stream-ordered: hipMalloc)
         const int rc = alloc_allowed(h, st, fn); if (rc != MPCG_OK) return rc;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->block_scratch64),
-                             (size_t)h->max_batch * h->N * ((size_t)h->n * h->n + h->n) * sizeof(double)));      // W_k (n x n) + z_k per knot
+        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&work),
+                             (size_t)h->max_batch * h->N * ((size_t)h->n * h->n + h->n) * sizeof(CT)));          // W_k (n x n) + z_k per knot
     }
     if (h->generic || h->producers_generic) {         // any state size: one workgroup per trajectory, operands in LDS (schur_generic.hip.h)
-        gen::BlockSolveGenArgsT<double, ST> ga{d_S, d_gamma, d_lambda, h->block_scratch64, (int)h->n, (int)h->N, (int)batch};
-        const size_t lds = gen::block_solve_lds_elems((int)h->n) * sizeof(double);      // 133,664 bytes at n = 64
-        { const int rc = gen_raise_lds(h, gen::bt_block_solve_kernel<double, ST>, lds); if (rc != MPCG_OK) return rc; }
-        hipLaunchKernelGGL((gen::bt_block_solve_kernel<double, ST>), dim3(batch), dim3(gen_threads((int)h->n)), lds, st, ga);
+        gen::BlockSolveGenArgsT<CT, ST> ga{d_S, d_gamma, d_lambda, work, (int)h->n, (int)h->N, (int)batch};
+        const size_t lds = gen::block_solve_lds_elems((int)h->n) * sizeof(CT);          // 133,664 bytes in double at n = 64
+        { const int rc = gen_raise_lds(h, gen::bt_block_solve_kernel<CT, ST>, lds); if (rc != MPCG_OK) return rc; }
+        hipLaunchKernelGGL((gen::bt_block_solve_kernel<CT, ST>), dim3(batch), dim3(gen_threads((int)h->n)), lds, st, ga);
         HIP_TRY(h, hipGetLastError());
         return MPCG_OK;
     }
-    // one trajectory per wavefront at every batch ("block_solve_wide" is not read: block_solve_f64.hip.h)
-    bs64::BlockSolve64Args<ST> a{d_S, d_gamma, d_lambda, h->block_scratch64, (int)h->N, (int)batch};
-    hipLaunchKernelGGL(bs64::bt_block_solve_f64_kernel<ST>, dim3(batch), dim3(64), 0, st, a);
+    const BlockSolveArgsT<CT, ST> a{d_S, d_gamma, d_lambda, work, (int)h->N, (int)batch};
+    if constexpr (std::is_same<CT, float>::value) {
+        // few trajectories: one per wavefront (columns dealt over the four DPP rows, ~2.5x shorter critical path);
+        // many: four per wavefront.  Same bits either way.  "block_solve_wide": -1 auto, 0 / 1 forced.
+        // (N=128: one per wave 0.35 / 0.53 ms at batch 1024 / 2048 against 0.71 / 0.75; at 4096 four per wave wins, 0.88 vs 0.93)
+        const bool wide = h->block_solve_wide < 0 ? batch <= 12u * (uint32_t)h->num_cus : h->block_solve_wide != 0;
+        if (!wide) {
+            hipLaunchKernelGGL(bt_block_solve_kernel, dim3((batch + 3) / 4), dim3(64), 0, st, a);
+            HIP_TRY(h, hipGetLastError());
+            return MPCG_OK;
+        }
+    }
+    // (CT = double: one trajectory per wavefront at every batch, "block_solve_wide" is not read: block_solve.hip.h)
+    hipLaunchKernelGGL((bt_block_solve_wide_kernel<CT, ST>), dim3(batch), dim3(64), 0, st, a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
@@ -278,39 +292,12 @@ extern "C" {
 
 int mpcg_block_solve(mpcg_handle* h, const float* d_S, const float* d_gamma, float* d_lambda, uint32_t batch, void* stream) {
     if (!h) return MPCG_ERR_INVALID;
-    if (h->block_solve_f64) return block_solve64_impl<float>(h, "mpcg_block_solve", d_S, d_gamma, d_lambda, batch, stream);
-    if (!d_S || !d_gamma || !d_lambda) return fail(h, MPCG_ERR_INVALID, "mpcg_block_solve: null device pointer");
-    if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_block_solve: batch exceeds max_batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->block_scratch) {                      // first call only (not stream-ordered: hipMalloc)
-        const int rc = alloc_allowed(h, static_cast<hipStream_t>(stream), "mpcg_block_solve"); if (rc != MPCG_OK) return rc;
-    }
-    if (!h->block_scratch)
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->block_scratch),
-                             (size_t)h->max_batch * h->N * ((size_t)h->n * h->n + h->n) * sizeof(float)));       // W_k (n x n) + z_k per knot
-    if (h->generic || h->producers_generic) {         // any state size: one workgroup per trajectory, operands in LDS (schur_generic.hip.h)
-        gen::BlockSolveGenArgs ga{d_S, d_gamma, d_lambda, h->block_scratch, (int)h->n, (int)h->N, (int)batch};
-        const size_t lds = gen::block_solve_lds_elems((int)h->n) * sizeof(float);
-        { const int rc = gen_raise_lds(h, gen::bt_block_solve_kernel<float>, lds); if (rc != MPCG_OK) return rc; }
-        hipLaunchKernelGGL(gen::bt_block_solve_kernel<float>, dim3(batch), dim3(gen_threads((int)h->n)), lds, static_cast<hipStream_t>(stream), ga);
-        HIP_TRY(h, hipGetLastError());
-        return MPCG_OK;
-    }
-    BlockSolveArgs a;
-    a.S = d_S; a.gamma = d_gamma; a.lambda = d_lambda; a.work = h->block_scratch; a.N = (int)h->N; a.batch = (int)batch;
-    // few trajectories: one per wavefront (columns dealt over the four DPP rows, ~2.5x shorter critical path);
-    // many: four per wavefront.  Same bits either way.  "block_solve_wide": -1 auto, 0 / 1 forced.
-    // (N=128: one per wave 0.35 / 0.53 ms at batch 1024 / 2048 against 0.71 / 0.75; at 4096 four per wave wins, 0.88 vs 0.93)
-    const bool wide = h->block_solve_wide < 0 ? batch <= 12u * (uint32_t)h->num_cus : h->block_solve_wide != 0;
-    if (wide) hipLaunchKernelGGL(bt_block_solve_wide_kernel, dim3(batch), dim3(64), 0, static_cast<hipStream_t>(stream), a);
-    else hipLaunchKernelGGL(bt_block_solve_kernel, dim3((batch + 3) / 4), dim3(64), 0, static_cast<hipStream_t>(stream), a);
-    HIP_TRY(h, hipGetLastError());
-    return MPCG_OK;
+    if (h->block_solve_f64) return block_solve_impl<double, float>(h, "mpcg_block_solve", d_S, d_gamma, d_lambda, batch, stream);
+    return block_solve_impl<float, float>(h, "mpcg_block_solve", d_S, d_gamma, d_lambda, batch, stream);
 }
 
 int mpcg_block_solve_f64(mpcg_handle* h, const double* d_S, const double* d_gamma, double* d_lambda, uint32_t batch, void* stream) {
-    return block_solve64_impl<double>(h, "mpcg_block_solve_f64", d_S, d_gamma, d_lambda, batch, stream);
+    return block_solve_impl<double, double>(h, "mpcg_block_solve_f64", d_S, d_gamma, d_lambda, batch, stream);
 }
 
 int mpcg_form_schur(mpcg_handle* h, uint32_t control_size, float* d_G_dense, const float* d_C_dense, const float* d_g,

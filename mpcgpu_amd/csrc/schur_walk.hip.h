@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "schur_generic.hip.h"
+#include "dpp_rows.hip.h"
 
 namespace mpcg {
 namespace sw {
@@ -62,19 +63,7 @@ __device__ __forceinline__ float rbc(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150 + L, 0xf, 0xf, true));
 }
 
-template <int I, int E>
-struct SFor {
-    template <class F>
-    static __device__ __forceinline__ void run(F&& f) {
-        f(std::integral_constant<int, I>{});
-        SFor<I + 1, E>::run(f);
-    }
-};
-template <int E>
-struct SFor<E, E> {
-    template <class F>
-    static __device__ __forceinline__ void run(F&&) {}
-};
+using sdpp::SFor;
 
 constexpr int np(int nc) { return (nc + 1) / 2; }
 // phase boundary: the scheduler may not move instructions across it (left alone it interleaves the independent inversions and products of

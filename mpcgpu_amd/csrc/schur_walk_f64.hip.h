@@ -26,18 +26,9 @@ using sw::rsrc_t;
 using sw::SFor;
 using sw::SW_OOB;
 
-// a * (b held by lane L of this lane's 16-lane row): v_mov_b64_dpp + a rounded multiply.  (gfx950 has DPP forms of v_mov_b64 and v_fmac_f64
-// only — v_mul_f64 / v_add_f64 are VOP3 — and the fused multiply-add is not what the oracle computes.)
-template <int L>
-__device__ __forceinline__ double mulbc(double a, double b) {
-    double r;
-    asm("v_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(b), "n"(L));
-    return a * r;
-}
-#define SW64_FENCE() __builtin_amdgcn_sched_barrier(0)
-// Two wait states between the last VALU write of an operand and its first DPP read: nothing is scheduled across this point, and the s_nop 1
-// stands between whatever wrote the operands before it and the DPP multiplies behind it (verified on the built code: tools/check_dpp_hazards.py).
-#define SW64_SETTLE() do { SW64_FENCE(); asm volatile("s_nop 1"); SW64_FENCE(); } while (0)
+// a * (b held by lane L of this lane's 16-lane row), SW64_FENCE() and SW64_SETTLE(): dpp_rows.hip.h, shared with the direct solve
+using sdpp::mulbc;
+using sdpp::matvec;
 
 // A private copy of a broadcast operand that the optimiser cannot identify with the original (as sw::launder): two products that broadcast
 // the same entries of the same operand (Dk L and Dm L^T) would otherwise share ONE v_mov_b64_dpp per entry, kept alive from the first product
@@ -78,18 +69,6 @@ __device__ __forceinline__ void gemm_nt(const double (&A)[NI], const double (&Bt
         Cm[Cc] = acc;
     });
 }
-// out[r] = sum_c M[r][c] * v[c]          v: element c in lane c
-template <int NC>
-__device__ __forceinline__ double matvec(const double (&M)[NC], double v) {
-    SW64_SETTLE();
-    double acc = 0.0;
-    SFor<0, NC>::run([&](auto cc) {
-        constexpr int Cc = decltype(cc)::value;
-        acc = acc + mulbc<Cc>(M[Cc], v);
-    });
-    return acc;
-}
-
 // One pivot step of the Gauss-Jordan elimination of [A | I] (include/utils/matrix.cuh:120-238), rows in lanes, as sw::gj_step: columns of A at
 // or left of the pivot and columns of I right of it are inert and skipped; the pivot row is scaled by a per-lane multiplier (1 / pivot in the
 // pivot lane, exactly 1.0 elsewhere), then every lane adds (-pcol) x (pivot row entry) with +0.0 as the pivot lane's multiplier.

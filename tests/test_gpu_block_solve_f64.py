@@ -1,7 +1,7 @@
 """GPU: the block-tridiagonal direct solve with the sweep in double — mpcg_block_solve_f64 (linsys_t = double) and option
 "block_solve_f64" = 1 of the float entry (float S / gamma widened on load, lambda rounded to float once on store) — against the CPU
 oracle's restatement of the sweep, which dispatches on the dtype of S: the same operation order on both sides, so every comparison is BIT
-FOR BIT.  State size 14 runs the register-resident kernel of csrc/block_solve_f64.hip.h (one trajectory per wavefront at every batch; the
+FOR BIT.  State size 14 runs the register-resident kernel of csrc/block_solve.hip.h (one trajectory per wavefront at every batch; the
 four-per-wavefront layout is not built in double, "block_solve_wide" is not read), every other state size — and 14 under
 "producers_generic" = 1 — the run-time-dimension LDS kernel of csrc/schur_generic.hip.h in double."""
 import ctypes as C

@@ -8,7 +8,7 @@ After 50 ms of back-to-back warm-up launches of all three: device events around 
 Before the timing the three results are compared against the float64 result (relative to max |lambda|).  One JSON line per shape.
 No ratio is promised: a knot's elimination is a dependent chain of fp64 operations at half the fp32 issue rate, with twice the scratch
 traffic.  Needs an MI355X:
-    python tools/time_block_solve_f64.py [reps]
+    [AB_LIB=<another build's libmpcg_hip.so>] python tools/time_block_solve_f64.py [reps]
 (tools/time_block_solve.py is the older comparison of the float solve against PCG.)"""
 import json
 import os
@@ -22,7 +22,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from mpcgpu_amd import PcgSolver  # noqa: E402
+from mpcgpu_amd import PcgSolver, _lib as _L  # noqa: E402
+if os.environ.get("AB_LIB"):                      # A/B against another build of the library
+    _L.LIB_PATH = os.environ["AB_LIB"]
 
 WINDOWS = 7
 
