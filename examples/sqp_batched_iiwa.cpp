@@ -9,8 +9,11 @@
 // 1.2, a success divides them, rho > 10 gives the trajectory up and resets rho) — still without a synchronisation inside an iteration; the JSON line
 // then also carries "rho_final", "drho_final" and "done" per trajectory.  --merit-f32 sets option "merit_f32" = 1 on the handle: every mpcg_compute_merit
 // of the run evaluates its point merits in packed float (the reference's own arithmetic; merits within 1e-5 max(1, |merit|) of the default's).
+// Compiled with -DUSE_DOUBLES (examples/sqp_batched_iiwa_f64; linsys_t = double, the reference's USE_DOUBLES build) the six calls are the library's double entry
+// points — mpcg_generate_kkt_f64 -> mpcg_form_schur(_rhov)_f64 -> mpcg_pcg_solve_f64 -> mpcg_compute_dz_f64 -> mpcg_compute_merit_f64 ->
+// mpcg_line_search_step(_rho)_f64 — on the same inputs widened to double; the merits are then printed with 17 digits.  --merit-f32 has no effect there.
 // Prints one JSON line; exits 0 only if every trajectory's merit went down.
-//   hipcc --offload-arch=gfx950 -O2 -Iinclude examples/sqp_batched_iiwa.cpp -Lmpcgpu_amd -lmpcg_hip
+//   hipcc --offload-arch=gfx950 -O2 [-DUSE_DOUBLES] -Iinclude examples/sqp_batched_iiwa.cpp -Lmpcgpu_amd -lmpcg_hip
 //   sqp_batched_iiwa [--batch 8] [--knots 32] [--iters 4] [--mu 10] [--rho 1e-3] [--adapt-rho] [--merit-f32]
 #include <hip/hip_runtime.h>
 
@@ -19,9 +22,21 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "mpcg.h"
+
+// linsys_t as in the reference's include/common/settings.cuh:41-49; LS(entry) is the library entry point of that type
+#ifdef USE_DOUBLES
+typedef double linsys_t;
+#define LS(entry) entry##_f64
+#define MERIT_FMT "%.17g"
+#else
+typedef float linsys_t;
+#define LS(entry) entry
+#define MERIT_FMT "%.9g"
+#endif
 
 static const int n = 14, m = 7, ROWW = 27, ROWS = 400;      // a row of the data file: x (14), u (7), end-effector pose (6)
 
@@ -59,7 +74,7 @@ static T* dalloc(size_t count) {
 
 int main(int argc, char** argv) {
     int B = 8, N = 32, K = 4;
-    float mu = 10.f, rho = 1e-3f;
+    linsys_t mu = 10.f, rho = (linsys_t)1e-3;
     bool adapt = false, merit_f32 = false;
     for (int i = 1; i < argc; i += 2) {
         if (!strcmp(argv[i], "--adapt-rho")) { adapt = true; --i; continue; }
@@ -68,12 +83,12 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i], "--batch")) B = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--knots")) N = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--iters")) K = atoi(argv[i + 1]);
-        else if (!strcmp(argv[i], "--mu")) mu = (float)atof(argv[i + 1]);
-        else if (!strcmp(argv[i], "--rho")) rho = (float)atof(argv[i + 1]);
+        else if (!strcmp(argv[i], "--mu")) mu = (linsys_t)atof(argv[i + 1]);
+        else if (!strcmp(argv[i], "--rho")) rho = (linsys_t)atof(argv[i + 1]);
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (B < 1 || N < 2 || N + 1 > ROWS || K < 1) { fprintf(stderr, "need batch >= 1, 2 <= knots < %d, iters >= 1\n", ROWS); return 2; }
-    const float dt = 1.0f / 64, qd_cost = 1e-4f, r_cost = N == 64 ? 1e-3f : 1e-4f;      // include/common/settings.cuh:84-94
+    const linsys_t dt = 1.0f / 64, qd_cost = (linsys_t)1e-4, r_cost = (linsys_t)(N == 64 ? 1e-3 : 1e-4);      // include/common/settings.cuh:84-94
     const size_t L = (size_t)(n + m) * N - m;
     const std::vector<float> rows = load_rows(argv[0]);
 
@@ -101,61 +116,62 @@ int main(int argc, char** argv) {
     if (mpcg_plant_create_iiwa14(&plant, -1) != MPCG_OK) { fprintf(stderr, "mpcg_plant_create_iiwa14: %s\n", mpcg_last_error(nullptr)); return 1; }
 
     const size_t nn = n * n, mm = m * m, nm = n * m;
-    float* d_xu = dalloc<float>((size_t)B * L);
-    float* d_goals = dalloc<float>(goals.size());
-    float* d_xs = dalloc<float>(xs.size());
-    float* d_G = dalloc<float>((size_t)B * ((nn + mm) * N - mm));
-    float* d_C = dalloc<float>((size_t)B * (nn + nm) * (N - 1));
-    float* d_g = dalloc<float>((size_t)B * L);
-    float* d_c = dalloc<float>((size_t)B * n * N);
-    float* d_S = dalloc<float>((size_t)B * 3 * nn * N);
-    float* d_Pinv = dalloc<float>((size_t)B * 3 * nn * N);
-    float* d_gamma = dalloc<float>((size_t)B * n * N);
-    float* d_lambda = dalloc<float>((size_t)B * n * N);
-    float* d_dz = dalloc<float>((size_t)B * L);
-    float* d_merit = dalloc<float>((size_t)B * 8);
-    float* d_merit_ref = dalloc<float>(B);
-    float* d_merit_hist = dalloc<float>((size_t)(K + 1) * B);
+    linsys_t* d_xu = dalloc<linsys_t>((size_t)B * L);
+    linsys_t* d_goals = dalloc<linsys_t>(goals.size());
+    linsys_t* d_xs = dalloc<linsys_t>(xs.size());
+    linsys_t* d_G = dalloc<linsys_t>((size_t)B * ((nn + mm) * N - mm));
+    linsys_t* d_C = dalloc<linsys_t>((size_t)B * (nn + nm) * (N - 1));
+    linsys_t* d_g = dalloc<linsys_t>((size_t)B * L);
+    linsys_t* d_c = dalloc<linsys_t>((size_t)B * n * N);
+    linsys_t* d_S = dalloc<linsys_t>((size_t)B * 3 * nn * N);
+    linsys_t* d_Pinv = dalloc<linsys_t>((size_t)B * 3 * nn * N);
+    linsys_t* d_gamma = dalloc<linsys_t>((size_t)B * n * N);
+    linsys_t* d_lambda = dalloc<linsys_t>((size_t)B * n * N);
+    linsys_t* d_dz = dalloc<linsys_t>((size_t)B * L);
+    linsys_t* d_merit = dalloc<linsys_t>((size_t)B * 8);
+    linsys_t* d_merit_ref = dalloc<linsys_t>(B);
+    linsys_t* d_merit_hist = dalloc<linsys_t>((size_t)(K + 1) * B);
     int32_t* d_step_hist = dalloc<int32_t>((size_t)K * B);
     uint32_t* d_iters = dalloc<uint32_t>(B);
     uint8_t* d_exit = dalloc<uint8_t>(B);
     // --adapt-rho: the per-trajectory state of the rho adaptation (rho = the initial value, drho = 1, nobody finished)
-    float* d_rho = dalloc<float>(B);
-    float* d_drho = dalloc<float>(B);
+    linsys_t* d_rho = dalloc<linsys_t>(B);
+    linsys_t* d_drho = dalloc<linsys_t>(B);
     uint8_t* d_done = dalloc<uint8_t>(B);
     {
-        const std::vector<float> rho0((size_t)B, rho), one((size_t)B, 1.0f);
-        HIP_OK(hipMemcpy(d_rho, rho0.data(), B * sizeof(float), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(d_drho, one.data(), B * sizeof(float), hipMemcpyHostToDevice));
+        const std::vector<linsys_t> rho0((size_t)B, rho), one((size_t)B, 1);
+        HIP_OK(hipMemcpy(d_rho, rho0.data(), B * sizeof(linsys_t), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_drho, one.data(), B * sizeof(linsys_t), hipMemcpyHostToDevice));
     }
-    HIP_OK(hipMemcpy(d_xu, xu.data(), xu.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_goals, goals.data(), goals.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_xs, xs.data(), xs.size() * sizeof(float), hipMemcpyHostToDevice));
+    for (auto pr : {std::make_pair(d_xu, &xu), std::make_pair(d_goals, &goals), std::make_pair(d_xs, &xs)}) {      // the float inputs, widened under USE_DOUBLES
+        const std::vector<linsys_t> w(pr.second->begin(), pr.second->end());
+        HIP_OK(hipMemcpy(pr.first, w.data(), w.size() * sizeof(linsys_t), hipMemcpyHostToDevice));
+    }
 
     hipStream_t st;
     HIP_OK(hipStreamCreate(&st));
-    float steps[8];
+    linsys_t steps[8];
     for (int p = 0; p < 8; ++p) steps[p] = -1.0f / (float)(1 << p);          // alpha = -1 / 2^p (include/common/merit.cuh:47)
-    const float zero = 0.f;
+    const linsys_t zero = 0;
     // the merit of the start iterate: the reference's compute_merit (include/pcg/sqp.cuh:171-187) — with the initial-state term, like the eight trials
-    MPCG_OK_OR_DIE(h, mpcg_compute_merit(h, plant, m, dt, d_goals, d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, (uint32_t)B, st));
-    HIP_OK(hipMemcpyAsync(d_merit_hist, d_merit_ref, B * sizeof(float), hipMemcpyDeviceToDevice, st));
+    MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant, m, dt, d_goals, d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, (uint32_t)B, st));
+    HIP_OK(hipMemcpyAsync(d_merit_hist, d_merit_ref, B * sizeof(linsys_t), hipMemcpyDeviceToDevice, st));
     for (int it = 0; it < K; ++it) {                                          // no host synchronisation in here
-        MPCG_OK_OR_DIE(h, mpcg_generate_kkt(h, plant, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, st));
-        if (adapt) MPCG_OK_OR_DIE(h, mpcg_form_schur_rhov(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_rho, (uint32_t)B, MPCG_PRECOND_SS, st));
-        else MPCG_OK_OR_DIE(h, mpcg_form_schur(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, rho, (uint32_t)B, MPCG_PRECOND_SS, st));
-        MPCG_OK_OR_DIE(h, mpcg_pcg_solve(h, d_S, d_Pinv, d_gamma, d_lambda, (uint32_t)B, 3000, 1e-7f, MPCG_PRECOND_SS, d_iters, d_exit, st));
-        MPCG_OK_OR_DIE(h, mpcg_compute_dz(h, m, d_G, d_C, d_g, d_lambda, d_dz, (uint32_t)B, st));
-        MPCG_OK_OR_DIE(h, mpcg_compute_merit(h, plant, m, dt, d_goals, d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, (uint32_t)B, st));
-        if (adapt) MPCG_OK_OR_DIE(h, mpcg_line_search_step_rho(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step_hist + (size_t)it * B, d_rho, d_drho, d_done,
-                                                               1.2f, 1e-3f, 10.f, rho, (uint32_t)B, st));
-        else MPCG_OK_OR_DIE(h, mpcg_line_search_step(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step_hist + (size_t)it * B, (uint32_t)B, st));
-        HIP_OK(hipMemcpyAsync(d_merit_hist + (size_t)(it + 1) * B, d_merit_ref, B * sizeof(float), hipMemcpyDeviceToDevice, st));
+        MPCG_OK_OR_DIE(h, LS(mpcg_generate_kkt)(h, plant, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, st));
+        if (adapt) MPCG_OK_OR_DIE(h, LS(mpcg_form_schur_rhov)(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_rho, (uint32_t)B, MPCG_PRECOND_SS, st));
+        else MPCG_OK_OR_DIE(h, LS(mpcg_form_schur)(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, rho, (uint32_t)B, MPCG_PRECOND_SS, st));
+        MPCG_OK_OR_DIE(h, LS(mpcg_pcg_solve)(h, d_S, d_Pinv, d_gamma, d_lambda, (uint32_t)B, 3000, (linsys_t)1e-7, MPCG_PRECOND_SS, d_iters, d_exit, st));
+        MPCG_OK_OR_DIE(h, LS(mpcg_compute_dz)(h, m, d_G, d_C, d_g, d_lambda, d_dz, (uint32_t)B, st));
+        MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant, m, dt, d_goals, d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, (uint32_t)B, st));
+        if (adapt) MPCG_OK_OR_DIE(h, LS(mpcg_line_search_step_rho)(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step_hist + (size_t)it * B, d_rho, d_drho, d_done,
+                                                               (linsys_t)1.2, (linsys_t)1e-3, (linsys_t)10, rho, (uint32_t)B, st));
+        else MPCG_OK_OR_DIE(h, LS(mpcg_line_search_step)(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step_hist + (size_t)it * B, (uint32_t)B, st));
+        HIP_OK(hipMemcpyAsync(d_merit_hist + (size_t)(it + 1) * B, d_merit_ref, B * sizeof(linsys_t), hipMemcpyDeviceToDevice, st));
     }
     HIP_OK(hipStreamSynchronize(st));
-    std::vector<float> hist((size_t)(K + 1) * B);
+    std::vector<linsys_t> hist((size_t)(K + 1) * B);
     std::vector<int32_t> expo((size_t)K * B);
-    HIP_OK(hipMemcpy(hist.data(), d_merit_hist, hist.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(hist.data(), d_merit_hist, hist.size() * sizeof(linsys_t), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(expo.data(), d_step_hist, expo.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
 
     bool ok = true;
@@ -163,7 +179,7 @@ int main(int argc, char** argv) {
     printf("{\"batch\": %d, \"knots\": %d, \"iters\": %d, \"mu\": %g, \"rho\": %g, \"merit\": [", B, N, K, (double)mu, (double)rho);
     for (int b = 0; b < B; ++b) {
         printf("%s[", b ? ", " : "");
-        for (int it = 0; it <= K; ++it) printf("%s%.9g", it ? ", " : "", (double)hist[(size_t)it * B + b]);
+        for (int it = 0; it <= K; ++it) printf("%s" MERIT_FMT, it ? ", " : "", (double)hist[(size_t)it * B + b]);
         printf("]");
     }
     printf("], \"exponents\": [");
@@ -173,15 +189,15 @@ int main(int argc, char** argv) {
         printf("]");
     }
     if (adapt) {
-        std::vector<float> rho_f(B), drho_f(B);
+        std::vector<linsys_t> rho_f(B), drho_f(B);
         std::vector<uint8_t> done_f(B);
-        HIP_OK(hipMemcpy(rho_f.data(), d_rho, B * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(drho_f.data(), d_drho, B * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(rho_f.data(), d_rho, B * sizeof(linsys_t), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(drho_f.data(), d_drho, B * sizeof(linsys_t), hipMemcpyDeviceToHost));
         HIP_OK(hipMemcpy(done_f.data(), d_done, B * sizeof(uint8_t), hipMemcpyDeviceToHost));
         printf("], \"rho_final\": [");
-        for (int b = 0; b < B; ++b) printf("%s%.9g", b ? ", " : "", (double)rho_f[b]);
+        for (int b = 0; b < B; ++b) printf("%s" MERIT_FMT, b ? ", " : "", (double)rho_f[b]);
         printf("], \"drho_final\": [");
-        for (int b = 0; b < B; ++b) printf("%s%.9g", b ? ", " : "", (double)drho_f[b]);
+        for (int b = 0; b < B; ++b) printf("%s" MERIT_FMT, b ? ", " : "", (double)drho_f[b]);
         printf("], \"done\": [");
         for (int b = 0; b < B; ++b) printf("%s%d", b ? ", " : "", (int)done_f[b]);
     }

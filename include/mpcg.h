@@ -41,7 +41,7 @@
  *     passed as void* (NULL = default stream).  Calls are stream-ordered and never synchronise.
  *   - batched entry points take `batch` independent trajectories stored back to back.
  *   - GRAPH CAPTURE.  Every compute entry point is pure stream work and may be captured into a hipGraph.  What the float PCG entry points need
- *     is allocated by mpcg_create; mpcg_form_schur(_f64), mpcg_block_solve(_f64), mpcg_compute_merit and a FORCED "cluster" on a horizon the automatic policy gives to one
+ *     is allocated by mpcg_create; mpcg_form_schur(_f64), mpcg_block_solve(_f64), mpcg_compute_merit(_f64) and a FORCED "cluster" on a horizon the automatic policy gives to one
  *     CU allocate a handle-owned work buffer at their first call (hipMalloc is not stream work): make that call once outside the capture — a
  *     first call on a capturing stream returns MPCG_ERR_INVALID with a message and leaves the capture intact.  linsys_t = double beyond 32
  *     knots (mpcg_pcg_solve_f64 / _ref_f64: cluster kernels with a queue + flags buffer and a double-sized copy of lambda0): mpcg_create makes
@@ -106,7 +106,7 @@ const char *mpcg_build_info(void);
  * the pinned word of the symmetry latch, the copy of d_lambda a cluster follow-up launch starts from (knot_points > 128)
  * and, for handles with at most 8 MB of double iterates, the double cluster kernels' buffers (GRAPH CAPTURE); from their
  * first use on, the staging buffers of mpcg_form_schur(_f64), the seam buffer of the chunk-walking Schur kernel, the
- * sweep scratch of mpcg_block_solve, that of mpcg_block_solve_f64 and the point-merit scratch of mpcg_compute_merit.  max_batch bounds `batch` of later calls.  device < 0 = current device.  One handle per
+ * sweep scratch of mpcg_block_solve, that of mpcg_block_solve_f64 and the point-merit scratch of mpcg_compute_merit(_f64).  max_batch bounds `batch` of later calls.  device < 0 = current device.  One handle per
  * (device, knot_points) and per concurrently used stream: calls on the same handle must not overlap on the host
  * side (launch knobs are chosen per call) and their device work must be ordered (one stream, or events) because
  * they share those buffers; different handles are independent. */
@@ -120,7 +120,7 @@ const char *mpcg_build_info(void);
  *     MPCG_ERR_INVALID.  mpcg_form_schur(_f64) needs one block row's operands, 6 n^2 + 2 n m + 2 m^2 + 12 n + 4 m elements, in 160 KiB of
  *     LDS: every m <= n <= 32 in both precisions (and e.g. 40 x 10); beyond that it returns MPCG_ERR_UNSUPPORTED.  The others serve every
  *     such handle.  batch x knot_points < 2^31.
- * mpcg_bt_spmv, mpcg_pcg_solve_f16, mpcg_generate_kkt, mpcg_compute_merit and mpcg_probe_hbm_read return MPCG_ERR_UNSUPPORTED on a handle with state_size != 14. */
+ * mpcg_bt_spmv, mpcg_pcg_solve_f16, mpcg_generate_kkt(_f64), mpcg_compute_merit(_f64) and mpcg_probe_hbm_read return MPCG_ERR_UNSUPPORTED on a handle with state_size != 14. */
 int mpcg_create(mpcg_handle **out, int device, uint32_t state_size, uint32_t knot_points, uint32_t max_batch);
 int mpcg_destroy(mpcg_handle *h);
 const char *mpcg_last_error(const mpcg_handle *h);   /* h may be NULL: last error of mpcg_create */
@@ -344,6 +344,16 @@ int mpcg_plant_destroy(mpcg_plant *p);
 int mpcg_generate_kkt(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size, float timestep, const float *d_eePos_traj,
                       const float *d_xs, const float *d_xu, float qd_cost, float r_cost, float *d_G_dense, float *d_C_dense,
                       float *d_g, float *d_c, uint32_t batch, void *stream);
+/* mpcg_generate_kkt_f64: the producer of mpcg_form_schur(_rhov)_f64 (linsys_t = double, the reference's USE_DOUBLES build).  The same kernel arithmetic —
+ * float64 inside, either gradient route of "kkt_analytic" — with every array in double: d_xu, d_xs and d_eePos_traj are read as doubles and used as they
+ * are (no pass through float), timestep and the costs arrive as doubles, and the four outputs are the float64 values mpcg_generate_kkt rounds to float on
+ * store — on float-representable inputs, rounding this entry's outputs to float gives mpcg_generate_kkt's bits.  Layouts, errors, batch == 0 and capture
+ * behaviour are mpcg_generate_kkt's: pure stream work from the first call on.  "kkt_f32" does NOT apply to this entry (it selects a float build of the
+ * float entry and is ignored here).  LDS and residency as the float entry's (csrc/kkt_plant.hip.h: a knot's outputs leave through the record region in
+ * three pieces of at most 308 doubles). */
+int mpcg_generate_kkt_f64(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size, double timestep, const double *d_eePos_traj,
+                          const double *d_xs, const double *d_xu, double qd_cost, double r_cost, double *d_G_dense, double *d_C_dense,
+                          double *d_g, double *d_c, uint32_t batch, void *stream);
 
 /* ---- the stage behind dz: merit function and line search on the device ----
  * mpcg_compute_merit replaces the eight cooperative launches of ls_gato_compute_merit (include/common/merit.cuh:16-94, launched at
@@ -417,6 +427,30 @@ int mpcg_line_search_step_rho(mpcg_handle *h, uint32_t control_size, const float
                               int32_t *d_step /* [batch] out */, float *d_rho /* [batch] in/out */, float *d_drho /* [batch] in/out */,
                               uint8_t *d_done /* [batch] in/out */, float rho_factor, float rho_min, float rho_max, float rho_reset,
                               uint32_t batch, void *stream);
+/* The double twins (linsys_t = double): the consumers of mpcg_compute_dz_f64 and the producer of the rho vector mpcg_form_schur_rhov_f64 reads.  Everything
+ * said above holds with every float replaced by double — layouts, side effects, error codes, batch == 0, capture behaviour:
+ *   mpcg_compute_merit_f64         the trial iterate is fma(step, dz, xu) in DOUBLE with one rounding (step 0 reads no dz), the same float64 kernel behind
+ *                                  it, the same scratch (shared with mpcg_compute_merit: whichever is called first allocates it, later calls of either
+ *                                  are pure stream work) and the same fixed sum order; d_merit receives the double row sums themselves, with no final
+ *                                  rounding.  "merit_f32" does NOT apply (it is ignored by this entry).
+ *   mpcg_line_search_step_f64      strict <, the first of equals wins, a NaN never wins; xu = fma(step_sizes[p], dz, xu) — the very double
+ *                                  mpcg_compute_merit_f64 evaluated, so the merit of the new iterate at step size 0 is the new d_merit_ref bit for bit.
+ *   mpcg_line_search_step_rho_f64  the rho rule in double, one rounding per operation (correctly rounded products and quotients, fmax / fmin); the
+ *                                  frozen and give-up semantics are unchanged. */
+int mpcg_compute_merit_f64(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size, double timestep,
+                           const double *d_eePos_traj, const double *d_xs /* may be NULL */, const double *d_xu,
+                           const double *d_dz /* may be NULL if every step size is 0 */,
+                           const double *step_sizes /* HOST, num_steps values, copied into the launch */, uint32_t num_steps,
+                           double mu, double qd_cost, double r_cost, double *d_merit /* [batch][num_steps] */,
+                           uint32_t batch, void *stream);
+int mpcg_line_search_step_f64(mpcg_handle *h, uint32_t control_size, const double *d_merit, const double *step_sizes, uint32_t num_steps,
+                              double *d_merit_ref /* [batch] in/out */, const double *d_dz, double *d_xu /* in/out */,
+                              int32_t *d_step /* [batch] out */, uint32_t batch, void *stream);
+int mpcg_line_search_step_rho_f64(mpcg_handle *h, uint32_t control_size, const double *d_merit, const double *step_sizes, uint32_t num_steps,
+                                  double *d_merit_ref /* [batch] in/out */, const double *d_dz, double *d_xu /* in/out */,
+                                  int32_t *d_step /* [batch] out */, double *d_rho /* [batch] in/out */, double *d_drho /* [batch] in/out */,
+                                  uint8_t *d_done /* [batch] in/out */, double rho_factor, double rho_min, double rho_max, double rho_reset,
+                                  uint32_t batch, void *stream);
 
 /* ---- plant simulation and horizon shift: the step between two SQP solves of the MPC loop (csrc/sim_plant.hip.h) ----
  * What simulateMPC does once per control update (reference include/mpcsim.cuh:288-348), batched, on the device, nothing read back.  Float, state_size

@@ -2,8 +2,8 @@
 // assembly with the robot dynamics, merit / line search, plant simulation + horizon shift).  The shim versions of sqpSolvePcg / sqpSolveQdldl /
 // simulateMPC (include/pcg/sqp.cuh, include/qdldl/sqp.cuh, include/mpcsim.cuh of THIS repo) keep the reference's names, argument lists and
 // return tuples and run the linear-system section on libmpcg_hip; wherever the reference calls one of those stages' kernels they call the
-// function registered here.  All three are in the library now and register themselves for the IIWA-14: use_mpcg_generate_kkt (mpcg_generate_kkt),
-// use_mpcg_line_search (mpcg_compute_merit + mpcg_line_search_step with the alpha / rho logic of include/pcg/sqp.cuh:264-353) and
+// function registered here.  All three are in the library now and register themselves for the IIWA-14: use_mpcg_generate_kkt (mpcg_generate_kkt; T = double:
+// mpcg_generate_kkt_f64), use_mpcg_line_search (mpcg_compute_merit + mpcg_line_search_step, T = double: their _f64 twins, with the alpha / rho logic of include/pcg/sqp.cuh:264-353) and
 // use_mpcg_simulate_and_shift (mpcg_simulate + mpcg_advance_horizon with the host bookkeeping of include/mpcsim.cuh:280-352).  A maintainer porting
 // MPCGPU with another robot registers thin wrappers around the reference's kernels instead; examples/mpcsim_shim_demo.cpp registers a synthetic
 // convex problem.
@@ -66,7 +66,19 @@ inline sqp_stages<T>& stages() {
 // generate_kkt stage — the default when an mpcg_plant is supplied; use_mpcg_line_search below adds the merit function / line search,
 // use_mpcg_simulate_and_shift the plant simulation and the horizon shift.
 // qd_cost / r_cost: QD_COST / R_COST of include/common/settings.cuh:84-94.  Needs gbd_pcg_compat/gpu_pcg.cuh (handle cache) before this header.
+// T = float runs the float entry points, T = double (the reference's USE_DOUBLES build, linsys_t = double) their _f64 twins: mpcg_entries<T> names them.
 #ifdef MPCG_H
+template <typename T> struct mpcg_entries;
+template <> struct mpcg_entries<float> {
+    static constexpr auto generate_kkt = &mpcg_generate_kkt;
+    static constexpr auto compute_merit = &mpcg_compute_merit;
+    static constexpr auto line_search_step = &mpcg_line_search_step;
+};
+template <> struct mpcg_entries<double> {
+    static constexpr auto generate_kkt = &mpcg_generate_kkt_f64;
+    static constexpr auto compute_merit = &mpcg_compute_merit_f64;
+    static constexpr auto line_search_step = &mpcg_line_search_step_f64;
+};
 template <typename T>
 inline void use_mpcg_generate_kkt(mpcg_plant* plant, float qd_cost, float r_cost) {
     auto& st = stages<T>();
@@ -74,8 +86,8 @@ inline void use_mpcg_generate_kkt(mpcg_plant* plant, float qd_cost, float r_cost
     st.generate_kkt = [qd_cost, r_cost](uint32_t state_size, uint32_t control_size, uint32_t knot_points, T* d_G_dense, T* d_C_dense, T* d_g, T* d_c,
                                          void* d_dynMem_const, float timestep, T* d_eePos_traj, T* d_xs, T* d_xu) {
         mpcg_handle* h = mpcg_compat::handle_for(state_size, knot_points);
-        if (mpcg_generate_kkt(h, static_cast<const mpcg_plant*>(d_dynMem_const), control_size, timestep, d_eePos_traj, d_xs, d_xu, qd_cost, r_cost,
-                              d_G_dense, d_C_dense, d_g, d_c, 1, /*stream*/ nullptr) != MPCG_OK)
+        if (mpcg_entries<T>::generate_kkt(h, static_cast<const mpcg_plant*>(d_dynMem_const), control_size, timestep, d_eePos_traj, d_xs, d_xu, qd_cost, r_cost,
+                                          d_G_dense, d_C_dense, d_g, d_c, 1, /*stream*/ nullptr) != MPCG_OK)
             mpcg_compat::die("generate_kkt_submatrices", h);
     };
 }
@@ -91,10 +103,10 @@ inline void use_mpcg_generate_kkt(mpcg_plant* plant, float qd_cost, float r_cost
 // step that does not move x_0 can never win by that term.  Here d_xs is passed to all nine evaluations: one function.
 template <typename T>
 inline void use_mpcg_line_search(float mu, float qd_cost, float r_cost, float timestep) {
-    static_assert(std::is_same<T, float>::value, "use_mpcg_line_search: mpcg_compute_merit / mpcg_line_search_step are float entry points");
+    static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "use_mpcg_line_search: float or double (the _f64 entry points)");
     struct ls_state {
         T *d_goal = nullptr, *d_xs = nullptr;
-        float* d_buf = nullptr;          // merit[8], merit_ref, step: 40 bytes that live as long as the process (the stage table is a static)
+        T* d_buf = nullptr;              // merit[8], merit_ref, step: ten elements that live as long as the process (the stage table is a static)
         T drho = 1;
     };
     auto s = std::make_shared<ls_state>();
@@ -108,24 +120,24 @@ inline void use_mpcg_line_search(float mu, float qd_cost, float r_cost, float ti
     };
     st.globalize_and_step = [s, mu, qd_cost, r_cost, timestep](uint32_t state_size, uint32_t control_size, uint32_t knot_points, T* d_xu, T* d_dz, T& rho,
                                                                 T rho_reset, uint32_t sqp_iter) -> bool {
-        const T rho_factor = 1.2f, rho_max = 10.f, rho_min = 1e-3f;            // include/common/settings.cuh:185-196
+        const T rho_factor = T(1.2), rho_max = T(10), rho_min = T(1e-3);       // include/common/settings.cuh:185-196
         mpcg_handle* h = mpcg_compat::handle_for(state_size, knot_points);
         const mpcg_plant* plant = static_cast<const mpcg_plant*>(stages<T>().dynmem);
-        if (!s->d_buf && hipMalloc(reinterpret_cast<void**>(&s->d_buf), 10 * sizeof(float)) != hipSuccess) mpcg_compat::die("use_mpcg_line_search: hipMalloc", h);
-        float *d_merit = s->d_buf, *d_merit_ref = s->d_buf + 8;
+        if (!s->d_buf && hipMalloc(reinterpret_cast<void**>(&s->d_buf), 10 * sizeof(T)) != hipSuccess) mpcg_compat::die("use_mpcg_line_search: hipMalloc", h);
+        T *d_merit = s->d_buf, *d_merit_ref = s->d_buf + 8;
         int32_t* d_step = reinterpret_cast<int32_t*>(s->d_buf + 9);
-        float steps[8];
+        T steps[8];
         for (int p = 0; p < 8; ++p) steps[p] = -1.0f / (float)(1 << p);       // alpha sign (include/common/merit.cuh:47)
         if (sqp_iter == 0) {                                                   // (:86, :171-187)
             s->drho = 1;
-            const float zero = 0.f;
-            if (mpcg_compute_merit(h, plant, control_size, timestep, s->d_goal, s->d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, 1,
-                                   /*stream*/ nullptr) != MPCG_OK)
+            const T zero = 0;
+            if (mpcg_entries<T>::compute_merit(h, plant, control_size, timestep, s->d_goal, s->d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, 1,
+                                               /*stream*/ nullptr) != MPCG_OK)
                 mpcg_compat::die("compute_merit", h);
         }
-        if (mpcg_compute_merit(h, plant, control_size, timestep, s->d_goal, s->d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, 1, nullptr) != MPCG_OK)
+        if (mpcg_entries<T>::compute_merit(h, plant, control_size, timestep, s->d_goal, s->d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, 1, nullptr) != MPCG_OK)
             mpcg_compat::die("ls_gato_compute_merit", h);                      // (:264-282)
-        if (mpcg_line_search_step(h, control_size, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step, 1, nullptr) != MPCG_OK)
+        if (mpcg_entries<T>::line_search_step(h, control_size, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step, 1, nullptr) != MPCG_OK)
             mpcg_compat::die("line_search_step", h);                           // (:292-301, :317, :332-338, :352)
         int32_t p = -1;
         if (hipMemcpy(&p, d_step, sizeof(p), hipMemcpyDeviceToHost) != hipSuccess) mpcg_compat::die("use_mpcg_line_search: hipMemcpy", h);

@@ -27,7 +27,7 @@ DEMO_BINS = {1: _ex("mpcsim_shim_demo_pcg"), 0: _ex("mpcsim_shim_demo_qdldl")}
 IIWA_DEMO_BINS = {1: _ex("mpcsim_iiwa_demo_pcg"), 0: _ex("mpcsim_iiwa_demo_qdldl")}
 MULTI_BIN = _ex("multi_gpu_pcg")
 UTILS_BIN = _ex("bd_utils_probe")
-SQP_BATCHED_BIN = _ex("sqp_batched_iiwa")
+SQP_BATCHED_BIN, SQP_BATCHED_BIN64 = _ex("sqp_batched_iiwa"), _ex("sqp_batched_iiwa_f64")
 LINE_SEARCH_STAGE_BIN = _ex("sqp_line_search_stage")
 MPC_CLOSED_LOOP_BIN = _ex("mpc_closed_loop")
 
@@ -141,6 +141,12 @@ def build_sqp_batched(force: bool = False, verbose: bool = False) -> str:
     """A batched SQP iteration that stays on the device: KKT -> Schur -> PCG -> dz -> merit -> line-search step over the C ABI."""
     _build_bins([SQP_BATCHED_BIN], force, verbose)
     return SQP_BATCHED_BIN
+
+
+def build_sqp_batched_f64(force: bool = False, verbose: bool = False) -> str:
+    """The same program compiled with -DUSE_DOUBLES (linsys_t = double): the six double entry points, KKT to line-search step."""
+    _build_bins([SQP_BATCHED_BIN64], force, verbose)
+    return SQP_BATCHED_BIN64
 
 
 def build_line_search_stage(force: bool = False, verbose: bool = False) -> str:

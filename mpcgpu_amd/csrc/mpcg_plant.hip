@@ -1,7 +1,8 @@
 // mpcg_plant.hip — C ABI (include/mpcg.h) of the producer of the path's inputs: the robot as data (mpcg_plant) and the KKT block assembly
-// mpcg_generate_kkt over the gfx950 kernel in kkt_plant.hip.h; the stage behind dz — mpcg_compute_merit and
-// mpcg_line_search_step over merit_plant.hip.h (the merit in packed float, "merit_f32": merit_plant_f32.hip.h); the step between two SQP solves — mpcg_simulate and mpcg_advance_horizon over sim_plant.hip.h.
+// mpcg_generate_kkt(_f64) over the gfx950 kernel in kkt_plant.hip.h; the stage behind dz — mpcg_compute_merit(_f64) and
+// mpcg_line_search_step(_rho)(_f64) over merit_plant.hip.h (the merit in packed float, "merit_f32": merit_plant_f32.hip.h); the step between two SQP solves — mpcg_simulate and mpcg_advance_horizon over sim_plant.hip.h.
 #include <cmath>
+#include <type_traits>
 #include "mpcg_handle.hpp"
 #include "kkt_plant.hip.h"
 #include "merit_plant.hip.h"
@@ -194,18 +195,20 @@ int mpcg_plant_destroy(mpcg_plant* p) {
     return MPCG_OK;
 }
 
-int mpcg_generate_kkt(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float timestep, const float* d_eePos_traj,
-                      const float* d_xs, const float* d_xu, float qd_cost, float r_cost, float* d_G_dense, float* d_C_dense,
-                      float* d_g, float* d_c, uint32_t batch, void* stream) {
+// mpcg_generate_kkt (T = float) and mpcg_generate_kkt_f64 (T = double): one host path (fn: the entry point's name).  "kkt_f32" selects a build of the float entry only.
+extern "C++" {
+template <typename T>
+static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, T timestep, const T* d_eePos_traj,
+                             const T* d_xs, const T* d_xu, T qd_cost, T r_cost, T* d_G_dense, T* d_C_dense, T* d_g, T* d_c, uint32_t batch, void* stream) {
     if (!h || !plant) return MPCG_ERR_INVALID;
     if (!d_eePos_traj || !d_xs || !d_xu || !d_G_dense || !d_C_dense || !d_g || !d_c)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_generate_kkt: null device pointer");
-    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_generate_kkt: state_size 14 / control_size 7 (IIWA-14) only");
-    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, "mpcg_generate_kkt: plant and handle live on different devices");
+        return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
+    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
     if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_generate_kkt: batch exceeds max_batch");
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
-    KktArgs a;
+    typename std::conditional<std::is_same<T, float>::value, KktArgs, KktArgsF64>::type a;
     a.plant = plant->d; a.eePos_traj = d_eePos_traj; a.xs = d_xs; a.xu = d_xu;
     a.G = d_G_dense; a.C = d_C_dense; a.g = d_g; a.c = d_c;
     a.N = (int)h->N; a.batch = (int)batch; a.dt = timestep; a.qd_cost = qd_cost; a.r_cost = r_cost;
@@ -213,51 +216,72 @@ int mpcg_generate_kkt(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_
     long blocks = ((long)batch * (h->N - 1) + KKT_ITEMS - 1) / KKT_ITEMS;      // one wavefront per KKT_ITEMS (trajectory, knot) pairs
     const long cap = (long)h->num_cus * 32;
     if (blocks > cap) blocks = cap;
-    if (h->kkt_analytic && h->kkt_f32) {                  // linsys_t = float arithmetic throughout, as the reference's GRiD code (kkt_plant.hip.h, R = float)
-        KktArgsT<float> f;
-        f.plant = plant->d32; f.eePos_traj = d_eePos_traj; f.xs = d_xs; f.xu = d_xu;
-        f.G = d_G_dense; f.C = d_C_dense; f.g = d_g; f.c = d_c;
-        f.N = (int)h->N; f.batch = (int)batch; f.dt = timestep; f.qd_cost = qd_cost; f.r_cost = r_cost; f.analytic = 1;
-        // 1: two knots per lane in packed float (whatever the size of the call: a trajectory's results do not depend on what else is in the batch);
-        // 2: one knot per lane (the packed build's checker; 8 % faster than the default, where the packed build is 1.6x faster on throughput-sized calls)
-        if (h->kkt_f32 == 1) {
-            long pblocks = ((long)batch * (h->N - 1) + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
-            if (pblocks > cap) pblocks = cap;
-            hipLaunchKernelGGL((generate_kkt_kernel<true, kkt_f2>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), f);
-        } else
-        hipLaunchKernelGGL((generate_kkt_kernel<true, float>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), f);
-    } else if (h->kkt_analytic) hipLaunchKernelGGL((generate_kkt_kernel<true, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    else hipLaunchKernelGGL((generate_kkt_kernel<false, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    if constexpr (std::is_same<T, double>::value) {       // double arrays: float64 inside, either gradient route
+        if (h->kkt_analytic) hipLaunchKernelGGL((generate_kkt_f64_kernel<true>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+        else hipLaunchKernelGGL((generate_kkt_f64_kernel<false>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    } else {
+        if (h->kkt_analytic && h->kkt_f32) {                  // linsys_t = float arithmetic throughout, as the reference's GRiD code (kkt_plant.hip.h, R = float)
+            KktArgsT<float> f;
+            f.plant = plant->d32; f.eePos_traj = d_eePos_traj; f.xs = d_xs; f.xu = d_xu;
+            f.G = d_G_dense; f.C = d_C_dense; f.g = d_g; f.c = d_c;
+            f.N = (int)h->N; f.batch = (int)batch; f.dt = timestep; f.qd_cost = qd_cost; f.r_cost = r_cost; f.analytic = 1;
+            // 1: two knots per lane in packed float (whatever the size of the call: a trajectory's results do not depend on what else is in the batch);
+            // 2: one knot per lane (the packed build's checker; 8 % faster than the default, where the packed build is 1.6x faster on throughput-sized calls)
+            if (h->kkt_f32 == 1) {
+                long pblocks = ((long)batch * (h->N - 1) + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
+                if (pblocks > cap) pblocks = cap;
+                hipLaunchKernelGGL((generate_kkt_kernel<true, kkt_f2>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), f);
+            } else
+            hipLaunchKernelGGL((generate_kkt_kernel<true, float>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), f);
+        } else if (h->kkt_analytic) hipLaunchKernelGGL((generate_kkt_kernel<true, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+        else hipLaunchKernelGGL((generate_kkt_kernel<false, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    }
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
+}  // extern "C++"
 
-// ---- merit function and line search (merit_plant.hip.h) ----
-static int check_steps(mpcg_handle* h, const char* who, const float* step_sizes, uint32_t num_steps) {
+int mpcg_generate_kkt(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float timestep, const float* d_eePos_traj,
+                      const float* d_xs, const float* d_xu, float qd_cost, float r_cost, float* d_G_dense, float* d_C_dense,
+                      float* d_g, float* d_c, uint32_t batch, void* stream) {
+    return generate_kkt_impl<float>(h, "mpcg_generate_kkt", plant, control_size, timestep, d_eePos_traj, d_xs, d_xu, qd_cost, r_cost, d_G_dense, d_C_dense, d_g, d_c, batch, stream);
+}
+
+int mpcg_generate_kkt_f64(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, double timestep, const double* d_eePos_traj,
+                          const double* d_xs, const double* d_xu, double qd_cost, double r_cost, double* d_G_dense, double* d_C_dense,
+                          double* d_g, double* d_c, uint32_t batch, void* stream) {
+    return generate_kkt_impl<double>(h, "mpcg_generate_kkt_f64", plant, control_size, timestep, d_eePos_traj, d_xs, d_xu, qd_cost, r_cost, d_G_dense, d_C_dense, d_g, d_c, batch, stream);
+}
+
+// ---- merit function and line search (merit_plant.hip.h): one host path per call for the float entries (T = float) and their _f64 twins (T = double) ----
+extern "C++" {
+template <typename T>
+static int check_steps(mpcg_handle* h, const char* who, const T* step_sizes, uint32_t num_steps) {
     if (!step_sizes) return fail(h, MPCG_ERR_INVALID, std::string(who) + ": null step_sizes");
     if (num_steps == 0 || num_steps > (uint32_t)MPCG_MAX_STEP_SIZES) return fail(h, MPCG_ERR_INVALID, std::string(who) + ": num_steps must be 1..16 (MPCG_MAX_STEP_SIZES)");
     return MPCG_OK;
 }
 
-int mpcg_compute_merit(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float timestep, const float* d_eePos_traj, const float* d_xs,
-                       const float* d_xu, const float* d_dz, const float* step_sizes, uint32_t num_steps, float mu, float qd_cost, float r_cost,
-                       float* d_merit, uint32_t batch, void* stream) {
+template <typename T>
+static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, T timestep, const T* d_eePos_traj, const T* d_xs,
+                              const T* d_xu, const T* d_dz, const T* step_sizes, uint32_t num_steps, T mu, T qd_cost, T r_cost, T* d_merit, uint32_t batch, void* stream) {
     static_assert(MERIT_MAX_STEPS == MPCG_MAX_STEP_SIZES, "scratch row stride");
+    constexpr bool F64 = std::is_same<T, double>::value;
     if (!h || !plant) return MPCG_ERR_INVALID;
-    if (!d_eePos_traj || !d_xu || !d_merit) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_merit: null device pointer");
-    { const int rc = check_steps(h, "mpcg_compute_merit", step_sizes, num_steps); if (rc != MPCG_OK) return rc; }
-    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_compute_merit: state_size 14 / control_size 7 (IIWA-14) only");
-    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_merit: plant and handle live on different devices");
-    MeritArgs a;
+    if (!d_eePos_traj || !d_xu || !d_merit) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    { const int rc = check_steps(h, fn, step_sizes, num_steps); if (rc != MPCG_OK) return rc; }
+    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
+    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
+    typename std::conditional<F64, MeritArgsF64, MeritArgs>::type a;
     bool moved = false;
-    for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) { a.alpha[i] = i < num_steps ? step_sizes[i] : 0.f; moved = moved || a.alpha[i] != 0.f; }
-    if (moved && !d_dz) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_merit: d_dz may be NULL only if every step size is 0");
+    for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) { a.alpha[i] = i < num_steps ? step_sizes[i] : T(0); moved = moved || a.alpha[i] != T(0); }
+    if (moved && !d_dz) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": d_dz may be NULL only if every step size is 0");
     if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_merit: batch exceeds max_batch");
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!h->merit_scratch) {                      // first call only (not stream-ordered: hipMalloc)
-        { const int rc = alloc_allowed(h, st, "mpcg_compute_merit"); if (rc != MPCG_OK) return rc; }
+    if (!h->merit_scratch) {                      // first call only (not stream-ordered: hipMalloc); shared by both entries
+        { const int rc = alloc_allowed(h, st, fn); if (rc != MPCG_OK) return rc; }
         HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->merit_scratch), (size_t)h->max_batch * MERIT_MAX_STEPS * h->N * sizeof(double)));
     }
     a.plant = plant->d; a.eePos_traj = d_eePos_traj; a.xs = d_xs; a.xu = d_xu; a.dz = d_dz; a.point = h->merit_scratch;
@@ -266,29 +290,38 @@ int mpcg_compute_merit(mpcg_handle* h, const mpcg_plant* plant, uint32_t control
     long blocks = ((long)batch * num_steps * h->N + KKT_ITEMS - 1) / KKT_ITEMS;      // one wavefront per KKT_ITEMS (trajectory, step size, knot) items
     const long cap = (long)h->num_cus * 32;
     if (blocks > cap) blocks = cap;
-    if (h->merit_f32) {                           // the reference's own arithmetic (merit.cuh, T = float): two items per lane group in packed float, whatever the size of the call
-        MeritArgsF32 f;
-        f.plant = plant->d32; f.eePos_traj = d_eePos_traj; f.xs = d_xs; f.xu = d_xu; f.dz = d_dz; f.point = h->merit_scratch;
-        f.N = a.N; f.batch = a.batch; f.A = a.A;
-        f.dt = timestep; f.mu = mu; f.qd_cost = qd_cost; f.r_cost = r_cost;
-        memcpy(f.alpha, a.alpha, sizeof(f.alpha));
-        // one wavefront per trip of 2 KKT_ITEMS items (no trip loop: merit_plant_f32.hip.h); at most max_batch x 16 x N / 8 of them, and a handle whose
-        // scratch of max_batch x 16 x N doubles could be allocated stays far below the 2^31 - 1 workgroups a grid dimension holds
-        const long pblocks = ((long)batch * num_steps * h->N + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
-        if (pblocks > 0x7fffffffL) return fail(h, MPCG_ERR_INVALID, "mpcg_compute_merit: batch x num_steps x knot_points exceeds the grid");
-        hipLaunchKernelGGL(merit_points_f32_kernel, dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
-    } else
-    hipLaunchKernelGGL(merit_points_kernel, dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
-    HIP_TRY(h, hipGetLastError());
     const int rows = (int)(batch * num_steps);
-    hipLaunchKernelGGL(merit_sum_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
+    if constexpr (F64) {                          // double arrays: float64 inside ("merit_f32" is the float entry's), the row sums stored as they are
+        hipLaunchKernelGGL(merit_points_f64_kernel, dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+        HIP_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(merit_sum_f64_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
+    } else {
+        if (h->merit_f32) {                           // the reference's own arithmetic (merit.cuh, T = float): two items per lane group in packed float, whatever the size of the call
+            MeritArgsF32 f;
+            f.plant = plant->d32; f.eePos_traj = d_eePos_traj; f.xs = d_xs; f.xu = d_xu; f.dz = d_dz; f.point = h->merit_scratch;
+            f.N = a.N; f.batch = a.batch; f.A = a.A;
+            f.dt = timestep; f.mu = mu; f.qd_cost = qd_cost; f.r_cost = r_cost;
+            memcpy(f.alpha, a.alpha, sizeof(f.alpha));
+            // one wavefront per trip of 2 KKT_ITEMS items (no trip loop: merit_plant_f32.hip.h); at most max_batch x 16 x N / 8 of them, and a handle whose
+            // scratch of max_batch x 16 x N doubles could be allocated stays far below the 2^31 - 1 workgroups a grid dimension holds
+            const long pblocks = ((long)batch * num_steps * h->N + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
+            if (pblocks > 0x7fffffffL) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch x num_steps x knot_points exceeds the grid");
+            hipLaunchKernelGGL(merit_points_f32_kernel, dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
+        } else
+        hipLaunchKernelGGL(merit_points_kernel, dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+        HIP_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(merit_sum_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
+    }
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
 
-// mpcg_line_search_step and mpcg_line_search_step_rho: one host path (fn: the entry point's name; rho: null for the former)
-static int line_search_step_impl(mpcg_handle* h, const char* fn, uint32_t control_size, const float* d_merit, const float* step_sizes, uint32_t num_steps,
-                                 float* d_merit_ref, const float* d_dz, float* d_xu, int32_t* d_step, const StepRhoArgs* rho, uint32_t batch, void* stream) {
+// mpcg_line_search_step(_f64) and mpcg_line_search_step_rho(_f64): one host path (fn: the entry point's name; rho: null for the former)
+template <typename T>
+static int line_search_step_impl(mpcg_handle* h, const char* fn, uint32_t control_size, const T* d_merit, const T* step_sizes, uint32_t num_steps,
+                                 T* d_merit_ref, const T* d_dz, T* d_xu, int32_t* d_step, const typename StepTypes<T>::with_rho* rho, uint32_t batch, void* stream) {
+    typedef typename StepTypes<T>::plain Plain;
+    typedef typename StepTypes<T>::with_rho WithRho;
     if (!h) return MPCG_ERR_INVALID;
     if (!d_merit || !d_merit_ref || !d_dz || !d_xu || !d_step || (rho && (!rho->rho || !rho->drho || !rho->done)))
         return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
@@ -297,36 +330,71 @@ static int line_search_step_impl(mpcg_handle* h, const char* fn, uint32_t contro
     if (rho) {
         if (!std::isfinite(rho->factor) || !std::isfinite(rho->rho_min) || !std::isfinite(rho->rho_max) || !std::isfinite(rho->rho_reset))
             return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": rho_factor, rho_min, rho_max and rho_reset must be finite");
-        if (!(rho->factor > 1.0f) || !(rho->rho_min > 0.0f) || rho->rho_max < rho->rho_min)
+        if (!(rho->factor > T(1)) || !(rho->rho_min > T(0)) || rho->rho_max < rho->rho_min)
             return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": needs rho_factor > 1, rho_min > 0 and rho_max >= rho_min");
     }
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
-    StepRhoArgs ra{};
+    WithRho ra{};
     if (rho) ra = *rho;
-    StepArgs& a = ra;
+    Plain& a = ra;
     a.merit = d_merit; a.merit_ref = d_merit_ref; a.dz = d_dz; a.xu = d_xu; a.step = d_step; a.A = (int)num_steps;
     a.len = (size_t)(h->n + control_size) * h->N - control_size;
-    for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) a.alpha[i] = i < num_steps ? step_sizes[i] : 0.f;
-    if (rho) hipLaunchKernelGGL(line_search_step_kernel<StepRhoArgs>, dim3(batch), dim3(256), 0, static_cast<hipStream_t>(stream), ra);
-    else hipLaunchKernelGGL(line_search_step_kernel<StepArgs>, dim3(batch), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) a.alpha[i] = i < num_steps ? step_sizes[i] : T(0);
+    if (rho) hipLaunchKernelGGL(line_search_step_kernel<WithRho>, dim3(batch), dim3(256), 0, static_cast<hipStream_t>(stream), ra);
+    else hipLaunchKernelGGL(line_search_step_kernel<Plain>, dim3(batch), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
 
+template <typename T>
+static int line_search_step_rho_impl(mpcg_handle* h, const char* fn, uint32_t control_size, const T* d_merit, const T* step_sizes, uint32_t num_steps,
+                                     T* d_merit_ref, const T* d_dz, T* d_xu, int32_t* d_step, T* d_rho, T* d_drho, uint8_t* d_done,
+                                     T rho_factor, T rho_min, T rho_max, T rho_reset, uint32_t batch, void* stream) {
+    static_assert(STEP_FROZEN == MPCG_STEP_FROZEN, "the frozen code of the header");
+    typename StepTypes<T>::with_rho r{};
+    r.rho = d_rho; r.drho = d_drho; r.done = d_done; r.factor = rho_factor; r.rho_min = rho_min; r.rho_max = rho_max; r.rho_reset = rho_reset;
+    return line_search_step_impl<T>(h, fn, control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, &r, batch, stream);
+}
+}  // extern "C++"
+
+int mpcg_compute_merit(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float timestep, const float* d_eePos_traj, const float* d_xs,
+                       const float* d_xu, const float* d_dz, const float* step_sizes, uint32_t num_steps, float mu, float qd_cost, float r_cost,
+                       float* d_merit, uint32_t batch, void* stream) {
+    return compute_merit_impl<float>(h, "mpcg_compute_merit", plant, control_size, timestep, d_eePos_traj, d_xs, d_xu, d_dz, step_sizes, num_steps, mu, qd_cost, r_cost,
+                                     d_merit, batch, stream);
+}
+
+int mpcg_compute_merit_f64(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, double timestep, const double* d_eePos_traj, const double* d_xs,
+                           const double* d_xu, const double* d_dz, const double* step_sizes, uint32_t num_steps, double mu, double qd_cost, double r_cost,
+                           double* d_merit, uint32_t batch, void* stream) {
+    return compute_merit_impl<double>(h, "mpcg_compute_merit_f64", plant, control_size, timestep, d_eePos_traj, d_xs, d_xu, d_dz, step_sizes, num_steps, mu, qd_cost,
+                                      r_cost, d_merit, batch, stream);
+}
+
 int mpcg_line_search_step(mpcg_handle* h, uint32_t control_size, const float* d_merit, const float* step_sizes, uint32_t num_steps,
                           float* d_merit_ref, const float* d_dz, float* d_xu, int32_t* d_step, uint32_t batch, void* stream) {
-    return line_search_step_impl(h, "mpcg_line_search_step", control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, nullptr, batch, stream);
+    return line_search_step_impl<float>(h, "mpcg_line_search_step", control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, nullptr, batch, stream);
+}
+
+int mpcg_line_search_step_f64(mpcg_handle* h, uint32_t control_size, const double* d_merit, const double* step_sizes, uint32_t num_steps,
+                              double* d_merit_ref, const double* d_dz, double* d_xu, int32_t* d_step, uint32_t batch, void* stream) {
+    return line_search_step_impl<double>(h, "mpcg_line_search_step_f64", control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, nullptr, batch, stream);
 }
 
 int mpcg_line_search_step_rho(mpcg_handle* h, uint32_t control_size, const float* d_merit, const float* step_sizes, uint32_t num_steps,
                               float* d_merit_ref, const float* d_dz, float* d_xu, int32_t* d_step, float* d_rho, float* d_drho, uint8_t* d_done,
                               float rho_factor, float rho_min, float rho_max, float rho_reset, uint32_t batch, void* stream) {
-    static_assert(STEP_FROZEN == MPCG_STEP_FROZEN, "the frozen code of the header");
-    StepRhoArgs r{};
-    r.rho = d_rho; r.drho = d_drho; r.done = d_done; r.factor = rho_factor; r.rho_min = rho_min; r.rho_max = rho_max; r.rho_reset = rho_reset;
-    return line_search_step_impl(h, "mpcg_line_search_step_rho", control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, &r, batch, stream);
+    return line_search_step_rho_impl<float>(h, "mpcg_line_search_step_rho", control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, d_rho, d_drho,
+                                            d_done, rho_factor, rho_min, rho_max, rho_reset, batch, stream);
+}
+
+int mpcg_line_search_step_rho_f64(mpcg_handle* h, uint32_t control_size, const double* d_merit, const double* step_sizes, uint32_t num_steps,
+                                  double* d_merit_ref, const double* d_dz, double* d_xu, int32_t* d_step, double* d_rho, double* d_drho, uint8_t* d_done,
+                                  double rho_factor, double rho_min, double rho_max, double rho_reset, uint32_t batch, void* stream) {
+    return line_search_step_rho_impl<double>(h, "mpcg_line_search_step_rho_f64", control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, d_rho,
+                                             d_drho, d_done, rho_factor, rho_min, rho_max, rho_reset, batch, stream);
 }
 
 // ---- plant simulation and horizon shift: the step between two SQP solves (sim_plant.hip.h) ----

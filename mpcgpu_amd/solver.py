@@ -171,6 +171,14 @@ class PcgSolver:
             raise ValueError(f"{name}: need contiguous cuda {dtype} tensor with {numel} elements, "
                              f"got {tuple(t.shape)} {t.dtype} {t.device}")
 
+    @staticmethod
+    def _one_dtype(name, *tensors):
+        """float32 or float64, shared by every tensor given (None entries are optional arguments left out): TypeError otherwise."""
+        dts = {t.dtype for t in tensors if t is not None}
+        if len(dts) != 1 or not dts <= {torch.float32, torch.float64}:
+            raise TypeError(f"{name}: the tensors must all be float32 or all be float64, got {sorted(str(d) for d in dts)}")
+        return dts.pop()
+
     def solve(self, S, Pinv, gamma, lam, config: pcg_config | None = None, precond: str = "ss",
               iters: torch.Tensor | None = None, exits: torch.Tensor | None = None):
         """In-place batched solve.  S, Pinv: [B, 3*n*n*N]; gamma, lam: [B, n*N] (lam in/out).
@@ -314,18 +322,22 @@ class PcgSolver:
     def generate_kkt(self, plant: "Plant", eePos_traj, xs, xu, timestep: float, qd_cost: float, r_cost: float,
                      control_size: int | None = None):
         """generate_kkt_submatrices (include/common/kkt.cuh:22-163), batched: eePos_traj [B, 6N], xs [B, n], xu [B, (n+m)N - m]
-        -> (G_dense, C_dense, g, c) device tensors in the layouts form_schur consumes."""
+        -> (G_dense, C_dense, g, c) device tensors in the layouts form_schur consumes.
+        float32 tensors: mpcg_generate_kkt; float64 tensors: mpcg_generate_kkt_f64 (linsys_t = double: inputs used as they are, outputs not rounded to
+        float).  Mixed dtypes raise TypeError."""
         B = xu.shape[0] if xu.dim() > 1 else 1
         n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        self._chk(eePos_traj, B * 6 * N, torch.float32, "eePos_traj")
-        self._chk(xs, B * n, torch.float32, "xs")
-        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
+        dt = self._one_dtype("generate_kkt", eePos_traj, xs, xu)
+        self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
+        self._chk(xs, B * n, dt, "xs")
+        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
         dev = xu.device
-        G = torch.empty(B, (n * n + m * m) * N - m * m, device=dev)
-        Cd = torch.empty(B, (n * n + n * m) * (N - 1), device=dev)
-        g = torch.empty(B, (n + m) * N - m, device=dev)
-        c = torch.empty(B, n * N, device=dev)
-        self._check(self.lib.mpcg_generate_kkt(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), float(qd_cost),
+        G = torch.empty(B, (n * n + m * m) * N - m * m, device=dev, dtype=dt)
+        Cd = torch.empty(B, (n * n + n * m) * (N - 1), device=dev, dtype=dt)
+        g = torch.empty(B, (n + m) * N - m, device=dev, dtype=dt)
+        c = torch.empty(B, n * N, device=dev, dtype=dt)
+        fn = self.lib.mpcg_generate_kkt if dt == torch.float32 else self.lib.mpcg_generate_kkt_f64
+        self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), float(qd_cost),
                                                float(r_cost), _ptr(G), _ptr(Cd), _ptr(g), _ptr(c), B, _stream()))
         return G, Cd, g, c
 
@@ -348,67 +360,77 @@ class PcgSolver:
         return dz
 
     @staticmethod
-    def _steps(step_sizes):
-        """The HOST array of step sizes both line-search calls take (copied into the launch)."""
+    def _steps(step_sizes, dtype=torch.float32):
+        """The HOST array of step sizes both line-search calls take (copied into the launch): floats, or doubles for the _f64 entries."""
         vals = [float(v) for v in step_sizes]
-        return (C.c_float * len(vals))(*vals), len(vals)
+        return ((C.c_float if dtype == torch.float32 else C.c_double) * len(vals))(*vals), len(vals)
 
     def compute_merit(self, plant: "Plant", eePos_traj, xs, xu, dz, step_sizes, timestep: float, mu: float, qd_cost: float,
                       r_cost: float, merit=None, control_size: int | None = None):
         """ls_gato_compute_merit / compute_merit (include/common/merit.cuh:16-143), batched over trajectories and step sizes:
         merit [B, A] float of the trial iterates xu + step_sizes[a] * dz.  xs = None: no initial-state term (the reference's compute_merit);
-        dz = None is allowed when every step size is 0."""
+        dz = None is allowed when every step size is 0.
+        float32 tensors: mpcg_compute_merit; float64 tensors: mpcg_compute_merit_f64 (the trial iterate and the merits in double, the step sizes
+        marshalled as doubles).  Mixed dtypes raise TypeError."""
         B = xu.shape[0] if xu.dim() > 1 else 1
         n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        arr, A = self._steps(step_sizes)
-        self._chk(eePos_traj, B * 6 * N, torch.float32, "eePos_traj")
-        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
+        dt = self._one_dtype("compute_merit", eePos_traj, xs, xu, dz, merit)
+        arr, A = self._steps(step_sizes, dt)
+        self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
+        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
         if xs is not None:
-            self._chk(xs, B * n, torch.float32, "xs")
+            self._chk(xs, B * n, dt, "xs")
         if dz is not None:
-            self._chk(dz, B * ((n + m) * N - m), torch.float32, "dz")
+            self._chk(dz, B * ((n + m) * N - m), dt, "dz")
         if merit is None:
-            merit = torch.empty(B, A, device=xu.device)
-        self._chk(merit, B * A, torch.float32, "merit")
-        self._check(self.lib.mpcg_compute_merit(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), _ptr(dz), arr, A,
+            merit = torch.empty(B, A, device=xu.device, dtype=dt)
+        self._chk(merit, B * A, dt, "merit")
+        fn = self.lib.mpcg_compute_merit if dt == torch.float32 else self.lib.mpcg_compute_merit_f64
+        self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), _ptr(dz), arr, A,
                                                 float(mu), float(qd_cost), float(r_cost), _ptr(merit), B, _stream()))
         return merit
 
     def line_search_step(self, merit, step_sizes, merit_ref, dz, xu, step=None, control_size: int | None = None):
         """The step selection and update of include/pcg/sqp.cuh:292-301, 317, 332-338, 352 per trajectory: the first strictly smallest merit below
-        merit_ref wins; xu and merit_ref are updated in place.  Returns the chosen index per trajectory (int32 [B], -1: no step)."""
+        merit_ref wins; xu and merit_ref are updated in place.  Returns the chosen index per trajectory (int32 [B], -1: no step).
+        float32 tensors: mpcg_line_search_step; float64 tensors: mpcg_line_search_step_f64.  Mixed dtypes raise TypeError."""
         B = merit_ref.numel()
         n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        arr, A = self._steps(step_sizes)
-        self._chk(merit, B * A, torch.float32, "merit")
-        self._chk(merit_ref, B, torch.float32, "merit_ref")
-        self._chk(dz, B * ((n + m) * N - m), torch.float32, "dz")
-        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
+        dt = self._one_dtype("line_search_step", merit, merit_ref, dz, xu)
+        arr, A = self._steps(step_sizes, dt)
+        self._chk(merit, B * A, dt, "merit")
+        self._chk(merit_ref, B, dt, "merit_ref")
+        self._chk(dz, B * ((n + m) * N - m), dt, "dz")
+        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
         if step is None:
             step = torch.empty(B, dtype=torch.int32, device=xu.device)
         self._chk(step, B, torch.int32, "step")
-        self._check(self.lib.mpcg_line_search_step(self._h, m, _ptr(merit), arr, A, _ptr(merit_ref), _ptr(dz), _ptr(xu), _ptr(step), B, _stream()))
+        fn = self.lib.mpcg_line_search_step if dt == torch.float32 else self.lib.mpcg_line_search_step_f64
+        self._check(fn(self._h, m, _ptr(merit), arr, A, _ptr(merit_ref), _ptr(dz), _ptr(xu), _ptr(step), B, _stream()))
         return step
 
     def line_search_step_rho(self, merit, step_sizes, merit_ref, dz, xu, rho, drho, done, rho_factor: float = 1.2, rho_min: float = 1e-3,
                              rho_max: float = 10.0, rho_reset: float = 1e-3, step=None, control_size: int | None = None):
         """line_search_step followed by the rho adaptation of include/pcg/sqp.cuh:304-320 with device state per trajectory: rho, drho (float32
         [B]) and done (uint8 [B]) are updated in place; a trajectory with done != 0 is frozen (step = MPCG_STEP_FROZEN, nothing else written).
-        `rho` is the tensor form_schur takes: nothing is read back inside an SQP loop."""
+        `rho` is the tensor form_schur takes: nothing is read back inside an SQP loop.
+        float32 tensors: mpcg_line_search_step_rho; float64 tensors (rho and drho float64 too): mpcg_line_search_step_rho_f64.  Mixed dtypes raise TypeError."""
         B = merit_ref.numel()
         n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        arr, A = self._steps(step_sizes)
-        self._chk(merit, B * A, torch.float32, "merit")
-        self._chk(merit_ref, B, torch.float32, "merit_ref")
-        self._chk(dz, B * ((n + m) * N - m), torch.float32, "dz")
-        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
-        self._chk(rho, B, torch.float32, "rho")
-        self._chk(drho, B, torch.float32, "drho")
+        dt = self._one_dtype("line_search_step_rho", merit, merit_ref, dz, xu, rho, drho)
+        arr, A = self._steps(step_sizes, dt)
+        self._chk(merit, B * A, dt, "merit")
+        self._chk(merit_ref, B, dt, "merit_ref")
+        self._chk(dz, B * ((n + m) * N - m), dt, "dz")
+        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
+        self._chk(rho, B, dt, "rho")
+        self._chk(drho, B, dt, "drho")
         self._chk(done, B, torch.uint8, "done")
         if step is None:
             step = torch.empty(B, dtype=torch.int32, device=xu.device)
         self._chk(step, B, torch.int32, "step")
-        self._check(self.lib.mpcg_line_search_step_rho(self._h, m, _ptr(merit), arr, A, _ptr(merit_ref), _ptr(dz), _ptr(xu), _ptr(step),
+        fn = self.lib.mpcg_line_search_step_rho if dt == torch.float32 else self.lib.mpcg_line_search_step_rho_f64
+        self._check(fn(self._h, m, _ptr(merit), arr, A, _ptr(merit_ref), _ptr(dz), _ptr(xu), _ptr(step),
                                                        _ptr(rho), _ptr(drho), _ptr(done), float(rho_factor), float(rho_min), float(rho_max),
                                                        float(rho_reset), B, _stream()))
         return step
