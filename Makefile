@@ -31,7 +31,7 @@ SHIM_SIM   := $(INC)/mpcsim.cuh $(INC)/pcg/sqp.cuh $(INC)/qdldl/sqp.cuh $(INC)/m
 
 EXAMPLES := examples/sqp_pcg_callsite examples/sqp_pcg_callsite_f64 examples/sqp_pcg_callsite_f64_n128 examples/sqp_linsys_chain examples/sqp_linsys_chain_f64 \
             examples/mpcsim_shim_demo_pcg examples/mpcsim_shim_demo_qdldl examples/mpcsim_iiwa_demo_pcg examples/mpcsim_iiwa_demo_qdldl \
-            examples/bd_utils_probe examples/multi_gpu_pcg examples/sqp_batched_iiwa examples/sqp_batched_iiwa_f64 examples/sqp_line_search_stage examples/mpc_closed_loop
+            examples/bd_utils_probe examples/multi_gpu_pcg examples/sqp_batched_iiwa examples/sqp_batched_iiwa_f64 examples/sqp_line_search_stage examples/mpc_closed_loop examples/mpc_closed_loop_f64
 
 .PHONY: all lib examples oracle clean
 all: lib examples
@@ -77,6 +77,8 @@ examples/sqp_line_search_stage: examples/sqp_line_search_stage.cpp $(LIB) $(SHIM
 	$(HIPCC) $(EXFLAGS) -DLINSYS_SOLVE=1 -I$(INC) $< $(LINKLIB) -o $@
 examples/mpc_closed_loop: examples/mpc_closed_loop.cpp $(LIB) $(SHIM_SIM)
 	$(HIPCC) $(EXFLAGS) -DLINSYS_SOLVE=1 -I$(INC) $< $(LINKLIB) -o $@
+examples/mpc_closed_loop_f64: examples/mpc_closed_loop.cpp $(LIB) $(SHIM_SIM)
+	$(HIPCC) $(EXFLAGS) -DUSE_DOUBLES -DLINSYS_SOLVE=1 -I$(INC) $< $(LINKLIB) -o $@
 
 clean:
 	rm -f $(LIB) $(LIB_OBJS) $(EXAMPLES)

@@ -6,8 +6,11 @@
 //   2. a batched run over the C ABI alone: B windows, U control updates, per update K iterations of the six SQP calls (rho per trajectory on the
 //      device), then mpcg_simulate under the previous plan and mpcg_advance_horizon — the host decides WHEN to shift from the clock bookkeeping, which
 //      is the same for every trajectory, so nothing synchronises inside an update; tracking errors wait in a device buffer and are read at the end.
+// Compiled with -DUSE_DOUBLES (examples/mpc_closed_loop_f64; linsys_t = double, the reference's USE_DOUBLES build) both runs are in double: the stages
+// are the <double> ones, the batched part calls the _f64 entry of all eight stages, and the float data file is widened on load.  The batched part's
+// substep is (linsys_t)2e-4f either way — ten substeps per 2,000 us; simulateMPC's stage uses linsys_t(2e-4) as the reference does (include/mpcg.h).
 // Prints one JSON line; exits 0 only if every tracking error is finite and every trajectory shifted the expected number of times.
-//   hipcc --offload-arch=gfx950 -O2 -DLINSYS_SOLVE=1 -Iinclude examples/mpc_closed_loop.cpp -Lmpcgpu_amd -lmpcg_hip
+//   hipcc --offload-arch=gfx950 -O2 -DLINSYS_SOLVE=1 [-DUSE_DOUBLES] -Iinclude examples/mpc_closed_loop.cpp -Lmpcgpu_amd -lmpcg_hip
 //   mpc_closed_loop [--batch 4] [--knots 16] [--updates 17] [--iters 1] [--mpc-steps 16]
 #include <cmath>
 #include <cstdio>
@@ -21,7 +24,12 @@
 #define PCG_MAX_ITER 3000
 #include "mpcsim.cuh"
 
-typedef float T;
+typedef linsys_t T;               // float, or double under -DUSE_DOUBLES; LS(entry) is the library entry point of that type
+#ifdef USE_DOUBLES
+#define LS(entry) entry##_f64
+#else
+#define LS(entry) entry
+#endif
 static const int n = 14, m = 7, ROWW = 27, ROWS = 400;      // a row of the data file: x (14), u (7), end-effector pose (6)
 
 #define MPCG_OK_OR_DIE(h, expr)                                                                              \
@@ -33,10 +41,10 @@ static std::vector<T> load_rows(const std::string& exe) {
     const std::string dir = exe.substr(0, exe.find_last_of('/') + 1);
     for (const std::string& p : {dir + "../mpcgpu_amd/data/iiwa_traj_0_0.f32", std::string("mpcgpu_amd/data/iiwa_traj_0_0.f32")}) {
         if (FILE* f = fopen(p.c_str(), "rb")) {
-            std::vector<T> v((size_t)ROWS * ROWW);
-            const size_t got = fread(v.data(), sizeof(T), v.size(), f);
+            std::vector<float> v((size_t)ROWS * ROWW);
+            const size_t got = fread(v.data(), sizeof(float), v.size(), f);
             fclose(f);
-            if (got == v.size()) return v;
+            if (got == v.size()) return std::vector<T>(v.begin(), v.end());      // (widened under USE_DOUBLES)
         }
     }
     fprintf(stderr, "cannot read mpcgpu_amd/data/iiwa_traj_0_0.f32\n");
@@ -133,15 +141,15 @@ int main(int argc, char** argv) {
     T *d_g = dalloc<T>((size_t)B * L), *d_c = dalloc<T>((size_t)B * n * N), *d_S = dalloc<T>((size_t)B * 3 * nn * N), *d_Pinv = dalloc<T>((size_t)B * 3 * nn * N);
     T *d_gamma = dalloc<T>((size_t)B * n * N), *d_lambda = dalloc<T>((size_t)B * n * N), *d_dz = dalloc<T>((size_t)B * L), *d_merit = dalloc<T>((size_t)B * 8);
     T *d_merit_ref = dalloc<T>(B), *d_eePos = dalloc<T>((size_t)B * 3), *d_err = dalloc<T>(B), *d_err_hist = dalloc<T>((size_t)U * B);
-    T *d_rho = to_device(std::vector<T>((size_t)B, 1e-3f)), *d_drho = dalloc<T>(B), *d_ones = to_device(std::vector<T>((size_t)B, 1.0f));
+    T *d_rho = to_device(std::vector<T>((size_t)B, (T)1e-3)), *d_drho = dalloc<T>(B), *d_ones = to_device(std::vector<T>((size_t)B, 1.0f));
     int32_t *d_step = dalloc<int32_t>(B), *d_offset = dalloc<int32_t>(B), *d_done = dalloc<int32_t>(B);
     uint32_t* d_iters = dalloc<uint32_t>(B);
     uint8_t *d_exit = dalloc<uint8_t>(B), *d_gave_up = dalloc<uint8_t>(B);
     hipStream_t s;
     gpuErrchk(hipStreamCreate(&s));
-    float steps[8];
+    T steps[8];
     for (int p = 0; p < 8; ++p) steps[p] = -1.0f / (float)(1 << p);
-    const float zero = 0.f;
+    const T zero = 0;
     ShiftClock clock(dt);
     double prev_us = 0;
     int shifts = 0;
@@ -149,21 +157,21 @@ int main(int argc, char** argv) {
         // one SQP call (include/pcg/sqp.cuh): x_s = x_0 of the iterate, drho = 1, merit of the start iterate, K iterations
         gpuErrchk(hipMemcpyAsync(d_drho, d_ones, B * sizeof(T), hipMemcpyDeviceToDevice, s));
         gpuErrchk(hipMemsetAsync(d_gave_up, 0, B, s));
-        MPCG_OK_OR_DIE(h, mpcg_compute_merit(h, plant, m, dt, d_goals, d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, (uint32_t)B, s));
+        MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant, m, dt, d_goals, d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, (uint32_t)B, s));
         for (int it = 0; it < K; ++it) {
-            MPCG_OK_OR_DIE(h, mpcg_generate_kkt(h, plant, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, s));
-            MPCG_OK_OR_DIE(h, mpcg_form_schur_rhov(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_rho, (uint32_t)B, MPCG_PRECOND_SS, s));
-            MPCG_OK_OR_DIE(h, mpcg_pcg_solve(h, d_S, d_Pinv, d_gamma, d_lambda, (uint32_t)B, PCG_MAX_ITER, 1e-7f, MPCG_PRECOND_SS, d_iters, d_exit, s));
-            MPCG_OK_OR_DIE(h, mpcg_compute_dz(h, m, d_G, d_C, d_g, d_lambda, d_dz, (uint32_t)B, s));
-            MPCG_OK_OR_DIE(h, mpcg_compute_merit(h, plant, m, dt, d_goals, d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, (uint32_t)B, s));
-            MPCG_OK_OR_DIE(h, mpcg_line_search_step_rho(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step, d_rho, d_drho, d_gave_up, 1.2f, 1e-3f, 10.f, 1e-3f,
+            MPCG_OK_OR_DIE(h, LS(mpcg_generate_kkt)(h, plant, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, s));
+            MPCG_OK_OR_DIE(h, LS(mpcg_form_schur_rhov)(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_rho, (uint32_t)B, MPCG_PRECOND_SS, s));
+            MPCG_OK_OR_DIE(h, LS(mpcg_pcg_solve)(h, d_S, d_Pinv, d_gamma, d_lambda, (uint32_t)B, PCG_MAX_ITER, (T)1e-7, MPCG_PRECOND_SS, d_iters, d_exit, s));
+            MPCG_OK_OR_DIE(h, LS(mpcg_compute_dz)(h, m, d_G, d_C, d_g, d_lambda, d_dz, (uint32_t)B, s));
+            MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant, m, dt, d_goals, d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, (uint32_t)B, s));
+            MPCG_OK_OR_DIE(h, LS(mpcg_line_search_step_rho)(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step, d_rho, d_drho, d_gave_up, (T)1.2, (T)1e-3, (T)10, (T)1e-3,
                                                         (uint32_t)B, s));
         }
         // the plant runs under the PREVIOUS plan for one period, offset by the previous period (include/mpcsim.cuh:288-291, :352)
-        MPCG_OK_OR_DIE(h, mpcg_simulate(h, plant, m, d_xs, d_xu_old, dt, prev_us, period_us, 2e-4f, d_eePos, (uint32_t)B, s));
+        MPCG_OK_OR_DIE(h, LS(mpcg_simulate)(h, plant, m, d_xs, d_xu_old, dt, prev_us, period_us, (T)2e-4f, d_eePos, (uint32_t)B, s));
         gpuErrchk(hipMemcpyAsync(d_xu_old, d_xu, (size_t)B * L * sizeof(T), hipMemcpyDeviceToDevice, s));
         const bool shift = clock.update(period_us);
-        MPCG_OK_OR_DIE(h, mpcg_advance_horizon(h, m, shift ? 1 : 0, d_xu, d_lambda, d_goals, d_xs, d_eePos, d_bplan, d_bgoals, (uint32_t)TS, (uint32_t)TS, 0,
+        MPCG_OK_OR_DIE(h, LS(mpcg_advance_horizon)(h, m, shift ? 1 : 0, d_xu, d_lambda, d_goals, d_xs, d_eePos, d_bplan, d_bgoals, (uint32_t)TS, (uint32_t)TS, 0,
                                                d_offset, d_done, d_err, (uint32_t)B, s));
         if (shift) {
             gpuErrchk(hipMemcpyAsync(d_err_hist + (size_t)shifts * B, d_err, B * sizeof(T), hipMemcpyDeviceToDevice, s));

@@ -503,6 +503,36 @@ int mpcg_advance_horizon(mpcg_handle *h, uint32_t control_size, uint32_t shift,
                          const float *d_xu_traj, const float *d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride,
                          uint32_t xu_fill_lead, int32_t *d_traj_offset, int32_t *d_done /* [batch] in/out */,
                          float *d_tracking_error /* [batch] out */, uint32_t batch, void *stream);
+/* The double twins (linsys_t = double, the reference's USE_DOUBLES build): with them a whole control update of the double build stays on the device.
+ * Everything said above of mpcg_simulate and mpcg_advance_horizon holds with float replaced by double — layouts, side effects, the frozen
+ * semantics of d_done, the error table (messages name the _f64 entry), batch == 0, nothing written on refusal, pure stream work from the first call
+ * on (capturable).  What differs:
+ *
+ * mpcg_simulate_f64.  d_xs and the controls are read as doubles and used as they are: nothing passes through float.  The state is carried in float64
+ * across the substeps, as in the float entry, and stored WITHOUT the final rounding; d_eePos likewise.  On float-representable inputs with the same
+ * substep schedule, rounding this entry's outputs to float gives mpcg_simulate's bits.  The schedule is the reference's with T = double
+ * (include/common/integrator.cuh:301-324), literally:  ss = sim_step, a double that is not passed through float;  S = (uint32)(sim / ss);
+ *   idx_s = (uint32)((toff + s * ss) / timestep), one rounding per operation;  the remainder substep is dt = fmod(sim, ss) AS A DOUBLE (not rounded
+ *   to float) with the control of the last full substep, or of (uint32)(toff / timestep) if S = 0;  a remainder of exactly 0 is not run.  The clamp
+ *   to knot_points - 2 and the cap MPCG_SIM_MAX_SUBSTEPS are the float entry's.
+ * A quirk of that arithmetic, reproduced literally (as xu_fill_lead = 0 is): with the reference's double substep 2e-4 and sim_time_us = 2000 the
+ * quotient 0.002 / 0.0002 rounds to exactly 10, but ten times the double 0.0002 exceeds the double 0.002, so fmod(0.002, 0.0002) is
+ * 0.00019999999999999996 (exact): the reference's double build runs TEN full substeps AND a remainder substep of almost a whole one.  A caller who
+ * wants ten substeps passes a substep whose tenfold does not exceed sim, e.g. (double)2e-4f — the value the float entry has always used, with a
+ * remainder of 5e-11 s.
+ *
+ * mpcg_advance_horizon_f64.  The same copies, in doubles; d_tracking_error[b] = (|ee0 - g0| + |ee1 - g1|) + |ee2 - g2| in double, in that order, one
+ * rounding per operation. */
+int mpcg_simulate_f64(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size,
+                      double *d_xs /* [batch][14] in/out */, const double *d_xu /* [batch][(n+m)N - m] */,
+                      double timestep, double time_offset_us, double sim_time_us, double sim_step /* reference with T = double: 2e-4 */,
+                      double *d_eePos /* [batch][3] or NULL */, uint32_t batch, void *stream);
+int mpcg_advance_horizon_f64(mpcg_handle *h, uint32_t control_size, uint32_t shift,
+                             double *d_xu, double *d_lambda, double *d_eePos_goal /* in/out */,
+                             const double *d_xs /* [batch][14] */, const double *d_eePos /* [batch][3]; needed when shift = 1 */,
+                             const double *d_xu_traj, const double *d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride,
+                             uint32_t xu_fill_lead, int32_t *d_traj_offset, int32_t *d_done /* [batch] in/out */,
+                             double *d_tracking_error /* [batch] out */, uint32_t batch, void *stream);
 
 /* ---- LINSYS_SOLVE == 0 as a selectable solver: the reference's CPU LDL^T path ----
  * The reference's second linear-system path factors the (negated) Schur matrix on the HOST with QDLDL

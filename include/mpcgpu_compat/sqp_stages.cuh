@@ -4,7 +4,7 @@
 // return tuples and run the linear-system section on libmpcg_hip; wherever the reference calls one of those stages' kernels they call the
 // function registered here.  All three are in the library now and register themselves for the IIWA-14: use_mpcg_generate_kkt (mpcg_generate_kkt; T = double:
 // mpcg_generate_kkt_f64), use_mpcg_line_search (mpcg_compute_merit + mpcg_line_search_step, T = double: their _f64 twins, with the alpha / rho logic of include/pcg/sqp.cuh:264-353) and
-// use_mpcg_simulate_and_shift (mpcg_simulate + mpcg_advance_horizon with the host bookkeeping of include/mpcsim.cuh:280-352).  A maintainer porting
+// use_mpcg_simulate_and_shift (mpcg_simulate + mpcg_advance_horizon, T = double: their _f64 twins, with the host bookkeeping of include/mpcsim.cuh:280-352).  A maintainer porting
 // MPCGPU with another robot registers thin wrappers around the reference's kernels instead; examples/mpcsim_shim_demo.cpp registers a synthetic
 // convex problem.
 #pragma once
@@ -73,11 +73,15 @@ template <> struct mpcg_entries<float> {
     static constexpr auto generate_kkt = &mpcg_generate_kkt;
     static constexpr auto compute_merit = &mpcg_compute_merit;
     static constexpr auto line_search_step = &mpcg_line_search_step;
+    static constexpr auto simulate = &mpcg_simulate;
+    static constexpr auto advance_horizon = &mpcg_advance_horizon;
 };
 template <> struct mpcg_entries<double> {
     static constexpr auto generate_kkt = &mpcg_generate_kkt_f64;
     static constexpr auto compute_merit = &mpcg_compute_merit_f64;
     static constexpr auto line_search_step = &mpcg_line_search_step_f64;
+    static constexpr auto simulate = &mpcg_simulate_f64;
+    static constexpr auto advance_horizon = &mpcg_advance_horizon_f64;
 };
 template <typename T>
 inline void use_mpcg_generate_kkt(mpcg_plant* plant, float qd_cost, float r_cost) {
@@ -164,13 +168,15 @@ inline void use_mpcg_line_search(float mu, float qd_cost, float r_cost, float ti
 //   max_control_updates                   > 0: `done` after that many updates (a demo's bound); 0: only when the plan is used up (:252)
 //   xu_fill_lead                          0: the reference's source row of the xu tail (:316); knot_points - 1: the row its goal fill uses
 // Needs an mpcg_plant in stages<T>().dynmem (use_mpcg_generate_kkt).
+// T = float: mpcg_simulate / mpcg_advance_horizon; T = double: their _f64 twins (mpcg_entries<T>), one body for both.  sim_step is T(2e-4) as
+// integrator.cuh:304 has it: with T = double that substep runs ten full substeps and a remainder of almost a whole one per 2,000 us (include/mpcg.h).
 template <typename T>
 inline void use_mpcg_simulate_and_shift(const T* d_xu_traj, const T* d_eePos_traj, uint32_t traj_steps, float timestep, double simulation_period_us = -1,
-                                        uint32_t max_control_updates = 0, uint32_t xu_fill_lead = 0, float sim_step = 2e-4f) {
-    static_assert(std::is_same<T, float>::value, "use_mpcg_simulate_and_shift: mpcg_simulate / mpcg_advance_horizon are float entry points");
+                                        uint32_t max_control_updates = 0, uint32_t xu_fill_lead = 0, T sim_step = T(2e-4)) {
+    static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "use_mpcg_simulate_and_shift: float or double (the _f64 entry points)");
     struct sim_state {
         T* d_xu_old = nullptr;           // the plan the plant runs under: the previous update's d_xu (:185-192, :291)
-        float* d_buf = nullptr;          // eePos[3], tracking error, traj_offset, done: 24 bytes that live as long as the process
+        T* d_buf = nullptr;              // eePos[3], tracking error, then traj_offset and done (an int32 in an element's place each): six elements that live as long as the process
         double prev_simulation_time = 0, time_since_timestep = 0;
         bool shifted = false;
         uint32_t traj_offset = 0, updates = 0;
@@ -184,16 +190,16 @@ inline void use_mpcg_simulate_and_shift(const T* d_xu_traj, const T* d_eePos_tra
         const mpcg_plant* plant = static_cast<const mpcg_plant*>(stages<T>().dynmem);
         const size_t traj_len = (size_t)(state_size + control_size) * knot_points - control_size;
         if (!s->d_buf) {
-            if (hipMalloc(reinterpret_cast<void**>(&s->d_buf), 6 * sizeof(float)) != hipSuccess || hipMemset(s->d_buf, 0, 6 * sizeof(float)) != hipSuccess ||
+            if (hipMalloc(reinterpret_cast<void**>(&s->d_buf), 6 * sizeof(T)) != hipSuccess || hipMemset(s->d_buf, 0, 6 * sizeof(T)) != hipSuccess ||
                 hipMalloc(reinterpret_cast<void**>(&s->d_xu_old), traj_len * sizeof(T)) != hipSuccess ||
                 hipMemcpy(s->d_xu_old, d_xu_traj, traj_len * sizeof(T), hipMemcpyDeviceToDevice) != hipSuccess)      // (:192)
                 mpcg_compat::die("use_mpcg_simulate_and_shift: hipMalloc", h);
         }
-        float *d_eePos = s->d_buf, *d_err = s->d_buf + 3;
+        T *d_eePos = s->d_buf, *d_err = s->d_buf + 3;
         int32_t *d_offset = reinterpret_cast<int32_t*>(s->d_buf + 4), *d_done = reinterpret_cast<int32_t*>(s->d_buf + 5);
         const double period = simulation_period_us < 0 ? (stages<T>().const_update_freq ? (double)SIMULATION_PERIOD : 0.0) : simulation_period_us;
         const double simulation_time = period > 0 ? period : sqp_solve_time_us;                                       // (:280-284)
-        if (mpcg_simulate(h, plant, control_size, d_xs, s->d_xu_old, timestep, s->prev_simulation_time, simulation_time, sim_step, d_eePos, 1,
+        if (mpcg_entries<T>::simulate(h, plant, control_size, d_xs, s->d_xu_old, timestep, s->prev_simulation_time, simulation_time, sim_step, d_eePos, 1,
                           /*stream*/ nullptr) != MPCG_OK)
             mpcg_compat::die("simple_simulate", h);                                                                   // (:288)
         if (hipMemcpyAsync(s->d_xu_old, d_xu, traj_len * sizeof(T), hipMemcpyDeviceToDevice, nullptr) != hipSuccess)  // (:291)
@@ -201,7 +207,7 @@ inline void use_mpcg_simulate_and_shift(const T* d_xu_traj, const T* d_eePos_tra
         s->time_since_timestep += simulation_time * 1e-6;
         const T shift_threshold = 1 * timestep;                                                                      // SHIFT_THRESHOLD
         const bool shift = !s->shifted && s->time_since_timestep > shift_threshold;                                   // (:297)
-        if (mpcg_advance_horizon(h, control_size, shift ? 1 : 0, d_xu, d_lambda, d_eePos_goal, d_xs, d_eePos, d_xu_traj, d_eePos_traj, traj_steps, 0,
+        if (mpcg_entries<T>::advance_horizon(h, control_size, shift ? 1 : 0, d_xu, d_lambda, d_eePos_goal, d_xs, d_eePos, d_xu_traj, d_eePos_traj, traj_steps, 0,
                                  xu_fill_lead, d_offset, d_done, d_err, 1, nullptr) != MPCG_OK)
             mpcg_compat::die("just_shift", h);                                                                        // (:300-348)
         if (shift) {

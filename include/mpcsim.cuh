@@ -3,7 +3,7 @@
 // sqpSolvePcg (this repo's include/pcg/sqp.cuh), otherwise sqpSolveQdldl (include/qdldl/sqp.cuh).  The rest of the MPC loop
 // body — plant simulation, tracking error, horizon shift (:288-348) — is the simulate_and_shift plug point of
 // mpcgpu_compat/sqp_stages.cuh; the library's own stage for it is use_mpcg_simulate_and_shift (mpcg_simulate +
-// mpcg_advance_horizon).  lambda is owned here and warm-starts every SQP call (:186, :190, :267), as in the reference.
+// mpcg_advance_horizon; T = double, the -DUSE_DOUBLES build: their _f64 twins).  lambda is owned here and warm-starts every SQP call (:186, :190, :267), as in the reference.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -26,7 +26,11 @@
 #include "qdldl/sqp.cuh"
 #endif
 
-typedef float linsys_t;           // include/common/settings.cuh:45-49 (USE_DOUBLES == 0)
+#ifdef USE_DOUBLES                // include/common/settings.cuh:41-49
+typedef double linsys_t;
+#else
+typedef float linsys_t;
+#endif
 #if TIME_LINSYS == 1
 typedef double toplevel_return_type;
 #else

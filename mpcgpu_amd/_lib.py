@@ -86,7 +86,11 @@ SYMBOLS = {
                                 C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_advance_horizon": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_ldl_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
+    "mpcg_simulate_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
+                                    C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_advance_horizon_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_ldl_create":(C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
     "mpcg_ldl_destroy": (C.c_int, [C.c_void_p]),
     "mpcg_ldl_pattern": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -29,7 +29,7 @@ MULTI_BIN = _ex("multi_gpu_pcg")
 UTILS_BIN = _ex("bd_utils_probe")
 SQP_BATCHED_BIN, SQP_BATCHED_BIN64 = _ex("sqp_batched_iiwa"), _ex("sqp_batched_iiwa_f64")
 LINE_SEARCH_STAGE_BIN = _ex("sqp_line_search_stage")
-MPC_CLOSED_LOOP_BIN = _ex("mpc_closed_loop")
+MPC_CLOSED_LOOP_BIN, MPC_CLOSED_LOOP_BIN64 = _ex("mpc_closed_loop"), _ex("mpc_closed_loop_f64")
 
 
 def sources():
@@ -159,6 +159,12 @@ def build_mpc_closed_loop(force: bool = False, verbose: bool = False) -> str:
     """simulateMPC over the shim headers with all three library stages (use_mpcg_simulate_and_shift), and a batched MPC run over the C ABI."""
     _build_bins([MPC_CLOSED_LOOP_BIN], force, verbose)
     return MPC_CLOSED_LOOP_BIN
+
+
+def build_mpc_closed_loop_f64(force: bool = False, verbose: bool = False) -> str:
+    """The same program compiled with -DUSE_DOUBLES (linsys_t = double): simulateMPC<double> with the three library stages, and the _f64 entry of all eight stages."""
+    _build_bins([MPC_CLOSED_LOOP_BIN64], force, verbose)
+    return MPC_CLOSED_LOOP_BIN64
 
 
 def build_all(force: bool = False, verbose: bool = False) -> str:

@@ -1,6 +1,6 @@
 // mpcg_plant.hip — C ABI (include/mpcg.h) of the producer of the path's inputs: the robot as data (mpcg_plant) and the KKT block assembly
 // mpcg_generate_kkt(_f64) over the gfx950 kernel in kkt_plant.hip.h; the stage behind dz — mpcg_compute_merit(_f64) and
-// mpcg_line_search_step(_rho)(_f64) over merit_plant.hip.h (the merit in packed float, "merit_f32": merit_plant_f32.hip.h); the step between two SQP solves — mpcg_simulate and mpcg_advance_horizon over sim_plant.hip.h.
+// mpcg_line_search_step(_rho)(_f64) over merit_plant.hip.h (the merit in packed float, "merit_f32": merit_plant_f32.hip.h); the step between two SQP solves — mpcg_simulate(_f64) and mpcg_advance_horizon(_f64) over sim_plant.hip.h.
 #include <cmath>
 #include <type_traits>
 #include "mpcg_handle.hpp"
@@ -398,56 +398,91 @@ int mpcg_line_search_step_rho_f64(mpcg_handle* h, uint32_t control_size, const d
 }
 
 // ---- plant simulation and horizon shift: the step between two SQP solves (sim_plant.hip.h) ----
-int mpcg_simulate(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float* d_xs, const float* d_xu, double timestep, double time_offset_us,
-                  double sim_time_us, float sim_step, float* d_eePos, uint32_t batch, void* stream) {
+// mpcg_simulate (T = float) and mpcg_simulate_f64 (T = double), mpcg_advance_horizon and mpcg_advance_horizon_f64: one host path each (fn: the entry point's name)
+extern "C++" {
+template <typename T>
+static int simulate_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, T* d_xs, const T* d_xu, double timestep,
+                         double time_offset_us, double sim_time_us, T sim_step, T* d_eePos, uint32_t batch, void* stream) {
     static_assert(SIM_MAX_SUBSTEPS == MPCG_SIM_MAX_SUBSTEPS, "the cap of the header");
+    constexpr bool F64 = std::is_same<T, double>::value;
     if (!h || !plant) return MPCG_ERR_INVALID;
-    if (!d_xs || !d_xu) return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: null device pointer");
-    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_simulate: state_size 14 / control_size 7 (IIWA-14) only");
-    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: plant and handle live on different devices");
+    if (!d_xs || !d_xu) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
+    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
     if (!std::isfinite(timestep) || !std::isfinite(time_offset_us) || !std::isfinite(sim_time_us) || !std::isfinite(sim_step))
-        return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: timestep, time_offset_us, sim_time_us and sim_step must be finite");
-    if (!(sim_step > 0.f) || !(timestep > 0.0) || time_offset_us < 0.0 || sim_time_us < 0.0)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: needs sim_step > 0, timestep > 0, time_offset_us >= 0 and sim_time_us >= 0");
+        return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": timestep, time_offset_us, sim_time_us and sim_step must be finite");
+    if (!(sim_step > T(0)) || !(timestep > 0.0) || time_offset_us < 0.0 || sim_time_us < 0.0)
+        return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": needs sim_step > 0, timestep > 0, time_offset_us >= 0 and sim_time_us >= 0");
     // the schedule of simple_simulate (include/common/integrator.cuh:301-322), in double
     const double ss = (double)sim_step, toff = time_offset_us * 1e-6, sim = sim_time_us * 1e-6;
     const double full = sim / ss;
-    if (!(full < (double)SIM_MAX_SUBSTEPS + 1.0)) return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: more than 65536 substeps (MPCG_SIM_MAX_SUBSTEPS) in one call");
+    if (!(full < (double)SIM_MAX_SUBSTEPS + 1.0)) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": more than 65536 substeps (MPCG_SIM_MAX_SUBSTEPS) in one call");
     if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_simulate: batch exceeds max_batch");
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
-    SimArgs a;
+    typename std::conditional<F64, SimArgsF64, SimArgs>::type a;
     a.plant = plant->d; a.xs = d_xs; a.xu = d_xu; a.eePos = d_eePos;
     a.N = (int)h->N; a.batch = (int)batch;
     a.S = (unsigned)full; a.ss = ss; a.toff = toff; a.timestep = timestep;
-    a.rem = (double)(float)fmod(sim, ss);
-    hipLaunchKernelGGL(simulate_kernel, dim3((batch + KKT_ITEMS - 1) / KKT_ITEMS), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    a.rem = (double)(T)fmod(sim, ss);                        // (the reference's T: a float remainder is rounded to float, a double one is fmod's value)
+    const dim3 grid((batch + KKT_ITEMS - 1) / KKT_ITEMS);
+    if constexpr (F64) hipLaunchKernelGGL(simulate_f64_kernel, grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    else hipLaunchKernelGGL(simulate_kernel, grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
+}
+
+template <typename T>
+static int advance_horizon_impl(mpcg_handle* h, const char* fn, uint32_t control_size, uint32_t shift, T* d_xu, T* d_lambda, T* d_eePos_goal, const T* d_xs,
+                                const T* d_eePos, const T* d_xu_traj, const T* d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride,
+                                uint32_t xu_fill_lead, int32_t* d_traj_offset, int32_t* d_done, T* d_tracking_error, uint32_t batch, void* stream) {
+    constexpr bool F64 = std::is_same<T, double>::value;
+    const std::string who(fn), sim(F64 ? "mpcg_simulate_f64" : "mpcg_simulate");
+    if (!h) return MPCG_ERR_INVALID;
+    if (shift > 1) return fail(h, MPCG_ERR_INVALID, who + ": shift must be 0 or 1");
+    if (!d_xu || !d_xs) return fail(h, MPCG_ERR_INVALID, who + ": null device pointer");
+    if (shift && !d_eePos) return fail(h, MPCG_ERR_INVALID, who + ": shift = 1 needs d_eePos (the end-effector position " + sim + " wrote)");
+    if (shift && (!d_lambda || !d_eePos_goal || !d_xu_traj || !d_eePos_traj || !d_traj_offset || !d_done || !d_tracking_error))
+        return fail(h, MPCG_ERR_INVALID, who + ": null device pointer (shift = 1 needs every array)");
+    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, who + ": state_size 14 / control_size 7 (IIWA-14) only");
+    if (shift && (traj_steps == 0 || xu_fill_lead > h->N - 1 || (traj_batch_stride != 0 && traj_batch_stride < traj_steps)))
+        return fail(h, MPCG_ERR_INVALID, who + ": needs traj_steps >= 1, xu_fill_lead <= knot_points - 1 and traj_batch_stride 0 or >= traj_steps");
+    if (batch == 0) return MPCG_OK;
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, who + ": batch exceeds max_batch");
+    HIP_TRY(h, hipSetDevice(h->device));
+    typename std::conditional<F64, AdvanceArgsF64, AdvanceArgs>::type a;
+    a.xu = d_xu; a.lambda = d_lambda; a.goal = d_eePos_goal; a.xs = d_xs; a.eePos = d_eePos; a.xu_traj = d_xu_traj; a.goal_traj = d_eePos_traj;
+    a.traj_offset = d_traj_offset; a.done = d_done; a.tracking_error = d_tracking_error;
+    a.n = h->n; a.m = control_size; a.N = h->N; a.traj_steps = traj_steps; a.traj_stride = traj_batch_stride; a.lead = xu_fill_lead; a.shift = shift;
+    if constexpr (F64) hipLaunchKernelGGL(advance_horizon_f64_kernel, dim3(batch), dim3(ADV_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    else hipLaunchKernelGGL(advance_horizon_kernel, dim3(batch), dim3(ADV_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
+}  // extern "C++"
+
+int mpcg_simulate(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float* d_xs, const float* d_xu, double timestep, double time_offset_us,
+                  double sim_time_us, float sim_step, float* d_eePos, uint32_t batch, void* stream) {
+    return simulate_impl<float>(h, "mpcg_simulate", plant, control_size, d_xs, d_xu, timestep, time_offset_us, sim_time_us, sim_step, d_eePos, batch, stream);
+}
+
+int mpcg_simulate_f64(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, double* d_xs, const double* d_xu, double timestep, double time_offset_us,
+                      double sim_time_us, double sim_step, double* d_eePos, uint32_t batch, void* stream) {
+    return simulate_impl<double>(h, "mpcg_simulate_f64", plant, control_size, d_xs, d_xu, timestep, time_offset_us, sim_time_us, sim_step, d_eePos, batch, stream);
 }
 
 int mpcg_advance_horizon(mpcg_handle* h, uint32_t control_size, uint32_t shift, float* d_xu, float* d_lambda, float* d_eePos_goal, const float* d_xs,
                          const float* d_eePos, const float* d_xu_traj, const float* d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride,
                          uint32_t xu_fill_lead, int32_t* d_traj_offset, int32_t* d_done, float* d_tracking_error, uint32_t batch, void* stream) {
-    if (!h) return MPCG_ERR_INVALID;
-    if (shift > 1) return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: shift must be 0 or 1");
-    if (!d_xu || !d_xs) return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: null device pointer");
-    if (shift && !d_eePos) return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: shift = 1 needs d_eePos (the end-effector position mpcg_simulate wrote)");
-    if (shift && (!d_lambda || !d_eePos_goal || !d_xu_traj || !d_eePos_traj || !d_traj_offset || !d_done || !d_tracking_error))
-        return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: null device pointer (shift = 1 needs every array)");
-    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_advance_horizon: state_size 14 / control_size 7 (IIWA-14) only");
-    if (shift && (traj_steps == 0 || xu_fill_lead > h->N - 1 || (traj_batch_stride != 0 && traj_batch_stride < traj_steps)))
-        return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: needs traj_steps >= 1, xu_fill_lead <= knot_points - 1 and traj_batch_stride 0 or >= traj_steps");
-    if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_advance_horizon: batch exceeds max_batch");
-    HIP_TRY(h, hipSetDevice(h->device));
-    AdvanceArgs a;
-    a.xu = d_xu; a.lambda = d_lambda; a.goal = d_eePos_goal; a.xs = d_xs; a.eePos = d_eePos; a.xu_traj = d_xu_traj; a.goal_traj = d_eePos_traj;
-    a.traj_offset = d_traj_offset; a.done = d_done; a.tracking_error = d_tracking_error;
-    a.n = h->n; a.m = control_size; a.N = h->N; a.traj_steps = traj_steps; a.traj_stride = traj_batch_stride; a.lead = xu_fill_lead; a.shift = shift;
-    hipLaunchKernelGGL(advance_horizon_kernel, dim3(batch), dim3(ADV_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    HIP_TRY(h, hipGetLastError());
-    return MPCG_OK;
+    return advance_horizon_impl<float>(h, "mpcg_advance_horizon", control_size, shift, d_xu, d_lambda, d_eePos_goal, d_xs, d_eePos, d_xu_traj, d_eePos_traj, traj_steps,
+                                       traj_batch_stride, xu_fill_lead, d_traj_offset, d_done, d_tracking_error, batch, stream);
+}
+
+int mpcg_advance_horizon_f64(mpcg_handle* h, uint32_t control_size, uint32_t shift, double* d_xu, double* d_lambda, double* d_eePos_goal, const double* d_xs,
+                             const double* d_eePos, const double* d_xu_traj, const double* d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride,
+                             uint32_t xu_fill_lead, int32_t* d_traj_offset, int32_t* d_done, double* d_tracking_error, uint32_t batch, void* stream) {
+    return advance_horizon_impl<double>(h, "mpcg_advance_horizon_f64", control_size, shift, d_xu, d_lambda, d_eePos_goal, d_xs, d_eePos, d_xu_traj, d_eePos_traj,
+                                        traj_steps, traj_batch_stride, xu_fill_lead, d_traj_offset, d_done, d_tracking_error, batch, stream);
 }
 
 }  // extern "C"

@@ -22,6 +22,11 @@
 //
 // advance_horizon_kernel.  One workgroup per trajectory; every value that moves is LOADED, then a barrier, then stored (the source and destination
 // regions of a shift overlap by one knot).  See include/mpcg.h for the order of operations.
+//
+// The double twins (mpcg_simulate_f64, mpcg_advance_horizon_f64; linsys_t = double): simulate_f64_kernel and advance_horizon_f64_kernel over the SAME body
+// texts (sim_steps.inc, sim_advance.inc, included by both kernels of a pair with IO = float / double).  simulate_f64_kernel uses d_xs and the controls as
+// they are and stores the float64 state and end-effector position without a rounding; its remainder is fmod(sim, ss) as a double (the host's part of
+// the schedule: mpcg_plant.hip).  advance_horizon_f64_kernel sweeps chunks of the same number of ELEMENTS and forms the tracking error in double.
 #pragma once
 #include "merit_plant.hip.h"
 #pragma clang fp contract(fast)
@@ -101,69 +106,27 @@ struct SimArgs {
     double rem;                          // the remainder substep, (double)(float)fmod(sim, ss); 0: none
 };
 
+// mpcg_simulate_f64 (linsys_t = double): the same fields with the arrays in double.  d_xs and the controls are used as they are, the state and the end-effector
+// position are stored without a rounding; rem is fmod(sim, ss) as a double.
+struct SimArgsF64 {
+    const PlantDev* plant;
+    double* xs;
+    const double* xu;
+    double* eePos;
+    int N, batch;
+    unsigned S;
+    double ss, toff, timestep;
+    double rem;
+};
+
+// One body text for both (sim_steps.inc, as kkt_knots.inc and merit_points.inc): the arithmetic between load and store is float64 in either.
 __global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgs a) {
-    typedef double R;
-    typedef KktLds<R>::vr kkt_lds_vd;
-    typedef KktLds<R>::item kkt_lds_item;
-    typedef PlantC<R>::creal creal;
-    constexpr int n = 2 * PJ, m = PJ;
-    __shared__ KktItemLds<R> sI[KKT_ITEMS];
-    __shared__ R sF[KKT_ITEMS][KKT_R0 * RN_ROWS];
-    static_assert(sizeof(KktItemLds<R>) * KKT_ITEMS + sizeof(R) * KKT_ITEMS * KKT_R0 * RN_ROWS <= 16384, "the merit kernel's LDS budget");
-    const int lane = threadIdx.x, gi = lane / KKT_GL, l = lane - gi * KKT_GL;
-    kkt_lds_item* I = (kkt_lds_item*)&sI[gi];
-    kkt_lds_vd* recs = (kkt_lds_vd*)&sF[gi][0];
-    kkt_lds_vd* fl = recs + (l < KKT_R0 ? l : 0) * RN_ROWS;
-    const PlantC<R> P{reinterpret_cast<creal*>(reinterpret_cast<unsigned long long>(a.plant))};
-    const long b0 = (long)blockIdx.x * KKT_ITEMS + gi;
-    const bool live = b0 < a.batch;                          // (a group without a trajectory recomputes the last one — it shares this wavefront — and writes nothing)
-    const size_t b = live ? (size_t)b0 : (size_t)a.batch - 1;
-    const float* xu = a.xu + b * ((size_t)(n + m) * a.N - m);
-    float* xs = a.xs + b * n;
-    const unsigned last = (unsigned)a.N - 2;                 // the last knot that has a control
-    auto knot_of = [&](double t) -> unsigned {               // (uint32)(t / timestep), clamped to the last control; one rounding per operation
-        const double v = __ddiv_rn(t, a.timestep);
-        return v >= (double)last ? last : (unsigned)v;
-    };
-    if (l < n) I->Xq[l] = (double)xs[l];
-    unsigned idx = knot_of(a.toff);
-    const unsigned steps = a.S + (a.rem != 0.0 ? 1u : 0u), rounds = steps + (a.eePos ? 1u : 0u);
-    for (unsigned k = 0; k < rounds; ++k) {
-        const bool step = k < steps;                         // the last round of a call with an end-effector output: the pose sweeps on the final state
-        double dt = a.rem;
-        if (k < a.S) { idx = knot_of(__dadd_rn(a.toff, __dmul_rn((double)k, a.ss))); dt = a.ss; }
-        if (l < m) {
-            if (step) I->U[l] = (double)xu[(size_t)idx * (n + m) + n + l];
-            double sn, cs;
-            kkt_sincos(I->Xq[l], sn, cs);
-            I->Sc[0][l] = sn;
-            I->Sc[1][l] = cs;
-        }
-        __syncthreads();
-        // ---- round 0 of the KKT kernel: lanes 0..6 ID(q, 0, e_l), lane 7 ID(q, qd, 0); in the pose round lanes 8..10 instead ----
-        if (l < KKT_R0 && (step ? l <= PJ : l > PJ)) {
-            R a6w[3], a6u[3];
-            RneaTask<R> t;
-            t.sj = -1; t.pj = -1; t.qdscale = (l == PJ) ? 1.0 : 0.0; t.knot_qdd = false; t.unit = l < PJ ? l : -1; t.base = l > PJ ? l - PJ - 1 : -1;
-            rnea<R>(P, fl, I, t, a6w, a6u);
-#pragma unroll
-            for (int r = 0; r < 3; ++r) { fl[RN_AW + r] = a6w[r]; fl[RN_AU + r] = a6u[r]; }
-        }
-        __syncthreads();
-        if (step && l < PJ) {                                // lanes 0..6: qdd_l, then joint l's Euler step from the old values
-            const R qdd = plant_qdd_lane(recs, I, l);
-            const R q = I->Xq[l], qd = I->Xq[PJ + l];
-            I->Xq[l] = q + dt * qd;
-            I->Xq[PJ + l] = qd + dt * qdd;
-        }
-        __syncthreads();
-    }
-    if (a.eePos && live && l < 3) {
-        R ee0, ee1, ee2;
-        plant_ee_pos(recs, ee0, ee1, ee2);
-        a.eePos[b * 3 + l] = (float)(l == 0 ? ee0 : (l == 1 ? ee1 : ee2));
-    }
-    if (live && l < n) xs[l] = (float)I->Xq[l];             // the one rounding of the call
+    typedef float IO;
+#include "sim_steps.inc"
+}
+__global__ __launch_bounds__(KKT_THREADS, 2) void simulate_f64_kernel(SimArgsF64 a) {
+    typedef double IO;
+#include "sim_steps.inc"
 }
 
 struct AdvanceArgs {
@@ -176,16 +139,34 @@ struct AdvanceArgs {
     uint32_t n, m, N, traj_steps, traj_stride, lead, shift;
 };
 
+struct AdvanceArgsF64 {                                     // mpcg_advance_horizon_f64: the same fields with the arrays in double
+    double* xu; double* lambda; double* goal;
+    const double* xs;
+    const double* eePos;
+    const double* xu_traj; const double* goal_traj;
+    int32_t* traj_offset; int32_t* done;
+    double* tracking_error;
+    uint32_t n, m, N, traj_steps, traj_stride, lead, shift;
+};
+
+// (|ee0 - g0| + |ee1 - g1|) + |ee2 - g2| in the arrays' type, in that order, one rounding per operation (mpcsim.cuh:303-306)
+__device__ __forceinline__ float tracking_error_of(const float* ee, const float* goal) {
+    return __fadd_rn(__fadd_rn(fabsf(__fsub_rn(ee[0], goal[0])), fabsf(__fsub_rn(ee[1], goal[1]))), fabsf(__fsub_rn(ee[2], goal[2])));
+}
+__device__ __forceinline__ double tracking_error_of(const double* ee, const double* goal) {
+    return __dadd_rn(__dadd_rn(fabs(__dsub_rn(ee[0], goal[0])), fabs(__dsub_rn(ee[1], goal[1]))), fabs(__dsub_rn(ee[2], goal[2])));
+}
+
 // Every element of the three iterates gets its new value from ONE source element (new_xu, new_goal, lambda[e + n]).  A shift moves values DOWN, so
-// a sweep in ascending chunks of ADV_THREADS x ADV_KEEP elements — load the chunk's sources into registers, barrier, store, barrier — never reads
+// a sweep in ascending chunks of ADV_THREADS x ADV_KEEP elements (floats or doubles) — load the chunk's sources into registers, barrier, store, barrier — never reads
 // an element that was already overwritten: what a store destroys is the source of an element of the same or an earlier chunk.
 constexpr int ADV_THREADS = 256, ADV_KEEP = 8;
-template <class F>
-__device__ __forceinline__ void advance_sweep(float* dst, const size_t count, F&& value) {
-    float v[ADV_KEEP];
+template <class V, class F>
+__device__ __forceinline__ void advance_sweep(V* dst, const size_t count, F&& value) {
+    V v[ADV_KEEP];
     for (size_t c0 = 0; c0 < count; c0 += (size_t)ADV_THREADS * ADV_KEEP) {
 #pragma unroll
-        for (int i = 0; i < ADV_KEEP; ++i) { const size_t e = c0 + (size_t)i * ADV_THREADS + threadIdx.x; v[i] = e < count ? value(e) : 0.f; }
+        for (int i = 0; i < ADV_KEEP; ++i) { const size_t e = c0 + (size_t)i * ADV_THREADS + threadIdx.x; v[i] = e < count ? value(e) : V(0); }
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < ADV_KEEP; ++i) { const size_t e = c0 + (size_t)i * ADV_THREADS + threadIdx.x; if (e < count) dst[e] = v[i]; }
@@ -194,47 +175,12 @@ __device__ __forceinline__ void advance_sweep(float* dst, const size_t count, F&
 }
 
 __global__ __launch_bounds__(ADV_THREADS) void advance_horizon_kernel(AdvanceArgs a) {
-    const size_t b = blockIdx.x;
-    const uint32_t n = a.n, m = a.m, N = a.N, nm = n + m, t = threadIdx.x;
-    const size_t len = (size_t)nm * N - m;
-    float* xu = a.xu + b * len;
-    const float* xs = a.xs + b * n;
-    if (a.done && a.done[b] != 0) return;                    // frozen (uniform; done is written behind the barriers below)
-    if (!a.shift) {                                          // mpcsim.cuh:348 alone
-        for (uint32_t e = t; e < n; e += ADV_THREADS) xu[e] = xs[e];
-        return;
-    }
-    float* lam = a.lambda + b * (size_t)n * N;
-    float* goal = a.goal + b * (size_t)6 * N;
-    const float* xut = a.xu_traj + b * (size_t)a.traj_stride * nm;
-    const float* gt = a.goal_traj + b * (size_t)a.traj_stride * 6;
-    const uint32_t off = (uint32_t)a.traj_offset[b] + 1;     // (:310; a value that is no row of the plan takes the else branch and reads the plan's last row)
-    const bool inside = off >= 1 && (uint64_t)off + N < a.traj_steps;    // (:314, :327)
-    float err = 0.f;
-    if (t == 0) {                                            // (:303-306) against knot 0 of the unshifted goals
-        const float* ee = a.eePos + b * 3;
-        err = __fadd_rn(__fadd_rn(fabsf(__fsub_rn(ee[0], goal[0])), fabsf(__fsub_rn(ee[1], goal[1]))), fabsf(__fsub_rn(ee[2], goal[2])));
-    }
-    // xu: x_0 from xs (:348, the last write of the reference); everything else below the last n + m elements from one knot up (just_shift: knots
-    // 0..N-3 whole, x_{N-2} <- x_{N-1} without a control, integrator.cuh:258-263); the last n + m elements u_{N-2}, x_{N-1} from the plan (:316) or
-    // the final plan position with zero velocity and zero control (:320-322).
-    advance_sweep(xu, len, [&](size_t e) -> float {
-        if (e < n) return xs[e];
-        if (e + nm < len) return xu[e + nm];
-        const uint32_t r = (uint32_t)(e + nm - len);         // 0..m-1: u_{N-2}; m..m+n-1: x_{N-1}
-        if (inside) return xut[(size_t)nm * (off + a.lead) - m + r];
-        return r >= m && r - m < n / 2 ? xut[(size_t)(a.traj_steps - 1) * nm + (r - m)] : 0.f;
-    });
-    advance_sweep(goal, (size_t)6 * N, [&](size_t e) -> float {      // (:326-334)
-        if (e + 6 < (size_t)6 * N) return goal[e + 6];
-        return gt[(size_t)(inside ? off + N - 1 : a.traj_steps - 1) * 6 + (e + 6 - (size_t)6 * N)];
-    });
-    advance_sweep(lam, (size_t)n * (N - 1), [&](size_t e) -> float { return lam[e + n]; });      // the last knot of lambda keeps its value (:337-338)
-    if (t == 0) {
-        a.tracking_error[b] = err;
-        a.traj_offset[b] = (int32_t)off;
-        if (off >= a.traj_steps) a.done[b] = 1;              // (:252)
-    }
+    typedef float IO;
+#include "sim_advance.inc"
+}
+__global__ __launch_bounds__(ADV_THREADS) void advance_horizon_f64_kernel(AdvanceArgsF64 a) {
+    typedef double IO;
+#include "sim_advance.inc"
 }
 
 }  // namespace mpcg

@@ -439,15 +439,20 @@ class PcgSolver:
                  eePos=None, control_size: int | None = None):
         """simple_simulate (include/common/integrator.cuh:295-325), batched, one launch for all substeps: the plant states xs [B, n] are
         integrated in place over sim_time_us under the controls of the plan xu [B, (n+m)N - m], starting time_offset_us into it.
-        eePos (optional, [B, 3]) receives the end-effector position of the new state — what advance_horizon(shift=1) takes."""
+        eePos (optional, [B, 3]) receives the end-effector position of the new state — what advance_horizon(shift=1) takes.
+        float32 tensors: mpcg_simulate (sim_step is rounded to float).  float64 tensors: mpcg_simulate_f64 — the inputs used as they are, the state
+        stored without a rounding, sim_step a double: at the default 2e-4 the reference's double schedule runs ten substeps AND a remainder of
+        almost a whole one per 2,000 us (include/mpcg.h); pass float(numpy.float32(2e-4)) for the float entry's ten.  Mixed dtypes raise TypeError."""
         B = xs.shape[0] if xs.dim() > 1 else 1
         n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        self._chk(xs, B * n, torch.float32, "xs")
-        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
+        dt = self._one_dtype("simulate", xs, xu, eePos)
+        self._chk(xs, B * n, dt, "xs")
+        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
         if eePos is not None:
-            self._chk(eePos, B * 3, torch.float32, "eePos")
-        self._check(self.lib.mpcg_simulate(self._h, plant._p, m, _ptr(xs), _ptr(xu), float(timestep), float(time_offset_us), float(sim_time_us),
-                                           float(sim_step), _ptr(eePos), B, _stream()))
+            self._chk(eePos, B * 3, dt, "eePos")
+        fn = self.lib.mpcg_simulate if dt == torch.float32 else self.lib.mpcg_simulate_f64
+        self._check(fn(self._h, plant._p, m, _ptr(xs), _ptr(xu), float(timestep), float(time_offset_us), float(sim_time_us),
+                       float(sim_step), _ptr(eePos), B, _stream()))
         return xs
 
     def advance_horizon(self, shift: bool, xu, xs, lam=None, eePos_goal=None, eePos=None, xu_traj=None, eePos_traj=None, traj_offset=None,
@@ -456,11 +461,14 @@ class PcgSolver:
         traj_offset += 1, the one-knot shift of xu / eePos_goal / lam with their tails refilled from the plan, then the start-state copy; done
         (int32 [B]) is set when a trajectory has used up its plan, and a trajectory with done != 0 on entry is frozen.
         The plan: xu_traj [T, n+m] and eePos_traj [T, 6] shared by the batch, or [B, T, n+m] and [B, T, 6] per trajectory.
-        xu_fill_lead: 0 = the reference's source row of the xu tail, N - 1 = the row its goal fill uses."""
+        xu_fill_lead: 0 = the reference's source row of the xu tail, N - 1 = the row its goal fill uses.
+        float32 tensors: mpcg_advance_horizon; float64 tensors: mpcg_advance_horizon_f64 (the copies and the tracking error in double).  traj_offset and
+        done are int32 for both.  Mixed dtypes raise TypeError."""
         B = xs.shape[0] if xs.dim() > 1 else 1
         n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        self._chk(xu, B * ((n + m) * N - m), torch.float32, "xu")
-        self._chk(xs, B * n, torch.float32, "xs")
+        dt = self._one_dtype("advance_horizon", xu, xs, lam, eePos_goal, eePos, xu_traj, eePos_traj, tracking_error)
+        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
+        self._chk(xs, B * n, dt, "xs")
         T = stride = 0
         if shift:
             for t, name in ((lam, "lam"), (eePos_goal, "eePos_goal"), (xu_traj, "xu_traj"), (eePos_traj, "eePos_traj"), (traj_offset, "traj_offset"),
@@ -470,19 +478,20 @@ class PcgSolver:
             per_traj = xu_traj.dim() == 3
             T = int(xu_traj.shape[-2])
             stride = T if per_traj else 0
-            self._chk(lam, B * n * N, torch.float32, "lam")
-            self._chk(eePos_goal, B * 6 * N, torch.float32, "eePos_goal")
-            self._chk(xu_traj, (B if per_traj else 1) * T * (n + m), torch.float32, "xu_traj")
-            self._chk(eePos_traj, (B if per_traj else 1) * T * 6, torch.float32, "eePos_traj")
+            self._chk(lam, B * n * N, dt, "lam")
+            self._chk(eePos_goal, B * 6 * N, dt, "eePos_goal")
+            self._chk(xu_traj, (B if per_traj else 1) * T * (n + m), dt, "xu_traj")
+            self._chk(eePos_traj, (B if per_traj else 1) * T * 6, dt, "eePos_traj")
             self._chk(traj_offset, B, torch.int32, "traj_offset")
-            self._chk(tracking_error, B, torch.float32, "tracking_error")
+            self._chk(tracking_error, B, dt, "tracking_error")
             if eePos is not None:
-                self._chk(eePos, B * 3, torch.float32, "eePos")
+                self._chk(eePos, B * 3, dt, "eePos")
         if done is not None:
             self._chk(done, B, torch.int32, "done")
-        self._check(self.lib.mpcg_advance_horizon(self._h, m, 1 if shift else 0, _ptr(xu), _ptr(lam), _ptr(eePos_goal), _ptr(xs), _ptr(eePos),
-                                                  _ptr(xu_traj), _ptr(eePos_traj), T, stride, int(xu_fill_lead), _ptr(traj_offset), _ptr(done),
-                                                  _ptr(tracking_error), B, _stream()))
+        fn = self.lib.mpcg_advance_horizon if dt == torch.float32 else self.lib.mpcg_advance_horizon_f64
+        self._check(fn(self._h, m, 1 if shift else 0, _ptr(xu), _ptr(lam), _ptr(eePos_goal), _ptr(xs), _ptr(eePos),
+                       _ptr(xu_traj), _ptr(eePos_traj), T, stride, int(xu_fill_lead), _ptr(traj_offset), _ptr(done),
+                       _ptr(tracking_error), B, _stream()))
         return xu
 
     def csr_nnz(self) -> int:
