@@ -9,9 +9,11 @@
 // Compiled with -DUSE_DOUBLES (examples/mpc_closed_loop_f64; linsys_t = double, the reference's USE_DOUBLES build) both runs are in double: the stages
 // are the <double> ones, the batched part calls the _f64 entry of all eight stages, and the float data file is widened on load.  The batched part's
 // substep is (linsys_t)2e-4f either way — ten substeps per 2,000 us; simulateMPC's stage uses linsys_t(2e-4) as the reference does (include/mpcg.h).
+// --integrator 1: both runs' KKT blocks and merits use semi-implicit Euler (option "integrator", the stages' integrator_type); --sim-integrator 1: both runs'
+// plant substeps too (option "sim_integrator").  The JSON line carries "integrator" and "sim_integrator" when either flag is given, and is what it was without.
 // Prints one JSON line; exits 0 only if every tracking error is finite and every trajectory shifted the expected number of times.
 //   hipcc --offload-arch=gfx950 -O2 -DLINSYS_SOLVE=1 [-DUSE_DOUBLES] -Iinclude examples/mpc_closed_loop.cpp -Lmpcgpu_amd -lmpcg_hip
-//   mpc_closed_loop [--batch 4] [--knots 16] [--updates 17] [--iters 1] [--mpc-steps 16]
+//   mpc_closed_loop [--batch 4] [--knots 16] [--updates 17] [--iters 1] [--mpc-steps 16] [--integrator {0,1}] [--sim-integrator {0,1}]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -77,15 +79,21 @@ struct ShiftClock {
 
 int main(int argc, char** argv) {
     int B = 4, N = 16, U = 17, K = 1, mpc_steps = 16;
+    int integrator = -1, sim_integrator = -1;                                 // -1: not given (0)
     for (int i = 1; i + 1 < argc; i += 2) {
         if (!strcmp(argv[i], "--batch")) B = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--knots")) N = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--updates")) U = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--iters")) K = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--mpc-steps")) mpc_steps = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--integrator")) integrator = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--sim-integrator")) sim_integrator = atoi(argv[i + 1]);
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (B < 1 || N < 2 || N > 128 || U < 1 || K < 1 || mpc_steps < 1) { fprintf(stderr, "need batch >= 1, 2 <= knots <= 128, updates, iters, mpc-steps >= 1\n"); return 2; }
+    if (integrator < -1 || integrator > 1 || sim_integrator < -1 || sim_integrator > 1) { fprintf(stderr, "--integrator and --sim-integrator take 0 or 1\n"); return 2; }
+    const bool flagged = integrator >= 0 || sim_integrator >= 0;
+    const unsigned integ = integrator > 0 ? 1u : 0u, sim_integ = sim_integrator > 0 ? 1u : 0u;
     const float dt = 1.0f / 64, qd_cost = 1e-4f, mu = 10.f;                  // include/common/settings.cuh:84-94, include/pcg/sqp.cuh:51
     const double period_us = 2000;                                            // SIMULATION_PERIOD
     const std::vector<T> rows = load_rows(argv[0]);
@@ -105,9 +113,9 @@ int main(int argc, char** argv) {
     std::vector<linsys_t> mpc_errors;
     {
         const float r_cost = KNOT_POINTS == 64 ? 1e-3f : 1e-4f;
-        mpcgpu_compat::use_mpcg_generate_kkt<T>(plant, qd_cost, r_cost);
-        mpcgpu_compat::use_mpcg_line_search<T>(mu, qd_cost, r_cost, dt);
-        mpcgpu_compat::use_mpcg_simulate_and_shift<T>(d_plan, d_plan_goals, ROWS, dt, period_us, (uint32_t)mpc_steps);
+        mpcgpu_compat::use_mpcg_generate_kkt<T>(plant, qd_cost, r_cost, integ);
+        mpcgpu_compat::use_mpcg_line_search<T>(mu, qd_cost, r_cost, dt, integ);
+        mpcgpu_compat::use_mpcg_simulate_and_shift<T>(d_plan, d_plan_goals, ROWS, dt, period_us, (uint32_t)mpc_steps, 0, T(2e-4), sim_integ);
         auto& st = mpcgpu_compat::stages<T>();
         st.sqp_max_iter = 2;
         st.const_update_freq = false;         // a fixed number of SQP iterations per update (the wall-clock time box would make the run depend on the machine)
@@ -135,6 +143,8 @@ int main(int argc, char** argv) {
     }
     mpcg_handle* h = nullptr;
     if (mpcg_create(&h, -1, n, (uint32_t)N, (uint32_t)B) != MPCG_OK) { fprintf(stderr, "mpcg_create: %s\n", mpcg_last_error(nullptr)); return 1; }
+    MPCG_OK_OR_DIE(h, mpcg_set_option(h, "integrator", (int)integ));
+    MPCG_OK_OR_DIE(h, mpcg_set_option(h, "sim_integrator", (int)sim_integ));
     T *d_bplan = to_device(bplan), *d_bgoals = to_device(bgoals), *d_xu = to_device(xu), *d_xu_old = to_device(xu), *d_goals = to_device(goals), *d_xs = to_device(xs);
     T* d_G = dalloc<T>((size_t)B * ((nn + mm) * N - mm));
     T* d_C = dalloc<T>((size_t)B * (nn + nm) * (N - 1));
@@ -191,7 +201,9 @@ int main(int argc, char** argv) {
     for (int i = 0; i < shifts * B; ++i) ok = ok && std::isfinite((double)err[i]);
     for (T x : xs_end) ok = ok && std::isfinite((double)x);
     for (int b = 0; b < B; ++b) ok = ok && offset[b] == shifts;
-    printf("{\"batch\": %d, \"knots\": %d, \"updates\": %d, \"iters\": %d, \"expected_shifts\": %d, \"shifts\": [", B, N, U, K, shifts);
+    printf("{\"batch\": %d, \"knots\": %d, \"updates\": %d, \"iters\": %d, ", B, N, U, K);
+    if (flagged) printf("\"integrator\": %u, \"sim_integrator\": %u, ", integ, sim_integ);
+    printf("\"expected_shifts\": %d, \"shifts\": [", shifts);
     for (int b = 0; b < B; ++b) printf("%s%d", b ? ", " : "", offset[b]);
     printf("], \"tracking_errors\": [");
     for (int i = 0; i < shifts; ++i) {

@@ -12,9 +12,11 @@
 // Compiled with -DUSE_DOUBLES (examples/sqp_batched_iiwa_f64; linsys_t = double, the reference's USE_DOUBLES build) the six calls are the library's double entry
 // points — mpcg_generate_kkt_f64 -> mpcg_form_schur(_rhov)_f64 -> mpcg_pcg_solve_f64 -> mpcg_compute_dz_f64 -> mpcg_compute_merit_f64 ->
 // mpcg_line_search_step(_rho)_f64 — on the same inputs widened to double; the merits are then printed with 17 digits.  --merit-f32 has no effect there.
+// --integrator 1 sets option "integrator" = 1: the KKT blocks and every merit of the run use semi-implicit Euler (q' = q + dt qd'; both builds, float and double);
+// the JSON line then carries "integrator".  Without the flag the line is what it was.
 // Prints one JSON line; exits 0 only if every trajectory's merit went down.
 //   hipcc --offload-arch=gfx950 -O2 [-DUSE_DOUBLES] -Iinclude examples/sqp_batched_iiwa.cpp -Lmpcgpu_amd -lmpcg_hip
-//   sqp_batched_iiwa [--batch 8] [--knots 32] [--iters 4] [--mu 10] [--rho 1e-3] [--adapt-rho] [--merit-f32]
+//   sqp_batched_iiwa [--batch 8] [--knots 32] [--iters 4] [--mu 10] [--rho 1e-3] [--adapt-rho] [--merit-f32] [--integrator {0,1}]
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -76,6 +78,7 @@ int main(int argc, char** argv) {
     int B = 8, N = 32, K = 4;
     linsys_t mu = 10.f, rho = (linsys_t)1e-3;
     bool adapt = false, merit_f32 = false;
+    int integrator = -1;                                                      // -1: not given (the handle's default, 0)
     for (int i = 1; i < argc; i += 2) {
         if (!strcmp(argv[i], "--adapt-rho")) { adapt = true; --i; continue; }
         if (!strcmp(argv[i], "--merit-f32")) { merit_f32 = true; --i; continue; }
@@ -85,9 +88,11 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--iters")) K = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--mu")) mu = (linsys_t)atof(argv[i + 1]);
         else if (!strcmp(argv[i], "--rho")) rho = (linsys_t)atof(argv[i + 1]);
+        else if (!strcmp(argv[i], "--integrator")) integrator = atoi(argv[i + 1]);
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (B < 1 || N < 2 || N + 1 > ROWS || K < 1) { fprintf(stderr, "need batch >= 1, 2 <= knots < %d, iters >= 1\n", ROWS); return 2; }
+    if (integrator < -1 || integrator > 1) { fprintf(stderr, "--integrator takes 0 or 1\n"); return 2; }
     const linsys_t dt = 1.0f / 64, qd_cost = (linsys_t)1e-4, r_cost = (linsys_t)(N == 64 ? 1e-3 : 1e-4);      // include/common/settings.cuh:84-94
     const size_t L = (size_t)(n + m) * N - m;
     const std::vector<float> rows = load_rows(argv[0]);
@@ -113,6 +118,7 @@ int main(int argc, char** argv) {
     mpcg_plant* plant = nullptr;
     if (mpcg_create(&h, -1, n, (uint32_t)N, (uint32_t)B) != MPCG_OK) { fprintf(stderr, "mpcg_create: %s\n", mpcg_last_error(nullptr)); return 1; }
     if (merit_f32) MPCG_OK_OR_DIE(h, mpcg_set_option(h, "merit_f32", 1));
+    if (integrator >= 0) MPCG_OK_OR_DIE(h, mpcg_set_option(h, "integrator", integrator));
     if (mpcg_plant_create_iiwa14(&plant, -1) != MPCG_OK) { fprintf(stderr, "mpcg_plant_create_iiwa14: %s\n", mpcg_last_error(nullptr)); return 1; }
 
     const size_t nn = n * n, mm = m * m, nm = n * m;
@@ -176,7 +182,9 @@ int main(int argc, char** argv) {
 
     bool ok = true;
     for (int b = 0; b < B; ++b) ok = ok && std::isfinite(hist[(size_t)K * B + b]) && hist[(size_t)K * B + b] < hist[b];
-    printf("{\"batch\": %d, \"knots\": %d, \"iters\": %d, \"mu\": %g, \"rho\": %g, \"merit\": [", B, N, K, (double)mu, (double)rho);
+    printf("{\"batch\": %d, \"knots\": %d, \"iters\": %d, \"mu\": %g, \"rho\": %g, ", B, N, K, (double)mu, (double)rho);
+    if (integrator >= 0) printf("\"integrator\": %d, ", integrator);
+    printf("\"merit\": [");
     for (int b = 0; b < B; ++b) {
         printf("%s[", b ? ", " : "");
         for (int it = 0; it <= K; ++it) printf("%s" MERIT_FMT, it ? ", " : "", (double)hist[(size_t)it * B + b]);

@@ -331,7 +331,18 @@ int mpcg_block_solve_f64(mpcg_handle *h, const double *d_S, const double *d_gamm
  * mpcg_plant_create checks what the device kernel relies on and returns MPCG_ERR_UNSUPPORTED / MPCG_ERR_INVALID otherwise: every joint
  * rotates about its own z axis (X_k(q) = blkdiag(Rz(q), Rz(q)) X_k(0), the form of GRiD's tables), the spatial inertias are symmetric and of
  * the rigid-body form [[Ibar, skew(m c)], [skew(m c)^T, m 1]], and Xhom describes the same chain as X (the end-effector position and
- * Jacobian are taken from the spatial transforms on the device; Xhom is used for that consistency check only). */
+ * Jacobian are taken from the spatial transforms on the device; Xhom is used for that consistency check only).
+ * THE INTEGRATOR.  Option "integrator" = 0 (default) is explicit Euler, both updates from the old values: A = I + dt [[0, I], [dqdd/dq, dqdd/dqd]],
+ * B = dt [0; Minv], c_{k+1} = x_{k+1} - (x_k + dt [qd; qdd]).  "integrator" = 1 is SEMI-IMPLICIT (symplectic) Euler, INTEGRATOR_TYPE == 1 of the reference
+ * (include/common/integrator.cuh:22-57 defect, :59-100 A and B, :103-130 step; a template parameter of generate_kkt_submatrices, kkt.cuh:22): with the
+ * same qdd = FD(q_k, qd_k, u_k),  qd' = qd + dt qdd,  q' = q + dt qd', so
+ *   c_{k+1} = x_{k+1} - [q + dt (qd + dt qdd) ; qd + dt qdd]                   (c_0 = x_0 - x_s unchanged)
+ *   A = I + dt [[dt dqdd/dq, I + dt dqdd/dqd], [dqdd/dq, dqdd/dqd]]            (the lower half unchanged, the upper half gains dt^2 x its derivative blocks)
+ *   B = [dt^2 Minv ; dt Minv]                                                   (the top half is no longer zero)
+ * stored as before (C = -A, -B, column-major); costs, layouts and the last-block quirk are unchanged.  The option is read when the call is made (a captured
+ * graph keeps what it was captured with), takes 0 or 1 (anything else: MPCG_ERR_INVALID, the value stays) and is orthogonal to "kkt_analytic" and "kkt_f32":
+ * every build has its semi-implicit instantiation (a compile-time parameter of the kernel: no run-time branch, the explicit instantiations are unchanged),
+ * and mpcg_generate_kkt_f64 honours it too.  mpcg_compute_merit(_f64) reads the SAME option: a line search must measure the map this call linearised. */
 typedef struct mpcg_plant mpcg_plant;
 int mpcg_plant_create(mpcg_plant **out, int device, uint32_t num_joints, const double *X_const, const double *I_spatial,
                       const double *Xhom_const, const int32_t *X_trig_idx, const double *X_trig_coef, const int32_t *X_trig_j,
@@ -383,6 +394,12 @@ int mpcg_generate_kkt_f64(mpcg_handle *h, const mpcg_plant *plant, uint32_t cont
  * number depends neither on the rest of the batch nor on the other step sizes of the call.  state_size 14 / control_size 7 only
  * (MPCG_ERR_UNSUPPORTED otherwise).  The first call allocates a handle-owned scratch of max_batch x 16 x knot_points doubles (hipMalloc — not
  * stream work: GRAPH CAPTURE above); later calls are pure stream work.
+ * Option "integrator" = 1 (default 0; the option mpcg_generate_kkt reads — one knob for both on purpose) replaces the violation of a knot by that of the
+ * semi-implicit Euler step (the reference's merit kernels take INTEGRATOR_TYPE as a template parameter, include/common/merit.cuh:99; integrator.cuh:22-57):
+ *   | x_{k+1} - [q_k + dt (qd_k + dt qdd_k) ; qd_k + dt qdd_k] |_1
+ * in the default build, with "merit_f32" = 1 and in mpcg_compute_merit_f64 alike; costs, the initial-state term, the one-rounding trial iterate and the
+ * fixed-order sums are unchanged.  Read when the call is made.  With d_xs given and step size 0, merit(mu + 1) - merit(mu) is the 1-norm of the d_c
+ * mpcg_generate_kkt stores under the same option value, to rounding (tested in double).
  *
  * mpcg_line_search_step is the reference's step selection and update (include/pcg/sqp.cuh:292-301, 317, 332-338, 352), per trajectory b:
  *   best = d_merit_ref[b]; p = -1;  for i in 0 .. num_steps-1: if (d_merit[b][i] < best) { best = d_merit[b][i]; p = i; }
@@ -464,6 +481,12 @@ int mpcg_line_search_step_rho_f64(mpcg_handle *h, uint32_t control_size, const d
  *   there, :322-324), or of (uint32)(toff / timestep) if S = 0.  A remainder of exactly 0 is not run: sim_time_us = 0 leaves d_xs bitwise unchanged.
  * A substep is explicit Euler from the old values, q += dt qd, qd += dt qdd, qdd = forward dynamics of the mpcg_plant without gravity in float64
  * (the arithmetic of mpcg_generate_kkt's integrator defect).  Substeps are gated on their number, never on time accumulated in float.
+ * Option "sim_integrator" = 1 (default 0; 0 or 1, anything else MPCG_ERR_INVALID; read when the call is made) makes every substep SEMI-IMPLICIT Euler,
+ * qd' = qd + dt qdd, q' = q + dt qd' (integrator.cuh:103-130, INTEGRATOR_TYPE == 1), for mpcg_simulate and mpcg_simulate_f64; the schedule, the clamp and
+ * the float64 state carried across substeps are unchanged.  It is an option of its own, apart from "integrator", because the reference's plant simulation
+ * is explicit Euler whatever the controller uses (simple_integrator_kernel calls integrator<T, 0, 0>, integrator.cuh:287): the default stays
+ * reference-exact, and 1 is for a caller whose plant model is the controller's (one substep of dt = timestep is then mpcg_generate_kkt's x_{k+1} - c_{k+1}
+ * under "integrator" = 1).
  * Two deliberate departures from the reference:
  *   - the state is carried in float64 across the substeps of a call and rounded to float ONCE, on store; the reference rounds after every substep
  *     (its T is float).  d_xs and the controls are read as float and widened.
@@ -623,7 +646,11 @@ int mpcg_qdldl_solve_schur(mpcg_handle *h, mpcg_ldl *l, const float *d_val, cons
  *       the default is the one for latency-sized calls), a trajectory's results independent of the rest of the batch; 2 = the same arithmetic with one
  *       knot per lane (8 % faster than the default; differs from 1 by float rounding); 0, the default: float64 inside, results rounded to float on
  *       the way out), "merit_f32" (mpcg_compute_merit: 0, the default: float64 inside; 1: the point merits in packed float, two work items per
- *       16-lane group — see mpcg_compute_merit; any other value is MPCG_ERR_INVALID; independent of "kkt_f32"), "nt_loads" / "spmv_blocks_per_cu" (mpcg_bt_spmv), "spmv_mfma" (the MFMA experiment kernel).
+ *       16-lane group — see mpcg_compute_merit; any other value is MPCG_ERR_INVALID; independent of "kkt_f32"), "integrator" (mpcg_generate_kkt(_f64) and
+ *       mpcg_compute_merit(_f64), every build: 0, the default: explicit Euler; 1: semi-implicit Euler, q' = q + dt qd' — see THE INTEGRATOR under mpcg_plant_create;
+ *       any other value is MPCG_ERR_INVALID and leaves the value; read when the call is made; orthogonal to "kkt_analytic", "kkt_f32" and "merit_f32"),
+ *       "sim_integrator" (mpcg_simulate(_f64): the same choice for the plant's substeps, 0 the default and the reference's — see mpcg_simulate;
+ *       independent of "integrator"), "nt_loads" / "spmv_blocks_per_cu" (mpcg_bt_spmv), "spmv_mfma" (the MFMA experiment kernel).
  * "assume_symmetric" (0 / 1), "symmetry_state" (read-only; 0 unknown, 1 block-symmetric, 2 violated): see BLOCK SYMMETRY above.
  * "reserve_f64" (= 1: allocate the double cluster kernels' buffers now; see GRAPH CAPTURE above).
  * Read-only: "cluster_fixups" (trajectories re-solved by fix-up launches since mpcg_create — each costs 1.5-4.5 ms of spinning; blocking 8-byte

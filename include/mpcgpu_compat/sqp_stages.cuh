@@ -67,6 +67,9 @@ inline sqp_stages<T>& stages() {
 // use_mpcg_simulate_and_shift the plant simulation and the horizon shift.
 // qd_cost / r_cost: QD_COST / R_COST of include/common/settings.cuh:84-94.  Needs gbd_pcg_compat/gpu_pcg.cuh (handle cache) before this header.
 // T = float runs the float entry points, T = double (the reference's USE_DOUBLES build, linsys_t = double) their _f64 twins: mpcg_entries<T> names them.
+// integrator_type (the reference's INTEGRATOR_TYPE, include/common/integrator.cuh): 0 explicit Euler (default), 1 semi-implicit Euler.  Each stage sets it on
+// the handle before its own calls: use_mpcg_generate_kkt and use_mpcg_line_search option "integrator" (give both the same value: the line search must
+// measure the map the KKT stage linearised), use_mpcg_simulate_and_shift option "sim_integrator" (the reference's plant is explicit Euler whatever the controller uses).
 #ifdef MPCG_H
 template <typename T> struct mpcg_entries;
 template <> struct mpcg_entries<float> {
@@ -84,12 +87,13 @@ template <> struct mpcg_entries<double> {
     static constexpr auto advance_horizon = &mpcg_advance_horizon_f64;
 };
 template <typename T>
-inline void use_mpcg_generate_kkt(mpcg_plant* plant, float qd_cost, float r_cost) {
+inline void use_mpcg_generate_kkt(mpcg_plant* plant, float qd_cost, float r_cost, unsigned integrator_type = 0) {
     auto& st = stages<T>();
     st.dynmem = plant;
-    st.generate_kkt = [qd_cost, r_cost](uint32_t state_size, uint32_t control_size, uint32_t knot_points, T* d_G_dense, T* d_C_dense, T* d_g, T* d_c,
+    st.generate_kkt = [qd_cost, r_cost, integrator_type](uint32_t state_size, uint32_t control_size, uint32_t knot_points, T* d_G_dense, T* d_C_dense, T* d_g, T* d_c,
                                          void* d_dynMem_const, float timestep, T* d_eePos_traj, T* d_xs, T* d_xu) {
         mpcg_handle* h = mpcg_compat::handle_for(state_size, knot_points);
+        if (mpcg_set_option(h, "integrator", (int)integrator_type) != MPCG_OK) mpcg_compat::die("use_mpcg_generate_kkt: integrator_type", h);
         if (mpcg_entries<T>::generate_kkt(h, static_cast<const mpcg_plant*>(d_dynMem_const), control_size, timestep, d_eePos_traj, d_xs, d_xu, qd_cost, r_cost,
                                           d_G_dense, d_C_dense, d_g, d_c, 1, /*stream*/ nullptr) != MPCG_OK)
             mpcg_compat::die("generate_kkt_submatrices", h);
@@ -106,7 +110,7 @@ inline void use_mpcg_generate_kkt(mpcg_plant* plant, float qd_cost, float r_cost
 // (include/common/merit.cuh:68-77), against an initial merit from compute_merit, which leaves it out (:133-135) — two different functions, and a
 // step that does not move x_0 can never win by that term.  Here d_xs is passed to all nine evaluations: one function.
 template <typename T>
-inline void use_mpcg_line_search(float mu, float qd_cost, float r_cost, float timestep) {
+inline void use_mpcg_line_search(float mu, float qd_cost, float r_cost, float timestep, unsigned integrator_type = 0) {
     static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "use_mpcg_line_search: float or double (the _f64 entry points)");
     struct ls_state {
         T *d_goal = nullptr, *d_xs = nullptr;
@@ -122,11 +126,12 @@ inline void use_mpcg_line_search(float mu, float qd_cost, float r_cost, float ti
         s->d_goal = d_eePos_traj; s->d_xs = d_xs;
         kkt(state_size, control_size, knot_points, d_G_dense, d_C_dense, d_g, d_c, d_dynMem_const, dt, d_eePos_traj, d_xs, d_xu);
     };
-    st.globalize_and_step = [s, mu, qd_cost, r_cost, timestep](uint32_t state_size, uint32_t control_size, uint32_t knot_points, T* d_xu, T* d_dz, T& rho,
+    st.globalize_and_step = [s, mu, qd_cost, r_cost, timestep, integrator_type](uint32_t state_size, uint32_t control_size, uint32_t knot_points, T* d_xu, T* d_dz, T& rho,
                                                                 T rho_reset, uint32_t sqp_iter) -> bool {
         const T rho_factor = T(1.2), rho_max = T(10), rho_min = T(1e-3);       // include/common/settings.cuh:185-196
         mpcg_handle* h = mpcg_compat::handle_for(state_size, knot_points);
         const mpcg_plant* plant = static_cast<const mpcg_plant*>(stages<T>().dynmem);
+        if (mpcg_set_option(h, "integrator", (int)integrator_type) != MPCG_OK) mpcg_compat::die("use_mpcg_line_search: integrator_type", h);
         if (!s->d_buf && hipMalloc(reinterpret_cast<void**>(&s->d_buf), 10 * sizeof(T)) != hipSuccess) mpcg_compat::die("use_mpcg_line_search: hipMalloc", h);
         T *d_merit = s->d_buf, *d_merit_ref = s->d_buf + 8;
         int32_t* d_step = reinterpret_cast<int32_t*>(s->d_buf + 9);
@@ -172,7 +177,7 @@ inline void use_mpcg_line_search(float mu, float qd_cost, float r_cost, float ti
 // integrator.cuh:304 has it: with T = double that substep runs ten full substeps and a remainder of almost a whole one per 2,000 us (include/mpcg.h).
 template <typename T>
 inline void use_mpcg_simulate_and_shift(const T* d_xu_traj, const T* d_eePos_traj, uint32_t traj_steps, float timestep, double simulation_period_us = -1,
-                                        uint32_t max_control_updates = 0, uint32_t xu_fill_lead = 0, T sim_step = T(2e-4)) {
+                                        uint32_t max_control_updates = 0, uint32_t xu_fill_lead = 0, T sim_step = T(2e-4), unsigned integrator_type = 0) {
     static_assert(std::is_same<T, float>::value || std::is_same<T, double>::value, "use_mpcg_simulate_and_shift: float or double (the _f64 entry points)");
     struct sim_state {
         T* d_xu_old = nullptr;           // the plan the plant runs under: the previous update's d_xu (:185-192, :291)
@@ -189,6 +194,7 @@ inline void use_mpcg_simulate_and_shift(const T* d_xu_traj, const T* d_eePos_tra
         mpcg_handle* h = mpcg_compat::handle_for(state_size, knot_points);
         const mpcg_plant* plant = static_cast<const mpcg_plant*>(stages<T>().dynmem);
         const size_t traj_len = (size_t)(state_size + control_size) * knot_points - control_size;
+        if (mpcg_set_option(h, "sim_integrator", (int)integrator_type) != MPCG_OK) mpcg_compat::die("use_mpcg_simulate_and_shift: integrator_type", h);
         if (!s->d_buf) {
             if (hipMalloc(reinterpret_cast<void**>(&s->d_buf), 6 * sizeof(T)) != hipSuccess || hipMemset(s->d_buf, 0, 6 * sizeof(T)) != hipSuccess ||
                 hipMalloc(reinterpret_cast<void**>(&s->d_xu_old), traj_len * sizeof(T)) != hipSuccess ||

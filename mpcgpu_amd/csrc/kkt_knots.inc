@@ -1,5 +1,5 @@
-// kkt_knots.inc — the body of generate_kkt_kernel<ANALYTIC, R> (IO = float: float arrays) and of generate_kkt_f64_kernel<ANALYTIC> (R = IO = double: double
-// arrays), included INSIDE each kernel (kkt_plant.hip.h) with ANALYTIC, R, IO and the argument struct `a` in scope.  One text for both: a shared
+// kkt_knots.inc — the body of generate_kkt_kernel<ANALYTIC, R, INTEGRATOR> (IO = float: float arrays) and of generate_kkt_f64_kernel<ANALYTIC, INTEGRATOR> (R = IO = double: double
+// arrays), included INSIDE each kernel (kkt_plant.hip.h) with ANALYTIC, R, IO, INTEGRATOR (0 explicit, 1 semi-implicit Euler: `if constexpr` only) and the argument struct `a` in scope.  One text for both: a shared
 // __device__ function in its place changed the code of the float kernels.  Only the loads and the output staging depend on IO.
     typedef KktR<R> T;
     typedef typename T::scalar S;
@@ -185,11 +185,14 @@
             if (l < n && !(KKT_ABLATE & 8)) {
                 const S dt = a.dt;
                 const S gql = l < PJ ? T::get(I->Gq[l], hf) : S(0.0), gq1l = l < PJ ? T::get(I->Gq1[l], hf) : S(0.0);
-                // column l (column-major):  A = I + dt [[0, I], [dqdd/dq, dqdd/dqd]],  Q = blkdiag(g g^T, QD I)
+                // column l (column-major):  A = I + dt [[0, I], [dqdd/dq, dqdd/dqd]] (semi-implicit: [[dt dqdd/dq, I + dt dqdd/dqd], [dqdd/dq, dqdd/dqd]]),  Q = blkdiag(g g^T, QD I)
 #pragma unroll
                 for (int r = 0; r < n; ++r) {
                     S av = (r == l) ? S(1.0) : S(0.0);
-                    if (r < PJ) av += (l == r + PJ) ? dt : S(0.0);
+                    if (r < PJ) {
+                        av += (l == r + PJ) ? dt : S(0.0);
+                        if constexpr (INTEGRATOR == 1) av += dt * (dt * T::get(colv[r], hf));      // semi-implicit: q' = q + dt qd', the upper half gains dt x the lower half's
+                    }
                     else av += dt * T::get(colv[r - PJ], hf);
                     st[ST_C + l * n + r] = (float)(-av);
                     S qv, q1;
@@ -200,7 +203,10 @@
                 }
                 if (l < m) {
 #pragma unroll
-                    for (int r = 0; r < n; ++r) st[ST_C + nn + l * n + r] = (float)(-(r < PJ ? S(0.0) : dt * T::get(I->Minv[r - PJ][l], hf)));      // B = dt [0; Minv]
+                    for (int r = 0; r < n; ++r) {
+                        if constexpr (INTEGRATOR == 1) st[ST_C + nn + l * n + r] = (float)(-(r < PJ ? dt * (dt * T::get(I->Minv[r][l], hf)) : dt * T::get(I->Minv[r - PJ][l], hf)));      // B = [dt^2 Minv; dt Minv]
+                        else st[ST_C + nn + l * n + r] = (float)(-(r < PJ ? S(0.0) : dt * T::get(I->Minv[r - PJ][l], hf)));      // B = dt [0; Minv]
+                    }
 #pragma unroll
                     for (int r = 0; r < m; ++r) st[ST_G + nn + l * m + r] = (float)(r == l ? a.r_cost : S(0.0));
                     st[ST_g + n + l] = (float)(a.r_cost * T::get(I->U[l], hf));
@@ -208,8 +214,12 @@
                 const S qdl = T::get(I->Xq[l < PJ ? l + PJ : l], hf);              // qd_{l mod 7}
                 st[ST_g + l] = (float)(l < PJ ? gql : a.qd_cost * qdl);
                 st[ST_g1 + l] = (float)(l < PJ ? gq1l : a.qd_cost * qdl);  // last block only (evaluated at x_{N-2}: iiwa_eepos_plant.cuh:407)
-                // integrator defect c_{k+1} = x_{k+1} - (x_k + dt [qd; qdd]);  c_0 = x_0 - x_s
-                const S pred = l < PJ ? T::get(I->Xq[l], hf) + dt * qdl : qdl + dt * T::get(I->Qdd[l - PJ], hf);
+                // integrator defect c_{k+1} = x_{k+1} - (x_k + dt [qd; qdd]) (semi-implicit: x_{k+1} - [q + dt qd'; qd'], qd' = qd + dt qdd);  c_0 = x_0 - x_s
+                S pred;
+                if constexpr (INTEGRATOR == 1) {
+                    const S qdn = qdl + dt * T::get(I->Qdd[l < PJ ? l : l - PJ], hf);
+                    pred = l < PJ ? T::get(I->Xq[l], hf) + dt * qdn : qdn;
+                } else pred = l < PJ ? T::get(I->Xq[l], hf) + dt * qdl : qdl + dt * T::get(I->Qdd[l - PJ], hf);
                 st[ST_c1 + l] = (float)((S)xu[hf][(n + m) + l] - pred);
                 if (k == 0) st[ST_c0 + l] = (float)((S)xu[hf][l] - (S)a.xs[(size_t)b * n + l]);
             }
@@ -247,13 +257,19 @@
 #pragma unroll
                 for (int r = 0; r < n; ++r) {
                     S av = (r == l) ? S(1.0) : S(0.0);
-                    if (r < PJ) av += (l == r + PJ) ? dt : S(0.0);
+                    if (r < PJ) {
+                        av += (l == r + PJ) ? dt : S(0.0);
+                        if constexpr (INTEGRATOR == 1) av += dt * (dt * colv[r]);
+                    }
                     else av += dt * colv[r - PJ];
                     sd[l * n + r] = -av;
                 }
                 if (l < m) {
 #pragma unroll
-                    for (int r = 0; r < n; ++r) sd[nn + l * n + r] = -(r < PJ ? S(0.0) : dt * I->Minv[r - PJ][l]);
+                    for (int r = 0; r < n; ++r) {
+                        if constexpr (INTEGRATOR == 1) sd[nn + l * n + r] = -(r < PJ ? dt * (dt * I->Minv[r][l]) : dt * I->Minv[r - PJ][l]);
+                        else sd[nn + l * n + r] = -(r < PJ ? S(0.0) : dt * I->Minv[r - PJ][l]);
+                    }
                 }
             }
             __syncthreads();
@@ -270,7 +286,11 @@
                 const S qdl = I->Xq[l < PJ ? l + PJ : l];
                 sd[SD_g + l] = l < PJ ? gql : a.qd_cost * qdl;
                 sd[SD_g1 + l] = l < PJ ? gq1l : a.qd_cost * qdl;
-                const S pred = l < PJ ? I->Xq[l] + dt * qdl : qdl + dt * I->Qdd[l - PJ];
+                S pred;
+                if constexpr (INTEGRATOR == 1) {
+                    const S qdn = qdl + dt * I->Qdd[l < PJ ? l : l - PJ];
+                    pred = l < PJ ? I->Xq[l] + dt * qdn : qdn;
+                } else pred = l < PJ ? I->Xq[l] + dt * qdl : qdl + dt * I->Qdd[l - PJ];
                 sd[SD_c1 + l] = xu[0][(n + m) + l] - pred;
                 if (k == 0) sd[SD_c0 + l] = xu[0][l] - a.xs[(size_t)b * n + l];
             }

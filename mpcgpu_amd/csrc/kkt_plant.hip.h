@@ -2,6 +2,9 @@
 // generate_kkt_submatrices (reference include/common/kkt.cuh:22-163) together with the plant functions it calls
 // (include/dynamics/iiwa/iiwa_eepos_plant.cuh: forwardDynamicsAndGradient :127-155, trackingCostGradientAndHessian :307-390,
 // _lastblock :392-411) and the Euler integrator (include/common/integrator.cuh:56-104, 143-162).  SURVEY.md §8f row 4.
+// The integrator is the kernels' last template parameter, as it is generate_kkt_submatrices' (kkt.cuh:22, INTEGRATOR_TYPE): 0 explicit Euler, 1 (option
+// "integrator") semi-implicit Euler, q' = q + dt qd' — A = I + dt [[dt dqdd/dq, I + dt dqdd/dqd], [dqdd/dq, dqdd/dqd]], B = [dt^2 Minv; dt Minv],
+// c_{k+1} = x_{k+1} - [q + dt (qd + dt qdd); qd + dt qdd] (integrator.cuh:22-100); `if constexpr` in kkt_knots.inc, no run-time branch.
 //
 // The reference runs GRiD-generated, robot-specific code (10 k lines of unrolled recursions) with one thread block per
 // knot.  Here the robot is DATA (struct PlantDev: the constant "tree" part of every joint's spatial transform — the joint rotation
@@ -457,13 +460,13 @@ __device__ __forceinline__ void kkt_copy_out(T* dst, L* src, int l) {
 #define KKT_WAVES_F32 2      // (the float build at three wavefronts per SIMD: 168 VGPRs, 17 spilled, 0.322 ms per 1024 x 127 knots; at two: 191, none, 0.303; double: 0.328)
 #endif
 // R = double | float: a lane group of 16 = one (trajectory, knot) pair per trip; R = kkt_f2: TWO — items 2 i and 2 i + 1 of the wavefront's eight — in the halves of every value.
-template <bool ANALYTIC, typename R = double>
+template <bool ANALYTIC, typename R = double, int INTEGRATOR = 0>
 __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALYTIC ? KKT_WAVES_ANALYTIC : 2) void generate_kkt_kernel(KktArgsT<typename KktR<R>::scalar> a) {
     typedef float IO;
 #include "kkt_knots.inc"
 }
 // mpcg_generate_kkt_f64: float64 inside as generate_kkt_kernel<ANALYTIC, double>, double arrays in and out
-template <bool ANALYTIC>
+template <bool ANALYTIC, int INTEGRATOR = 0>
 __global__ __launch_bounds__(KKT_THREADS, ANALYTIC ? KKT_WAVES_ANALYTIC : 2) void generate_kkt_f64_kernel(KktArgsF64 a) {
     typedef double R;
     typedef double IO;

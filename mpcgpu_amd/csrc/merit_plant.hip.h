@@ -6,6 +6,9 @@
 //     merit(b, a) = sum_{k<N} J_k + mu ( sum_{k<N-1} | x_{k+1} - (x_k + dt [qd_k; qdd_k]) |_1  +  [xs given] | x_0 - xs_b |_1 )      at z = xu_b + alpha_a dz_b
 //     J_k = 1/2 |ee(q_k) - goal_k|^2 + 1/2 qd_cost |qd_k|^2 + [k < N-1] 1/2 r_cost |u_k|^2
 //
+// The integrator is a compile-time parameter of the three point-merit kernels (INTEGRATOR, option "integrator": the one mpcg_generate_kkt reads, merit.cuh:99):
+// 0 the explicit Euler step above, 1 semi-implicit Euler, | x_{k+1} - [q_k + dt (qd_k + dt qdd_k); qd_k + dt qdd_k] |_1 (integrator.cuh:22-57).
+//
 // What a point merit needs is what round 0 of generate_kkt_kernel (kkt_plant.hip.h) computes — qdd = M^-1 (u - bias) and the end-effector position —
 // so the mapping is that kernel's: a 16-lane group per work item (trajectory, step size, knot), four items per wavefront; lanes 0..6 the
 // inertia-matrix columns, lane 7 the bias, lanes 8..10 the pose sweeps through the same rnea<double>, then lanes 0..6 the Cholesky solve.  There is no
@@ -69,10 +72,12 @@ struct MeritArgsF64 {
     double alpha[MERIT_MAX_STEPS];
 };
 
+template <int INTEGRATOR = 0>
 __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(MeritArgs a) {
     typedef float IO;
 #include "merit_points.inc"
 }
+template <int INTEGRATOR = 0>
 __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f64_kernel(MeritArgsF64 a) {
     typedef double IO;
 #include "merit_points.inc"

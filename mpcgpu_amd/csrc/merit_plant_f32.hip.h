@@ -38,6 +38,7 @@ struct MeritArgsF32 {
 
 __device__ __forceinline__ kkt_f2 merit_sel(const bool (&c)[2], kkt_f2 x, kkt_f2 y) { return kkt_f2{c[0] ? x.x : y.x, c[1] ? x.y : y.y}; }
 
+template <int INTEGRATOR = 0>
 __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(MeritArgsF32 a) {
     typedef kkt_f2 R;
     typedef KktR<R> T;
@@ -188,7 +189,12 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(MeritA
             }
             // the dynamics half's control cost and integrator defect: computed for both halves, kept where the half is a dynamics item
             const R pm_dyn = pm + sp(0.5f * a.r_cost) * ul * ul;
-            const R viol_dyn = __builtin_elementwise_abs(xn_q - (q + sp(a.dt) * qd)) + __builtin_elementwise_abs(xn_qd - (qd + sp(a.dt) * qdd));
+            R viol_dyn;
+            if constexpr (INTEGRATOR == 1) {                 // semi-implicit Euler: q' = q + dt qd', qd' = qd + dt qdd
+                const R qdn = qd + sp(a.dt) * qdd;
+                viol_dyn = __builtin_elementwise_abs(xn_q - (q + sp(a.dt) * qdn)) + __builtin_elementwise_abs(xn_qd - qdn);
+            } else
+            viol_dyn = __builtin_elementwise_abs(xn_q - (q + sp(a.dt) * qd)) + __builtin_elementwise_abs(xn_qd - (qd + sp(a.dt) * qdd));
             pm = merit_sel(dyn, pm_dyn, pm);
             R viol = merit_sel(dyn, viol_dyn, sp(0.f));
             // the initial-state term, likewise (a half that has none reads its trajectory's x_s all the same; no x_s at all: x_0 of the first trajectory — finite or not, dropped)

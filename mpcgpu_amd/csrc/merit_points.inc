@@ -1,5 +1,5 @@
 // merit_points.inc — the body of merit_points_kernel (IO = float) and of merit_points_f64_kernel (IO = double), included INSIDE each kernel
-// (merit_plant.hip.h) with IO and the argument struct `a` in scope.  One text for both: a shared __device__ function in its place changed the code of
+// (merit_plant.hip.h) with IO, INTEGRATOR (0 explicit, 1 semi-implicit Euler) and the argument struct `a` in scope.  One text for both: a shared __device__ function in its place changed the code of
 // the float kernel.  Only the loads and the trial iterate depend on IO.
     typedef double R;
     typedef KktLds<R>::vr kkt_lds_vd;
@@ -121,6 +121,10 @@
             R viol = 0.0;
             if (dyn) {
                 pm += 0.5 * a.r_cost * ul * ul;
+                if constexpr (INTEGRATOR == 1) {                  // semi-implicit Euler: q' = q + dt qd', qd' = qd + dt qdd (the map the KKT kernel linearised)
+                    const R qdn = qd + a.dt * qdd;
+                    viol = fabs(xn_q - (q + a.dt * qdn)) + fabs(xn_qd - qdn);
+                } else
                 viol = fabs(xn_q - (q + a.dt * qd)) + fabs(xn_qd - (qd + a.dt * qdd));
             }
             if (k == 0 && a.xs) viol += fabs(q - (R)a.xs[(size_t)b * n + l]) + fabs(qd - (R)a.xs[(size_t)b * n + PJ + l]);

@@ -55,6 +55,8 @@ struct mpcg_handle {
     int kkt_analytic = 1;     // mpcg_generate_kkt: 1 = analytic gradient recursion of the inverse dynamics (as the reference's GRiD code), 0 = one-sided float64 differences (the checker)
     int kkt_f32 = 0;          // mpcg_generate_kkt: 1 = the analytic kernel in float arithmetic (linsys_t's own, as the reference's GRiD<float>); 0 = float64 inside
     int merit_f32 = 0;        // mpcg_compute_merit: 1 = the point merits in packed float (merit_plant_f32.hip.h: the reference's own arithmetic, two items per lane group); 0 = float64 inside
+    int integrator = 0;       // mpcg_generate_kkt(_f64) and mpcg_compute_merit(_f64), every build: 0 = explicit Euler, 1 = semi-implicit (symplectic) Euler, q' = q + dt qd' (the reference's INTEGRATOR_TYPE)
+    int sim_integrator = 0;   // mpcg_simulate(_f64): the same choice for the plant's substep (the reference's plant is explicit Euler whatever the controller uses: 0)
     int dz_dpp = 1;           // 1: four-knots-per-wavefront dz recovery (schur_walk.hip.h), 0: the LDS kernel (schur_generic.hip.h)
     int last_schur_chunk = 0; //   what the last mpcg_form_schur used (0: the LDS kernels)
     int producers_generic = 0; // 1: form_schur(_f64), compute_dz(_f64) and block_solve of a (14, 7) call run the run-time-dimension kernels (schur_generic.hip.h) every other shape gets (formation and dz: what "schur_dpp" / "dz_dpp" = 0 run too)

@@ -318,6 +318,10 @@ int mpcg_set_option(mpcg_handle* h, const char* key, int value) {
         if (value != 0 && value != 1) return fail(h, MPCG_ERR_INVALID, "merit_f32 must be 0 (float64 inside) or 1 (packed float)");
         h->merit_f32 = value; return MPCG_OK;
     }
+    if (!strcmp(key, "integrator") || !strcmp(key, "sim_integrator")) {
+        if (value != 0 && value != 1) return fail(h, MPCG_ERR_INVALID, std::string(key) + " must be 0 (explicit Euler) or 1 (semi-implicit Euler)");
+        (key[0] == 's' ? h->sim_integrator : h->integrator) = value; return MPCG_OK;
+    }
     if (!strcmp(key, "block_solve_f64")) {
         if (value != 0 && value != 1) return fail(h, MPCG_ERR_INVALID, "block_solve_f64 must be 0 (the float sweep) or 1 (float64 inside)");
         h->block_solve_f64 = value; return MPCG_OK;
@@ -361,6 +365,8 @@ int mpcg_get_option(const mpcg_handle* h, const char* key, int* value) {
     if (!strcmp(key, "kkt_analytic")) { *value = h->kkt_analytic; return MPCG_OK; }
     if (!strcmp(key, "kkt_f32")) { *value = h->kkt_f32; return MPCG_OK; }
     if (!strcmp(key, "merit_f32")) { *value = h->merit_f32; return MPCG_OK; }
+    if (!strcmp(key, "integrator")) { *value = h->integrator; return MPCG_OK; }
+    if (!strcmp(key, "sim_integrator")) { *value = h->sim_integrator; return MPCG_OK; }
     if (!strcmp(key, "block_solve_f64")) { *value = h->block_solve_f64; return MPCG_OK; }
     if (!strcmp(key, "sched_hint")) { *value = h->sched_hint; return MPCG_OK; }
     if (!strcmp(key, "spmv_blocks_per_cu")) { *value = h->spmv_blocks_per_cu; return MPCG_OK; }

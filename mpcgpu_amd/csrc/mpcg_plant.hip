@@ -216,9 +216,12 @@ static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* p
     long blocks = ((long)batch * (h->N - 1) + KKT_ITEMS - 1) / KKT_ITEMS;      // one wavefront per KKT_ITEMS (trajectory, knot) pairs
     const long cap = (long)h->num_cus * 32;
     if (blocks > cap) blocks = cap;
+    // "integrator" = 1: the semi-implicit instantiation of the same build (a compile-time parameter: the explicit instantiations are the kernels they were)
+    const bool semi = h->integrator == 1;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
     if constexpr (std::is_same<T, double>::value) {       // double arrays: float64 inside, either gradient route
-        if (h->kkt_analytic) hipLaunchKernelGGL((generate_kkt_f64_kernel<true>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
-        else hipLaunchKernelGGL((generate_kkt_f64_kernel<false>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+        if (h->kkt_analytic) hipLaunchKernelGGL((semi ? generate_kkt_f64_kernel<true, 1> : generate_kkt_f64_kernel<true, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((semi ? generate_kkt_f64_kernel<false, 1> : generate_kkt_f64_kernel<false, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
     } else {
         if (h->kkt_analytic && h->kkt_f32) {                  // linsys_t = float arithmetic throughout, as the reference's GRiD code (kkt_plant.hip.h, R = float)
             KktArgsT<float> f;
@@ -230,11 +233,11 @@ static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* p
             if (h->kkt_f32 == 1) {
                 long pblocks = ((long)batch * (h->N - 1) + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
                 if (pblocks > cap) pblocks = cap;
-                hipLaunchKernelGGL((generate_kkt_kernel<true, kkt_f2>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), f);
+                hipLaunchKernelGGL((semi ? generate_kkt_kernel<true, kkt_f2, 1> : generate_kkt_kernel<true, kkt_f2, 0>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
             } else
-            hipLaunchKernelGGL((generate_kkt_kernel<true, float>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), f);
-        } else if (h->kkt_analytic) hipLaunchKernelGGL((generate_kkt_kernel<true, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
-        else hipLaunchKernelGGL((generate_kkt_kernel<false, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+            hipLaunchKernelGGL((semi ? generate_kkt_kernel<true, float, 1> : generate_kkt_kernel<true, float, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, f);
+        } else if (h->kkt_analytic) hipLaunchKernelGGL((semi ? generate_kkt_kernel<true, double, 1> : generate_kkt_kernel<true, double, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((semi ? generate_kkt_kernel<false, double, 1> : generate_kkt_kernel<false, double, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
     }
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
@@ -291,8 +294,9 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
     const long cap = (long)h->num_cus * 32;
     if (blocks > cap) blocks = cap;
     const int rows = (int)(batch * num_steps);
+    const bool semi = h->integrator == 1;          // "integrator": the map mpcg_generate_kkt linearised (one knob for both, every build)
     if constexpr (F64) {                          // double arrays: float64 inside ("merit_f32" is the float entry's), the row sums stored as they are
-        hipLaunchKernelGGL(merit_points_f64_kernel, dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+        hipLaunchKernelGGL((semi ? merit_points_f64_kernel<1> : merit_points_f64_kernel<0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
         HIP_TRY(h, hipGetLastError());
         hipLaunchKernelGGL(merit_sum_f64_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
     } else {
@@ -306,9 +310,9 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
             // scratch of max_batch x 16 x N doubles could be allocated stays far below the 2^31 - 1 workgroups a grid dimension holds
             const long pblocks = ((long)batch * num_steps * h->N + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
             if (pblocks > 0x7fffffffL) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch x num_steps x knot_points exceeds the grid");
-            hipLaunchKernelGGL(merit_points_f32_kernel, dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
+            hipLaunchKernelGGL((semi ? merit_points_f32_kernel<1> : merit_points_f32_kernel<0>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
         } else
-        hipLaunchKernelGGL(merit_points_kernel, dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+        hipLaunchKernelGGL((semi ? merit_points_kernel<1> : merit_points_kernel<0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
         HIP_TRY(h, hipGetLastError());
         hipLaunchKernelGGL(merit_sum_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
     }
@@ -426,8 +430,9 @@ static int simulate_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant
     a.S = (unsigned)full; a.ss = ss; a.toff = toff; a.timestep = timestep;
     a.rem = (double)(T)fmod(sim, ss);                        // (the reference's T: a float remainder is rounded to float, a double one is fmod's value)
     const dim3 grid((batch + KKT_ITEMS - 1) / KKT_ITEMS);
-    if constexpr (F64) hipLaunchKernelGGL(simulate_f64_kernel, grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    else hipLaunchKernelGGL(simulate_kernel, grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    const bool semi = h->sim_integrator == 1;      // "sim_integrator": the substep q' = q + dt qd' (0, the default: the reference's plant, explicit Euler)
+    if constexpr (F64) hipLaunchKernelGGL((semi ? simulate_f64_kernel<1> : simulate_f64_kernel<0>), grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    else hipLaunchKernelGGL((semi ? simulate_kernel<1> : simulate_kernel<0>), grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }

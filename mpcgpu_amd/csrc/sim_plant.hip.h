@@ -3,7 +3,8 @@
 // all substeps, and of the tracking error, just_shift, the tail fills and the start-state copy of simulateMPC (include/mpcsim.cuh:300-348: one
 // cudaMemcpy per knot) as a second, dynamics-free kernel.
 //
-// simulate_kernel.  A substep is the explicit Euler step of the KKT kernel's integrator, q += dt qd, qd += dt qdd (both from the old values), qdd =
+// simulate_kernel<INTEGRATOR>.  A substep is the explicit Euler step of the KKT kernel's integrator, q += dt qd, qd += dt qdd (both from the old values;
+// INTEGRATOR = 1, option "sim_integrator": semi-implicit Euler, qd' = qd + dt qdd, q' = q + dt qd' — a compile-time parameter, `if constexpr` in sim_steps.inc), qdd =
 // Minv (u - bias) without gravity, so the mapping is merit_points_kernel's: a 16-lane group per trajectory, four trajectories per wavefront; lanes
 // 0..6 the inertia-matrix columns and lane 7 the bias through rnea<double>, then lanes 0..6 the Cholesky solve (plant_qdd_lane: the merit kernel's
 // arithmetic).  The substeps are a loop INSIDE the kernel: q, qd and sin / cos wait in the item record in LDS between them.  The schedule is the reference's,
@@ -120,10 +121,12 @@ struct SimArgsF64 {
 };
 
 // One body text for both (sim_steps.inc, as kkt_knots.inc and merit_points.inc): the arithmetic between load and store is float64 in either.
+template <int INTEGRATOR = 0>
 __global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgs a) {
     typedef float IO;
 #include "sim_steps.inc"
 }
+template <int INTEGRATOR = 0>
 __global__ __launch_bounds__(KKT_THREADS, 2) void simulate_f64_kernel(SimArgsF64 a) {
     typedef double IO;
 #include "sim_steps.inc"

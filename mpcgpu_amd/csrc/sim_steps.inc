@@ -1,5 +1,5 @@
 // sim_steps.inc — the body of simulate_kernel (IO = float) and of simulate_f64_kernel (IO = double), included INSIDE each kernel (sim_plant.hip.h)
-// with IO and the argument struct `a` in scope.  One text for both, as kkt_knots.inc and merit_points.inc: only the loads (widened, or used as they
+// with IO, INTEGRATOR (0 explicit, 1 semi-implicit Euler: "sim_integrator") and the argument struct `a` in scope.  One text for both, as kkt_knots.inc and merit_points.inc: only the loads (widened, or used as they
 // are) and the stores (rounded once, or not at all) depend on IO.
     typedef double R;
     typedef KktLds<R>::vr kkt_lds_vd;
@@ -52,8 +52,14 @@
         if (step && l < PJ) {                                // lanes 0..6: qdd_l, then joint l's Euler step from the old values
             const R qdd = plant_qdd_lane(recs, I, l);
             const R q = I->Xq[l], qd = I->Xq[PJ + l];
+            if constexpr (INTEGRATOR == 1) {                 // semi-implicit Euler: the position moves with the NEW velocity
+                const R qdn = qd + dt * qdd;
+                I->Xq[l] = q + dt * qdn;
+                I->Xq[PJ + l] = qdn;
+            } else {
             I->Xq[l] = q + dt * qd;
             I->Xq[PJ + l] = qd + dt * qdd;
+            }
         }
         __syncthreads();
     }
