@@ -11,9 +11,14 @@
 // substep is (linsys_t)2e-4f either way — ten substeps per 2,000 us; simulateMPC's stage uses linsys_t(2e-4) as the reference does (include/mpcg.h).
 // --integrator 1: both runs' KKT blocks and merits use semi-implicit Euler (option "integrator", the stages' integrator_type); --sim-integrator 1: both runs'
 // plant substeps too (option "sim_integrator").  The JSON line carries "integrator" and "sim_integrator" when either flag is given, and is what it was without.
+// --gravity G: the controller's model is the plant cloned with the reference's scalar gato_plant::GRAVITY = G (mpcg_plant_clone_gravity, base acceleration
+// {0, 0, G}; 9.81: the arm stands on the ground) in both runs, and the file's controls — made for zero gravity — gain the gravity torques
+// mpcg_inverse_dynamics(q_row, 0, 0) once, up front, on the device.  --sim-gravity G (default: --gravity) is the SIMULATED plant's scalar in the batched run,
+// as --sim-integrator is its integrator: the plant need not be the controller's model.  (simulateMPC's stages share one plant, stages<T>().dynmem: the
+// controller's.)  The JSON line carries "gravity" and "sim_gravity" when either is non-zero, and is what it was otherwise.
 // Prints one JSON line; exits 0 only if every tracking error is finite and every trajectory shifted the expected number of times.
 //   hipcc --offload-arch=gfx950 -O2 -DLINSYS_SOLVE=1 [-DUSE_DOUBLES] -Iinclude examples/mpc_closed_loop.cpp -Lmpcgpu_amd -lmpcg_hip
-//   mpc_closed_loop [--batch 4] [--knots 16] [--updates 17] [--iters 1] [--mpc-steps 16] [--integrator {0,1}] [--sim-integrator {0,1}]
+//   mpc_closed_loop [--batch 4] [--knots 16] [--updates 17] [--iters 1] [--mpc-steps 16] [--integrator {0,1}] [--sim-integrator {0,1}] [--gravity G] [--sim-gravity G]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -77,8 +82,27 @@ struct ShiftClock {
     }
 };
 
+// u_row += tau_row for `count` rows of (x, u) of the plan
+__global__ void gather_q(const T* rows, T* q, int count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count * m) q[i] = rows[(size_t)(i / m) * (n + m) + i % m];
+}
+__global__ void add_to_u(T* rows, const T* tau, int count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count * m) rows[(size_t)(i / m) * (n + m) + n + i % m] += tau[i];
+}
+
+static mpcg_plant* clone_with_gravity(const mpcg_plant* src, double g) {
+    const double base_accel[3] = {0.0, 0.0, g};
+    mpcg_plant* p = nullptr;
+    if (mpcg_plant_clone_gravity(&p, src, base_accel) != MPCG_OK) { fprintf(stderr, "mpcg_plant_clone_gravity: %s\n", mpcg_last_error(nullptr)); exit(1); }
+    return p;
+}
+
 int main(int argc, char** argv) {
     int B = 4, N = 16, U = 17, K = 1, mpc_steps = 16;
+    double gravity = 0.0, sim_gravity = 0.0;
+    bool sim_gravity_given = false;
     int integrator = -1, sim_integrator = -1;                                 // -1: not given (0)
     for (int i = 1; i + 1 < argc; i += 2) {
         if (!strcmp(argv[i], "--batch")) B = atoi(argv[i + 1]);
@@ -88,10 +112,14 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--mpc-steps")) mpc_steps = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--integrator")) integrator = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--sim-integrator")) sim_integrator = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--gravity")) gravity = atof(argv[i + 1]);
+        else if (!strcmp(argv[i], "--sim-gravity")) { sim_gravity = atof(argv[i + 1]); sim_gravity_given = true; }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (B < 1 || N < 2 || N > 128 || U < 1 || K < 1 || mpc_steps < 1) { fprintf(stderr, "need batch >= 1, 2 <= knots <= 128, updates, iters, mpc-steps >= 1\n"); return 2; }
     if (integrator < -1 || integrator > 1 || sim_integrator < -1 || sim_integrator > 1) { fprintf(stderr, "--integrator and --sim-integrator take 0 or 1\n"); return 2; }
+    if (!sim_gravity_given) sim_gravity = gravity;
+    if (!std::isfinite(gravity) || !std::isfinite(sim_gravity)) { fprintf(stderr, "--gravity and --sim-gravity take finite numbers\n"); return 2; }
     const bool flagged = integrator >= 0 || sim_integrator >= 0;
     const unsigned integ = integrator > 0 ? 1u : 0u, sim_integ = sim_integrator > 0 ? 1u : 0u;
     const float dt = 1.0f / 64, qd_cost = 1e-4f, mu = 10.f;                  // include/common/settings.cuh:84-94, include/pcg/sqp.cuh:51
@@ -106,14 +134,30 @@ int main(int argc, char** argv) {
     auto rnd = [&seed]() { seed = seed * 1664525u + 1013904223u; return ((seed >> 8) & 0xffff) / 65536.0f - 0.5f; };
     mpcg_plant* plant = nullptr;
     if (mpcg_plant_create_iiwa14(&plant, -1) != MPCG_OK) { fprintf(stderr, "mpcg_plant_create_iiwa14: %s\n", mpcg_last_error(nullptr)); return 1; }
+    // the controller's model and the simulated plant of the batched run: the plain plant, or clones with gato_plant::GRAVITY = G
+    mpcg_plant* plant_ctrl = gravity != 0.0 ? clone_with_gravity(plant, gravity) : plant;
+    mpcg_plant* plant_sim = sim_gravity == gravity ? plant_ctrl : (sim_gravity != 0.0 ? clone_with_gravity(plant, sim_gravity) : plant);
     T* d_plan = to_device(plan);
     T* d_plan_goals = to_device(plan_goals);
+    if (gravity != 0.0) {                                                     // the file's controls hold the arm without gravity: u_row += ID(q_row, 0, 0), once
+        mpcg_handle* hid = nullptr;                                           // (a handle for this call alone: count <= max_batch x knot_points)
+        if (mpcg_create(&hid, -1, n, 32, (uint32_t)((ROWS + 31) / 32)) != MPCG_OK) { fprintf(stderr, "mpcg_create: %s\n", mpcg_last_error(nullptr)); return 1; }
+        T *d_q = dalloc<T>((size_t)ROWS * m), *d_tau = dalloc<T>((size_t)ROWS * m);
+        const int blocks = (ROWS * m + 255) / 256;
+        hipLaunchKernelGGL(gather_q, dim3(blocks), dim3(256), 0, nullptr, d_plan, d_q, ROWS);
+        MPCG_OK_OR_DIE(hid, LS(mpcg_inverse_dynamics)(hid, plant_ctrl, d_q, nullptr, nullptr, d_tau, (uint32_t)ROWS, nullptr));
+        hipLaunchKernelGGL(add_to_u, dim3(blocks), dim3(256), 0, nullptr, d_plan, d_tau, ROWS);
+        gpuErrchk(hipMemcpy(plan.data(), d_plan, plan.size() * sizeof(T), hipMemcpyDeviceToHost));      // (the batched run's plans and iterates are cut from it below)
+        gpuErrchk(hipFree(d_q));
+        gpuErrchk(hipFree(d_tau));
+        mpcg_destroy(hid);
+    }
 
     // ---- 1. simulateMPC with the three library stages (single trajectory, KNOT_POINTS knots) ----
     std::vector<linsys_t> mpc_errors;
     {
         const float r_cost = KNOT_POINTS == 64 ? 1e-3f : 1e-4f;
-        mpcgpu_compat::use_mpcg_generate_kkt<T>(plant, qd_cost, r_cost, integ);
+        mpcgpu_compat::use_mpcg_generate_kkt<T>(plant_ctrl, qd_cost, r_cost, integ);
         mpcgpu_compat::use_mpcg_line_search<T>(mu, qd_cost, r_cost, dt, integ);
         mpcgpu_compat::use_mpcg_simulate_and_shift<T>(d_plan, d_plan_goals, ROWS, dt, period_us, (uint32_t)mpc_steps, 0, T(2e-4), sim_integ);
         auto& st = mpcgpu_compat::stages<T>();
@@ -167,18 +211,18 @@ int main(int argc, char** argv) {
         // one SQP call (include/pcg/sqp.cuh): x_s = x_0 of the iterate, drho = 1, merit of the start iterate, K iterations
         gpuErrchk(hipMemcpyAsync(d_drho, d_ones, B * sizeof(T), hipMemcpyDeviceToDevice, s));
         gpuErrchk(hipMemsetAsync(d_gave_up, 0, B, s));
-        MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant, m, dt, d_goals, d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, (uint32_t)B, s));
+        MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, (uint32_t)B, s));
         for (int it = 0; it < K; ++it) {
-            MPCG_OK_OR_DIE(h, LS(mpcg_generate_kkt)(h, plant, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, s));
+            MPCG_OK_OR_DIE(h, LS(mpcg_generate_kkt)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, s));
             MPCG_OK_OR_DIE(h, LS(mpcg_form_schur_rhov)(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_rho, (uint32_t)B, MPCG_PRECOND_SS, s));
             MPCG_OK_OR_DIE(h, LS(mpcg_pcg_solve)(h, d_S, d_Pinv, d_gamma, d_lambda, (uint32_t)B, PCG_MAX_ITER, (T)1e-7, MPCG_PRECOND_SS, d_iters, d_exit, s));
             MPCG_OK_OR_DIE(h, LS(mpcg_compute_dz)(h, m, d_G, d_C, d_g, d_lambda, d_dz, (uint32_t)B, s));
-            MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant, m, dt, d_goals, d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, (uint32_t)B, s));
+            MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, (uint32_t)B, s));
             MPCG_OK_OR_DIE(h, LS(mpcg_line_search_step_rho)(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step, d_rho, d_drho, d_gave_up, (T)1.2, (T)1e-3, (T)10, (T)1e-3,
                                                         (uint32_t)B, s));
         }
         // the plant runs under the PREVIOUS plan for one period, offset by the previous period (include/mpcsim.cuh:288-291, :352)
-        MPCG_OK_OR_DIE(h, LS(mpcg_simulate)(h, plant, m, d_xs, d_xu_old, dt, prev_us, period_us, (T)2e-4f, d_eePos, (uint32_t)B, s));
+        MPCG_OK_OR_DIE(h, LS(mpcg_simulate)(h, plant_sim, m, d_xs, d_xu_old, dt, prev_us, period_us, (T)2e-4f, d_eePos, (uint32_t)B, s));
         gpuErrchk(hipMemcpyAsync(d_xu_old, d_xu, (size_t)B * L * sizeof(T), hipMemcpyDeviceToDevice, s));
         const bool shift = clock.update(period_us);
         MPCG_OK_OR_DIE(h, LS(mpcg_advance_horizon)(h, m, shift ? 1 : 0, d_xu, d_lambda, d_goals, d_xs, d_eePos, d_bplan, d_bgoals, (uint32_t)TS, (uint32_t)TS, 0,
@@ -203,6 +247,7 @@ int main(int argc, char** argv) {
     for (int b = 0; b < B; ++b) ok = ok && offset[b] == shifts;
     printf("{\"batch\": %d, \"knots\": %d, \"updates\": %d, \"iters\": %d, ", B, N, U, K);
     if (flagged) printf("\"integrator\": %u, \"sim_integrator\": %u, ", integ, sim_integ);
+    if (gravity != 0.0 || sim_gravity != 0.0) printf("\"gravity\": %g, \"sim_gravity\": %g, ", gravity, sim_gravity);
     printf("\"expected_shifts\": %d, \"shifts\": [", shifts);
     for (int b = 0; b < B; ++b) printf("%s%d", b ? ", " : "", offset[b]);
     printf("], \"tracking_errors\": [");
@@ -221,6 +266,8 @@ int main(int argc, char** argv) {
                     (void*)d_exit, (void*)d_gave_up})
         gpuErrchk(hipFree(p));
     gpuErrchk(hipStreamDestroy(s));
+    if (plant_sim != plant_ctrl && plant_sim != plant) mpcg_plant_destroy(plant_sim);
+    if (plant_ctrl != plant) mpcg_plant_destroy(plant_ctrl);
     mpcg_plant_destroy(plant);
     mpcg_destroy(h);
     return ok ? 0 : 1;

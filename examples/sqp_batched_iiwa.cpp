@@ -14,9 +14,12 @@
 // mpcg_line_search_step(_rho)_f64 — on the same inputs widened to double; the merits are then printed with 17 digits.  --merit-f32 has no effect there.
 // --integrator 1 sets option "integrator" = 1: the KKT blocks and every merit of the run use semi-implicit Euler (q' = q + dt qd'; both builds, float and double);
 // the JSON line then carries "integrator".  Without the flag the line is what it was.
+// --gravity G clones the plant with the reference's scalar gato_plant::GRAVITY = G (mpcg_plant_clone_gravity, base acceleration {0, 0, G}; 9.81: the arm stands
+// on the ground) and, because the file's controls were made for zero gravity, adds the gravity torques mpcg_inverse_dynamics(q_k, 0, 0) to the iterate's controls
+// once, up front, on the device; the JSON line then carries "gravity".  With G = 0 or without the flag nothing of this runs and the line is what it was.
 // Prints one JSON line; exits 0 only if every trajectory's merit went down.
 //   hipcc --offload-arch=gfx950 -O2 [-DUSE_DOUBLES] -Iinclude examples/sqp_batched_iiwa.cpp -Lmpcgpu_amd -lmpcg_hip
-//   sqp_batched_iiwa [--batch 8] [--knots 32] [--iters 4] [--mu 10] [--rho 1e-3] [--adapt-rho] [--merit-f32] [--integrator {0,1}]
+//   sqp_batched_iiwa [--batch 8] [--knots 32] [--iters 4] [--mu 10] [--rho 1e-3] [--adapt-rho] [--merit-f32] [--integrator {0,1}] [--gravity G]
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -74,8 +77,19 @@ static T* dalloc(size_t count) {
     return p;
 }
 
+// u_k += tau_k for the `count` knots that have a control: knot s is trajectory s / per, knot s % per, of an iterate of L values per trajectory
+__global__ void gather_q(const linsys_t* xu, linsys_t* q, int count, int per, size_t L) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count * m) q[i] = xu[(size_t)(i / m / per) * L + (size_t)(i / m % per) * (n + m) + i % m];
+}
+__global__ void add_to_u(linsys_t* xu, const linsys_t* tau, int count, int per, size_t L) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count * m) xu[(size_t)(i / m / per) * L + (size_t)(i / m % per) * (n + m) + n + i % m] += tau[i];
+}
+
 int main(int argc, char** argv) {
     int B = 8, N = 32, K = 4;
+    double gravity = 0.0;
     linsys_t mu = 10.f, rho = (linsys_t)1e-3;
     bool adapt = false, merit_f32 = false;
     int integrator = -1;                                                      // -1: not given (the handle's default, 0)
@@ -89,10 +103,12 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--mu")) mu = (linsys_t)atof(argv[i + 1]);
         else if (!strcmp(argv[i], "--rho")) rho = (linsys_t)atof(argv[i + 1]);
         else if (!strcmp(argv[i], "--integrator")) integrator = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--gravity")) gravity = atof(argv[i + 1]);
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (B < 1 || N < 2 || N + 1 > ROWS || K < 1) { fprintf(stderr, "need batch >= 1, 2 <= knots < %d, iters >= 1\n", ROWS); return 2; }
     if (integrator < -1 || integrator > 1) { fprintf(stderr, "--integrator takes 0 or 1\n"); return 2; }
+    if (!std::isfinite(gravity)) { fprintf(stderr, "--gravity takes a finite number\n"); return 2; }
     const linsys_t dt = 1.0f / 64, qd_cost = (linsys_t)1e-4, r_cost = (linsys_t)(N == 64 ? 1e-3 : 1e-4);      // include/common/settings.cuh:84-94
     const size_t L = (size_t)(n + m) * N - m;
     const std::vector<float> rows = load_rows(argv[0]);
@@ -120,6 +136,13 @@ int main(int argc, char** argv) {
     if (merit_f32) MPCG_OK_OR_DIE(h, mpcg_set_option(h, "merit_f32", 1));
     if (integrator >= 0) MPCG_OK_OR_DIE(h, mpcg_set_option(h, "integrator", integrator));
     if (mpcg_plant_create_iiwa14(&plant, -1) != MPCG_OK) { fprintf(stderr, "mpcg_plant_create_iiwa14: %s\n", mpcg_last_error(nullptr)); return 1; }
+    if (gravity != 0.0) {                                                     // the plant with gato_plant::GRAVITY = G: a clone, the plain one is not needed any more
+        const double base_accel[3] = {0.0, 0.0, gravity};
+        mpcg_plant* heavy = nullptr;
+        if (mpcg_plant_clone_gravity(&heavy, plant, base_accel) != MPCG_OK) { fprintf(stderr, "mpcg_plant_clone_gravity: %s\n", mpcg_last_error(nullptr)); return 1; }
+        mpcg_plant_destroy(plant);
+        plant = heavy;
+    }
 
     const size_t nn = n * n, mm = m * m, nm = n * m;
     linsys_t* d_xu = dalloc<linsys_t>((size_t)B * L);
@@ -159,6 +182,17 @@ int main(int argc, char** argv) {
     linsys_t steps[8];
     for (int p = 0; p < 8; ++p) steps[p] = -1.0f / (float)(1 << p);          // alpha = -1 / 2^p (include/common/merit.cuh:47)
     const linsys_t zero = 0;
+    if (gravity != 0.0) {                                                     // the file's controls hold the arm without gravity: u_k += ID(q_k, 0, 0), once
+        const int count = B * (N - 1), blocks = (count * m + 255) / 256;
+        linsys_t* d_q = dalloc<linsys_t>((size_t)count * m);
+        linsys_t* d_tau = dalloc<linsys_t>((size_t)count * m);
+        hipLaunchKernelGGL(gather_q, dim3(blocks), dim3(256), 0, st, d_xu, d_q, count, N - 1, L);
+        MPCG_OK_OR_DIE(h, LS(mpcg_inverse_dynamics)(h, plant, d_q, nullptr, nullptr, d_tau, (uint32_t)count, st));
+        hipLaunchKernelGGL(add_to_u, dim3(blocks), dim3(256), 0, st, d_xu, d_tau, count, N - 1, L);
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipFree(d_q));
+        HIP_OK(hipFree(d_tau));
+    }
     // the merit of the start iterate: the reference's compute_merit (include/pcg/sqp.cuh:171-187) — with the initial-state term, like the eight trials
     MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant, m, dt, d_goals, d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, (uint32_t)B, st));
     HIP_OK(hipMemcpyAsync(d_merit_hist, d_merit_ref, B * sizeof(linsys_t), hipMemcpyDeviceToDevice, st));
@@ -184,6 +218,7 @@ int main(int argc, char** argv) {
     for (int b = 0; b < B; ++b) ok = ok && std::isfinite(hist[(size_t)K * B + b]) && hist[(size_t)K * B + b] < hist[b];
     printf("{\"batch\": %d, \"knots\": %d, \"iters\": %d, \"mu\": %g, \"rho\": %g, ", B, N, K, (double)mu, (double)rho);
     if (integrator >= 0) printf("\"integrator\": %d, ", integrator);
+    if (gravity != 0.0) printf("\"gravity\": %g, ", gravity);
     printf("\"merit\": [");
     for (int b = 0; b < B; ++b) {
         printf("%s[", b ? ", " : "");

@@ -342,7 +342,23 @@ int mpcg_block_solve_f64(mpcg_handle *h, const double *d_S, const double *d_gamm
  * stored as before (C = -A, -B, column-major); costs, layouts and the last-block quirk are unchanged.  The option is read when the call is made (a captured
  * graph keeps what it was captured with), takes 0 or 1 (anything else: MPCG_ERR_INVALID, the value stays) and is orthogonal to "kkt_analytic" and "kkt_f32":
  * every build has its semi-implicit instantiation (a compile-time parameter of the kernel: no run-time branch, the explicit instantiations are unchanged),
- * and mpcg_generate_kkt_f64 honours it too.  mpcg_compute_merit(_f64) reads the SAME option: a line search must measure the map this call linearised. */
+ * and mpcg_generate_kkt_f64 honours it too.  mpcg_compute_merit(_f64) reads the SAME option: a line search must measure the map this call linearised.
+ * GRAVITY.  The reference hands gato_plant::GRAVITY<T>() (include/dynamics/iiwa/iiwa_eepos_plant.cuh:51) to every GRiD call, and GRiD uses it as the
+ * acceleration the chain's root starts from: a_1 = X_1[:, 5] * gravity, a base spatial acceleration [0 0 0 0 0 g].  Here that is model data of the plant:
+ * base_accel, the LINEAR spatial acceleration of the root in the base frame, three numbers.  GRiD's scalar g is base_accel = {0, 0, g}.  SIGN: it is the
+ * acceleration the base is given, so the physical gravitational acceleration is its NEGATIVE — {0, 0, +9.81} models an arm standing on the ground with z
+ * up (gravity pulls along -z).  mpcg_plant_create and mpcg_plant_create_iiwa14 make plants with {0, 0, 0}: the reference's constant is 0 because its iiwa
+ * is gravity-compensated, and every output of such a plant is bit for bit what it was before the vector existed.  mpcg_plant_clone_gravity makes the plant
+ * with another vector.  mpcg_generate_kkt(_f64), mpcg_compute_merit(_f64), mpcg_simulate(_f64) and mpcg_inverse_dynamics(_f64) all read the vector from the
+ * plant THEY ARE GIVEN (every build: both gradient routes, "kkt_f32", "merit_f32", both integrators), so the controller's model and the simulated plant may
+ * differ in it, as they may in "sim_integrator".  It enters the bias ID(q, qd, 0) — hence qdd = Minv (u - bias), A, B, the defects, the merit's violation
+ * terms and the simulated state — and nothing else: the inertia matrix and the end-effector pose do not depend on it.
+ *   mpcg_plant_clone_gravity   *out = a NEW plant, the tables of src with base_accel; src is not touched.  A clone and not a setter: kernels read the model
+ *                              as invariant data and captured graphs keep the pointer, so a plant never changes after creation.  The clone owns its own
+ *                              device allocation (on src's device); source and clone may be destroyed in either order.  It allocates and copies
+ *                              (hipMalloc, blocking hipMemcpy), as mpcg_plant_create does: neither is stream work, neither may be called while a stream
+ *                              of the calling thread is being captured.  MPCG_ERR_INVALID: a NULL argument or a non-finite component (*out = NULL).
+ *   mpcg_plant_get_gravity     the plant's vector ({0, 0, 0} for mpcg_plant_create / _create_iiwa14); MPCG_ERR_INVALID: a NULL argument. */
 typedef struct mpcg_plant mpcg_plant;
 int mpcg_plant_create(mpcg_plant **out, int device, uint32_t num_joints, const double *X_const, const double *I_spatial,
                       const double *Xhom_const, const int32_t *X_trig_idx, const double *X_trig_coef, const int32_t *X_trig_j,
@@ -351,7 +367,21 @@ int mpcg_plant_create(mpcg_plant **out, int device, uint32_t num_joints, const d
 /* The KUKA LBR iiwa 14 of the reference from the tables built into the library (the same numbers as mpcgpu_amd/data/iiwa14_model.json):
  * replaces gato_plant::initializeDynamicsConstMem<T>() (include/dynamics/iiwa/iiwa_eepos_plant.cuh:63-66, called at include/mpcsim.cuh:194). */
 int mpcg_plant_create_iiwa14(mpcg_plant **out, int device);
+int mpcg_plant_clone_gravity(mpcg_plant **out, const mpcg_plant *src, const double base_accel[3]);
+int mpcg_plant_get_gravity(const mpcg_plant *p, double out[3]);
 int mpcg_plant_destroy(mpcg_plant *p);
+/* mpcg_inverse_dynamics: d_tau[i] = ID(q_i, qd_i, qdd_i) of the plant, ITS GRAVITY INCLUDED, for count independent states (arrays [count][7]; d_qd and
+ * d_qdd may each be NULL: zero).  With both NULL it returns the gravity torques — what the controls of a plan made for zero gravity must gain before a
+ * loop over a gravity clone starts from it (u' = u + ID(q, 0, 0) keeps qdd, hence the plan a solution).  Float64 inside like the other plant kernels, the
+ * sweep their bias lane runs (csrc/invdyn_plant.hip.h); the float entry rounds once on store, the _f64 entry reads and stores doubles.  Pure stream work
+ * from the first call on (capturable); a state's result does not depend on the rest of the call.
+ *   MPCG_ERR_INVALID       a NULL handle, plant, d_q or d_tau; count > max_batch x knot_points of the handle; a plant on another device
+ *   MPCG_ERR_UNSUPPORTED   a handle whose state_size is not 14
+ *   count == 0             MPCG_OK, nothing launched */
+int mpcg_inverse_dynamics(mpcg_handle *h, const mpcg_plant *plant, const float *d_q, const float *d_qd /* NULL: 0 */,
+                          const float *d_qdd /* NULL: 0 */, float *d_tau, uint32_t count, void *stream);
+int mpcg_inverse_dynamics_f64(mpcg_handle *h, const mpcg_plant *plant, const double *d_q, const double *d_qd /* NULL: 0 */,
+                              const double *d_qdd /* NULL: 0 */, double *d_tau, uint32_t count, void *stream);
 int mpcg_generate_kkt(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size, float timestep, const float *d_eePos_traj,
                       const float *d_xs, const float *d_xu, float qd_cost, float r_cost, float *d_G_dense, float *d_C_dense,
                       float *d_g, float *d_c, uint32_t batch, void *stream);
@@ -373,7 +403,7 @@ int mpcg_generate_kkt_f64(mpcg_handle *h, const mpcg_plant *plant, uint32_t cont
  *   d_merit[b][a] = sum_{k<N} J_k + mu ( sum_{k<N-1} | x_{k+1} - (x_k + dt [qd_k ; qdd_k]) |_1  +  [d_xs given] | x_0 - xs_b |_1 )
  *   J_k = 1/2 |ee(q_k) - goal_k[0:3]|^2 + 1/2 qd_cost |qd_k|^2 + [k < N-1] 1/2 r_cost |u_k|^2
  * with the plant functions the reference calls (gato_plant::trackingcost, include/dynamics/iiwa/iiwa_eepos_plant.cuh:242-290; integratorError
- * with the Euler integrator, include/common/integrator.cuh; forward dynamics of the mpcg_plant without gravity, as mpcg_generate_kkt).  The last
+ * with the Euler integrator, include/common/integrator.cuh; forward dynamics of the mpcg_plant given, with that plant's gravity — GRAVITY under mpcg_plant_create —, as mpcg_generate_kkt).  The last
  * knot's cost is evaluated at its own state x_{N-1} against goal_{N-1} (merit.cuh:62) — not at x_{N-2} as the KKT stage's _lastblock does.
  * The initial-state term is what ls_gato_compute_merit adds in its last block (merit.cuh:68-77); the reference's compute_merit, which gives
  * the merit the line search compares against, leaves it out (:133-135): d_xs = NULL reproduces that.  Pass the same d_xs for both and all
@@ -479,7 +509,7 @@ int mpcg_line_search_step_rho_f64(mpcg_handle *h, uint32_t control_size, const d
  *   S = (uint32)(sim / ss) full substeps of dt = ss; substep s applies u of knot idx_s = (uint32)((toff + s * ss) / timestep);
  *   then one remainder substep of dt = (float)fmod(sim, ss) with the control of the LAST full substep (the reference does not recompute the index
  *   there, :322-324), or of (uint32)(toff / timestep) if S = 0.  A remainder of exactly 0 is not run: sim_time_us = 0 leaves d_xs bitwise unchanged.
- * A substep is explicit Euler from the old values, q += dt qd, qd += dt qdd, qdd = forward dynamics of the mpcg_plant without gravity in float64
+ * A substep is explicit Euler from the old values, q += dt qd, qd += dt qdd, qdd = forward dynamics of the mpcg_plant given (its own gravity vector: GRAVITY under mpcg_plant_create) in float64
  * (the arithmetic of mpcg_generate_kkt's integrator defect).  Substeps are gated on their number, never on time accumulated in float.
  * Option "sim_integrator" = 1 (default 0; 0 or 1, anything else MPCG_ERR_INVALID; read when the call is made) makes every substep SEMI-IMPLICIT Euler,
  * qd' = qd + dt qdd, q' = q + dt qd' (integrator.cuh:103-130, INTEGRATOR_TYPE == 1), for mpcg_simulate and mpcg_simulate_f64; the schedule, the clamp and

@@ -69,6 +69,7 @@ constexpr int RN_AW = 3, RN_AU = 9;      // rows (3 each) where a lane leaves th
 template <typename R> struct PlantDevT {
     R ET[PJ][9], BT[PJ][9];
     R Ib[PJ][10];                                // Ixx Ixy Ixz Iyy Iyz Izz  hx hy hz  m
+    R grav[3];                                   // linear spatial acceleration the root starts from, base frame (GRiD's scalar `gravity` g: {0, 0, g}); behind Ib: no offset above moves
 };
 typedef PlantDevT<double> PlantDev;              // R = double: the round-2..5 kernel (float64 inside, the checker of the float build); R = float (round 6): linsys_t's own
                                                  // arithmetic, what the reference's GRiD code runs in (gato_plant::forwardDynamicsAndGradient<T>, T = linsys_t = float)
@@ -108,6 +109,7 @@ template <typename R> struct PlantC {
     __device__ __forceinline__ creal* ET(int k) const { return at(offsetof(PlantDevT<R>, ET), k, 9); }
     __device__ __forceinline__ creal* BT(int k) const { return at(offsetof(PlantDevT<R>, BT), k, 9); }
     __device__ __forceinline__ creal* Ib(int k) const { return at(offsetof(PlantDevT<R>, Ib), k, 10); }
+    __device__ __forceinline__ creal* grav() const { return at(offsetof(PlantDevT<R>, grav), 0, 0); }
 };
 
 // ---- arithmetic types of the kernel: double (default), float ("kkt_f32" = 1 below a full batch), and kkt_f2 = TWO knots per lane in packed float
@@ -185,7 +187,11 @@ template <typename R> struct RneaTask {                        // what this lane
     int base;                            // unit angular base acceleration e_base (-1: none)
 };
 
-// tau = ID(q, qd, qdd) without gravity (gato_plant::GRAVITY = 0, iiwa_eepos_plant.cuh:53).  The link forces that wait for the backward
+// tau = ID(q, qd, qdd).  Gravity is the plant's (PlantDevT::grav, gato_plant::GRAVITY of iiwa_eepos_plant.cuh:51; {0, 0, 0} unless the plant is a
+// mpcg_plant_clone_gravity): the linear acceleration au of the root starts at t.qdscale x grav — GRiD's a_1 = X_1[:, 5] * gravity — so it enters exactly
+// the sweeps that carry the knot's velocity (the bias lane ID(q, qd, 0) and the difference tasks ID(q + h e, qd + h e, qdd), qdscale = 1) and not the
+// inertia-matrix columns ID(q, 0, e_j) or the pose sweeps (qdscale = 0).  Three scalar loads; 1 x 0 = 0 leaves every bit of a plain plant's sweep.
+// The link forces that wait for the backward
 // sweep live in this lane's record `fl` (rows RN_*), and both sweeps are RUNTIME loops over the joints.  Measured alternatives on
 // gfx950 (hipcc 7.2): everything in registers with unrolled sweeps = 3.4 KB of scratch per lane (the 84 force registers, plus the
 // transforms the compiler keeps from the forward sweep for the backward one, plus 840 hoisted table loads); plain (non-volatile)
@@ -198,7 +204,7 @@ __device__ __forceinline__ void rnea(const PlantC<typename KktR<R>::scalar>& P, 
     typedef typename PlantC<typename KktR<R>::scalar>::creal creal;
     R vw[3], vu[3], aw[3], au[3], f[6];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) { vw[r] = KR(0.0); vu[r] = KR(0.0); aw[r] = KR(0.0); au[r] = KR(0.0); f[r] = KR(0.0); f[3 + r] = KR(0.0); }
+    for (int r = 0; r < 3; ++r) { vw[r] = KR(0.0); vu[r] = KR(0.0); aw[r] = KR(0.0); au[r] = t.qdscale * KktR<R>::mk(P.grav()[r], P.grav()[r]); f[r] = KR(0.0); f[3 + r] = KR(0.0); }
     if (t.base >= 0) aw[t.base] = KR(1.0);
 #pragma nounroll
     for (int kv = 0; kv < PJ; ++kv) {
@@ -330,7 +336,8 @@ __device__ __forceinline__ void rnea_grad(const PlantC<typename KktR<R>::scalar>
     const int first = nom ? 0 : col;
     R vw[3], vu[3], aw[3], au[3], f[6];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) { vw[r] = KR(0.0); vu[r] = KR(0.0); aw[r] = KR(0.0); au[r] = KR(0.0); f[r] = KR(0.0); f[3 + r] = KR(0.0); }
+    // gravity (PlantDevT::grav): the nominal lane's root acceleration; a column lane starts from zero and receives X_k a_{k-1} from it by DPP as before
+    for (int r = 0; r < 3; ++r) { vw[r] = KR(0.0); vu[r] = KR(0.0); aw[r] = KR(0.0); au[r] = nom ? KktR<R>::mk(P.grav()[r], P.grav()[r]) : KR(0.0); f[r] = KR(0.0); f[3 + r] = KR(0.0); }
 #pragma nounroll
     for (int kv = 0; kv < PJ; ++kv) {
         const int k = __builtin_amdgcn_readfirstlane(kv);

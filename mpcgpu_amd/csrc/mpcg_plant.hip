@@ -1,6 +1,7 @@
 // mpcg_plant.hip — C ABI (include/mpcg.h) of the producer of the path's inputs: the robot as data (mpcg_plant) and the KKT block assembly
 // mpcg_generate_kkt(_f64) over the gfx950 kernel in kkt_plant.hip.h; the stage behind dz — mpcg_compute_merit(_f64) and
-// mpcg_line_search_step(_rho)(_f64) over merit_plant.hip.h (the merit in packed float, "merit_f32": merit_plant_f32.hip.h); the step between two SQP solves — mpcg_simulate(_f64) and mpcg_advance_horizon(_f64) over sim_plant.hip.h.
+// mpcg_line_search_step(_rho)(_f64) over merit_plant.hip.h (the merit in packed float, "merit_f32": merit_plant_f32.hip.h); the step between two SQP solves — mpcg_simulate(_f64) and mpcg_advance_horizon(_f64) over sim_plant.hip.h;
+// the plant's gravity (mpcg_plant_clone_gravity) and mpcg_inverse_dynamics(_f64) over invdyn_plant.hip.h.
 #include <cmath>
 #include <type_traits>
 #include "mpcg_handle.hpp"
@@ -8,13 +9,17 @@
 #include "merit_plant.hip.h"
 #include "merit_plant_f32.hip.h"
 #include "sim_plant.hip.h"
+#include "invdyn_plant.hip.h"
 
 using namespace mpcg;
 
 extern "C" {
 
 // ---- the producer of the path's inputs: KKT block assembly with the robot as data (kkt_plant.hip.h) ----
-struct mpcg_plant { int device = 0; PlantDev* d = nullptr; PlantDevT<float>* d32 = nullptr; };      // (d32: the same tables rounded to float, behind d in ONE allocation)
+struct mpcg_plant {
+    int device = 0; PlantDev* d = nullptr; PlantDevT<float>* d32 = nullptr;      // (d32: the same tables rounded to float, behind d in ONE allocation)
+    PlantDev host; PlantDevT<float> host32;                                      // what the device holds: mpcg_plant_clone_gravity copies these, mpcg_plant_get_gravity reads host.grav
+};
 
 int mpcg_plant_create(mpcg_plant** out, int device, uint32_t num_joints, const double* X_const, const double* I_spatial, const double* Xhom_const,
                       const int32_t* X_trig_idx, const double* X_trig_coef, const int32_t* X_trig_j, uint32_t n_X_trig,
@@ -175,6 +180,7 @@ int mpcg_plant_create(mpcg_plant** out, int device, uint32_t num_joints, const d
         return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_create: cannot place the model on the device");
     }
     pl->d32 = reinterpret_cast<PlantDevT<float>*>(pl->d + 1);
+    pl->host = *hp; pl->host32 = *hp32;                     // (grav = {0, 0, 0}: hp was zero-filled, hp32 value-initialised)
     delete hp; delete hp32;
     *out = pl;
     return MPCG_OK;
@@ -187,6 +193,43 @@ int mpcg_plant_create_iiwa14(mpcg_plant** out, int device) {
     return mpcg_plant_create(out, device, 7, kIiwa14_X_const, kIiwa14_I, kIiwa14_Xhom_const, kIiwa14_X_trig_idx, kIiwa14_X_trig_coef, kIiwa14_X_trig_j,
                              (uint32_t)(sizeof(kIiwa14_X_trig_idx) / sizeof(int32_t)), kIiwa14_Xhom_trig_idx, kIiwa14_Xhom_trig_coef, kIiwa14_Xhom_trig_j,
                              (uint32_t)(sizeof(kIiwa14_Xhom_trig_idx) / sizeof(int32_t)));
+}
+
+// The plant with another root acceleration (PlantDevT::grav): a NEW plant with its own device allocation, because kernels read the model through the
+// constant address space as invariant data and captured graphs keep the pointer — a plant never changes after creation.
+int mpcg_plant_clone_gravity(mpcg_plant** out, const mpcg_plant* src, const double base_accel[3]) {
+    if (!out) return MPCG_ERR_INVALID;
+    *out = nullptr;
+    if (!src || !base_accel) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_gravity: null argument");
+    if (!std::isfinite(base_accel[0]) || !std::isfinite(base_accel[1]) || !std::isfinite(base_accel[2]))
+        return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_gravity: base_accel must be finite");
+    mpcg_plant* pl = new (std::nothrow) mpcg_plant();
+    if (!pl) return MPCG_ERR_NOMEM;
+    pl->device = src->device;
+    pl->host = src->host; pl->host32 = src->host32;
+    for (int r = 0; r < 3; ++r) {
+        pl->host.grav[r] = base_accel[r] + 0.0;             // (-0 becomes +0: a zero vector is the plain plant's, whatever its sign bits)
+        pl->host32.grav[r] = (float)pl->host.grav[r];
+    }
+    if (hipSetDevice(pl->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&pl->d), sizeof(PlantDev) + sizeof(PlantDevT<float>)) != hipSuccess) {
+        delete pl;
+        return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_clone_gravity: cannot place the model on the device");
+    }
+    if (hipMemcpy(pl->d, &pl->host, sizeof(PlantDev), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(pl->d + 1, &pl->host32, sizeof(PlantDevT<float>), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(pl->d);
+        delete pl;
+        return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_clone_gravity: cannot place the model on the device");
+    }
+    pl->d32 = reinterpret_cast<PlantDevT<float>*>(pl->d + 1);
+    *out = pl;
+    return MPCG_OK;
+}
+
+int mpcg_plant_get_gravity(const mpcg_plant* p, double out[3]) {
+    if (!p || !out) return MPCG_ERR_INVALID;
+    for (int r = 0; r < 3; ++r) out[r] = p->host.grav[r];
+    return MPCG_OK;
 }
 
 int mpcg_plant_destroy(mpcg_plant* p) {
@@ -474,6 +517,34 @@ int mpcg_simulate(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size
 int mpcg_simulate_f64(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, double* d_xs, const double* d_xu, double timestep, double time_offset_us,
                       double sim_time_us, double sim_step, double* d_eePos, uint32_t batch, void* stream) {
     return simulate_impl<double>(h, "mpcg_simulate_f64", plant, control_size, d_xs, d_xu, timestep, time_offset_us, sim_time_us, sim_step, d_eePos, batch, stream);
+}
+
+// ---- batched inverse dynamics (invdyn_plant.hip.h): mpcg_inverse_dynamics (T = float) and mpcg_inverse_dynamics_f64 (T = double), one host path ----
+extern "C++" {
+template <typename T>
+static int inverse_dynamics_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, const T* d_q, const T* d_qd, const T* d_qdd, T* d_tau, uint32_t count, void* stream) {
+    if (!h || !plant) return MPCG_ERR_INVALID;
+    if (!d_q || !d_tau) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    if (h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 (IIWA-14) only");
+    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
+    if (count == 0) return MPCG_OK;
+    if ((uint64_t)count > (uint64_t)h->max_batch * h->N) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": count exceeds max_batch x knot_points");
+    HIP_TRY(h, hipSetDevice(h->device));
+    InvDynArgsT<T> a;
+    a.plant = plant->d; a.q = d_q; a.qd = d_qd; a.qdd = d_qdd; a.tau = d_tau; a.count = count;
+    hipLaunchKernelGGL(inverse_dynamics_kernel<T>, dim3((count + KKT_ITEMS - 1) / KKT_ITEMS), dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
+}  // extern "C++"
+
+int mpcg_inverse_dynamics(mpcg_handle* h, const mpcg_plant* plant, const float* d_q, const float* d_qd, const float* d_qdd, float* d_tau, uint32_t count, void* stream) {
+    return inverse_dynamics_impl<float>(h, "mpcg_inverse_dynamics", plant, d_q, d_qd, d_qdd, d_tau, count, stream);
+}
+
+int mpcg_inverse_dynamics_f64(mpcg_handle* h, const mpcg_plant* plant, const double* d_q, const double* d_qd, const double* d_qdd, double* d_tau, uint32_t count,
+                              void* stream) {
+    return inverse_dynamics_impl<double>(h, "mpcg_inverse_dynamics_f64", plant, d_q, d_qd, d_qdd, d_tau, count, stream);
 }
 
 int mpcg_advance_horizon(mpcg_handle* h, uint32_t control_size, uint32_t shift, float* d_xu, float* d_lambda, float* d_eePos_goal, const float* d_xs,

@@ -5,7 +5,7 @@
 //
 // simulate_kernel<INTEGRATOR>.  A substep is the explicit Euler step of the KKT kernel's integrator, q += dt qd, qd += dt qdd (both from the old values;
 // INTEGRATOR = 1, option "sim_integrator": semi-implicit Euler, qd' = qd + dt qdd, q' = q + dt qd' — a compile-time parameter, `if constexpr` in sim_steps.inc), qdd =
-// Minv (u - bias) without gravity, so the mapping is merit_points_kernel's: a 16-lane group per trajectory, four trajectories per wavefront; lanes
+// Minv (u - bias) (the bias with the gravity vector of the plant given: rnea, kkt_plant.hip.h), so the mapping is merit_points_kernel's: a 16-lane group per trajectory, four trajectories per wavefront; lanes
 // 0..6 the inertia-matrix columns and lane 7 the bias through rnea<double>, then lanes 0..6 the Cholesky solve (plant_qdd_lane: the merit kernel's
 // arithmetic).  The substeps are a loop INSIDE the kernel: q, qd and sin / cos wait in the item record in LDS between them.  The schedule is the reference's,
 // evaluated in IEEE double with one rounding per operation (no contraction: __dmul_rn / __dadd_rn / __ddiv_rn):

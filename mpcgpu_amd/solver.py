@@ -42,12 +42,16 @@ def _stream():
 
 class Plant:
     """Device-side robot model for mpcg_generate_kkt: the reference's d_dynMem_const (GRiD robotModel,
-    gato_plant::initializeDynamicsConstMem, include/dynamics/iiwa/iiwa_eepos_plant.cuh:63-66) as data."""
+    gato_plant::initializeDynamicsConstMem, include/dynamics/iiwa/iiwa_eepos_plant.cuh:63-66) as data.
+    `gravity` = (gx, gy, gz): the linear acceleration the chain's root starts from, in the base frame (include/mpcg.h, GRAVITY: GRiD's scalar g is
+    (0, 0, g); the physical gravitational acceleration is its negative).  None: (0, 0, 0), the reference's gravity-compensated iiwa.  A plant never
+    changes: `with_gravity` returns a new one (mpcg_plant_clone_gravity)."""
 
-    def __init__(self, model=None, device: int | None = None):
+    def __init__(self, model=None, device: int | None = None, gravity=None):
         import numpy as np
         from . import iiwa
         self.lib = _lib.load()
+        self._p = None
         self.model = model or iiwa.Model()
         m = self.model
         dev = torch.cuda.current_device() if device is None else int(device)
@@ -61,6 +65,34 @@ class Plant:
         if rc != _lib.MPCG_OK:
             raise _lib.MpcgError(rc, self.lib.mpcg_last_error(None).decode())
         self._p = h
+        if gravity is not None:
+            plain, self._p = self._p, self._clone(h, gravity)
+            self.lib.mpcg_plant_destroy(plain)
+
+    def _clone(self, src, gravity):
+        g = [float(v) for v in gravity]
+        if len(g) != 3:
+            raise ValueError("gravity: three components (gx, gy, gz)")
+        h = C.c_void_p()
+        rc = self.lib.mpcg_plant_clone_gravity(C.byref(h), src, (C.c_double * 3)(*g))
+        if rc != _lib.MPCG_OK:
+            raise _lib.MpcgError(rc, self.lib.mpcg_last_error(None).decode())
+        return h
+
+    def with_gravity(self, gravity) -> "Plant":
+        """A new Plant: this one's tables with `gravity` (mpcg_plant_clone_gravity); this one is not touched, either may be closed first."""
+        new = object.__new__(Plant)
+        new.lib, new.model, new._p = self.lib, self.model, None
+        new._p = self._clone(self._p, gravity)
+        return new
+
+    @property
+    def gravity(self):
+        out = (C.c_double * 3)()
+        rc = self.lib.mpcg_plant_get_gravity(self._p, out)
+        if rc != _lib.MPCG_OK:
+            raise _lib.MpcgError(rc, "mpcg_plant_get_gravity")
+        return tuple(out)
 
     def close(self):
         if getattr(self, "_p", None):
@@ -454,6 +486,25 @@ class PcgSolver:
         self._check(fn(self._h, plant._p, m, _ptr(xs), _ptr(xu), float(timestep), float(time_offset_us), float(sim_time_us),
                        float(sim_step), _ptr(eePos), B, _stream()))
         return xs
+
+    def inverse_dynamics(self, plant: "Plant", q, qd=None, qdd=None, tau=None):
+        """tau = ID(q, qd, qdd) of the plant, its gravity included, for q [count, 7] (qd, qdd: None = 0; both None: the gravity torques), in the dtype
+        of q.  float32 tensors: mpcg_inverse_dynamics (float64 inside, rounded once); float64 tensors: mpcg_inverse_dynamics_f64.  count is at most
+        max_batch x knot_points.  Mixed dtypes raise TypeError."""
+        dt = self._one_dtype("inverse_dynamics", q, qd, qdd, tau)
+        if q.numel() % 7:
+            raise ValueError("inverse_dynamics: q must hold [count, 7] values")
+        count = q.numel() // 7
+        self._chk(q, count * 7, dt, "q")
+        for t, name in ((qd, "qd"), (qdd, "qdd")):
+            if t is not None:
+                self._chk(t, count * 7, dt, name)
+        if tau is None:
+            tau = torch.empty(count, 7, device=q.device, dtype=dt)
+        self._chk(tau, count * 7, dt, "tau")
+        fn = self.lib.mpcg_inverse_dynamics if dt == torch.float32 else self.lib.mpcg_inverse_dynamics_f64
+        self._check(fn(self._h, plant._p, _ptr(q), _ptr(qd), _ptr(qdd), _ptr(tau), count, _stream()))
+        return tau
 
     def advance_horizon(self, shift: bool, xu, xs, lam=None, eePos_goal=None, eePos=None, xu_traj=None, eePos_traj=None, traj_offset=None,
                         done=None, tracking_error=None, xu_fill_lead: int = 0, control_size: int | None = None):
