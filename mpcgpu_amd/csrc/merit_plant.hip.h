@@ -22,9 +22,9 @@
 // joint's share of the point merit and lane 0 adds them in lane order; the point merits wait as doubles in a handle-owned scratch [batch][16][N], and
 // merit_sum_kernel adds a row knot by knot and rounds ONCE to float.  An item's arithmetic depends on nothing but its own (trajectory, step size,
 // knot): results are bitwise reproducible and independent of the rest of the batch and of the other step sizes of the call.
-// The double twins (mpcg_compute_merit_f64, mpcg_line_search_step(_rho)_f64; linsys_t = double): merit_points_f64_kernel over the SAME body text
-// (merit_points.inc, included by both kernels) with double loads and the trial iterate fma(alpha, dz, xu) in double; merit_sum_f64_kernel stores the double
-// sum itself; line_search_step_kernel over StepArgsF64 / StepRhoArgsF64.
+// The double twins (mpcg_compute_merit_f64, mpcg_line_search_step(_rho)_f64; linsys_t = double) are the same templates: merit_points_kernel<double, INTEGRATOR>
+// with double loads and the trial iterate fma(alpha, dz, xu) in double; merit_sum_kernel<double> stores the double sum itself; line_search_step_kernel over
+// StepArgsT<double> / StepRhoArgsT<double>.
 // LDS per wavefront: the KKT kernel's item records (4 x 840 B) + 11 recursion records per item (4 x 3,256 B) = 16,384 B — its budget exactly.
 #pragma once
 #include <type_traits>
@@ -47,45 +47,168 @@ __device__ __forceinline__ double step_max(double a, double b) { return fmax(a, 
 __device__ __forceinline__ float step_min(float a, float b) { return fminf(a, b); }
 __device__ __forceinline__ double step_min(double a, double b) { return fmin(a, b); }
 
-struct MeritArgs {
-    const PlantDev* plant;
-    const float* eePos_traj;             // [batch][N][6]
-    const float* xs;                     // [batch][n] or NULL: no initial-state term (the reference's compute_merit, merit.cuh:133-135)
-    const float* xu;                     // [batch][(n+m)N - m]
-    const float* dz;                     // same shape; NULL allowed when every step size is 0
+// IO: the type of the arrays and of the step sizes; S: the type of the model tables and of the scalars (float: merit_points_f32_kernel, merit_plant_f32.hip.h).
+// IO = double (mpcg_compute_merit_f64, linsys_t = double): the trial iterate is fma(alpha, dz, xu) in DOUBLE with one rounding — the double
+// line_search_step_kernel stores; float64 inside only: "merit_f32" does not apply to that entry.
+template <typename IO, typename S = double> struct MeritArgsT {
+    const PlantDevT<S>* plant;
+    const IO* eePos_traj;                // [batch][N][6]
+    const IO* xs;                        // [batch][n] or NULL: no initial-state term (the reference's compute_merit, merit.cuh:133-135)
+    const IO* xu;                        // [batch][(n+m)N - m]
+    const IO* dz;                        // same shape; NULL allowed when every step size is 0
     double* point;                       // [batch][MERIT_MAX_STEPS][N] point merits
     int N, batch, A;
-    double dt, mu, qd_cost, r_cost;
-    float alpha[MERIT_MAX_STEPS];
-};
-// mpcg_compute_merit_f64 (linsys_t = double): the same fields with every array in double.  The trial iterate is fma(alpha, dz, xu) in DOUBLE with one
-// rounding — the double line_search_step_kernel stores; float64 inside only: "merit_f32" does not apply to this entry.
-struct MeritArgsF64 {
-    const PlantDev* plant;
-    const double* eePos_traj;
-    const double* xs;
-    const double* xu;
-    const double* dz;
-    double* point;
-    int N, batch, A;
-    double dt, mu, qd_cost, r_cost;
-    double alpha[MERIT_MAX_STEPS];
+    S dt, mu, qd_cost, r_cost;
+    IO alpha[MERIT_MAX_STEPS];
 };
 
-template <int INTEGRATOR = 0>
-__global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(MeritArgs a) {
-    typedef float IO;
-#include "merit_points.inc"
-}
-template <int INTEGRATOR = 0>
-__global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f64_kernel(MeritArgsF64 a) {
-    typedef double IO;
-#include "merit_points.inc"
+// IO = float: mpcg_compute_merit; IO = double: mpcg_compute_merit_f64.  Only the loads and the trial iterate depend on IO; INTEGRATOR: 0 explicit, 1 semi-implicit
+// Euler.  (A shared __device__ body was tried and changed the float kernel's code.)
+template <typename IO, int INTEGRATOR = 0>
+__global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(MeritArgsT<IO> a) {
+    typedef double R;
+    typedef KktLds<R>::vr kkt_lds_vd;
+    typedef KktLds<R>::item kkt_lds_item;
+    typedef PlantC<R>::creal creal;
+    constexpr int n = 2 * PJ, m = PJ;
+    __shared__ KktItemLds<R> sI[KKT_ITEMS];
+    __shared__ R sF[KKT_ITEMS][KKT_R0 * RN_ROWS];
+    static_assert(sizeof(KktItemLds<R>) * KKT_ITEMS + sizeof(R) * KKT_ITEMS * KKT_R0 * RN_ROWS <= 16384, "the KKT kernel's LDS budget: ten wavefronts per CU");
+    const int lane = threadIdx.x, gi = lane / KKT_GL, l = lane - gi * KKT_GL;
+    kkt_lds_item* I = (kkt_lds_item*)&sI[gi];
+    kkt_lds_vd* recs = (kkt_lds_vd*)&sF[gi][0];
+    auto rec = [&](int j) -> kkt_lds_vd* { return recs + j * RN_ROWS; };
+    kkt_lds_vd* fl = rec(l < KKT_R0 ? l : 0);
+    const PlantC<R> P{reinterpret_cast<creal*>(reinterpret_cast<unsigned long long>(a.plant))};
+    const int N = a.N;
+    const long per_traj = (long)a.A * N, total = (long)a.batch * per_traj;
+    const size_t xu_len = (size_t)(n + m) * N - m;
+    // consecutive items per wavefront, as the KKT kernel: the four point merits of a trip are neighbours in the scratch
+    const long groups = (total + KKT_ITEMS - 1) / KKT_ITEMS, per = (groups + gridDim.x - 1) / gridDim.x;
+    const long g_begin = (long)blockIdx.x * per, g_end = g_begin + per < groups ? g_begin + per : groups;
+    for (long grp = g_begin; grp < g_end; ++grp) {
+        const long item0 = grp * KKT_ITEMS + gi;
+        const bool live = item0 < total;                     // (a group without an item recomputes the last one and writes nothing)
+        const long item = live ? item0 : total - 1;
+        const int b = (int)(item / per_traj);
+        const int rem = (int)(item - (long)b * per_traj);
+        const int ai = rem / N, k = rem - ai * N;
+        const bool dyn = k < N - 1;                          // the last knot has no control and no successor: cost only
+        IO alpha = 0;
+#pragma unroll
+        for (int i = 0; i < MERIT_MAX_STEPS; ++i) alpha = i == ai ? a.alpha[i] : alpha;
+        const bool moved = alpha != 0;
+        const IO* xu = a.xu + (size_t)b * xu_len;
+        const IO* dz = moved ? a.dz + (size_t)b * xu_len : nullptr;
+        auto trial = [&](size_t e) -> double {               // one rounding in the arrays' type (float: then widened)
+            IO x = xu[e];
+            if (moved) x = step_fma(alpha, dz[e], x);
+            return (double)x;
+        };
+        const size_t xk = (size_t)k * (n + m);
+        double ul = 0.0, xn_q = 0.0, xn_qd = 0.0;
+        if (l < n) I->Xq[l] = trial(xk + l);
+        if (l < m) {
+            if (dyn) { ul = trial(xk + n + l); xn_q = trial(xk + (n + m) + l); xn_qd = trial(xk + (n + m) + PJ + l); }
+            I->U[l] = ul;
+            double sn, cs;
+            kkt_sincos(trial(xk + l), sn, cs);
+            I->Sc[0][l] = sn;
+            I->Sc[1][l] = cs;
+        }
+        __syncthreads();
+        // ---- round 0 of the KKT kernel: lanes 0..6 ID(q, 0, e_l), lane 7 ID(q, qd, 0), lanes 8..10 the pose sweeps (the last knot: those only) ----
+        if (l < KKT_R0 && (dyn || l > PJ)) {
+            R a6w[3], a6u[3];
+            RneaTask<R> t;
+            t.sj = -1; t.pj = -1; t.qdscale = (l == PJ) ? 1.0 : 0.0; t.knot_qdd = false; t.unit = l < PJ ? l : -1; t.base = l > PJ ? l - PJ - 1 : -1;
+            rnea<R>(P, fl, I, t, a6w, a6u);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) { fl[RN_AW + r] = a6w[r]; fl[RN_AU + r] = a6u[r]; }
+        }
+        __syncthreads();
+        // ---- lanes 0..6: qdd_l = Minv_l . (u - bias) through the Cholesky solve of the symmetrised M (as the KKT kernel), then joint l's share of the point merit ----
+        if (l < PJ) {
+            R qdd = 0.0;
+            if (dyn) {
+                R Lm[PJ][PJ], rd[PJ];
+#pragma unroll
+                for (int i = 0; i < PJ; ++i)
+#pragma unroll
+                    for (int jj = 0; jj <= i; ++jj) {
+                        R sv = 0.5 * (rec(jj)[RN_TAU(i)] + rec(i)[RN_TAU(jj)]);
+#pragma unroll
+                        for (int t = 0; t < jj; ++t) sv -= Lm[i][t] * Lm[jj][t];
+                        if (i == jj) {
+                            R y = __builtin_amdgcn_rsq(sv);
+                            y = __builtin_elementwise_fma(y * 0.5, __builtin_elementwise_fma(-sv * y, y, 1.0), y);
+                            y = __builtin_elementwise_fma(y * 0.5, __builtin_elementwise_fma(-sv * y, y, 1.0), y);
+                            rd[i] = y;
+                            Lm[i][i] = sv * y;
+                        }
+                        else Lm[i][jj] = sv * rd[jj];
+                    }
+                R y[PJ];
+#pragma unroll
+                for (int i = 0; i < PJ; ++i) {
+                    R sv = (i == l) ? 1.0 : 0.0;
+#pragma unroll
+                    for (int t = 0; t < i; ++t) sv -= Lm[i][t] * y[t];
+                    y[i] = sv * rd[i];
+                }
+#pragma unroll
+                for (int i = PJ - 1; i >= 0; --i) {
+                    R sv = y[i];
+#pragma unroll
+                    for (int t = i + 1; t < PJ; ++t) sv -= Lm[t][i] * y[t];
+                    y[i] = sv * rd[i];
+                }
+#pragma unroll
+                for (int i = 0; i < PJ; ++i) qdd += y[i] * (I->U[i] - rec(PJ)[RN_TAU(i)]);      // bias_i = tau_i of lane 7
+            }
+            // end-effector position from the three pose sweeps (kkt_plant.hip.h: [W_i ; V_i] = [R e_i ; R (e_i x p)])
+            R W1[3], W2[3], V0[3], V1[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                W1[r] = rec(PJ + 2)[RN_AW + r]; W2[r] = rec(PJ + 3)[RN_AW + r];
+                V0[r] = rec(PJ + 1)[RN_AU + r]; V1[r] = rec(PJ + 2)[RN_AU + r];
+            }
+            const R ee0 = -(W2[0] * V1[0] + W2[1] * V1[1] + W2[2] * V1[2]);
+            const R ee1 = W2[0] * V0[0] + W2[1] * V0[1] + W2[2] * V0[2];
+            const R ee2 = -(W1[0] * V0[0] + W1[1] * V0[1] + W1[2] * V0[2]);
+            const R q = I->Xq[l], qd = I->Xq[PJ + l];
+            R pm = 0.5 * a.qd_cost * qd * qd;
+            if (l < 3) {                                     // lanes 0..2: one coordinate of the tracking error each
+                const IO* goal = a.eePos_traj + ((size_t)b * N + k) * 6;
+                const R d = (l == 0 ? ee0 : (l == 1 ? ee1 : ee2)) - (R)goal[l];
+                pm += 0.5 * d * d;
+            }
+            R viol = 0.0;
+            if (dyn) {
+                pm += 0.5 * a.r_cost * ul * ul;
+                if constexpr (INTEGRATOR == 1) {                  // semi-implicit Euler: q' = q + dt qd', qd' = qd + dt qdd (the map the KKT kernel linearised)
+                    const R qdn = qd + a.dt * qdd;
+                    viol = fabs(xn_q - (q + a.dt * qdn)) + fabs(xn_qd - qdn);
+                } else
+                viol = fabs(xn_q - (q + a.dt * qd)) + fabs(xn_qd - (qd + a.dt * qdd));
+            }
+            if (k == 0 && a.xs) viol += fabs(q - (R)a.xs[(size_t)b * n + l]) + fabs(qd - (R)a.xs[(size_t)b * n + PJ + l]);
+            I->Gq[l] = pm + a.mu * viol;
+        }
+        __syncthreads();
+        if (l == 0 && live) {                                // the group's sum, in lane order
+            R s = I->Gq[0];
+#pragma unroll
+            for (int i = 1; i < PJ; ++i) s += I->Gq[i];
+            a.point[((size_t)b * MERIT_MAX_STEPS + ai) * N + k] = s;
+        }
+        __syncthreads();
+    }
 }
 
 // One thread per (trajectory, step size): the point merits of its row added knot by knot, rounded once (T = double: the sum itself).
 template <typename T>
-__device__ __forceinline__ void merit_sum(const double* point, T* merit, int N, int A, int rows) {
+__global__ __launch_bounds__(64) void merit_sum_kernel(const double* point, T* merit, int N, int A, int rows) {
     const int r = blockIdx.x * 64 + threadIdx.x;
     if (r >= rows) return;
     const int b = r / A, ai = r - b * A;
@@ -95,61 +218,40 @@ __device__ __forceinline__ void merit_sum(const double* point, T* merit, int N, 
     for (int k = 1; k < N; ++k) s += p[k];
     merit[r] = (T)s;
 }
-__global__ __launch_bounds__(64) void merit_sum_kernel(const double* point, float* merit, int N, int A, int rows) { merit_sum(point, merit, N, A, rows); }
-__global__ __launch_bounds__(64) void merit_sum_f64_kernel(const double* point, double* merit, int N, int A, int rows) { merit_sum(point, merit, N, A, rows); }
 
 // The step selection of include/pcg/sqp.cuh:292-301 and the update :317, 332-338, 352, per trajectory (one workgroup each): strict comparison, the
-// first of equals wins, a NaN never wins; p >= 0: xu = fmaf(alpha_p, dz, xu) — the float merit_points_kernel evaluated — and merit_ref = merit[p];
-// p = -1: xu and merit_ref are not written.
-struct StepArgs {
-    const float* merit;                  // [batch][A]
-    float* merit_ref;                    // [batch] in/out
-    const float* dz;
-    float* xu;
+// first of equals wins, a NaN never wins; p >= 0: xu = fma(alpha_p, dz, xu) in T — what merit_points_kernel<T> evaluated — and merit_ref = merit[p];
+// p = -1: xu and merit_ref are not written.  T = float: mpcg_line_search_step; T = double: mpcg_line_search_step_f64.
+template <typename T> struct StepArgsT {
+    const T* merit;                      // [batch][A]
+    T* merit_ref;                        // [batch] in/out
+    const T* dz;
+    T* xu;
     int32_t* step;                       // [batch] out
     int A;
     size_t len;                          // (n + m) N - m
-    float alpha[MERIT_MAX_STEPS];
-    typedef float real;
-};
-struct StepArgsF64 {                     // mpcg_line_search_step_f64: the same fields in double
-    const double* merit;
-    double* merit_ref;
-    const double* dz;
-    double* xu;
-    int32_t* step;
-    int A;
-    size_t len;
-    double alpha[MERIT_MAX_STEPS];
-    typedef double real;
+    T alpha[MERIT_MAX_STEPS];
+    typedef T real;
 };
 
-// mpcg_line_search_step_rho: the same selection and update, then the rho adaptation of sqp.cuh:304-320 per trajectory, in float with one rounding
-// per operation (nothing here can contract: no product feeds an addition) and correctly rounded divisions:
+// mpcg_line_search_step_rho(_f64): the same selection and update, then the rho adaptation of sqp.cuh:304-320 per trajectory, in T with one rounding
+// per operation (nothing here can contract: no product feeds an addition; step_mul, step_div, step_max, step_min) and correctly rounded divisions:
 //   p < 0 :  drho = max(drho * f, f);      rho = max(rho * drho, rho_min);  rho > rho_max: rho = rho_reset, done = 1
 //   p >= 0:  drho = min(drho / f, 1 / f);  rho = max(rho * drho, rho_min)
 // A trajectory with done != 0 on entry is frozen: step = STEP_FROZEN and nothing else is written.
-struct StepRhoArgs : StepArgs {
-    float* rho;                          // [batch] in/out
-    float* drho;                         // [batch] in/out
+template <typename T> struct StepRhoArgsT : StepArgsT<T> {
+    T* rho;                              // [batch] in/out
+    T* drho;                             // [batch] in/out
     uint8_t* done;                       // [batch] in/out
-    float factor, rho_min, rho_max, rho_reset;
-};
-struct StepRhoArgsF64 : StepArgsF64 {    // mpcg_line_search_step_rho_f64: the rule above in double (__dmul_rn, __ddiv_rn, fmax, fmin)
-    double* rho;
-    double* drho;
-    uint8_t* done;
-    double factor, rho_min, rho_max, rho_reset;
+    T factor, rho_min, rho_max, rho_reset;
 };
 constexpr int32_t STEP_FROZEN = -2;      // MPCG_STEP_FROZEN
-template <typename T> struct StepTypes { typedef StepArgs plain; typedef StepRhoArgs with_rho; };
-template <> struct StepTypes<double> { typedef StepArgsF64 plain; typedef StepRhoArgsF64 with_rho; };
 
-// SA = StepArgs(F64): mpcg_line_search_step(_f64); SA = StepRhoArgs(F64): mpcg_line_search_step_rho(_f64) — one selection, one update
-template <class SA = StepArgs>
+// SA = StepArgsT<T>: mpcg_line_search_step(_f64); SA = StepRhoArgsT<T>: mpcg_line_search_step_rho(_f64) — one selection, one update
+template <class SA = StepArgsT<float>>
 __global__ __launch_bounds__(256) void line_search_step_kernel(SA a) {
     typedef typename SA::real T;
-    constexpr bool RHO = std::is_same<SA, typename StepTypes<T>::with_rho>::value;
+    constexpr bool RHO = std::is_same<SA, StepRhoArgsT<T>>::value;
     const size_t b = blockIdx.x;
     if constexpr (RHO) {
         if (a.done[b] != 0) {                                // (uniform; nobody in this workgroup writes done before the barrier below)

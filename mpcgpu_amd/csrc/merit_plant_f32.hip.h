@@ -24,22 +24,11 @@
 
 namespace mpcg {
 
-struct MeritArgsF32 {
-    const PlantDevT<float>* plant;
-    const float* eePos_traj;             // as MeritArgs
-    const float* xs;
-    const float* xu;
-    const float* dz;
-    double* point;                       // [batch][MERIT_MAX_STEPS][N] point merits: the double kernel's scratch
-    int N, batch, A;
-    float dt, mu, qd_cost, r_cost;
-    float alpha[MERIT_MAX_STEPS];
-};
-
 __device__ __forceinline__ kkt_f2 merit_sel(const bool (&c)[2], kkt_f2 x, kkt_f2 y) { return kkt_f2{c[0] ? x.x : y.x, c[1] ? x.y : y.y}; }
 
+// MeritArgsT<float, float>: the float model tables and float scalars; `point` is the double kernel's scratch
 template <int INTEGRATOR = 0>
-__global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(MeritArgsF32 a) {
+__global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(MeritArgsT<float, float> a) {
     typedef kkt_f2 R;
     typedef KktR<R> T;
     typedef KktLds<R>::vr kkt_lds_vd;

@@ -3,6 +3,7 @@
 // mpcg_line_search_step(_rho)(_f64) over merit_plant.hip.h (the merit in packed float, "merit_f32": merit_plant_f32.hip.h); the step between two SQP solves — mpcg_simulate(_f64) and mpcg_advance_horizon(_f64) over sim_plant.hip.h;
 // the plant's gravity (mpcg_plant_clone_gravity) and mpcg_inverse_dynamics(_f64) over invdyn_plant.hip.h.
 #include <cmath>
+#include <memory>
 #include <type_traits>
 #include "mpcg_handle.hpp"
 #include "kkt_plant.hip.h"
@@ -21,6 +22,22 @@ struct mpcg_plant {
     PlantDev host; PlantDevT<float> host32;                                      // what the device holds: mpcg_plant_clone_gravity copies these, mpcg_plant_get_gravity reads host.grav
 };
 
+// pl->host and pl->host32 into ONE new allocation on pl->device (host32 behind host); on failure nothing stays allocated
+static bool plant_upload(mpcg_plant* pl) {
+    if (hipSetDevice(pl->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&pl->d), sizeof(PlantDev) + sizeof(PlantDevT<float>)) != hipSuccess) {
+        pl->d = nullptr;
+        return false;
+    }
+    if (hipMemcpy(pl->d, &pl->host, sizeof(PlantDev), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(pl->d + 1, &pl->host32, sizeof(PlantDevT<float>), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(pl->d);
+        pl->d = nullptr;
+        return false;
+    }
+    pl->d32 = reinterpret_cast<PlantDevT<float>*>(pl->d + 1);
+    return true;
+}
+
 int mpcg_plant_create(mpcg_plant** out, int device, uint32_t num_joints, const double* X_const, const double* I_spatial, const double* Xhom_const,
                       const int32_t* X_trig_idx, const double* X_trig_coef, const int32_t* X_trig_j, uint32_t n_X_trig,
                       const int32_t* Xhom_trig_idx, const double* Xhom_trig_coef, const int32_t* Xhom_trig_j, uint32_t n_Xhom_trig) {
@@ -30,15 +47,15 @@ int mpcg_plant_create(mpcg_plant** out, int device, uint32_t num_joints, const d
     if (!X_const || !I_spatial || !Xhom_const || (n_X_trig && (!X_trig_idx || !X_trig_coef || !X_trig_j)) ||
         (n_Xhom_trig && (!Xhom_trig_idx || !Xhom_trig_coef || !Xhom_trig_j)))
         return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_create: null table");
-    PlantDev* hp = new (std::nothrow) PlantDev();
+    std::unique_ptr<PlantDev> hp(new (std::nothrow) PlantDev());
     if (!hp) return MPCG_ERR_NOMEM;
-    memset(hp, 0, sizeof(PlantDev));
+    memset(hp.get(), 0, sizeof(PlantDev));
     // The tables as given: X_k(q_k) = [[E, 0], [B, E]] with E = E0 + Es sin q_k + Ec cos q_k (likewise B), homogeneous transforms
     // R = R0 + Rs sin + Rc cos and translation p.  Tables are column-major (6x6 / 4x4), these are row-major 3x3 blocks.
     struct Given { double E0[PJ][9], Es[PJ][9], Ec[PJ][9], B0[PJ][9], Bs[PJ][9], Bc[PJ][9], R0[PJ][9], Rs[PJ][9], Rc[PJ][9], p[PJ][3], I[PJ][36]; };
-    Given* gv = new (std::nothrow) Given();
-    if (!gv) { delete hp; return MPCG_ERR_NOMEM; }
-    memset(gv, 0, sizeof(Given));
+    std::unique_ptr<Given> gv(new (std::nothrow) Given());
+    if (!gv) return MPCG_ERR_NOMEM;
+    memset(gv.get(), 0, sizeof(Given));
     auto place = [&](int k, int r, int c, double v, int which /*0 const, 1 sin, 2 cos*/) -> bool {
         double(*E)[9] = which == 0 ? gv->E0 : (which == 1 ? gv->Es : gv->Ec);
         double(*B)[9] = which == 0 ? gv->B0 : (which == 1 ? gv->Bs : gv->Bc);
@@ -70,7 +87,7 @@ int mpcg_plant_create(mpcg_plant** out, int device, uint32_t num_joints, const d
         gv->R0[k][3 * r + c] = 0.0;
         (j < PJ ? gv->Rs : gv->Rc)[k][3 * r + c] = Xhom_trig_coef[t];
     }
-    if (!ok) { delete hp; delete gv; return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_create: tables do not describe a serial chain of revolute joints (X = [[E, 0], [B, E]], joint k depends on q_k)"); }
+    if (!ok) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_create: tables do not describe a serial chain of revolute joints (X = [[E, 0], [B, E]], joint k depends on q_k)");
     // The kernel applies X_k(q) as blkdiag(Rz, Rz) Xtree, Rz = [[c, s, 0], [-s, c, 0], [0, 0, 1]] (a revolute joint about its own z axis,
     // the convention of GRiD's tables): row 0 = c T0 + s T1, row 1 = -s T0 + c T1, row 2 = T2 with T = E0 + Ec the transform at q = 0.
     // Verify that the given constant / sin / cos parts have exactly that form.
@@ -95,20 +112,15 @@ int mpcg_plant_create(mpcg_plant** out, int device, uint32_t num_joints, const d
         dev = fmax(dev, rotz_form(hp->ET[k], gv->E0[k], gv->Es[k], gv->Ec[k]));
         dev = fmax(dev, rotz_form(hp->BT[k], gv->B0[k], gv->Bs[k], gv->Bc[k]));
     }
-    if (!(dev <= 1e-12 * fmax(scale, 1.0))) {
-        delete hp; delete gv;
+    if (!(dev <= 1e-12 * fmax(scale, 1.0)))
         return fail(nullptr, MPCG_ERR_UNSUPPORTED, "mpcg_plant_create: every joint must rotate about its own z axis, X_k(q) = blkdiag(Rz(q), Rz(q)) X_k(0) (the form of GRiD's tables)");
-    }
     // Spatial inertias: the kernel multiplies with the rigid-body form [[Ibar, skew(h)], [skew(h)^T, m 1]] (ten numbers).
     for (int k = 0; k < PJ; ++k) {
         const double* Ik = gv->I[k];
         double sc = 0.0, asym = 0.0;
         for (int r = 0; r < 6; ++r)
             for (int c = 0; c < 6; ++c) { sc = fmax(sc, fabs(Ik[6 * r + c])); asym = fmax(asym, fabs(Ik[6 * r + c] - Ik[6 * c + r])); }
-        if (!(asym <= 1e-12 * fmax(1.0, sc))) {
-            delete hp; delete gv;
-            return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_create: spatial inertias must be symmetric");
-        }
+        if (!(asym <= 1e-12 * fmax(1.0, sc))) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_create: spatial inertias must be symmetric");
         const double mass = Ik[6 * 3 + 3], h[3] = {Ik[6 * 2 + 4], Ik[6 * 0 + 5], Ik[6 * 1 + 3]};      // skew(h) = [[0, -hz, hy], [hz, 0, -hx], [-hy, hx, 0]]
         const double sk[9] = {0, -h[2], h[1], h[2], 0, -h[0], -h[1], h[0], 0};
         double devI = 0.0;
@@ -117,10 +129,8 @@ int mpcg_plant_create(mpcg_plant** out, int device, uint32_t num_joints, const d
                 devI = fmax(devI, fabs(Ik[6 * r + 3 + c] - sk[3 * r + c]));
                 devI = fmax(devI, fabs(Ik[6 * (3 + r) + 3 + c] - (r == c ? mass : 0.0)));
             }
-        if (!(devI <= 1e-12 * fmax(1.0, sc))) {
-            delete hp; delete gv;
+        if (!(devI <= 1e-12 * fmax(1.0, sc)))
             return fail(nullptr, MPCG_ERR_UNSUPPORTED, "mpcg_plant_create: spatial inertias must have the rigid-body form [[Ibar, skew(m c)], [skew(m c)^T, m 1]]");
-        }
         const double ib[10] = {Ik[0], Ik[1], Ik[2], Ik[7], Ik[8], Ik[14], h[0], h[1], h[2], mass};
         memcpy(hp->Ib[k], ib, sizeof(ib));
     }
@@ -156,33 +166,24 @@ int mpcg_plant_create(mpcg_plant** out, int device, uint32_t num_joints, const d
                                   -(W[1][0] * V[0][0] + W[1][1] * V[0][1] + W[1][2] * V[0][2])};
             for (int r = 0; r < 3; ++r) worst = fmax(worst, fabs(ee[r] - pos[r]));
         }
-        if (!(worst <= 1e-9)) {
-            delete hp; delete gv;
+        if (!(worst <= 1e-9))
             return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_create: the homogeneous transforms (Xhom) and the spatial transforms (X) describe different chains");
-        }
     }
-    delete gv;
-    mpcg_plant* pl = new (std::nothrow) mpcg_plant();
-    if (!pl) { delete hp; return MPCG_ERR_NOMEM; }
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) { delete hp; delete pl; return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_create: no HIP device"); }
+    gv.reset();
+    std::unique_ptr<mpcg_plant> pl(new (std::nothrow) mpcg_plant());
+    if (!pl) return MPCG_ERR_NOMEM;
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_create: no HIP device");
     pl->device = device;
     // the float build of the kernel (linsys_t's own arithmetic, "kkt_f32") reads the same tables rounded to float
-    PlantDevT<float>* hp32 = new (std::nothrow) PlantDevT<float>();
-    if (!hp32) { delete hp; delete pl; return MPCG_ERR_NOMEM; }
+    std::unique_ptr<PlantDevT<float>> hp32(new (std::nothrow) PlantDevT<float>());
+    if (!hp32) return MPCG_ERR_NOMEM;
     for (int k = 0; k < PJ; ++k) {
         for (int e = 0; e < 9; ++e) { hp32->ET[k][e] = (float)hp->ET[k][e]; hp32->BT[k][e] = (float)hp->BT[k][e]; }
         for (int e = 0; e < 10; ++e) hp32->Ib[k][e] = (float)hp->Ib[k][e];
     }
-    if (hipSetDevice(device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&pl->d), sizeof(PlantDev) + sizeof(PlantDevT<float>)) != hipSuccess ||
-        hipMemcpy(pl->d, hp, sizeof(PlantDev), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(pl->d + 1, hp32, sizeof(PlantDevT<float>), hipMemcpyHostToDevice) != hipSuccess) {
-        delete hp; delete hp32; delete pl;
-        return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_create: cannot place the model on the device");
-    }
-    pl->d32 = reinterpret_cast<PlantDevT<float>*>(pl->d + 1);
     pl->host = *hp; pl->host32 = *hp32;                     // (grav = {0, 0, 0}: hp was zero-filled, hp32 value-initialised)
-    delete hp; delete hp32;
-    *out = pl;
+    if (!plant_upload(pl.get())) return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_create: cannot place the model on the device");
+    *out = pl.release();
     return MPCG_OK;
 }
 
@@ -211,17 +212,10 @@ int mpcg_plant_clone_gravity(mpcg_plant** out, const mpcg_plant* src, const doub
         pl->host.grav[r] = base_accel[r] + 0.0;             // (-0 becomes +0: a zero vector is the plain plant's, whatever its sign bits)
         pl->host32.grav[r] = (float)pl->host.grav[r];
     }
-    if (hipSetDevice(pl->device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&pl->d), sizeof(PlantDev) + sizeof(PlantDevT<float>)) != hipSuccess) {
+    if (!plant_upload(pl)) {
         delete pl;
         return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_clone_gravity: cannot place the model on the device");
     }
-    if (hipMemcpy(pl->d, &pl->host, sizeof(PlantDev), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(pl->d + 1, &pl->host32, sizeof(PlantDevT<float>), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(pl->d);
-        delete pl;
-        return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_clone_gravity: cannot place the model on the device");
-    }
-    pl->d32 = reinterpret_cast<PlantDevT<float>*>(pl->d + 1);
     *out = pl;
     return MPCG_OK;
 }
@@ -251,11 +245,14 @@ static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* p
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
-    typename std::conditional<std::is_same<T, float>::value, KktArgs, KktArgsF64>::type a;
-    a.plant = plant->d; a.eePos_traj = d_eePos_traj; a.xs = d_xs; a.xu = d_xu;
-    a.G = d_G_dense; a.C = d_C_dense; a.g = d_g; a.c = d_c;
-    a.N = (int)h->N; a.batch = (int)batch; a.dt = timestep; a.qd_cost = qd_cost; a.r_cost = r_cost;
-    a.analytic = h->kkt_analytic;
+    auto fill = [&](auto& k, const auto* tables) {        // one fill for either arithmetic: the scalars convert to the struct's S
+        k.plant = tables; k.eePos_traj = d_eePos_traj; k.xs = d_xs; k.xu = d_xu;
+        k.G = d_G_dense; k.C = d_C_dense; k.g = d_g; k.c = d_c;
+        k.N = (int)h->N; k.batch = (int)batch; k.dt = timestep; k.qd_cost = qd_cost; k.r_cost = r_cost;
+        k.analytic = h->kkt_analytic;
+    };
+    KktArgsT<double, T> a;
+    fill(a, plant->d);
     long blocks = ((long)batch * (h->N - 1) + KKT_ITEMS - 1) / KKT_ITEMS;      // one wavefront per KKT_ITEMS (trajectory, knot) pairs
     const long cap = (long)h->num_cus * 32;
     if (blocks > cap) blocks = cap;
@@ -263,14 +260,12 @@ static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* p
     const bool semi = h->integrator == 1;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     if constexpr (std::is_same<T, double>::value) {       // double arrays: float64 inside, either gradient route
-        if (h->kkt_analytic) hipLaunchKernelGGL((semi ? generate_kkt_f64_kernel<true, 1> : generate_kkt_f64_kernel<true, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
-        else hipLaunchKernelGGL((semi ? generate_kkt_f64_kernel<false, 1> : generate_kkt_f64_kernel<false, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+        if (h->kkt_analytic) hipLaunchKernelGGL((semi ? generate_kkt_kernel<true, double, 1, double> : generate_kkt_kernel<true, double, 0, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((semi ? generate_kkt_kernel<false, double, 1, double> : generate_kkt_kernel<false, double, 0, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
     } else {
         if (h->kkt_analytic && h->kkt_f32) {                  // linsys_t = float arithmetic throughout, as the reference's GRiD code (kkt_plant.hip.h, R = float)
             KktArgsT<float> f;
-            f.plant = plant->d32; f.eePos_traj = d_eePos_traj; f.xs = d_xs; f.xu = d_xu;
-            f.G = d_G_dense; f.C = d_C_dense; f.g = d_g; f.c = d_c;
-            f.N = (int)h->N; f.batch = (int)batch; f.dt = timestep; f.qd_cost = qd_cost; f.r_cost = r_cost; f.analytic = 1;
+            fill(f, plant->d32);
             // 1: two knots per lane in packed float (whatever the size of the call: a trajectory's results do not depend on what else is in the batch);
             // 2: one knot per lane (the packed build's checker; 8 % faster than the default, where the packed build is 1.6x faster on throughput-sized calls)
             if (h->kkt_f32 == 1) {
@@ -318,7 +313,7 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
     { const int rc = check_steps(h, fn, step_sizes, num_steps); if (rc != MPCG_OK) return rc; }
     if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
     if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
-    typename std::conditional<F64, MeritArgsF64, MeritArgs>::type a;
+    MeritArgsT<T> a;
     bool moved = false;
     for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) { a.alpha[i] = i < num_steps ? step_sizes[i] : T(0); moved = moved || a.alpha[i] != T(0); }
     if (moved && !d_dz) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": d_dz may be NULL only if every step size is 0");
@@ -330,24 +325,25 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
         { const int rc = alloc_allowed(h, st, fn); if (rc != MPCG_OK) return rc; }
         HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->merit_scratch), (size_t)h->max_batch * MERIT_MAX_STEPS * h->N * sizeof(double)));
     }
-    a.plant = plant->d; a.eePos_traj = d_eePos_traj; a.xs = d_xs; a.xu = d_xu; a.dz = d_dz; a.point = h->merit_scratch;
-    a.N = (int)h->N; a.batch = (int)batch; a.A = (int)num_steps;
-    a.dt = timestep; a.mu = mu; a.qd_cost = qd_cost; a.r_cost = r_cost;
+    auto fill = [&](auto& k, const auto* tables) {        // everything but the step sizes; the scalars convert to the struct's S
+        k.plant = tables; k.eePos_traj = d_eePos_traj; k.xs = d_xs; k.xu = d_xu; k.dz = d_dz; k.point = h->merit_scratch;
+        k.N = (int)h->N; k.batch = (int)batch; k.A = (int)num_steps;
+        k.dt = timestep; k.mu = mu; k.qd_cost = qd_cost; k.r_cost = r_cost;
+    };
+    fill(a, plant->d);
     long blocks = ((long)batch * num_steps * h->N + KKT_ITEMS - 1) / KKT_ITEMS;      // one wavefront per KKT_ITEMS (trajectory, step size, knot) items
     const long cap = (long)h->num_cus * 32;
     if (blocks > cap) blocks = cap;
     const int rows = (int)(batch * num_steps);
     const bool semi = h->integrator == 1;          // "integrator": the map mpcg_generate_kkt linearised (one knob for both, every build)
     if constexpr (F64) {                          // double arrays: float64 inside ("merit_f32" is the float entry's), the row sums stored as they are
-        hipLaunchKernelGGL((semi ? merit_points_f64_kernel<1> : merit_points_f64_kernel<0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+        hipLaunchKernelGGL((semi ? merit_points_kernel<double, 1> : merit_points_kernel<double, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
         HIP_TRY(h, hipGetLastError());
-        hipLaunchKernelGGL(merit_sum_f64_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
+        hipLaunchKernelGGL(merit_sum_kernel<double>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
     } else {
         if (h->merit_f32) {                           // the reference's own arithmetic (merit.cuh, T = float): two items per lane group in packed float, whatever the size of the call
-            MeritArgsF32 f;
-            f.plant = plant->d32; f.eePos_traj = d_eePos_traj; f.xs = d_xs; f.xu = d_xu; f.dz = d_dz; f.point = h->merit_scratch;
-            f.N = a.N; f.batch = a.batch; f.A = a.A;
-            f.dt = timestep; f.mu = mu; f.qd_cost = qd_cost; f.r_cost = r_cost;
+            MeritArgsT<float, float> f;
+            fill(f, plant->d32);
             memcpy(f.alpha, a.alpha, sizeof(f.alpha));
             // one wavefront per trip of 2 KKT_ITEMS items (no trip loop: merit_plant_f32.hip.h); at most max_batch x 16 x N / 8 of them, and a handle whose
             // scratch of max_batch x 16 x N doubles could be allocated stays far below the 2^31 - 1 workgroups a grid dimension holds
@@ -355,9 +351,9 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
             if (pblocks > 0x7fffffffL) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch x num_steps x knot_points exceeds the grid");
             hipLaunchKernelGGL((semi ? merit_points_f32_kernel<1> : merit_points_f32_kernel<0>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
         } else
-        hipLaunchKernelGGL((semi ? merit_points_kernel<1> : merit_points_kernel<0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+        hipLaunchKernelGGL((semi ? merit_points_kernel<float, 1> : merit_points_kernel<float, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
         HIP_TRY(h, hipGetLastError());
-        hipLaunchKernelGGL(merit_sum_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
+        hipLaunchKernelGGL(merit_sum_kernel<float>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
     }
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
@@ -366,9 +362,9 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
 // mpcg_line_search_step(_f64) and mpcg_line_search_step_rho(_f64): one host path (fn: the entry point's name; rho: null for the former)
 template <typename T>
 static int line_search_step_impl(mpcg_handle* h, const char* fn, uint32_t control_size, const T* d_merit, const T* step_sizes, uint32_t num_steps,
-                                 T* d_merit_ref, const T* d_dz, T* d_xu, int32_t* d_step, const typename StepTypes<T>::with_rho* rho, uint32_t batch, void* stream) {
-    typedef typename StepTypes<T>::plain Plain;
-    typedef typename StepTypes<T>::with_rho WithRho;
+                                 T* d_merit_ref, const T* d_dz, T* d_xu, int32_t* d_step, const StepRhoArgsT<T>* rho, uint32_t batch, void* stream) {
+    typedef StepArgsT<T> Plain;
+    typedef StepRhoArgsT<T> WithRho;
     if (!h) return MPCG_ERR_INVALID;
     if (!d_merit || !d_merit_ref || !d_dz || !d_xu || !d_step || (rho && (!rho->rho || !rho->drho || !rho->done)))
         return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
@@ -400,7 +396,7 @@ static int line_search_step_rho_impl(mpcg_handle* h, const char* fn, uint32_t co
                                      T* d_merit_ref, const T* d_dz, T* d_xu, int32_t* d_step, T* d_rho, T* d_drho, uint8_t* d_done,
                                      T rho_factor, T rho_min, T rho_max, T rho_reset, uint32_t batch, void* stream) {
     static_assert(STEP_FROZEN == MPCG_STEP_FROZEN, "the frozen code of the header");
-    typename StepTypes<T>::with_rho r{};
+    StepRhoArgsT<T> r{};
     r.rho = d_rho; r.drho = d_drho; r.done = d_done; r.factor = rho_factor; r.rho_min = rho_min; r.rho_max = rho_max; r.rho_reset = rho_reset;
     return line_search_step_impl<T>(h, fn, control_size, d_merit, step_sizes, num_steps, d_merit_ref, d_dz, d_xu, d_step, &r, batch, stream);
 }
@@ -451,7 +447,6 @@ template <typename T>
 static int simulate_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, T* d_xs, const T* d_xu, double timestep,
                          double time_offset_us, double sim_time_us, T sim_step, T* d_eePos, uint32_t batch, void* stream) {
     static_assert(SIM_MAX_SUBSTEPS == MPCG_SIM_MAX_SUBSTEPS, "the cap of the header");
-    constexpr bool F64 = std::is_same<T, double>::value;
     if (!h || !plant) return MPCG_ERR_INVALID;
     if (!d_xs || !d_xu) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
     if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
@@ -467,15 +462,14 @@ static int simulate_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
-    typename std::conditional<F64, SimArgsF64, SimArgs>::type a;
+    SimArgsT<T> a;
     a.plant = plant->d; a.xs = d_xs; a.xu = d_xu; a.eePos = d_eePos;
     a.N = (int)h->N; a.batch = (int)batch;
     a.S = (unsigned)full; a.ss = ss; a.toff = toff; a.timestep = timestep;
     a.rem = (double)(T)fmod(sim, ss);                        // (the reference's T: a float remainder is rounded to float, a double one is fmod's value)
     const dim3 grid((batch + KKT_ITEMS - 1) / KKT_ITEMS);
     const bool semi = h->sim_integrator == 1;      // "sim_integrator": the substep q' = q + dt qd' (0, the default: the reference's plant, explicit Euler)
-    if constexpr (F64) hipLaunchKernelGGL((semi ? simulate_f64_kernel<1> : simulate_f64_kernel<0>), grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    else hipLaunchKernelGGL((semi ? simulate_kernel<1> : simulate_kernel<0>), grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL((semi ? simulate_kernel<T, 1> : simulate_kernel<T, 0>), grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
@@ -498,12 +492,11 @@ static int advance_horizon_impl(mpcg_handle* h, const char* fn, uint32_t control
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, who + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
-    typename std::conditional<F64, AdvanceArgsF64, AdvanceArgs>::type a;
+    AdvanceArgsT<T> a;
     a.xu = d_xu; a.lambda = d_lambda; a.goal = d_eePos_goal; a.xs = d_xs; a.eePos = d_eePos; a.xu_traj = d_xu_traj; a.goal_traj = d_eePos_traj;
     a.traj_offset = d_traj_offset; a.done = d_done; a.tracking_error = d_tracking_error;
     a.n = h->n; a.m = control_size; a.N = h->N; a.traj_steps = traj_steps; a.traj_stride = traj_batch_stride; a.lead = xu_fill_lead; a.shift = shift;
-    if constexpr (F64) hipLaunchKernelGGL(advance_horizon_f64_kernel, dim3(batch), dim3(ADV_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    else hipLaunchKernelGGL(advance_horizon_kernel, dim3(batch), dim3(ADV_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(advance_horizon_kernel<T>, dim3(batch), dim3(ADV_THREADS), 0, static_cast<hipStream_t>(stream), a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }

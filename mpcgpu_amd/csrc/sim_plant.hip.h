@@ -3,8 +3,8 @@
 // all substeps, and of the tracking error, just_shift, the tail fills and the start-state copy of simulateMPC (include/mpcsim.cuh:300-348: one
 // cudaMemcpy per knot) as a second, dynamics-free kernel.
 //
-// simulate_kernel<INTEGRATOR>.  A substep is the explicit Euler step of the KKT kernel's integrator, q += dt qd, qd += dt qdd (both from the old values;
-// INTEGRATOR = 1, option "sim_integrator": semi-implicit Euler, qd' = qd + dt qdd, q' = q + dt qd' — a compile-time parameter, `if constexpr` in sim_steps.inc), qdd =
+// simulate_kernel<IO, INTEGRATOR>.  A substep is the explicit Euler step of the KKT kernel's integrator, q += dt qd, qd += dt qdd (both from the old values;
+// INTEGRATOR = 1, option "sim_integrator": semi-implicit Euler, qd' = qd + dt qdd, q' = q + dt qd' — a compile-time parameter, `if constexpr` in the kernel), qdd =
 // Minv (u - bias) (the bias with the gravity vector of the plant given: rnea, kkt_plant.hip.h), so the mapping is merit_points_kernel's: a 16-lane group per trajectory, four trajectories per wavefront; lanes
 // 0..6 the inertia-matrix columns and lane 7 the bias through rnea<double>, then lanes 0..6 the Cholesky solve (plant_qdd_lane: the merit kernel's
 // arithmetic).  The substeps are a loop INSIDE the kernel: q, qd and sin / cos wait in the item record in LDS between them.  The schedule is the reference's,
@@ -21,13 +21,12 @@
 // recomputes the last one and writes nothing; no atomics; a trajectory's arithmetic depends on nothing but that trajectory.
 // LDS per wavefront: merit_points_kernel's (4 x 840 B item records + 4 x 11 recursion records of 296 B) = 16,384 B.
 //
-// advance_horizon_kernel.  One workgroup per trajectory; every value that moves is LOADED, then a barrier, then stored (the source and destination
+// advance_horizon_kernel<IO>.  One workgroup per trajectory; every value that moves is LOADED, then a barrier, then stored (the source and destination
 // regions of a shift overlap by one knot).  See include/mpcg.h for the order of operations.
 //
-// The double twins (mpcg_simulate_f64, mpcg_advance_horizon_f64; linsys_t = double): simulate_f64_kernel and advance_horizon_f64_kernel over the SAME body
-// texts (sim_steps.inc, sim_advance.inc, included by both kernels of a pair with IO = float / double).  simulate_f64_kernel uses d_xs and the controls as
-// they are and stores the float64 state and end-effector position without a rounding; its remainder is fmod(sim, ss) as a double (the host's part of
-// the schedule: mpcg_plant.hip).  advance_horizon_f64_kernel sweeps chunks of the same number of ELEMENTS and forms the tracking error in double.
+// The double twins (mpcg_simulate_f64, mpcg_advance_horizon_f64; linsys_t = double) are the same two templates with IO = double.  simulate_kernel<double> uses
+// d_xs and the controls as they are and stores the float64 state and end-effector position without a rounding; its remainder is fmod(sim, ss) as a double (the host's part of
+// the schedule: mpcg_plant.hip).  advance_horizon_kernel<double> sweeps chunks of the same number of ELEMENTS and forms the tracking error in double.
 #pragma once
 #include "merit_plant.hip.h"
 #pragma clang fp contract(fast)
@@ -96,59 +95,100 @@ __device__ __forceinline__ void plant_ee_pos(KktLds<double>::vr* recs, double& e
     ee2 = -(W1[0] * V0[0] + W1[1] * V0[1] + W1[2] * V0[2]);
 }
 
-struct SimArgs {
+// IO = float: mpcg_simulate; IO = double (mpcg_simulate_f64, linsys_t = double): d_xs and the controls are used as they are, the state and the end-effector
+// position are stored without a rounding.
+template <typename IO> struct SimArgsT {
     const PlantDev* plant;
-    float* xs;                           // [batch][n] in/out
-    const float* xu;                     // [batch][(n+m)N - m]
-    float* eePos;                        // [batch][3] or NULL
+    IO* xs;                              // [batch][n] in/out
+    const IO* xu;                        // [batch][(n+m)N - m]
+    IO* eePos;                           // [batch][3] or NULL
     int N, batch;
     unsigned S;                          // full substeps
     double ss, toff, timestep;           // substep, time offset, knot spacing [s]
-    double rem;                          // the remainder substep, (double)(float)fmod(sim, ss); 0: none
+    double rem;                          // the remainder substep, (double)(IO)fmod(sim, ss): rounded to float, or fmod's value as a double; 0: none
 };
 
-// mpcg_simulate_f64 (linsys_t = double): the same fields with the arrays in double.  d_xs and the controls are used as they are, the state and the end-effector
-// position are stored without a rounding; rem is fmod(sim, ss) as a double.
-struct SimArgsF64 {
-    const PlantDev* plant;
-    double* xs;
-    const double* xu;
-    double* eePos;
-    int N, batch;
-    unsigned S;
-    double ss, toff, timestep;
-    double rem;
-};
-
-// One body text for both (sim_steps.inc, as kkt_knots.inc and merit_points.inc): the arithmetic between load and store is float64 in either.
-template <int INTEGRATOR = 0>
-__global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgs a) {
-    typedef float IO;
-#include "sim_steps.inc"
+// The arithmetic between load and store is float64 for either IO: only the loads (widened, or used as they are) and the stores (rounded once, or not at all)
+// depend on it.  INTEGRATOR: 0 explicit, 1 semi-implicit Euler ("sim_integrator").  (As for the KKT and merit kernels, a shared __device__ body was tried and changed the code.)
+template <typename IO, int INTEGRATOR = 0>
+__global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgsT<IO> a) {
+    typedef double R;
+    typedef KktLds<R>::vr kkt_lds_vd;
+    typedef KktLds<R>::item kkt_lds_item;
+    typedef PlantC<R>::creal creal;
+    constexpr int n = 2 * PJ, m = PJ;
+    __shared__ KktItemLds<R> sI[KKT_ITEMS];
+    __shared__ R sF[KKT_ITEMS][KKT_R0 * RN_ROWS];
+    static_assert(sizeof(KktItemLds<R>) * KKT_ITEMS + sizeof(R) * KKT_ITEMS * KKT_R0 * RN_ROWS <= 16384, "the merit kernel's LDS budget");
+    const int lane = threadIdx.x, gi = lane / KKT_GL, l = lane - gi * KKT_GL;
+    kkt_lds_item* I = (kkt_lds_item*)&sI[gi];
+    kkt_lds_vd* recs = (kkt_lds_vd*)&sF[gi][0];
+    kkt_lds_vd* fl = recs + (l < KKT_R0 ? l : 0) * RN_ROWS;
+    const PlantC<R> P{reinterpret_cast<creal*>(reinterpret_cast<unsigned long long>(a.plant))};
+    const long b0 = (long)blockIdx.x * KKT_ITEMS + gi;
+    const bool live = b0 < a.batch;                          // (a group without a trajectory recomputes the last one — it shares this wavefront — and writes nothing)
+    const size_t b = live ? (size_t)b0 : (size_t)a.batch - 1;
+    const IO* xu = a.xu + b * ((size_t)(n + m) * a.N - m);
+    IO* xs = a.xs + b * n;
+    const unsigned last = (unsigned)a.N - 2;                 // the last knot that has a control
+    auto knot_of = [&](double t) -> unsigned {               // (uint32)(t / timestep), clamped to the last control; one rounding per operation
+        const double v = __ddiv_rn(t, a.timestep);
+        return v >= (double)last ? last : (unsigned)v;
+    };
+    if (l < n) I->Xq[l] = (double)xs[l];
+    unsigned idx = knot_of(a.toff);
+    const unsigned steps = a.S + (a.rem != 0.0 ? 1u : 0u), rounds = steps + (a.eePos ? 1u : 0u);
+    for (unsigned k = 0; k < rounds; ++k) {
+        const bool step = k < steps;                         // the last round of a call with an end-effector output: the pose sweeps on the final state
+        double dt = a.rem;
+        if (k < a.S) { idx = knot_of(__dadd_rn(a.toff, __dmul_rn((double)k, a.ss))); dt = a.ss; }
+        if (l < m) {
+            if (step) I->U[l] = (double)xu[(size_t)idx * (n + m) + n + l];
+            double sn, cs;
+            kkt_sincos(I->Xq[l], sn, cs);
+            I->Sc[0][l] = sn;
+            I->Sc[1][l] = cs;
+        }
+        __syncthreads();
+        // ---- round 0 of the KKT kernel: lanes 0..6 ID(q, 0, e_l), lane 7 ID(q, qd, 0); in the pose round lanes 8..10 instead ----
+        if (l < KKT_R0 && (step ? l <= PJ : l > PJ)) {
+            R a6w[3], a6u[3];
+            RneaTask<R> t;
+            t.sj = -1; t.pj = -1; t.qdscale = (l == PJ) ? 1.0 : 0.0; t.knot_qdd = false; t.unit = l < PJ ? l : -1; t.base = l > PJ ? l - PJ - 1 : -1;
+            rnea<R>(P, fl, I, t, a6w, a6u);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) { fl[RN_AW + r] = a6w[r]; fl[RN_AU + r] = a6u[r]; }
+        }
+        __syncthreads();
+        if (step && l < PJ) {                                // lanes 0..6: qdd_l, then joint l's Euler step from the old values
+            const R qdd = plant_qdd_lane(recs, I, l);
+            const R q = I->Xq[l], qd = I->Xq[PJ + l];
+            if constexpr (INTEGRATOR == 1) {                 // semi-implicit Euler: the position moves with the NEW velocity
+                const R qdn = qd + dt * qdd;
+                I->Xq[l] = q + dt * qdn;
+                I->Xq[PJ + l] = qdn;
+            } else {
+            I->Xq[l] = q + dt * qd;
+            I->Xq[PJ + l] = qd + dt * qdd;
+            }
+        }
+        __syncthreads();
+    }
+    if (a.eePos && live && l < 3) {
+        R ee0, ee1, ee2;
+        plant_ee_pos(recs, ee0, ee1, ee2);
+        a.eePos[b * 3 + l] = (IO)(l == 0 ? ee0 : (l == 1 ? ee1 : ee2));
+    }
+    if (live && l < n) xs[l] = (IO)I->Xq[l];                // IO = float: the one rounding of the call; IO = double: the state as it is
 }
-template <int INTEGRATOR = 0>
-__global__ __launch_bounds__(KKT_THREADS, 2) void simulate_f64_kernel(SimArgsF64 a) {
-    typedef double IO;
-#include "sim_steps.inc"
-}
 
-struct AdvanceArgs {
-    float* xu; float* lambda; float* goal;                  // [batch][(n+m)N - m], [batch][n N], [batch][6 N] in/out
-    const float* xs;                                        // [batch][n]
-    const float* eePos;                                     // [batch][3] (shift = 1)
-    const float* xu_traj; const float* goal_traj;           // the plan: traj_steps rows of (n + m) / 6
+template <typename IO> struct AdvanceArgsT {                // IO = float: mpcg_advance_horizon; IO = double: mpcg_advance_horizon_f64
+    IO* xu; IO* lambda; IO* goal;                           // [batch][(n+m)N - m], [batch][n N], [batch][6 N] in/out
+    const IO* xs;                                           // [batch][n]
+    const IO* eePos;                                        // [batch][3] (shift = 1)
+    const IO* xu_traj; const IO* goal_traj;                 // the plan: traj_steps rows of (n + m) / 6
     int32_t* traj_offset; int32_t* done;                    // [batch] in/out
-    float* tracking_error;                                  // [batch] out
-    uint32_t n, m, N, traj_steps, traj_stride, lead, shift;
-};
-
-struct AdvanceArgsF64 {                                     // mpcg_advance_horizon_f64: the same fields with the arrays in double
-    double* xu; double* lambda; double* goal;
-    const double* xs;
-    const double* eePos;
-    const double* xu_traj; const double* goal_traj;
-    int32_t* traj_offset; int32_t* done;
-    double* tracking_error;
+    IO* tracking_error;                                     // [batch] out
     uint32_t n, m, N, traj_steps, traj_stride, lead, shift;
 };
 
@@ -177,13 +217,47 @@ __device__ __forceinline__ void advance_sweep(V* dst, const size_t count, F&& va
     }
 }
 
-__global__ __launch_bounds__(ADV_THREADS) void advance_horizon_kernel(AdvanceArgs a) {
-    typedef float IO;
-#include "sim_advance.inc"
-}
-__global__ __launch_bounds__(ADV_THREADS) void advance_horizon_f64_kernel(AdvanceArgsF64 a) {
-    typedef double IO;
-#include "sim_advance.inc"
+// Copies only, and the tracking error in IO (tracking_error_of: one rounding per operation).
+template <typename IO>
+__global__ __launch_bounds__(ADV_THREADS) void advance_horizon_kernel(AdvanceArgsT<IO> a) {
+    const size_t b = blockIdx.x;
+    const uint32_t n = a.n, m = a.m, N = a.N, nm = n + m, t = threadIdx.x;
+    const size_t len = (size_t)nm * N - m;
+    IO* xu = a.xu + b * len;
+    const IO* xs = a.xs + b * n;
+    if (a.done && a.done[b] != 0) return;                    // frozen (uniform; done is written behind the barriers below)
+    if (!a.shift) {                                          // mpcsim.cuh:348 alone
+        for (uint32_t e = t; e < n; e += ADV_THREADS) xu[e] = xs[e];
+        return;
+    }
+    IO* lam = a.lambda + b * (size_t)n * N;
+    IO* goal = a.goal + b * (size_t)6 * N;
+    const IO* xut = a.xu_traj + b * (size_t)a.traj_stride * nm;
+    const IO* gt = a.goal_traj + b * (size_t)a.traj_stride * 6;
+    const uint32_t off = (uint32_t)a.traj_offset[b] + 1;     // (:310; a value that is no row of the plan takes the else branch and reads the plan's last row)
+    const bool inside = off >= 1 && (uint64_t)off + N < a.traj_steps;    // (:314, :327)
+    IO err = 0;
+    if (t == 0) err = tracking_error_of(a.eePos + b * 3, goal);          // (:303-306) against knot 0 of the unshifted goals
+    // xu: x_0 from xs (:348, the last write of the reference); everything else below the last n + m elements from one knot up (just_shift: knots
+    // 0..N-3 whole, x_{N-2} <- x_{N-1} without a control, integrator.cuh:258-263); the last n + m elements u_{N-2}, x_{N-1} from the plan (:316) or
+    // the final plan position with zero velocity and zero control (:320-322).
+    advance_sweep(xu, len, [&](size_t e) -> IO {
+        if (e < n) return xs[e];
+        if (e + nm < len) return xu[e + nm];
+        const uint32_t r = (uint32_t)(e + nm - len);         // 0..m-1: u_{N-2}; m..m+n-1: x_{N-1}
+        if (inside) return xut[(size_t)nm * (off + a.lead) - m + r];
+        return r >= m && r - m < n / 2 ? xut[(size_t)(a.traj_steps - 1) * nm + (r - m)] : IO(0);
+    });
+    advance_sweep(goal, (size_t)6 * N, [&](size_t e) -> IO {         // (:326-334)
+        if (e + 6 < (size_t)6 * N) return goal[e + 6];
+        return gt[(size_t)(inside ? off + N - 1 : a.traj_steps - 1) * 6 + (e + 6 - (size_t)6 * N)];
+    });
+    advance_sweep(lam, (size_t)n * (N - 1), [&](size_t e) -> IO { return lam[e + n]; });         // the last knot of lambda keeps its value (:337-338)
+    if (t == 0) {
+        a.tracking_error[b] = err;
+        a.traj_offset[b] = (int32_t)off;
+        if (off >= a.traj_steps) a.done[b] = 1;              // (:252)
+    }
 }
 
 }  // namespace mpcg

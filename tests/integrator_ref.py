@@ -1,6 +1,6 @@
 """Float64 restatement of the SECOND integrator of the reference, semi-implicit (symplectic) Euler — INTEGRATOR_TYPE == 1 of include/common/integrator.cuh
 (:22-57 defect, :59-100 A and B, :103-130 step) — TEST INFRASTRUCTURE, the checker of options "integrator" and "sim_integrator" = 1
-(mpcgpu_amd/csrc/kkt_knots.inc, merit_points.inc, merit_plant_f32.hip.h, sim_steps.inc).  With qdd = FD(q, qd, u) as everywhere else (no gravity):
+(mpcgpu_amd/csrc/kkt_plant.hip.h, merit_plant.hip.h, merit_plant_f32.hip.h, sim_plant.hip.h).  With qdd = FD(q, qd, u) as everywhere else (no gravity):
 
     step     qd' = qd + dt qdd;  q' = q + dt qd'
     defect   c_{k+1} = x_{k+1} - [q + dt (qd + dt qdd); qd + dt qdd]          (c_0 = x_0 - x_s as before)

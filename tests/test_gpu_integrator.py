@@ -1,5 +1,5 @@
 """GPU: options "integrator" and "sim_integrator" = 1 — semi-implicit (symplectic) Euler, the reference's INTEGRATOR_TYPE == 1 (include/common/integrator.cuh),
-as a compile-time parameter of the KKT, merit and simulate kernels (mpcgpu_amd/csrc/kkt_knots.inc, merit_points.inc, merit_plant_f32.hip.h, sim_steps.inc) —
+as a compile-time parameter of the KKT, merit and simulate kernels (mpcgpu_amd/csrc/kkt_plant.hip.h, merit_plant.hip.h, merit_plant_f32.hip.h, sim_plant.hip.h) —
 against the float64 restatement tests/integrator_ref.py (pinned in tests/test_integrator_ref_cpu.py, which also shows that the cases here tell the two
 integrators apart by 100 x / 10 x their tolerances), across kernels (the merit measures the map the KKT kernel linearised; one simulated step is that map),
 in a hipGraph and in a closed SQP iteration; and both options at 0 set explicitly give the bits of a handle on which they were never set.

@@ -1,4 +1,4 @@
-"""GPU: mpcg_generate_kkt_f64 (mpcgpu_amd/csrc/kkt_plant.hip.h, kkt_knots.inc) — the KKT block assembly with double arrays in and out, the producer of
+"""GPU: mpcg_generate_kkt_f64 (mpcgpu_amd/csrc/kkt_plant.hip.h: generate_kkt_kernel with IO = double) — the KKT block assembly with double arrays in and out, the producer of
 mpcg_form_schur(_rhov)_f64.  The arithmetic is the float entry's (float64 inside): on float-representable inputs the outputs rounded to float ARE the
 float entry's bits; on genuinely double inputs nothing passes through float; against the float64 restatement oracle/iiwa_ref.py the arrays without a
 dynamics derivative agree far below the float entry's output rounding.  Bit-stability over the batch, inside a hipGraph, guard bands, errors, and the

@@ -1,4 +1,4 @@
-"""GPU: mpcg_compute_merit_f64, mpcg_line_search_step_f64 and mpcg_line_search_step_rho_f64 (mpcgpu_amd/csrc/merit_plant.hip.h, merit_points.inc) — the
+"""GPU: mpcg_compute_merit_f64, mpcg_line_search_step_f64 and mpcg_line_search_step_rho_f64 (mpcgpu_amd/csrc/merit_plant.hip.h: merit_points_kernel, merit_sum_kernel and line_search_step_kernel in double) — the
 double consumers behind mpcg_compute_dz_f64.  The merit: the float entry's arithmetic bit for bit where the float trial iterate is exact; against
 tests/merit_ref.py::merit_at at the correctly rounded double trial iterate (tests/merit_ref_f64.py); the accepted merit is the merit of the new
 iterate; bit-stability.  The step and the rho rule: tests/rho_ref_f64.py bit for bit.  The closed loop: one whole batched adaptive SQP iteration in

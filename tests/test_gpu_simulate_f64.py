@@ -1,4 +1,4 @@
-"""GPU: mpcg_simulate_f64 and mpcg_advance_horizon_f64 (mpcgpu_amd/csrc/sim_plant.hip.h, sim_steps.inc, sim_advance.inc) — the step between two SQP
+"""GPU: mpcg_simulate_f64 and mpcg_advance_horizon_f64 (mpcgpu_amd/csrc/sim_plant.hip.h: simulate_kernel and advance_horizon_kernel with IO = double) — the step between two SQP
 solves with double arrays in and out, which closes the double MPC loop on the device.  The arithmetic is the float entries' (float64 inside): on
 float-representable inputs and a shared substep schedule the outputs rounded to float ARE the float entry's bits; on genuinely double inputs nothing
 passes through float; against the float64 restatement tests/sim_ref_f64.py (pinned in tests/test_sim_ref_f64_cpu.py) and against the double KKT

@@ -2,9 +2,10 @@
 """Device-code identity of two builds of the library: disassembles every gfx950 code object of both (as disasm_kernel.py does) and compares
 the instruction text per demangled kernel name, addresses and absolute branch targets stripped.  Prints the kernels that differ, were
 added or were removed; exit status 1 if a kernel present in both differs.  A kernel that changed its NAME between the builds (it became a
-template, say) is compared as a pair with --rename 'OLD NAME=NEW NAME' (demangled, as printed under removed / added; repeatable).
+template, say) is compared as a pair with --rename 'OLD NAME=NEW NAME' (demangled, as printed under removed / added; repeatable), or with
+--rename-file FILE holding one such pair per line.
 --opcodes: under each kernel that differs, the opcodes whose counts changed (old -> new; DPP forms counted apart, as opcode_dpp).
-   python tools/_prof/diff_kernels.py old/libmpcg_hip.so new/libmpcg_hip.so [--opcodes] [--rename 'old=new' ...]"""
+   python tools/_prof/diff_kernels.py old/libmpcg_hip.so new/libmpcg_hip.so [--opcodes] [--rename 'old=new' ...] [--rename-file pairs.txt]"""
 import collections, os, re, shutil, subprocess, sys, tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 
@@ -44,12 +45,17 @@ def opcodes(ins):
 
 
 old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+pairs = []
 for i, a in enumerate(sys.argv):
     if a == "--rename":
-        o, _, nw = sys.argv[i + 1].partition("=")
-        assert o in old and nw in new and nw not in old, "no such pair of kernels: " + sys.argv[i + 1]
-        old[nw] = old.pop(o)
-        print(f"compared as one kernel: {o}  ->  {nw}")
+        pairs.append(sys.argv[i + 1])
+    if a == "--rename-file":                                      # one OLD NAME=NEW NAME per line
+        pairs += [l.strip() for l in open(sys.argv[i + 1]) if l.strip()]
+for pair in pairs:
+    o, _, nw = pair.partition("=")
+    assert o in old and nw in new and nw not in old, "no such pair of kernels: " + pair
+    old[nw] = old.pop(o)
+    print(f"compared as one kernel: {o}  ->  {nw}")
 common = sorted(set(old) & set(new))
 differ = [k for k in common if old[k] != new[k]]
 for title, names in (("removed", sorted(set(old) - set(new))), ("added", sorted(set(new) - set(old))), ("DIFFER", differ)):
