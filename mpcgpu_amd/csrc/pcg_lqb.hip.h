@@ -27,8 +27,12 @@
 // Inner product without the assembled vector, from the partial sums themselves (no weights, no duplicates): x^T M x = sum over lanes of
 // x_k[piece g] . (ypart + its L part) — the coupling term x_{k-1}^T (L^T x_k) taken as x_k^T (L x_{k-1}) from the direct product.
 // Block-Jacobi (Pinv without off-diagonal blocks) is a build of its own, PC3 = false: no L sub-block of Pinv in registers, no z, a shorter epilogue.
-// Measured (steady clocks, tools/_prof/lqb_ab.py; lane-pair kernel in brackets): N = 128 SS 1.49 (1.62) us per iteration of one trajectory, 5.98 (6.54) per
-// 1024 — 1.58 and 6.32 before the stage priorities (LQB_PHASE below); block-Jacobi 1.21 (1.35), 4.86 (5.52) per 1024; N = 64, two independent workgroups
+// Stage order of a pass: transposed -> direct L -> direct D -> epilogue (wavefront sum of the inner-product share, y / z merged, stores) -> barrier;
+// in the 128-knot SS build: direct L -> direct D -> wavefront sum and merged y, stored -> transposed -> merged z, stored -> barrier (lqb_merge_z
+// below), all matrix pairs in registers.  alpha and beta stay in VGPRs (every lane forms them from the same LDS words with the same operations) and
+// are the op_sel-broadcast operand of the rebuild's packed FMAs; v_readfirstlane only where a branch needs an SGPR: the exit test.
+// Measured (steady clocks, tools/_prof/lqb_ab.py; lane-pair kernel in brackets): N = 128 SS 1.46 (1.65) us per iteration of one trajectory, 5.81 (6.85) per
+// 1024 — 1.58 and 6.32 before the stage priorities (LQB_PHASE below), 1.48 and 5.96 before the split epilogue and the VGPR scalars; block-Jacobi 1.21 (1.35), 4.86 (5.52) per 1024; N = 64, two independent workgroups
 // per CU: 1.02 (1.44), 2.98 (3.71); DESIGN.md §3.2b for where an iteration goes.
 //
 // Reads only the left + diagonal block columns (include/mpcg.h, BLOCK SYMMETRY), like the lane-pair kernel; same PCG, same exit rule, same
@@ -181,10 +185,13 @@ __device__ __forceinline__ void lqb_load_blocks_lds(rsrc_t MS, rsrc_t MP, int kf
 #ifndef LQB_NPARK
 #define LQB_NPARK 6      // pairs of each matrix's diagonal sub-block parked in LDS (lane-private slots inside the wavefront's second load tile, idle after the load)
 #endif
+#ifndef LQB_NPARK_SPLIT
+#define LQB_NPARK_SPLIT 0    // the same for the 128-knot SS build, whose stage order keeps z out of the direct stages: none needed (254 VGPRs, no scratch)
+#endif
 #ifndef LQB_NPARK_J
 #define LQB_NPARK_J 0    // the same for the block-Jacobi build: none — it carries no off-diagonal Pinv sub-block (214 VGPRs); 0 / 3 / 6 parked: 1.287 / 1.295 / 1.319 us per iteration at N = 128
 #endif
-static_assert(LQB_NPARK >= 0 && LQB_NPARK <= 6 && LQB_NPARK_J >= 0 && LQB_NPARK_J <= 6, "2 x NPARK x 512 B must fit the wavefront's 6,272-byte tile");
+static_assert(LQB_NPARK >= 0 && LQB_NPARK <= 6 && LQB_NPARK_SPLIT >= 0 && LQB_NPARK_SPLIT <= 6 && LQB_NPARK_J >= 0 && LQB_NPARK_J <= 6, "2 x NPARK x 512 B must fit the wavefront's 6,272-byte tile");
 // x + y of a pair as ONE scalar add (left to the compiler, neighbouring horizontal sums are "vectorised": three moves + a packed add per two)
 __device__ __forceinline__ float lqb_hsum(f2 v) {
     float r;
@@ -240,8 +247,34 @@ __device__ __forceinline__ void lqb_epilogue(float& part, LqbPiece& fin, const L
           "s"(diag));                                                                                    // 29
     fin.p[0] = f2{k0, k1}; fin.p[1] = f2{k2, k3}; fin.p[2] = f2{k4, k5}; fin.s = k6;
 }
-// The same for a block-Jacobi Pinv pass (no off-diagonal blocks: nothing for knot k-1, z stays zero): the wavefront sum interleaved with the seven merge
-// adds of y — the lanes h == g publish, the others have nothing to select or send.  16 instructions instead of 27.
+// The same epilogue cut in TWO, with the transposed product between the halves: the 128-knot SS build (SPLIT in the kernel).  Neither the wavefront
+// sum of `part` nor the merged y depends on z, so both leave in front of the transposed product and their LDS stores fly under its FMAs:
+//   * block A is lqb_epilogue_y below (the block-Jacobi Pinv pass ends with the same block): the wavefront sum, and between its steps the seven
+//     merge adds t1 = y + (y of quad lane [1,3,0,2]);
+//   * block B, lqb_merge_z, behind the transposed product: t2 = z + (z of quad lane [1,3,0,2]), seven adds.
+// The receiver of quad_perm [1,3,0,2] wants the sender's y where it is a lane h == g and the sender's z where it is not, so t1 is what a lane
+// h == g publishes and t2 what a lane h != g publishes: each is stored by its lanes under an EXEC mask (SALU only), and the 14 v_cndmask go.
+// IEEE addition is commutative, so t1 / t2 carry the bits of lqb_epilogue's keep + send.  Behind the last FMA of the pass: seven adds and the
+// h != g lanes' stores instead of 27 instructions and all stores.  z is no longer live across the direct stages, which is what lets this build
+// keep every matrix pair in registers (LQB_NPARK_SPLIT = 0: 12 LDS reads less per pass; with 6 / 3 pairs parked this order is 12 / 7 % SLOWER
+// than the one-block order, with none 0.9 % faster: DESIGN.md §3.2b).  Not for the 64- / 32-knot builds and the block-Jacobi build's S pass:
+// measured there, this order costs 7-10 % and 3 % (no barrier partner's FMAs to hide under / nothing parked to win back).
+__device__ __forceinline__ void lqb_merge_z(LqbPiece& fin, const LqbPiece& z) {
+    float k0, k1, k2, k3, k4, k5, k6;
+    asm volatile(
+        "v_add_f32_dpp %0, %7, %7 quad_perm:[1,3,0,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_add_f32_dpp %1, %8, %8 quad_perm:[1,3,0,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_add_f32_dpp %2, %9, %9 quad_perm:[1,3,0,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_add_f32_dpp %3, %10, %10 quad_perm:[1,3,0,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_add_f32_dpp %4, %11, %11 quad_perm:[1,3,0,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_add_f32_dpp %5, %12, %12 quad_perm:[1,3,0,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_add_f32_dpp %6, %13, %13 quad_perm:[1,3,0,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "=&v"(k0), "=&v"(k1), "=&v"(k2), "=&v"(k3), "=&v"(k4), "=&v"(k5), "=&v"(k6)
+        : "v"(z.p[0].x), "v"(z.p[0].y), "v"(z.p[1].x), "v"(z.p[1].y), "v"(z.p[2].x), "v"(z.p[2].y), "v"(z.s));
+    fin.p[0] = f2{k0, k1}; fin.p[1] = f2{k2, k3}; fin.p[2] = f2{k4, k5}; fin.s = k6;
+}
+// Block A of the split epilogue; the whole epilogue of a block-Jacobi Pinv pass (no off-diagonal blocks: nothing for knot k-1, z stays zero): the wavefront sum
+// interleaved with the seven merge adds of y — the lanes h == g publish.  16 instructions.
 __device__ __forceinline__ void lqb_epilogue_y(float& part, LqbPiece& fin, const LqbPiece& y) {
     float k0, k1, k2, k3, k4, k5, k6;
     asm volatile(
@@ -276,9 +309,10 @@ __device__ __forceinline__ void lqb_epilogue_y(float& part, LqbPiece& fin, const
 // Issue priority by the work a wavefront has LEFT in its pass (128 knots: the two wavefronts of a SIMD belong to ONE trajectory and meet at the same
 // barrier).  The SIMD arbitrates by age: left alone, the older wavefront wins every packed-FMA slot, is done with its whole pass first, and the younger
 // one runs what is left of its FMAs and its epilogue ALONE, at one instruction per 4 clocks, half of the VALU pipe idle — 200 clocks per pass in front
-// of the barrier.  With s_setprio 3 / 2 / 1 / 0 at the transposed product / direct L / direct D / epilogue the wavefront that is BEHIND wins the slot:
-// the lead changes hands at every stage, the two are never further apart than one stage, and the epilogue of one co-issues with the last FMAs of
-// the other.  No value changes (same instructions, same operands: tests/test_gpu_lqb_bits.py).  __builtin_amdgcn_sched_barrier keeps a stage's
+// of the barrier.  With s_setprio 3 / 2 / 1 / 0 at the transposed product / direct L / direct D / epilogue (block-Jacobi build) or at direct L / direct D
+// and block A / the transposed product / block B and the last stores (SS build, split epilogue) — monotone in the work that is left either way —
+// the wavefront that is BEHIND wins the slot: the lead changes hands at every stage, the two are never further apart than one stage, and the
+// tail of one co-issues with the last FMAs of the other.  No value changes (same instructions, same operands: tests/test_gpu_lqb_bits.py).  __builtin_amdgcn_sched_barrier keeps a stage's
 // instructions on their side of the s_setprio (it is no scheduling boundary of its own).  N = 128 SS batch 1024: 6.32 -> 5.98 us per iteration,
 // block-Jacobi 5.06 -> 4.86 (tools/_prof/lqb_ab.py; profiles/r08_lqb_ab.txt).  Not at 64 / 32 knots: the wavefronts of a SIMD are independent
 // workgroups there, no barrier joins them.
@@ -287,6 +321,7 @@ template <int NMAXQ, bool PC3>
 __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
     typedef LqbLds<NMAXQ> L;
     constexpr int NW = L::NW, NTHR = NW * 64;
+    constexpr bool SPLIT = NW == 8 && PC3;                     // the split epilogue (lqb_merge_z above): the 128-knot SS build
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int N = a.N;
     const int tid = threadIdx.x;
@@ -349,7 +384,7 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
     // registers + the working set of a pass only just, and what the compiler spills goes to SCRATCH, reloaded in every pass (pcg_lpk.hip.h).
     // The slots live in this wavefront's own second load tile, idle from here on.
     f2* const parkS = reinterpret_cast<f2*>(lds + L::TILE2 + w * LPK_TILE_FLOATS) + lane;
-    constexpr int NPK = PC3 ? LQB_NPARK : LQB_NPARK_J;
+    constexpr int NPK = PC3 ? (SPLIT ? LQB_NPARK_SPLIT : LQB_NPARK) : LQB_NPARK_J;
     f2* const parkP = parkS + NPK * 64;
 #pragma unroll
     for (int i = 0; i < NPK; ++i) {
@@ -412,19 +447,21 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
 
     // One pass of matrix (D, L) over the operand whose carried piece is `mine`: publishes y / z to TOUT / TOUT + VS, the wave's share of x^T M x
     // to red[w].  hasL: wave-uniform (block-Jacobi's Pinv has no off-diagonal blocks).  `park`: this matrix's pairs parked in LDS.
-    // Order (register budget): transposed product in two column groups -> direct L (x_{k-1}) -> direct D (x_k), the parked pairs last.
+    // Order: transposed product in two column groups -> direct L (x_{k-1}) -> direct D (x_k), the parked pairs last -> the one-block epilogue.
+    // Order of the 128-knot SS build (SPLIT): direct L -> direct D -> `part`, its wavefront sum and the merged y (block A), stored at once ->
+    // transposed product -> merged z (block B) and its stores: nothing of the fold or of y waits for the transposed product, which feeds
+    // neither, and z is not live across the direct stages.  Every accumulator sums in the same order either way: same bits.
     // The coupling term of the inner product comes from the DIRECT product: x_{k-1}^T (L^T x_k) = x_k^T (L x_{k-1}), so that x_{k-1}'s piece is
     // dead once the L columns are done: x^T M x = sum x_k[piece g] . (ypart + L-part of ypart).
     auto pass = [&](auto hasl_tag, const LqbSub& D, const LqbSub& Lb, const LqbPiece& mine, int TOUT, float* red, const f2* park, int pb) {
         constexpr bool hasL = decltype(hasl_tag)::value;
+        constexpr bool TAIL = hasL && SPLIT;
         LQB_PHASE(3);
         const LqbPiece xg = lqb_quad<LQB_QP_XG>(mine);
         MPCG_STAMP(pb + 1);
-        LqbPiece ypart, zpart;
-        f2 acc[3], dd;
-        float y6, ds;
-        if constexpr (hasL) {
-            // transposed: zpart[piece h] = L^T x_k[piece g]
+        // transposed: zpart[piece h] = L^T x_k[piece g]
+        auto transposed = [&]() -> LqbPiece {
+            LqbPiece zpart;
             const f2 xs = f2{xg.s, xg.s};
             {
                 f2 zt[4];
@@ -448,8 +485,17 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
                 zpart.p[2] = __builtin_elementwise_fma(Lb.B[2], xs, f2{lqb_hsum(zt[0]), lqb_hsum(zt[1])});
                 zpart.s = fmaf(Lb.e, xg.s, lqb_hsum(zt[2]));
             }
+            return zpart;
+        };
+        LqbPiece ypart, zpart;
+        f2 acc[3], dd;
+        float y6, ds;
+        if constexpr (hasL) {
+            if constexpr (!TAIL) {
+                zpart = transposed();
+                LQB_PHASE(2);
+            }
             // direct, off-diagonal block: L x_{k-1}[piece h]
-            LQB_PHASE(2);
             const LqbPiece xm = lqb_quad<LQB_QP_XM>(mine);
 #pragma unroll
             for (int rp = 0; rp < 3; ++rp) acc[rp] = Lb.A[rp][0] * bc(xm, std::integral_constant<int, 0>{});
@@ -474,7 +520,7 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
             y6 = 0.f; ds = 0.f; dd = f2{0.f, 0.f}; zpart.s = 0.f;
         }
         // direct, diagonal block: D x_k[piece h]; the pairs parked in LDS are requested here (volatile: in program order) and used last
-        LQB_PHASE(1);
+        LQB_PHASE(TAIL ? 2 : 1);
         const LqbPiece xh = lqb_quad<LQB_QP_XH>(mine);
         f2 pk_[NPK > 0 ? NPK : 1];
 #pragma unroll
@@ -499,17 +545,31 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
         dd = __builtin_elementwise_fma(ypart.p[1], xg.p[1], dd);
         dd = __builtin_elementwise_fma(ypart.p[2], xg.p[2], dd);
         MPCG_STAMP(pb + 2);
-        LQB_PHASE(0);
+        if constexpr (!TAIL) LQB_PHASE(0);
         float part = fmaf(ypart.s, xg.s, ds) + lqb_hsum(dd);
         LqbPiece fin;
-        if constexpr (hasL) lqb_epilogue(part, fin, ypart, zpart, diag_mask);
-        else lqb_epilogue_y(part, fin, ypart);
-        if (lane == 63) red[w] = part;
-        if (hasL || diag) {                                  // (block-Jacobi: the z vector stays at its zeros)
-            float* out = lds + TOUT;
+        float* out = lds + TOUT;
+        auto publish = [&]() {                                   // (ob, os: T for the lanes h == g, Z = T + VS for the others)
 #pragma unroll
             for (int rp = 0; rp < 3; ++rp) *reinterpret_cast<f2*>(out + ob + K2 * rp) = fin.p[rp];
             out[os] = fin.s;
+        };
+        if constexpr (TAIL) {
+            // block A: the wave's share of x^T M x and the merged y, on their way to LDS in front of the transposed product
+            lqb_epilogue_y(part, fin, ypart);
+            if (lane == 63) red[w] = part;
+            if (diag) publish();
+            LQB_PHASE(1);
+            zpart = transposed();
+            // block B: the merged z
+            LQB_PHASE(0);
+            lqb_merge_z(fin, zpart);
+            if (!diag) publish();
+        } else {
+            if constexpr (hasL) lqb_epilogue(part, fin, ypart, zpart, diag_mask);
+            else lqb_epilogue_y(part, fin, ypart);
+            if (lane == 63) red[w] = part;
+            if (hasL || diag) publish();                         // (block-Jacobi: the z vector stays at its zeros)
         }
         MPCG_STAMP(pb + 3);
     };
@@ -560,7 +620,9 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
             rd = load_red(red_v);
             f = fetch(L::US);                                   // (the operand loads fly during the scalar chain)
             // alpha = eta / v ; lambda += alpha p ; r -= alpha upsilon ; r~ = Pinv r ; eta' = r . r~
-            const float alpha = uniform(eta / sum_red(rd));    // (IEEE division: 75 clocks of the chain, measured by ablation; the reciprocal forms were slower, see above)
+            // (IEEE division: 75 clocks of the chain, measured by ablation; the reciprocal forms were slower, see above.  alpha and beta stay VGPRs, the same
+            //  bits in every lane: no v_readfirstlane + s_nop at the end of either chain, and beta's division runs beside the exit test's SGPR round trip)
+            const float alpha = eta / sum_red(rd);
 #pragma unroll
             for (int i = 0; i < 3; ++i) lam.p[i] = lam.p[i] + alpha * pv.p[i];
             lam.s = lam.s + alpha * pv.s;
@@ -572,10 +634,11 @@ __global__ __launch_bounds__(NMAXQ * 4, 2) void pcg_lqb_kernel(PcgArgs a) {
             rd = load_red(red_e);
             f = fetch(L::RT);
             // eta' ; exit test ; beta
-            const float eta_new = uniform(sum_red(rd));
+            const float eta_new_v = sum_red(rd);
+            const float eta_new = uniform(eta_new_v);
             iters = (uint32_t)(it + 1);
             if (fabsf(eta_new) < a.exit_tol) { max_iter_exit = 0; p_pending = false; break; }     // (the reference leaves p as it is on this exit)
-            beta = uniform(eta_new / eta);
+            beta = eta_new_v / eta;
             eta = eta_new;
             MPCG_STAMP(10);
         }

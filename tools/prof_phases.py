@@ -38,7 +38,7 @@ LPK_NAMES = ["S transp", "S direct", "S merge+dot", "(to barrier)", "barrier A",
              "P transp", "P direct", "P merge+dot", "(to barrier)", "barrier C", "eta+p upd", "barrier D"]
 for spec in args.cfg or ["4:7:-1"]:
     f = [int(x) for x in spec.split(":")] if spec not in ("lpk", "lqb") else [4 if N <= 64 else 8]
-    if spec == "lqb":     # float lane-quad kernel: every wave runs both passes.  0 iteration start | 1 operand in place | 2 FMAs done | 3 published | 4 past barrier A | 5 alpha known | 6 operand | 7 FMAs done | 8 published | 9 past barrier C
+    if spec == "lqb":     # float lane-quad kernel: every wave runs both passes.  0 iteration start | 1 operand in place | 2 direct FMAs done (128-knot SS build: the wavefront sum, the y stores and the transposed product follow) | 3 published | 4 past barrier A | 5 alpha known | 6 operand | 7 FMAs done | 8 published | 9 past barrier C
         f = [8 if N > 64 else 4 if N > 32 else 2]
         NAMES = ["rebuild p", "S FMAs", "S epilogue", "barrier A", "alpha", "rebuild r", "P FMAs", "P epilogue", "barrier C", "beta"] + ["-"] * 5
         sol.set_option("pcg_lpk", 1); sol.set_option("pcg_lqb", 1); sol.set_option("assume_symmetric", 1)
