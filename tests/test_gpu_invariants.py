@@ -14,33 +14,29 @@ states, with S / Pinv / gamma promoted to float64 and nothing but textbook preco
   conjugacy | p_K' S p_{K-1} | / sqrt((p_K' S p_K)(p_{K-1}' S p_{K-1})) <= 2e-3 (local conjugacy survives finite precision);
   orthogonality  | r_K' Pinv r_{K-1} | / sqrt(eta_K eta_{K-1}) <= 2e-3.
 
-K = 10, 50, 167 for N = 32 (row-per-lane kernel), 128 (lane-pair kernel), 512 (clustered kernel); symmetric-stair and block-Jacobi Pinv."""
+K = 10, 50, 167 for N = 32 (row-per-lane kernel), 128 (lane-pair kernel), 512 (clustered kernel); symmetric-stair and block-Jacobi Pinv.
+The "jacobi" parameter is block-Jacobi DATA (zeros in the off-diagonal blocks of Pinv) through the symmetric-stair builds: the 12-argument
+entries always apply three columns of Pinv.  The block-Jacobi builds proper are reached only by the batched entries: tests/test_gpu_first_steps.py.
+
+test_one_step_at_ragged_horizons and its double twin run the same checks over tests/pcg_step_cases.py: horizons that are no multiple of a
+kernel's knots per wavefront or workgroup, every family and workgroup width the launch plan has, state sizes other than 14, K from 1 upwards
+(K by the rule of that module), and the K = 0 state — max_iter = 0 returns 0 iterations, exit flag 1, lambda0 bit for bit, d_r = gamma - S lambda0
+and d_p = Pinv d_r, each compared directly with its float64 evaluation in the "r" / "p" scalings.  The checkers themselves:
+tests/pcg_step_model.py, pinned without a GPU by tests/test_pcg_step_model_cpu.py."""
 import numpy as np
 import pytest
 import torch
 
+import pcg_step_cases as cases
 from mpcgpu_amd import synth
+from pcg_step_model import EPS32, HP, LIMITS, initial_state_quantities, step_quantities
 
 pytestmark = pytest.mark.gpu
 n = 14
-EPS32 = 2.0 ** -24
-
-
-HP = [np.float64]          # the host's evaluation precision: float64 for the float kernels, the x87 80-bit long double for the double kernels
-
-
-def bt_matvec(M, x, N):
-    """Block-tridiagonal product from the bd layout in HP[0] precision (numpy): y_k = M[k,0] x_{k-1} + M[k,1] x_k + M[k,2] x_{k+1}, blocks column-major."""
-    B = np.nan_to_num(np.asarray(M, HP[0])).reshape(N, 3, n, n).transpose(0, 1, 3, 2)       # [k][col] as row-major matrices
-    X = np.asarray(x, HP[0]).reshape(N, n)
-    y = np.einsum("kij,kj->ki", B[:, 1], X)
-    y[1:] += np.einsum("kij,kj->ki", B[1:, 0], X[:-1])
-    y[:-1] += np.einsum("kij,kj->ki", B[:-1, 2], X[1:])
-    return y.reshape(-1)
 
 
 def state(sol, dS, dP, dg, lam0, K):
-    N = sol.N
+    N, n = sol.N, sol.n
     dt = dS.dtype                                          # float32, or float64 = linsys_t double (the same checks at u = 2^-53)
     d_lam = torch.from_numpy(lam0.copy()).cuda()
     d_r = torch.full((n * N,), float("nan"), device="cuda", dtype=dt)
@@ -54,51 +50,6 @@ def state(sol, dS, dP, dg, lam0, K):
     out = [t.cpu().numpy().astype(HP[0]) for t in (d_lam, d_r, d_p)]
     assert all(np.isfinite(v).all() for v in out)
     return out
-
-
-def abs_matvec(M, x, N):
-    """|M| |x|: the size of the terms a float32 evaluation of M x rounds (cancellation inside the three-block sums shows here, not in |M x|)."""
-    return bt_matvec(np.abs(np.nan_to_num(M)), np.abs(x), N)
-
-
-def step_quantities(S, P, g, lam0, st_a, st_b, N, K, EPS32=EPS32):
-    """Every checked quantity DIVIDED BY the scale its float32 rounding model gives it (u = 2^-24): a correct kernel lands at O(1..30)
-    whatever N, K, the preconditioner or the conditioning; tools/_prof/inv_probe.py prints them for 96 (system, K) pairs."""
-    (lam_a, r_a, p_a), (lam_b, r_b, p_b) = st_a, st_b
-    inf = lambda x: np.abs(x).max()
-    Sp, z_a, z_b = bt_matvec(S, p_a, N), bt_matvec(P, r_a, N), bt_matvec(P, r_b, N)
-    eta_a, eta_b, v = r_a @ z_a, r_b @ z_b, p_a @ Sp
-    assert eta_a < 0 and eta_b < 0 and v < 0             # S and Pinv are stored negated (include/pcg/linsys_setup.cuh:15-19): eta = r' Pinv r < 0
-    alpha, beta = eta_a / v, eta_b / eta_a
-    # what the kernel itself used, recovered from its own updates (least squares along p_{K-1})
-    alpha_hat = ((lam_b - lam_a) @ p_a) / (p_a @ p_a)
-    beta_hat = ((p_b - z_b) @ p_a) / (p_a @ p_a)
-    # cancellation of the three inner products: sum |terms| / |sum|
-    c_eta_a = (np.abs(r_a) @ abs_matvec(P, r_a, N)) / abs(eta_a)
-    c_eta_b = (np.abs(r_b) @ abs_matvec(P, r_b, N)) / abs(eta_b)
-    c_v = (np.abs(p_a) @ abs_matvec(S, p_a, N)) / abs(v)
-    q = {
-        # the update directions, with the kernel's own scalars: pure axpy / matvec rounding
-        "lam": inf(lam_b - (lam_a + alpha_hat * p_a)) / (EPS32 * (inf(lam_b) + abs(alpha_hat) * inf(p_a))),
-        "r": inf(r_b - (r_a - alpha_hat * Sp)) / (EPS32 * (inf(r_a) + abs(alpha_hat) * inf(abs_matvec(S, p_a, N)))),
-        "p": inf(p_b - (z_b + beta_hat * p_a)) / (EPS32 * (inf(abs_matvec(P, r_b, N)) + abs(beta_hat) * inf(p_a))),
-        # the scalars: float32 inner products of ~14 N terms against their float64 values, scaled by the cancellation of the sums
-        "alpha": abs(alpha_hat / alpha - 1) / (EPS32 * (c_eta_a + c_v)),
-        "beta": abs(beta_hat / beta - 1) / (EPS32 * (c_eta_a + c_eta_b)),
-    }
-    Snorm = float(np.abs(np.nan_to_num(S).astype(np.float64).reshape(N, 3, n, n)).sum(axis=(1, 2)).max())      # ||S||_inf (a block row's three blocks, summed along rows)
-    true_r = g.astype(HP[0]) - bt_matvec(S, lam_b, N)
-    nrm = lambda x: float(np.sqrt(float(x @ x)))
-    q["gap"] = nrm(r_b - true_r) / (K * EPS32 * Snorm * max(nrm(lam_b), nrm(np.asarray(lam0, HP[0]))))
-    q["conjugacy"] = abs(p_b @ Sp) / np.sqrt((p_b @ bt_matvec(S, p_b, N)) * v)
-    q["orthogonality"] = abs(r_b @ z_a) / np.sqrt(eta_a * eta_b)
-    return {k_: float(v_) for k_, v_ in q.items()}
-
-
-# Worst over 96 (system, K) pairs on an MI355X (tools/_prof/inv_probe.py -> profiles/r05_invariants.txt): lam 0.89 u, r 1.67 u, p 0.95 u of their update's
-# terms; alpha 0.57, beta 1.26 u x the cancellation of their inner products; gap 0.30 of K u ||S|| ||lambda||; conjugacy 1.7e-4, orthogonality 3.4e-4.
-# The limits leave a factor 4-6: an error of a few float32 ulps in ONE update of ONE iteration fails.
-LIMITS = {"lam": 4.0, "r": 8.0, "p": 8.0, "alpha": 8.0, "beta": 8.0, "gap": 2.0, "conjugacy": 2e-3, "orthogonality": 2e-3}
 
 
 @pytest.mark.parametrize("N,family", [(32, 5), (64, 11), (128, 11), (128, 6), (512, 7)])
@@ -161,3 +112,58 @@ def _double_invariants(sol, dS, dP, dg, S, P, g, lam0, N, family, pc, U64):
         for key, lim in LIMITS.items():
             scale = 1.0 if key in ("lam", "r", "p", "alpha", "beta", "gap") else 2.0 ** -29      # (conjugacy / orthogonality scale with u: float32's limit x 2^-29)
             assert q[key] <= lim * scale, (N, pc, K, key, q[key], lim * scale)
+
+
+def ragged_one_step(r, u):
+    """One row of tests/pcg_step_cases.py through the 12-argument entry (trajectory 0): the launch, the K = 0 state, then one step at every K."""
+    from mpcgpu_amd import PcgSolver
+    S, P, g, lam0 = (np.array(a[0]) for a in cases.three_column_matrices(r))
+    Sh, Ph = (a[0] for a in cases.host_matrices(r)[:2])   # (the host side: the never-read slots as zeros, the matrices as the row's kernel applies them)
+    sol = PcgSolver(r.N, max_batch=1, state_size=r.n)
+    for key, value in r.opts:
+        sol.set_option(key, value)
+    dS, dP, dg = (torch.from_numpy(a).cuda() for a in (S, P, g))
+    scale = lambda key: 1.0 if u == EPS32 or key not in ("conjugacy", "orthogonality") else 2.0 ** -29      # (as the double test above)
+    tag = cases.row_id(r)
+
+    def launched():
+        assert sol.get_option("last_kernel_family") == r.family and sol.get_option("last_kernel_waves") == r.waves, \
+            (tag, sol.get_option("last_kernel_family"), sol.get_option("last_kernel_waves"))
+        if r.family in cases.CLUSTERED:
+            assert sol.get_option("cluster_fixups") == 0, tag
+
+    st = {0: state(sol, dS, dP, dg, lam0, 0)}             # (state() asserts iters = K and the exit flag)
+    launched()
+    same = np.array_equal(st[0][0], lam0.astype(HP[0])) and np.array_equal(np.signbit(st[0][0]), np.signbit(lam0))     # (the widening is exact)
+    assert same, (tag, "max_iter = 0 must hand lambda0 back bit for bit")
+    q0 = initial_state_quantities(Sh, Ph, g, lam0, st[0][1], st[0][2], r.N, r.n, "ss", u)
+    print(f"{tag} K=0: " + " ".join(f"{a} {b:.2g}" for a, b in q0.items()))
+    for key, v in q0.items():
+        assert v <= LIMITS[key], (tag, "K = 0", key, v, LIMITS[key])
+    for K in cases.ks(r, 0)[1]:
+        for k_ in (K - 1, K):
+            if k_ not in st:
+                st[k_] = state(sol, dS, dP, dg, lam0, k_)
+                launched()
+        q = step_quantities(Sh, Ph, g, lam0, st[K - 1], st[K], r.N, K, EPS32=u, n=r.n)
+        print(f"{tag} K={K}: " + " ".join(f"{a} {b:.2g}" for a, b in q.items()))
+        for key, lim in LIMITS.items():
+            assert q[key] <= lim * scale(key), (tag, K, key, q[key], lim * scale(key))
+
+
+@pytest.mark.parametrize("r", cases.ROWS32, ids=cases.row_id)
+def test_one_step_at_ragged_horizons(r):
+    """Float rows.  Worst values per family on an MI355X: profiles/pcg_step_model.txt."""
+    ragged_one_step(r, EPS32)
+
+
+@pytest.mark.parametrize("r", cases.ROWS64, ids=cases.row_id)
+def test_one_step_at_ragged_horizons_in_double(r):
+    """Double rows, u = 2^-53, the host in long double; conjugacy and orthogonality at float32's limit x 2^-29 as above."""
+    if np.finfo(np.longdouble).eps > 2.0 ** -60:
+        pytest.skip("no extended-precision long double on this host")
+    HP[0] = np.longdouble
+    try:
+        ragged_one_step(r, 2.0 ** -53)
+    finally:
+        HP[0] = np.float64
