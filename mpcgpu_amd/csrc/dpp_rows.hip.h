@@ -2,8 +2,8 @@
 // row holds ROW r of every 14x14 operand in registers, and what another row needs from row t of an operand is a `row_newbcast:t` DPP source
 // modifier on the multiply (verified on the chip: tools/_prof/dpp_probe.hip).  Used by the block-tridiagonal direct solver
 // (block_solve.hip.h), in float and in double; what the two differ in is the section "float and double rows" below, which
-// schur_walk_f64.hip.h uses too.  (Rounds 2-3 ran the Schur formation on these as well; round 4's formation, schur_walk.hip.h, has its own
-// column-pair versions.)
+// schur_walk.hip.h uses too.  (Rounds 2-3 ran the Schur formation on these as well; round 4's formation, schur_walk.hip.h, has its own
+// column-pair versions in float.)
 //
 // Contraction is OFF: every a*b+c is a rounded multiply followed by a rounded add, sequential over the contracted index, accumulators
 // starting at +0 — the C oracle's bits.
@@ -48,20 +48,21 @@ __device__ __forceinline__ double bperm(int addr, double v) {
     const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)(uint32_t)(u >> 32));
     return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
 }
-#define SW64_FENCE() __builtin_amdgcn_sched_barrier(0)
+// phase boundary: the scheduler may not move instructions across it
+#define SW_FENCE() __builtin_amdgcn_sched_barrier(0)
 // Two wait states between the last VALU write of an operand and its first DPP read: nothing is scheduled across this point, and the s_nop 1
 // stands between whatever wrote the operands before it and the DPP multiplies behind it (verified on the built code: tools/check_dpp_hazards.py).
-#define SW64_SETTLE() do { SW64_FENCE(); asm volatile("s_nop 1"); SW64_FENCE(); } while (0)
+#define SW64_SETTLE() do { SW_FENCE(); asm volatile("s_nop 1"); SW_FENCE(); } while (0)
 // The same three idioms for code written once for both types: nothing in float, where the compiler owns the DPP modifier and its hazard.
 template <typename T>
 __device__ __forceinline__ void sched_fence() {
-    if constexpr (std::is_same<T, double>::value) SW64_FENCE();
+    if constexpr (std::is_same<T, double>::value) SW_FENCE();
 }
 template <typename T>
 __device__ __forceinline__ void settle() {
     if constexpr (std::is_same<T, double>::value) SW64_SETTLE();
 }
-// keeps the VALU write of v in front of this point (the launder idiom of schur_walk_f64.hip.h)
+// keeps the VALU write of v in front of this point (the launder idiom of schur_walk.hip.h)
 template <typename T>
 __device__ __forceinline__ void pin(T& v) {
     if constexpr (std::is_same<T, double>::value) asm volatile("" : "+v"(v));

@@ -1,17 +1,16 @@
 // mpcg_producers.hip — C ABI (include/mpcg.h) of the steps either side of the solve: Schur + preconditioner formation, dz
 // recovery (float and linsys_t = double), the CSR emitter of the QDLDL path and the block-tridiagonal direct solve.  Two sets of gfx950
-// kernels serve them: the register-resident ones of schur_walk.hip.h / schur_walk_f64.hip.h / block_solve.hip.h (the tuned 14 x 7 shape,
+// kernels serve them: the register-resident ones of schur_walk.hip.h / block_solve.hip.h (the tuned 14 x 7 shape,
 // the default there) and the run-time-dimension LDS kernels of schur_generic.hip.h (every other 1 <= control_size <= state_size <= 64; at
 // 14 x 7 under "schur_dpp" / "dz_dpp" = 0 or "producers_generic" = 1, and for calls beyond the register-resident kernels' 31-bit offsets).
 // Formation, dz and the direct solve have ONE host path each, form_schur_impl<T>, compute_dz_impl<T> and block_solve_impl<CT, ST>; ProducerTraits<T>
 // holds what float and double differ in.
 #include "mpcg_handle.hpp"
 #ifndef MPCG_DZ64_CAPMUL
-#define MPCG_DZ64_CAPMUL 4      // (grid cap of compute_dz_dpp_f64_kernel in units of 64 workgroups per CU; tools/_prof/dz64_ab.py)
+#define MPCG_DZ64_CAPMUL 4      // (grid cap of compute_dz_dpp_kernel<double> in units of 64 workgroups per CU; tools/_prof/dz64_ab.py)
 #endif
 #include "schur_generic.hip.h"
 #include "schur_walk.hip.h"
-#include "schur_walk_f64.hip.h"
 #include "block_solve.hip.h"
 
 using namespace mpcg;
@@ -74,26 +73,15 @@ static int gen_ensure_staging(mpcg_handle* h, T** buf, size_t* have, size_t need
     return MPCG_OK;
 }
 
-// What the float and the double producers differ in: the register-resident kernels and their argument struct, the handle's staging buffer
-// (one per type) and the grid cap of the dz kernel.
+// What the float and the double producers differ in: the handle's staging buffer (one per type) and the grid cap of the dz kernel.
 template <typename T> struct ProducerTraits;
 template <> struct ProducerTraits<float> {
-    typedef sw::WalkArgs WalkArgs;
-    typedef sw::WalkArgsV WalkArgsV;
-    static constexpr auto walk_kernel = sw::schur_walk_kernel<sw::WalkArgs>, seam_kernel = sw::schur_seam_kernel;
-    static constexpr auto walk_kernel_rhov = sw::schur_walk_kernel<sw::WalkArgsV>;
-    static constexpr auto dz_dpp_kernel = sw::compute_dz_dpp_kernel;
     static constexpr auto staging = &mpcg_handle::ginv_scratch;
     static constexpr auto staging_elems = &mpcg_handle::ginv_scratch_floats;
     static constexpr auto block_scratch = &mpcg_handle::block_scratch;
     static constexpr long dz_capmul = 4;
 };
 template <> struct ProducerTraits<double> {
-    typedef sw64::WalkArgs64 WalkArgs;
-    typedef sw64::WalkArgs64V WalkArgsV;
-    static constexpr auto walk_kernel = sw64::schur_walk_f64_kernel<sw64::WalkArgs64>, seam_kernel = sw64::schur_seam_f64_kernel;
-    static constexpr auto walk_kernel_rhov = sw64::schur_walk_f64_kernel<sw64::WalkArgs64V>;
-    static constexpr auto dz_dpp_kernel = sw64::compute_dz_dpp_f64_kernel;
     static constexpr auto staging = &mpcg_handle::ginv_scratch_f64;
     static constexpr auto staging_elems = &mpcg_handle::ginv_scratch_f64_elems;
     static constexpr auto block_scratch = &mpcg_handle::block_scratch64;
@@ -141,12 +129,11 @@ static int form_schur_lds(mpcg_handle* h, const char* fn, const char* why, Schur
     return MPCG_OK;
 }
 
-// Register-resident formation (schur_walk.hip.h, schur_walk_f64.hip.h; 14 x 7): a 16-lane row walks a chunk of L consecutive block rows, a
+// Register-resident formation (schur_walk.hip.h; 14 x 7): a 16-lane row walks a chunk of L consecutive block rows, a
 // second kernel closes the seams between chunks.  L trades parallelism against seam work: as long as a call has fewer than ~6 wavefronts of
 // four chunks per CU the chunks are made shorter (L = 1: every row a seam — one trajectory of the MPC loop's own call; 16 at 1024 x 128 knots).
 template <typename T>
 static int form_schur_walk(mpcg_handle* h, const SchurArgsVT<T>& a, hipStream_t st) {
-    typedef ProducerTraits<T> Tr;
     int wL = h->schur_chunk;
     if (wL <= 0) {
         const long rows = (long)a.batch * (a.N - 1), want = (long)h->num_cus * 6 * 4;
@@ -156,8 +143,8 @@ static int form_schur_walk(mpcg_handle* h, const SchurArgsVT<T>& a, hipStream_t 
     const int wchunks = (a.N - 1 + wL - 1) / wL;
     // seam buffer: one Q^-1 per chunk (ensure_seam_buffer: sized once for every automatic chunk length of this handle)
     { const int rc = ensure_seam_buffer(h, (size_t)a.batch * wchunks, sizeof(T), st); if (rc != MPCG_OK) return rc; }
-    typename Tr::WalkArgsV wv;
-    typename Tr::WalkArgs& w = wv;               // (what the scalar walking kernel and the seam kernel take)
+    sw::WalkArgsVT<T> wv;
+    sw::WalkArgsT<T>& w = wv;                    // (what the scalar walking kernel and the seam kernel take)
     w.s = a;                                     // (Ginv_scratch stays null: G^-1 is written in place)
     w.seam_qinv = static_cast<T*>(h->seam_qinv); w.L = wL; w.chunks = wchunks;
     wv.rho_v = a.rho_v;
@@ -165,13 +152,13 @@ static int form_schur_walk(mpcg_handle* h, const SchurArgsVT<T>& a, hipStream_t 
     const long capw = (long)h->num_cus * 64;
     long bw = ((long)a.batch * wchunks + 3) / 4;
     if (bw > capw) bw = capw;
-    if (a.rho_v) hipLaunchKernelGGL(Tr::walk_kernel_rhov, dim3((unsigned)bw), dim3(64), 0, st, wv);
-    else hipLaunchKernelGGL(Tr::walk_kernel, dim3((unsigned)bw), dim3(64), 0, st, w);
+    if (a.rho_v) hipLaunchKernelGGL((sw::schur_walk_kernel<T, sw::WalkArgsVT<T>>), dim3((unsigned)bw), dim3(64), 0, st, wv);
+    else hipLaunchKernelGGL(sw::schur_walk_kernel<T>, dim3((unsigned)bw), dim3(64), 0, st, w);
     HIP_TRY(h, hipGetLastError());
     if (wchunks > 1) {
         long bs = ((long)a.batch * (wchunks - 1) + 3) / 4;
         if (bs > capw) bs = capw;
-        hipLaunchKernelGGL(Tr::seam_kernel, dim3((unsigned)bs), dim3(64), 0, st, w);
+        hipLaunchKernelGGL(sw::schur_seam_kernel<T>, dim3((unsigned)bs), dim3(64), 0, st, w);
         HIP_TRY(h, hipGetLastError());
     }
     return MPCG_OK;
@@ -236,11 +223,11 @@ static int compute_dz_impl(mpcg_handle* h, const char* fn, uint32_t control_size
     const uint64_t knots = (uint64_t)batch * h->N;
     if (gen_route(h, control_size) || !h->dz_dpp || h->N < 2 || knots * dz_bytes_per_knot(a.n, a.m, sizeof(T)) >= (1ull << 31))
         return compute_dz_lds<T>(h, a, st);
-    // four knots per wavefront (schur_walk.hip.h, schur_walk_f64.hip.h): grid-stride over quads of knots
+    // four knots per wavefront (schur_walk.hip.h): grid-stride over quads of knots
     const long cap = (long)h->num_cus * 64 * Tr::dz_capmul;
     long bq = ((long)knots + 3) / 4;
     if (bq > cap) bq = cap;
-    hipLaunchKernelGGL(Tr::dz_dpp_kernel, dim3((unsigned)bq), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(sw::compute_dz_dpp_kernel<T>, dim3((unsigned)bq), dim3(64), 0, st, a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }

@@ -4,7 +4,7 @@
 //   gen::compute_dz_kernel                             dz = G^-1 (g - C^T lambda)      replaces compute_dz (include/common/dz.cuh:3-136)
 //   gen::bt_block_solve_kernel                         block-tridiagonal direct solve of S lambda = gamma (float, double, float storage / double sweep)
 // and, ahead of them, what every producer kernel of the library shares: the argument structs of formation and dz (the register-resident
-// kernels of schur_walk.hip.h / schur_walk_f64.hip.h take the same ones) and the two CSR kernels of the QDLDL path.
+// kernels of schur_walk.hip.h take the same ones) and the two CSR kernels of the QDLDL path.
 //
 // Arithmetic follows the reference operation for operation and is written with contraction OFF, sequential inner products and pivot-free
 // Gauss-Jordan (pivot row scaled by 1 / pivot, then eliminated from every other row), so that it is BIT-IDENTICAL to the C oracle

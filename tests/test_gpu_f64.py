@@ -71,7 +71,7 @@ def test_f64_form_schur_and_dz_bit_exact_vs_oracle(orc, N, precond, formation):
     """linsys_t = double types the whole linear-system step of the reference (include/common/settings.cuh:41-49), not only the PCG:
     mpcg_form_schur_f64 / mpcg_compute_dz_f64 against the oracle's double instantiation, bit for bit (same operation order, contraction
     off on both sides), including which bd slots are left unwritten; then the double-precision chain KKT blocks -> Schur -> PCG -> dz
-    solves the KKT system to 1e-9.  Round 5: the register-resident walking formation in double (schur_walk_f64.hip.h) at every chunk length
+    solves the KKT system to 1e-9.  Round 5: the register-resident walking formation in double (schur_walk.hip.h, schur_walk_kernel<double>) at every chunk length
     — auto (L = 1 here), 16, 5 (ragged last chunk), 1 — and the four-knots-per-wavefront dz kernel; "lds" = the LDS kernels of schur_generic.hip.h
     ("schur_dpp" = 0, "dz_dpp" = 0)."""
     from mpcgpu_amd import PcgSolver, pcg_config

@@ -33,7 +33,8 @@ def kernels(lib):
             l = re.sub(r"\s*<[^<>]*\+0x[0-9a-f]+>$", "", l)      # the absolute target objdump appends to a branch
             if l and l != "..." and "file format" not in l and not l.startswith("Disassembly of section"):
                 ins.append(l)
-        while ins and ins[-1] in ("s_nop 0", "s_code_end"):       # padding behind the last instruction: how much depends on what follows in the section
+        # padding behind the last instruction: how much depends on what follows in the section (a zero dword disassembles as the v_cndmask below)
+        while ins and ins[-1] in ("s_nop 0", "s_code_end", "v_cndmask_b32_e32 v0, s0, v0, vcc"):
             ins.pop()
         assert m.group(1) not in out, "two code objects define " + m.group(1)
         out[m.group(1)] = ins

@@ -10,8 +10,12 @@ N, B, pc, mi, tol, spB = (sys.argv[2:] + ["128", "1024", "ss", "167", "0.0001", 
 pmc = json.load(open(os.path.join(ROOT, "profiles", f"{tag}_pmc.json")))["kernels"]
 out = {"source": f"profiles/{tag}_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `python bench.py --steps 3 --warmup 1 --profile-lean`)",
        "fetch_correction": "fetch_bytes_corrected = 2 x FETCH_SIZE (gfx950 tallies 128-byte read requests at 64 bytes)", "kernels": {}}
+# schur_walk.hip.h's kernels are templates over float / double under one base name: a run that launched both keeps the <float one
+f64_twin = lambda name, base: base + "<double" in name and any(base + "<float" in n_ for n_ in pmc)
 for name, k in pmc.items():
     if "hbm_traffic_bytes_per_launch" not in k:
+        continue
+    if any(f64_twin(name, base) for base in ("compute_dz_dpp_kernel", "schur_walk_kernel")):
         continue
     if "pcg_lqb_kernel<128, true>" in name:          # the headline kernel since round 6 (the lane-pair kernel before: the same key with its name)
         key = f"pcg_lqb_kernel|N{N}_B{B}_{pc}_it{mi}_tol{float(tol):g}"
@@ -30,7 +34,7 @@ for name, k in pmc.items():
     else:
         continue
     if key.startswith("form_schur"):      # the formation is two kernels: the walking pass + the seam kernel
-        seam = next((v for n_, v in pmc.items() if "schur_seam_kernel" in n_ and "hbm_traffic_bytes_per_launch" in v), None)
+        seam = next((v for n_, v in pmc.items() if "schur_seam_kernel" in n_ and not f64_twin(n_, "schur_seam_kernel") and "hbm_traffic_bytes_per_launch" in v), None)
         if seam:
             k = dict(k, hbm_traffic_bytes_per_launch=k["hbm_traffic_bytes_per_launch"] + seam["hbm_traffic_bytes_per_launch"],
                      fetch_bytes_corrected=k["fetch_bytes_corrected"] + seam["fetch_bytes_corrected"], write_bytes=k["write_bytes"] + seam["write_bytes"])
