@@ -158,7 +158,10 @@ int mpcg_pcg_solve(mpcg_handle *h,
 
 /* Same solve for ONE trajectory with exactly the reference kernel's 12 arguments, in order
  * (include/pcg/sqp.cuh:137-150).  d_r and d_p receive the final residual and search direction
- * (the reference uses them as global scratch); d_v_temp and d_eta_new_temp (the reference's
+ * (the reference uses them as global scratch): at a zero-iteration exit (|eta| < exit_tol after the setup step, or
+ * max_iter = 0) d_r = gamma - S lambda0 and d_p = Pinv d_r, d_lambda untouched; at a tolerance exit after k iterations
+ * r_k and the p that iteration k used (not updated, as in the reference); at a max_iter exit the updated p.
+ * d_v_temp and d_eta_new_temp (the reference's
  * per-block partial-sum buffers, :124-125) are accepted and left untouched.  d_pcg_exit points
  * to a 1-byte bool as in the reference.  The symmetric-stair preconditioner is assumed, as in the
  * reference (its Pinv always carries the off-diagonal blocks). */

@@ -334,8 +334,9 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
             float eta = uniform(exchange(SlotE{}, poll_p, L::RT, L::ZP, p3));
             if constexpr (!P) f = fetch(L::RT, L::ZP);
             if (failed) { iters = 0xFFFFFFFFu; max_iter_exit = 2; return; }
-            if (fabsf(eta) < a.exit_tol) { max_iter_exit = 0; return; }
-            for (int it = 0; it < a.max_iter; ++it) {
+            // (a setup exit skips the loop, not the store behind it: the Pinv waves hold r_0 = gamma - S lambda0 in x.k, R0 still holds gamma)
+            if (fabsf(eta) < a.exit_tol) max_iter_exit = 0;
+            else for (int it = 0; it < a.max_iter; ++it) {
 #ifdef MPCG_PROF
                 prof_on = cl == 0 && g == 0 && it == 20;
 #endif

@@ -283,8 +283,9 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqkc_f64_kernel(ClusterArgs6
             real eta = lqk_uniform(exchange(SlotE{}, poll_p, L::RT, L::ZP, p3));
             if constexpr (!P) f = fetch(L::RT, L::ZP);
             if (failed) { iters = 0xFFFFFFFFu; max_iter_exit = 2; return; }
-            if (fabs(eta) < a.exit_tol) { max_iter_exit = 0; return; }
-            for (int it = 0; it < a.max_iter; ++it) {
+            // (a setup exit skips the loop, not the store behind it: the Pinv waves hold r_0 = gamma - S lambda0 in x.k, R0 still holds gamma)
+            if (fabs(eta) < a.exit_tol) max_iter_exit = 0;
+            else for (int it = 0; it < a.max_iter; ++it) {
                 real v;
                 if constexpr (!P) {
                     x = half(std::integral_constant<int, 2>{}, SlotV{}, f, x, beta, L::US, L::ZS);
