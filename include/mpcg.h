@@ -40,6 +40,20 @@
  *   - every pointer named d_* is a DEVICE pointer on the handle's device; `stream` is a hipStream_t
  *     passed as void* (NULL = default stream).  Calls are stream-ordered and never synchronise.
  *   - batched entry points take `batch` independent trajectories stored back to back.
+ *   - ALIGNMENT AND EXTENTS.  A device pointer needs the alignment of ITS ELEMENT (4 bytes for float, int32_t and uint32_t, 8 for double, 2 for
+ *     the uint16_t of half storage, 1 for uint8_t) and nothing more — whatever vector width a kernel uses inside (16-byte accesses go to
+ *     dword-aligned addresses all over the path: the Q blocks of d_G_dense lie 245 elements apart, x_k of d_xu 21 elements apart) — with these
+ *     exceptions, each refused with MPCG_ERR_INVALID and a message that says "aligned", before anything is launched or written:
+ *         mpcg_pcg_solve, mpcg_pcg_solve_ref    d_S and d_Pinv 16-byte aligned
+ *         mpcg_bt_spmv                          d_M 16-byte aligned; d_x and d_y 8-byte aligned
+ *         mpcg_convert_f32_to_f16               d_src and d_dst 16-byte aligned
+ *         mpcg_pcg_solve_f16                    d_S16 and d_Pinv16 4-byte aligned
+ *         mpcg_probe_hbm_read                   d_src 16-byte aligned
+ *     (an exact-size hipMalloc satisfies all of them; a matrix at an odd offset inside a larger allocation may not).  NO ENTRY READS OR WRITES
+ *     OUTSIDE THE EXTENTS GIVEN HERE for its arrays, writes an array declared const, or — the 12-argument entries, whose reference signature has
+ *     no const — writes d_S, d_Pinv, d_gamma, d_v_temp or d_eta_new_temp; d_max_iter_exit / d_pcg_exit is written one byte per trajectory.  No
+ *     kernel uses an atomic operation on caller memory (those there are act on handle-owned buffers and on LDS).  tests/test_gpu_arena_*.py hold
+ *     every entry to this: all arrays of a call inside one allocation, each at exactly its smallest accepted alignment, guard bands between.
  *   - GRAPH CAPTURE.  Every compute entry point is pure stream work and may be captured into a hipGraph.  What the float PCG entry points need
  *     is allocated by mpcg_create; mpcg_form_schur(_f64), mpcg_block_solve(_f64), mpcg_compute_merit(_f64) and a FORCED "cluster" on a horizon the automatic policy gives to one
  *     CU allocate a handle-owned work buffer at their first call (hipMalloc is not stream work): make that call once outside the capture — a
@@ -208,6 +222,10 @@ int mpcg_pcg_solve_f16(mpcg_handle *h,
  *   d_C_dense [batch][(n^2+nm)(N-1)]     -A_k, -B_k (already negated, include/common/kkt.cuh:115-116)
  *   d_g [batch][(n+m)N - m], d_c [batch][nN]
  *   d_S, d_Pinv, d_gamma                 outputs in the layouts mpcg_pcg_solve consumes
+ * Blocks (0, left) and (N-1, right) of d_S and d_Pinv lie outside the matrix: NO routing of this entry writes them (the register-resident
+ * formation at any "schur_chunk", the LDS kernels of "schur_dpp" = 0 / "producers_generic" = 1 / other shapes, float and double, scalar rho
+ * and _rhov alike) — they keep the caller's bytes, as in the reference (:97, 118), and no solver entry reads them.  Every other element of
+ * d_S and d_gamma, and all of d_G_dense, is written by every call.
  * precond = MPCG_PRECOND_NONE writes S and gamma only (d_Pinv is not touched and may be NULL): what
  * mpcg_block_solve needs; it saves the inversion of every diagonal block of S and the completion kernel's products.
  * precond = MPCG_PRECOND_JACOBI skips the symmetric-stair completion (:9-137): the off-diagonal

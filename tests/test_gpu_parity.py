@@ -320,6 +320,30 @@ def test_error_behaviour(P):
     rc = lib.mpcg_pcg_solve(sol._h, C.c_void_p(p + 4), C.c_void_p(p), C.c_void_p(p), C.c_void_p(p), 1, 5, 0.0, 3,
                             C.c_void_p(it.data_ptr()), C.c_void_p(ex.data_ptr()), None)
     assert rc == _lib.MPCG_ERR_INVALID and b"aligned" in lib.mpcg_last_error(sol._h)
+    # every alignment refusal of include/mpcg.h (ALIGNMENT), one pointer at a time short of what the entry asks for, inside a guard-banded arena
+    # (tests/arena.py): the code, the word — and not one byte of the arena changed, so nothing was launched
+    import arena
+    import arena_specs
+    for mode in arena.MODES:
+        ar = arena.Arena(arena_specs.refusals(N), mode, "torch")
+        for name in ("S", "Pinv", "gamma"):
+            ar.put(name, G[name])
+        at = lambda name, shift=0: C.c_void_p(ar.address(name) + shift)
+        h = sol._h
+        refused = [(lib.mpcg_pcg_solve, (h, at("S", s), at("Pinv", q), at("gamma"), at("lambda"), 1, 5, 0.0, 3, at("iters"), at("exits"), None))
+                   for s, q in ((4, 0), (0, 4), (8, 0), (0, 8))]
+        refused += [(lib.mpcg_pcg_solve_ref, (h, at("S", s), at("Pinv", q), at("gamma"), at("lambda"), at("r"), at("p"), at("r"), at("p"), at("iters"),
+                                              at("exits"), 5, 0.0, None)) for s, q in ((4, 0), (0, 4))]
+        refused += [(lib.mpcg_bt_spmv, (h, at("S", s), at("gamma", x), at("lambda", y), 1, 3, None)) for s, x, y in ((4, 0, 0), (8, 0, 0), (0, 4, 0), (0, 0, 4))]
+        refused += [(lib.mpcg_convert_f32_to_f16, (h, at("S", s), at("S16", d), 64, None)) for s, d in ((4, 0), (0, 2), (0, 8))]
+        refused += [(lib.mpcg_pcg_solve_f16, (h, at("S16", s), at("P16", q), at("gamma"), at("lambda"), 1, 5, 0.0, 3, at("iters"), at("exits"), None))
+                    for s, q in ((2, 0), (0, 2))]
+        refused += [(lib.mpcg_probe_hbm_read, (h, at("S", 4), 1024, at("sink"), None))]
+        before = ar.snapshot()
+        for fn, args in refused:
+            rc = fn(*args)
+            assert rc == _lib.MPCG_ERR_INVALID and b"aligned" in lib.mpcg_last_error(h), (mode, fn.__name__, rc, lib.mpcg_last_error(h))
+        assert np.array_equal(ar.snapshot(), before), mode
     rc = lib.mpcg_pcg_solve(sol._h, None, C.c_void_p(p), C.c_void_p(p), C.c_void_p(p), 1, 5, 0.0, 3,
                             C.c_void_p(it.data_ptr()), C.c_void_p(ex.data_ptr()), None)
     assert rc == _lib.MPCG_ERR_INVALID
