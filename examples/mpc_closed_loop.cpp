@@ -16,9 +16,14 @@
 // mpcg_inverse_dynamics(q_row, 0, 0) once, up front, on the device.  --sim-gravity G (default: --gravity) is the SIMULATED plant's scalar in the batched run,
 // as --sim-integrator is its integrator: the plant need not be the controller's model.  (simulateMPC's stages share one plant, stages<T>().dynmem: the
 // controller's.)  The JSON line carries "gravity" and "sim_gravity" when either is non-zero, and is what it was otherwise.
+// --q-cost Q / --u-relative 1 (the batched run): its KKT blocks and merits come from mpcg_generate_kkt_xuref / mpcg_compute_merit_xuref with the running cost
+// 1/2 |ee - goal|^2 + 1/2 Q |q - q_plan|^2 + 1/2 qd_cost |qd|^2 + 1/2 r_cost |u - [u-relative] u_plan|^2, the reference row read from the trajectory's own plan at
+// the offset mpcg_advance_horizon advances: "stay near the planned posture", and (with --gravity) penalise what the control adds to the plan's gravity-compensating
+// torque instead of the torque itself.  The JSON line carries "q_cost" and "u_relative" when either is given, and is what it was without.
 // Prints one JSON line; exits 0 only if every tracking error is finite and every trajectory shifted the expected number of times.
 //   hipcc --offload-arch=gfx950 -O2 -DLINSYS_SOLVE=1 [-DUSE_DOUBLES] -Iinclude examples/mpc_closed_loop.cpp -Lmpcgpu_amd -lmpcg_hip
 //   mpc_closed_loop [--batch 4] [--knots 16] [--updates 17] [--iters 1] [--mpc-steps 16] [--integrator {0,1}] [--sim-integrator {0,1}] [--gravity G] [--sim-gravity G]
+//                   [--q-cost Q] [--u-relative {0,1}]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -101,8 +106,9 @@ static mpcg_plant* clone_with_gravity(const mpcg_plant* src, double g) {
 
 int main(int argc, char** argv) {
     int B = 4, N = 16, U = 17, K = 1, mpc_steps = 16;
-    double gravity = 0.0, sim_gravity = 0.0;
+    double gravity = 0.0, sim_gravity = 0.0, q_cost = 0.0;
     bool sim_gravity_given = false;
+    int u_relative = 0;
     int integrator = -1, sim_integrator = -1;                                 // -1: not given (0)
     for (int i = 1; i + 1 < argc; i += 2) {
         if (!strcmp(argv[i], "--batch")) B = atoi(argv[i + 1]);
@@ -114,12 +120,16 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--sim-integrator")) sim_integrator = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--gravity")) gravity = atof(argv[i + 1]);
         else if (!strcmp(argv[i], "--sim-gravity")) { sim_gravity = atof(argv[i + 1]); sim_gravity_given = true; }
+        else if (!strcmp(argv[i], "--q-cost")) q_cost = atof(argv[i + 1]);
+        else if (!strcmp(argv[i], "--u-relative")) u_relative = atoi(argv[i + 1]);
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (B < 1 || N < 2 || N > 128 || U < 1 || K < 1 || mpc_steps < 1) { fprintf(stderr, "need batch >= 1, 2 <= knots <= 128, updates, iters, mpc-steps >= 1\n"); return 2; }
     if (integrator < -1 || integrator > 1 || sim_integrator < -1 || sim_integrator > 1) { fprintf(stderr, "--integrator and --sim-integrator take 0 or 1\n"); return 2; }
     if (!sim_gravity_given) sim_gravity = gravity;
     if (!std::isfinite(gravity) || !std::isfinite(sim_gravity)) { fprintf(stderr, "--gravity and --sim-gravity take finite numbers\n"); return 2; }
+    if (!std::isfinite(q_cost) || q_cost < 0.0 || u_relative < 0 || u_relative > 1) { fprintf(stderr, "--q-cost takes a finite number >= 0, --u-relative 0 or 1\n"); return 2; }
+    const bool xuref = q_cost != 0.0 || u_relative != 0;                     // the batched run's cost tracks the joint-space plan (the _xuref entries)
     const bool flagged = integrator >= 0 || sim_integrator >= 0;
     const unsigned integ = integrator > 0 ? 1u : 0u, sim_integ = sim_integrator > 0 ? 1u : 0u;
     const float dt = 1.0f / 64, qd_cost = 1e-4f, mu = 10.f;                  // include/common/settings.cuh:84-94, include/pcg/sqp.cuh:51
@@ -204,6 +214,12 @@ int main(int argc, char** argv) {
     T steps[8];
     for (int p = 0; p < 8; ++p) steps[p] = -1.0f / (float)(1 << p);
     const T zero = 0;
+    // the generalised cost's reference: each trajectory's own plan, at the offset mpcg_advance_horizon advances (read when the kernels run)
+    const mpcg_xuref ref = {d_bplan, (uint32_t)TS, (uint32_t)TS, d_offset, 1.0, q_cost, u_relative ? MPCG_XUREF_U_RELATIVE : 0u};
+    auto merit_of = [&](const T* dz, const T* st, uint32_t count, T* out) {
+        return xuref ? LS(mpcg_compute_merit_xuref)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, dz, st, count, mu, qd_cost, r_cost, &ref, out, (uint32_t)B, s)
+                     : LS(mpcg_compute_merit)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, dz, st, count, mu, qd_cost, r_cost, out, (uint32_t)B, s);
+    };
     ShiftClock clock(dt);
     double prev_us = 0;
     int shifts = 0;
@@ -211,13 +227,14 @@ int main(int argc, char** argv) {
         // one SQP call (include/pcg/sqp.cuh): x_s = x_0 of the iterate, drho = 1, merit of the start iterate, K iterations
         gpuErrchk(hipMemcpyAsync(d_drho, d_ones, B * sizeof(T), hipMemcpyDeviceToDevice, s));
         gpuErrchk(hipMemsetAsync(d_gave_up, 0, B, s));
-        MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, nullptr, &zero, 1, mu, qd_cost, r_cost, d_merit_ref, (uint32_t)B, s));
+        MPCG_OK_OR_DIE(h, merit_of(nullptr, &zero, 1, d_merit_ref));
         for (int it = 0; it < K; ++it) {
-            MPCG_OK_OR_DIE(h, LS(mpcg_generate_kkt)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, s));
+            if (xuref) MPCG_OK_OR_DIE(h, LS(mpcg_generate_kkt_xuref)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, &ref, d_G, d_C, d_g, d_c, (uint32_t)B, s));
+            else MPCG_OK_OR_DIE(h, LS(mpcg_generate_kkt)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, s));
             MPCG_OK_OR_DIE(h, LS(mpcg_form_schur_rhov)(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_rho, (uint32_t)B, MPCG_PRECOND_SS, s));
             MPCG_OK_OR_DIE(h, LS(mpcg_pcg_solve)(h, d_S, d_Pinv, d_gamma, d_lambda, (uint32_t)B, PCG_MAX_ITER, (T)1e-7, MPCG_PRECOND_SS, d_iters, d_exit, s));
             MPCG_OK_OR_DIE(h, LS(mpcg_compute_dz)(h, m, d_G, d_C, d_g, d_lambda, d_dz, (uint32_t)B, s));
-            MPCG_OK_OR_DIE(h, LS(mpcg_compute_merit)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, d_dz, steps, 8, mu, qd_cost, r_cost, d_merit, (uint32_t)B, s));
+            MPCG_OK_OR_DIE(h, merit_of(d_dz, steps, 8, d_merit));
             MPCG_OK_OR_DIE(h, LS(mpcg_line_search_step_rho)(h, m, d_merit, steps, 8, d_merit_ref, d_dz, d_xu, d_step, d_rho, d_drho, d_gave_up, (T)1.2, (T)1e-3, (T)10, (T)1e-3,
                                                         (uint32_t)B, s));
         }
@@ -248,6 +265,7 @@ int main(int argc, char** argv) {
     printf("{\"batch\": %d, \"knots\": %d, \"updates\": %d, \"iters\": %d, ", B, N, U, K);
     if (flagged) printf("\"integrator\": %u, \"sim_integrator\": %u, ", integ, sim_integ);
     if (gravity != 0.0 || sim_gravity != 0.0) printf("\"gravity\": %g, \"sim_gravity\": %g, ", gravity, sim_gravity);
+    if (xuref) printf("\"q_cost\": %g, \"u_relative\": %d, ", q_cost, u_relative);
     printf("\"expected_shifts\": %d, \"shifts\": [", shifts);
     for (int b = 0; b < B; ++b) printf("%s%d", b ? ", " : "", offset[b]);
     printf("], \"tracking_errors\": [");

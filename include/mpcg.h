@@ -520,6 +520,64 @@ int mpcg_line_search_step_rho_f64(mpcg_handle *h, uint32_t control_size, const d
                                   uint8_t *d_done /* [batch] in/out */, double rho_factor, double rho_min, double rho_max, double rho_reset,
                                   uint32_t batch, void *stream);
 
+/* ---- joint-space reference cost (xu_ref): mpcg_generate_kkt and mpcg_compute_merit with a generalised running cost ----
+ * The cost the calls above know is the end-effector plant's (include/dynamics/iiwa/iiwa_eepos_plant.cuh).  The _xuref entries add the reference's other
+ * plant (include/dynamics/iiwa/iiwa_plant.cuh: a joint-space plan tracked with Q_cost |q - q_ref|^2, QD_cost |qd - qd_ref|^2, R_cost |u|^2) and contain
+ * both as special cases.  Trajectory b, knot k; the plan row ref = [q_ref(7), qd_ref(7), u_ref(7)]:
+ *
+ *     J_k = 1/2 ee_cost |ee(q_k) - goal_k[0:3]|^2 + 1/2 q_cost |q_k - q_ref|^2 + 1/2 qd_cost |qd_k - [QD_RELATIVE] qd_ref|^2
+ *           + [k < N-1] 1/2 r_cost |u_k - [U_RELATIVE] u_ref|^2
+ *     row(b, k) = clamp(off_b + k, 0, traj_steps - 1), evaluated in 64-bit;  off_b = d_traj_offset ? d_traj_offset[b] : 0
+ *     plan_b    = d_xu_traj + b * traj_batch_stride * 21      (stride 0: one plan shared by the batch) — the plan, stride and offsets of mpcg_advance_horizon
+ *
+ * mpcg_generate_kkt_xuref(_f64) stores, in mpcg_generate_kkt(_f64)'s layouts and with its C, c, integrators ("integrator"), builds ("kkt_analytic", "kkt_f32")
+ * and plant gravity (gq = J^T (ee - goal)):
+ *     Q_k = blkdiag(ee_cost gq gq^T + q_cost I, qd_cost I),   R_k = r_cost I,
+ *     q_k = [ee_cost gq + q_cost (q - q_ref); qd_cost (qd - [QD_RELATIVE] qd_ref)],   r_k = r_cost (u - [U_RELATIVE] u_ref).
+ *   The last block (Q_{N-1}, q_{N-1}): the JOINT-SPACE terms are evaluated at x_{N-1} against row(b, N-1) (iiwa_plant.cuh:300-323; where the merit evaluates them).
+ *   Its END-EFFECTOR term keeps the quirk of mpcg_generate_kkt (_lastblock): the pose of x_{N-2} against goal_{N-1} — the pose of x_{N-1} is not computed.
+ *   ee_cost = 0, q_cost > 0, flags = QD_RELATIVE is iiwa_plant.cuh.  ee_cost = 1, q_cost = 0, flags = 0 gives mpcg_generate_kkt's numbers (a -0 may become +0)
+ *   except the seven qd entries of q_{N-1}: qd_cost qd_{N-1}, not qd_cost qd_{N-2}.
+ * mpcg_compute_merit_xuref(_f64) is mpcg_compute_merit(_f64) with J_k above, every knot (the last included) at its own state against its own row; violation
+ *   terms, mu, d_xs, the one-rounding trial iterate, the fixed-order sums, "merit_f32" and the shared scratch with its first-call allocation are unchanged, and
+ *   mpcg_line_search_step(_rho)(_f64) follow it as they are.
+ *
+ * mpcg_xuref is a HOST struct, copied into the launch: a captured graph keeps its scalars and pointers.  d_traj_offset is DEVICE data read when the kernel
+ * runs and is not validated (the clamp keeps every read inside the plan): a captured graph follows what mpcg_advance_horizon has written since.
+ * The plan needs element alignment only; no byte outside traj_steps (+ (batch - 1) traj_batch_stride) rows of 21 elements is read.
+ * d_eePos_traj may be NULL exactly when ee_cost == 0.
+ *   MPCG_ERR_INVALID, nothing launched or written: ref or d_xu_traj NULL; traj_steps == 0; 0 < traj_batch_stride < traj_steps; a negative or non-finite
+ *     ee_cost / q_cost; an unknown flag bit; d_eePos_traj NULL with ee_cost != 0; everything mpcg_generate_kkt / mpcg_compute_merit refuse.
+ *   MPCG_ERR_UNSUPPORTED: anything but state_size 14 / control_size 7.  batch == 0: MPCG_OK.  Capture rules: those of the parent entries. */
+#define MPCG_XUREF_QD_RELATIVE 1u
+#define MPCG_XUREF_U_RELATIVE  2u
+typedef struct mpcg_xuref {
+    const void    *d_xu_traj;         /* plan rows of 21 elements of the ENTRY's type: float for the float entries, double for _f64 */
+    uint32_t       traj_steps;        /* >= 1 */
+    uint32_t       traj_batch_stride; /* 0 or >= traj_steps */
+    const int32_t *d_traj_offset;     /* [batch] or NULL (= 0): device data, read when the kernel runs */
+    double         ee_cost, q_cost;   /* finite, >= 0 */
+    uint32_t       flags;             /* MPCG_XUREF_* */
+} mpcg_xuref;
+int mpcg_generate_kkt_xuref(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size, float timestep,
+                            const float *d_eePos_traj /* may be NULL if ee_cost == 0 */, const float *d_xs, const float *d_xu,
+                            float qd_cost, float r_cost, const mpcg_xuref *ref, float *d_G_dense, float *d_C_dense, float *d_g, float *d_c,
+                            uint32_t batch, void *stream);
+int mpcg_generate_kkt_xuref_f64(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size, double timestep,
+                                const double *d_eePos_traj /* may be NULL if ee_cost == 0 */, const double *d_xs, const double *d_xu,
+                                double qd_cost, double r_cost, const mpcg_xuref *ref, double *d_G_dense, double *d_C_dense, double *d_g, double *d_c,
+                                uint32_t batch, void *stream);
+int mpcg_compute_merit_xuref(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size, float timestep,
+                             const float *d_eePos_traj /* may be NULL if ee_cost == 0 */, const float *d_xs /* may be NULL */, const float *d_xu,
+                             const float *d_dz /* may be NULL if every step size is 0 */, const float *step_sizes, uint32_t num_steps,
+                             float mu, float qd_cost, float r_cost, const mpcg_xuref *ref, float *d_merit /* [batch][num_steps] */,
+                             uint32_t batch, void *stream);
+int mpcg_compute_merit_xuref_f64(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size, double timestep,
+                                 const double *d_eePos_traj /* may be NULL if ee_cost == 0 */, const double *d_xs /* may be NULL */, const double *d_xu,
+                                 const double *d_dz /* may be NULL if every step size is 0 */, const double *step_sizes, uint32_t num_steps,
+                                 double mu, double qd_cost, double r_cost, const mpcg_xuref *ref, double *d_merit /* [batch][num_steps] */,
+                                 uint32_t batch, void *stream);
+
 /* ---- plant simulation and horizon shift: the step between two SQP solves of the MPC loop (csrc/sim_plant.hip.h) ----
  * What simulateMPC does once per control update (reference include/mpcsim.cuh:288-348), batched, on the device, nothing read back.  Float, state_size
  * 14 / control_size 7 only (MPCG_ERR_UNSUPPORTED otherwise); both calls are pure stream work from the first call on (capturable).

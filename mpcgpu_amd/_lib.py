@@ -22,6 +22,15 @@ MPCG_PRECOND_SS = 3
 MPCG_MAX_STEP_SIZES = 16
 MPCG_STEP_FROZEN = -2
 MPCG_SIM_MAX_SUBSTEPS = 65536
+MPCG_XUREF_QD_RELATIVE = 1
+MPCG_XUREF_U_RELATIVE = 2
+
+
+class mpcg_xuref(C.Structure):
+    """The HOST struct of the _xuref entries (include/mpcg.h), copied into the launch."""
+    _fields_ = [("d_xu_traj", C.c_void_p), ("traj_steps", C.c_uint32), ("traj_batch_stride", C.c_uint32), ("d_traj_offset", C.c_void_p),
+                ("ee_cost", C.c_double), ("q_cost", C.c_double), ("flags", C.c_uint32)]
+
 
 # every symbol include/mpcg.h declares: (name, restype, argtypes)
 _f32p = C.c_void_p   # device pointers travel as integers
@@ -86,6 +95,16 @@ SYMBOLS = {
     "mpcg_line_search_step_rho_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
                                                 C.c_uint32, C.c_void_p]),
+    "mpcg_generate_kkt_xuref": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                          C.POINTER(mpcg_xuref), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_generate_kkt_xuref_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                              C.POINTER(mpcg_xuref), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_compute_merit_xuref": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float, C.c_float, C.POINTER(mpcg_xuref), C.c_void_p, C.c_uint32,
+                                           C.c_void_p]),
+    "mpcg_compute_merit_xuref_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(C.c_double), C.c_uint32, C.c_double, C.c_double, C.c_double, C.POINTER(mpcg_xuref), C.c_void_p,
+                                               C.c_uint32, C.c_void_p]),
     "mpcg_simulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_float,
                                 C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_advance_horizon": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -87,6 +87,32 @@ template <typename S, typename IO = float> struct KktArgsT {
     int analytic;                        // 1: round 1 = the analytic gradient recursion of the inverse dynamics (default); 0: one-sided differences
 };
 
+// COST = 1 (mpcg_generate_kkt_xuref, mpcg_compute_merit_xuref): the running cost also tracks the joint-space plan the closed loop keeps on the device
+// (mpcg_advance_horizon's d_xu_traj / d_traj_offset; the reference's other plant, include/dynamics/iiwa/iiwa_plant.cuh):
+//     J_k = 1/2 ee_cost |ee(q_k) - goal_k|^2 + 1/2 q_cost |q_k - q_ref|^2 + 1/2 qd_cost |qd_k - [QD_REL] qd_ref|^2 + [k < N-1] 1/2 r_cost |u_k - [U_REL] u_ref|^2
+// with [q_ref, qd_ref, u_ref] = row clamp(off_b + k, 0, traj_steps - 1) of trajectory b's plan.  The cost is a compile-time parameter of the kernels (as INTEGRATOR):
+// the COST = 0 instantiations are the kernels they were; weights and flags are run-time arguments of the COST = 1 ones.
+constexpr int XU_ROW = 3 * PJ;           // a plan row: x (14) + u (7)
+constexpr uint32_t XUREF_QD_RELATIVE = 1u, XUREF_U_RELATIVE = 2u;      // MPCG_XUREF_QD_RELATIVE, MPCG_XUREF_U_RELATIVE
+template <typename S, typename IO> struct XuRefT {
+    const IO* xu_traj;                   // [traj_steps][21], or [batch][traj_stride][21]
+    const int32_t* traj_offset;          // [batch] or NULL (= 0): read when the kernel runs
+    uint32_t traj_steps, traj_stride;
+    S ee_cost, q_cost;
+    uint32_t flags;
+    // row(b, k) = clamp(off_b + k, 0, traj_steps - 1), in 64-bit: no offset an int32 holds leaves the plan.  In two steps, so that a kernel can ask for off_b
+    // first and for the row — a load that depends on it — behind independent work.
+    __device__ __forceinline__ int offset(int b) const { return traj_offset ? traj_offset[b] : 0; }
+    __device__ __forceinline__ const IO* row(int b, int off, int k) const {
+        long r = (long)off + k;
+        r = r < 0 ? 0 : (r > (long)traj_steps - 1 ? (long)traj_steps - 1 : r);
+        return xu_traj + ((size_t)b * traj_stride + (size_t)r) * XU_ROW;
+    }
+};
+template <typename S, typename IO = float> struct KktXuArgsT : KktArgsT<S, IO> { XuRefT<S, IO> ref; };
+template <int COST, typename S, typename IO> struct KktArgsSel { typedef KktArgsT<S, IO> type; };
+template <typename S, typename IO> struct KktArgsSel<1, S, IO> { typedef KktXuArgsT<S, IO> type; };
+
 // The model tables are read through the CONSTANT address space (same 64-bit address as the global pointer): loads from it are
 // invariant by definition, so a uniform address makes them scalar loads (s_load, scalar cache).  Through the plain global
 // pointer the compiler must assume the kernel's own stores may clobber the table and emits ~1,300 vector loads per knot
@@ -458,8 +484,9 @@ __device__ __forceinline__ void kkt_copy_out(T* dst, L* src, int l) {
 // R = double | float: a lane group of 16 = one (trajectory, knot) pair per trip; R = kkt_f2: TWO — items 2 i and 2 i + 1 of the wavefront's eight — in the halves of every value.
 // IO = float: mpcg_generate_kkt; IO = double (R = double only): mpcg_generate_kkt_f64, float64 inside, double arrays in and out.  Only the loads and the output
 // staging depend on IO; INTEGRATOR (0 explicit, 1 semi-implicit Euler) is read in `if constexpr` only.  (A shared __device__ body was tried and changed the float kernels' code.)
-template <bool ANALYTIC, typename R = double, int INTEGRATOR = 0, typename IO = float>
-__global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALYTIC ? KKT_WAVES_ANALYTIC : 2) void generate_kkt_kernel(KktArgsT<typename KktR<R>::scalar, IO> a) {
+// COST (0: the end-effector plant's cost, 1: the generalised cost over a joint-space plan, KktXuArgsT) is read in `if constexpr` only, as INTEGRATOR.
+template <bool ANALYTIC, typename R = double, int INTEGRATOR = 0, typename IO = float, int COST = 0>
+__global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALYTIC ? KKT_WAVES_ANALYTIC : 2) void generate_kkt_kernel(typename KktArgsSel<COST, typename KktR<R>::scalar, IO>::type a) {
     typedef KktR<R> T;
     typedef typename T::scalar S;
     constexpr int KP = T::KP;
@@ -509,6 +536,13 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
             }
             xu[hf] = a.xu + (size_t)bb[hf] * ((size_t)(n + m) * N - m) + (size_t)kk[hf] * (n + m);      // x_k, u_k, x_{k+1}
         }
+        // COST = 1: the trajectory's plan offset is asked for here, the plan row that depends on it behind the sines and cosines (two dependent loads in a row at the
+        // top of the trip were 10 % of the kernel's time at two wavefronts per SIMD)
+        [[maybe_unused]] int roff[KP];
+        if constexpr (COST == 1) {
+#pragma unroll
+            for (int hf = 0; hf < KP; ++hf) roff[hf] = a.ref.offset(bb[hf]);
+        }
         if (l < n) I->Xq[l] = T::mk((S)xu[0][l], (S)xu[KP - 1][l]);
         if (l < m) {
             I->U[l] = T::mk((S)xu[0][n + l], (S)xu[KP - 1][n + l]);
@@ -520,6 +554,18 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
             }
             I->Sc[0][l] = T::mk((S)sn_[0], (S)sn_[KP - 1]);
             I->Sc[1][l] = T::mk((S)cs_[0], (S)cs_[KP - 1]);
+        }
+        // COST = 1: the plan row of the knot, read ONCE per item, here, and kept as the arrays' type until the store epilogue: lane l holds entry l of x_ref, of u_ref
+        // (lanes 0..6) and, for the last block, of the x_ref of knot k + 1 (always a row of the plan: the clamp).  Every lane reads (lanes 14, 15 an entry they drop).
+        [[maybe_unused]] IO rvx[KP], rvu[KP], rvx1[KP];
+        if constexpr (COST == 1) {
+            const int lx = l < n ? l : n - 1, lu = l < m ? l : m - 1;
+#pragma unroll
+            for (int hf = 0; hf < KP; ++hf) {
+                const IO* ref = a.ref.row(bb[hf], roff[hf], kk[hf]);
+                const IO* ref1 = a.ref.row(bb[hf], roff[hf], kk[hf] + 1);
+                rvx[hf] = ref[lx]; rvu[hf] = ref[n + lu]; rvx1[hf] = ref1[lx];
+            }
         }
         __syncthreads();
         // ---- round 0: lanes 0..6 inertia-matrix columns ID(q, 0, e_l), lane 7 bias ID(q, qd, 0), lanes 8..10 the pose sweeps ----
@@ -597,10 +643,20 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
 #pragma unroll
             for (int hf = 0; hf < KP; ++hf) goal[hf] = a.eePos_traj + ((size_t)bb[hf] * N + kk[hf]) * 6;
             R s0 = KR(0.0), s1 = KR(0.0);
+            if constexpr (COST == 1) {                        // d_eePos_traj may be NULL (ee_cost = 0): no goal is read, and ee_cost x (a finite gq) = 0
+                const bool goals = a.eePos_traj != nullptr;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const R gk = goals ? T::mk((S)goal[0][r], (S)goal[KP - 1][r]) : KR(0.0), gk1 = goals ? T::mk((S)goal[0][6 + r], (S)goal[KP - 1][6 + r]) : KR(0.0);
+                    s0 += J[r] * (ee[r] - gk);
+                    s1 += J[r] * (ee[r] - gk1);
+                }
+            } else {
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
                 s0 += J[r] * (ee[r] - T::mk((S)goal[0][r], (S)goal[KP - 1][r]));
                 s1 += J[r] * (ee[r] - T::mk((S)goal[0][6 + r], (S)goal[KP - 1][6 + r]));       // goal of knot k+1: used by the last block only
+            }
             }
             I->Gq[l] = s0;
             I->Gq1[l] = s1;
@@ -644,6 +700,16 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
             if (l < n && !(KKT_ABLATE & 8)) {
                 const S dt = a.dt;
                 const S gql = l < PJ ? T::get(I->Gq[l], hf) : S(0.0), gq1l = l < PJ ? T::get(I->Gq1[l], hf) : S(0.0);
+                // COST = 1: Q = blkdiag(ee_cost g g^T + q_cost I, QD I), q = [ee_cost g + q_cost (q - q_ref); QD (qd - [QD_REL] qd_ref)], r = R (u - [U_REL] u_ref); the last block's
+                // joint-space terms at x_{N-1} against its own row, its end-effector term as before.  (ee_cost = 1, q_cost = 0, no flags: every product and sum below is exact.)
+                [[maybe_unused]] S egl = gql, eg1l = gq1l, rdx = S(0.0), rdx1 = S(0.0), rdu = S(0.0);
+                if constexpr (COST == 1) {
+                    egl = a.ref.ee_cost * gql; eg1l = a.ref.ee_cost * gq1l;
+                    const bool rel = l < PJ || (a.ref.flags & XUREF_QD_RELATIVE) != 0;      // x_l - ref_l: q - q_ref; qd - [QD_REL] qd_ref
+                    rdx = T::get(I->Xq[l], hf) - (rel ? (S)rvx[hf] : S(0.0));
+                    rdx1 = (S)xu[hf][(n + m) + l] - (rel ? (S)rvx1[hf] : S(0.0));            // x_{k+1} against the row of knot k + 1: the last block's (iiwa_plant.cuh:300-323)
+                    if (l < m) rdu = T::get(I->U[l], hf) - ((a.ref.flags & XUREF_U_RELATIVE) != 0 ? (S)rvu[hf] : S(0.0));
+                }
                 // column l (column-major):  A = I + dt [[0, I], [dqdd/dq, dqdd/dqd]] (semi-implicit: [[dt dqdd/dq, I + dt dqdd/dqd], [dqdd/dq, dqdd/dqd]]),  Q = blkdiag(g g^T, QD I)
 #pragma unroll
                 for (int r = 0; r < n; ++r) {
@@ -655,10 +721,18 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
                     else av += dt * T::get(colv[r - PJ], hf);
                     st[ST_C + l * n + r] = (float)(-av);
                     S qv, q1;
-                    if (r < PJ) { qv = T::get(I->Gq[r], hf) * gql; q1 = T::get(I->Gq1[r], hf) * gq1l; }
+                    if (r < PJ) {
+                        if constexpr (COST == 1) { qv = T::get(I->Gq[r], hf) * egl; q1 = T::get(I->Gq1[r], hf) * eg1l; }      // (+ q_cost on the diagonal: below)
+                        else { qv = T::get(I->Gq[r], hf) * gql; q1 = T::get(I->Gq1[r], hf) * gq1l; }
+                    }
+                    else if constexpr (COST == 1) qv = q1 = S(0.0);
                     else qv = q1 = (r == l) ? a.qd_cost : S(0.0);
                     st[ST_G + l * n + r] = (float)qv;
                     st[ST_Q1 + l * n + r] = (float)q1;
+                }
+                if constexpr (COST == 1) {                    // the diagonal of Q, by its own lane at a run-time index: (r == l) ? q_cost : 0 per row would be seven
+                    st[ST_G + l * n + l] = (float)(l < PJ ? gql * egl + a.ref.q_cost : a.qd_cost);      // loop-invariant selects the compiler keeps in registers across the recursion
+                    st[ST_Q1 + l * n + l] = (float)(l < PJ ? gq1l * eg1l + a.ref.q_cost : a.qd_cost);
                 }
                 if (l < m) {
 #pragma unroll
@@ -668,11 +742,17 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
                     }
 #pragma unroll
                     for (int r = 0; r < m; ++r) st[ST_G + nn + l * m + r] = (float)(r == l ? a.r_cost : S(0.0));
-                    st[ST_g + n + l] = (float)(a.r_cost * T::get(I->U[l], hf));
+                    if constexpr (COST == 1) st[ST_g + n + l] = (float)(a.r_cost * rdu);
+                    else st[ST_g + n + l] = (float)(a.r_cost * T::get(I->U[l], hf));
                 }
                 const S qdl = T::get(I->Xq[l < PJ ? l + PJ : l], hf);              // qd_{l mod 7}
+                if constexpr (COST == 1) {
+                    st[ST_g + l] = (float)(l < PJ ? egl + a.ref.q_cost * rdx : a.qd_cost * rdx);
+                    st[ST_g1 + l] = (float)(l < PJ ? eg1l + a.ref.q_cost * rdx1 : a.qd_cost * rdx1);
+                } else {
                 st[ST_g + l] = (float)(l < PJ ? gql : a.qd_cost * qdl);
                 st[ST_g1 + l] = (float)(l < PJ ? gq1l : a.qd_cost * qdl);  // last block only (evaluated at x_{N-2}: iiwa_eepos_plant.cuh:407)
+                }
                 // integrator defect c_{k+1} = x_{k+1} - (x_k + dt [qd; qdd]) (semi-implicit: x_{k+1} - [q + dt qd'; qd'], qd' = qd + dt qdd);  c_0 = x_0 - x_s
                 S pred;
                 if constexpr (INTEGRATOR == 1) {
@@ -708,6 +788,16 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
             const bool on = !(KKT_ABLATE & 8), lastblk = k == N - 2;
             const S dt = a.dt;
             const S gql = l < PJ ? I->Gq[l] : S(0.0), gq1l = l < PJ ? I->Gq1[l] : S(0.0);
+            [[maybe_unused]] S egl = gql, eg1l = gq1l, rdx = S(0.0), rdx1 = S(0.0), rdu = S(0.0);           // COST = 1: as the float arrays' path above, expression for expression
+            if constexpr (COST == 1) {
+                egl = a.ref.ee_cost * gql; eg1l = a.ref.ee_cost * gq1l;
+                if (l < n) {
+                    const bool rel = l < PJ || (a.ref.flags & XUREF_QD_RELATIVE) != 0;
+                    rdx = I->Xq[l] - (rel ? (S)rvx[0] : S(0.0));
+                    rdx1 = (S)xu[0][(n + m) + l] - (rel ? (S)rvx1[0] : S(0.0));
+                    if (l < m) rdu = I->U[l] - ((a.ref.flags & XUREF_U_RELATIVE) != 0 ? (S)rvu[0] : S(0.0));
+                }
+            }
             IO* G = a.G + (size_t)b * ((size_t)(nn + mm) * N - mm) + (size_t)(nn + mm) * k;
             IO* Cm = a.C + (size_t)b * (size_t)(nn + nm) * (N - 1) + (size_t)(nn + nm) * k;
             IO* g = a.g + (size_t)b * ((size_t)(n + m) * N - m) + (size_t)(n + m) * k;
@@ -736,15 +826,25 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
             __syncthreads();
             if (l < n && on) {
 #pragma unroll
-                for (int r = 0; r < n; ++r) sd[SD_G + l * n + r] = r < PJ ? I->Gq[r] * gql : ((r == l) ? a.qd_cost : S(0.0));
+                for (int r = 0; r < n; ++r) {
+                    if constexpr (COST == 1) sd[SD_G + l * n + r] = r < PJ ? I->Gq[r] * egl : S(0.0);      // (the diagonal: below, at a run-time index — see the float arrays' path)
+                    else sd[SD_G + l * n + r] = r < PJ ? I->Gq[r] * gql : ((r == l) ? a.qd_cost : S(0.0));
+                }
+                if constexpr (COST == 1) sd[SD_G + l * n + l] = l < PJ ? gql * egl + a.ref.q_cost : a.qd_cost;
                 if (l < m) {
 #pragma unroll
                     for (int r = 0; r < m; ++r) sd[SD_G + nn + l * m + r] = r == l ? a.r_cost : S(0.0);
-                    sd[SD_g + n + l] = a.r_cost * I->U[l];
+                    if constexpr (COST == 1) sd[SD_g + n + l] = a.r_cost * rdu;
+                    else sd[SD_g + n + l] = a.r_cost * I->U[l];
                 }
                 const S qdl = I->Xq[l < PJ ? l + PJ : l];
+                if constexpr (COST == 1) {
+                    sd[SD_g + l] = l < PJ ? egl + a.ref.q_cost * rdx : a.qd_cost * rdx;
+                    sd[SD_g1 + l] = l < PJ ? eg1l + a.ref.q_cost * rdx1 : a.qd_cost * rdx1;
+                } else {
                 sd[SD_g + l] = l < PJ ? gql : a.qd_cost * qdl;
                 sd[SD_g1 + l] = l < PJ ? gq1l : a.qd_cost * qdl;
+                }
                 S pred;
                 if constexpr (INTEGRATOR == 1) {
                     const S qdn = qdl + dt * I->Qdd[l < PJ ? l : l - PJ];
@@ -765,7 +865,11 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
             // the last block's Q_{N-1} (evaluated at x_{N-2}); the barriers are taken by every group of the wavefront, whichever knot it holds
             if (l < n && on && lastblk) {
 #pragma unroll
-                for (int r = 0; r < n; ++r) sd[l * n + r] = r < PJ ? I->Gq1[r] * gq1l : ((r == l) ? a.qd_cost : S(0.0));
+                for (int r = 0; r < n; ++r) {
+                    if constexpr (COST == 1) sd[l * n + r] = r < PJ ? I->Gq1[r] * eg1l : S(0.0);
+                    else sd[l * n + r] = r < PJ ? I->Gq1[r] * gq1l : ((r == l) ? a.qd_cost : S(0.0));
+                }
+                if constexpr (COST == 1) sd[l * n + l] = l < PJ ? gq1l * eg1l + a.ref.q_cost : a.qd_cost;
             }
             __syncthreads();
             if (live[0] && on && lastblk) kkt_copy_out<nn>(G + nn + mm, sd, l);

@@ -62,10 +62,15 @@ template <typename IO, typename S = double> struct MeritArgsT {
     IO alpha[MERIT_MAX_STEPS];
 };
 
+// COST = 1 (mpcg_compute_merit_xuref): J_k of the generalised cost (kkt_plant.hip.h, XuRefT) — every knot, the last one included, at its own state against its own plan row
+template <typename IO, typename S = double> struct MeritXuArgsT : MeritArgsT<IO, S> { XuRefT<S, IO> ref; };
+template <int COST, typename IO, typename S> struct MeritArgsSel { typedef MeritArgsT<IO, S> type; };
+template <typename IO, typename S> struct MeritArgsSel<1, IO, S> { typedef MeritXuArgsT<IO, S> type; };
+
 // IO = float: mpcg_compute_merit; IO = double: mpcg_compute_merit_f64.  Only the loads and the trial iterate depend on IO; INTEGRATOR: 0 explicit, 1 semi-implicit
-// Euler.  (A shared __device__ body was tried and changed the float kernel's code.)
-template <typename IO, int INTEGRATOR = 0>
-__global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(MeritArgsT<IO> a) {
+// Euler; COST: 0 the end-effector plant's cost, 1 the generalised cost (`if constexpr` only).  (A shared __device__ body was tried and changed the float kernel's code.)
+template <typename IO, int INTEGRATOR = 0, int COST = 0>
+__global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(typename MeritArgsSel<COST, IO, double>::type a) {
     typedef double R;
     typedef KktLds<R>::vr kkt_lds_vd;
     typedef KktLds<R>::item kkt_lds_item;
@@ -107,6 +112,8 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(MeritArgsT
         };
         const size_t xk = (size_t)k * (n + m);
         double ul = 0.0, xn_q = 0.0, xn_qd = 0.0;
+        [[maybe_unused]] int roff = 0;                       // COST = 1: the plan offset is asked for here, the row that depends on it behind the sines and cosines
+        if constexpr (COST == 1) roff = a.ref.offset(b);
         if (l < n) I->Xq[l] = trial(xk + l);
         if (l < m) {
             if (dyn) { ul = trial(xk + n + l); xn_q = trial(xk + (n + m) + l); xn_qd = trial(xk + (n + m) + PJ + l); }
@@ -115,6 +122,13 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(MeritArgsT
             kkt_sincos(trial(xk + l), sn, cs);
             I->Sc[0][l] = sn;
             I->Sc[1][l] = cs;
+        }
+        // COST = 1: joint l's entries of the knot's plan row, read ONCE per item, here, kept as the arrays' type (every lane reads: lanes 7..15 an entry they drop;
+        // a row has its 21 entries at the last knot too)
+        [[maybe_unused]] IO rvq = 0, rvqd = 0, rvu = 0;
+        if constexpr (COST == 1) {
+            const IO* ref = a.ref.row(b, roff, k) + (l < m ? l : m - 1);
+            rvq = ref[0]; rvqd = ref[PJ]; rvu = ref[n];
         }
         __syncthreads();
         // ---- round 0 of the KKT kernel: lanes 0..6 ID(q, 0, e_l), lane 7 ID(q, qd, 0), lanes 8..10 the pose sweeps (the last knot: those only) ----
@@ -177,14 +191,26 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(MeritArgsT
             const R ee1 = W2[0] * V0[0] + W2[1] * V0[1] + W2[2] * V0[2];
             const R ee2 = -(W1[0] * V0[0] + W1[1] * V0[1] + W1[2] * V0[2]);
             const R q = I->Xq[l], qd = I->Xq[PJ + l];
-            R pm = 0.5 * a.qd_cost * qd * qd;
+            R pm;
+            if constexpr (COST == 1) { const R dqd = qd - ((a.ref.flags & XUREF_QD_RELATIVE) != 0 ? (R)rvqd : 0.0); pm = 0.5 * a.qd_cost * dqd * dqd; }
+            else pm = 0.5 * a.qd_cost * qd * qd;
             if (l < 3) {                                     // lanes 0..2: one coordinate of the tracking error each
+                if constexpr (COST == 1) {
+                    if (a.eePos_traj) {                      // (NULL with ee_cost = 0: no goal is read)
+                        const IO* goal = a.eePos_traj + ((size_t)b * N + k) * 6;
+                        const R d = (l == 0 ? ee0 : (l == 1 ? ee1 : ee2)) - (R)goal[l];
+                        pm += 0.5 * a.ref.ee_cost * d * d;
+                    }
+                } else {
                 const IO* goal = a.eePos_traj + ((size_t)b * N + k) * 6;
                 const R d = (l == 0 ? ee0 : (l == 1 ? ee1 : ee2)) - (R)goal[l];
                 pm += 0.5 * d * d;
+                }
             }
             R viol = 0.0;
             if (dyn) {
+                if constexpr (COST == 1) { const R du = ul - ((a.ref.flags & XUREF_U_RELATIVE) != 0 ? (R)rvu : 0.0); pm += 0.5 * a.r_cost * du * du; }
+                else
                 pm += 0.5 * a.r_cost * ul * ul;
                 if constexpr (INTEGRATOR == 1) {                  // semi-implicit Euler: q' = q + dt qd', qd' = qd + dt qdd (the map the KKT kernel linearised)
                     const R qdn = qd + a.dt * qdd;
@@ -193,6 +219,7 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(MeritArgsT
                 viol = fabs(xn_q - (q + a.dt * qd)) + fabs(xn_qd - (qd + a.dt * qdd));
             }
             if (k == 0 && a.xs) viol += fabs(q - (R)a.xs[(size_t)b * n + l]) + fabs(qd - (R)a.xs[(size_t)b * n + PJ + l]);
+            if constexpr (COST == 1) { const R dq = q - (R)rvq; pm += 0.5 * a.ref.q_cost * dq * dq; }      // the joint-space term: behind the existing ones
             I->Gq[l] = pm + a.mu * viol;
         }
         __syncthreads();

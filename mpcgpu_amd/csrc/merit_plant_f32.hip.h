@@ -26,9 +26,10 @@ namespace mpcg {
 
 __device__ __forceinline__ kkt_f2 merit_sel(const bool (&c)[2], kkt_f2 x, kkt_f2 y) { return kkt_f2{c[0] ? x.x : y.x, c[1] ? x.y : y.y}; }
 
-// MeritArgsT<float, float>: the float model tables and float scalars; `point` is the double kernel's scratch
-template <int INTEGRATOR = 0>
-__global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(MeritArgsT<float, float> a) {
+// MeritArgsT<float, float>: the float model tables and float scalars; `point` is the double kernel's scratch.  COST = 1 (mpcg_compute_merit_xuref with "merit_f32"):
+// the generalised cost of MeritXuArgsT, each half against its own knot's plan row.
+template <int INTEGRATOR = 0, int COST = 0>
+__global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(typename MeritArgsSel<COST, float, float>::type a) {
     typedef kkt_f2 R;
     typedef KktR<R> T;
     typedef KktLds<R>::vr kkt_lds_vd;
@@ -90,6 +91,8 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(MeritA
             const float x = xu[hf][e], t = __fmaf_rn(alpha[hf], dz[hf][e], x);
             return moved[hf] ? t : x;
         };
+        [[maybe_unused]] int roff[KP] = {0, 0};             // COST = 1: the plan offsets are asked for here, the rows that depend on them behind the sines and cosines
+        if constexpr (COST == 1) { roff[0] = a.ref.offset(bb[0]); roff[1] = a.ref.offset(bb[1]); }
         if (l < n) I->Xq[l] = T::mk(trial(0, xk[0] + l), trial(1, xk[1] + l));
         if (l < m) {
             float u_[KP], nq_[KP], nqd_[KP], sn_[KP], cs_[KP];
@@ -110,6 +113,14 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(MeritA
             I->Gq1[l] = T::mk(nqd_[0], nqd_[1]);
             I->Sc[0][l] = T::mk(sn_[0], sn_[1]);
             I->Sc[1][l] = T::mk(cs_[0], cs_[1]);
+        }
+        // COST = 1: joint l's entries of each half's plan row, read ONCE per item, here (every lane reads: lanes 7..15 an entry they drop; a cost-only half: a row
+        // has its 21 entries, and what it computes from u_ref is dropped by the select)
+        [[maybe_unused]] R rq = sp(0.f), rqd = sp(0.f), ru = sp(0.f);
+        if constexpr (COST == 1) {
+            const float* ref0 = a.ref.row(bb[0], roff[0], kk[0]) + (l < m ? l : m - 1);
+            const float* ref1 = a.ref.row(bb[1], roff[1], kk[1]) + (l < m ? l : m - 1);
+            rq = T::mk(ref0[0], ref1[0]); rqd = T::mk(ref0[PJ], ref1[PJ]); ru = T::mk(ref0[n], ref1[n]);
         }
         __syncthreads();
         // ---- round 0 of the packed KKT kernel: lanes 0..6 ID(q, 0, e_l), lane 7 ID(q, qd, 0), lanes 8..10 the pose sweeps — for both halves, whatever they are ----
@@ -170,14 +181,26 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(MeritA
             const R ee1 = W2[0] * V0[0] + W2[1] * V0[1] + W2[2] * V0[2];
             const R ee2 = -(W1[0] * V0[0] + W1[1] * V0[1] + W1[2] * V0[2]);
             const R q = I->Xq[l], qd = I->Xq[PJ + l], ul = I->U[l], xn_q = I->Qdd[l], xn_qd = I->Gq1[l];
-            R pm = sp(0.5f * a.qd_cost) * qd * qd;
+            R pm;
+            if constexpr (COST == 1) { const R dqd = (a.ref.flags & XUREF_QD_RELATIVE) != 0 ? qd - rqd : qd; pm = sp(0.5f * a.qd_cost) * dqd * dqd; }
+            else pm = sp(0.5f * a.qd_cost) * qd * qd;
             if (l < 3) {                                     // lanes 0..2: one coordinate of the tracking error each
+                if constexpr (COST == 1) {
+                    if (a.eePos_traj) {                      // (NULL with ee_cost = 0: no goal is read)
+                        const R goal = T::mk(a.eePos_traj[((size_t)bb[0] * N + kk[0]) * 6 + l], a.eePos_traj[((size_t)bb[1] * N + kk[1]) * 6 + l]);
+                        const R d = (l == 0 ? ee0 : (l == 1 ? ee1 : ee2)) - goal;
+                        pm += sp(0.5f * a.ref.ee_cost) * d * d;
+                    }
+                } else {
                 const R goal = T::mk(a.eePos_traj[((size_t)bb[0] * N + kk[0]) * 6 + l], a.eePos_traj[((size_t)bb[1] * N + kk[1]) * 6 + l]);
                 const R d = (l == 0 ? ee0 : (l == 1 ? ee1 : ee2)) - goal;
                 pm += sp(0.5f) * d * d;
+                }
             }
             // the dynamics half's control cost and integrator defect: computed for both halves, kept where the half is a dynamics item
-            const R pm_dyn = pm + sp(0.5f * a.r_cost) * ul * ul;
+            R pm_dyn;
+            if constexpr (COST == 1) { const R du = (a.ref.flags & XUREF_U_RELATIVE) != 0 ? ul - ru : ul; pm_dyn = pm + sp(0.5f * a.r_cost) * du * du; }
+            else pm_dyn = pm + sp(0.5f * a.r_cost) * ul * ul;
             R viol_dyn;
             if constexpr (INTEGRATOR == 1) {                 // semi-implicit Euler: q' = q + dt qd', qd' = qd + dt qdd
                 const R qdn = qd + sp(a.dt) * qdd;
@@ -193,6 +216,7 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(MeritA
             const R xs_q = T::mk(xs0[l], xs1[l]), xs_qd = T::mk(xs0[PJ + l], xs1[PJ + l]);
             const R viol_first = viol + (__builtin_elementwise_abs(q - xs_q) + __builtin_elementwise_abs(qd - xs_qd));
             viol = merit_sel(first, viol_first, viol);
+            if constexpr (COST == 1) { const R dq = q - rq; pm += sp(0.5f * a.ref.q_cost) * dq * dq; }      // the joint-space term: behind the existing ones
             I->Gq[l] = pm + sp(a.mu) * viol;
         }
         __syncthreads();

@@ -233,13 +233,38 @@ int mpcg_plant_destroy(mpcg_plant* p) {
 }
 
 // mpcg_generate_kkt (T = float) and mpcg_generate_kkt_f64 (T = double): one host path (fn: the entry point's name).  "kkt_f32" selects a build of the float entry only.
+// The _xuref entries (xuref = true) go the same way with the COST = 1 instantiation of the build the options select; `ref` is copied into the launch.
 extern "C++" {
+// the rules of mpcg_xuref (include/mpcg.h); MPCG_OK, or the error left in the handle
+static int check_xuref(mpcg_handle* h, const char* fn, const mpcg_xuref* ref, const void* d_eePos_traj) {
+    static_assert(XUREF_QD_RELATIVE == MPCG_XUREF_QD_RELATIVE && XUREF_U_RELATIVE == MPCG_XUREF_U_RELATIVE, "the flags of the header");
+    const std::string who(fn);
+    if (!ref || !ref->d_xu_traj) return fail(h, MPCG_ERR_INVALID, who + ": null mpcg_xuref or d_xu_traj");
+    if (ref->traj_steps == 0 || (ref->traj_batch_stride != 0 && ref->traj_batch_stride < ref->traj_steps))
+        return fail(h, MPCG_ERR_INVALID, who + ": needs traj_steps >= 1 and traj_batch_stride 0 or >= traj_steps");
+    if (!std::isfinite(ref->ee_cost) || !std::isfinite(ref->q_cost) || ref->ee_cost < 0.0 || ref->q_cost < 0.0)
+        return fail(h, MPCG_ERR_INVALID, who + ": ee_cost and q_cost must be finite and >= 0");
+    if (ref->flags & ~(MPCG_XUREF_QD_RELATIVE | MPCG_XUREF_U_RELATIVE)) return fail(h, MPCG_ERR_INVALID, who + ": unknown flag bit");
+    if (!d_eePos_traj && ref->ee_cost != 0.0) return fail(h, MPCG_ERR_INVALID, who + ": d_eePos_traj may be NULL only if ee_cost is 0");
+    return MPCG_OK;
+}
+
+template <typename S, typename T>
+static XuRefT<S, T> xuref_args(const mpcg_xuref* ref) {
+    XuRefT<S, T> x;
+    x.xu_traj = static_cast<const T*>(ref->d_xu_traj); x.traj_offset = ref->d_traj_offset; x.traj_steps = ref->traj_steps; x.traj_stride = ref->traj_batch_stride;
+    x.ee_cost = (S)ref->ee_cost; x.q_cost = (S)ref->q_cost; x.flags = ref->flags;
+    return x;
+}
+
 template <typename T>
 static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, T timestep, const T* d_eePos_traj,
-                             const T* d_xs, const T* d_xu, T qd_cost, T r_cost, T* d_G_dense, T* d_C_dense, T* d_g, T* d_c, uint32_t batch, void* stream) {
+                             const T* d_xs, const T* d_xu, T qd_cost, T r_cost, T* d_G_dense, T* d_C_dense, T* d_g, T* d_c, uint32_t batch, void* stream,
+                             bool xuref = false, const mpcg_xuref* ref = nullptr) {
     if (!h || !plant) return MPCG_ERR_INVALID;
-    if (!d_eePos_traj || !d_xs || !d_xu || !d_G_dense || !d_C_dense || !d_g || !d_c)
+    if ((!d_eePos_traj && !xuref) || !d_xs || !d_xu || !d_G_dense || !d_C_dense || !d_g || !d_c)
         return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    if (xuref) { const int rc = check_xuref(h, fn, ref, d_eePos_traj); if (rc != MPCG_OK) return rc; }
     if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
     if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
     if (batch == 0) return MPCG_OK;
@@ -259,7 +284,32 @@ static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* p
     // "integrator" = 1: the semi-implicit instantiation of the same build (a compile-time parameter: the explicit instantiations are the kernels they were)
     const bool semi = h->integrator == 1;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    if constexpr (std::is_same<T, double>::value) {       // double arrays: float64 inside, either gradient route
+    if (xuref) {                                          // the same build, its COST = 1 instantiation
+        auto go = [&](auto explicit_k, auto semi_k, const auto& args, long nb) {
+            typedef std::remove_cv_t<std::remove_reference_t<decltype(args)>> Args;      // KktArgsT<S, T>
+            typedef decltype(args.dt) S;
+            static_assert(std::is_same<Args, KktArgsT<S, T>>::value, "one fill");
+            KktXuArgsT<S, T> x;
+            static_cast<Args&>(x) = args;
+            x.ref = xuref_args<S, T>(ref);
+            hipLaunchKernelGGL((semi ? semi_k : explicit_k), dim3((unsigned)nb), dim3(KKT_THREADS), 0, st, x);
+        };
+        if constexpr (std::is_same<T, double>::value) {
+            if (h->kkt_analytic) go(generate_kkt_kernel<true, double, 0, double, 1>, generate_kkt_kernel<true, double, 1, double, 1>, a, blocks);
+            else go(generate_kkt_kernel<false, double, 0, double, 1>, generate_kkt_kernel<false, double, 1, double, 1>, a, blocks);
+        } else {
+            if (h->kkt_analytic && h->kkt_f32) {
+                KktArgsT<float> f;
+                fill(f, plant->d32);
+                if (h->kkt_f32 == 1) {
+                    long pblocks = ((long)batch * (h->N - 1) + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
+                    if (pblocks > cap) pblocks = cap;
+                    go(generate_kkt_kernel<true, kkt_f2, 0, float, 1>, generate_kkt_kernel<true, kkt_f2, 1, float, 1>, f, pblocks);
+                } else go(generate_kkt_kernel<true, float, 0, float, 1>, generate_kkt_kernel<true, float, 1, float, 1>, f, blocks);
+            } else if (h->kkt_analytic) go(generate_kkt_kernel<true, double, 0, float, 1>, generate_kkt_kernel<true, double, 1, float, 1>, a, blocks);
+            else go(generate_kkt_kernel<false, double, 0, float, 1>, generate_kkt_kernel<false, double, 1, float, 1>, a, blocks);
+        }
+    } else if constexpr (std::is_same<T, double>::value) {       // double arrays: float64 inside, either gradient route
         if (h->kkt_analytic) hipLaunchKernelGGL((semi ? generate_kkt_kernel<true, double, 1, double> : generate_kkt_kernel<true, double, 0, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
         else hipLaunchKernelGGL((semi ? generate_kkt_kernel<false, double, 1, double> : generate_kkt_kernel<false, double, 0, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
     } else {
@@ -294,6 +344,20 @@ int mpcg_generate_kkt_f64(mpcg_handle* h, const mpcg_plant* plant, uint32_t cont
     return generate_kkt_impl<double>(h, "mpcg_generate_kkt_f64", plant, control_size, timestep, d_eePos_traj, d_xs, d_xu, qd_cost, r_cost, d_G_dense, d_C_dense, d_g, d_c, batch, stream);
 }
 
+int mpcg_generate_kkt_xuref(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float timestep, const float* d_eePos_traj,
+                            const float* d_xs, const float* d_xu, float qd_cost, float r_cost, const mpcg_xuref* ref, float* d_G_dense, float* d_C_dense,
+                            float* d_g, float* d_c, uint32_t batch, void* stream) {
+    return generate_kkt_impl<float>(h, "mpcg_generate_kkt_xuref", plant, control_size, timestep, d_eePos_traj, d_xs, d_xu, qd_cost, r_cost, d_G_dense, d_C_dense, d_g, d_c, batch,
+                                    stream, true, ref);
+}
+
+int mpcg_generate_kkt_xuref_f64(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, double timestep, const double* d_eePos_traj,
+                                const double* d_xs, const double* d_xu, double qd_cost, double r_cost, const mpcg_xuref* ref, double* d_G_dense, double* d_C_dense,
+                                double* d_g, double* d_c, uint32_t batch, void* stream) {
+    return generate_kkt_impl<double>(h, "mpcg_generate_kkt_xuref_f64", plant, control_size, timestep, d_eePos_traj, d_xs, d_xu, qd_cost, r_cost, d_G_dense, d_C_dense, d_g, d_c,
+                                     batch, stream, true, ref);
+}
+
 // ---- merit function and line search (merit_plant.hip.h): one host path per call for the float entries (T = float) and their _f64 twins (T = double) ----
 extern "C++" {
 template <typename T>
@@ -305,11 +369,13 @@ static int check_steps(mpcg_handle* h, const char* who, const T* step_sizes, uin
 
 template <typename T>
 static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, T timestep, const T* d_eePos_traj, const T* d_xs,
-                              const T* d_xu, const T* d_dz, const T* step_sizes, uint32_t num_steps, T mu, T qd_cost, T r_cost, T* d_merit, uint32_t batch, void* stream) {
+                              const T* d_xu, const T* d_dz, const T* step_sizes, uint32_t num_steps, T mu, T qd_cost, T r_cost, T* d_merit, uint32_t batch, void* stream,
+                              bool xuref = false, const mpcg_xuref* ref = nullptr) {
     static_assert(MERIT_MAX_STEPS == MPCG_MAX_STEP_SIZES, "scratch row stride");
     constexpr bool F64 = std::is_same<T, double>::value;
     if (!h || !plant) return MPCG_ERR_INVALID;
-    if (!d_eePos_traj || !d_xu || !d_merit) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    if ((!d_eePos_traj && !xuref) || !d_xu || !d_merit) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    if (xuref) { const int rc = check_xuref(h, fn, ref, d_eePos_traj); if (rc != MPCG_OK) return rc; }
     { const int rc = check_steps(h, fn, step_sizes, num_steps); if (rc != MPCG_OK) return rc; }
     if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
     if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
@@ -336,7 +402,26 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
     if (blocks > cap) blocks = cap;
     const int rows = (int)(batch * num_steps);
     const bool semi = h->integrator == 1;          // "integrator": the map mpcg_generate_kkt linearised (one knob for both, every build)
-    if constexpr (F64) {                          // double arrays: float64 inside ("merit_f32" is the float entry's), the row sums stored as they are
+    if (xuref) {                                  // the same build, its COST = 1 instantiation; the row sums as below
+        if (!F64 && h->merit_f32) {
+            if constexpr (!F64) {
+                MeritXuArgsT<float, float> f;
+                fill(f, plant->d32);
+                memcpy(f.alpha, a.alpha, sizeof(f.alpha));
+                f.ref = xuref_args<float, float>(ref);
+                const long pblocks = ((long)batch * num_steps * h->N + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
+                if (pblocks > 0x7fffffffL) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch x num_steps x knot_points exceeds the grid");
+                hipLaunchKernelGGL((semi ? merit_points_f32_kernel<1, 1> : merit_points_f32_kernel<0, 1>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
+            }
+        } else {
+            MeritXuArgsT<T> x;
+            static_cast<MeritArgsT<T>&>(x) = a;
+            x.ref = xuref_args<double, T>(ref);
+            hipLaunchKernelGGL((semi ? merit_points_kernel<T, 1, 1> : merit_points_kernel<T, 0, 1>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, x);
+        }
+        HIP_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(merit_sum_kernel<T>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
+    } else if constexpr (F64) {                          // double arrays: float64 inside ("merit_f32" is the float entry's), the row sums stored as they are
         hipLaunchKernelGGL((semi ? merit_points_kernel<double, 1> : merit_points_kernel<double, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
         HIP_TRY(h, hipGetLastError());
         hipLaunchKernelGGL(merit_sum_kernel<double>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
@@ -414,6 +499,20 @@ int mpcg_compute_merit_f64(mpcg_handle* h, const mpcg_plant* plant, uint32_t con
                            double* d_merit, uint32_t batch, void* stream) {
     return compute_merit_impl<double>(h, "mpcg_compute_merit_f64", plant, control_size, timestep, d_eePos_traj, d_xs, d_xu, d_dz, step_sizes, num_steps, mu, qd_cost,
                                       r_cost, d_merit, batch, stream);
+}
+
+int mpcg_compute_merit_xuref(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float timestep, const float* d_eePos_traj, const float* d_xs,
+                             const float* d_xu, const float* d_dz, const float* step_sizes, uint32_t num_steps, float mu, float qd_cost, float r_cost,
+                             const mpcg_xuref* ref, float* d_merit, uint32_t batch, void* stream) {
+    return compute_merit_impl<float>(h, "mpcg_compute_merit_xuref", plant, control_size, timestep, d_eePos_traj, d_xs, d_xu, d_dz, step_sizes, num_steps, mu, qd_cost,
+                                     r_cost, d_merit, batch, stream, true, ref);
+}
+
+int mpcg_compute_merit_xuref_f64(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, double timestep, const double* d_eePos_traj, const double* d_xs,
+                                 const double* d_xu, const double* d_dz, const double* step_sizes, uint32_t num_steps, double mu, double qd_cost, double r_cost,
+                                 const mpcg_xuref* ref, double* d_merit, uint32_t batch, void* stream) {
+    return compute_merit_impl<double>(h, "mpcg_compute_merit_xuref_f64", plant, control_size, timestep, d_eePos_traj, d_xs, d_xu, d_dz, step_sizes, num_steps, mu,
+                                      qd_cost, r_cost, d_merit, batch, stream, true, ref);
 }
 
 int mpcg_line_search_step(mpcg_handle* h, uint32_t control_size, const float* d_merit, const float* step_sizes, uint32_t num_steps,

@@ -102,6 +102,23 @@ class Plant:
     __del__ = close
 
 
+@dataclass
+class XuRef:
+    """The joint-space plan and the weights of the generalised running cost (mpcg_xuref, include/mpcg.h):
+        J_k = 1/2 ee_cost |ee(q_k) - goal_k|^2 + 1/2 q_cost |q_k - q_ref|^2 + 1/2 qd_cost |qd_k - [qd_relative] qd_ref|^2 + 1/2 r_cost |u_k - [u_relative] u_ref|^2
+    xu_traj: the plan advance_horizon takes — [T, 21] shared by the batch; [B, T, 21] per trajectory; or, with traj_batch_stride = S > 0, [rows, 21] with
+    trajectory b's plan starting at row b S (traj_steps, default S, rows of it are the plan; (B - 1) S + traj_steps <= rows);
+    traj_offset: int32 [B] on the device or None (= 0), read when the kernel runs: row clamp(traj_offset[b] + k, 0, traj_steps - 1) is knot k's reference."""
+    xu_traj: torch.Tensor
+    traj_offset: torch.Tensor | None = None
+    traj_batch_stride: int = 0
+    ee_cost: float = 1.0
+    q_cost: float = 0.0
+    qd_relative: bool = False
+    u_relative: bool = False
+    traj_steps: int | None = None
+
+
 class QdldlSolver:
     """The reference's LINSYS_SOLVE == 0 path (include/qdldl/sqp.cuh) as a selectable solver: CSR lower-triangle pattern
     (include/utils/csr.cuh:40-73) + elimination tree once, then numeric LDL^T factor + solve per call on the HOST
@@ -372,6 +389,75 @@ class PcgSolver:
         self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), float(qd_cost),
                                                float(r_cost), _ptr(G), _ptr(Cd), _ptr(g), _ptr(c), B, _stream()))
         return G, Cd, g, c
+
+    def _xuref(self, name, ref: "XuRef", dt, B, n, m):
+        """The mpcg_xuref of a call over B trajectories of dtype dt."""
+        t = ref.xu_traj
+        if t.dtype != dt:
+            raise TypeError(f"{name}: xu_traj must have the dtype of the other tensors ({dt}), got {t.dtype}")
+        stride = int(ref.traj_batch_stride)
+        self._chk(t, t.numel(), dt, "xu_traj")
+        if t.numel() % (n + m):
+            raise ValueError(f"{name}: xu_traj must hold rows of {n + m} values")
+        rows = t.numel() // (n + m)
+        if t.dim() == 3:                                       # [B, T, 21]: a plan per trajectory
+            if stride not in (0, int(t.shape[-2])) or int(t.shape[0]) != B:
+                raise ValueError(f"{name}: a [B, T, 21] plan has B trajectories and traj_batch_stride T")
+            stride = int(t.shape[-2])
+        T = int(ref.traj_steps) if ref.traj_steps is not None else (stride if stride else rows)
+        if T < 1 or (stride and stride < T) or (B - 1) * stride + T > rows:
+            raise ValueError(f"{name}: xu_traj holds {rows} rows, fewer than (B - 1) traj_batch_stride + traj_steps, or traj_batch_stride < traj_steps")
+        if ref.traj_offset is not None:
+            self._chk(ref.traj_offset, B, torch.int32, "traj_offset")
+        flags = (_lib.MPCG_XUREF_QD_RELATIVE if ref.qd_relative else 0) | (_lib.MPCG_XUREF_U_RELATIVE if ref.u_relative else 0)
+        return _lib.mpcg_xuref(t.data_ptr(), T, stride, ref.traj_offset.data_ptr() if ref.traj_offset is not None else None,
+                               float(ref.ee_cost), float(ref.q_cost), flags)
+
+    def generate_kkt_xuref(self, plant: "Plant", eePos_traj, xs, xu, timestep: float, qd_cost: float, r_cost: float, ref: "XuRef",
+                           control_size: int | None = None):
+        """generate_kkt with the generalised running cost of `ref` (mpcg_generate_kkt_xuref; float64 tensors: mpcg_generate_kkt_xuref_f64): the same
+        layouts, C and c.  eePos_traj may be None exactly when ref.ee_cost == 0.  Mixed dtypes raise TypeError."""
+        B = xu.shape[0] if xu.dim() > 1 else 1
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        dt = self._one_dtype("generate_kkt_xuref", eePos_traj, xs, xu, ref.xu_traj)
+        if eePos_traj is not None:
+            self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
+        self._chk(xs, B * n, dt, "xs")
+        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
+        x = self._xuref("generate_kkt_xuref", ref, dt, B, n, m)
+        dev = xu.device
+        G = torch.empty(B, (n * n + m * m) * N - m * m, device=dev, dtype=dt)
+        Cd = torch.empty(B, (n * n + n * m) * (N - 1), device=dev, dtype=dt)
+        g = torch.empty(B, (n + m) * N - m, device=dev, dtype=dt)
+        c = torch.empty(B, n * N, device=dev, dtype=dt)
+        fn = self.lib.mpcg_generate_kkt_xuref if dt == torch.float32 else self.lib.mpcg_generate_kkt_xuref_f64
+        self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), float(qd_cost), float(r_cost), C.byref(x),
+                       _ptr(G), _ptr(Cd), _ptr(g), _ptr(c), B, _stream()))
+        return G, Cd, g, c
+
+    def compute_merit_xuref(self, plant: "Plant", eePos_traj, xs, xu, dz, step_sizes, timestep: float, mu: float, qd_cost: float, r_cost: float,
+                            ref: "XuRef", merit=None, control_size: int | None = None):
+        """compute_merit with the generalised running cost of `ref` (mpcg_compute_merit_xuref; float64 tensors: mpcg_compute_merit_xuref_f64); what
+        line_search_step(_rho) consumes.  eePos_traj may be None exactly when ref.ee_cost == 0.  Mixed dtypes raise TypeError."""
+        B = xu.shape[0] if xu.dim() > 1 else 1
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        dt = self._one_dtype("compute_merit_xuref", eePos_traj, xs, xu, dz, merit, ref.xu_traj)
+        arr, A = self._steps(step_sizes, dt)
+        if eePos_traj is not None:
+            self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
+        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
+        if xs is not None:
+            self._chk(xs, B * n, dt, "xs")
+        if dz is not None:
+            self._chk(dz, B * ((n + m) * N - m), dt, "dz")
+        x = self._xuref("compute_merit_xuref", ref, dt, B, n, m)
+        if merit is None:
+            merit = torch.empty(B, A, device=xu.device, dtype=dt)
+        self._chk(merit, B * A, dt, "merit")
+        fn = self.lib.mpcg_compute_merit_xuref if dt == torch.float32 else self.lib.mpcg_compute_merit_xuref_f64
+        self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), _ptr(dz), arr, A,
+                       float(mu), float(qd_cost), float(r_cost), C.byref(x), _ptr(merit), B, _stream()))
+        return merit
 
     def compute_dz(self, Ginv_dense, C_dense, g, lam, dz=None, control_size: int | None = None):
         """compute_dz (include/common/dz.cuh:124-136), batched."""
