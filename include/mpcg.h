@@ -35,6 +35,23 @@
  *     block column, a third of its HBM bytes) run once it says symmetric.  A handle that does not know yet checks the matrices of its first
  *     mpcg_pcg_solve_f64 call with ONE blocking 8-byte copy (never during graph capture: a captured call on such a handle runs a kernel that
  *     reads all three columns — family 8 up to 256 knots, family 3 beyond).
+ *   - NON-FINITE DATA.  The trajectories of a batched call are independent: no result of a trajectory depends on the FLOATING-POINT DATA of another
+ *     one, finite or not.  A trajectory whose arrays hold Inf or NaN — a diverged iterate, a solve mpcg_line_search_step_rho has given up and that
+ *     the other stages keep computing — or finite values that overflow, or singular (all-zero) matrices, leaves every output of every other
+ *     trajectory of the call bit for bit what healthy data in its place would have left, in every entry point and every build: the kernels that
+ *     carry several trajectories in one wavefront (four 16-lane rows in mpcg_block_solve, the chunk-walking formation, mpcg_compute_dz,
+ *     mpcg_generate_kkt, mpcg_compute_merit, mpcg_simulate, mpcg_inverse_dynamics; two items per packed value under "kkt_f32" = 1 and
+ *     "merit_f32" = 1; the rows of the whole batch in mpcg_bt_spmv) select by predicate, reduce within a row, and let rows without an item redo a
+ *     valid one without storing.  THE ONE HANDLE-WIDE EFFECT is the symmetry latch above: its check counts a NaN in an OFF-DIAGONAL block of d_S
+ *     (or, symmetric stair, of d_Pinv) of ANY trajectory as a violation — also the NaN of Inf - Inf when both blocks of a pair hold an Inf; a lone Inf passes the relative test —
+ *     so such a value in a call made while the latch is open sends the handle to the three-column kernels for good ("symmetry_state" 2: other bits and a
+ *     slower kernel for every trajectory of every later call; never a wrong system).  Non-finite values in d_gamma, d_lambda or a diagonal block
+ *     do not touch it, and neither does anything once the latch has resolved or under "assume_symmetric" = 1.  For the non-finite trajectory
+ *     ITSELF: every call returns — every loop and every spin of a kernel is bounded by a host argument (max_iter, knot_points, the substep
+ *     count) or a constant, never by data; |eta| < exit_tol is false for a NaN —, d_iters[b] <= max_iter, d_max_iter_exit[b] is 0 or 1 (no
+ *     cluster gives such a trajectory up: its members see the same bits and agree), d_step[b] is -1 ("a NaN never wins") or MPCG_STEP_FROZEN,
+ *     and the integer bookkeeping (d_traj_offset, d_done) goes on as for any other; its floating-point outputs are unspecified.  Integer arrays
+ *     and host scalars are validated or clamped as each entry says.  tests/test_gpu_containment_*.py hold every entry to this.
  *   - gamma, lambda: [N][n] floats per trajectory; lambda is in/out (warm start,
  *     include/mpcsim.cuh:186,267,337).
  *   - every pointer named d_* is a DEVICE pointer on the handle's device; `stream` is a hipStream_t
