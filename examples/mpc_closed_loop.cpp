@@ -20,10 +20,15 @@
 // 1/2 |ee - goal|^2 + 1/2 Q |q - q_plan|^2 + 1/2 qd_cost |qd|^2 + 1/2 r_cost |u - [u-relative] u_plan|^2, the reference row read from the trajectory's own plan at
 // the offset mpcg_advance_horizon advances: "stay near the planned posture", and (with --gravity) penalise what the control adds to the plan's gravity-compensating
 // torque instead of the torque itself.  The JSON line carries "q_cost" and "u_relative" when either is given, and is what it was without.
+// --u-max X --u-weight W [--sim-saturate] (the batched run): the controller's model is cloned with the soft torque limits |u_i| <= X at weight W
+// (mpcg_plant_clone_limits), which the _xuref entries penalise — with the neutral cost ee_cost = 1, q_cost = 0 unless --q-cost / --u-relative say otherwise —, and
+// with --sim-saturate the simulated plant clamps every control it applies to [-X, X].  The JSON line then carries "u_max", "u_weight", "sim_saturate" and
+// "u_excess_peak", the largest max(|u| - X, 0) over the controls of every iterate the SQP calls left; with --u-max inf, or without it, it is what it was
+// (--u-weight or --sim-saturate without --u-max is refused).
 // Prints one JSON line; exits 0 only if every tracking error is finite and every trajectory shifted the expected number of times.
 //   hipcc --offload-arch=gfx950 -O2 -DLINSYS_SOLVE=1 [-DUSE_DOUBLES] -Iinclude examples/mpc_closed_loop.cpp -Lmpcgpu_amd -lmpcg_hip
 //   mpc_closed_loop [--batch 4] [--knots 16] [--updates 17] [--iters 1] [--mpc-steps 16] [--integrator {0,1}] [--sim-integrator {0,1}] [--gravity G] [--sim-gravity G]
-//                   [--q-cost Q] [--u-relative {0,1}]
+//                   [--q-cost Q] [--u-relative {0,1}] [--u-max X] [--u-weight W] [--sim-saturate]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -97,6 +102,38 @@ __global__ void add_to_u(T* rows, const T* tau, int count) {
     if (i < count * m) rows[(size_t)(i / m) * (n + m) + n + i % m] += tau[i];
 }
 
+// *peak = max(*peak, max over the controls of `batch` iterates of max(|u| - u_max, 0)): one workgroup, no atomics
+__global__ void u_excess_peak(const T* xu, int batch, int N, double u_max, double* peak) {
+    __shared__ double part[256];
+    const size_t L = (size_t)(n + m) * N - m;
+    double worst = 0.0;
+    for (long i = threadIdx.x; i < (long)batch * (N - 1) * m; i += 256) {
+        const long b = i / ((long)(N - 1) * m), r = i - b * (long)(N - 1) * m;
+        const double e = fabs((double)xu[b * L + (size_t)(r / m) * (n + m) + n + r % m]) - u_max;
+        worst = e > worst ? e : worst;
+    }
+    part[threadIdx.x] = worst;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w && part[threadIdx.x + w] > part[threadIdx.x]) part[threadIdx.x] = part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && part[0] > *peak) *peak = part[0];
+}
+
+static mpcg_plant* clone_with_limits(const mpcg_plant* src, double u_max, double u_weight, bool saturate) {
+    mpcg_limits lim;
+    for (int i = 0; i < m; ++i) {
+        lim.q_lo[i] = lim.qd_lo[i] = -INFINITY; lim.q_hi[i] = lim.qd_hi[i] = INFINITY;
+        lim.u_lo[i] = -u_max; lim.u_hi[i] = u_max;
+    }
+    lim.q_weight = lim.qd_weight = 0.0; lim.u_weight = u_weight;
+    lim.flags = saturate ? MPCG_LIMITS_SIM_SATURATE : 0u;
+    mpcg_plant* p = nullptr;
+    if (mpcg_plant_clone_limits(&p, src, &lim) != MPCG_OK) { fprintf(stderr, "mpcg_plant_clone_limits: %s\n", mpcg_last_error(nullptr)); exit(1); }
+    return p;
+}
+
 static mpcg_plant* clone_with_gravity(const mpcg_plant* src, double g) {
     const double base_accel[3] = {0.0, 0.0, g};
     mpcg_plant* p = nullptr;
@@ -106,11 +143,14 @@ static mpcg_plant* clone_with_gravity(const mpcg_plant* src, double g) {
 
 int main(int argc, char** argv) {
     int B = 4, N = 16, U = 17, K = 1, mpc_steps = 16;
-    double gravity = 0.0, sim_gravity = 0.0, q_cost = 0.0;
+    double gravity = 0.0, sim_gravity = 0.0, q_cost = 0.0, u_max = INFINITY, u_weight = 0.0;
+    bool sim_saturate = false, u_max_given = false, u_weight_given = false;
     bool sim_gravity_given = false;
     int u_relative = 0;
     int integrator = -1, sim_integrator = -1;                                 // -1: not given (0)
-    for (int i = 1; i + 1 < argc; i += 2) {
+    for (int i = 1; i < argc; i += 2) {
+        if (!strcmp(argv[i], "--sim-saturate")) { sim_saturate = true; --i; continue; }      // (a flag without a value)
+        if (i + 1 >= argc) break;
         if (!strcmp(argv[i], "--batch")) B = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--knots")) N = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--updates")) U = atoi(argv[i + 1]);
@@ -122,6 +162,8 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--sim-gravity")) { sim_gravity = atof(argv[i + 1]); sim_gravity_given = true; }
         else if (!strcmp(argv[i], "--q-cost")) q_cost = atof(argv[i + 1]);
         else if (!strcmp(argv[i], "--u-relative")) u_relative = atoi(argv[i + 1]);
+        else if (!strcmp(argv[i], "--u-max")) { u_max = atof(argv[i + 1]); u_max_given = true; }
+        else if (!strcmp(argv[i], "--u-weight")) { u_weight = atof(argv[i + 1]); u_weight_given = true; }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
     if (B < 1 || N < 2 || N > 128 || U < 1 || K < 1 || mpc_steps < 1) { fprintf(stderr, "need batch >= 1, 2 <= knots <= 128, updates, iters, mpc-steps >= 1\n"); return 2; }
@@ -129,7 +171,10 @@ int main(int argc, char** argv) {
     if (!sim_gravity_given) sim_gravity = gravity;
     if (!std::isfinite(gravity) || !std::isfinite(sim_gravity)) { fprintf(stderr, "--gravity and --sim-gravity take finite numbers\n"); return 2; }
     if (!std::isfinite(q_cost) || q_cost < 0.0 || u_relative < 0 || u_relative > 1) { fprintf(stderr, "--q-cost takes a finite number >= 0, --u-relative 0 or 1\n"); return 2; }
-    const bool xuref = q_cost != 0.0 || u_relative != 0;                     // the batched run's cost tracks the joint-space plan (the _xuref entries)
+    if ((u_weight_given || sim_saturate) && !u_max_given) { fprintf(stderr, "--u-weight and --sim-saturate need --u-max\n"); return 2; }
+    if (!(u_max > 0.0) || !std::isfinite(u_weight) || u_weight < 0.0) { fprintf(stderr, "--u-max takes a number > 0 (inf: no limit), --u-weight a finite number >= 0\n"); return 2; }
+    const bool limits = std::isfinite(u_max);                                 // the batched run's plants carry torque limits: its cost comes from the _xuref entries
+    const bool xuref = q_cost != 0.0 || u_relative != 0 || limits;           // the batched run's cost tracks the joint-space plan (the _xuref entries)
     const bool flagged = integrator >= 0 || sim_integrator >= 0;
     const unsigned integ = integrator > 0 ? 1u : 0u, sim_integ = sim_integrator > 0 ? 1u : 0u;
     const float dt = 1.0f / 64, qd_cost = 1e-4f, mu = 10.f;                  // include/common/settings.cuh:84-94, include/pcg/sqp.cuh:51
@@ -195,6 +240,11 @@ int main(int argc, char** argv) {
         memcpy(&goals[(size_t)b * 6 * N], &plan_goals[(size_t)t0 * 6], (size_t)6 * N * sizeof(T));
         for (int i = 0; i < n; ++i) xs[(size_t)b * n + i] = xu[(size_t)b * L + i] + 0.04f * rnd();
     }
+    // the batched run's plants: with --u-max, limits clones of the two above (simulateMPC's stages call the plain entries, which refuse a plant with limits)
+    mpcg_plant* plant_ctrl_b = limits ? clone_with_limits(plant_ctrl, u_max, u_weight, false) : plant_ctrl;
+    mpcg_plant* plant_sim_b = limits ? clone_with_limits(plant_sim, u_max, u_weight, sim_saturate) : plant_sim;
+    double* d_peak = nullptr;
+    if (limits) { d_peak = dalloc<double>(1); gpuErrchk(hipMemset(d_peak, 0, sizeof(double))); }
     mpcg_handle* h = nullptr;
     if (mpcg_create(&h, -1, n, (uint32_t)N, (uint32_t)B) != MPCG_OK) { fprintf(stderr, "mpcg_create: %s\n", mpcg_last_error(nullptr)); return 1; }
     MPCG_OK_OR_DIE(h, mpcg_set_option(h, "integrator", (int)integ));
@@ -217,7 +267,7 @@ int main(int argc, char** argv) {
     // the generalised cost's reference: each trajectory's own plan, at the offset mpcg_advance_horizon advances (read when the kernels run)
     const mpcg_xuref ref = {d_bplan, (uint32_t)TS, (uint32_t)TS, d_offset, 1.0, q_cost, u_relative ? MPCG_XUREF_U_RELATIVE : 0u};
     auto merit_of = [&](const T* dz, const T* st, uint32_t count, T* out) {
-        return xuref ? LS(mpcg_compute_merit_xuref)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, dz, st, count, mu, qd_cost, r_cost, &ref, out, (uint32_t)B, s)
+        return xuref ? LS(mpcg_compute_merit_xuref)(h, plant_ctrl_b, m, dt, d_goals, d_xs, d_xu, dz, st, count, mu, qd_cost, r_cost, &ref, out, (uint32_t)B, s)
                      : LS(mpcg_compute_merit)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, dz, st, count, mu, qd_cost, r_cost, out, (uint32_t)B, s);
     };
     ShiftClock clock(dt);
@@ -229,7 +279,7 @@ int main(int argc, char** argv) {
         gpuErrchk(hipMemsetAsync(d_gave_up, 0, B, s));
         MPCG_OK_OR_DIE(h, merit_of(nullptr, &zero, 1, d_merit_ref));
         for (int it = 0; it < K; ++it) {
-            if (xuref) MPCG_OK_OR_DIE(h, LS(mpcg_generate_kkt_xuref)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, &ref, d_G, d_C, d_g, d_c, (uint32_t)B, s));
+            if (xuref) MPCG_OK_OR_DIE(h, LS(mpcg_generate_kkt_xuref)(h, plant_ctrl_b, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, &ref, d_G, d_C, d_g, d_c, (uint32_t)B, s));
             else MPCG_OK_OR_DIE(h, LS(mpcg_generate_kkt)(h, plant_ctrl, m, dt, d_goals, d_xs, d_xu, qd_cost, r_cost, d_G, d_C, d_g, d_c, (uint32_t)B, s));
             MPCG_OK_OR_DIE(h, LS(mpcg_form_schur_rhov)(h, m, d_G, d_C, d_g, d_c, d_S, d_Pinv, d_gamma, d_rho, (uint32_t)B, MPCG_PRECOND_SS, s));
             MPCG_OK_OR_DIE(h, LS(mpcg_pcg_solve)(h, d_S, d_Pinv, d_gamma, d_lambda, (uint32_t)B, PCG_MAX_ITER, (T)1e-7, MPCG_PRECOND_SS, d_iters, d_exit, s));
@@ -239,7 +289,8 @@ int main(int argc, char** argv) {
                                                         (uint32_t)B, s));
         }
         // the plant runs under the PREVIOUS plan for one period, offset by the previous period (include/mpcsim.cuh:288-291, :352)
-        MPCG_OK_OR_DIE(h, LS(mpcg_simulate)(h, plant_sim, m, d_xs, d_xu_old, dt, prev_us, period_us, (T)2e-4f, d_eePos, (uint32_t)B, s));
+        if (limits) hipLaunchKernelGGL(u_excess_peak, dim3(1), dim3(256), 0, s, d_xu, B, N, u_max, d_peak);
+        MPCG_OK_OR_DIE(h, LS(mpcg_simulate)(h, plant_sim_b, m, d_xs, d_xu_old, dt, prev_us, period_us, (T)2e-4f, d_eePos, (uint32_t)B, s));
         gpuErrchk(hipMemcpyAsync(d_xu_old, d_xu, (size_t)B * L * sizeof(T), hipMemcpyDeviceToDevice, s));
         const bool shift = clock.update(period_us);
         MPCG_OK_OR_DIE(h, LS(mpcg_advance_horizon)(h, m, shift ? 1 : 0, d_xu, d_lambda, d_goals, d_xs, d_eePos, d_bplan, d_bgoals, (uint32_t)TS, (uint32_t)TS, 0,
@@ -257,6 +308,9 @@ int main(int argc, char** argv) {
     gpuErrchk(hipMemcpy(offset.data(), d_offset, B * sizeof(int32_t), hipMemcpyDeviceToHost));
     gpuErrchk(hipMemcpy(xs_end.data(), d_xs, xs_end.size() * sizeof(T), hipMemcpyDeviceToHost));
 
+    double peak = 0.0;
+    if (limits) gpuErrchk(hipMemcpy(&peak, d_peak, sizeof(double), hipMemcpyDeviceToHost));
+
     bool ok = (int)mpc_errors.size() == mpc_steps;
     for (linsys_t e : mpc_errors) ok = ok && std::isfinite((double)e);
     for (int i = 0; i < shifts * B; ++i) ok = ok && std::isfinite((double)err[i]);
@@ -265,7 +319,8 @@ int main(int argc, char** argv) {
     printf("{\"batch\": %d, \"knots\": %d, \"updates\": %d, \"iters\": %d, ", B, N, U, K);
     if (flagged) printf("\"integrator\": %u, \"sim_integrator\": %u, ", integ, sim_integ);
     if (gravity != 0.0 || sim_gravity != 0.0) printf("\"gravity\": %g, \"sim_gravity\": %g, ", gravity, sim_gravity);
-    if (xuref) printf("\"q_cost\": %g, \"u_relative\": %d, ", q_cost, u_relative);
+    if (q_cost != 0.0 || u_relative != 0) printf("\"q_cost\": %g, \"u_relative\": %d, ", q_cost, u_relative);
+    if (limits) printf("\"u_max\": %g, \"u_weight\": %g, \"sim_saturate\": %d, \"u_excess_peak\": %.9g, ", u_max, u_weight, sim_saturate ? 1 : 0, peak);
     printf("\"expected_shifts\": %d, \"shifts\": [", shifts);
     for (int b = 0; b < B; ++b) printf("%s%d", b ? ", " : "", offset[b]);
     printf("], \"tracking_errors\": [");
@@ -284,6 +339,7 @@ int main(int argc, char** argv) {
                     (void*)d_exit, (void*)d_gave_up})
         gpuErrchk(hipFree(p));
     gpuErrchk(hipStreamDestroy(s));
+    if (limits) { gpuErrchk(hipFree(d_peak)); mpcg_plant_destroy(plant_ctrl_b); mpcg_plant_destroy(plant_sim_b); }
     if (plant_sim != plant_ctrl && plant_sim != plant) mpcg_plant_destroy(plant_sim);
     if (plant_ctrl != plant) mpcg_plant_destroy(plant_ctrl);
     mpcg_plant_destroy(plant);

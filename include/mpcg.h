@@ -396,7 +396,37 @@ int mpcg_block_solve_f64(mpcg_handle *h, const double *d_S, const double *d_gamm
  *                              device allocation (on src's device); source and clone may be destroyed in either order.  It allocates and copies
  *                              (hipMalloc, blocking hipMemcpy), as mpcg_plant_create does: neither is stream work, neither may be called while a stream
  *                              of the calling thread is being captured.  MPCG_ERR_INVALID: a NULL argument or a non-finite component (*out = NULL).
- *   mpcg_plant_get_gravity     the plant's vector ({0, 0, 0} for mpcg_plant_create / _create_iiwa14); MPCG_ERR_INVALID: a NULL argument. */
+ *   mpcg_plant_get_gravity     the plant's vector ({0, 0, 0} for mpcg_plant_create / _create_iiwa14); MPCG_ERR_INVALID: a NULL argument.
+ * LIMITS.  The reference has no inequality constraints.  Here a plant may carry SOFT joint, velocity and torque limits as model data, like its gravity: per
+ * joint a lower and an upper bound on q, qd and u (-INFINITY / +INFINITY: no bound on that side), one weight per kind, and flags.  With
+ *     viol(x; lo, hi) = x > hi ? x - hi : (x < lo ? x - lo : 0)          (strict comparisons: a value ON a bound violates nothing, and neither does a NaN)
+ * the running cost of the _xuref entries (below) given such a plant gains the one-sided quadratic penalty
+ *     J_k += 1/2 q_weight sum_i viol(q_i)^2 + 1/2 qd_weight sum_i viol(qd_i)^2 + [k < N-1] 1/2 u_weight sum_i viol(u_i)^2.
+ * It is C^1 and its Gauss-Newton Hessian is a non-negative diagonal, so mpcg_generate_kkt_xuref(_f64) adds w [viol != 0] to Q_k[i, i], Q_k[7 + i, 7 + i] and
+ * R_k[i, i] and w viol to q_k[i], q_k[7 + i] and r_k[i] (the last block at x_{N-1}, where its joint-space terms are) — C and c are untouched, and the Schur
+ * formation, both solvers, dz, the line search and the rho rule take it as they are.  mpcg_compute_merit_xuref(_f64) adds exactly the sum above, every knot at
+ * its own state.  Every build honours it (both gradient routes, "kkt_f32" = 1 and 2, "merit_f32", both integrators, float and double) as one more value of the
+ * kernels' compile-time cost, launched exactly when the plant given has limits: a plant without limits runs the device code it ran before.  The float builds
+ * ("kkt_f32", "merit_f32") use the bounds and weights ROUNDED TO FLOAT; every other build, the float entries' default included, uses them as doubles.
+ * A NaN state or control violates no bound: it adds nothing here and poisons what it poisoned before, its own trajectory only.
+ * The PLAIN entries mpcg_generate_kkt(_f64) and mpcg_compute_merit(_f64) given a plant with limits return MPCG_ERR_UNSUPPORTED and launch nothing: use the
+ * _xuref entries with the neutral cost (ee_cost = 1, q_cost = 0, no flags) — the two families differ in where the last block's velocity term is evaluated,
+ * and a silent switch would change numbers.  mpcg_inverse_dynamics(_f64) ignores limits.
+ * MPCG_LIMITS_SIM_SATURATE: mpcg_simulate(_f64) given such a plant clamps every control it applies to [u_lo, u_hi] (the double bounds, in either entry; a NaN
+ * control passes) where it is loaded and widened — the actuator saturates — and changes nothing else.  Without the flag mpcg_simulate ignores limits.  The
+ * controller's plant and the simulated plant may differ in this, as they may in gravity.
+ *   mpcg_plant_clone_limits    *out = a NEW plant, the tables AND GRAVITY of src with the limits given (replacing any src had); a gravity clone of a limits
+ *                              plant keeps its limits.  A clone and not a setter, with the allocation and capture rules of mpcg_plant_clone_gravity.
+ *                              MPCG_ERR_INVALID (*out = NULL): a NULL argument; a NaN bound; lo > hi; lo = +inf or hi = -inf; a weight that is negative
+ *                              or not finite; an unknown flag bit.
+ *   mpcg_plant_get_limits      *has_limits = 1 and *out = the limits as given for a limits clone; 0 for any other plant (*out: no bounds, zero weights, no
+ *                              flags).  MPCG_ERR_INVALID: a NULL argument. */
+#define MPCG_LIMITS_SIM_SATURATE 1u
+typedef struct mpcg_limits {
+    double q_lo[7], q_hi[7], qd_lo[7], qd_hi[7], u_lo[7], u_hi[7]; /* -INFINITY / +INFINITY: no bound on that side */
+    double q_weight, qd_weight, u_weight;                          /* finite, >= 0 */
+    uint32_t flags;                                                /* MPCG_LIMITS_* */
+} mpcg_limits;
 typedef struct mpcg_plant mpcg_plant;
 int mpcg_plant_create(mpcg_plant **out, int device, uint32_t num_joints, const double *X_const, const double *I_spatial,
                       const double *Xhom_const, const int32_t *X_trig_idx, const double *X_trig_coef, const int32_t *X_trig_j,
@@ -407,6 +437,8 @@ int mpcg_plant_create(mpcg_plant **out, int device, uint32_t num_joints, const d
 int mpcg_plant_create_iiwa14(mpcg_plant **out, int device);
 int mpcg_plant_clone_gravity(mpcg_plant **out, const mpcg_plant *src, const double base_accel[3]);
 int mpcg_plant_get_gravity(const mpcg_plant *p, double out[3]);
+int mpcg_plant_clone_limits(mpcg_plant **out, const mpcg_plant *src, const mpcg_limits *lim);
+int mpcg_plant_get_limits(const mpcg_plant *p, mpcg_limits *out, int *has_limits);
 int mpcg_plant_destroy(mpcg_plant *p);
 /* mpcg_inverse_dynamics: d_tau[i] = ID(q_i, qd_i, qdd_i) of the plant, ITS GRAVITY INCLUDED, for count independent states (arrays [count][7]; d_qd and
  * d_qdd may each be NULL: zero).  With both NULL it returns the gravity torques — what the controls of a plan made for zero gravity must gain before a
@@ -558,6 +590,7 @@ int mpcg_line_search_step_rho_f64(mpcg_handle *h, uint32_t control_size, const d
  * mpcg_compute_merit_xuref(_f64) is mpcg_compute_merit(_f64) with J_k above, every knot (the last included) at its own state against its own row; violation
  *   terms, mu, d_xs, the one-rounding trial iterate, the fixed-order sums, "merit_f32" and the shared scratch with its first-call allocation are unchanged, and
  *   mpcg_line_search_step(_rho)(_f64) follow it as they are.
+ * A plant with LIMITS (mpcg_plant_clone_limits, above) adds its penalty to J_k in both calls; these entries are the only ones that honour it.
  *
  * mpcg_xuref is a HOST struct, copied into the launch: a captured graph keeps its scalars and pointers.  d_traj_offset is DEVICE data read when the kernel
  * runs and is not validated (the clamp keeps every read inside the plan): a captured graph follows what mpcg_advance_horizon has written since.
@@ -607,6 +640,7 @@ int mpcg_compute_merit_xuref_f64(mpcg_handle *h, const mpcg_plant *plant, uint32
  *   there, :322-324), or of (uint32)(toff / timestep) if S = 0.  A remainder of exactly 0 is not run: sim_time_us = 0 leaves d_xs bitwise unchanged.
  * A substep is explicit Euler from the old values, q += dt qd, qd += dt qdd, qdd = forward dynamics of the mpcg_plant given (its own gravity vector: GRAVITY under mpcg_plant_create) in float64
  * (the arithmetic of mpcg_generate_kkt's integrator defect).  Substeps are gated on their number, never on time accumulated in float.
+ * A plant whose limits carry MPCG_LIMITS_SIM_SATURATE (mpcg_plant_clone_limits) clamps every control it applies to [u_lo, u_hi] as it is loaded; a NaN passes.
  * Option "sim_integrator" = 1 (default 0; 0 or 1, anything else MPCG_ERR_INVALID; read when the call is made) makes every substep SEMI-IMPLICIT Euler,
  * qd' = qd + dt qdd, q' = q + dt qd' (integrator.cuh:103-130, INTEGRATOR_TYPE == 1), for mpcg_simulate and mpcg_simulate_f64; the schedule, the clamp and
  * the float64 state carried across substeps are unchanged.  It is an option of its own, apart from "integrator", because the reference's plant simulation

@@ -24,12 +24,20 @@ MPCG_STEP_FROZEN = -2
 MPCG_SIM_MAX_SUBSTEPS = 65536
 MPCG_XUREF_QD_RELATIVE = 1
 MPCG_XUREF_U_RELATIVE = 2
+MPCG_LIMITS_SIM_SATURATE = 1
 
 
 class mpcg_xuref(C.Structure):
     """The HOST struct of the _xuref entries (include/mpcg.h), copied into the launch."""
     _fields_ = [("d_xu_traj", C.c_void_p), ("traj_steps", C.c_uint32), ("traj_batch_stride", C.c_uint32), ("d_traj_offset", C.c_void_p),
                 ("ee_cost", C.c_double), ("q_cost", C.c_double), ("flags", C.c_uint32)]
+
+
+class mpcg_limits(C.Structure):
+    """The soft limits of a plant (include/mpcg.h, LIMITS): -inf / +inf = no bound on that side."""
+    _fields_ = [("q_lo", C.c_double * 7), ("q_hi", C.c_double * 7), ("qd_lo", C.c_double * 7), ("qd_hi", C.c_double * 7),
+                ("u_lo", C.c_double * 7), ("u_hi", C.c_double * 7),
+                ("q_weight", C.c_double), ("qd_weight", C.c_double), ("u_weight", C.c_double), ("flags", C.c_uint32)]
 
 
 # every symbol include/mpcg.h declares: (name, restype, argtypes)
@@ -74,6 +82,8 @@ SYMBOLS = {
     "mpcg_plant_create_iiwa14": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
     "mpcg_plant_clone_gravity": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_double)]),
     "mpcg_plant_get_gravity": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "mpcg_plant_clone_limits": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(mpcg_limits)]),
+    "mpcg_plant_get_limits": (C.c_int, [C.c_void_p, C.POINTER(mpcg_limits), C.POINTER(C.c_int)]),
     "mpcg_inverse_dynamics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_inverse_dynamics_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_plant_destroy": (C.c_int, [C.c_void_p]),

@@ -70,7 +70,19 @@ template <typename R> struct PlantDevT {
     R ET[PJ][9], BT[PJ][9];
     R Ib[PJ][10];                                // Ixx Ixy Ixz Iyy Iyz Izz  hx hy hz  m
     R grav[3];                                   // linear spatial acceleration the root starts from, base frame (GRiD's scalar `gravity` g: {0, 0, g}); behind Ib: no offset above moves
+    // soft limits (mpcg_plant_clone_limits; read by the COST = 2 instantiations and by simulate_kernel<IO, INTEGRATOR, 1> only), behind grav: no offset above moves.
+    // Entry l of [q; qd] is bounded by xlo[l], xhi[l] — the lane that owns entry l reads its own pair — and u_l by ulo[l], uhi[l]; -inf / +inf: no bound.
+    // A plant without limits holds -inf / +inf and zero weights.
+    R xlo[2 * PJ], xhi[2 * PJ], ulo[PJ], uhi[PJ];
+    R limw[3];                                   // q_weight, qd_weight, u_weight
 };
+// viol(x; lo, hi) of the limits penalty: strict comparisons, so a value ON a bound and a NaN violate nothing
+template <typename S> __device__ __forceinline__ S lim_viol(S x, S lo, S hi) { return x > hi ? x - hi : (x < lo ? x - lo : S(0)); }
+// what a store of the KKT kernel holds: `base` (COST = 1's expression, untouched in the COST < 2 instantiations) plus, with COST = 2, the limits term `extra`
+template <int COST, typename S> __device__ __forceinline__ S lim_plus(S base, S extra) {
+    if constexpr (COST == 2) return base + extra;
+    else return base;
+}
 typedef PlantDevT<double> PlantDev;              // R = double: the round-2..5 kernel (float64 inside, the checker of the float build); R = float (round 6): linsys_t's own
                                                  // arithmetic, what the reference's GRiD code runs in (gato_plant::forwardDynamicsAndGradient<T>, T = linsys_t = float)
 
@@ -112,6 +124,11 @@ template <typename S, typename IO> struct XuRefT {
 template <typename S, typename IO = float> struct KktXuArgsT : KktArgsT<S, IO> { XuRefT<S, IO> ref; };
 template <int COST, typename S, typename IO> struct KktArgsSel { typedef KktArgsT<S, IO> type; };
 template <typename S, typename IO> struct KktArgsSel<1, S, IO> { typedef KktXuArgsT<S, IO> type; };
+// COST = 2 (the _xuref entries given a plant with limits): COST = 1 plus the one-sided quadratic penalty of the plant's soft limits,
+//     J_k += 1/2 q_weight sum_i viol(q_i)^2 + 1/2 qd_weight sum_i viol(qd_i)^2 + [k < N-1] 1/2 u_weight sum_i viol(u_i)^2,   viol = lim_viol above;
+// its Gauss-Newton Hessian is a non-negative diagonal: w [viol != 0] to Q_k[l, l] and R_k[i, i], w viol to q_k[l] and r_k[i] (the last block at x_{N-1}, where COST = 1's
+// joint-space terms are).  Bounds and weights are the plant's (PlantDevT::xlo ...): the arguments are COST = 1's.  Every `COST >= 1` below is what COST = 1 does.
+template <typename S, typename IO> struct KktArgsSel<2, S, IO> { typedef KktXuArgsT<S, IO> type; };
 
 // The model tables are read through the CONSTANT address space (same 64-bit address as the global pointer): loads from it are
 // invariant by definition, so a uniform address makes them scalar loads (s_load, scalar cache).  Through the plain global
@@ -125,6 +142,11 @@ template <typename R> struct PlantC {
     __device__ __forceinline__ creal* BT(int k) const { return at(offsetof(PlantDevT<R>, BT), k, 9); }
     __device__ __forceinline__ creal* Ib(int k) const { return at(offsetof(PlantDevT<R>, Ib), k, 10); }
     __device__ __forceinline__ creal* grav() const { return at(offsetof(PlantDevT<R>, grav), 0, 0); }
+    __device__ __forceinline__ creal* xlo() const { return at(offsetof(PlantDevT<R>, xlo), 0, 0); }
+    __device__ __forceinline__ creal* xhi() const { return at(offsetof(PlantDevT<R>, xhi), 0, 0); }
+    __device__ __forceinline__ creal* ulo() const { return at(offsetof(PlantDevT<R>, ulo), 0, 0); }
+    __device__ __forceinline__ creal* uhi() const { return at(offsetof(PlantDevT<R>, uhi), 0, 0); }
+    __device__ __forceinline__ creal* limw() const { return at(offsetof(PlantDevT<R>, limw), 0, 0); }
 };
 
 // ---- arithmetic types of the kernel: double (default), float ("kkt_f32" = 1 below a full batch), and kkt_f2 = TWO knots per lane in packed float
@@ -484,7 +506,7 @@ __device__ __forceinline__ void kkt_copy_out(T* dst, L* src, int l) {
 // R = double | float: a lane group of 16 = one (trajectory, knot) pair per trip; R = kkt_f2: TWO — items 2 i and 2 i + 1 of the wavefront's eight — in the halves of every value.
 // IO = float: mpcg_generate_kkt; IO = double (R = double only): mpcg_generate_kkt_f64, float64 inside, double arrays in and out.  Only the loads and the output
 // staging depend on IO; INTEGRATOR (0 explicit, 1 semi-implicit Euler) is read in `if constexpr` only.  (A shared __device__ body was tried and changed the float kernels' code.)
-// COST (0: the end-effector plant's cost, 1: the generalised cost over a joint-space plan, KktXuArgsT) is read in `if constexpr` only, as INTEGRATOR.
+// COST (0: the end-effector plant's cost, 1: the generalised cost over a joint-space plan, KktXuArgsT, 2: that plus the plant's soft limits) is read in `if constexpr` only, as INTEGRATOR.
 template <bool ANALYTIC, typename R = double, int INTEGRATOR = 0, typename IO = float, int COST = 0>
 __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALYTIC ? KKT_WAVES_ANALYTIC : 2) void generate_kkt_kernel(typename KktArgsSel<COST, typename KktR<R>::scalar, IO>::type a) {
     typedef KktR<R> T;
@@ -539,7 +561,7 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
         // COST = 1: the trajectory's plan offset is asked for here, the plan row that depends on it behind the sines and cosines (two dependent loads in a row at the
         // top of the trip were 10 % of the kernel's time at two wavefronts per SIMD)
         [[maybe_unused]] int roff[KP];
-        if constexpr (COST == 1) {
+        if constexpr (COST >= 1) {
 #pragma unroll
             for (int hf = 0; hf < KP; ++hf) roff[hf] = a.ref.offset(bb[hf]);
         }
@@ -558,7 +580,7 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
         // COST = 1: the plan row of the knot, read ONCE per item, here, and kept as the arrays' type until the store epilogue: lane l holds entry l of x_ref, of u_ref
         // (lanes 0..6) and, for the last block, of the x_ref of knot k + 1 (always a row of the plan: the clamp).  Every lane reads (lanes 14, 15 an entry they drop).
         [[maybe_unused]] IO rvx[KP], rvu[KP], rvx1[KP];
-        if constexpr (COST == 1) {
+        if constexpr (COST >= 1) {
             const int lx = l < n ? l : n - 1, lu = l < m ? l : m - 1;
 #pragma unroll
             for (int hf = 0; hf < KP; ++hf) {
@@ -643,7 +665,7 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
 #pragma unroll
             for (int hf = 0; hf < KP; ++hf) goal[hf] = a.eePos_traj + ((size_t)bb[hf] * N + kk[hf]) * 6;
             R s0 = KR(0.0), s1 = KR(0.0);
-            if constexpr (COST == 1) {                        // d_eePos_traj may be NULL (ee_cost = 0): no goal is read, and ee_cost x (a finite gq) = 0
+            if constexpr (COST >= 1) {                        // d_eePos_traj may be NULL (ee_cost = 0): no goal is read, and ee_cost x (a finite gq) = 0
                 const bool goals = a.eePos_traj != nullptr;
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
@@ -703,12 +725,21 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
                 // COST = 1: Q = blkdiag(ee_cost g g^T + q_cost I, QD I), q = [ee_cost g + q_cost (q - q_ref); QD (qd - [QD_REL] qd_ref)], r = R (u - [U_REL] u_ref); the last block's
                 // joint-space terms at x_{N-1} against its own row, its end-effector term as before.  (ee_cost = 1, q_cost = 0, no flags: every product and sum below is exact.)
                 [[maybe_unused]] S egl = gql, eg1l = gq1l, rdx = S(0.0), rdx1 = S(0.0), rdu = S(0.0);
-                if constexpr (COST == 1) {
+                if constexpr (COST >= 1) {
                     egl = a.ref.ee_cost * gql; eg1l = a.ref.ee_cost * gq1l;
                     const bool rel = l < PJ || (a.ref.flags & XUREF_QD_RELATIVE) != 0;      // x_l - ref_l: q - q_ref; qd - [QD_REL] qd_ref
                     rdx = T::get(I->Xq[l], hf) - (rel ? (S)rvx[hf] : S(0.0));
                     rdx1 = (S)xu[hf][(n + m) + l] - (rel ? (S)rvx1[hf] : S(0.0));            // x_{k+1} against the row of knot k + 1: the last block's (iiwa_plant.cuh:300-323)
                     if (l < m) rdu = T::get(I->U[l], hf) - ((a.ref.flags & XUREF_U_RELATIVE) != 0 ? (S)rvu[hf] : S(0.0));
+                }
+                // COST = 2: the limits penalty of entry l of x_k, of x_{k+1} (the last block's) and of u_k — this lane's own bounds, read here, behind the recursion
+                [[maybe_unused]] S lwx = S(0.0), lvx = S(0.0), lvx1 = S(0.0), lwu = S(0.0), lvu = S(0.0);
+                if constexpr (COST == 2) {
+                    const S lo = P.xlo()[l], hi = P.xhi()[l];
+                    lwx = P.limw()[l < PJ ? 0 : 1];
+                    lvx = lim_viol(T::get(I->Xq[l], hf), lo, hi);
+                    lvx1 = lim_viol((S)xu[hf][(n + m) + l], lo, hi);
+                    if (l < m) { lwu = P.limw()[2]; lvu = lim_viol(T::get(I->U[l], hf), (S)P.ulo()[l], (S)P.uhi()[l]); }
                 }
                 // column l (column-major):  A = I + dt [[0, I], [dqdd/dq, dqdd/dqd]] (semi-implicit: [[dt dqdd/dq, I + dt dqdd/dqd], [dqdd/dq, dqdd/dqd]]),  Q = blkdiag(g g^T, QD I)
 #pragma unroll
@@ -722,17 +753,18 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
                     st[ST_C + l * n + r] = (float)(-av);
                     S qv, q1;
                     if (r < PJ) {
-                        if constexpr (COST == 1) { qv = T::get(I->Gq[r], hf) * egl; q1 = T::get(I->Gq1[r], hf) * eg1l; }      // (+ q_cost on the diagonal: below)
+                        if constexpr (COST >= 1) { qv = T::get(I->Gq[r], hf) * egl; q1 = T::get(I->Gq1[r], hf) * eg1l; }      // (+ q_cost on the diagonal: below)
                         else { qv = T::get(I->Gq[r], hf) * gql; q1 = T::get(I->Gq1[r], hf) * gq1l; }
                     }
-                    else if constexpr (COST == 1) qv = q1 = S(0.0);
+                    else if constexpr (COST >= 1) qv = q1 = S(0.0);
                     else qv = q1 = (r == l) ? a.qd_cost : S(0.0);
                     st[ST_G + l * n + r] = (float)qv;
                     st[ST_Q1 + l * n + r] = (float)q1;
                 }
-                if constexpr (COST == 1) {                    // the diagonal of Q, by its own lane at a run-time index: (r == l) ? q_cost : 0 per row would be seven
-                    st[ST_G + l * n + l] = (float)(l < PJ ? gql * egl + a.ref.q_cost : a.qd_cost);      // loop-invariant selects the compiler keeps in registers across the recursion
-                    st[ST_Q1 + l * n + l] = (float)(l < PJ ? gq1l * eg1l + a.ref.q_cost : a.qd_cost);
+                if constexpr (COST >= 1) {                    // the diagonal of Q, by its own lane at a run-time index: (r == l) ? q_cost : 0 per row would be seven
+                    // loop-invariant selects the compiler keeps in registers across the recursion; COST = 2: + w [viol != 0]
+                    st[ST_G + l * n + l] = (float)lim_plus<COST, S>(l < PJ ? gql * egl + a.ref.q_cost : a.qd_cost, lvx != S(0.0) ? lwx : S(0.0));
+                    st[ST_Q1 + l * n + l] = (float)lim_plus<COST, S>(l < PJ ? gq1l * eg1l + a.ref.q_cost : a.qd_cost, lvx1 != S(0.0) ? lwx : S(0.0));
                 }
                 if (l < m) {
 #pragma unroll
@@ -742,13 +774,15 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
                     }
 #pragma unroll
                     for (int r = 0; r < m; ++r) st[ST_G + nn + l * m + r] = (float)(r == l ? a.r_cost : S(0.0));
-                    if constexpr (COST == 1) st[ST_g + n + l] = (float)(a.r_cost * rdu);
+                    // COST = 2: R's diagonal gains w [viol != 0], by its own lane (the store above it is this lane's: program order), and r gains w viol
+                    if constexpr (COST == 2) st[ST_G + nn + l * m + l] = (float)(a.r_cost + (lvu != S(0.0) ? lwu : S(0.0)));
+                    if constexpr (COST >= 1) st[ST_g + n + l] = (float)lim_plus<COST, S>(a.r_cost * rdu, lwu * lvu);
                     else st[ST_g + n + l] = (float)(a.r_cost * T::get(I->U[l], hf));
                 }
                 const S qdl = T::get(I->Xq[l < PJ ? l + PJ : l], hf);              // qd_{l mod 7}
-                if constexpr (COST == 1) {
-                    st[ST_g + l] = (float)(l < PJ ? egl + a.ref.q_cost * rdx : a.qd_cost * rdx);
-                    st[ST_g1 + l] = (float)(l < PJ ? eg1l + a.ref.q_cost * rdx1 : a.qd_cost * rdx1);
+                if constexpr (COST >= 1) {
+                    st[ST_g + l] = (float)lim_plus<COST, S>(l < PJ ? egl + a.ref.q_cost * rdx : a.qd_cost * rdx, lwx * lvx);
+                    st[ST_g1 + l] = (float)lim_plus<COST, S>(l < PJ ? eg1l + a.ref.q_cost * rdx1 : a.qd_cost * rdx1, lwx * lvx1);
                 } else {
                 st[ST_g + l] = (float)(l < PJ ? gql : a.qd_cost * qdl);
                 st[ST_g1 + l] = (float)(l < PJ ? gq1l : a.qd_cost * qdl);  // last block only (evaluated at x_{N-2}: iiwa_eepos_plant.cuh:407)
@@ -789,13 +823,23 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
             const S dt = a.dt;
             const S gql = l < PJ ? I->Gq[l] : S(0.0), gq1l = l < PJ ? I->Gq1[l] : S(0.0);
             [[maybe_unused]] S egl = gql, eg1l = gq1l, rdx = S(0.0), rdx1 = S(0.0), rdu = S(0.0);           // COST = 1: as the float arrays' path above, expression for expression
-            if constexpr (COST == 1) {
+            if constexpr (COST >= 1) {
                 egl = a.ref.ee_cost * gql; eg1l = a.ref.ee_cost * gq1l;
                 if (l < n) {
                     const bool rel = l < PJ || (a.ref.flags & XUREF_QD_RELATIVE) != 0;
                     rdx = I->Xq[l] - (rel ? (S)rvx[0] : S(0.0));
                     rdx1 = (S)xu[0][(n + m) + l] - (rel ? (S)rvx1[0] : S(0.0));
                     if (l < m) rdu = I->U[l] - ((a.ref.flags & XUREF_U_RELATIVE) != 0 ? (S)rvu[0] : S(0.0));
+                }
+            }
+            [[maybe_unused]] S lwx = S(0.0), lvx = S(0.0), lvx1 = S(0.0), lwu = S(0.0), lvu = S(0.0);      // COST = 2: as the float arrays' path above
+            if constexpr (COST == 2) {
+                if (l < n) {
+                    const S lo = P.xlo()[l], hi = P.xhi()[l];
+                    lwx = P.limw()[l < PJ ? 0 : 1];
+                    lvx = lim_viol((S)I->Xq[l], lo, hi);
+                    lvx1 = lim_viol((S)xu[0][(n + m) + l], lo, hi);
+                    if (l < m) { lwu = P.limw()[2]; lvu = lim_viol((S)I->U[l], (S)P.ulo()[l], (S)P.uhi()[l]); }
                 }
             }
             IO* G = a.G + (size_t)b * ((size_t)(nn + mm) * N - mm) + (size_t)(nn + mm) * k;
@@ -827,20 +871,21 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
             if (l < n && on) {
 #pragma unroll
                 for (int r = 0; r < n; ++r) {
-                    if constexpr (COST == 1) sd[SD_G + l * n + r] = r < PJ ? I->Gq[r] * egl : S(0.0);      // (the diagonal: below, at a run-time index — see the float arrays' path)
+                    if constexpr (COST >= 1) sd[SD_G + l * n + r] = r < PJ ? I->Gq[r] * egl : S(0.0);      // (the diagonal: below, at a run-time index — see the float arrays' path)
                     else sd[SD_G + l * n + r] = r < PJ ? I->Gq[r] * gql : ((r == l) ? a.qd_cost : S(0.0));
                 }
-                if constexpr (COST == 1) sd[SD_G + l * n + l] = l < PJ ? gql * egl + a.ref.q_cost : a.qd_cost;
+                if constexpr (COST >= 1) sd[SD_G + l * n + l] = lim_plus<COST, S>(l < PJ ? gql * egl + a.ref.q_cost : a.qd_cost, lvx != S(0.0) ? lwx : S(0.0));
                 if (l < m) {
 #pragma unroll
                     for (int r = 0; r < m; ++r) sd[SD_G + nn + l * m + r] = r == l ? a.r_cost : S(0.0);
-                    if constexpr (COST == 1) sd[SD_g + n + l] = a.r_cost * rdu;
+                    if constexpr (COST == 2) sd[SD_G + nn + l * m + l] = a.r_cost + (lvu != S(0.0) ? lwu : S(0.0));
+                    if constexpr (COST >= 1) sd[SD_g + n + l] = lim_plus<COST, S>(a.r_cost * rdu, lwu * lvu);
                     else sd[SD_g + n + l] = a.r_cost * I->U[l];
                 }
                 const S qdl = I->Xq[l < PJ ? l + PJ : l];
-                if constexpr (COST == 1) {
-                    sd[SD_g + l] = l < PJ ? egl + a.ref.q_cost * rdx : a.qd_cost * rdx;
-                    sd[SD_g1 + l] = l < PJ ? eg1l + a.ref.q_cost * rdx1 : a.qd_cost * rdx1;
+                if constexpr (COST >= 1) {
+                    sd[SD_g + l] = lim_plus<COST, S>(l < PJ ? egl + a.ref.q_cost * rdx : a.qd_cost * rdx, lwx * lvx);
+                    sd[SD_g1 + l] = lim_plus<COST, S>(l < PJ ? eg1l + a.ref.q_cost * rdx1 : a.qd_cost * rdx1, lwx * lvx1);
                 } else {
                 sd[SD_g + l] = l < PJ ? gql : a.qd_cost * qdl;
                 sd[SD_g1 + l] = l < PJ ? gq1l : a.qd_cost * qdl;
@@ -866,10 +911,10 @@ __global__ __launch_bounds__(KKT_THREADS, sizeof(R) == 4 ? KKT_WAVES_F32 : ANALY
             if (l < n && on && lastblk) {
 #pragma unroll
                 for (int r = 0; r < n; ++r) {
-                    if constexpr (COST == 1) sd[l * n + r] = r < PJ ? I->Gq1[r] * eg1l : S(0.0);
+                    if constexpr (COST >= 1) sd[l * n + r] = r < PJ ? I->Gq1[r] * eg1l : S(0.0);
                     else sd[l * n + r] = r < PJ ? I->Gq1[r] * gq1l : ((r == l) ? a.qd_cost : S(0.0));
                 }
-                if constexpr (COST == 1) sd[l * n + l] = l < PJ ? gq1l * eg1l + a.ref.q_cost : a.qd_cost;
+                if constexpr (COST >= 1) sd[l * n + l] = lim_plus<COST, S>(l < PJ ? gq1l * eg1l + a.ref.q_cost : a.qd_cost, lvx1 != S(0.0) ? lwx : S(0.0));
             }
             __syncthreads();
             if (live[0] && on && lastblk) kkt_copy_out<nn>(G + nn + mm, sd, l);

@@ -66,9 +66,11 @@ template <typename IO, typename S = double> struct MeritArgsT {
 template <typename IO, typename S = double> struct MeritXuArgsT : MeritArgsT<IO, S> { XuRefT<S, IO> ref; };
 template <int COST, typename IO, typename S> struct MeritArgsSel { typedef MeritArgsT<IO, S> type; };
 template <typename IO, typename S> struct MeritArgsSel<1, IO, S> { typedef MeritXuArgsT<IO, S> type; };
+// COST = 2 (the plant given has limits): COST = 1 plus the limits penalty of kkt_plant.hip.h (KktArgsSel<2>), every knot at its own state; the arguments are COST = 1's
+template <typename IO, typename S> struct MeritArgsSel<2, IO, S> { typedef MeritXuArgsT<IO, S> type; };
 
 // IO = float: mpcg_compute_merit; IO = double: mpcg_compute_merit_f64.  Only the loads and the trial iterate depend on IO; INTEGRATOR: 0 explicit, 1 semi-implicit
-// Euler; COST: 0 the end-effector plant's cost, 1 the generalised cost (`if constexpr` only).  (A shared __device__ body was tried and changed the float kernel's code.)
+// Euler; COST: 0 the end-effector plant's cost, 1 the generalised cost, 2 that plus the plant's soft limits (`if constexpr` only).  (A shared __device__ body was tried and changed the float kernel's code.)
 template <typename IO, int INTEGRATOR = 0, int COST = 0>
 __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(typename MeritArgsSel<COST, IO, double>::type a) {
     typedef double R;
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(typename M
         const size_t xk = (size_t)k * (n + m);
         double ul = 0.0, xn_q = 0.0, xn_qd = 0.0;
         [[maybe_unused]] int roff = 0;                       // COST = 1: the plan offset is asked for here, the row that depends on it behind the sines and cosines
-        if constexpr (COST == 1) roff = a.ref.offset(b);
+        if constexpr (COST >= 1) roff = a.ref.offset(b);
         if (l < n) I->Xq[l] = trial(xk + l);
         if (l < m) {
             if (dyn) { ul = trial(xk + n + l); xn_q = trial(xk + (n + m) + l); xn_qd = trial(xk + (n + m) + PJ + l); }
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(typename M
         // COST = 1: joint l's entries of the knot's plan row, read ONCE per item, here, kept as the arrays' type (every lane reads: lanes 7..15 an entry they drop;
         // a row has its 21 entries at the last knot too)
         [[maybe_unused]] IO rvq = 0, rvqd = 0, rvu = 0;
-        if constexpr (COST == 1) {
+        if constexpr (COST >= 1) {
             const IO* ref = a.ref.row(b, roff, k) + (l < m ? l : m - 1);
             rvq = ref[0]; rvqd = ref[PJ]; rvu = ref[n];
         }
@@ -192,10 +194,10 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(typename M
             const R ee2 = -(W1[0] * V0[0] + W1[1] * V0[1] + W1[2] * V0[2]);
             const R q = I->Xq[l], qd = I->Xq[PJ + l];
             R pm;
-            if constexpr (COST == 1) { const R dqd = qd - ((a.ref.flags & XUREF_QD_RELATIVE) != 0 ? (R)rvqd : 0.0); pm = 0.5 * a.qd_cost * dqd * dqd; }
+            if constexpr (COST >= 1) { const R dqd = qd - ((a.ref.flags & XUREF_QD_RELATIVE) != 0 ? (R)rvqd : 0.0); pm = 0.5 * a.qd_cost * dqd * dqd; }
             else pm = 0.5 * a.qd_cost * qd * qd;
             if (l < 3) {                                     // lanes 0..2: one coordinate of the tracking error each
-                if constexpr (COST == 1) {
+                if constexpr (COST >= 1) {
                     if (a.eePos_traj) {                      // (NULL with ee_cost = 0: no goal is read)
                         const IO* goal = a.eePos_traj + ((size_t)b * N + k) * 6;
                         const R d = (l == 0 ? ee0 : (l == 1 ? ee1 : ee2)) - (R)goal[l];
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(typename M
             }
             R viol = 0.0;
             if (dyn) {
-                if constexpr (COST == 1) { const R du = ul - ((a.ref.flags & XUREF_U_RELATIVE) != 0 ? (R)rvu : 0.0); pm += 0.5 * a.r_cost * du * du; }
+                if constexpr (COST >= 1) { const R du = ul - ((a.ref.flags & XUREF_U_RELATIVE) != 0 ? (R)rvu : 0.0); pm += 0.5 * a.r_cost * du * du; }
                 else
                 pm += 0.5 * a.r_cost * ul * ul;
                 if constexpr (INTEGRATOR == 1) {                  // semi-implicit Euler: q' = q + dt qd', qd' = qd + dt qdd (the map the KKT kernel linearised)
@@ -219,7 +221,13 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_kernel(typename M
                 viol = fabs(xn_q - (q + a.dt * qd)) + fabs(xn_qd - (qd + a.dt * qdd));
             }
             if (k == 0 && a.xs) viol += fabs(q - (R)a.xs[(size_t)b * n + l]) + fabs(qd - (R)a.xs[(size_t)b * n + PJ + l]);
-            if constexpr (COST == 1) { const R dq = q - (R)rvq; pm += 0.5 * a.ref.q_cost * dq * dq; }      // the joint-space term: behind the existing ones
+            if constexpr (COST >= 1) { const R dq = q - (R)rvq; pm += 0.5 * a.ref.q_cost * dq * dq; }      // the joint-space term: behind the existing ones
+            if constexpr (COST == 2) {                       // the limits penalty of joint l: behind that (this lane's own bounds, read here)
+                const R vq = lim_viol(q, (R)P.xlo()[l], (R)P.xhi()[l]), vqd = lim_viol(qd, (R)P.xlo()[PJ + l], (R)P.xhi()[PJ + l]);
+                pm += 0.5 * P.limw()[0] * vq * vq;
+                pm += 0.5 * P.limw()[1] * vqd * vqd;
+                if (dyn) { const R vu = lim_viol(ul, (R)P.ulo()[l], (R)P.uhi()[l]); pm += 0.5 * P.limw()[2] * vu * vu; }
+            }
             I->Gq[l] = pm + a.mu * viol;
         }
         __syncthreads();

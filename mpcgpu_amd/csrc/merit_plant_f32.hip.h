@@ -92,7 +92,7 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(typena
             return moved[hf] ? t : x;
         };
         [[maybe_unused]] int roff[KP] = {0, 0};             // COST = 1: the plan offsets are asked for here, the rows that depend on them behind the sines and cosines
-        if constexpr (COST == 1) { roff[0] = a.ref.offset(bb[0]); roff[1] = a.ref.offset(bb[1]); }
+        if constexpr (COST >= 1) { roff[0] = a.ref.offset(bb[0]); roff[1] = a.ref.offset(bb[1]); }
         if (l < n) I->Xq[l] = T::mk(trial(0, xk[0] + l), trial(1, xk[1] + l));
         if (l < m) {
             float u_[KP], nq_[KP], nqd_[KP], sn_[KP], cs_[KP];
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(typena
         // COST = 1: joint l's entries of each half's plan row, read ONCE per item, here (every lane reads: lanes 7..15 an entry they drop; a cost-only half: a row
         // has its 21 entries, and what it computes from u_ref is dropped by the select)
         [[maybe_unused]] R rq = sp(0.f), rqd = sp(0.f), ru = sp(0.f);
-        if constexpr (COST == 1) {
+        if constexpr (COST >= 1) {
             const float* ref0 = a.ref.row(bb[0], roff[0], kk[0]) + (l < m ? l : m - 1);
             const float* ref1 = a.ref.row(bb[1], roff[1], kk[1]) + (l < m ? l : m - 1);
             rq = T::mk(ref0[0], ref1[0]); rqd = T::mk(ref0[PJ], ref1[PJ]); ru = T::mk(ref0[n], ref1[n]);
@@ -182,10 +182,10 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(typena
             const R ee2 = -(W1[0] * V0[0] + W1[1] * V0[1] + W1[2] * V0[2]);
             const R q = I->Xq[l], qd = I->Xq[PJ + l], ul = I->U[l], xn_q = I->Qdd[l], xn_qd = I->Gq1[l];
             R pm;
-            if constexpr (COST == 1) { const R dqd = (a.ref.flags & XUREF_QD_RELATIVE) != 0 ? qd - rqd : qd; pm = sp(0.5f * a.qd_cost) * dqd * dqd; }
+            if constexpr (COST >= 1) { const R dqd = (a.ref.flags & XUREF_QD_RELATIVE) != 0 ? qd - rqd : qd; pm = sp(0.5f * a.qd_cost) * dqd * dqd; }
             else pm = sp(0.5f * a.qd_cost) * qd * qd;
             if (l < 3) {                                     // lanes 0..2: one coordinate of the tracking error each
-                if constexpr (COST == 1) {
+                if constexpr (COST >= 1) {
                     if (a.eePos_traj) {                      // (NULL with ee_cost = 0: no goal is read)
                         const R goal = T::mk(a.eePos_traj[((size_t)bb[0] * N + kk[0]) * 6 + l], a.eePos_traj[((size_t)bb[1] * N + kk[1]) * 6 + l]);
                         const R d = (l == 0 ? ee0 : (l == 1 ? ee1 : ee2)) - goal;
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(typena
             }
             // the dynamics half's control cost and integrator defect: computed for both halves, kept where the half is a dynamics item
             R pm_dyn;
-            if constexpr (COST == 1) { const R du = (a.ref.flags & XUREF_U_RELATIVE) != 0 ? ul - ru : ul; pm_dyn = pm + sp(0.5f * a.r_cost) * du * du; }
+            if constexpr (COST >= 1) { const R du = (a.ref.flags & XUREF_U_RELATIVE) != 0 ? ul - ru : ul; pm_dyn = pm + sp(0.5f * a.r_cost) * du * du; }
             else pm_dyn = pm + sp(0.5f * a.r_cost) * ul * ul;
             R viol_dyn;
             if constexpr (INTEGRATOR == 1) {                 // semi-implicit Euler: q' = q + dt qd', qd' = qd + dt qdd
@@ -216,7 +216,15 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void merit_points_f32_kernel(typena
             const R xs_q = T::mk(xs0[l], xs1[l]), xs_qd = T::mk(xs0[PJ + l], xs1[PJ + l]);
             const R viol_first = viol + (__builtin_elementwise_abs(q - xs_q) + __builtin_elementwise_abs(qd - xs_qd));
             viol = merit_sel(first, viol_first, viol);
-            if constexpr (COST == 1) { const R dq = q - rq; pm += sp(0.5f * a.ref.q_cost) * dq * dq; }      // the joint-space term: behind the existing ones
+            if constexpr (COST >= 1) { const R dq = q - rq; pm += sp(0.5f * a.ref.q_cost) * dq * dq; }      // the joint-space term: behind the existing ones
+            if constexpr (COST == 2) {                       // the limits penalty of joint l: behind that; the control's for both halves, kept where the half is a dynamics item
+                const float qlo = P.xlo()[l], qhi = P.xhi()[l], dlo = P.xlo()[PJ + l], dhi = P.xhi()[PJ + l], clo = P.ulo()[l], chi = P.uhi()[l];
+                const R vq = T::mk(lim_viol(q.x, qlo, qhi), lim_viol(q.y, qlo, qhi)), vqd = T::mk(lim_viol(qd.x, dlo, dhi), lim_viol(qd.y, dlo, dhi));
+                const R vu = T::mk(lim_viol(ul.x, clo, chi), lim_viol(ul.y, clo, chi));
+                pm += sp(0.5f * P.limw()[0]) * vq * vq;
+                pm += sp(0.5f * P.limw()[1]) * vqd * vqd;
+                pm = merit_sel(dyn, pm + sp(0.5f * P.limw()[2]) * vu * vu, pm);
+            }
             I->Gq[l] = pm + sp(a.mu) * viol;
         }
         __syncthreads();

@@ -1,7 +1,8 @@
 // mpcg_plant.hip — C ABI (include/mpcg.h) of the producer of the path's inputs: the robot as data (mpcg_plant) and the KKT block assembly
 // mpcg_generate_kkt(_f64) over the gfx950 kernel in kkt_plant.hip.h; the stage behind dz — mpcg_compute_merit(_f64) and
 // mpcg_line_search_step(_rho)(_f64) over merit_plant.hip.h (the merit in packed float, "merit_f32": merit_plant_f32.hip.h); the step between two SQP solves — mpcg_simulate(_f64) and mpcg_advance_horizon(_f64) over sim_plant.hip.h;
-// the plant's gravity (mpcg_plant_clone_gravity) and mpcg_inverse_dynamics(_f64) over invdyn_plant.hip.h.
+// the plant's gravity (mpcg_plant_clone_gravity) and mpcg_inverse_dynamics(_f64) over invdyn_plant.hip.h; the plant's soft limits (mpcg_plant_clone_limits): the COST = 2
+// instantiations behind the _xuref entries and the saturating instantiation of simulate_kernel, launched exactly when the plant given carries them.
 #include <cmath>
 #include <memory>
 #include <type_traits>
@@ -20,7 +21,32 @@ extern "C" {
 struct mpcg_plant {
     int device = 0; PlantDev* d = nullptr; PlantDevT<float>* d32 = nullptr;      // (d32: the same tables rounded to float, behind d in ONE allocation)
     PlantDev host; PlantDevT<float> host32;                                      // what the device holds: mpcg_plant_clone_gravity copies these, mpcg_plant_get_gravity reads host.grav
+    bool has_limits = false; mpcg_limits lim;                                    // mpcg_plant_clone_limits: the limits as given (host.xlo ... hold them for the kernels)
 };
+
+// `lim` into the tables of both precisions (the float ones rounded) and into pl->lim
+static void plant_set_limits(mpcg_plant* pl, const mpcg_limits& lim) {
+    pl->lim = lim;
+    for (int i = 0; i < PJ; ++i) {
+        pl->host.xlo[i] = lim.q_lo[i]; pl->host.xhi[i] = lim.q_hi[i]; pl->host.xlo[PJ + i] = lim.qd_lo[i]; pl->host.xhi[PJ + i] = lim.qd_hi[i];
+        pl->host.ulo[i] = lim.u_lo[i]; pl->host.uhi[i] = lim.u_hi[i];
+    }
+    pl->host.limw[0] = lim.q_weight; pl->host.limw[1] = lim.qd_weight; pl->host.limw[2] = lim.u_weight;
+    for (int i = 0; i < 2 * PJ; ++i) { pl->host32.xlo[i] = (float)pl->host.xlo[i]; pl->host32.xhi[i] = (float)pl->host.xhi[i]; }
+    for (int i = 0; i < PJ; ++i) { pl->host32.ulo[i] = (float)pl->host.ulo[i]; pl->host32.uhi[i] = (float)pl->host.uhi[i]; }
+    for (int i = 0; i < 3; ++i) pl->host32.limw[i] = (float)pl->host.limw[i];
+}
+// no bound on either side, zero weights, no flags: what a plant without limits holds and reports
+static mpcg_limits no_limits() {
+    mpcg_limits lim;
+    for (int i = 0; i < PJ; ++i) {
+        lim.q_lo[i] = lim.qd_lo[i] = lim.u_lo[i] = -INFINITY;
+        lim.q_hi[i] = lim.qd_hi[i] = lim.u_hi[i] = INFINITY;
+    }
+    lim.q_weight = lim.qd_weight = lim.u_weight = 0.0;
+    lim.flags = 0;
+    return lim;
+}
 
 // pl->host and pl->host32 into ONE new allocation on pl->device (host32 behind host); on failure nothing stays allocated
 static bool plant_upload(mpcg_plant* pl) {
@@ -182,6 +208,7 @@ int mpcg_plant_create(mpcg_plant** out, int device, uint32_t num_joints, const d
         for (int e = 0; e < 10; ++e) hp32->Ib[k][e] = (float)hp->Ib[k][e];
     }
     pl->host = *hp; pl->host32 = *hp32;                     // (grav = {0, 0, 0}: hp was zero-filled, hp32 value-initialised)
+    plant_set_limits(pl.get(), no_limits());
     if (!plant_upload(pl.get())) return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_create: cannot place the model on the device");
     *out = pl.release();
     return MPCG_OK;
@@ -208,6 +235,7 @@ int mpcg_plant_clone_gravity(mpcg_plant** out, const mpcg_plant* src, const doub
     if (!pl) return MPCG_ERR_NOMEM;
     pl->device = src->device;
     pl->host = src->host; pl->host32 = src->host32;
+    pl->has_limits = src->has_limits; pl->lim = src->lim;    // a gravity clone of a limits plant keeps its limits
     for (int r = 0; r < 3; ++r) {
         pl->host.grav[r] = base_accel[r] + 0.0;             // (-0 becomes +0: a zero vector is the plain plant's, whatever its sign bits)
         pl->host32.grav[r] = (float)pl->host.grav[r];
@@ -223,6 +251,46 @@ int mpcg_plant_clone_gravity(mpcg_plant** out, const mpcg_plant* src, const doub
 int mpcg_plant_get_gravity(const mpcg_plant* p, double out[3]) {
     if (!p || !out) return MPCG_ERR_INVALID;
     for (int r = 0; r < 3; ++r) out[r] = p->host.grav[r];
+    return MPCG_OK;
+}
+
+// The plant with soft limits (PlantDevT::xlo ..., mpcg_limits): a NEW plant for the reasons mpcg_plant_clone_gravity gives; the gravity of src is kept.
+int mpcg_plant_clone_limits(mpcg_plant** out, const mpcg_plant* src, const mpcg_limits* lim) {
+    static_assert(PJ == 7, "mpcg_limits holds seven joints");
+    if (!out) return MPCG_ERR_INVALID;
+    *out = nullptr;
+    if (!src || !lim) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_limits: null argument");
+    const double* lo[3] = {lim->q_lo, lim->qd_lo, lim->u_lo};
+    const double* hi[3] = {lim->q_hi, lim->qd_hi, lim->u_hi};
+    for (int t = 0; t < 3; ++t)
+        for (int i = 0; i < PJ; ++i) {
+            if (std::isnan(lo[t][i]) || std::isnan(hi[t][i])) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_limits: a bound is NaN");
+            if (lo[t][i] > hi[t][i]) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_limits: a lower bound exceeds its upper bound");
+            if (lo[t][i] == INFINITY || hi[t][i] == -INFINITY)
+                return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_limits: a lower bound of +inf or an upper bound of -inf");
+        }
+    const double w[3] = {lim->q_weight, lim->qd_weight, lim->u_weight};
+    for (int t = 0; t < 3; ++t)
+        if (!std::isfinite(w[t]) || w[t] < 0.0) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_limits: weights must be finite and >= 0");
+    if (lim->flags & ~MPCG_LIMITS_SIM_SATURATE) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_limits: unknown flag bit");
+    mpcg_plant* pl = new (std::nothrow) mpcg_plant();
+    if (!pl) return MPCG_ERR_NOMEM;
+    pl->device = src->device;
+    pl->host = src->host; pl->host32 = src->host32;
+    pl->has_limits = true;
+    plant_set_limits(pl, *lim);
+    if (!plant_upload(pl)) {
+        delete pl;
+        return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_clone_limits: cannot place the model on the device");
+    }
+    *out = pl;
+    return MPCG_OK;
+}
+
+int mpcg_plant_get_limits(const mpcg_plant* p, mpcg_limits* out, int* has_limits) {
+    if (!p || !out || !has_limits) return MPCG_ERR_INVALID;
+    *out = p->lim;
+    *has_limits = p->has_limits ? 1 : 0;
     return MPCG_OK;
 }
 
@@ -249,6 +317,12 @@ static int check_xuref(mpcg_handle* h, const char* fn, const mpcg_xuref* ref, co
     return MPCG_OK;
 }
 
+// the plain entries refuse a plant with limits: the two families differ in the last block's quirk, and a silent switch would change numbers
+static std::string limits_need_xuref(const char* fn) {
+    return std::string(fn) + ": the plant has limits (mpcg_plant_clone_limits), which only the _xuref entries honour: call " + fn +
+           "'s _xuref twin with the neutral cost (ee_cost = 1, q_cost = 0, no flags)";
+}
+
 template <typename S, typename T>
 static XuRefT<S, T> xuref_args(const mpcg_xuref* ref) {
     XuRefT<S, T> x;
@@ -267,6 +341,7 @@ static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* p
     if (xuref) { const int rc = check_xuref(h, fn, ref, d_eePos_traj); if (rc != MPCG_OK) return rc; }
     if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
     if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
+    if (!xuref && plant->has_limits) return fail(h, MPCG_ERR_UNSUPPORTED, limits_need_xuref(fn));
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -284,7 +359,7 @@ static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* p
     // "integrator" = 1: the semi-implicit instantiation of the same build (a compile-time parameter: the explicit instantiations are the kernels they were)
     const bool semi = h->integrator == 1;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    if (xuref) {                                          // the same build, its COST = 1 instantiation
+    if (xuref) {                                          // the same build, its COST = 1 instantiation — COST = 2 exactly when the plant given has limits
         auto go = [&](auto explicit_k, auto semi_k, const auto& args, long nb) {
             typedef std::remove_cv_t<std::remove_reference_t<decltype(args)>> Args;      // KktArgsT<S, T>
             typedef decltype(args.dt) S;
@@ -294,21 +369,26 @@ static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* p
             x.ref = xuref_args<S, T>(ref);
             hipLaunchKernelGGL((semi ? semi_k : explicit_k), dim3((unsigned)nb), dim3(KKT_THREADS), 0, st, x);
         };
-        if constexpr (std::is_same<T, double>::value) {
-            if (h->kkt_analytic) go(generate_kkt_kernel<true, double, 0, double, 1>, generate_kkt_kernel<true, double, 1, double, 1>, a, blocks);
-            else go(generate_kkt_kernel<false, double, 0, double, 1>, generate_kkt_kernel<false, double, 1, double, 1>, a, blocks);
-        } else {
-            if (h->kkt_analytic && h->kkt_f32) {
-                KktArgsT<float> f;
-                fill(f, plant->d32);
-                if (h->kkt_f32 == 1) {
-                    long pblocks = ((long)batch * (h->N - 1) + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
-                    if (pblocks > cap) pblocks = cap;
-                    go(generate_kkt_kernel<true, kkt_f2, 0, float, 1>, generate_kkt_kernel<true, kkt_f2, 1, float, 1>, f, pblocks);
-                } else go(generate_kkt_kernel<true, float, 0, float, 1>, generate_kkt_kernel<true, float, 1, float, 1>, f, blocks);
-            } else if (h->kkt_analytic) go(generate_kkt_kernel<true, double, 0, float, 1>, generate_kkt_kernel<true, double, 1, float, 1>, a, blocks);
-            else go(generate_kkt_kernel<false, double, 0, float, 1>, generate_kkt_kernel<false, double, 1, float, 1>, a, blocks);
-        }
+        auto launch = [&](auto cost) {
+            constexpr int COST = decltype(cost)::value;
+            if constexpr (std::is_same<T, double>::value) {
+                if (h->kkt_analytic) go(generate_kkt_kernel<true, double, 0, double, COST>, generate_kkt_kernel<true, double, 1, double, COST>, a, blocks);
+                else go(generate_kkt_kernel<false, double, 0, double, COST>, generate_kkt_kernel<false, double, 1, double, COST>, a, blocks);
+            } else {
+                if (h->kkt_analytic && h->kkt_f32) {
+                    KktArgsT<float> f;
+                    fill(f, plant->d32);
+                    if (h->kkt_f32 == 1) {
+                        long pblocks = ((long)batch * (h->N - 1) + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
+                        if (pblocks > cap) pblocks = cap;
+                        go(generate_kkt_kernel<true, kkt_f2, 0, float, COST>, generate_kkt_kernel<true, kkt_f2, 1, float, COST>, f, pblocks);
+                    } else go(generate_kkt_kernel<true, float, 0, float, COST>, generate_kkt_kernel<true, float, 1, float, COST>, f, blocks);
+                } else if (h->kkt_analytic) go(generate_kkt_kernel<true, double, 0, float, COST>, generate_kkt_kernel<true, double, 1, float, COST>, a, blocks);
+                else go(generate_kkt_kernel<false, double, 0, float, COST>, generate_kkt_kernel<false, double, 1, float, COST>, a, blocks);
+            }
+        };
+        if (plant->has_limits) launch(std::integral_constant<int, 2>());
+        else launch(std::integral_constant<int, 1>());
     } else if constexpr (std::is_same<T, double>::value) {       // double arrays: float64 inside, either gradient route
         if (h->kkt_analytic) hipLaunchKernelGGL((semi ? generate_kkt_kernel<true, double, 1, double> : generate_kkt_kernel<true, double, 0, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
         else hipLaunchKernelGGL((semi ? generate_kkt_kernel<false, double, 1, double> : generate_kkt_kernel<false, double, 0, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
@@ -379,6 +459,7 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
     { const int rc = check_steps(h, fn, step_sizes, num_steps); if (rc != MPCG_OK) return rc; }
     if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
     if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
+    if (!xuref && plant->has_limits) return fail(h, MPCG_ERR_UNSUPPORTED, limits_need_xuref(fn));
     MeritArgsT<T> a;
     bool moved = false;
     for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) { a.alpha[i] = i < num_steps ? step_sizes[i] : T(0); moved = moved || a.alpha[i] != T(0); }
@@ -402,7 +483,8 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
     if (blocks > cap) blocks = cap;
     const int rows = (int)(batch * num_steps);
     const bool semi = h->integrator == 1;          // "integrator": the map mpcg_generate_kkt linearised (one knob for both, every build)
-    if (xuref) {                                  // the same build, its COST = 1 instantiation; the row sums as below
+    if (xuref) {                                  // the same build, its COST = 1 instantiation — COST = 2 exactly when the plant given has limits; the row sums as below
+        const bool lim = plant->has_limits;
         if (!F64 && h->merit_f32) {
             if constexpr (!F64) {
                 MeritXuArgsT<float, float> f;
@@ -411,12 +493,16 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
                 f.ref = xuref_args<float, float>(ref);
                 const long pblocks = ((long)batch * num_steps * h->N + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
                 if (pblocks > 0x7fffffffL) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch x num_steps x knot_points exceeds the grid");
+                if (lim) hipLaunchKernelGGL((semi ? merit_points_f32_kernel<1, 2> : merit_points_f32_kernel<0, 2>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
+                else
                 hipLaunchKernelGGL((semi ? merit_points_f32_kernel<1, 1> : merit_points_f32_kernel<0, 1>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
             }
         } else {
             MeritXuArgsT<T> x;
             static_cast<MeritArgsT<T>&>(x) = a;
             x.ref = xuref_args<double, T>(ref);
+            if (lim) hipLaunchKernelGGL((semi ? merit_points_kernel<T, 1, 2> : merit_points_kernel<T, 0, 2>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, x);
+            else
             hipLaunchKernelGGL((semi ? merit_points_kernel<T, 1, 1> : merit_points_kernel<T, 0, 1>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, x);
         }
         HIP_TRY(h, hipGetLastError());
@@ -568,6 +654,10 @@ static int simulate_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant
     a.rem = (double)(T)fmod(sim, ss);                        // (the reference's T: a float remainder is rounded to float, a double one is fmod's value)
     const dim3 grid((batch + KKT_ITEMS - 1) / KKT_ITEMS);
     const bool semi = h->sim_integrator == 1;      // "sim_integrator": the substep q' = q + dt qd' (0, the default: the reference's plant, explicit Euler)
+    // a plant whose limits carry MPCG_LIMITS_SIM_SATURATE: the instantiation that clamps the controls it applies; any other plant: the kernels they were
+    if (plant->has_limits && (plant->lim.flags & MPCG_LIMITS_SIM_SATURATE))
+        hipLaunchKernelGGL((semi ? simulate_kernel<T, 1, 1> : simulate_kernel<T, 0, 1>), grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    else
     hipLaunchKernelGGL((semi ? simulate_kernel<T, 1> : simulate_kernel<T, 0>), grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;

@@ -110,7 +110,9 @@ template <typename IO> struct SimArgsT {
 
 // The arithmetic between load and store is float64 for either IO: only the loads (widened, or used as they are) and the stores (rounded once, or not at all)
 // depend on it.  INTEGRATOR: 0 explicit, 1 semi-implicit Euler ("sim_integrator").  (As for the KKT and merit kernels, a shared __device__ body was tried and changed the code.)
-template <typename IO, int INTEGRATOR = 0>
+// SATURATE = 1 (a plant whose limits carry MPCG_LIMITS_SIM_SATURATE): every control applied is clamped to the plant's [u_lo, u_hi] where it is loaded and widened
+// — the actuator saturates; a NaN passes.  Read in `if constexpr` only: SATURATE = 0 is the kernel it was.
+template <typename IO, int INTEGRATOR = 0, int SATURATE = 0>
 __global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgsT<IO> a) {
     typedef double R;
     typedef KktLds<R>::vr kkt_lds_vd;
@@ -143,6 +145,12 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgsT<IO> a
         double dt = a.rem;
         if (k < a.S) { idx = knot_of(__dadd_rn(a.toff, __dmul_rn((double)k, a.ss))); dt = a.ss; }
         if (l < m) {
+            if constexpr (SATURATE == 1) {
+                if (step) {
+                    const double u = (double)xu[(size_t)idx * (n + m) + n + l], lo = P.ulo()[l], hi = P.uhi()[l];
+                    I->U[l] = u > hi ? hi : (u < lo ? lo : u);
+                }
+            } else
             if (step) I->U[l] = (double)xu[(size_t)idx * (n + m) + n + l];
             double sn, cs;
             kkt_sincos(I->Xq[l], sn, cs);

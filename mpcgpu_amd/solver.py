@@ -45,7 +45,8 @@ class Plant:
     gato_plant::initializeDynamicsConstMem, include/dynamics/iiwa/iiwa_eepos_plant.cuh:63-66) as data.
     `gravity` = (gx, gy, gz): the linear acceleration the chain's root starts from, in the base frame (include/mpcg.h, GRAVITY: GRiD's scalar g is
     (0, 0, g); the physical gravitational acceleration is its negative).  None: (0, 0, 0), the reference's gravity-compensated iiwa.  A plant never
-    changes: `with_gravity` returns a new one (mpcg_plant_clone_gravity)."""
+    changes: `with_gravity` returns a new one (mpcg_plant_clone_gravity), and `with_limits` one with soft joint, velocity and torque limits
+    (mpcg_plant_clone_limits), which the _xuref entries penalise and simulate may saturate at."""
 
     def __init__(self, model=None, device: int | None = None, gravity=None):
         import numpy as np
@@ -93,6 +94,62 @@ class Plant:
         if rc != _lib.MPCG_OK:
             raise _lib.MpcgError(rc, "mpcg_plant_get_gravity")
         return tuple(out)
+
+    @staticmethod
+    def _bounds(name, pair):
+        """(lo, hi) -> two lists of 7 floats; None: no bound; a scalar broadcasts.  TypeError on anything that is not a pair of None / scalar / 7 numbers."""
+        import math
+        import numpy as np
+        if pair is None:
+            pair = (None, None)
+        if isinstance(pair, (str, bytes)) or not hasattr(pair, "__len__") or len(pair) != 2:
+            raise TypeError(f"with_limits: {name} must be a pair (lo, hi) or None")
+        out = []
+        for side, v in zip((-math.inf, math.inf), pair):
+            if v is None:
+                out.append([side] * 7)
+                continue
+            try:
+                a = np.asarray(v)
+            except (TypeError, ValueError):
+                a = np.asarray(None)
+            if a.dtype.kind not in "fiu" or a.shape not in ((), (7,)):
+                raise TypeError(f"with_limits: a bound of {name} must be None, a number or 7 numbers")
+            out.append([float(x) for x in np.broadcast_to(a.astype(np.float64), (7,))])
+        return out
+
+    def with_limits(self, q=None, qd=None, u=None, q_weight: float = 0.0, qd_weight: float = 0.0, u_weight: float = 0.0,
+                    sim_saturate: bool = False) -> "Plant":
+        """A new Plant: this one's tables and gravity with soft limits (mpcg_plant_clone_limits; include/mpcg.h, LIMITS).  q, qd, u = (lo, hi): each side
+        None (no bound), a number (every joint) or 7 numbers.  The _xuref entries given the new plant add 1/2 weight viol^2 per bound kind to the cost;
+        sim_saturate: simulate clamps the controls it applies to u's bounds.  The plain generate_kkt / compute_merit refuse such a plant."""
+        lim = _lib.mpcg_limits()
+        for name, pair in (("q", q), ("qd", qd), ("u", u)):
+            lo, hi = self._bounds(name, pair)
+            setattr(lim, name + "_lo", (C.c_double * 7)(*lo))
+            setattr(lim, name + "_hi", (C.c_double * 7)(*hi))
+        lim.q_weight, lim.qd_weight, lim.u_weight = float(q_weight), float(qd_weight), float(u_weight)
+        lim.flags = _lib.MPCG_LIMITS_SIM_SATURATE if sim_saturate else 0
+        h = C.c_void_p()
+        rc = self.lib.mpcg_plant_clone_limits(C.byref(h), self._p, C.byref(lim))
+        if rc != _lib.MPCG_OK:
+            raise _lib.MpcgError(rc, self.lib.mpcg_last_error(None).decode())
+        new = object.__new__(Plant)
+        new.lib, new.model, new._p = self.lib, self.model, h
+        return new
+
+    @property
+    def limits(self):
+        """None for a plant without limits; otherwise a dict: q, qd, u = (lo, hi) tuples of 7 floats, q_weight, qd_weight, u_weight, sim_saturate."""
+        lim, has = _lib.mpcg_limits(), C.c_int(0)
+        rc = self.lib.mpcg_plant_get_limits(self._p, C.byref(lim), C.byref(has))
+        if rc != _lib.MPCG_OK:
+            raise _lib.MpcgError(rc, "mpcg_plant_get_limits")
+        if not has.value:
+            return None
+        return {"q": (tuple(lim.q_lo), tuple(lim.q_hi)), "qd": (tuple(lim.qd_lo), tuple(lim.qd_hi)), "u": (tuple(lim.u_lo), tuple(lim.u_hi)),
+                "q_weight": lim.q_weight, "qd_weight": lim.qd_weight, "u_weight": lim.u_weight,
+                "sim_saturate": bool(lim.flags & _lib.MPCG_LIMITS_SIM_SATURATE)}
 
     def close(self):
         if getattr(self, "_p", None):
