@@ -4,7 +4,8 @@
 //   mpcg_producers.hip  Schur + preconditioner formation, dz recovery, CSR emitter, block-tridiagonal direct solve (schur_*.hip.h, block_solve.hip.h;
 //                       any other (state_size, control_size) than 14 x 7: schur_generic.hip.h)
 //   mpcg_plant.hip      the robot as data + KKT block assembly (kkt_plant.hip.h), merit function + line-search step (merit_plant.hip.h, merit_plant_f32.hip.h),
-//                       plant simulation + horizon shift (sim_plant.hip.h)
+//                       plant simulation + horizon shift (sim_plant.hip.h), inverse dynamics (invdyn_plant.hip.h): one host path per call for float and
+//                       double, each kernel family selected in one place (launch_kkt, launch_merit_points, simulate_impl)
 //   mpcg_ldl.hip        the host LDL^T twin of the reference's QDLDL path (ldl_host.hpp)
 // Every kernel header is included by exactly one of them (their non-template kernels have external linkage).
 #pragma once
@@ -53,7 +54,8 @@ struct mpcg_handle {
     uint32_t* sched_order = nullptr;   // [1 + max_batch] {batch it was made for, dispatch order}: written after every hinted solve, checked on the device
     int schur_chunk = 0;      //   block rows per chunk of the walking kernel: 0 auto (by call size), 1..2048 forced
     int kkt_analytic = 1;     // mpcg_generate_kkt: 1 = analytic gradient recursion of the inverse dynamics (as the reference's GRiD code), 0 = one-sided float64 differences (the checker)
-    int kkt_f32 = 0;          // mpcg_generate_kkt: 1 = the analytic kernel in float arithmetic (linsys_t's own, as the reference's GRiD<float>); 0 = float64 inside
+    int kkt_f32 = 0;          // mpcg_generate_kkt: 1 = the analytic kernel in float arithmetic (linsys_t's own, as the reference's GRiD<float>), two knots per lane in packed float;
+                              //   2 = the same arithmetic, one knot per lane (the packed build's checker); 0 = float64 inside.  Float arrays with "kkt_analytic" = 1 only
     int merit_f32 = 0;        // mpcg_compute_merit: 1 = the point merits in packed float (merit_plant_f32.hip.h: the reference's own arithmetic, two items per lane group); 0 = float64 inside
     int integrator = 0;       // mpcg_generate_kkt(_f64) and mpcg_compute_merit(_f64), every build: 0 = explicit Euler, 1 = semi-implicit (symplectic) Euler, q' = q + dt qd' (the reference's INTEGRATOR_TYPE)
     int sim_integrator = 0;   // mpcg_simulate(_f64): the same choice for the plant's substep (the reference's plant is explicit Euler whatever the controller uses: 0)

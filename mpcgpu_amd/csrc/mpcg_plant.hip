@@ -1,8 +1,7 @@
-// mpcg_plant.hip — C ABI (include/mpcg.h) of the producer of the path's inputs: the robot as data (mpcg_plant) and the KKT block assembly
-// mpcg_generate_kkt(_f64) over the gfx950 kernel in kkt_plant.hip.h; the stage behind dz — mpcg_compute_merit(_f64) and
-// mpcg_line_search_step(_rho)(_f64) over merit_plant.hip.h (the merit in packed float, "merit_f32": merit_plant_f32.hip.h); the step between two SQP solves — mpcg_simulate(_f64) and mpcg_advance_horizon(_f64) over sim_plant.hip.h;
-// the plant's gravity (mpcg_plant_clone_gravity) and mpcg_inverse_dynamics(_f64) over invdyn_plant.hip.h; the plant's soft limits (mpcg_plant_clone_limits): the COST = 2
-// instantiations behind the _xuref entries and the saturating instantiation of simulate_kernel, launched exactly when the plant given carries them.
+// mpcg_plant.hip — C ABI (include/mpcg.h) of the entries around the robot as data (mpcg_plant), one host path per call for float and double: the KKT block
+// assembly (kkt_plant.hip.h), the merit function and the line-search step (merit_plant.hip.h, merit_plant_f32.hip.h), plant simulation
+// and horizon shift (sim_plant.hip.h), inverse dynamics (invdyn_plant.hip.h).  Each kernel family is selected in ONE place — launch_kkt, launch_merit_points,
+// simulate_impl — from the handle's options, the entry (the _xuref entries: COST >= 1) and the plant given (one with soft limits: COST = 2, saturating simulate).
 #include <cmath>
 #include <memory>
 #include <type_traits>
@@ -62,6 +61,19 @@ static bool plant_upload(mpcg_plant* pl) {
     }
     pl->d32 = reinterpret_cast<PlantDevT<float>*>(pl->d + 1);
     return true;
+}
+
+// A new plant for src's device with src's host tables and limits, nothing on the device yet (null: no memory).  The clone entries change one thing and
+// upload; the owner frees the plant on any failure.  Clones, because kernels read the model through the constant address space as invariant data and
+// captured graphs keep the pointer — a plant never changes after creation.
+static std::unique_ptr<mpcg_plant> plant_clone(const mpcg_plant* src) {
+    std::unique_ptr<mpcg_plant> pl(new (std::nothrow) mpcg_plant());
+    if (pl) {
+        pl->device = src->device;
+        pl->host = src->host; pl->host32 = src->host32;
+        pl->has_limits = src->has_limits; pl->lim = src->lim;
+    }
+    return pl;
 }
 
 int mpcg_plant_create(mpcg_plant** out, int device, uint32_t num_joints, const double* X_const, const double* I_spatial, const double* Xhom_const,
@@ -223,28 +235,21 @@ int mpcg_plant_create_iiwa14(mpcg_plant** out, int device) {
                              (uint32_t)(sizeof(kIiwa14_Xhom_trig_idx) / sizeof(int32_t)));
 }
 
-// The plant with another root acceleration (PlantDevT::grav): a NEW plant with its own device allocation, because kernels read the model through the
-// constant address space as invariant data and captured graphs keep the pointer — a plant never changes after creation.
+// The plant with another root acceleration (PlantDevT::grav): a NEW plant with its own device allocation (plant_clone).
 int mpcg_plant_clone_gravity(mpcg_plant** out, const mpcg_plant* src, const double base_accel[3]) {
     if (!out) return MPCG_ERR_INVALID;
     *out = nullptr;
     if (!src || !base_accel) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_gravity: null argument");
     if (!std::isfinite(base_accel[0]) || !std::isfinite(base_accel[1]) || !std::isfinite(base_accel[2]))
         return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_gravity: base_accel must be finite");
-    mpcg_plant* pl = new (std::nothrow) mpcg_plant();
+    std::unique_ptr<mpcg_plant> pl = plant_clone(src);      // (a gravity clone of a limits plant keeps its limits)
     if (!pl) return MPCG_ERR_NOMEM;
-    pl->device = src->device;
-    pl->host = src->host; pl->host32 = src->host32;
-    pl->has_limits = src->has_limits; pl->lim = src->lim;    // a gravity clone of a limits plant keeps its limits
     for (int r = 0; r < 3; ++r) {
         pl->host.grav[r] = base_accel[r] + 0.0;             // (-0 becomes +0: a zero vector is the plain plant's, whatever its sign bits)
         pl->host32.grav[r] = (float)pl->host.grav[r];
     }
-    if (!plant_upload(pl)) {
-        delete pl;
-        return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_clone_gravity: cannot place the model on the device");
-    }
-    *out = pl;
+    if (!plant_upload(pl.get())) return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_clone_gravity: cannot place the model on the device");
+    *out = pl.release();
     return MPCG_OK;
 }
 
@@ -273,17 +278,12 @@ int mpcg_plant_clone_limits(mpcg_plant** out, const mpcg_plant* src, const mpcg_
     for (int t = 0; t < 3; ++t)
         if (!std::isfinite(w[t]) || w[t] < 0.0) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_limits: weights must be finite and >= 0");
     if (lim->flags & ~MPCG_LIMITS_SIM_SATURATE) return fail(nullptr, MPCG_ERR_INVALID, "mpcg_plant_clone_limits: unknown flag bit");
-    mpcg_plant* pl = new (std::nothrow) mpcg_plant();
+    std::unique_ptr<mpcg_plant> pl = plant_clone(src);
     if (!pl) return MPCG_ERR_NOMEM;
-    pl->device = src->device;
-    pl->host = src->host; pl->host32 = src->host32;
     pl->has_limits = true;
-    plant_set_limits(pl, *lim);
-    if (!plant_upload(pl)) {
-        delete pl;
-        return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_clone_limits: cannot place the model on the device");
-    }
-    *out = pl;
+    plant_set_limits(pl.get(), *lim);
+    if (!plant_upload(pl.get())) return fail(nullptr, MPCG_ERR_HIP, "mpcg_plant_clone_limits: cannot place the model on the device");
+    *out = pl.release();
     return MPCG_OK;
 }
 
@@ -317,10 +317,17 @@ static int check_xuref(mpcg_handle* h, const char* fn, const mpcg_xuref* ref, co
     return MPCG_OK;
 }
 
-// the plain entries refuse a plant with limits: the two families differ in the last block's quirk, and a silent switch would change numbers
-static std::string limits_need_xuref(const char* fn) {
-    return std::string(fn) + ": the plant has limits (mpcg_plant_clone_limits), which only the _xuref entries honour: call " + fn +
-           "'s _xuref twin with the neutral cost (ee_cost = 1, q_cost = 0, no flags)";
+// What the entries that take a plant check once their own pointers are good (fn: the entry's name), in the order each of them always has: 14 x 7 only, plant
+// and handle on one device and, where the entry cannot honour them (the plain KKT and merit entries: the two families differ in the last block's quirk, and a
+// silent switch would change numbers), a plant without limits.  MPCG_OK, or the error left in the handle.  Checks that an entry makes between these and
+// its batch checks stay in the entry, and so do the batch checks: every pair of wrong arguments is answered as it always was.
+static int check_plant(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, bool honours_limits) {
+    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
+    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
+    if (!honours_limits && plant->has_limits)
+        return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": the plant has limits (mpcg_plant_clone_limits), which only the _xuref entries honour: call " + fn +
+                                                 "'s _xuref twin with the neutral cost (ee_cost = 1, q_cost = 0, no flags)");
+    return MPCG_OK;
 }
 
 template <typename S, typename T>
@@ -331,6 +338,17 @@ static XuRefT<S, T> xuref_args(const mpcg_xuref* ref) {
     return x;
 }
 
+// One launch of generate_kkt_kernel<ANALYTIC, R, *, T, COST>: the argument struct that instantiation takes (KktArgsSel) from the filled KktArgsT — with the plan's
+// when COST >= 1 — and the explicit or the semi-implicit instantiation ("integrator"; a compile-time parameter: the explicit ones are the kernels they were).
+template <bool ANALYTIC, typename R, typename T, int COST, typename S>
+static void launch_kkt(bool semi, long blocks, hipStream_t st, const KktArgsT<S, T>& base, const mpcg_xuref* ref) {
+    static_assert(std::is_same<S, typename KktR<R>::scalar>::value, "the arithmetic of the build");
+    typename KktArgsSel<COST, S, T>::type a;
+    static_cast<KktArgsT<S, T>&>(a) = base;
+    if constexpr (COST >= 1) a.ref = xuref_args<S, T>(ref);
+    hipLaunchKernelGGL((semi ? generate_kkt_kernel<ANALYTIC, R, 1, T, COST> : generate_kkt_kernel<ANALYTIC, R, 0, T, COST>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+}
+
 template <typename T>
 static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, T timestep, const T* d_eePos_traj,
                              const T* d_xs, const T* d_xu, T qd_cost, T r_cost, T* d_G_dense, T* d_C_dense, T* d_g, T* d_c, uint32_t batch, void* stream,
@@ -339,9 +357,7 @@ static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* p
     if ((!d_eePos_traj && !xuref) || !d_xs || !d_xu || !d_G_dense || !d_C_dense || !d_g || !d_c)
         return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
     if (xuref) { const int rc = check_xuref(h, fn, ref, d_eePos_traj); if (rc != MPCG_OK) return rc; }
-    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
-    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
-    if (!xuref && plant->has_limits) return fail(h, MPCG_ERR_UNSUPPORTED, limits_need_xuref(fn));
+    { const int rc = check_plant(h, fn, plant, control_size, xuref); if (rc != MPCG_OK) return rc; }
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
@@ -351,62 +367,33 @@ static int generate_kkt_impl(mpcg_handle* h, const char* fn, const mpcg_plant* p
         k.N = (int)h->N; k.batch = (int)batch; k.dt = timestep; k.qd_cost = qd_cost; k.r_cost = r_cost;
         k.analytic = h->kkt_analytic;
     };
-    KktArgsT<double, T> a;
-    fill(a, plant->d);
-    long blocks = ((long)batch * (h->N - 1) + KKT_ITEMS - 1) / KKT_ITEMS;      // one wavefront per KKT_ITEMS (trajectory, knot) pairs
-    const long cap = (long)h->num_cus * 32;
-    if (blocks > cap) blocks = cap;
-    // "integrator" = 1: the semi-implicit instantiation of the same build (a compile-time parameter: the explicit instantiations are the kernels they were)
+    // one wavefront per `items` (trajectory, knot) pairs — KKT_ITEMS, the packed build 2 KKT_ITEMS — and at most 32 per CU: the kernels loop
+    auto grid = [&](long items) { return std::min(((long)batch * (h->N - 1) + items - 1) / items, (long)h->num_cus * 32); };
     const bool semi = h->integrator == 1;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    if (xuref) {                                          // the same build, its COST = 1 instantiation — COST = 2 exactly when the plant given has limits
-        auto go = [&](auto explicit_k, auto semi_k, const auto& args, long nb) {
-            typedef std::remove_cv_t<std::remove_reference_t<decltype(args)>> Args;      // KktArgsT<S, T>
-            typedef decltype(args.dt) S;
-            static_assert(std::is_same<Args, KktArgsT<S, T>>::value, "one fill");
-            KktXuArgsT<S, T> x;
-            static_cast<Args&>(x) = args;
-            x.ref = xuref_args<S, T>(ref);
-            hipLaunchKernelGGL((semi ? semi_k : explicit_k), dim3((unsigned)nb), dim3(KKT_THREADS), 0, st, x);
-        };
-        auto launch = [&](auto cost) {
-            constexpr int COST = decltype(cost)::value;
-            if constexpr (std::is_same<T, double>::value) {
-                if (h->kkt_analytic) go(generate_kkt_kernel<true, double, 0, double, COST>, generate_kkt_kernel<true, double, 1, double, COST>, a, blocks);
-                else go(generate_kkt_kernel<false, double, 0, double, COST>, generate_kkt_kernel<false, double, 1, double, COST>, a, blocks);
-            } else {
-                if (h->kkt_analytic && h->kkt_f32) {
-                    KktArgsT<float> f;
-                    fill(f, plant->d32);
-                    if (h->kkt_f32 == 1) {
-                        long pblocks = ((long)batch * (h->N - 1) + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
-                        if (pblocks > cap) pblocks = cap;
-                        go(generate_kkt_kernel<true, kkt_f2, 0, float, COST>, generate_kkt_kernel<true, kkt_f2, 1, float, COST>, f, pblocks);
-                    } else go(generate_kkt_kernel<true, float, 0, float, COST>, generate_kkt_kernel<true, float, 1, float, COST>, f, blocks);
-                } else if (h->kkt_analytic) go(generate_kkt_kernel<true, double, 0, float, COST>, generate_kkt_kernel<true, double, 1, float, COST>, a, blocks);
-                else go(generate_kkt_kernel<false, double, 0, float, COST>, generate_kkt_kernel<false, double, 1, float, COST>, a, blocks);
+    // The build, from the handle's options and T, for the COST the call has.  Float arrays: "kkt_f32" (with the analytic route only) is linsys_t = float
+    // arithmetic throughout, as the reference's GRiD code, on the tables rounded to float — 1: two knots per lane in packed float (whatever the size of the
+    // call: a trajectory's results do not depend on what else is in the batch); 2: one knot per lane (the packed build's checker; 8 % faster than the
+    // default, where the packed build is 1.6x faster on throughput-sized calls).  Otherwise, and for double arrays always: float64 inside, either gradient route.
+    auto launch = [&](auto cost) {
+        constexpr int COST = decltype(cost)::value;
+        if constexpr (std::is_same<T, float>::value) {
+            if (h->kkt_analytic && h->kkt_f32) {
+                KktArgsT<float> f;
+                fill(f, plant->d32);
+                if (h->kkt_f32 == 1) return launch_kkt<true, kkt_f2, float, COST>(semi, grid(2 * KKT_ITEMS), st, f, ref);
+                return launch_kkt<true, float, float, COST>(semi, grid(KKT_ITEMS), st, f, ref);
             }
-        };
-        if (plant->has_limits) launch(std::integral_constant<int, 2>());
-        else launch(std::integral_constant<int, 1>());
-    } else if constexpr (std::is_same<T, double>::value) {       // double arrays: float64 inside, either gradient route
-        if (h->kkt_analytic) hipLaunchKernelGGL((semi ? generate_kkt_kernel<true, double, 1, double> : generate_kkt_kernel<true, double, 0, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
-        else hipLaunchKernelGGL((semi ? generate_kkt_kernel<false, double, 1, double> : generate_kkt_kernel<false, double, 0, double>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
-    } else {
-        if (h->kkt_analytic && h->kkt_f32) {                  // linsys_t = float arithmetic throughout, as the reference's GRiD code (kkt_plant.hip.h, R = float)
-            KktArgsT<float> f;
-            fill(f, plant->d32);
-            // 1: two knots per lane in packed float (whatever the size of the call: a trajectory's results do not depend on what else is in the batch);
-            // 2: one knot per lane (the packed build's checker; 8 % faster than the default, where the packed build is 1.6x faster on throughput-sized calls)
-            if (h->kkt_f32 == 1) {
-                long pblocks = ((long)batch * (h->N - 1) + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
-                if (pblocks > cap) pblocks = cap;
-                hipLaunchKernelGGL((semi ? generate_kkt_kernel<true, kkt_f2, 1> : generate_kkt_kernel<true, kkt_f2, 0>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
-            } else
-            hipLaunchKernelGGL((semi ? generate_kkt_kernel<true, float, 1> : generate_kkt_kernel<true, float, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, f);
-        } else if (h->kkt_analytic) hipLaunchKernelGGL((semi ? generate_kkt_kernel<true, double, 1> : generate_kkt_kernel<true, double, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
-        else hipLaunchKernelGGL((semi ? generate_kkt_kernel<false, double, 1> : generate_kkt_kernel<false, double, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
-    }
+        }
+        KktArgsT<double, T> a;
+        fill(a, plant->d);
+        if (h->kkt_analytic) return launch_kkt<true, double, T, COST>(semi, grid(KKT_ITEMS), st, a, ref);
+        return launch_kkt<false, double, T, COST>(semi, grid(KKT_ITEMS), st, a, ref);
+    };
+    // COST = 0: the end-effector plant's cost; the _xuref entries: 1, and 2 exactly when the plant given has limits
+    if (!xuref) launch(std::integral_constant<int, 0>());
+    else if (plant->has_limits) launch(std::integral_constant<int, 2>());
+    else launch(std::integral_constant<int, 1>());
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
@@ -447,22 +434,32 @@ static int check_steps(mpcg_handle* h, const char* who, const T* step_sizes, uin
     return MPCG_OK;
 }
 
+// One launch of the point-merit kernel of the arithmetic S — double: merit_points_kernel<T, *, COST>; float: the packed merit_points_f32_kernel<*, COST> (float
+// arrays only) — with the argument struct that instantiation takes (MeritArgsSel) from the filled MeritArgsT, the plan's added when COST >= 1.
+template <int COST, typename T, typename S>
+static void launch_merit_points(bool semi, long blocks, hipStream_t st, const MeritArgsT<T, S>& base, const mpcg_xuref* ref) {
+    typename MeritArgsSel<COST, T, S>::type a;
+    static_cast<MeritArgsT<T, S>&>(a) = base;
+    if constexpr (COST >= 1) a.ref = xuref_args<S, T>(ref);
+    if constexpr (std::is_same<S, float>::value)
+        hipLaunchKernelGGL((semi ? merit_points_f32_kernel<1, COST> : merit_points_f32_kernel<0, COST>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((semi ? merit_points_kernel<T, 1, COST> : merit_points_kernel<T, 0, COST>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
+}
+
 template <typename T>
 static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, T timestep, const T* d_eePos_traj, const T* d_xs,
                               const T* d_xu, const T* d_dz, const T* step_sizes, uint32_t num_steps, T mu, T qd_cost, T r_cost, T* d_merit, uint32_t batch, void* stream,
                               bool xuref = false, const mpcg_xuref* ref = nullptr) {
     static_assert(MERIT_MAX_STEPS == MPCG_MAX_STEP_SIZES, "scratch row stride");
-    constexpr bool F64 = std::is_same<T, double>::value;
     if (!h || !plant) return MPCG_ERR_INVALID;
     if ((!d_eePos_traj && !xuref) || !d_xu || !d_merit) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
     if (xuref) { const int rc = check_xuref(h, fn, ref, d_eePos_traj); if (rc != MPCG_OK) return rc; }
     { const int rc = check_steps(h, fn, step_sizes, num_steps); if (rc != MPCG_OK) return rc; }
-    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
-    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
-    if (!xuref && plant->has_limits) return fail(h, MPCG_ERR_UNSUPPORTED, limits_need_xuref(fn));
-    MeritArgsT<T> a;
+    { const int rc = check_plant(h, fn, plant, control_size, xuref); if (rc != MPCG_OK) return rc; }
+    T alpha[MERIT_MAX_STEPS];
     bool moved = false;
-    for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) { a.alpha[i] = i < num_steps ? step_sizes[i] : T(0); moved = moved || a.alpha[i] != T(0); }
+    for (uint32_t i = 0; i < (uint32_t)MERIT_MAX_STEPS; ++i) { alpha[i] = i < num_steps ? step_sizes[i] : T(0); moved = moved || alpha[i] != T(0); }
     if (moved && !d_dz) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": d_dz may be NULL only if every step size is 0");
     if (batch == 0) return MPCG_OK;
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
@@ -472,60 +469,42 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
         { const int rc = alloc_allowed(h, st, fn); if (rc != MPCG_OK) return rc; }
         HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->merit_scratch), (size_t)h->max_batch * MERIT_MAX_STEPS * h->N * sizeof(double)));
     }
-    auto fill = [&](auto& k, const auto* tables) {        // everything but the step sizes; the scalars convert to the struct's S
+    auto fill = [&](auto& k, const auto* tables) {        // one fill for either arithmetic: the scalars convert to the struct's S
         k.plant = tables; k.eePos_traj = d_eePos_traj; k.xs = d_xs; k.xu = d_xu; k.dz = d_dz; k.point = h->merit_scratch;
         k.N = (int)h->N; k.batch = (int)batch; k.A = (int)num_steps;
         k.dt = timestep; k.mu = mu; k.qd_cost = qd_cost; k.r_cost = r_cost;
+        memcpy(k.alpha, alpha, sizeof(alpha));
     };
-    fill(a, plant->d);
-    long blocks = ((long)batch * num_steps * h->N + KKT_ITEMS - 1) / KKT_ITEMS;      // one wavefront per KKT_ITEMS (trajectory, step size, knot) items
-    const long cap = (long)h->num_cus * 32;
-    if (blocks > cap) blocks = cap;
-    const int rows = (int)(batch * num_steps);
+    const long items = (long)batch * num_steps * h->N;     // (trajectory, step size, knot)
     const bool semi = h->integrator == 1;          // "integrator": the map mpcg_generate_kkt linearised (one knob for both, every build)
-    if (xuref) {                                  // the same build, its COST = 1 instantiation — COST = 2 exactly when the plant given has limits; the row sums as below
-        const bool lim = plant->has_limits;
-        if (!F64 && h->merit_f32) {
-            if constexpr (!F64) {
-                MeritXuArgsT<float, float> f;
+    // The build, for the COST the call has.  Float arrays with "merit_f32": the reference's own arithmetic (merit.cuh, T = float), two items per lane group in
+    // packed float, whatever the size of the call.  Otherwise, and for double arrays always: float64 inside.
+    auto launch = [&](auto cost) -> int {
+        constexpr int COST = decltype(cost)::value;
+        if constexpr (std::is_same<T, float>::value) {
+            if (h->merit_f32) {
+                MeritArgsT<float, float> f;
                 fill(f, plant->d32);
-                memcpy(f.alpha, a.alpha, sizeof(f.alpha));
-                f.ref = xuref_args<float, float>(ref);
-                const long pblocks = ((long)batch * num_steps * h->N + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
+                // one wavefront per trip of 2 KKT_ITEMS items (no trip loop: merit_plant_f32.hip.h); at most max_batch x 16 x N / 8 of them, and a handle whose
+                // scratch of max_batch x 16 x N doubles could be allocated stays far below the 2^31 - 1 workgroups a grid dimension holds
+                const long pblocks = (items + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
                 if (pblocks > 0x7fffffffL) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch x num_steps x knot_points exceeds the grid");
-                if (lim) hipLaunchKernelGGL((semi ? merit_points_f32_kernel<1, 2> : merit_points_f32_kernel<0, 2>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
-                else
-                hipLaunchKernelGGL((semi ? merit_points_f32_kernel<1, 1> : merit_points_f32_kernel<0, 1>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
+                launch_merit_points<COST>(semi, pblocks, st, f, ref);
+                return MPCG_OK;
             }
-        } else {
-            MeritXuArgsT<T> x;
-            static_cast<MeritArgsT<T>&>(x) = a;
-            x.ref = xuref_args<double, T>(ref);
-            if (lim) hipLaunchKernelGGL((semi ? merit_points_kernel<T, 1, 2> : merit_points_kernel<T, 0, 2>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, x);
-            else
-            hipLaunchKernelGGL((semi ? merit_points_kernel<T, 1, 1> : merit_points_kernel<T, 0, 1>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, x);
         }
-        HIP_TRY(h, hipGetLastError());
-        hipLaunchKernelGGL(merit_sum_kernel<T>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
-    } else if constexpr (F64) {                          // double arrays: float64 inside ("merit_f32" is the float entry's), the row sums stored as they are
-        hipLaunchKernelGGL((semi ? merit_points_kernel<double, 1> : merit_points_kernel<double, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
-        HIP_TRY(h, hipGetLastError());
-        hipLaunchKernelGGL(merit_sum_kernel<double>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
-    } else {
-        if (h->merit_f32) {                           // the reference's own arithmetic (merit.cuh, T = float): two items per lane group in packed float, whatever the size of the call
-            MeritArgsT<float, float> f;
-            fill(f, plant->d32);
-            memcpy(f.alpha, a.alpha, sizeof(f.alpha));
-            // one wavefront per trip of 2 KKT_ITEMS items (no trip loop: merit_plant_f32.hip.h); at most max_batch x 16 x N / 8 of them, and a handle whose
-            // scratch of max_batch x 16 x N doubles could be allocated stays far below the 2^31 - 1 workgroups a grid dimension holds
-            const long pblocks = ((long)batch * num_steps * h->N + 2 * KKT_ITEMS - 1) / (2 * KKT_ITEMS);
-            if (pblocks > 0x7fffffffL) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch x num_steps x knot_points exceeds the grid");
-            hipLaunchKernelGGL((semi ? merit_points_f32_kernel<1> : merit_points_f32_kernel<0>), dim3((unsigned)pblocks), dim3(KKT_THREADS), 0, st, f);
-        } else
-        hipLaunchKernelGGL((semi ? merit_points_kernel<float, 1> : merit_points_kernel<float, 0>), dim3((unsigned)blocks), dim3(KKT_THREADS), 0, st, a);
-        HIP_TRY(h, hipGetLastError());
-        hipLaunchKernelGGL(merit_sum_kernel<float>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
-    }
+        MeritArgsT<T> a;
+        fill(a, plant->d);
+        // one wavefront per KKT_ITEMS items and at most 32 per CU: the kernel loops
+        launch_merit_points<COST>(semi, std::min((items + KKT_ITEMS - 1) / KKT_ITEMS, (long)h->num_cus * 32), st, a, ref);
+        return MPCG_OK;
+    };
+    // COST as in generate_kkt_impl: 0; the _xuref entries 1, and 2 exactly when the plant given has limits
+    const int rc = !xuref ? launch(std::integral_constant<int, 0>()) : plant->has_limits ? launch(std::integral_constant<int, 2>()) : launch(std::integral_constant<int, 1>());
+    if (rc != MPCG_OK) return rc;
+    HIP_TRY(h, hipGetLastError());
+    const int rows = (int)(batch * num_steps);             // the row sums, stored as T
+    hipLaunchKernelGGL(merit_sum_kernel<T>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
@@ -634,8 +613,7 @@ static int simulate_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant
     static_assert(SIM_MAX_SUBSTEPS == MPCG_SIM_MAX_SUBSTEPS, "the cap of the header");
     if (!h || !plant) return MPCG_ERR_INVALID;
     if (!d_xs || !d_xu) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
-    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 / control_size 7 (IIWA-14) only");
-    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
+    { const int rc = check_plant(h, fn, plant, control_size, true); if (rc != MPCG_OK) return rc; }
     if (!std::isfinite(timestep) || !std::isfinite(time_offset_us) || !std::isfinite(sim_time_us) || !std::isfinite(sim_step))
         return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": timestep, time_offset_us, sim_time_us and sim_step must be finite");
     if (!(sim_step > T(0)) || !(timestep > 0.0) || time_offset_us < 0.0 || sim_time_us < 0.0)
@@ -655,10 +633,9 @@ static int simulate_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant
     const dim3 grid((batch + KKT_ITEMS - 1) / KKT_ITEMS);
     const bool semi = h->sim_integrator == 1;      // "sim_integrator": the substep q' = q + dt qd' (0, the default: the reference's plant, explicit Euler)
     // a plant whose limits carry MPCG_LIMITS_SIM_SATURATE: the instantiation that clamps the controls it applies; any other plant: the kernels they were
-    if (plant->has_limits && (plant->lim.flags & MPCG_LIMITS_SIM_SATURATE))
-        hipLaunchKernelGGL((semi ? simulate_kernel<T, 1, 1> : simulate_kernel<T, 0, 1>), grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    else
-    hipLaunchKernelGGL((semi ? simulate_kernel<T, 1> : simulate_kernel<T, 0>), grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    const bool saturate = plant->has_limits && (plant->lim.flags & MPCG_LIMITS_SIM_SATURATE);
+    void (*const kernel)(SimArgsT<T>) = saturate ? (semi ? simulate_kernel<T, 1, 1> : simulate_kernel<T, 0, 1>) : (semi ? simulate_kernel<T, 1, 0> : simulate_kernel<T, 0, 0>);
+    hipLaunchKernelGGL(kernel, grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
@@ -707,8 +684,8 @@ template <typename T>
 static int inverse_dynamics_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, const T* d_q, const T* d_qd, const T* d_qdd, T* d_tau, uint32_t count, void* stream) {
     if (!h || !plant) return MPCG_ERR_INVALID;
     if (!d_q || !d_tau) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
-    if (h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 (IIWA-14) only");
-    if (plant->device != h->device) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": plant and handle live on different devices");
+    if (h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": state_size 14 (IIWA-14) only");      // (no control size: the entry's own words)
+    { const int rc = check_plant(h, fn, plant, PJ, true); if (rc != MPCG_OK) return rc; }
     if (count == 0) return MPCG_OK;
     if ((uint64_t)count > (uint64_t)h->max_batch * h->N) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": count exceeds max_batch x knot_points");
     HIP_TRY(h, hipSetDevice(h->device));

@@ -67,25 +67,26 @@ class Plant:
             raise _lib.MpcgError(rc, self.lib.mpcg_last_error(None).decode())
         self._p = h
         if gravity is not None:
-            plain, self._p = self._p, self._clone(h, gravity)
-            self.lib.mpcg_plant_destroy(plain)
+            heavy = self.with_gravity(gravity)
+            self.lib.mpcg_plant_destroy(h)
+            self._p, heavy._p = heavy._p, None
 
-    def _clone(self, src, gravity):
-        g = [float(v) for v in gravity]
-        if len(g) != 3:
-            raise ValueError("gravity: three components (gx, gy, gz)")
+    def _clone(self, entry, arg) -> "Plant":
+        """A new Plant around what the clone entry `entry` (mpcg_plant_clone_gravity / _limits) makes of this one and `arg`; MpcgError if it refuses."""
         h = C.c_void_p()
-        rc = self.lib.mpcg_plant_clone_gravity(C.byref(h), src, (C.c_double * 3)(*g))
+        rc = entry(C.byref(h), self._p, arg)
         if rc != _lib.MPCG_OK:
             raise _lib.MpcgError(rc, self.lib.mpcg_last_error(None).decode())
-        return h
+        new = object.__new__(Plant)
+        new.lib, new.model, new._p = self.lib, self.model, h
+        return new
 
     def with_gravity(self, gravity) -> "Plant":
         """A new Plant: this one's tables with `gravity` (mpcg_plant_clone_gravity); this one is not touched, either may be closed first."""
-        new = object.__new__(Plant)
-        new.lib, new.model, new._p = self.lib, self.model, None
-        new._p = self._clone(self._p, gravity)
-        return new
+        g = [float(v) for v in gravity]
+        if len(g) != 3:
+            raise ValueError("gravity: three components (gx, gy, gz)")
+        return self._clone(self.lib.mpcg_plant_clone_gravity, (C.c_double * 3)(*g))
 
     @property
     def gravity(self):
@@ -130,13 +131,7 @@ class Plant:
             setattr(lim, name + "_hi", (C.c_double * 7)(*hi))
         lim.q_weight, lim.qd_weight, lim.u_weight = float(q_weight), float(qd_weight), float(u_weight)
         lim.flags = _lib.MPCG_LIMITS_SIM_SATURATE if sim_saturate else 0
-        h = C.c_void_p()
-        rc = self.lib.mpcg_plant_clone_limits(C.byref(h), self._p, C.byref(lim))
-        if rc != _lib.MPCG_OK:
-            raise _lib.MpcgError(rc, self.lib.mpcg_last_error(None).decode())
-        new = object.__new__(Plant)
-        new.lib, new.model, new._p = self.lib, self.model, h
-        return new
+        return self._clone(self.lib.mpcg_plant_clone_limits, C.byref(lim))
 
     @property
     def limits(self):
@@ -431,20 +426,27 @@ class PcgSolver:
         -> (G_dense, C_dense, g, c) device tensors in the layouts form_schur consumes.
         float32 tensors: mpcg_generate_kkt; float64 tensors: mpcg_generate_kkt_f64 (linsys_t = double: inputs used as they are, outputs not rounded to
         float).  Mixed dtypes raise TypeError."""
+        return self._generate_kkt(False, plant, eePos_traj, xs, xu, timestep, qd_cost, r_cost, None, control_size)
+
+    def _generate_kkt(self, xuref: bool, plant, eePos_traj, xs, xu, timestep, qd_cost, r_cost, ref, control_size):
+        """generate_kkt (ref = None) and generate_kkt_xuref (xuref): the C entry of that name or its _f64 twin; only the latter may leave eePos_traj out."""
+        name = "generate_kkt_xuref" if xuref else "generate_kkt"
         B = xu.shape[0] if xu.dim() > 1 else 1
         n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        dt = self._one_dtype("generate_kkt", eePos_traj, xs, xu)
-        self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
+        dt = self._one_dtype(name, eePos_traj, xs, xu, *((ref.xu_traj,) if xuref else ()))
+        if eePos_traj is not None or not xuref:
+            self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
         self._chk(xs, B * n, dt, "xs")
         self._chk(xu, B * ((n + m) * N - m), dt, "xu")
+        x = (C.byref(self._xuref(name, ref, dt, B, n, m)),) if xuref else ()
         dev = xu.device
         G = torch.empty(B, (n * n + m * m) * N - m * m, device=dev, dtype=dt)
         Cd = torch.empty(B, (n * n + n * m) * (N - 1), device=dev, dtype=dt)
         g = torch.empty(B, (n + m) * N - m, device=dev, dtype=dt)
         c = torch.empty(B, n * N, device=dev, dtype=dt)
-        fn = self.lib.mpcg_generate_kkt if dt == torch.float32 else self.lib.mpcg_generate_kkt_f64
-        self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), float(qd_cost),
-                                               float(r_cost), _ptr(G), _ptr(Cd), _ptr(g), _ptr(c), B, _stream()))
+        fn = getattr(self.lib, "mpcg_" + name + ("" if dt == torch.float32 else "_f64"))
+        self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), float(qd_cost), float(r_cost), *x,
+                       _ptr(G), _ptr(Cd), _ptr(g), _ptr(c), B, _stream()))
         return G, Cd, g, c
 
     def _xuref(self, name, ref: "XuRef", dt, B, n, m):
@@ -474,47 +476,13 @@ class PcgSolver:
                            control_size: int | None = None):
         """generate_kkt with the generalised running cost of `ref` (mpcg_generate_kkt_xuref; float64 tensors: mpcg_generate_kkt_xuref_f64): the same
         layouts, C and c.  eePos_traj may be None exactly when ref.ee_cost == 0.  Mixed dtypes raise TypeError."""
-        B = xu.shape[0] if xu.dim() > 1 else 1
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        dt = self._one_dtype("generate_kkt_xuref", eePos_traj, xs, xu, ref.xu_traj)
-        if eePos_traj is not None:
-            self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
-        self._chk(xs, B * n, dt, "xs")
-        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
-        x = self._xuref("generate_kkt_xuref", ref, dt, B, n, m)
-        dev = xu.device
-        G = torch.empty(B, (n * n + m * m) * N - m * m, device=dev, dtype=dt)
-        Cd = torch.empty(B, (n * n + n * m) * (N - 1), device=dev, dtype=dt)
-        g = torch.empty(B, (n + m) * N - m, device=dev, dtype=dt)
-        c = torch.empty(B, n * N, device=dev, dtype=dt)
-        fn = self.lib.mpcg_generate_kkt_xuref if dt == torch.float32 else self.lib.mpcg_generate_kkt_xuref_f64
-        self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), float(qd_cost), float(r_cost), C.byref(x),
-                       _ptr(G), _ptr(Cd), _ptr(g), _ptr(c), B, _stream()))
-        return G, Cd, g, c
+        return self._generate_kkt(True, plant, eePos_traj, xs, xu, timestep, qd_cost, r_cost, ref, control_size)
 
     def compute_merit_xuref(self, plant: "Plant", eePos_traj, xs, xu, dz, step_sizes, timestep: float, mu: float, qd_cost: float, r_cost: float,
                             ref: "XuRef", merit=None, control_size: int | None = None):
         """compute_merit with the generalised running cost of `ref` (mpcg_compute_merit_xuref; float64 tensors: mpcg_compute_merit_xuref_f64); what
         line_search_step(_rho) consumes.  eePos_traj may be None exactly when ref.ee_cost == 0.  Mixed dtypes raise TypeError."""
-        B = xu.shape[0] if xu.dim() > 1 else 1
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        dt = self._one_dtype("compute_merit_xuref", eePos_traj, xs, xu, dz, merit, ref.xu_traj)
-        arr, A = self._steps(step_sizes, dt)
-        if eePos_traj is not None:
-            self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
-        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
-        if xs is not None:
-            self._chk(xs, B * n, dt, "xs")
-        if dz is not None:
-            self._chk(dz, B * ((n + m) * N - m), dt, "dz")
-        x = self._xuref("compute_merit_xuref", ref, dt, B, n, m)
-        if merit is None:
-            merit = torch.empty(B, A, device=xu.device, dtype=dt)
-        self._chk(merit, B * A, dt, "merit")
-        fn = self.lib.mpcg_compute_merit_xuref if dt == torch.float32 else self.lib.mpcg_compute_merit_xuref_f64
-        self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), _ptr(dz), arr, A,
-                       float(mu), float(qd_cost), float(r_cost), C.byref(x), _ptr(merit), B, _stream()))
-        return merit
+        return self._compute_merit(True, plant, eePos_traj, xs, xu, dz, step_sizes, timestep, mu, qd_cost, r_cost, ref, merit, control_size)
 
     def compute_dz(self, Ginv_dense, C_dense, g, lam, dz=None, control_size: int | None = None):
         """compute_dz (include/common/dz.cuh:124-136), batched."""
@@ -547,22 +515,29 @@ class PcgSolver:
         dz = None is allowed when every step size is 0.
         float32 tensors: mpcg_compute_merit; float64 tensors: mpcg_compute_merit_f64 (the trial iterate and the merits in double, the step sizes
         marshalled as doubles).  Mixed dtypes raise TypeError."""
+        return self._compute_merit(False, plant, eePos_traj, xs, xu, dz, step_sizes, timestep, mu, qd_cost, r_cost, None, merit, control_size)
+
+    def _compute_merit(self, xuref: bool, plant, eePos_traj, xs, xu, dz, step_sizes, timestep, mu, qd_cost, r_cost, ref, merit, control_size):
+        """compute_merit (ref = None) and compute_merit_xuref (xuref): the C entry of that name or its _f64 twin; only the latter may leave eePos_traj out."""
+        name = "compute_merit_xuref" if xuref else "compute_merit"
         B = xu.shape[0] if xu.dim() > 1 else 1
         n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        dt = self._one_dtype("compute_merit", eePos_traj, xs, xu, dz, merit)
+        dt = self._one_dtype(name, eePos_traj, xs, xu, dz, merit, *((ref.xu_traj,) if xuref else ()))
         arr, A = self._steps(step_sizes, dt)
-        self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
+        if eePos_traj is not None or not xuref:
+            self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
         self._chk(xu, B * ((n + m) * N - m), dt, "xu")
         if xs is not None:
             self._chk(xs, B * n, dt, "xs")
         if dz is not None:
             self._chk(dz, B * ((n + m) * N - m), dt, "dz")
+        x = (C.byref(self._xuref(name, ref, dt, B, n, m)),) if xuref else ()
         if merit is None:
             merit = torch.empty(B, A, device=xu.device, dtype=dt)
         self._chk(merit, B * A, dt, "merit")
-        fn = self.lib.mpcg_compute_merit if dt == torch.float32 else self.lib.mpcg_compute_merit_f64
+        fn = getattr(self.lib, "mpcg_" + name + ("" if dt == torch.float32 else "_f64"))
         self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), _ptr(dz), arr, A,
-                                                float(mu), float(qd_cost), float(r_cost), _ptr(merit), B, _stream()))
+                       float(mu), float(qd_cost), float(r_cost), *x, _ptr(merit), B, _stream()))
         return merit
 
     def line_search_step(self, merit, step_sizes, merit_ref, dz, xu, step=None, control_size: int | None = None):
