@@ -71,6 +71,17 @@
  *     no const — writes d_S, d_Pinv, d_gamma, d_v_temp or d_eta_new_temp; d_max_iter_exit / d_pcg_exit is written one byte per trajectory.  No
  *     kernel uses an atomic operation on caller memory (those there are act on handle-owned buffers and on LDS).  tests/test_gpu_arena_*.py hold
  *     every entry to this: all arrays of a call inside one allocation, each at exactly its smallest accepted alignment, guard bands between.
+ *     LARGE EXTENTS.  Every array of a call may pass 2^31 and 2^32 bytes, and a trajectory's results do not depend on where in the batch it
+ *     stands; tests/test_gpu_large_*.py hold the entries to this on either side of each line below.  Two entries SWITCH KERNELS, same bits:
+ *         mpcg_form_schur(_rhov)(_f64), 14 x 7   batch x knot_points x 3 n^2 x sizeof(T) >= 2^31 (the bytes of d_S: from 913,046 knots in float,
+ *                                                456,523 in double): the LDS kernels instead of the register-resident ones, whose byte offsets
+ *                                                are 31-bit; "last_schur_chunk" then reads 0.  Like "schur_dpp" = 0 this route owns a staging
+ *                                                buffer, so the FIRST such call of a handle allocates and is refused inside a stream capture.
+ *         mpcg_compute_dz(_f64), 14 x 7          batch x knot_points x (n^2 + n m) x sizeof(T) >= 2^31 (from 1,826,092 knots in float, 913,046
+ *                                                in double): the LDS kernel; "last_dz_route" reads 0.
+ *     One line REFUSES: mpcg_form_schur(_rhov)(_f64) returns MPCG_ERR_UNSUPPORTED for batch x knot_points >= 2^31 (a knot's index is an int).
+ *     Every other entry indexes with 64-bit offsets (the PCG kernels and mpcg_bt_spmv through one buffer resource per trajectory) and serves
+ *     whatever batch <= max_batch the device memory holds; mpcg_convert_f32_to_f16 takes any count below 2^42.
  *   - GRAPH CAPTURE.  Every compute entry point is pure stream work and may be captured into a hipGraph.  What the float PCG entry points need
  *     is allocated by mpcg_create; mpcg_form_schur(_f64), mpcg_block_solve(_f64), mpcg_compute_merit(_f64) and a FORCED "cluster" on a horizon the automatic policy gives to one
  *     CU allocate a handle-owned work buffer at their first call (hipMalloc is not stream work): make that call once outside the capture — a
@@ -815,7 +826,8 @@ int mpcg_qdldl_solve_schur(mpcg_handle *h, mpcg_ldl *l, const float *d_val, cons
  * "reserve_f64" (= 1: allocate the double cluster kernels' buffers now; see GRAPH CAPTURE above).
  * Read-only: "cluster_fixups" (trajectories re-solved by fix-up launches since mpcg_create — each costs 1.5-4.5 ms of spinning; blocking 8-byte
  *       D2H read), "last_symmetry_violations", "num_cus", "pcg_resident" (1 if the single-workgroup configuration streams nothing inside the PCG
- *       loop), "last_schur_chunk" (block rows per chunk of the last mpcg_form_schur, 0 = the LDS kernels), "last_kernel_family" (kernel of the
+ *       loop), "last_schur_chunk" (block rows per chunk of the last mpcg_form_schur, 0 = the LDS kernels), "last_dz_route" (the last
+ *       mpcg_compute_dz(_f64): 1 = four knots per wavefront, 0 = the LDS kernel), "last_kernel_family" (kernel of the
  *       last solve: 0 single-workgroup row-pair, 3 generic, 5 row-per-lane, 6 lane-pair-per-knot, 7 clustered lane-pair, 8 clustered row-per-lane
  *       (double), 9 lane-quad-per-knot (double), 10 clustered lane-quad (double), 11 lane-quad-per-knot with both matrices per wavefront (float, round 6); 1, 2, 4 were kernels retired in round 4), "last_kernel_{waves,reg_rows,lds_rows,lds_extra,stream_bufs,cluster,lds_bytes}". */
 int mpcg_set_option(mpcg_handle *h, const char *key, int value);

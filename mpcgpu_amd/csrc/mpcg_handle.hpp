@@ -61,6 +61,7 @@ struct mpcg_handle {
     int sim_integrator = 0;   // mpcg_simulate(_f64): the same choice for the plant's substep (the reference's plant is explicit Euler whatever the controller uses: 0)
     int dz_dpp = 1;           // 1: four-knots-per-wavefront dz recovery (schur_walk.hip.h), 0: the LDS kernel (schur_generic.hip.h)
     int last_schur_chunk = 0; //   what the last mpcg_form_schur used (0: the LDS kernels)
+    int last_dz_route = 0;    //   what the last mpcg_compute_dz(_f64) ran: 1 = four knots per wavefront (schur_walk.hip.h), 0 = the LDS kernel
     int producers_generic = 0; // 1: form_schur(_f64), compute_dz(_f64) and block_solve of a (14, 7) call run the run-time-dimension kernels (schur_generic.hip.h) every other shape gets (formation and dz: what "schur_dpp" / "dz_dpp" = 0 run too)
     void* seam_qinv = nullptr;       // schur_walk: one Q^-1 per chunk seam (float or double; ensure_seam_buffer)
     size_t seam_qinv_bytes = 0;

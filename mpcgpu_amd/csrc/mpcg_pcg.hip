@@ -360,6 +360,7 @@ int mpcg_get_option(const mpcg_handle* h, const char* key, int* value) {
     if (!strcmp(key, "schur_dpp")) { *value = h->schur_dpp; return MPCG_OK; }
     if (!strcmp(key, "schur_chunk")) { *value = h->schur_chunk; return MPCG_OK; }
     if (!strcmp(key, "last_schur_chunk")) { *value = h->last_schur_chunk; return MPCG_OK; }
+    if (!strcmp(key, "last_dz_route")) { *value = h->last_dz_route; return MPCG_OK; }
     if (!strcmp(key, "dz_dpp")) { *value = h->dz_dpp; return MPCG_OK; }
     if (!strcmp(key, "producers_generic")) { *value = h->producers_generic; return MPCG_OK; }
     if (!strcmp(key, "kkt_analytic")) { *value = h->kkt_analytic; return MPCG_OK; }

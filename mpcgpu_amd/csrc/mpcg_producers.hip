@@ -221,8 +221,10 @@ static int compute_dz_impl(mpcg_handle* h, const char* fn, uint32_t control_size
     hipStream_t st = static_cast<hipStream_t>(stream);
     const DzArgsT<T> a{d_Ginv, d_C, d_g, d_lambda, d_dz, (int)h->n, (int)control_size, (int)h->N, (int)batch};
     const uint64_t knots = (uint64_t)batch * h->N;
+    h->last_dz_route = 0;
     if (gen_route(h, control_size) || !h->dz_dpp || h->N < 2 || knots * dz_bytes_per_knot(a.n, a.m, sizeof(T)) >= (1ull << 31))
         return compute_dz_lds<T>(h, a, st);
+    h->last_dz_route = 1;
     // four knots per wavefront (schur_walk.hip.h): grid-stride over quads of knots
     const long cap = (long)h->num_cus * 64 * Tr::dz_capmul;
     long bq = ((long)knots + 3) / 4;
