@@ -1,6 +1,8 @@
 // mpcg_handle.hpp — what the translation units of libmpcg_hip.so share: the handle behind include/mpcg.h, the error convention, the HIP_TRY
 // macro.  The library is four translation units over this header (Makefile: every csrc/*.hip is compiled on its own and linked once):
-//   mpcg_pcg.hip        handle / options / the PCG launch policy and entry points (pcg_*.hip.h kernels)
+//   mpcg_pcg.hip        handle / options / the PCG launch policy and entry points (pcg_*.hip.h kernels): every option is one row of one table
+//                       (kOptions), the five solve entries share one argument check and one argument fill (solve_ends, solve_args), the float and
+//                       double symmetry latches one check launch, one re-open rule and one warning
 //   mpcg_producers.hip  Schur + preconditioner formation, dz recovery, CSR emitter, block-tridiagonal direct solve (schur_*.hip.h, block_solve.hip.h;
 //                       any other (state_size, control_size) than 14 x 7: schur_generic.hip.h)
 //   mpcg_plant.hip      the robot as data + KKT block assembly (kkt_plant.hip.h), merit function + line-search step (merit_plant.hip.h, merit_plant_f32.hip.h),

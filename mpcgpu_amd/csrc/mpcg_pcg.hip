@@ -1,5 +1,9 @@
 // mpcg_pcg.hip — C ABI (include/mpcg.h) of the hot path: handle and options, the PCG launch policy (which kernel family serves a call), the
 // PCG / SpMV entry points, over the gfx950 kernels in pcg_*.hip.h.  Host side is plain C++/HIP: no torch types, no CPU fallback.
+// Each thing is written once, in this order: the handle's device buffers (scratch layouts, counter line, grow_lam_backup) and mpcg_create /
+// _destroy; the options (kOptions: one row per key, read by mpcg_set_option and mpcg_get_option); the launch plan (plan_f32 / plan_f64) and
+// its launch (launch_plan); the symmetry latch (one check launch, one warning, one re-open rule under the asynchronous float latch and the
+// blocking double one); the solve entries (solve_ends: their argument checks, solve_args: their kernel arguments).
 #include "mpcg_handle.hpp"
 #include "pcg_kernels.hip.h"
 #include "pcg_lpk.hip.h"
@@ -17,38 +21,6 @@ using namespace mpcg;
 
 thread_local std::string mpcg_create_err;
 
-// the symmetry latch: has the asynchronous copy of the device flag landed?
-// (never while `st` is being captured into a graph: an event query is not a capturable operation and would invalidate the capture —
-//  a capturing caller stays on the guarded launches, which are plain kernel launches)
-static void sym_poll(mpcg_handle* h, hipStream_t st = nullptr, bool have_stream = false) {
-    if (!h->sym_pending) return;
-    if (have_stream) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return;
-    }
-    // (the query itself in relaxed capture mode: with ANOTHER stream of this thread being captured in global mode an event query is an
-    //  "unsafe" call that would invalidate that unrelated capture — mpcg_get_option("symmetry_state") passes no stream at all)
-    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-    (void)hipThreadExchangeStreamCaptureMode(&mode);
-    const hipError_t q = hipEventQuery(h->sym_event);
-    (void)hipThreadExchangeStreamCaptureMode(&mode);
-    if (q != hipSuccess) return;
-    h->sym_pending = false;
-    if (*h->sym_host == 0 && h->sym_guard_seq != h->sym_armed_seq) {
-        // guarded solves were issued AFTER this copy was armed: a clean flag says nothing about their matrices.  Stay unknown — the next
-        // guarded call arms a new copy, which (the device flag is sticky) covers them all.
-        return;
-    }
-    if (*h->sym_host) {
-        h->sym_state = 2;
-        h->err = "warning: S / Pinv of a solve on this handle were not block-symmetric (block (k, right) != block (k+1, left)^T): the handle now "
-                 "runs kernels that read all three block columns (include/mpcg.h, BLOCK SYMMETRY)";
-    } else {
-        h->sym_state = 1;
-        h->sym_pinv_ok = h->sym_armed_pinv;
-    }
-}
-
 // n = 14 is the tuned specialisation (every entry point); any other 1 <= n <= 64 is served by the generic PCG kernel
 // (mpcg_pcg_solve / _ref / _f64: pcg_generic_kernel, pcg_f64.hip.h), as long as its iterate vectors fit the LDS, and by the
 // run-time-dimension producers of schur_generic.hip.h (mpcg_producers.hip).
@@ -57,15 +29,18 @@ static bool generic_shape_supported(uint32_t n, uint32_t N) {
     return n >= 1 && n <= 64 && n != (uint32_t)NS && N >= 2 && N <= 2048 && pcg_generic_lds_elems((int)N, (int)n) * sizeof(float) <= 160 * 1024;
 }
 
-static size_t lds_bytes_for(uint32_t N, int nw) { return pcg_lds_floats((int)N, nw) * sizeof(float); }
 static constexpr size_t kLdsMax = 160 * 1024;
 static constexpr uint32_t kRplMaxN = 64;          // row-per-lane kernel: full block rows of S and Pinv in registers
 static constexpr uint32_t kLpbMaxN = 128;         // one block per lane: 8 waves x 64 lanes hold 2 (2N - 1) blocks
+static constexpr uint32_t kLqkMaxN = 64;          // linsys_t = double: knots one CU holds as lane quads (pcg_lqk_f64.hip.h)
+static constexpr uint32_t kCluster64MaxN = 64 * LQKC_MAX_G;      // linsys_t = double: the longest horizon a cluster kernel holds (eight members of 64 knots)
+static constexpr size_t kEagerF64Bytes = (size_t)8 << 20;        // double iterates up to which mpcg_create makes the double clusters' buffers (reserve_f64)
+static size_t lds_bytes_for(uint32_t N, int nw) { return pcg_lds_floats((int)N, nw) * sizeof(float); }
 
+// (defined below, used by mpcg_create and the options)
 static int stream_bufs_for(const mpcg_handle* h, const PcgKnobs& k, int nw, int esz);
 static void choose_auto(const mpcg_handle* h, PcgKnobs& k, uint32_t batch, int esz);
-static constexpr uint32_t kLqkMaxN = 64;      // linsys_t = double: knots one CU holds as lane quads (pcg_lqk_f64.hip.h)
-static constexpr uint32_t kCluster64MaxN = 64 * LQKC_MAX_G;      // linsys_t = double: the longest horizon a cluster kernel holds (eight members of 64 knots)
+static void sym_poll(mpcg_handle* h, hipStream_t st = nullptr, bool have_stream = false);
 
 extern "C" {
 
@@ -75,30 +50,26 @@ const char* mpcg_build_info(void) {
     return "libmpcg_hip gfx950 fp32 n=14 (row-per-lane DPP PCG for short horizons, lane-pair register-resident PCG to N = 128, clustered lane-pair PCG beyond, wave64 row-triple streaming PCG; linsys_t = double: row-per-lane to N = 32, lane-quad register-resident PCG to N = 64, clustered to 512; chunk-walking Schur formation in float and double; IIWA-14 KKT blocks with the analytic inverse-dynamics gradient)";
 }
 
-// device scratch of the clustered kernel: [queue line][flags: one 128-byte line per trajectory of the CALL, up to max_batch][cells: 1 KB
-// per member of the launch, up to two members per CU]
+// Device scratch of the clustered kernels, one contiguous run per call so that one small fill precedes every launch —
+//   float  (cluster_scratch):   [queue line][flags: one 128-byte line per trajectory of the CALL, up to max_batch][cells: 1 KB per member of the
+//                               launch, up to two members per CU][the handle's counter line, never re-zeroed by a launch: CounterSlot]
+//   double (cluster64_scratch): [queue line][flags][cells: one member per CU][a spare line]
 static size_t cluster_alloc_words(const mpcg_handle* h) {
-    return (size_t)2 * h->num_cus * LPKC_WG_WORDS + CL_FLAG_STRIDE + (size_t)h->max_batch * CL_FLAG_STRIDE
-           + 16;                         // + one line for the "cluster_fixups" counter (never re-zeroed by a launch)
+    return (size_t)2 * h->num_cus * LPKC_WG_WORDS + CL_FLAG_STRIDE + (size_t)h->max_batch * CL_FLAG_STRIDE + 16;
 }
-static unsigned long long* fixup_counter(const mpcg_handle* h) { return h->cluster_scratch + cluster_alloc_words(h) - 16; }
-// A handle whose latch resolved on block-Jacobi calls knows S only: the first SS call (Pinv has off-diagonal blocks) re-opens it, so that its
-// Pinv goes through a check before a lower-triangle kernel reads it.  Also where a pending reset of the device flag is issued.
-static int sym_prepare(mpcg_handle* h, int pcols, hipStream_t st) {
-    if (h->sym_state == 1 && pcols == 3 && !h->sym_pinv_ok) h->sym_state = 0;
-    if (h->sym_flag_reset) {
-        hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, st, fixup_counter(h) + 9, (size_t)1);
-        HIP_TRY(h, hipGetLastError());
-        h->sym_flag_reset = false;
-    }
-    return MPCG_OK;
+static size_t cluster64_alloc_words(const mpcg_handle* h) {
+    return CL_FLAG_STRIDE + (size_t)h->max_batch * CL_FLAG_STRIDE + (size_t)h->num_cus * RPLC_WG_WORDS + 16;
 }
-// The handle's copy of lambda0 (mpcg_handle::lam_backup).  mpcg_create sizes it for every horizon the automatic policy gives to a cluster kernel;
-// a forced "cluster" = G on a shorter horizon allocates at its first launch (hipMalloc: not inside a stream capture).
-static int ensure_lam_backup(mpcg_handle* h, size_t bytes, hipStream_t st) {
+// words of the counter line: trajectories re-solved by fix-up launches ("cluster_fixups"), block pairs that failed the last "check_symmetry" run,
+// the symmetry latch's sticky device flag
+enum CounterSlot { CTR_FIXUPS = 0, CTR_SYM_VIOLATIONS = 8, CTR_SYM_FLAG = 9 };
+static unsigned long long* counter(const mpcg_handle* h, CounterSlot slot) { return h->cluster_scratch + cluster_alloc_words(h) - 16 + slot; }
+
+// The handle's copy of lambda0 (mpcg_handle::lam_backup), grown to `bytes`: blocking (hipMalloc), behind whatever may still read the old copy.
+// Who sizes it: mpcg_create for every horizon the automatic policy gives to a cluster kernel, reserve_f64 for the double clusters, and
+// (ensure_lam_backup) a forced "cluster" = G on a shorter horizon at its first launch — hipMalloc: not inside a stream capture.
+static int grow_lam_backup(mpcg_handle* h, size_t bytes) {
     if (h->lam_backup_bytes >= bytes) return MPCG_OK;
-    { const int rc = alloc_allowed(h, st, "a cluster launch whose copy of lambda mpcg_create did not size (a forced \"cluster\" on a horizon the automatic policy gives to one CU; a "
-                                          "first double solve on a handle created with more than 8 MB of double iterates: \"reserve_f64\")"); if (rc != MPCG_OK) return rc; }
     if (h->lam_backup) {
         HIP_TRY(h, hipDeviceSynchronize());              // (an earlier call's fix-up launch may still read the old copy)
         HIP_TRY(h, hipFree(h->lam_backup));
@@ -107,6 +78,12 @@ static int ensure_lam_backup(mpcg_handle* h, size_t bytes, hipStream_t st) {
     HIP_TRY(h, hipMalloc(&h->lam_backup, bytes));
     h->lam_backup_bytes = bytes;
     return MPCG_OK;
+}
+static int ensure_lam_backup(mpcg_handle* h, size_t bytes, hipStream_t st) {
+    if (h->lam_backup_bytes >= bytes) return MPCG_OK;
+    const int rc = alloc_allowed(h, st, "a cluster launch whose copy of lambda mpcg_create did not size (a forced \"cluster\" on a horizon the automatic policy gives to one CU; a "
+                                        "first double solve on a handle created with more than 8 MB of double iterates: \"reserve_f64\")");
+    return rc != MPCG_OK ? rc : grow_lam_backup(h, bytes);
 }
 // queue + flags + cells zeroed and lambda copied, one launch (cluster_prologue_kernel)
 static int launch_cluster_prologue(mpcg_handle* h, unsigned long long* words, size_t zw, const void* lambda, size_t lam_bytes, hipStream_t st) {
@@ -127,11 +104,6 @@ static int launch_cluster_report(mpcg_handle* h, const unsigned long long* flags
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
-// the double cluster kernels' scratch: queue + flags + cells
-static size_t cluster64_alloc_words(const mpcg_handle* h) {
-    return CL_FLAG_STRIDE + (size_t)h->max_batch * CL_FLAG_STRIDE + (size_t)h->num_cus * RPLC_WG_WORDS + 16;
-}
-static constexpr size_t kEagerF64Bytes = (size_t)8 << 20;
 // the double cluster kernels' buffers: queue + flags + cells, and the double-sized copy of lambda0 their fix-up launch starts from.  Blocking
 // (hipMalloc): mpcg_create for small handles, "reserve_f64" = 1, or the first double cluster solve outside a capture.
 static int reserve_f64(mpcg_handle* h) {
@@ -141,17 +113,7 @@ static int reserve_f64(mpcg_handle* h) {
         HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->cluster64_scratch), cluster64_alloc_words(h) * sizeof(unsigned long long)));
         HIP_TRY(h, hipMemset(h->cluster64_scratch, 0, cluster64_alloc_words(h) * sizeof(unsigned long long)));
     }
-    const size_t bytes = (size_t)h->max_batch * h->N * h->n * sizeof(double);
-    if (h->lam_backup_bytes < bytes) {
-        if (h->lam_backup) {
-            HIP_TRY(h, hipDeviceSynchronize());              // (an earlier call's fix-up launch may still read the old copy)
-            HIP_TRY(h, hipFree(h->lam_backup));
-            h->lam_backup = nullptr; h->lam_backup_bytes = 0;
-        }
-        HIP_TRY(h, hipMalloc(&h->lam_backup, bytes));
-        h->lam_backup_bytes = bytes;
-    }
-    return MPCG_OK;
+    return grow_lam_backup(h, (size_t)h->max_batch * h->N * h->n * sizeof(double));
 }
 
 int mpcg_create(mpcg_handle** out, int device, uint32_t state_size, uint32_t knot_points, uint32_t max_batch) {
@@ -180,20 +142,17 @@ int mpcg_create(mpcg_handle** out, int device, uint32_t state_size, uint32_t kno
     h->nt_loads = 1;                    // SpMV kernel only: the matrix is read once — non-temporal loads, +4..9 % (profiles/r02_tune_spmv.txt, r04_spmv.txt)
     choose_auto(h, h->k, 1, 4);         // knobs of the single-workgroup kernels as a batch-1 call would pick them
     choose_auto(h, h->k, 1, 2);
+    // every failure from here on leaves through mpcg_destroy (which tolerates the members not made yet)
+    const auto give_up = [h](int rc, const std::string& msg) { (void)mpcg_destroy(h); return fail(nullptr, rc, msg); };
     // hand-off cells of the cluster kernel (512 B per member, up to two members per CU), allocated here so that every solve is pure stream work
     // and can be captured into a hipGraph
     if (hipSetDevice(device) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&h->cluster_scratch), cluster_alloc_words(h) * sizeof(unsigned long long)) != hipSuccess) {
-        delete h;
-        return fail(nullptr, MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the cluster scratch");
-    }
+        hipMalloc(reinterpret_cast<void**>(&h->cluster_scratch), cluster_alloc_words(h) * sizeof(unsigned long long)) != hipSuccess)
+        return give_up(MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the cluster scratch");
     (void)hipMemset(h->cluster_scratch, 0, cluster_alloc_words(h) * sizeof(unsigned long long));
     if (hipMalloc(reinterpret_cast<void**>(&h->sched_order), ((size_t)max_batch + 1) * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(h->sched_order, 0, ((size_t)max_batch + 1) * sizeof(uint32_t)) != hipSuccess) {      // tag 0 = no permutation yet (sched_pick)
-        (void)hipFree(h->cluster_scratch);
-        delete h;
-        return fail(nullptr, MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the dispatch-order buffer");
-    }
+        hipMemset(h->sched_order, 0, ((size_t)max_batch + 1) * sizeof(uint32_t)) != hipSuccess)      // tag 0 = no permutation yet (sched_pick)
+        return give_up(MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the dispatch-order buffer");
     // linsys_t = double beyond N = 32 runs cluster kernels with a queue + flags + cells buffer of their own and a DOUBLE-sized copy of lambda0.
     // A float caller never needs either (N = 128, max_batch 4096 = 59 MB per handle for nothing), so mpcg_create makes them only
     // while they are small (<= 8 MB of double iterates: every handle of the C++ shim, max_batch = 1) — then a fresh handle's first
@@ -203,21 +162,14 @@ int mpcg_create(mpcg_handle** out, int device, uint32_t state_size, uint32_t kno
         const size_t bytes64 = (size_t)max_batch * knot_points * state_size * sizeof(double);
         if (knot_points <= kCluster64MaxN && bytes64 <= kEagerF64Bytes) {
             const int rc = reserve_f64(h);
-            if (rc != MPCG_OK) { const std::string e = h->err; (void)mpcg_destroy(h); return fail(nullptr, rc, "mpcg_create: " + e); }
-        } else if (knot_points > kLpbMaxN) {
-            const size_t bytes = (size_t)max_batch * knot_points * state_size * sizeof(float);
-            if (hipMalloc(&h->lam_backup, bytes) != hipSuccess) {
-                (void)mpcg_destroy(h);
-                return fail(nullptr, MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the copy of lambda the cluster fix-up starts from");
-            }
-            h->lam_backup_bytes = bytes;
+            if (rc != MPCG_OK) return give_up(rc, "mpcg_create: " + h->err);
+        } else if (knot_points > kLpbMaxN && grow_lam_backup(h, (size_t)max_batch * knot_points * state_size * sizeof(float)) != MPCG_OK) {
+            return give_up(MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the copy of lambda the cluster fix-up starts from");
         }
     }
     if (hipEventCreateWithFlags(&h->sym_event, hipEventDisableTiming) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&h->sym_host), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
-        (void)mpcg_destroy(h);
-        return fail(nullptr, MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the symmetry latch");
-    }
+        hipHostMalloc(reinterpret_cast<void**>(&h->sym_host), sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
+        return give_up(MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the symmetry latch");
     *h->sym_host = 0;
     *out = h;
     return MPCG_OK;
@@ -246,152 +198,149 @@ int mpcg_destroy(mpcg_handle* h) {
 
 const char* mpcg_last_error(const mpcg_handle* h) { return h ? h->err.c_str() : mpcg_create_err.c_str(); }
 
-// key -> int member of the handle (plain knobs without range checks)
-static int* knob_ptr(mpcg_handle* h, const char* key) {
-    if (!strcmp(key, "pcg_reg_rows")) return &h->k.reg_rows;          // validated at launch
-    if (!strcmp(key, "pcg_lds_rows")) return &h->k.lds_rows;
-    if (!strcmp(key, "pcg_stream_bufs")) return &h->k.stream_bufs;
-    if (!strcmp(key, "lds_extra")) return &h->k.lds_extra;
-    if (!strcmp(key, "block_solve_wide")) return &h->block_solve_wide;
-    if (!strcmp(key, "pcg16_waves")) return &h->k.waves16;
-    if (!strcmp(key, "pcg16_reg_rows")) return &h->k.reg_rows16;
-    if (!strcmp(key, "pcg16_lds_rows")) return &h->k.lds_rows16;
+// ---- options: one table (include/mpcg.h, Options, documents every row) ---------------------------------------------------------------
+// A row: the key, where its value lives (an int of the handle, of its knobs or of `last`; none: the key's case in set / get does it all), the
+// range a set accepts (lo > hi: any value) with the rest of "<key> ..." it is refused with, flags, and the key's special case if it has one.
+enum : unsigned { OPT_R = 1, OPT_W = 2, OPT_RW = 3,
+                  OPT_BOOL = 4,             // stored as value ? 1 : 0
+                  OPT_CLEARS_AUTO = 8 };    // an explicit launch knob switches the automatic per-call configuration off — once the value has validated
+enum OptCase { O_PLAIN, O_WAVES, O_PCG_RPL, O_PCG_LQK, O_PCG_LPK, O_KKT_F32, O_RESERVE_F64, O_ASSUME_SYMMETRIC, O_SYMMETRY_STATE, O_PCG_RESIDENT, O_AUTO_CFG,
+               O_CLUSTER_FIXUPS };
+struct Opt {
+    const char* key;
+    int mpcg_handle::* hm; int PcgKnobs::* km; int LastKernel::* lm;
+    int lo, hi;
+    unsigned flags;
+    const char* refusal = nullptr;
+    OptCase special = O_PLAIN;
+};
+#define OPT_H(m) &mpcg_handle::m, nullptr, nullptr
+#define OPT_K(m) nullptr, &PcgKnobs::m, nullptr
+#define OPT_L(m) nullptr, nullptr, &LastKernel::m
+#define OPT_NONE nullptr, nullptr, nullptr
+#define ANY 1, 0
+static const Opt kOptions[] = {
+    // launch knobs of the single-workgroup kernels (the plain ones: unchecked here, validated at launch)
+    {"pcg_waves", OPT_K(waves), 4, 16, OPT_RW | OPT_CLEARS_AUTO, " must be 4, 8 or 16", O_WAVES},
+    {"pcg_max_wg_per_cu", OPT_K(max_wg_per_cu), 0, 8, OPT_RW | OPT_CLEARS_AUTO, " out of range"},
+    {"pcg_reg_rows", OPT_K(reg_rows), ANY, OPT_RW | OPT_CLEARS_AUTO},
+    {"pcg_lds_rows", OPT_K(lds_rows), ANY, OPT_RW | OPT_CLEARS_AUTO},
+    {"pcg_stream_bufs", OPT_K(stream_bufs), ANY, OPT_RW | OPT_CLEARS_AUTO},
+    {"lds_extra", OPT_K(lds_extra), ANY, OPT_RW},
+    {"pcg16_waves", OPT_K(waves16), ANY, OPT_RW},
+    {"pcg16_reg_rows", OPT_K(reg_rows16), ANY, OPT_RW},
+    {"pcg16_lds_rows", OPT_K(lds_rows16), ANY, OPT_RW},
+    {"pcg_resident", OPT_NONE, ANY, OPT_R, nullptr, O_PCG_RESIDENT},         // 1: the single-workgroup configuration streams nothing
+    {"auto_cfg", OPT_NONE, ANY, OPT_R, nullptr, O_AUTO_CFG},
+    // kernel families (quirk: these pcg_* keys leave "auto_cfg" alone)
+    {"pcg_rpl", OPT_H(rpl), -1, 1, OPT_RW, " must be -1 (auto), 0 or 1", O_PCG_RPL},
+    {"rpl_waves", OPT_H(rpl_waves), 0, 16, OPT_RW, " must be 0 (auto), 4, 8 or 16", O_WAVES},
+    {"pcg_lqk", OPT_H(lqk), -1, 1, OPT_RW, " must be -1 (auto), 0 (off) or 1 (forced)", O_PCG_LQK},
+    {"pcg_lqb", OPT_H(lqb), -1, 1, OPT_RW, " must be -1 (auto), 0 (off) or 1 (in place of the lane-pair kernel)"},
+    {"pcg_lpk", OPT_H(lpk), -1, 1, OPT_RW, " must be -1 (auto), 0 (off) or 1 (forced)", O_PCG_LPK},
+    {"cluster", OPT_H(cluster), -1, 32, OPT_RW, " must be -1 (auto), 0 (off) or 1..32 workgroups per trajectory"},
+    {"cluster_fixup", OPT_H(cluster_fixup), ANY, OPT_RW | OPT_BOOL},
+    {"cluster_l2", OPT_H(cluster_l2), ANY, OPT_RW | OPT_BOOL},
+    {"cluster_test_fail", OPT_H(cluster_test_fail), ANY, OPT_W | OPT_BOOL},
+    {"cluster_fixups", OPT_NONE, ANY, OPT_R, nullptr, O_CLUSTER_FIXUPS},
+    {"reserve_f64", OPT_NONE, ANY, OPT_W, nullptr, O_RESERVE_F64},
+    {"sched_hint", OPT_H(sched_hint), ANY, OPT_RW | OPT_BOOL},
+    {"num_cus", OPT_H(num_cus), ANY, OPT_R},
+    // the symmetry latch
+    {"check_symmetry", OPT_H(check_symmetry), ANY, OPT_RW | OPT_BOOL},
+    {"last_symmetry_violations", OPT_H(last_sym_violations), ANY, OPT_R},
+    {"assume_symmetric", OPT_NONE, ANY, OPT_W, nullptr, O_ASSUME_SYMMETRIC},
+    {"symmetry_state", OPT_H(sym_state), ANY, OPT_R, nullptr, O_SYMMETRY_STATE},
+    // SpMV, producers, plant
+    {"nt_loads", OPT_H(nt_loads), ANY, OPT_RW | OPT_BOOL},
+    {"spmv_mfma", OPT_H(spmv_mfma), ANY, OPT_RW | OPT_BOOL},
+    {"spmv_blocks_per_cu", OPT_H(spmv_blocks_per_cu), 1, 64, OPT_RW, " out of range"},
+    {"schur_dpp", OPT_H(schur_dpp), ANY, OPT_RW | OPT_BOOL},
+    {"schur_chunk", OPT_H(schur_chunk), 0, 2048, OPT_RW, " must be 0 (auto) or 1..2048 block rows"},
+    {"last_schur_chunk", OPT_H(last_schur_chunk), ANY, OPT_R},
+    {"dz_dpp", OPT_H(dz_dpp), ANY, OPT_RW | OPT_BOOL},
+    {"last_dz_route", OPT_H(last_dz_route), ANY, OPT_R},
+    {"producers_generic", OPT_H(producers_generic), ANY, OPT_RW | OPT_BOOL},
+    {"block_solve_wide", OPT_H(block_solve_wide), ANY, OPT_RW},
+    {"block_solve_f64", OPT_H(block_solve_f64), 0, 1, OPT_RW, " must be 0 (the float sweep) or 1 (float64 inside)"},
+    {"kkt_analytic", OPT_H(kkt_analytic), ANY, OPT_RW | OPT_BOOL},
+    {"kkt_f32", OPT_H(kkt_f32), ANY, OPT_RW, nullptr, O_KKT_F32},
+    {"merit_f32", OPT_H(merit_f32), 0, 1, OPT_RW, " must be 0 (float64 inside) or 1 (packed float)"},
+    {"integrator", OPT_H(integrator), 0, 1, OPT_RW, " must be 0 (explicit Euler) or 1 (semi-implicit Euler)"},
+    {"sim_integrator", OPT_H(sim_integrator), 0, 1, OPT_RW, " must be 0 (explicit Euler) or 1 (semi-implicit Euler)"},
+    // what the last solve on this handle launched (family: 0 single-workgroup row-pair, 3 generic, 5 row-per-lane, 6 lane-pair, 7 clustered lane-pair,
+    // 8 clustered row-per-lane (double), 9 / 10 lane-quad and clustered lane-quad (double), 11 lane-quad)
+    {"last_kernel_family", OPT_L(family), ANY, OPT_R},
+    {"last_kernel_waves", OPT_L(waves), ANY, OPT_R},
+    {"last_kernel_reg_rows", OPT_L(reg_rows), ANY, OPT_R},
+    {"last_kernel_lds_rows", OPT_L(lds_rows), ANY, OPT_R},
+    {"last_kernel_lds_extra", OPT_L(lds_extra), ANY, OPT_R},
+    {"last_kernel_stream_bufs", OPT_L(stream_bufs), ANY, OPT_R},
+    {"last_kernel_cluster", OPT_L(cluster), ANY, OPT_R},
+    {"last_kernel_lds_bytes", OPT_L(lds_bytes), ANY, OPT_R},
+};
+#undef OPT_H
+#undef OPT_K
+#undef OPT_L
+#undef OPT_NONE
+#undef ANY
+static const Opt* find_option(const char* key, unsigned access) {
+    for (const Opt& o : kOptions)
+        if (!strcmp(key, o.key)) return o.flags & access ? &o : nullptr;
     return nullptr;
 }
+static int* option_slot(mpcg_handle* h, const Opt& o) { return o.hm ? &(h->*o.hm) : o.km ? &(h->k.*o.km) : &(h->last.*o.lm); }
 
 int mpcg_set_option(mpcg_handle* h, const char* key, int value) {
     if (!h || !key) return MPCG_ERR_INVALID;
-    // an explicit pcg_* knob switches the automatic per-call configuration off — once the key has validated
-    const bool is_pcg = !strncmp(key, "pcg_", 4);
-    if (!strcmp(key, "pcg_waves")) {
-        if (value != 4 && value != 8 && value != 16) return fail(h, MPCG_ERR_INVALID, "pcg_waves must be 4, 8 or 16");
-        h->k.waves = value; h->auto_cfg = false; return MPCG_OK;
-    }
-    if (!strcmp(key, "pcg_max_wg_per_cu")) {
-        if (value < 0 || value > 8) return fail(h, MPCG_ERR_INVALID, "pcg_max_wg_per_cu out of range");
-        h->k.max_wg_per_cu = value; h->auto_cfg = false; return MPCG_OK;
-    }
-    if (!strcmp(key, "pcg_rpl")) {
-        if (value < -1 || value > 1) return fail(h, MPCG_ERR_INVALID, "pcg_rpl must be -1 (auto), 0 or 1");
-        if (value == 1 && h->N > kRplMaxN) return fail(h, MPCG_ERR_UNSUPPORTED, "pcg_rpl: the row-per-lane kernel holds knot_points <= 64");
-        h->rpl = value; return MPCG_OK;
-    }
-    if (!strcmp(key, "rpl_waves")) {
-        if (value != 0 && value != 4 && value != 8 && value != 16) return fail(h, MPCG_ERR_INVALID, "rpl_waves must be 0 (auto), 4, 8 or 16");
-        h->rpl_waves = value; return MPCG_OK;
-    }
-    if (!strcmp(key, "pcg_lqk")) {
-        if (value < -1 || value > 1) return fail(h, MPCG_ERR_INVALID, "pcg_lqk must be -1 (auto), 0 (off) or 1 (forced)");
-        if (value == 1 && h->N > kLqkMaxN) return fail(h, MPCG_ERR_UNSUPPORTED, "pcg_lqk: the lane-quad kernel holds knot_points <= 64");
-        h->lqk = value; return MPCG_OK;
-    }
-    if (!strcmp(key, "pcg_lqb")) {
-        if (value < -1 || value > 1) return fail(h, MPCG_ERR_INVALID, "pcg_lqb must be -1 (auto), 0 (off) or 1 (in place of the lane-pair kernel)");
-        h->lqb = value; return MPCG_OK;
-    }
-    if (!strcmp(key, "pcg_lpk")) {
-        if (value < -1 || value > 1) return fail(h, MPCG_ERR_INVALID, "pcg_lpk must be -1 (auto), 0 (off) or 1 (forced)");
-        if (value == 1 && h->N > kLpbMaxN) return fail(h, MPCG_ERR_UNSUPPORTED, "pcg_lpk: the lane-pair kernel holds knot_points <= 128");
-        h->lpk = value; return MPCG_OK;
-    }
-    if (int* p = knob_ptr(h, key)) { *p = value; if (is_pcg) h->auto_cfg = false; return MPCG_OK; }
-    if (!strcmp(key, "nt_loads")) { h->nt_loads = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "cluster_fixup")) { h->cluster_fixup = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "cluster_l2")) { h->cluster_l2 = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "reserve_f64")) { return value ? reserve_f64(h) : MPCG_OK; }
-    if (!strcmp(key, "cluster_test_fail")) { h->cluster_test_fail = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "check_symmetry")) { h->check_symmetry = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "assume_symmetric")) {      // 1: the caller vouches (or fills only the lower block triangle): no check; 0: back to "unknown"
+    const Opt* o = find_option(key, OPT_W);
+    if (!o) return fail(h, MPCG_ERR_INVALID, std::string("unknown option ") + key);
+    const auto refuse = [&](int rc, const char* why) { return fail(h, rc, std::string(key) + why); };
+    const auto too_long = [&](uint32_t nmax, const char* kernel) {
+        return refuse(MPCG_ERR_UNSUPPORTED, (": the " + std::string(kernel) + " kernel holds knot_points <= " + std::to_string(nmax)).c_str());
+    };
+    if (o->lo <= o->hi && (value < o->lo || value > o->hi)) return refuse(MPCG_ERR_INVALID, o->refusal);
+    switch (o->special) {
+    case O_WAVES: if (value != 0 && value != 4 && value != 8 && value != 16) return refuse(MPCG_ERR_INVALID, o->refusal); break;
+    case O_PCG_RPL: if (value == 1 && h->N > kRplMaxN) return too_long(kRplMaxN, "row-per-lane"); break;
+    case O_PCG_LQK: if (value == 1 && h->N > kLqkMaxN) return too_long(kLqkMaxN, "lane-quad"); break;
+    case O_PCG_LPK: if (value == 1 && h->N > kLpbMaxN) return too_long(kLpbMaxN, "lane-pair"); break;
+    case O_KKT_F32: value = value == 2 ? 2 : value ? 1 : 0; break;
+    case O_RESERVE_F64: return value ? reserve_f64(h) : MPCG_OK;
+    case O_ASSUME_SYMMETRIC:      // 1: the caller vouches (or fills only the lower block triangle): no check; 0: back to "unknown"
         // (1 vouches for Pinv too.  0 also forgets a violation: the sticky device flag is cleared by the next solve, on its stream)
         h->sym_state = value ? 1 : 0; h->sym_pending = false; h->sym_pinv_ok = value != 0;
         h->sym_pinv_guarded = h->sym_armed_pinv = false;
         if (!value) h->sym_flag_reset = true;
         return MPCG_OK;
+    default: break;
     }
-    if (!strcmp(key, "schur_dpp")) { h->schur_dpp = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "schur_chunk")) { if (value < 0 || value > 2048) return fail(h, MPCG_ERR_INVALID, "schur_chunk must be 0 (auto) or 1..2048 block rows"); h->schur_chunk = value; return MPCG_OK; }
-    if (!strcmp(key, "dz_dpp")) { h->dz_dpp = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "producers_generic")) { h->producers_generic = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "kkt_analytic")) { h->kkt_analytic = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "kkt_f32")) { h->kkt_f32 = value == 2 ? 2 : value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "merit_f32")) {
-        if (value != 0 && value != 1) return fail(h, MPCG_ERR_INVALID, "merit_f32 must be 0 (float64 inside) or 1 (packed float)");
-        h->merit_f32 = value; return MPCG_OK;
-    }
-    if (!strcmp(key, "integrator") || !strcmp(key, "sim_integrator")) {
-        if (value != 0 && value != 1) return fail(h, MPCG_ERR_INVALID, std::string(key) + " must be 0 (explicit Euler) or 1 (semi-implicit Euler)");
-        (key[0] == 's' ? h->sim_integrator : h->integrator) = value; return MPCG_OK;
-    }
-    if (!strcmp(key, "block_solve_f64")) {
-        if (value != 0 && value != 1) return fail(h, MPCG_ERR_INVALID, "block_solve_f64 must be 0 (the float sweep) or 1 (float64 inside)");
-        h->block_solve_f64 = value; return MPCG_OK;
-    }
-    if (!strcmp(key, "sched_hint")) { h->sched_hint = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "cluster")) {
-        if (value < -1 || value > 32) return fail(h, MPCG_ERR_INVALID, "cluster must be -1 (auto), 0 (off) or 1..32 workgroups per trajectory");
-        h->cluster = value; return MPCG_OK;
-    }
-    if (!strcmp(key, "spmv_mfma")) { h->spmv_mfma = value ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "spmv_blocks_per_cu")) {
-        if (value < 1 || value > 64) return fail(h, MPCG_ERR_INVALID, "spmv_blocks_per_cu out of range");
-        h->spmv_blocks_per_cu = value; return MPCG_OK;
-    }
-    return fail(h, MPCG_ERR_INVALID, std::string("unknown option ") + key);
+    *option_slot(h, *o) = o->flags & OPT_BOOL ? (value ? 1 : 0) : value;
+    if (o->flags & OPT_CLEARS_AUTO) h->auto_cfg = false;
+    return MPCG_OK;
 }
 
-int mpcg_get_option(const mpcg_handle* h, const char* key, int* value) {
+int mpcg_get_option(const mpcg_handle* h, const char* key, int* value) {      // (an unknown key: MPCG_ERR_INVALID, the handle's error text stays)
     if (!h || !key || !value) return MPCG_ERR_INVALID;
-    if (!strcmp(key, "pcg_waves")) { *value = h->k.waves; return MPCG_OK; }
-    if (!strcmp(key, "pcg_max_wg_per_cu")) { *value = h->k.max_wg_per_cu; return MPCG_OK; }
-    if (!strcmp(key, "pcg_lpk")) { *value = h->lpk; return MPCG_OK; }
-    if (!strcmp(key, "pcg_lqb")) { *value = h->lqb; return MPCG_OK; }
-    if (!strcmp(key, "pcg_lqk")) { *value = h->lqk; return MPCG_OK; }
-    if (!strcmp(key, "pcg_rpl")) { *value = h->rpl; return MPCG_OK; }
-    if (!strcmp(key, "rpl_waves")) { *value = h->rpl_waves; return MPCG_OK; }
-    if (const int* p = knob_ptr(const_cast<mpcg_handle*>(h), key)) { *value = *p; return MPCG_OK; }
-    if (!strcmp(key, "nt_loads")) { *value = h->nt_loads; return MPCG_OK; }
-    if (!strcmp(key, "pcg_resident")) { *value = stream_bufs_for(h, h->k, h->k.waves, 4) == 0; return MPCG_OK; }   // 1: the single-workgroup configuration streams nothing
-    if (!strcmp(key, "cluster")) { *value = h->cluster; return MPCG_OK; }
-    if (!strcmp(key, "cluster_fixup")) { *value = h->cluster_fixup; return MPCG_OK; }
-    if (!strcmp(key, "cluster_l2")) { *value = h->cluster_l2; return MPCG_OK; }
-    if (!strcmp(key, "check_symmetry")) { *value = h->check_symmetry; return MPCG_OK; }
-    if (!strcmp(key, "last_symmetry_violations")) { *value = h->last_sym_violations; return MPCG_OK; }
-    if (!strcmp(key, "symmetry_state")) { sym_poll(const_cast<mpcg_handle*>(h)); *value = h->sym_state; return MPCG_OK; }
-    if (!strcmp(key, "schur_dpp")) { *value = h->schur_dpp; return MPCG_OK; }
-    if (!strcmp(key, "schur_chunk")) { *value = h->schur_chunk; return MPCG_OK; }
-    if (!strcmp(key, "last_schur_chunk")) { *value = h->last_schur_chunk; return MPCG_OK; }
-    if (!strcmp(key, "last_dz_route")) { *value = h->last_dz_route; return MPCG_OK; }
-    if (!strcmp(key, "dz_dpp")) { *value = h->dz_dpp; return MPCG_OK; }
-    if (!strcmp(key, "producers_generic")) { *value = h->producers_generic; return MPCG_OK; }
-    if (!strcmp(key, "kkt_analytic")) { *value = h->kkt_analytic; return MPCG_OK; }
-    if (!strcmp(key, "kkt_f32")) { *value = h->kkt_f32; return MPCG_OK; }
-    if (!strcmp(key, "merit_f32")) { *value = h->merit_f32; return MPCG_OK; }
-    if (!strcmp(key, "integrator")) { *value = h->integrator; return MPCG_OK; }
-    if (!strcmp(key, "sim_integrator")) { *value = h->sim_integrator; return MPCG_OK; }
-    if (!strcmp(key, "block_solve_f64")) { *value = h->block_solve_f64; return MPCG_OK; }
-    if (!strcmp(key, "sched_hint")) { *value = h->sched_hint; return MPCG_OK; }
-    if (!strcmp(key, "spmv_blocks_per_cu")) { *value = h->spmv_blocks_per_cu; return MPCG_OK; }
-    if (!strcmp(key, "spmv_mfma")) { *value = h->spmv_mfma; return MPCG_OK; }
-    if (!strcmp(key, "num_cus")) { *value = h->num_cus; return MPCG_OK; }
-    if (!strcmp(key, "auto_cfg")) { *value = h->auto_cfg ? 1 : 0; return MPCG_OK; }
-    if (!strcmp(key, "cluster_fixups")) {
+    const Opt* o = find_option(key, OPT_R);
+    if (!o) return MPCG_ERR_INVALID;
+    mpcg_handle* hm = const_cast<mpcg_handle*>(h);
+    switch (o->special) {
+    case O_PCG_RESIDENT: *value = stream_bufs_for(h, h->k, h->k.waves, 4) == 0; return MPCG_OK;
+    case O_AUTO_CFG: *value = h->auto_cfg ? 1 : 0; return MPCG_OK;
+    case O_CLUSTER_FIXUPS: {
         // trajectories re-solved by fix-up launches since mpcg_create (their cluster gave up after the bounded spin): a blocking
         // 8-byte D2H copy — it waits for the device work queued before it
         unsigned long long v = 0;
-        if (hipSetDevice(h->device) != hipSuccess || hipMemcpy(&v, fixup_counter(h), sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return MPCG_ERR_HIP;
+        if (hipSetDevice(h->device) != hipSuccess || hipMemcpy(&v, counter(h, CTR_FIXUPS), sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return MPCG_ERR_HIP;
         *value = v > 0x7fffffffull ? 0x7fffffff : (int)v;
         return MPCG_OK;
     }
-    // what the last solve on this handle launched
-    if (!strcmp(key, "last_kernel_family")) { *value = h->last.family; return MPCG_OK; }      // 0 single-workgroup row-pair, 3 generic, 5 row-per-lane, 6 lane-pair, 7 clustered lane-pair, 8 clustered row-per-lane (double)
-    if (!strcmp(key, "last_kernel_waves")) { *value = h->last.waves; return MPCG_OK; }
-    if (!strcmp(key, "last_kernel_reg_rows")) { *value = h->last.reg_rows; return MPCG_OK; }
-    if (!strcmp(key, "last_kernel_lds_rows")) { *value = h->last.lds_rows; return MPCG_OK; }
-    if (!strcmp(key, "last_kernel_lds_extra")) { *value = h->last.lds_extra; return MPCG_OK; }
-    if (!strcmp(key, "last_kernel_stream_bufs")) { *value = h->last.stream_bufs; return MPCG_OK; }
-    if (!strcmp(key, "last_kernel_cluster")) { *value = h->last.cluster; return MPCG_OK; }
-    if (!strcmp(key, "last_kernel_lds_bytes")) { *value = h->last.lds_bytes; return MPCG_OK; }
-    return MPCG_ERR_INVALID;
+    case O_SYMMETRY_STATE: sym_poll(hm); break;
+    default: break;
+    }
+    *value = *option_slot(hm, *o);
+    return MPCG_OK;
 }
 
 }  // extern "C"
@@ -784,10 +733,15 @@ static PcgPlan plan_f64(const mpcg_handle* h, uint32_t batch, int pcols, bool lo
 }
 
 // ---- launching a plan -------------------------------------------------------------------------------
-// hipFuncSetAttribute when the launch needs more than 48 KiB of LDS, the launch (grid 0: `batch` workgroups), the error check
+// hipFuncSetAttribute when a launch needs more than 48 KiB of LDS
+static int raise_lds(mpcg_handle* h, const Launch& L) {
+    if (L.lds > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(L.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    return MPCG_OK;
+}
+// the LDS limit, the launch (grid 0: `batch` workgroups), the error check
 static int launch(mpcg_handle* h, const Launch& L, void* arg, uint32_t batch, hipStream_t st) {
     if (L.rc != MPCG_OK) return fail(h, L.rc, L.err);
-    if (L.lds > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(L.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    { const int rc = raise_lds(h, L); if (rc != MPCG_OK) return rc; }
     void* args[] = {arg};
     (void)hipLaunchKernel(L.kern, dim3(L.grid ? L.grid : batch), dim3(L.block), args, L.lds, st);
     HIP_TRY(h, hipGetLastError());
@@ -835,7 +789,7 @@ static int launch_cluster(mpcg_handle* h, const PcgPlan& p, const A& a, uint32_t
     if (!p.fixup) return launch_cluster_report(h, ca.fail_flags, p.G, batch, a.iters, a.max_iter_exit, st);
     A c = a;
     c.redo_flags = ca.fail_flags; c.redo_stride = CL_FLAG_STRIDE; c.redo_skip = (unsigned)p.G;
-    c.redo_count = count_fixups ? fixup_counter(h) : nullptr;
+    c.redo_count = count_fixups ? counter(h, CTR_FIXUPS) : nullptr;
     c.lam0 = static_cast<decltype(c.lam0)>(h->lam_backup);     // (members that finished a trajectory their cluster did not have written their knots of lambda)
     if constexpr (std::is_same<A, PcgArgs64>::value) c.lower = p.fix_lower;
     return launch_args(h, p.fix, c, batch, st);
@@ -848,6 +802,7 @@ static int launch_plan(mpcg_handle* h, const PcgPlan& p, const A& a, uint32_t ba
     return rc;
 }
 
+// ---- the symmetry latch (mpcg.h, BLOCK SYMMETRY) ----------------------------------------------------------------------------------
 // Tolerance of the block-symmetry checks: block pairs (k, right) / (k+1, left) that differ by more than 1 % of their largest entry.  The
 // reference's construction gives 0 for S; its symmetric-stair Pinv[k,right] / Pinv[k+1,left] are the same triple product associated two ways
 // in float — measured on the bench's systems: 2.5e-5 of the largest entry in the median, 6e-5 at worst, more on worse-conditioned blocks —
@@ -857,23 +812,68 @@ static constexpr float kSymRelTol = 1e-2f;
 //  different system than the caller's without a word — ADVICE r05)
 static constexpr double kSymRelTol64 = 1e-6;
 
-// block pairs of S and (SS only) Pinv that fail the check.  Blocking: waits for `st`.
-// S (and Pinv when it has off-diagonal blocks) of one call through bd_symmetry_check_kernel, in the call's storage type
-static void launch_symmetry_check(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st, unsigned blocks, unsigned long long* cnt, unsigned long long* flag) {
-    for (const void* m : {a.S, a.pcols == 3 ? a.Pinv : nullptr}) {
-        if (!m) continue;
-        if (a.esz == 2)
-            hipLaunchKernelGGL(bd_symmetry_check_kernel<_Float16>, dim3(blocks), dim3(256), 0, st, static_cast<const _Float16*>(m), (int)h->N, (int)batch, kSymRelTol, cnt, flag);
-        else
-            hipLaunchKernelGGL(bd_symmetry_check_kernel<float>, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(m), (int)h->N, (int)batch, kSymRelTol, cnt, flag);
-    }
-}
-static int symmetry_violations(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st, int* out) {
-    unsigned long long* cnt = fixup_counter(h) + 8;
-    HIP_TRY(h, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st));
+// S (and Pinv when it has off-diagonal blocks: pcols = 3) of one call through bd_symmetry_check_kernel, in the call's storage type (esz 2, 4 or 8
+// bytes) with that type's tolerance: failing block pairs are added to *cnt, OR-ed into *flag (either may be null)
+static void launch_sym_check(mpcg_handle* h, int esz, const void* S, const void* Pinv, int pcols, uint32_t batch, hipStream_t st,
+                             unsigned long long* cnt, unsigned long long* flag) {
     const long items = (long)batch * ((long)h->N - 1);
     const unsigned blocks = (unsigned)((items + 3) / 4);
-    launch_symmetry_check(h, a, batch, st, blocks, cnt, nullptr);
+    const auto go = [&](auto type, float tol) {
+        using MT = decltype(type);
+        for (const void* m : {S, pcols == 3 ? Pinv : nullptr})
+            if (m) hipLaunchKernelGGL(bd_symmetry_check_kernel<MT>, dim3(blocks), dim3(256), 0, st, static_cast<const MT*>(m), (int)h->N, (int)batch, tol, cnt, flag);
+    };
+    if (esz == 2) go(_Float16(), kSymRelTol); else if (esz == 4) go(float(), kSymRelTol); else go(double(), (float)kSymRelTol64);
+}
+static void sym_mark_violated(mpcg_handle* h) {
+    h->sym_state = 2;
+    h->err = "warning: S / Pinv of a solve on this handle were not block-symmetric (block (k, right) != block (k+1, left)^T): the handle now "
+             "runs kernels that read all three block columns (include/mpcg.h, BLOCK SYMMETRY)";
+}
+// A handle whose latch resolved on block-Jacobi calls knows S only: the first SS call (Pinv has off-diagonal blocks) re-opens it, so that its
+// Pinv goes through a check before a lower-triangle kernel reads it.
+static void sym_reopen_for_pinv(mpcg_handle* h, int pcols) {
+    if (h->sym_state == 1 && pcols == 3 && !h->sym_pinv_ok) h->sym_state = 0;
+}
+// a pending reset of the sticky device flag ("assume_symmetric" = 0 after a violation) is issued by the next solve, on its stream
+static int sym_reset_flag(mpcg_handle* h, hipStream_t st) {
+    if (!h->sym_flag_reset) return MPCG_OK;
+    hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, st, counter(h, CTR_SYM_FLAG), (size_t)1);
+    HIP_TRY(h, hipGetLastError());
+    h->sym_flag_reset = false;
+    return MPCG_OK;
+}
+// has the asynchronous copy of the device flag landed?
+// (never while `st` is being captured into a graph: an event query is not a capturable operation and would invalidate the capture —
+//  a capturing caller stays on the guarded launches, which are plain kernel launches)
+static void sym_poll(mpcg_handle* h, hipStream_t st, bool have_stream) {
+    if (!h->sym_pending) return;
+    if (have_stream) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return;
+    }
+    // (the query itself in relaxed capture mode: with ANOTHER stream of this thread being captured in global mode an event query is an
+    //  "unsafe" call that would invalidate that unrelated capture — mpcg_get_option("symmetry_state") passes no stream at all)
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    (void)hipThreadExchangeStreamCaptureMode(&mode);
+    const hipError_t q = hipEventQuery(h->sym_event);
+    (void)hipThreadExchangeStreamCaptureMode(&mode);
+    if (q != hipSuccess) return;
+    h->sym_pending = false;
+    if (*h->sym_host == 0 && h->sym_guard_seq != h->sym_armed_seq) {
+        // guarded solves were issued AFTER this copy was armed: a clean flag says nothing about their matrices.  Stay unknown — the next
+        // guarded call arms a new copy, which (the device flag is sticky) covers them all.
+        return;
+    }
+    if (*h->sym_host) sym_mark_violated(h);
+    else { h->sym_state = 1; h->sym_pinv_ok = h->sym_armed_pinv; }
+}
+
+// "check_symmetry": block pairs of S and (SS only) Pinv that fail the check.  Blocking: waits for `st`.
+static int symmetry_violations(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st, int* out) {
+    unsigned long long* cnt = counter(h, CTR_SYM_VIOLATIONS);
+    HIP_TRY(h, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st));
+    launch_sym_check(h, a.esz, a.S, a.Pinv, a.pcols, batch, st, cnt, nullptr);
     HIP_TRY(h, hipGetLastError());
     unsigned long long v = 0;
     HIP_TRY(h, hipMemcpyAsync(&v, cnt, sizeof v, hipMemcpyDeviceToHost, st));
@@ -882,7 +882,7 @@ static int symmetry_violations(mpcg_handle* h, const PcgArgs& a, uint32_t batch,
     return MPCG_OK;
 }
 
-// A lower-triangle launch of a handle that does not know yet whether its caller's matrices are block-symmetric (mpcg.h, BLOCK SYMMETRY):
+// The float latch: asynchronous.  A lower-triangle launch of a handle that does not know yet whether its caller's matrices are block-symmetric:
 //   check kernel(s)  -> OR into the handle's device flag (never reset: the latch)
 //   the lower-triangle kernel, gated: its workgroups leave at once if the flag is set
 //   a three-column kernel, gated the other way: runs only if the flag is set
@@ -891,12 +891,10 @@ static int symmetry_violations(mpcg_handle* h, const PcgArgs& a, uint32_t batch,
 // Returns 1 when the plan has no lower-triangle kernel after all (the check kernels have run: the caller falls through).
 static int launch_guarded(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipStream_t st, bool* order) {
     const PcgPlan p = plan_f32(h, batch, a.esz, a.pcols, GATED);
-    unsigned long long* flag = fixup_counter(h) + 9;
-    const long items = (long)batch * ((long)h->N - 1);
-    const unsigned blocks = (unsigned)((items + 3) / 4);
+    unsigned long long* flag = counter(h, CTR_SYM_FLAG);
     ++h->sym_guard_seq;
     if (a.pcols == 3) h->sym_pinv_guarded = true;
-    launch_symmetry_check(h, a, batch, st, blocks, nullptr, flag);
+    launch_sym_check(h, a.esz, a.S, a.Pinv, a.pcols, batch, st, nullptr, flag);
     HIP_TRY(h, hipGetLastError());
     const int fam = p.last.family;
     if (fam != FAM_LPK && fam != FAM_LQB && fam != FAM_LPKC) return 1;
@@ -920,6 +918,60 @@ static int launch_guarded(mpcg_handle* h, const PcgArgs& a, uint32_t batch, hipS
     }
     return MPCG_OK;
 }
+// The double latch: the double kernels that read only the left + diagonal block columns use the same per-handle state, but a handle that does not
+// know yet checks THIS call's matrices once, with one blocking 8-byte copy (never during capture: a capturing call on such a handle runs a
+// kernel that reads all three columns).
+static int f64_symmetry_latch(mpcg_handle* h, const PcgArgs64& a, uint32_t batch, hipStream_t st) {
+    sym_poll(h, st, true);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    sym_reopen_for_pinv(h, a.pcols);      // (a capturing call cannot check the Pinv it re-opens for: it runs a three-column kernel)
+    if (h->sym_state != 0 || h->sym_pending || capturing) return MPCG_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    { const int rc = sym_reset_flag(h, st); if (rc != MPCG_OK) return rc; }
+    unsigned long long* flag = counter(h, CTR_SYM_FLAG);
+    launch_sym_check(h, sizeof(double), a.S, a.Pinv, a.pcols, batch, st, nullptr, flag);
+    HIP_TRY(h, hipGetLastError());
+    unsigned long long v = 0;
+    HIP_TRY(h, hipMemcpyAsync(&v, flag, sizeof v, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    if (v) sym_mark_violated(h); else h->sym_state = 1;
+    h->sym_pinv_ok = !v && a.pcols == 3;
+    return MPCG_OK;
+}
+
+// ---- the solve entries' shared host path -------------------------------------------------------------------------------------------
+// The fields PcgArgs and PcgArgsG<T> have in common, from an entry's arguments (everything else: the structs' defaults, set by the launch paths)
+template <typename A, typename MT, typename T>
+static A solve_args(const mpcg_handle* h, const MT* S, const MT* Pinv, const T* gamma, T* lambda, T* r_out, T* p_out, uint32_t* iters, uint8_t* exits,
+                    uint32_t max_iter, T exit_tol, int pcols) {
+    A a{};
+    a.S = S; a.Pinv = Pinv; a.gamma = gamma; a.lambda = lambda; a.r_out = r_out; a.p_out = p_out;
+    a.iters = iters; a.max_iter_exit = exits;
+    a.N = (int)h->N; a.max_iter = (int)max_iter; a.exit_tol = exit_tol; a.pcols = pcols;
+    return a;
+}
+// What the five solve entries check before they launch, in the order they report it: null handle; null pointers; (the batched entries) batch 0 —
+// nothing to do — batch above max_batch, the preconditioner; max_iter; the alignment of S / Pinv in their storage type MT (float 16 bytes,
+// fp16 4, double none) — which the float `_ref` entry looks at BEFORE max_iter.  Returns true when the call ends here, with *rc.
+template <typename MT>
+static bool solve_ends(mpcg_handle* h, const char* entry, bool ref, const MT* S, const MT* Pinv, const void* gamma, const void* lambda, const void* iters,
+                       const void* exits, uint32_t batch, int precond, uint32_t max_iter, int* rc) {
+    constexpr uintptr_t align = std::is_same<MT, float>::value ? 16 : std::is_same<MT, uint16_t>::value ? 4 : 1;
+    const auto refuse = [&](const char* why) { *rc = h ? fail(h, MPCG_ERR_INVALID, std::string(entry) + why) : MPCG_ERR_INVALID; return true; };
+    const auto misaligned = [&] { return ((reinterpret_cast<uintptr_t>(S) | reinterpret_cast<uintptr_t>(Pinv)) & (align - 1)) != 0; };
+    const char* align_text = align == 16 ? ": d_S / d_Pinv must be 16-byte aligned" : ": d_S16 / d_Pinv16 must be 4-byte aligned";
+    if (!h) return refuse("");
+    if (!S || !Pinv || !gamma || !lambda || !iters || !exits) return refuse(": null device pointer");
+    if (!ref) {
+        if (batch == 0) { *rc = MPCG_OK; return true; }
+        if (batch > h->max_batch) return refuse(": batch exceeds max_batch");
+        if (precond != MPCG_PRECOND_JACOBI && precond != MPCG_PRECOND_SS) return refuse(": bad preconditioner");
+    } else if (misaligned()) return refuse(align_text);
+    if (max_iter > 0x7fffffffu) return refuse(": max_iter too large");
+    if (misaligned()) return refuse(align_text);
+    return false;
+}
 
 // One float / fp16 solve.  *order: the launched plan asks for the dispatch-order kernel.
 static int launch_pcg(mpcg_handle* h, const PcgArgs& a_in, uint32_t batch, hipStream_t st, int esz, bool* order) {
@@ -929,10 +981,8 @@ static int launch_pcg(mpcg_handle* h, const PcgArgs& a_in, uint32_t batch, hipSt
     PcgPlan p = plan_f32(h, batch, esz, a.pcols, LOWER);
     *order = false;
     if (h->generic) {      // state_size != 14: the PcgArgs of the tuned path re-packed for the generic kernel
-        PcgArgsG<float> g;
-        g.S = static_cast<const float*>(a.S); g.Pinv = static_cast<const float*>(a.Pinv); g.gamma = a.gamma; g.lambda = a.lambda;
-        g.r_out = a.r_out; g.p_out = a.p_out; g.iters = a.iters; g.max_iter_exit = a.max_iter_exit;
-        g.N = a.N; g.max_iter = a.max_iter; g.exit_tol = a.exit_tol; g.pcols = a.pcols;
+        const auto g = solve_args<PcgArgsG<float>>(h, static_cast<const float*>(a.S), static_cast<const float*>(a.Pinv), a.gamma, a.lambda, a.r_out, a.p_out,
+                                                   a.iters, a.max_iter_exit, (uint32_t)a.max_iter, a.exit_tol, a.pcols);
         const int rc = launch_args(h, p.k, g, batch, st);
         if (rc == MPCG_OK) h->last = p.last;
         return rc;
@@ -951,7 +1001,8 @@ static int launch_pcg(mpcg_handle* h, const PcgArgs& a_in, uint32_t batch, hipSt
         } else if (p.lower) {
             // the symmetry latch (see launch_guarded): no synchronisation, no per-solve D2H
             sym_poll(h, st, true);
-            { const int rc = sym_prepare(h, a.pcols, st); if (rc != MPCG_OK) return rc; }
+            sym_reopen_for_pinv(h, a.pcols);
+            { const int rc = sym_reset_flag(h, st); if (rc != MPCG_OK) return rc; }
             if (h->sym_state == 2) lower_ok = false;
             else if (h->sym_state == 0) {
                 const int rc = launch_guarded(h, a, batch, st, order);
@@ -965,37 +1016,7 @@ static int launch_pcg(mpcg_handle* h, const PcgArgs& a_in, uint32_t batch, hipSt
     return rc;
 }
 
-// The double kernels that read only the left + diagonal block columns use the float path's latch (mpcg.h, BLOCK SYMMETRY): a handle that does not
-// know yet checks THIS call's matrices once, with one blocking 8-byte copy (never during capture: a capturing call on such a handle runs a
-// kernel that reads all three columns).
-static int f64_symmetry_latch(mpcg_handle* h, const PcgArgs64& a, uint32_t batch, hipStream_t st) {
-    sym_poll(h, st, true);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-    if (h->sym_state == 1 && a.pcols == 3 && !h->sym_pinv_ok) {
-        // latched on block-Jacobi calls: this call's Pinv has never been looked at.  (A capturing call cannot check: it runs a three-column kernel.)
-        h->sym_state = 0;
-    }
-    if (h->sym_state != 0 || h->sym_pending) return MPCG_OK;
-    if (capturing) return MPCG_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    { const int rc = sym_prepare(h, a.pcols, st); if (rc != MPCG_OK) return rc; }
-    unsigned long long* flag = fixup_counter(h) + 9;
-    const long items = (long)batch * ((long)h->N - 1);
-    const unsigned blocks = (unsigned)((items + 3) / 4);
-    for (const double* m : {a.S, a.pcols == 3 ? a.Pinv : (const double*)nullptr})
-        if (m) hipLaunchKernelGGL(bd_symmetry_check_kernel<double>, dim3(blocks), dim3(256), 0, st, m, (int)h->N, (int)batch, (float)kSymRelTol64, (unsigned long long*)nullptr, flag);
-    HIP_TRY(h, hipGetLastError());
-    unsigned long long v = 0;
-    HIP_TRY(h, hipMemcpyAsync(&v, flag, sizeof v, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    h->sym_state = v ? 2 : 1;
-    h->sym_pinv_ok = !v && a.pcols == 3;
-    if (v) h->err = "warning: S / Pinv of a solve on this handle were not block-symmetric (block (k, right) != block (k+1, left)^T): the handle now "
-                    "runs kernels that read all three block columns (include/mpcg.h, BLOCK SYMMETRY)";
-    return MPCG_OK;
-}
-
+// One double solve.
 static int launch_f64(mpcg_handle* h, PcgArgs64 a, uint32_t batch, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1054,7 +1075,7 @@ int mpcg_check_pcg_occupancy(mpcg_handle* h, uint32_t* resident_trajectories) {
         return MPCG_OK;
     }
     if (p.k.rc != MPCG_OK) return fail(h, p.k.rc, p.k.err);
-    if (p.k.lds > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(p.k.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.k.lds));
+    { const int rc = raise_lds(h, p.k); if (rc != MPCG_OK) return rc; }
     int per_cu = 0;
     HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p.k.kern, (int)p.k.block, p.k.lds));
     if (per_cu < 1) return fail(h, MPCG_ERR_UNSUPPORTED, "PCG workgroup does not fit on a CU");
@@ -1065,27 +1086,15 @@ int mpcg_check_pcg_occupancy(mpcg_handle* h, uint32_t* resident_trajectories) {
 int mpcg_pcg_solve(mpcg_handle* h, const float* d_S, const float* d_Pinv, const float* d_gamma, float* d_lambda,
                    uint32_t batch, uint32_t max_iter, float exit_tol, mpcg_precond precond,
                    uint32_t* d_iters, uint8_t* d_max_iter_exit, void* stream) {
-    if (!h) return MPCG_ERR_INVALID;
-    if (!d_S || !d_Pinv || !d_gamma || !d_lambda || !d_iters || !d_max_iter_exit)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve: null device pointer");
-    if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve: batch exceeds max_batch");
-    if (precond != MPCG_PRECOND_JACOBI && precond != MPCG_PRECOND_SS)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve: bad preconditioner");
-    if (max_iter > 0x7fffffffu) return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve: max_iter too large");
-    if ((reinterpret_cast<uintptr_t>(d_S) | reinterpret_cast<uintptr_t>(d_Pinv)) & 15u)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve: d_S / d_Pinv must be 16-byte aligned");
-    PcgArgs a;
-    a.S = d_S; a.Pinv = d_Pinv; a.gamma = d_gamma; a.lambda = d_lambda;
-    a.r_out = nullptr; a.p_out = nullptr;
-    a.iters = d_iters; a.max_iter_exit = d_max_iter_exit;
-    a.N = (int)h->N; a.max_iter = (int)max_iter; a.exit_tol = exit_tol; a.pcols = (int)precond; a.lds_rows = 0;
+    int rc;
+    if (solve_ends(h, "mpcg_pcg_solve", false, d_S, d_Pinv, d_gamma, d_lambda, d_iters, d_max_iter_exit, batch, precond, max_iter, &rc)) return rc;
+    PcgArgs a = solve_args<PcgArgs>(h, d_S, d_Pinv, d_gamma, d_lambda, (float*)nullptr, (float*)nullptr, d_iters, d_max_iter_exit, max_iter, exit_tol, (int)precond);
     // Calls with more trajectories than CUs: dispatch longest-expected first, the expectation being the previous call's iteration
     // counts for the same batch (pcg_kernels.hip.h: sched_order_kernel).  A scheduling hint only: no result depends on it.
     const bool hinted = h->sched_hint && !h->generic && batch > (uint32_t)h->num_cus;
     if (hinted) { a.order = h->sched_order; a.order_tag = batch; }       // (used only if the stored permutation was made for this batch: sched_pick)
     bool order = false;
-    const int rc = launch_pcg(h, a, batch, static_cast<hipStream_t>(stream), 4, &order);
+    rc = launch_pcg(h, a, batch, static_cast<hipStream_t>(stream), 4, &order);
     if (rc == MPCG_OK && hinted && order) {
         hipLaunchKernelGGL(sched_order_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), d_iters, (int)batch, h->sched_order);
         HIP_TRY(h, hipGetLastError());
@@ -1094,23 +1103,14 @@ int mpcg_pcg_solve(mpcg_handle* h, const float* d_S, const float* d_Pinv, const 
 }
 
 int mpcg_pcg_solve_ref(mpcg_handle* h, float* d_S, float* d_Pinv, float* d_gamma, float* d_lambda,
-                       float* d_r, float* d_p, float* d_v_temp, float* d_eta_new_temp,
+                       float* d_r, float* d_p, float* /*d_v_temp*/, float* /*d_eta_new_temp*/,      // (the reference's per-block partial-sum scratch: not needed)
                        uint32_t* d_pcg_iters, uint8_t* d_pcg_exit,
                        uint32_t pcg_max_iter, float pcg_exit_tol, void* stream) {
-    (void)d_v_temp; (void)d_eta_new_temp;   // reference's per-block partial-sum scratch: not needed
-    if (!h) return MPCG_ERR_INVALID;
-    if (!d_S || !d_Pinv || !d_gamma || !d_lambda || !d_pcg_iters || !d_pcg_exit)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_ref: null device pointer");
-    if ((reinterpret_cast<uintptr_t>(d_S) | reinterpret_cast<uintptr_t>(d_Pinv)) & 15u)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_ref: d_S / d_Pinv must be 16-byte aligned");
-    if (pcg_max_iter > 0x7fffffffu) return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_ref: max_iter too large");
-    PcgArgs a;
-    a.S = d_S; a.Pinv = d_Pinv; a.gamma = d_gamma; a.lambda = d_lambda;
-    a.r_out = d_r; a.p_out = d_p;
-    a.iters = d_pcg_iters; a.max_iter_exit = d_pcg_exit;
-    a.N = (int)h->N; a.max_iter = (int)pcg_max_iter; a.exit_tol = pcg_exit_tol; a.pcols = 3; a.lds_rows = 0;
-    bool order;
-    return launch_pcg(h, a, 1, static_cast<hipStream_t>(stream), 4, &order);
+    int rc;
+    if (solve_ends(h, "mpcg_pcg_solve_ref", true, d_S, d_Pinv, d_gamma, d_lambda, d_pcg_iters, d_pcg_exit, 1, MPCG_PRECOND_SS, pcg_max_iter, &rc)) return rc;
+    bool order = false;
+    return launch_pcg(h, solve_args<PcgArgs>(h, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, d_pcg_iters, d_pcg_exit, pcg_max_iter, pcg_exit_tol, 3), 1,
+                      static_cast<hipStream_t>(stream), 4, &order);
 }
 
 int mpcg_bt_spmv(mpcg_handle* h, const float* d_M, const float* d_x, float* d_y, uint32_t batch, int cols, void* stream) {
@@ -1168,61 +1168,31 @@ int mpcg_convert_f32_to_f16(mpcg_handle* h, const float* d_src, uint16_t* d_dst,
 int mpcg_pcg_solve_f16(mpcg_handle* h, const uint16_t* d_S16, const uint16_t* d_Pinv16, const float* d_gamma,
                        float* d_lambda, uint32_t batch, uint32_t max_iter, float exit_tol, mpcg_precond precond,
                        uint32_t* d_iters, uint8_t* d_max_iter_exit, void* stream) {
-    if (!h) return MPCG_ERR_INVALID;
-    if (h->generic) return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_pcg_solve_f16: state_size = 14 only (other state sizes: PCG entry points through the generic kernel)");
-    if (!d_S16 || !d_Pinv16 || !d_gamma || !d_lambda || !d_iters || !d_max_iter_exit)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_f16: null device pointer");
-    if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_f16: batch exceeds max_batch");
-    if (precond != MPCG_PRECOND_JACOBI && precond != MPCG_PRECOND_SS)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_f16: bad preconditioner");
-    if (max_iter > 0x7fffffffu) return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_f16: max_iter too large");
-    if ((reinterpret_cast<uintptr_t>(d_S16) | reinterpret_cast<uintptr_t>(d_Pinv16)) & 3u)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_f16: d_S16 / d_Pinv16 must be 4-byte aligned");
-    PcgArgs a;
-    a.S = d_S16; a.Pinv = d_Pinv16; a.gamma = d_gamma; a.lambda = d_lambda;
-    a.r_out = nullptr; a.p_out = nullptr;
-    a.iters = d_iters; a.max_iter_exit = d_max_iter_exit;
-    a.N = (int)h->N; a.max_iter = (int)max_iter; a.exit_tol = exit_tol; a.pcols = (int)precond; a.lds_rows = 0;
-    bool order;
-    return launch_pcg(h, a, batch, static_cast<hipStream_t>(stream), 2, &order);
+    if (h && h->generic)      // (before any argument is looked at)
+        return fail(h, MPCG_ERR_UNSUPPORTED, "mpcg_pcg_solve_f16: state_size = 14 only (other state sizes: PCG entry points through the generic kernel)");
+    int rc;
+    if (solve_ends(h, "mpcg_pcg_solve_f16", false, d_S16, d_Pinv16, d_gamma, d_lambda, d_iters, d_max_iter_exit, batch, precond, max_iter, &rc)) return rc;
+    bool order = false;
+    return launch_pcg(h, solve_args<PcgArgs>(h, d_S16, d_Pinv16, d_gamma, d_lambda, (float*)nullptr, (float*)nullptr, d_iters, d_max_iter_exit, max_iter, exit_tol, (int)precond),
+                      batch, static_cast<hipStream_t>(stream), 2, &order);
 }
 
 int mpcg_pcg_solve_f64(mpcg_handle* h, const double* d_S, const double* d_Pinv, const double* d_gamma, double* d_lambda,
                        uint32_t batch, uint32_t max_iter, double exit_tol, mpcg_precond precond,
                        uint32_t* d_iters, uint8_t* d_max_iter_exit, void* stream) {
-    if (!h) return MPCG_ERR_INVALID;
-    if (!d_S || !d_Pinv || !d_gamma || !d_lambda || !d_iters || !d_max_iter_exit)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_f64: null device pointer");
-    if (batch == 0) return MPCG_OK;
-    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_f64: batch exceeds max_batch");
-    if (precond != MPCG_PRECOND_JACOBI && precond != MPCG_PRECOND_SS)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_f64: bad preconditioner");
-    if (max_iter > 0x7fffffffu) return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_f64: max_iter too large");
-    PcgArgs64 a;
-    a.S = d_S; a.Pinv = d_Pinv; a.gamma = d_gamma; a.lambda = d_lambda; a.r_out = nullptr; a.p_out = nullptr;
-    a.iters = d_iters; a.max_iter_exit = d_max_iter_exit; a.N = (int)h->N; a.max_iter = (int)max_iter;
-    a.exit_tol = exit_tol; a.pcols = precond == MPCG_PRECOND_SS ? 3 : 1;
-    return launch_f64(h, a, batch, stream);
+    int rc;
+    if (solve_ends(h, "mpcg_pcg_solve_f64", false, d_S, d_Pinv, d_gamma, d_lambda, d_iters, d_max_iter_exit, batch, precond, max_iter, &rc)) return rc;
+    return launch_f64(h, solve_args<PcgArgs64>(h, d_S, d_Pinv, d_gamma, d_lambda, (double*)nullptr, (double*)nullptr, d_iters, d_max_iter_exit, max_iter, exit_tol, (int)precond),
+                      batch, stream);
 }
 
 int mpcg_pcg_solve_ref_f64(mpcg_handle* h, double* d_S, double* d_Pinv, double* d_gamma, double* d_lambda,
                            double* d_r, double* d_p, double* /*d_v_temp*/, double* /*d_eta_new_temp*/,
                            uint32_t* d_pcg_iters, uint8_t* d_pcg_exit, uint32_t pcg_max_iter, double pcg_exit_tol, void* stream) {
-    if (!h) return MPCG_ERR_INVALID;
-    if (!d_S || !d_Pinv || !d_gamma || !d_lambda || !d_pcg_iters || !d_pcg_exit)
-        return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_ref_f64: null device pointer");
-    if (pcg_max_iter > 0x7fffffffu) return fail(h, MPCG_ERR_INVALID, "mpcg_pcg_solve_ref_f64: max_iter too large");
-    PcgArgs64 a;
-    a.S = d_S; a.Pinv = d_Pinv; a.gamma = d_gamma; a.lambda = d_lambda; a.r_out = d_r; a.p_out = d_p;
-    a.iters = d_pcg_iters; a.max_iter_exit = d_pcg_exit; a.N = (int)h->N; a.max_iter = (int)pcg_max_iter;
-    a.exit_tol = pcg_exit_tol; a.pcols = 3;
-    return launch_f64(h, a, 1, stream);
+    int rc;
+    if (solve_ends(h, "mpcg_pcg_solve_ref_f64", true, d_S, d_Pinv, d_gamma, d_lambda, d_pcg_iters, d_pcg_exit, 1, MPCG_PRECOND_SS, pcg_max_iter, &rc)) return rc;
+    return launch_f64(h, solve_args<PcgArgs64>(h, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, d_pcg_iters, d_pcg_exit, pcg_max_iter, pcg_exit_tol, 3), 1, stream);
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int mpcg_debug_read_cluster_scratch(mpcg_handle* h, unsigned long long* out, int count) {
     if (!h || !out || count < 0 || (size_t)count > cluster_alloc_words(h)) return MPCG_ERR_INVALID;

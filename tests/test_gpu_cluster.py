@@ -325,3 +325,113 @@ def test_without_a_fixup_launch_an_abandoned_trajectory_is_always_reported(preci
     it2, _ = solve(dS, dP, dg, lam2, cfg)
     torch.cuda.synchronize()
     assert (it2.cpu().numpy() == K).all() and torch.equal(lam2, lam_ok)
+
+
+# ---- the handle's copy of lambda (mpcg_handle::lam_backup): sized by mpcg_create, at the first launch that needs it, or by "reserve_f64" ----
+LAMCOPY_N, LAMCOPY_B, LAMCOPY_K = 64, 2, 6
+LAMCOPY_MAX_BATCH = 1200        # 1200 x 64 x 14 doubles > 8 MB: mpcg_create sizes no copy for this handle (64 knots: no automatic cluster either)
+_lamcopy = {}
+
+
+def lamcopy_system(orc):
+    """The float and double systems of these tests, a warm start and the oracle's lambda after LAMCOPY_K iterations: computed once, never changed."""
+    if not _lamcopy:
+        N, B, K = LAMCOPY_N, LAMCOPY_B, LAMCOPY_K
+        k = synth.make_kkt(N, B, 8640)
+        lam0 = np.random.default_rng(64).normal(0, 0.3, (B, n * N))
+        for dt in (np.float32, np.float64):
+            S, P, g = synth.form_schur(k, dtype=dt)
+            l0 = lam0.astype(dt)
+            ref = [orc.pcg(S[b].astype(np.float64), P[b].astype(np.float64), g[b].astype(np.float64), l0[b].astype(np.float64), N, K, 0.0, "ss")["lam"]
+                   for b in range(B)]
+            tol = [1e-9 if dt is np.float64 else max(2e-5, 4 * fp32_band(orc, S[b], P[b], g[b], l0[b], N, K, "ss", ref[b], trials=2)) for b in range(B)]
+            _lamcopy[dt] = (S, P, g, l0, ref, tol)
+    return _lamcopy
+
+
+def lamcopy_solve(sol, sysd, dbl, family):
+    """One warm-started solve of the shared system on `sol`; asserts the family, the counts and the answer.  Returns lambda."""
+    from mpcgpu_amd import pcg_config
+    S, P, g, l0, ref, tol = sysd[np.float64 if dbl else np.float32]
+    lam = dev(l0.copy())
+    it, ex = (sol.solve_f64 if dbl else sol.solve)(dev(S), dev(P), dev(g), lam, pcg_config(pcg_exit_tol=0.0, pcg_max_iter=LAMCOPY_K), "ss")
+    torch.cuda.synchronize()
+    assert sol.get_option("last_kernel_family") == family and sol.get_option("last_kernel_cluster") == 2
+    assert (it.cpu().numpy() == LAMCOPY_K).all() and (ex.cpu().numpy() == 1).all()
+    for b in range(LAMCOPY_B):
+        assert relinf(lam[b].cpu().numpy(), ref[b]) <= tol[b], (b, relinf(lam[b].cpu().numpy(), ref[b]), tol[b])
+    return lam
+
+
+def test_a_forced_cluster_sizes_its_copy_of_lambda_at_the_first_launch_and_grows_it_for_double(orc):
+    """A forced "cluster" = 2 on a horizon for which mpcg_create sized no copy of lambda: the first launch allocates it (float-sized, for the
+    call's batch) and solves correctly; the fix-up launch of a later call really starts from that copy ("cluster_test_fail"); the first double
+    cluster solve on the same handle replaces it with the double-sized one (an allocation behind work that may still read the old copy), and
+    float solves after that still give their earlier bits."""
+    from mpcgpu_amd import PcgSolver
+    sysd = lamcopy_system(orc)
+    sol = PcgSolver(LAMCOPY_N, max_batch=LAMCOPY_MAX_BATCH)
+    sol.set_option("cluster", 2)
+    first = lamcopy_solve(sol, sysd, False, 7)              # guarded (fresh latch): allocates inside the cluster launch
+    assert sol.get_option("symmetry_state") == 1 and sol.get_option("cluster_fixups") == 0
+    sol.set_option("cluster_test_fail", 1)
+    lamcopy_solve(sol, sysd, False, 7)                      # trajectory 0 re-solved by the fix-up launch, from the copy of the warm start
+    assert 1 <= sol.get_option("cluster_fixups") <= 2
+    sol.set_option("cluster_test_fail", 0)
+    fixed = sol.get_option("cluster_fixups")
+    lamcopy_solve(sol, sysd, True, 10)                      # the double clusters' buffers and the double-sized copy: made here
+    sol.set_option("cluster_test_fail", 1)
+    lamcopy_solve(sol, sysd, True, 10)
+    assert fixed + 1 <= sol.get_option("cluster_fixups") <= fixed + 2
+    sol.set_option("cluster_test_fail", 0)
+    assert torch.equal(lamcopy_solve(sol, sysd, False, 7), first)
+
+
+def test_a_forced_clusters_first_launch_is_refused_inside_a_capture_and_leaves_it_intact(orc):
+    """The same first launch while its stream is being captured: MPCG_ERR_INVALID with the message of include/mpcg.h (GRAPH CAPTURE), the capture
+    stays usable — a solve of another handle captured behind the refused call replays its eager answer — and the handle solves eagerly afterwards."""
+    from mpcgpu_amd import PcgSolver, pcg_config
+    from mpcgpu_amd._lib import MpcgError, MPCG_ERR_INVALID
+    sysd = lamcopy_system(orc)
+    S, P, g, l0, _, _ = sysd[np.float32]
+    dS, dP, dg = dev(S), dev(P), dev(g)
+    cfg = pcg_config(pcg_exit_tol=0.0, pcg_max_iter=LAMCOPY_K)
+    other = PcgSolver(LAMCOPY_N, max_batch=LAMCOPY_B)
+    want = dev(l0.copy())
+    for _ in range(2):                                      # (the second call: latched, plain launches — what the capture below records)
+        want.copy_(dev(l0))
+        other.solve(dS, dP, dg, want, cfg, "ss")
+        torch.cuda.synchronize()
+    assert other.get_option("symmetry_state") == 1
+    sol = PcgSolver(LAMCOPY_N, max_batch=LAMCOPY_MAX_BATCH)
+    sol.set_option("cluster", 2)
+    lam, lam2, start = dev(l0.copy()), dev(l0.copy()), dev(l0.copy())
+    it = torch.zeros(LAMCOPY_B, dtype=torch.int32, device="cuda"); ex = torch.zeros(LAMCOPY_B, dtype=torch.uint8, device="cuda")
+    graph = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    with torch.cuda.graph(graph):
+        with pytest.raises(MpcgError, match="a cluster launch whose copy of lambda mpcg_create did not size") as e:
+            sol.solve(dS, dP, dg, lam, cfg, "ss", iters=it, exits=ex)
+        assert e.value.code == MPCG_ERR_INVALID and "outside the stream capture" in str(e.value)
+        lam2.copy_(start)
+        other.solve(dS, dP, dg, lam2, cfg, "ss", iters=it, exits=ex)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(lam2, want) and (it.cpu().numpy() == LAMCOPY_K).all()
+    lamcopy_solve(sol, sysd, False, 7)
+
+
+def test_reserve_f64_sizes_the_copy_of_lambda_for_float_and_double_clusters(orc):
+    """"reserve_f64" = 1 on such a handle: the double-sized copy is made ahead of any solve; a float cluster solve and then a double one use it,
+    both correct, fix-up launches included."""
+    from mpcgpu_amd import PcgSolver
+    sysd = lamcopy_system(orc)
+    sol = PcgSolver(LAMCOPY_N, max_batch=LAMCOPY_MAX_BATCH)
+    sol.set_option("cluster", 2)
+    sol.set_option("reserve_f64", 1)
+    lamcopy_solve(sol, sysd, False, 7)
+    lamcopy_solve(sol, sysd, True, 10)
+    sol.set_option("cluster_test_fail", 1)
+    lamcopy_solve(sol, sysd, False, 7)
+    lamcopy_solve(sol, sysd, True, 10)
+    assert 2 <= sol.get_option("cluster_fixups") <= 4

@@ -340,6 +340,82 @@ def test_hbm_read_probe_contract():
         sol.probe_hbm_read(src[1:], sink)                   # 4-byte aligned only
 
 
+_NULL_MSG = "{e}: null device pointer"
+_BATCH_MSG = "{e}: batch exceeds max_batch"
+_PRECOND_MSG = "{e}: bad preconditioner"
+_ITER_MSG = "{e}: max_iter too large"
+_ALIGN_MSG = {"mpcg_pcg_solve": "{e}: d_S / d_Pinv must be 16-byte aligned", "mpcg_pcg_solve_ref": "{e}: d_S / d_Pinv must be 16-byte aligned",
+              "mpcg_pcg_solve_f16": "{e}: d_S16 / d_Pinv16 must be 4-byte aligned"}
+_F16_GENERIC_MSG = "mpcg_pcg_solve_f16: state_size = 14 only (other state sizes: PCG entry points through the generic kernel)"
+
+
+@pytest.mark.parametrize("entry", ["mpcg_pcg_solve", "mpcg_pcg_solve_ref", "mpcg_pcg_solve_f16", "mpcg_pcg_solve_f64", "mpcg_pcg_solve_ref_f64"])
+def test_argument_errors(entry):
+    """Every refusal of the five PCG solve entries, one fault at a time, and which message wins when two faults come together (the order of the
+    entry's checks is part of the contract: `_f16` refuses a generic handle before anything else, the float `_ref` entry looks at the alignment
+    before max_iter, every other entry at max_iter first; the `_ref` entries take no batch and no preconditioner, the double entries ask for no
+    alignment).  Return codes and texts are literals.  No call here launches anything: each is refused, or has batch 0."""
+    import ctypes as C
+    from mpcgpu_amd import PcgSolver, _lib
+    N, B = 8, 2
+    sol = PcgSolver(N, max_batch=B)
+    lib, h = sol.lib, sol._h
+    fn = getattr(lib, entry)
+    ref, f16, f64 = "_ref" in entry, entry.endswith("_f16"), entry.endswith("_f64")
+    buf = torch.zeros(1 << 18, dtype=torch.float64, device="cuda")        # room for any array of a batch-2 call, 256-byte aligned
+    p = buf.data_ptr()
+    INV, UNS = _lib.MPCG_ERR_INVALID, _lib.MPCG_ERR_UNSUPPORTED
+    off = 2 if f16 else 4                                                  # d_S short of the entry's alignment (double: none asked for)
+    BIG = 1 << 31
+
+    def call(handle=h, null=None, batch=B, precond=3, max_iter=5, s_off=0):
+        """One call with every argument valid except the named ones.  `null`: index of the pointer argument passed as NULL."""
+        ptrs = [C.c_void_p(p + s_off)] + [C.c_void_p(p)] * 5             # S, Pinv, gamma, lambda, iters, exits
+        if null is not None:
+            ptrs[null] = None
+        S, P, g, lam, it, ex = ptrs
+        if ref:
+            return fn(handle, S, P, g, lam, C.c_void_p(p), C.c_void_p(p), None, None, it, ex, max_iter, 0.0, None)
+        return fn(handle, S, P, g, lam, batch, max_iter, 0.0, precond, it, ex, None)
+
+    def refused(rc, code, msg):
+        assert rc == code and lib.mpcg_last_error(h).decode() == msg.format(e=entry), (rc, lib.mpcg_last_error(h))
+
+    assert call(handle=None) == INV
+    for i in range(6):
+        refused(call(null=i), INV, _NULL_MSG)
+    refused(call(max_iter=BIG), INV, _ITER_MSG)
+    if not ref:
+        assert call(batch=0) == _lib.MPCG_OK
+        refused(call(batch=B + 1), INV, _BATCH_MSG)
+        for bad in (0, 2, 4):
+            refused(call(precond=bad), INV, _PRECOND_MSG)
+        # null and over-batch: the null pointer is reported; over-batch and bad preconditioner: the batch
+        refused(call(null=0, batch=B + 1), INV, _NULL_MSG)
+        refused(call(null=5, batch=B + 1), INV, _NULL_MSG)
+        refused(call(batch=B + 1, precond=2), INV, _BATCH_MSG)
+        refused(call(batch=B + 1, precond=2, max_iter=BIG, s_off=off), INV, _BATCH_MSG)
+        refused(call(precond=2, max_iter=BIG), INV, _PRECOND_MSG)
+    if not f64:
+        refused(call(s_off=off), INV, _ALIGN_MSG[entry])
+        if not f16:
+            refused(call(s_off=8), INV, _ALIGN_MSG[entry])
+    # max_iter and misalignment: the float `_ref` entry reports the alignment, every other entry max_iter (the double entries have no alignment rule)
+    refused(call(max_iter=BIG, s_off=off), INV, _ALIGN_MSG[entry] if entry == "mpcg_pcg_solve_ref" else _ITER_MSG)
+    refused(call(null=2, max_iter=BIG, s_off=off), INV, _NULL_MSG)
+    # a state_size 6 handle: `_f16` refuses it before it looks at any argument; the other entries check their arguments as above
+    gen = PcgSolver(N, max_batch=B, state_size=6)
+    h = gen._h
+    if f16:
+        for kw in ({}, {"null": 0}, {"batch": B + 1}, {"batch": 0}, {"precond": 2}, {"max_iter": BIG}, {"s_off": off}):
+            refused(call(handle=h, **kw), UNS, _F16_GENERIC_MSG)
+    else:
+        refused(call(handle=h, null=1), INV, _NULL_MSG)
+        refused(call(handle=h, max_iter=BIG), INV, _ITER_MSG)
+    torch.cuda.synchronize()
+    assert float(buf.abs().max()) == 0.0                                    # nothing ran
+
+
 @pytest.mark.parametrize("precision", ["float", "double"])
 def test_a_latch_that_resolved_on_block_jacobi_calls_reopens_at_the_first_ss_call(orc, precision):
     """block-Jacobi calls never show the handle a Pinv with off-diagonal blocks.  A handle whose latch resolved to "symmetric" on such
@@ -407,3 +483,68 @@ def test_double_symmetry_check_uses_a_double_tolerance(orc):
     for b in range(B):
         ref = orc.pcg(S[b], Pa[b], g[b], np.zeros(n * N), N, K, 0.0, "ss")["lam"]
         assert relinf(lam[b].cpu().numpy(), ref) <= 1e-9
+
+
+# (precision, preconditioner, matrices) of each call, then the expected ("symmetry_state", "last_kernel_family") after it has finished.
+# Matrices: "sym" the reference's own, "asymP" Pinv block (0, right) scaled by 1.5, "asymS" the same done to S.  "forget": "assume_symmetric" = 0.
+# 40 knots: float calls plan the lane-quad kernel (11; three columns: the row-per-lane kernel, 5), double calls the lane-quad kernel of one CU
+# (9; three columns: the clustered row-per-lane kernel, 8).
+LATCH_SEQUENCES = {
+    # the double latch resolves on a block-Jacobi call (S only): the first SS call re-opens it, finds the Pinv and goes to three columns for good
+    "double_jacobi_then_double_ss_asym": [(("f64", "jacobi", "sym"), (1, 9)), (("f64", "ss", "asymP"), (2, 8)), (("f64", "ss", "sym"), (2, 8))],
+    # the float latch the same: the SS call is guarded again (the lower-triangle family is launched, gated), its symmetric Pinv latches for SS too —
+    # after which a caller-made Pinv is no longer looked at (the documented limit of a per-handle latch)
+    "float_jacobi_then_float_ss_sym": [(("f32", "jacobi", "sym"), (1, 11)), (("f32", "ss", "sym"), (1, 11)), (("f32", "ss", "asymP"), (1, 11))],
+    "float_jacobi_then_float_ss_asym": [(("f32", "jacobi", "sym"), (1, 11)), (("f32", "ss", "asymP"), (2, 11)), (("f32", "ss", "asymP"), (2, 5))],
+    # a float latch serves the double calls: no second check of S (an asymmetric S goes unseen) — but what it never saw, a Pinv, is checked
+    "float_jacobi_then_double": [(("f32", "jacobi", "sym"), (1, 11)), (("f64", "jacobi", "asymS"), (1, 9)), (("f64", "ss", "asymP"), (2, 8)),
+                                 (("f32", "ss", "sym"), (2, 5))],
+    "float_ss_then_double_ss": [(("f32", "ss", "sym"), (1, 11)), (("f64", "ss", "asymP"), (1, 9))],
+    # a violation, forgotten: the sticky device flag is cleared by the next solve — here a double one — and the handle latches symmetric again
+    "violation_forgotten": [(("f32", "ss", "asymP"), (2, 11)), (("f32", "ss", "sym"), (2, 5)), ("forget", (0, 5)), (("f64", "ss", "sym"), (1, 9)),
+                            (("f32", "ss", "sym"), (1, 11))],
+    "double_violation_forgotten": [(("f64", "ss", "asymP"), (2, 8)), ("forget", (0, 8)), (("f32", "ss", "sym"), (1, 11)), (("f64", "ss", "sym"), (1, 9))],
+}
+_latch_inputs = {}
+
+
+def latch_inputs():
+    if not _latch_inputs:
+        N, B = 40, 2
+        k = synth.make_kkt(N, B, 4040)
+        for prec, dt in (("f32", np.float32), ("f64", np.float64)):
+            S, Pinv, g = synth.form_schur(k, precond="ss", dtype=dt)
+
+            def scaled(M):
+                A = np.array(M, dt).reshape(B, N, 3, 196).copy()
+                A[:, 0, 2] *= 1.5
+                return A.reshape(B, -1)
+            _latch_inputs[prec] = {"sym": (dev(S), dev(Pinv)), "asymP": (dev(S), dev(scaled(Pinv))), "asymS": (dev(scaled(S)), dev(Pinv)), "g": dev(g)}
+    return _latch_inputs
+
+
+@pytest.mark.parametrize("name", list(LATCH_SEQUENCES))
+def test_latch_sequences_across_precisions(name):
+    """The symmetry latch is one per handle, shared by the float and the double entries (include/mpcg.h, BLOCK SYMMETRY): sequences of calls that
+    cross preconditioners and precisions on one 40-knot handle, "symmetry_state" and "last_kernel_family" after every call."""
+    from mpcgpu_amd import PcgSolver, pcg_config
+    N, B = 40, 2
+    inp = latch_inputs()
+    sol = PcgSolver(N, max_batch=B)
+    cfg = pcg_config(pcg_exit_tol=0.0, pcg_max_iter=3)
+    got = []
+    for step, _ in LATCH_SEQUENCES[name]:
+        if step == "forget":
+            sol.set_option("assume_symmetric", 0)
+        else:
+            prec, pc, mats = step
+            S, P = inp[prec][mats]
+            lam = torch.zeros(B, n * N, dtype=torch.float64 if prec == "f64" else torch.float32, device="cuda")
+            it, _ = (sol.solve_f64 if prec == "f64" else sol.solve)(S, P, inp[prec]["g"], lam, cfg, pc)
+            torch.cuda.synchronize()
+            assert (it.cpu().numpy() == 3).all() and torch.isfinite(lam).all()
+        got.append((sol.get_option("symmetry_state"), sol.get_option("last_kernel_family")))
+    print(name, got)
+    assert got == [want for _, want in LATCH_SEQUENCES[name]]
+    if got[-1][0] == 2:
+        assert "block-symmetric" in sol.last_error()
