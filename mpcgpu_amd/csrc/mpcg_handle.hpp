@@ -38,6 +38,22 @@ struct PcgKnobs {
 enum { FAM_NONE = -1, FAM_TRAJ = 0, /* 1, 2, 4: kernels retired in round 4 (HISTORY.md) */ FAM_GENERIC = 3, FAM_RPL = 5, FAM_LPK = 6, FAM_LPKC = 7, FAM_RPLC64 = 8, FAM_LQK64 = 9, FAM_LQKC64 = 10, FAM_LQB = 11 };
 struct LastKernel { int family = FAM_NONE, waves = 0, reg_rows = 0, lds_rows = 0, stream_bufs = 0, cluster = 0, lds_bytes = 0, lds_extra = 0; };
 
+// The handle's device buffers: what mpcg_destroy walks and buf_reserve fills.  Who sizes which, when and to what: DESIGN.md, "Handle work buffers".
+struct DevBuf { void* p = nullptr; size_t bytes = 0; };
+enum BufId {
+    BUF_CLUSTER,        // the clustered float kernels' queue | flags | cells and the handle's counter line (mpcg_pcg.hip: cluster_alloc_words); mpcg_create
+    BUF_CLUSTER64,      // the same for the clustered kernels in double: queue | flags | cells (reserve_f64)
+    BUF_SCHED_ORDER,    // uint32 [1 + max_batch] {batch it was made for, dispatch order}: written after every hinted solve, checked on the device; mpcg_create
+    BUF_LAM_BACKUP,     // the handle's copy of the caller's lambda ([batch][N][n]) made in front of every cluster launch: what the fix-up launch warm-starts from
+    BUF_SEAM,           // schur_walk: one Q^-1 per chunk seam (float or double; ensure_seam_buffer)
+    BUF_STAGING,        // staging for the in-place G <- G^-1 of mpcg_form_schur: max_batch x ((n^2 + m^2) N - m^2) floats, m the largest control_size seen
+    BUF_STAGING64,      // the same for mpcg_form_schur_f64, in doubles
+    BUF_BLOCK,          // W_k, z_k of mpcg_block_solve: max_batch x N x (n^2 + n) floats (first call)
+    BUF_BLOCK64,        // the same for the sweeps in double, mpcg_block_solve_f64 and "block_solve_f64" = 1 (their first call): neither buffer is shared
+    BUF_MERIT,          // point merits of mpcg_compute_merit: max_batch x 16 x N doubles (first call of any of the four entries)
+    BUF_COUNT
+};
+
 struct mpcg_handle {
     int device = 0;
     uint32_t n = 0, N = 0, max_batch = 0;
@@ -53,7 +69,6 @@ struct mpcg_handle {
     int block_solve_f64 = 0;  // mpcg_block_solve: 1 = float S / gamma widened on load, the sweep in double (block_solve.hip.h), lambda rounded once on store; 0 = the float sweep
     int schur_dpp = 1;        // 1: register-resident Schur formation (schur_walk.hip.h: the chunk-walking kernel + its seam kernel), 0: the LDS kernels (schur_generic.hip.h)
     int sched_hint = 1;       // dispatch the trajectories of a large call longest-expected-first, predicted by the previous call's iteration counts (sched_order_kernel)
-    uint32_t* sched_order = nullptr;   // [1 + max_batch] {batch it was made for, dispatch order}: written after every hinted solve, checked on the device
     int schur_chunk = 0;      //   block rows per chunk of the walking kernel: 0 auto (by call size), 1..2048 forced
     int kkt_analytic = 1;     // mpcg_generate_kkt: 1 = analytic gradient recursion of the inverse dynamics (as the reference's GRiD code), 0 = one-sided float64 differences (the checker)
     int kkt_f32 = 0;          // mpcg_generate_kkt: 1 = the analytic kernel in float arithmetic (linsys_t's own, as the reference's GRiD<float>), two knots per lane in packed float;
@@ -65,8 +80,6 @@ struct mpcg_handle {
     int last_schur_chunk = 0; //   what the last mpcg_form_schur used (0: the LDS kernels)
     int last_dz_route = 0;    //   what the last mpcg_compute_dz(_f64) ran: 1 = four knots per wavefront (schur_walk.hip.h), 0 = the LDS kernel
     int producers_generic = 0; // 1: form_schur(_f64), compute_dz(_f64) and block_solve of a (14, 7) call run the run-time-dimension kernels (schur_generic.hip.h) every other shape gets (formation and dz: what "schur_dpp" / "dz_dpp" = 0 run too)
-    void* seam_qinv = nullptr;       // schur_walk: one Q^-1 per chunk seam (float or double; ensure_seam_buffer)
-    size_t seam_qinv_bytes = 0;
     int cluster = -1;         // workgroups per trajectory of the clustered lane-pair kernel (pcg_lpk_cluster.hip.h): 0 off, -1 auto (N > 128), G > 0 forced
     int cluster_l2 = 1;       // clustered lane-pair kernel: 1 = L2-resident hand-offs when a cluster's members share an XCD, 0 = always write-through
     int lqb = -1;             // the float lane-quad kernel (pcg_lqb.hip.h) in place of the lane-pair kernel: -1 auto, 0 off, 1 wherever the lane-pair kernel would run
@@ -87,22 +100,12 @@ struct mpcg_handle {
     bool sym_flag_reset = false;   // "assume_symmetric" = 0 after a violation: the sticky device flag is cleared by the next solve, on its stream
     hipEvent_t sym_event = nullptr;
     unsigned long long* sym_host = nullptr;      // pinned
-    unsigned long long* cluster_scratch = nullptr;
-    // the handle's copy of the caller's lambda ([batch][N][n]) made in front of every cluster launch: what the fix-up launch warm-starts from
-    void* lam_backup = nullptr;
-    size_t lam_backup_bytes = 0;
-    unsigned long long* cluster64_scratch = nullptr;   // the clustered row-per-lane kernel in double (pcg_rpl_cluster_f64.hip.h): queue | flags | cells, first use
+    DevBuf buf[BUF_COUNT];
+    template <typename T> T* ptr(BufId id) const { return static_cast<T*>(buf[id].p); }
     bool auto_cfg = true;     // launch knobs still at mpcg_create's choice (any valid pcg_* set_option clears this)
     bool generic = false;     // state_size != 14: PCG through pcg_generic_kernel, producers / dz / block solve / CSR through schur_generic.hip.h
     int spmv_blocks_per_cu = 3;    // (sweep at 4096 trajectories = 1.2 GB of S, a true HBM stream: profiles/r04_spmv.txt; until round 4: 4)
     int spmv_mfma = 0;        // 1 = the MFMA experiment kernel for mpcg_bt_spmv
-    float* block_scratch = nullptr;  // W_k, z_k of mpcg_block_solve: max_batch x N x (n^2 + n) floats (first call)
-    double* block_scratch64 = nullptr;   // the same for the sweeps in double, mpcg_block_solve_f64 and "block_solve_f64" = 1 (their first call): block_solve_impl<CT, ...> picks by CT, neither buffer is shared
-    float* ginv_scratch = nullptr;   // staging for the in-place G <- G^-1 of mpcg_form_schur: max_batch x ((n^2 + m^2) N - m^2), m the largest control_size seen
-    size_t ginv_scratch_floats = 0;
-    double* ginv_scratch_f64 = nullptr;   // the same for mpcg_form_schur_f64
-    size_t ginv_scratch_f64_elems = 0;
-    double* merit_scratch = nullptr;   // point merits of mpcg_compute_merit: max_batch x 16 x N doubles (first call)
     std::string err;
 };
 
@@ -136,4 +139,23 @@ static inline int alloc_allowed(mpcg_handle* h, hipStream_t st, const char* what
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) return MPCG_OK;
     return fail(h, MPCG_ERR_INVALID, std::string(what) + ": the handle allocates a work buffer at the first such call — make one outside the stream capture first");
+}
+
+// THE way a handle buffer comes by its memory: at least `bytes` in buf[id], or why not.  Large enough already: nothing happens.  Otherwise the
+// call blocks (hipMalloc is not stream work), so with a stream to guard (st) it is refused while that stream is capturing, under the caller's
+// text `what`; an old copy goes first, behind whatever may still read it (hipDeviceSynchronize); `zero`: the new memory is cleared.
+// (A graph captured earlier keeps the old copy's address: DESIGN.md, "Handle work buffers", known defects.)
+static inline int buf_reserve(mpcg_handle* h, BufId id, size_t bytes, const hipStream_t* st = nullptr, const char* what = "", bool zero = false) {
+    DevBuf& b = h->buf[id];
+    if (b.bytes >= bytes) return MPCG_OK;
+    if (st) { const int rc = alloc_allowed(h, *st, what); if (rc != MPCG_OK) return rc; }
+    if (b.p) {
+        HIP_TRY(h, hipDeviceSynchronize());
+        HIP_TRY(h, hipFree(b.p));
+        b = DevBuf();
+    }
+    HIP_TRY(h, hipMalloc(&b.p, bytes));
+    if (zero) HIP_TRY(h, hipMemset(b.p, 0, bytes));
+    b.bytes = bytes;
+    return MPCG_OK;
 }

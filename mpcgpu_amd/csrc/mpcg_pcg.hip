@@ -1,6 +1,6 @@
 // mpcg_pcg.hip — C ABI (include/mpcg.h) of the hot path: handle and options, the PCG launch policy (which kernel family serves a call), the
 // PCG / SpMV entry points, over the gfx950 kernels in pcg_*.hip.h.  Host side is plain C++/HIP: no torch types, no CPU fallback.
-// Each thing is written once, in this order: the handle's device buffers (scratch layouts, counter line, grow_lam_backup) and mpcg_create /
+// Each thing is written once, in this order: the handle's device buffers (scratch layouts, counter line, reserve_f64) and mpcg_create /
 // _destroy; the options (kOptions: one row per key, read by mpcg_set_option and mpcg_get_option); the launch plan (plan_f32 / plan_f64) and
 // its launch (launch_plan); the symmetry latch (one check launch, one warning, one re-open rule under the asynchronous float latch and the
 // blocking double one); the solve entries (solve_ends: their argument checks, solve_args: their kernel arguments).
@@ -51,9 +51,9 @@ const char* mpcg_build_info(void) {
 }
 
 // Device scratch of the clustered kernels, one contiguous run per call so that one small fill precedes every launch —
-//   float  (cluster_scratch):   [queue line][flags: one 128-byte line per trajectory of the CALL, up to max_batch][cells: 1 KB per member of the
+//   float  (BUF_CLUSTER):       [queue line][flags: one 128-byte line per trajectory of the CALL, up to max_batch][cells: 1 KB per member of the
 //                               launch, up to two members per CU][the handle's counter line, never re-zeroed by a launch: CounterSlot]
-//   double (cluster64_scratch): [queue line][flags][cells: one member per CU][a spare line]
+//   double (BUF_CLUSTER64):     [queue line][flags][cells: one member per CU][a spare line]
 static size_t cluster_alloc_words(const mpcg_handle* h) {
     return (size_t)2 * h->num_cus * LPKC_WG_WORDS + CL_FLAG_STRIDE + (size_t)h->max_batch * CL_FLAG_STRIDE + 16;
 }
@@ -63,38 +63,22 @@ static size_t cluster64_alloc_words(const mpcg_handle* h) {
 // words of the counter line: trajectories re-solved by fix-up launches ("cluster_fixups"), block pairs that failed the last "check_symmetry" run,
 // the symmetry latch's sticky device flag
 enum CounterSlot { CTR_FIXUPS = 0, CTR_SYM_VIOLATIONS = 8, CTR_SYM_FLAG = 9 };
-static unsigned long long* counter(const mpcg_handle* h, CounterSlot slot) { return h->cluster_scratch + cluster_alloc_words(h) - 16 + slot; }
+static unsigned long long* counter(const mpcg_handle* h, CounterSlot slot) { return h->ptr<unsigned long long>(BUF_CLUSTER) + cluster_alloc_words(h) - 16 + slot; }
 
-// The handle's copy of lambda0 (mpcg_handle::lam_backup), grown to `bytes`: blocking (hipMalloc), behind whatever may still read the old copy.
-// Who sizes it: mpcg_create for every horizon the automatic policy gives to a cluster kernel, reserve_f64 for the double clusters, and
-// (ensure_lam_backup) a forced "cluster" = G on a shorter horizon at its first launch — hipMalloc: not inside a stream capture.
-static int grow_lam_backup(mpcg_handle* h, size_t bytes) {
-    if (h->lam_backup_bytes >= bytes) return MPCG_OK;
-    if (h->lam_backup) {
-        HIP_TRY(h, hipDeviceSynchronize());              // (an earlier call's fix-up launch may still read the old copy)
-        HIP_TRY(h, hipFree(h->lam_backup));
-        h->lam_backup = nullptr; h->lam_backup_bytes = 0;
-    }
-    HIP_TRY(h, hipMalloc(&h->lam_backup, bytes));
-    h->lam_backup_bytes = bytes;
-    return MPCG_OK;
-}
-static int ensure_lam_backup(mpcg_handle* h, size_t bytes, hipStream_t st) {
-    if (h->lam_backup_bytes >= bytes) return MPCG_OK;
-    const int rc = alloc_allowed(h, st, "a cluster launch whose copy of lambda mpcg_create did not size (a forced \"cluster\" on a horizon the automatic policy gives to one CU; a "
-                                        "first double solve on a handle created with more than 8 MB of double iterates: \"reserve_f64\")");
-    return rc != MPCG_OK ? rc : grow_lam_backup(h, bytes);
-}
-// queue + flags + cells zeroed and lambda copied, one launch (cluster_prologue_kernel)
+// queue + flags + cells zeroed and lambda copied, one launch (cluster_prologue_kernel).  The handle's copy of lambda0 (BUF_LAM_BACKUP): mpcg_create
+// sizes it for every horizon the automatic policy gives to a cluster kernel, reserve_f64 for the double clusters; a forced "cluster" = G on a
+// shorter horizon gets it here, for the call's batch — outside a stream capture.
 static int launch_cluster_prologue(mpcg_handle* h, unsigned long long* words, size_t zw, const void* lambda, size_t lam_bytes, hipStream_t st) {
-    const int rc = ensure_lam_backup(h, lam_bytes, st);
+    const int rc = buf_reserve(h, BUF_LAM_BACKUP, lam_bytes, &st,
+                               "a cluster launch whose copy of lambda mpcg_create did not size (a forced \"cluster\" on a horizon the automatic policy gives to one CU; a "
+                               "first double solve on a handle created with more than 8 MB of double iterates: \"reserve_f64\")");
     if (rc != MPCG_OK) return rc;
     const size_t work = zw > lam_bytes / 16 ? zw : lam_bytes / 16;
     size_t blocks = (work + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     if (blocks * 256 < zw) blocks = (zw + 255) / 256;
     hipLaunchKernelGGL(cluster_prologue_kernel, dim3((unsigned)blocks), dim3(256), 0, st, words, zw, static_cast<const uint32_t*>(lambda),
-                       static_cast<uint32_t*>(h->lam_backup), lam_bytes / 4);
+                       h->ptr<uint32_t>(BUF_LAM_BACKUP), lam_bytes / 4);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
@@ -109,11 +93,8 @@ static int launch_cluster_report(mpcg_handle* h, const unsigned long long* flags
 static int reserve_f64(mpcg_handle* h) {
     if (h->generic || h->N <= 32 || h->N > kCluster64MaxN) return MPCG_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (!h->cluster64_scratch) {
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->cluster64_scratch), cluster64_alloc_words(h) * sizeof(unsigned long long)));
-        HIP_TRY(h, hipMemset(h->cluster64_scratch, 0, cluster64_alloc_words(h) * sizeof(unsigned long long)));
-    }
-    return grow_lam_backup(h, (size_t)h->max_batch * h->N * h->n * sizeof(double));
+    { const int rc = buf_reserve(h, BUF_CLUSTER64, cluster64_alloc_words(h) * sizeof(unsigned long long), nullptr, "", true); if (rc != MPCG_OK) return rc; }
+    return buf_reserve(h, BUF_LAM_BACKUP, (size_t)h->max_batch * h->N * h->n * sizeof(double));
 }
 
 int mpcg_create(mpcg_handle** out, int device, uint32_t state_size, uint32_t knot_points, uint32_t max_batch) {
@@ -146,12 +127,10 @@ int mpcg_create(mpcg_handle** out, int device, uint32_t state_size, uint32_t kno
     const auto give_up = [h](int rc, const std::string& msg) { (void)mpcg_destroy(h); return fail(nullptr, rc, msg); };
     // hand-off cells of the cluster kernel (512 B per member, up to two members per CU), allocated here so that every solve is pure stream work
     // and can be captured into a hipGraph
-    if (hipSetDevice(device) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&h->cluster_scratch), cluster_alloc_words(h) * sizeof(unsigned long long)) != hipSuccess)
+    if (hipSetDevice(device) != hipSuccess || buf_reserve(h, BUF_CLUSTER, cluster_alloc_words(h) * sizeof(unsigned long long)) != MPCG_OK)
         return give_up(MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the cluster scratch");
-    (void)hipMemset(h->cluster_scratch, 0, cluster_alloc_words(h) * sizeof(unsigned long long));
-    if (hipMalloc(reinterpret_cast<void**>(&h->sched_order), ((size_t)max_batch + 1) * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(h->sched_order, 0, ((size_t)max_batch + 1) * sizeof(uint32_t)) != hipSuccess)      // tag 0 = no permutation yet (sched_pick)
+    (void)hipMemset(h->buf[BUF_CLUSTER].p, 0, h->buf[BUF_CLUSTER].bytes);          // (the one fill whose result is not looked at)
+    if (buf_reserve(h, BUF_SCHED_ORDER, ((size_t)max_batch + 1) * sizeof(uint32_t), nullptr, "", true) != MPCG_OK)      // tag 0 = no permutation yet (sched_pick)
         return give_up(MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the dispatch-order buffer");
     // linsys_t = double beyond N = 32 runs cluster kernels with a queue + flags + cells buffer of their own and a DOUBLE-sized copy of lambda0.
     // A float caller never needs either (N = 128, max_batch 4096 = 59 MB per handle for nothing), so mpcg_create makes them only
@@ -163,7 +142,7 @@ int mpcg_create(mpcg_handle** out, int device, uint32_t state_size, uint32_t kno
         if (knot_points <= kCluster64MaxN && bytes64 <= kEagerF64Bytes) {
             const int rc = reserve_f64(h);
             if (rc != MPCG_OK) return give_up(rc, "mpcg_create: " + h->err);
-        } else if (knot_points > kLpbMaxN && grow_lam_backup(h, (size_t)max_batch * knot_points * state_size * sizeof(float)) != MPCG_OK) {
+        } else if (knot_points > kLpbMaxN && buf_reserve(h, BUF_LAM_BACKUP, (size_t)max_batch * knot_points * state_size * sizeof(float)) != MPCG_OK) {
             return give_up(MPCG_ERR_NOMEM, "mpcg_create: cannot allocate the copy of lambda the cluster fix-up starts from");
         }
     }
@@ -179,18 +158,10 @@ int mpcg_destroy(mpcg_handle* h) {
     if (h) {
         RelaxedCaptureScope relaxed;
         (void)hipSetDevice(h->device);
-        if (h->lam_backup) (void)hipFree(h->lam_backup);
-        if (h->block_scratch) (void)hipFree(h->block_scratch);
-        if (h->block_scratch64) (void)hipFree(h->block_scratch64);
-        if (h->ginv_scratch) (void)hipFree(h->ginv_scratch);
-        if (h->seam_qinv) (void)hipFree(h->seam_qinv);
+        for (const DevBuf& b : h->buf)
+            if (b.p) (void)hipFree(b.p);
         if (h->sym_event) (void)hipEventDestroy(h->sym_event);
         if (h->sym_host) (void)hipHostFree(h->sym_host);
-        if (h->ginv_scratch_f64) (void)hipFree(h->ginv_scratch_f64);
-        if (h->merit_scratch) (void)hipFree(h->merit_scratch);
-        if (h->cluster_scratch) (void)hipFree(h->cluster_scratch);
-        if (h->cluster64_scratch) (void)hipFree(h->cluster64_scratch);
-        if (h->sched_order) (void)hipFree(h->sched_order);
     }
     delete h;
     return MPCG_OK;
@@ -767,7 +738,7 @@ static int launch_args(mpcg_handle* h, const Launch& L, PcgArgsG<T> a, uint32_t 
 // (not behind a gated launch, whose gated exits are no abandoned trajectories).
 template <typename CA, typename A>
 static int launch_cluster(mpcg_handle* h, const PcgPlan& p, const A& a, uint32_t batch, hipStream_t st, bool count_fixups) {
-    unsigned long long* words = p.lam_esz == sizeof(double) ? h->cluster64_scratch : h->cluster_scratch;
+    unsigned long long* words = h->ptr<unsigned long long>(p.lam_esz == sizeof(double) ? BUF_CLUSTER64 : BUF_CLUSTER);
     const uint32_t clusters = batch < p.resident ? batch : p.resident;
     CA ca;
     if constexpr (std::is_same<CA, ClusterArgs>::value) ca.kl_max = 128;
@@ -790,7 +761,7 @@ static int launch_cluster(mpcg_handle* h, const PcgPlan& p, const A& a, uint32_t
     A c = a;
     c.redo_flags = ca.fail_flags; c.redo_stride = CL_FLAG_STRIDE; c.redo_skip = (unsigned)p.G;
     c.redo_count = count_fixups ? counter(h, CTR_FIXUPS) : nullptr;
-    c.lam0 = static_cast<decltype(c.lam0)>(h->lam_backup);     // (members that finished a trajectory their cluster did not have written their knots of lambda)
+    c.lam0 = static_cast<decltype(c.lam0)>(h->buf[BUF_LAM_BACKUP].p);     // (members that finished a trajectory their cluster did not have written their knots of lambda)
     if constexpr (std::is_same<A, PcgArgs64>::value) c.lower = p.fix_lower;
     return launch_args(h, p.fix, c, batch, st);
 }
@@ -1032,7 +1003,7 @@ static int launch_f64(mpcg_handle* h, PcgArgs64 a, uint32_t batch, void* stream)
         if (rc != MPCG_OK) return rc;
         a.lower = h->sym_state == 1 ? 1 : 0;
     }
-    if (p.G && (!h->cluster64_scratch || (h->cluster_fixup && h->lam_backup_bytes < (size_t)h->max_batch * h->N * NS * sizeof(double)))) {
+    if (p.G && (!h->buf[BUF_CLUSTER64].p || (h->cluster_fixup && h->buf[BUF_LAM_BACKUP].bytes < (size_t)h->max_batch * h->N * NS * sizeof(double)))) {
         // (mpcg_create made them for handles with <= 8 MB of double iterates; "reserve_f64" = 1 makes them ahead of a capture)
         { const int rc = alloc_allowed(h, st, "mpcg_pcg_solve_f64 (or set \"reserve_f64\" = 1 first)"); if (rc != MPCG_OK) return rc; }
         { const int rc = reserve_f64(h); if (rc != MPCG_OK) return rc; }
@@ -1092,11 +1063,11 @@ int mpcg_pcg_solve(mpcg_handle* h, const float* d_S, const float* d_Pinv, const 
     // Calls with more trajectories than CUs: dispatch longest-expected first, the expectation being the previous call's iteration
     // counts for the same batch (pcg_kernels.hip.h: sched_order_kernel).  A scheduling hint only: no result depends on it.
     const bool hinted = h->sched_hint && !h->generic && batch > (uint32_t)h->num_cus;
-    if (hinted) { a.order = h->sched_order; a.order_tag = batch; }       // (used only if the stored permutation was made for this batch: sched_pick)
+    if (hinted) { a.order = h->ptr<uint32_t>(BUF_SCHED_ORDER); a.order_tag = batch; }       // (used only if the stored permutation was made for this batch: sched_pick)
     bool order = false;
     rc = launch_pcg(h, a, batch, static_cast<hipStream_t>(stream), 4, &order);
     if (rc == MPCG_OK && hinted && order) {
-        hipLaunchKernelGGL(sched_order_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), d_iters, (int)batch, h->sched_order);
+        hipLaunchKernelGGL(sched_order_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), d_iters, (int)batch, h->ptr<uint32_t>(BUF_SCHED_ORDER));
         HIP_TRY(h, hipGetLastError());
     }
     return rc;
@@ -1197,7 +1168,7 @@ int mpcg_pcg_solve_ref_f64(mpcg_handle* h, double* d_S, double* d_Pinv, double* 
 int mpcg_debug_read_cluster_scratch(mpcg_handle* h, unsigned long long* out, int count) {
     if (!h || !out || count < 0 || (size_t)count > cluster_alloc_words(h)) return MPCG_ERR_INVALID;
     if (hipDeviceSynchronize() != hipSuccess) return MPCG_ERR_HIP;
-    return hipMemcpy(out, h->cluster_scratch, sizeof(unsigned long long) * (size_t)count, hipMemcpyDeviceToHost) == hipSuccess ? MPCG_OK : MPCG_ERR_HIP;
+    return hipMemcpy(out, h->buf[BUF_CLUSTER].p, sizeof(unsigned long long) * (size_t)count, hipMemcpyDeviceToHost) == hipSuccess ? MPCG_OK : MPCG_ERR_HIP;
 }
 
 #ifdef MPCG_PROF

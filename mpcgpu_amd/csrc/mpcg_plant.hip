@@ -465,12 +465,11 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!h->merit_scratch) {                      // first call only (not stream-ordered: hipMalloc); shared by both entries
-        { const int rc = alloc_allowed(h, st, fn); if (rc != MPCG_OK) return rc; }
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->merit_scratch), (size_t)h->max_batch * MERIT_MAX_STEPS * h->N * sizeof(double)));
-    }
+    // the point merits: made at the first call (not stream-ordered: hipMalloc), shared by the four entries
+    { const int rc = buf_reserve(h, BUF_MERIT, (size_t)h->max_batch * MERIT_MAX_STEPS * h->N * sizeof(double), &st, fn); if (rc != MPCG_OK) return rc; }
+    double* const points = h->ptr<double>(BUF_MERIT);
     auto fill = [&](auto& k, const auto* tables) {        // one fill for either arithmetic: the scalars convert to the struct's S
-        k.plant = tables; k.eePos_traj = d_eePos_traj; k.xs = d_xs; k.xu = d_xu; k.dz = d_dz; k.point = h->merit_scratch;
+        k.plant = tables; k.eePos_traj = d_eePos_traj; k.xs = d_xs; k.xu = d_xu; k.dz = d_dz; k.point = points;
         k.N = (int)h->N; k.batch = (int)batch; k.A = (int)num_steps;
         k.dt = timestep; k.mu = mu; k.qd_cost = qd_cost; k.r_cost = r_cost;
         memcpy(k.alpha, alpha, sizeof(alpha));
@@ -504,7 +503,7 @@ static int compute_merit_impl(mpcg_handle* h, const char* fn, const mpcg_plant* 
     if (rc != MPCG_OK) return rc;
     HIP_TRY(h, hipGetLastError());
     const int rows = (int)(batch * num_steps);             // the row sums, stored as T
-    hipLaunchKernelGGL(merit_sum_kernel<T>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, h->merit_scratch, d_merit, (int)h->N, (int)num_steps, rows);
+    hipLaunchKernelGGL(merit_sum_kernel<T>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, points, d_merit, (int)h->N, (int)num_steps, rows);
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }

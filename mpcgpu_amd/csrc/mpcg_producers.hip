@@ -25,16 +25,7 @@ static int ensure_seam_buffer(mpcg_handle* h, size_t chunks_needed, size_t elem_
     const size_t auto_chunks = std::max<size_t>(2 * want + h->max_batch + 4, (size_t)h->max_batch * (size_t)(((size_t)h->N - 1 + 15) / 16));
     // (the automatic part in doubles whatever this call's type: a float call followed by a linsys_t = double call must not reallocate either)
     const size_t need = 196 * std::max(chunks_needed * elem_bytes, auto_chunks * sizeof(double));
-    if (h->seam_qinv_bytes >= need) return MPCG_OK;
-    { const int rc = alloc_allowed(h, st, "mpcg_form_schur (the seam buffer; a forced short \"schur_chunk\" needs a larger one)"); if (rc != MPCG_OK) return rc; }
-    if (h->seam_qinv) {
-        HIP_TRY(h, hipDeviceSynchronize());          // (an earlier call's kernels may still read the old buffer)
-        HIP_TRY(h, hipFree(h->seam_qinv));
-    }
-    h->seam_qinv = nullptr; h->seam_qinv_bytes = 0;
-    HIP_TRY(h, hipMalloc(&h->seam_qinv, need));
-    h->seam_qinv_bytes = need;
-    return MPCG_OK;
+    return buf_reserve(h, BUF_SEAM, need, &st, "mpcg_form_schur (the seam buffer; a forced short \"schur_chunk\" needs a larger one)");
 }
 
 // ---- the LDS route (schur_generic.hip.h): any 1 <= control_size <= state_size; at (14, 7) whatever does not run register-resident ----
@@ -57,34 +48,15 @@ static int gen_raise_lds(mpcg_handle* h, K kern, size_t lds_bytes) {      // (as
     if (lds_bytes > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     return MPCG_OK;
 }
-// the G^-1 staging buffer of the LDS formation, max_batch x ((n^2 + m^2) N - m^2) elements: grows with the largest control_size seen,
-// outside a stream capture only (an earlier call's kernels may still use the old one: synchronise before it goes)
-template <typename T>
-static int gen_ensure_staging(mpcg_handle* h, T** buf, size_t* have, size_t need, hipStream_t st, const std::string& what) {
-    if (*have >= need) return MPCG_OK;
-    { const int rc = alloc_allowed(h, st, what.c_str()); if (rc != MPCG_OK) return rc; }
-    if (*buf) {
-        HIP_TRY(h, hipDeviceSynchronize());
-        HIP_TRY(h, hipFree(*buf));
-    }
-    *buf = nullptr; *have = 0;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(buf), need * sizeof(T)));
-    *have = need;
-    return MPCG_OK;
-}
 
-// What the float and the double producers differ in: the handle's staging buffer (one per type) and the grid cap of the dz kernel.
+// What the float and the double producers differ in: the handle's staging and block-solve buffers (one of each per type) and the grid cap of the dz kernel.
 template <typename T> struct ProducerTraits;
 template <> struct ProducerTraits<float> {
-    static constexpr auto staging = &mpcg_handle::ginv_scratch;
-    static constexpr auto staging_elems = &mpcg_handle::ginv_scratch_floats;
-    static constexpr auto block_scratch = &mpcg_handle::block_scratch;
+    static constexpr BufId staging = BUF_STAGING, block_scratch = BUF_BLOCK;
     static constexpr long dz_capmul = 4;
 };
 template <> struct ProducerTraits<double> {
-    static constexpr auto staging = &mpcg_handle::ginv_scratch_f64;
-    static constexpr auto staging_elems = &mpcg_handle::ginv_scratch_f64_elems;
-    static constexpr auto block_scratch = &mpcg_handle::block_scratch64;
+    static constexpr BufId staging = BUF_STAGING64, block_scratch = BUF_BLOCK64;
     // (126 VGPRs, four wavefronts per SIMD against the float kernel's seven: capped at 1 the 1024 x 128 call ran two quads per workgroup,
     //  0.1165-0.1175 ms against 0.1126-0.1128 with the float kernel's cap, tools/_prof/dz64_ab.py)
     static constexpr long dz_capmul = MPCG_DZ64_CAPMUL;
@@ -109,9 +81,10 @@ static int form_schur_lds(mpcg_handle* h, const char* fn, const char* why, Schur
     if (lds > kGenLdsMax)
         return fail(h, MPCG_ERR_UNSUPPORTED, std::string(fn) + ": the operands of one block row (" + std::to_string(lds) + " bytes at state_size " + std::to_string(n) +
                     ", control_size " + std::to_string(m) + ") exceed the LDS limit of 160 KiB (6 n^2 + 2 n m + 2 m^2 + 12 n + 4 m elements)");
+    // the G^-1 staging buffer, max_batch x ((n^2 + m^2) N - m^2) elements: grows with the largest control_size seen, outside a stream capture only
     const size_t Gsz = (size_t)(n * n + m * m) * N - (size_t)m * m;
-    { const int rc = gen_ensure_staging(h, &(h->*Tr::staging), &(h->*Tr::staging_elems), Gsz * h->max_batch, st, std::string(fn) + why); if (rc != MPCG_OK) return rc; }
-    a.Ginv_scratch = h->*Tr::staging;
+    { const int rc = buf_reserve(h, Tr::staging, Gsz * h->max_batch * sizeof(T), &st, (std::string(fn) + why).c_str()); if (rc != MPCG_OK) return rc; }
+    a.Ginv_scratch = h->ptr<T>(Tr::staging);
     const long items = (long)a.batch * N;
     const int nt = gen_threads(n);
     const SchurArgsT<T>& as = a;
@@ -146,7 +119,7 @@ static int form_schur_walk(mpcg_handle* h, const SchurArgsVT<T>& a, hipStream_t 
     sw::WalkArgsVT<T> wv;
     sw::WalkArgsT<T>& w = wv;                    // (what the scalar walking kernel and the seam kernel take)
     w.s = a;                                     // (Ginv_scratch stays null: G^-1 is written in place)
-    w.seam_qinv = static_cast<T*>(h->seam_qinv); w.L = wL; w.chunks = wchunks;
+    w.seam_qinv = h->ptr<T>(BUF_SEAM); w.L = wL; w.chunks = wchunks;
     wv.rho_v = a.rho_v;
     h->last_schur_chunk = wL;
     const long capw = (long)h->num_cus * 64;
@@ -235,7 +208,7 @@ static int compute_dz_impl(mpcg_handle* h, const char* fn, uint32_t control_size
 }
 
 // The direct solve, ONE host path: CT is the sweep type, ST the storage type of S, gamma and lambda (CT = double, ST = float: widened on load,
-// lambda rounded once on store).  W_k, z_k go through block_scratch (CT = float) or block_scratch64 (CT = double), two buffers of their own,
+// lambda rounded once on store).  W_k, z_k go through BUF_BLOCK (CT = float) or BUF_BLOCK64 (CT = double), two buffers of their own,
 // each allocated on its first use: neither is ever resized, freed or shared — a solve captured into a graph has its pointer baked in.
 template <typename CT, typename ST>
 static int block_solve_impl(mpcg_handle* h, const char* fn, const ST* d_S, const ST* d_gamma, ST* d_lambda, uint32_t batch, void* stream) {
@@ -245,12 +218,9 @@ static int block_solve_impl(mpcg_handle* h, const char* fn, const ST* d_S, const
     if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    CT*& work = h->*ProducerTraits<CT>::block_scratch;
-    if (!work) {                                  // first call only (not stream-ordered: hipMalloc)
-        const int rc = alloc_allowed(h, st, fn); if (rc != MPCG_OK) return rc;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&work),
-                             (size_t)h->max_batch * h->N * ((size_t)h->n * h->n + h->n) * sizeof(CT)));          // W_k (n x n) + z_k per knot
-    }
+    // W_k (n x n) + z_k per knot: made at the first call of this sweep type (not stream-ordered: hipMalloc)
+    { const int rc = buf_reserve(h, ProducerTraits<CT>::block_scratch, (size_t)h->max_batch * h->N * ((size_t)h->n * h->n + h->n) * sizeof(CT), &st, fn); if (rc != MPCG_OK) return rc; }
+    CT* work = h->ptr<CT>(ProducerTraits<CT>::block_scratch);
     if (h->generic || h->producers_generic) {         // any state size: one workgroup per trajectory, operands in LDS (schur_generic.hip.h)
         gen::BlockSolveGenArgsT<CT, ST> ga{d_S, d_gamma, d_lambda, work, (int)h->n, (int)h->N, (int)batch};
         const size_t lds = gen::block_solve_lds_elems((int)h->n) * sizeof(CT);          // 133,664 bytes in double at n = 64

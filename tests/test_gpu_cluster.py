@@ -327,7 +327,7 @@ def test_without_a_fixup_launch_an_abandoned_trajectory_is_always_reported(preci
     assert (it2.cpu().numpy() == K).all() and torch.equal(lam2, lam_ok)
 
 
-# ---- the handle's copy of lambda (mpcg_handle::lam_backup): sized by mpcg_create, at the first launch that needs it, or by "reserve_f64" ----
+# ---- the handle's copy of lambda (BUF_LAM_BACKUP of mpcg_handle): sized by mpcg_create, at the first launch that needs it, or by "reserve_f64" ----
 LAMCOPY_N, LAMCOPY_B, LAMCOPY_K = 64, 2, 6
 LAMCOPY_MAX_BATCH = 1200        # 1200 x 64 x 14 doubles > 8 MB: mpcg_create sizes no copy for this handle (64 knots: no automatic cluster either)
 _lamcopy = {}
