@@ -25,10 +25,14 @@
 // with --sim-saturate the simulated plant clamps every control it applies to [-X, X].  The JSON line then carries "u_max", "u_weight", "sim_saturate" and
 // "u_excess_peak", the largest max(|u| - X, 0) over the controls of every iterate the SQP calls left; with --u-max inf, or without it, it is what it was
 // (--u-weight or --sim-saturate without --u-max is refused).
+// --periods-us p0,p1,... (the batched run): trajectory b updates every p[b mod count] microseconds — every trajectory on its own schedule.  The clocks
+// (prev_simulation_time, time_since_timestep, shifted) then live in device arrays and the run calls mpcg_simulate_clk / mpcg_advance_horizon_clk, which decide
+// each trajectory's shift on the device; the host ShiftClock is run once per distinct period for the expected shift counts.  The JSON line then carries
+// "periods_us", "expected_shifts" and "shifts" per trajectory, and "tracking_errors" as one list per trajectory; without the flag it is what it was.
 // Prints one JSON line; exits 0 only if every tracking error is finite and every trajectory shifted the expected number of times.
 //   hipcc --offload-arch=gfx950 -O2 -DLINSYS_SOLVE=1 [-DUSE_DOUBLES] -Iinclude examples/mpc_closed_loop.cpp -Lmpcgpu_amd -lmpcg_hip
 //   mpc_closed_loop [--batch 4] [--knots 16] [--updates 17] [--iters 1] [--mpc-steps 16] [--integrator {0,1}] [--sim-integrator {0,1}] [--gravity G] [--sim-gravity G]
-//                   [--q-cost Q] [--u-relative {0,1}] [--u-max X] [--u-weight W] [--sim-saturate]
+//                   [--q-cost Q] [--u-relative {0,1}] [--u-max X] [--u-weight W] [--sim-saturate] [--periods-us p0,p1,...]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -147,6 +151,7 @@ int main(int argc, char** argv) {
     bool sim_saturate = false, u_max_given = false, u_weight_given = false;
     bool sim_gravity_given = false;
     int u_relative = 0;
+    std::vector<double> periods;                                              // --periods-us: empty = one clock on the host, 2,000 us for all
     int integrator = -1, sim_integrator = -1;                                 // -1: not given (0)
     for (int i = 1; i < argc; i += 2) {
         if (!strcmp(argv[i], "--sim-saturate")) { sim_saturate = true; --i; continue; }      // (a flag without a value)
@@ -163,6 +168,14 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--q-cost")) q_cost = atof(argv[i + 1]);
         else if (!strcmp(argv[i], "--u-relative")) u_relative = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--u-max")) { u_max = atof(argv[i + 1]); u_max_given = true; }
+        else if (!strcmp(argv[i], "--periods-us")) {
+            for (const char* c = argv[i + 1]; *c;) {
+                char* end = nullptr;
+                periods.push_back(strtod(c, &end));
+                if (end == c || (*end && *end != ',')) { fprintf(stderr, "--periods-us takes a comma-separated list of numbers\n"); return 2; }
+                c = *end ? end + 1 : end;
+            }
+        }
         else if (!strcmp(argv[i], "--u-weight")) { u_weight = atof(argv[i + 1]); u_weight_given = true; }
         else { fprintf(stderr, "unknown option %s\n", argv[i]); return 2; }
     }
@@ -173,6 +186,9 @@ int main(int argc, char** argv) {
     if (!std::isfinite(q_cost) || q_cost < 0.0 || u_relative < 0 || u_relative > 1) { fprintf(stderr, "--q-cost takes a finite number >= 0, --u-relative 0 or 1\n"); return 2; }
     if ((u_weight_given || sim_saturate) && !u_max_given) { fprintf(stderr, "--u-weight and --sim-saturate need --u-max\n"); return 2; }
     if (!(u_max > 0.0) || !std::isfinite(u_weight) || u_weight < 0.0) { fprintf(stderr, "--u-max takes a number > 0 (inf: no limit), --u-weight a finite number >= 0\n"); return 2; }
+    for (double p : periods)
+        if (!std::isfinite(p) || p < 0.0) { fprintf(stderr, "--periods-us takes finite numbers >= 0\n"); return 2; }
+    const bool clocks = !periods.empty();                                     // the batched run keeps per-trajectory clocks on the device
     const bool limits = std::isfinite(u_max);                                 // the batched run's plants carry torque limits: its cost comes from the _xuref entries
     const bool xuref = q_cost != 0.0 || u_relative != 0 || limits;           // the batched run's cost tracks the joint-space plan (the _xuref entries)
     const bool flagged = integrator >= 0 || sim_integrator >= 0;
@@ -273,6 +289,11 @@ int main(int argc, char** argv) {
     ShiftClock clock(dt);
     double prev_us = 0;
     int shifts = 0;
+    // --periods-us: the clocks of all trajectories on the device, zero at the start; the decisions of every update wait in d_did_hist
+    std::vector<double> sim_us((size_t)B, period_us);
+    for (int b = 0; clocks && b < B; ++b) sim_us[b] = periods[(size_t)b % periods.size()];
+    double *d_sim_us = to_device(sim_us), *d_prev_us = dalloc<double>(B), *d_since = dalloc<double>(B);
+    int32_t *d_shifted = dalloc<int32_t>(B), *d_did = dalloc<int32_t>(B), *d_did_hist = dalloc<int32_t>((size_t)U * B);
     for (int u = 0; u < U; ++u) {                                             // no host synchronisation in here
         // one SQP call (include/pcg/sqp.cuh): x_s = x_0 of the iterate, drho = 1, merit of the start iterate, K iterations
         gpuErrchk(hipMemcpyAsync(d_drho, d_ones, B * sizeof(T), hipMemcpyDeviceToDevice, s));
@@ -290,6 +311,15 @@ int main(int argc, char** argv) {
         }
         // the plant runs under the PREVIOUS plan for one period, offset by the previous period (include/mpcsim.cuh:288-291, :352)
         if (limits) hipLaunchKernelGGL(u_excess_peak, dim3(1), dim3(256), 0, s, d_xu, B, N, u_max, d_peak);
+        if (clocks) {                                                         // every trajectory's own offset, period and shift decision, on the device
+            MPCG_OK_OR_DIE(h, LS(mpcg_simulate_clk)(h, plant_sim_b, m, d_xs, d_xu_old, dt, d_prev_us, d_sim_us, (T)2e-4f, d_eePos, d_done, (uint32_t)B, s));
+            gpuErrchk(hipMemcpyAsync(d_xu_old, d_xu, (size_t)B * L * sizeof(T), hipMemcpyDeviceToDevice, s));
+            MPCG_OK_OR_DIE(h, LS(mpcg_advance_horizon_clk)(h, m, d_xu, d_lambda, d_goals, d_xs, d_eePos, d_bplan, d_bgoals, (uint32_t)TS, (uint32_t)TS, 0, d_offset, d_done,
+                                                           d_err, dt, (double)(T)(1 * dt), d_sim_us, d_prev_us, d_since, d_shifted, d_did, (uint32_t)B, s));
+            gpuErrchk(hipMemcpyAsync(d_err_hist + (size_t)u * B, d_err, B * sizeof(T), hipMemcpyDeviceToDevice, s));
+            gpuErrchk(hipMemcpyAsync(d_did_hist + (size_t)u * B, d_did, B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            continue;
+        }
         MPCG_OK_OR_DIE(h, LS(mpcg_simulate)(h, plant_sim_b, m, d_xs, d_xu_old, dt, prev_us, period_us, (T)2e-4f, d_eePos, (uint32_t)B, s));
         gpuErrchk(hipMemcpyAsync(d_xu_old, d_xu, (size_t)B * L * sizeof(T), hipMemcpyDeviceToDevice, s));
         const bool shift = clock.update(period_us);
@@ -313,18 +343,55 @@ int main(int argc, char** argv) {
 
     bool ok = (int)mpc_errors.size() == mpc_steps;
     for (linsys_t e : mpc_errors) ok = ok && std::isfinite((double)e);
-    for (int i = 0; i < shifts * B; ++i) ok = ok && std::isfinite((double)err[i]);
     for (T x : xs_end) ok = ok && std::isfinite((double)x);
-    for (int b = 0; b < B; ++b) ok = ok && offset[b] == shifts;
+    // --periods-us: the expected count of each trajectory from the host clock, run once per distinct period; its errors are those of the updates it shifted in
+    std::vector<int32_t> did((size_t)U * B, 0);
+    std::vector<int> expected((size_t)B, 0);
+    if (clocks) {
+        gpuErrchk(hipMemcpy(did.data(), d_did_hist, did.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < periods.size() && i < (size_t)B; ++i) {
+            size_t first = 0;
+            while (periods[first] != periods[i]) ++first;
+            if (first == i) {
+                ShiftClock c(dt);
+                for (int u = 0; u < U; ++u) expected[i] += c.update(periods[i]) ? 1 : 0;
+            } else expected[i] = expected[first];
+        }
+        for (int b = (int)periods.size(); b < B; ++b) expected[b] = expected[(size_t)b % periods.size()];
+        for (int b = 0; b < B; ++b) {
+            int count = 0;
+            for (int u = 0; u < U; ++u)
+                if (did[(size_t)u * B + b]) { ++count; ok = ok && std::isfinite((double)err[(size_t)u * B + b]); }
+            ok = ok && count == expected[b] && offset[b] == expected[b];
+        }
+    } else {
+        for (int i = 0; i < shifts * B; ++i) ok = ok && std::isfinite((double)err[i]);
+        for (int b = 0; b < B; ++b) ok = ok && offset[b] == shifts;
+    }
     printf("{\"batch\": %d, \"knots\": %d, \"updates\": %d, \"iters\": %d, ", B, N, U, K);
     if (flagged) printf("\"integrator\": %u, \"sim_integrator\": %u, ", integ, sim_integ);
     if (gravity != 0.0 || sim_gravity != 0.0) printf("\"gravity\": %g, \"sim_gravity\": %g, ", gravity, sim_gravity);
     if (q_cost != 0.0 || u_relative != 0) printf("\"q_cost\": %g, \"u_relative\": %d, ", q_cost, u_relative);
     if (limits) printf("\"u_max\": %g, \"u_weight\": %g, \"sim_saturate\": %d, \"u_excess_peak\": %.9g, ", u_max, u_weight, sim_saturate ? 1 : 0, peak);
-    printf("\"expected_shifts\": %d, \"shifts\": [", shifts);
+    if (clocks) {
+        printf("\"periods_us\": [");
+        for (int b = 0; b < B; ++b) printf("%s%.17g", b ? ", " : "", sim_us[b]);
+        printf("], \"expected_shifts\": [");
+        for (int b = 0; b < B; ++b) printf("%s%d", b ? ", " : "", expected[b]);
+        printf("], \"shifts\": [");
+    } else {
+        printf("\"expected_shifts\": %d, \"shifts\": [", shifts);
+    }
     for (int b = 0; b < B; ++b) printf("%s%d", b ? ", " : "", offset[b]);
     printf("], \"tracking_errors\": [");
-    for (int i = 0; i < shifts; ++i) {
+    for (int b = 0; clocks && b < B; ++b) {                                     // one list per trajectory: the updates it shifted in
+        printf("%s[", b ? ", " : "");
+        bool any = false;
+        for (int u = 0; u < U; ++u)
+            if (did[(size_t)u * B + b]) { printf("%s%.9g", any ? ", " : "", (double)err[(size_t)u * B + b]); any = true; }
+        printf("]");
+    }
+    for (int i = 0; !clocks && i < shifts; ++i) {
         printf("%s[", i ? ", " : "");
         for (int b = 0; b < B; ++b) printf("%s%.9g", b ? ", " : "", (double)err[(size_t)i * B + b]);
         printf("]");
@@ -336,7 +403,8 @@ int main(int argc, char** argv) {
     for (void* p : {(void*)d_plan, (void*)d_plan_goals, (void*)d_bplan, (void*)d_bgoals, (void*)d_xu, (void*)d_xu_old, (void*)d_goals, (void*)d_xs, (void*)d_G, (void*)d_C,
                     (void*)d_g, (void*)d_c, (void*)d_S, (void*)d_Pinv, (void*)d_gamma, (void*)d_lambda, (void*)d_dz, (void*)d_merit, (void*)d_merit_ref, (void*)d_eePos,
                     (void*)d_err, (void*)d_err_hist, (void*)d_rho, (void*)d_drho, (void*)d_ones, (void*)d_step, (void*)d_offset, (void*)d_done, (void*)d_iters,
-                    (void*)d_exit, (void*)d_gave_up})
+                    (void*)d_exit, (void*)d_gave_up, (void*)d_sim_us, (void*)d_prev_us, (void*)d_since, (void*)d_shifted, (void*)d_did,
+                    (void*)d_did_hist})
         gpuErrchk(hipFree(p));
     gpuErrchk(hipStreamDestroy(s));
     if (limits) { gpuErrchk(hipFree(d_peak)); mpcg_plant_destroy(plant_ctrl_b); mpcg_plant_destroy(plant_sim_b); }

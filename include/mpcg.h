@@ -728,6 +728,72 @@ int mpcg_advance_horizon_f64(mpcg_handle *h, uint32_t control_size, uint32_t shi
                              uint32_t xu_fill_lead, int32_t *d_traj_offset, int32_t *d_done /* [batch] in/out */,
                              double *d_tracking_error /* [batch] out */, uint32_t batch, void *stream);
 
+/* ---- per-trajectory clocks: every trajectory of a batch on its own update schedule (csrc/sim_plant.hip.h) ----
+ * The two calls above take ONE time offset, ONE simulated time and ONE shift decision per call: the clock bookkeeping of simulateMPC
+ * (prev_simulation_time, time_since_timestep, shifted: include/mpcsim.cuh:280-352) is the caller's, in host scalars, the same for the whole batch.
+ * The _clk entries keep it in device arrays, one element per trajectory: trajectories may update at different rates or phases (the reference's own
+ * non-CONST_UPDATE_FREQ mode, simulation_time = sqp_solve_time_us, differs per trajectory as soon as iteration counts do), and ONE captured control
+ * update follows whatever the arrays hold at each replay.  Float and _f64 twins as above (arrays double, sim_step a double, the remainder not rounded
+ * to float); the time and clock arrays are double / int32 in both.  state_size 14 / control_size 7 only (MPCG_ERR_UNSUPPORTED); pure stream work,
+ * capturable from the first call: no allocation, no read-back.  batch == 0 returns MPCG_OK.
+ *
+ * mpcg_simulate_clk.  Trajectory b gets exactly — bit for bit — what mpcg_simulate gives it with time_offset_us = d_time_offset_us[b] and
+ * sim_time_us = d_sim_time_us[b]; everything said of mpcg_simulate holds per trajectory: the schedule with its remainder substep under the index of the
+ * last full substep, the clamp to knot_points - 2, "a remainder of exactly 0 is not run", the float64 state rounded once on store, "sim_integrator"
+ * and MPCG_LIMITS_SIM_SATURATE.  The host's part of the schedule — toff = t * 1e-6, sim = t * 1e-6, S = (uint32)(sim / ss), rem = (double)(T)fmod(sim, ss) —
+ * is evaluated on the device in IEEE double, one rounding per operation (fmod is exact).  Four trajectories share a wavefront whose substep loop has
+ * barriers: A WAVEFRONT TAKES AS LONG AS ITS LONGEST TRAJECTORY (a call as long as its longest wavefront); a trajectory's results do not depend on its
+ * neighbours.
+ *   d_done (may be NULL): a trajectory with d_done[b] != 0 on entry is FROZEN: nothing of it is written, neither d_xs nor d_eePos.
+ *   A trajectory whose times are no schedule — non-finite or negative, or sim / ss >= 65537 (MPCG_SIM_MAX_SUBSTEPS) — is not simulated: nothing of it is
+ *   written except d_done[b] = MPCG_DONE_BAD_CLOCK when d_done is given (without d_done it is skipped silently).  Its neighbours are unaffected.
+ *   MPCG_ERR_INVALID   as mpcg_simulate for the arguments that remain (null d_xs / d_xu, sim_step <= 0, timestep <= 0, non-finite, batch > max_batch,
+ *                      a plant on another device), and a null time array.  Nothing is written.
+ *
+ * mpcg_advance_horizon_clk.  mpcg_advance_horizon's arguments without `shift`, the knot spacing, the shift threshold in seconds (the reference's
+ * SHIFT_THRESHOLD: (double)(T)(1 * timestep)) and the clock: d_sim_time_us [batch] (in), d_prev_sim_us [batch] (prev_simulation_time, us), d_since_s
+ * [batch] (time_since_timestep, s), d_shifted [batch] (int32 0 / 1), in/out, and d_did_shift [batch] (out, may be NULL).  One workgroup per trajectory;
+ * for every trajectory with d_done[b] == 0, include/mpcsim.cuh:294-352 literally, in double with one rounding per operation:
+ *     since = d_since_s[b] + d_sim_time_us[b] * 1e-6
+ *     shift = d_shifted[b] == 0 && since > shift_threshold_s
+ *     exactly what mpcg_advance_horizon does to trajectory b with that shift (shift = 0: the start-state copy only, d_tracking_error[b] untouched)
+ *     if (shift) shifted = 1
+ *     if (since > timestep) { shifted = 0; since = fmod(since, timestep) }
+ *     d_since_s[b] = since, d_shifted[b] = shifted, d_prev_sim_us[b] = d_sim_time_us[b], d_did_shift[b] = shift
+ *   A FROZEN trajectory (d_done[b] != 0 on entry) keeps everything, its clock included; only d_did_shift[b] = 0 is written.
+ *   A non-finite or negative d_sim_time_us[b] on a live trajectory sets d_done[b] = MPCG_DONE_BAD_CLOCK and writes nothing else.
+ *   The reference hands prev_simulation_time to simple_simulate as the time offset (:288), not time_since_timestep: a loop passes d_prev_sim_us as
+ *   mpcg_simulate_clk's d_time_offset_us —  per update: d_xu_old <- d_xu; mpcg_simulate_clk(d_xs, d_xu_old, d_prev_sim_us, d_sim_time_us);
+ *   mpcg_advance_horizon_clk(..., d_sim_time_us, d_prev_sim_us, d_since_s, d_shifted).  A new loop starts from zeros in all three state arrays.
+ *   MPCG_ERR_INVALID   a null array other than d_did_shift (any trajectory may shift: every array of mpcg_advance_horizon(shift = 1) is required, d_eePos and
+ *                      d_done included); a non-finite or non-positive timestep; a non-finite or negative shift_threshold_s; traj_steps = 0;
+ *                      xu_fill_lead > N - 1; 0 < traj_batch_stride < traj_steps; batch > max_batch.  Nothing is written. */
+#define MPCG_DONE_BAD_CLOCK 2
+int mpcg_simulate_clk(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size,
+                      float *d_xs /* [batch][14] in/out */, const float *d_xu /* [batch][(n+m)N - m] */, double timestep,
+                      const double *d_time_offset_us /* [batch] */, const double *d_sim_time_us /* [batch] */, float sim_step /* reference: 2e-4f */,
+                      float *d_eePos /* [batch][3] or NULL */, int32_t *d_done /* [batch] in/out, or NULL */, uint32_t batch, void *stream);
+int mpcg_simulate_clk_f64(mpcg_handle *h, const mpcg_plant *plant, uint32_t control_size,
+                          double *d_xs /* [batch][14] in/out */, const double *d_xu /* [batch][(n+m)N - m] */, double timestep,
+                          const double *d_time_offset_us /* [batch] */, const double *d_sim_time_us /* [batch] */, double sim_step,
+                          double *d_eePos /* [batch][3] or NULL */, int32_t *d_done /* [batch] in/out, or NULL */, uint32_t batch, void *stream);
+int mpcg_advance_horizon_clk(mpcg_handle *h, uint32_t control_size,
+                             float *d_xu, float *d_lambda, float *d_eePos_goal /* in/out */,
+                             const float *d_xs /* [batch][14] */, const float *d_eePos /* [batch][3] */,
+                             const float *d_xu_traj, const float *d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride,
+                             uint32_t xu_fill_lead, int32_t *d_traj_offset, int32_t *d_done /* [batch] in/out */,
+                             float *d_tracking_error /* [batch] out */, double timestep, double shift_threshold_s,
+                             const double *d_sim_time_us /* [batch] */, double *d_prev_sim_us, double *d_since_s, int32_t *d_shifted /* [batch] in/out */,
+                             int32_t *d_did_shift /* [batch] out, or NULL */, uint32_t batch, void *stream);
+int mpcg_advance_horizon_clk_f64(mpcg_handle *h, uint32_t control_size,
+                                 double *d_xu, double *d_lambda, double *d_eePos_goal /* in/out */,
+                                 const double *d_xs /* [batch][14] */, const double *d_eePos /* [batch][3] */,
+                                 const double *d_xu_traj, const double *d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride,
+                                 uint32_t xu_fill_lead, int32_t *d_traj_offset, int32_t *d_done /* [batch] in/out */,
+                                 double *d_tracking_error /* [batch] out */, double timestep, double shift_threshold_s,
+                                 const double *d_sim_time_us /* [batch] */, double *d_prev_sim_us, double *d_since_s, int32_t *d_shifted /* [batch] in/out */,
+                                 int32_t *d_did_shift /* [batch] out, or NULL */, uint32_t batch, void *stream);
+
 /* ---- LINSYS_SOLVE == 0 as a selectable solver: the reference's CPU LDL^T path ----
  * The reference's second linear-system path factors the (negated) Schur matrix on the HOST with QDLDL
  * (include/qdldl/sqp.cuh: pattern prep_csr :164 + QDLDL_etree :193 once per SQP call; per SQP iteration D2H(values,

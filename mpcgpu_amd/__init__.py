@@ -3,8 +3,8 @@
 Product = libmpcg_hip.so (C ABI in include/mpcg.h, kernels in mpcgpu_amd/csrc/).
 This package is the thin host-side mirror of the reference's interface for that path.
 """
-from .solver import PcgSolver, Plant, QdldlSolver, XuRef, pcg_config, pcgSharedMemSize  # noqa: F401
+from .solver import Clocks, PcgSolver, Plant, QdldlSolver, XuRef, pcg_config, pcgSharedMemSize  # noqa: F401
 
 LdlSolver = QdldlSolver     # (the host LDL^T twin under its shorter name)
 
-__all__ = ["PcgSolver", "Plant", "QdldlSolver", "XuRef", "LdlSolver", "pcg_config", "pcgSharedMemSize"]
+__all__ = ["Clocks", "PcgSolver", "Plant", "QdldlSolver", "XuRef", "LdlSolver", "pcg_config", "pcgSharedMemSize"]

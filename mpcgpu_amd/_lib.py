@@ -22,6 +22,7 @@ MPCG_PRECOND_SS = 3
 MPCG_MAX_STEP_SIZES = 16
 MPCG_STEP_FROZEN = -2
 MPCG_SIM_MAX_SUBSTEPS = 65536
+MPCG_DONE_BAD_CLOCK = 2
 MPCG_XUREF_QD_RELATIVE = 1
 MPCG_XUREF_U_RELATIVE = 2
 MPCG_LIMITS_SIM_SATURATE = 1
@@ -123,6 +124,16 @@ SYMBOLS = {
                                     C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_advance_horizon_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_simulate_clk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_float,
+                                    C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_simulate_clk_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_double,
+                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_advance_horizon_clk": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mpcg_advance_horizon_clk_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "mpcg_ldl_create":(C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
     "mpcg_ldl_destroy": (C.c_int, [C.c_void_p]),
     "mpcg_ldl_pattern": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),

@@ -604,7 +604,8 @@ int mpcg_line_search_step_rho_f64(mpcg_handle* h, uint32_t control_size, const d
 }
 
 // ---- plant simulation and horizon shift: the step between two SQP solves (sim_plant.hip.h) ----
-// mpcg_simulate (T = float) and mpcg_simulate_f64 (T = double), mpcg_advance_horizon and mpcg_advance_horizon_f64: one host path each (fn: the entry point's name)
+// mpcg_simulate (T = float) and mpcg_simulate_f64 (T = double), mpcg_advance_horizon and mpcg_advance_horizon_f64: one host path each (fn: the entry point's name);
+// their _clk entries (per-trajectory clocks in device arrays) likewise, behind them
 extern "C++" {
 template <typename T>
 static int simulate_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, T* d_xs, const T* d_xu, double timestep,
@@ -665,6 +666,64 @@ static int advance_horizon_impl(mpcg_handle* h, const char* fn, uint32_t control
     HIP_TRY(h, hipGetLastError());
     return MPCG_OK;
 }
+
+// mpcg_simulate_clk (T = float) and mpcg_simulate_clk_f64 (T = double), mpcg_advance_horizon_clk and mpcg_advance_horizon_clk_f64: the two entries above with the
+// clock in device arrays, one host path each.  What simulate_impl computes of the schedule on the host, the CLOCK = 1 kernels compute per trajectory.
+template <typename T>
+static int simulate_clk_impl(mpcg_handle* h, const char* fn, const mpcg_plant* plant, uint32_t control_size, T* d_xs, const T* d_xu, double timestep,
+                             const double* d_time_offset_us, const double* d_sim_time_us, T sim_step, T* d_eePos, int32_t* d_done, uint32_t batch, void* stream) {
+    static_assert(SIM_DONE_BAD_CLOCK == MPCG_DONE_BAD_CLOCK && ADV_DONE_BAD_CLOCK == MPCG_DONE_BAD_CLOCK, "the flag of the header");
+    if (!h || !plant) return MPCG_ERR_INVALID;
+    if (!d_xs || !d_xu || !d_time_offset_us || !d_sim_time_us) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": null device pointer");
+    { const int rc = check_plant(h, fn, plant, control_size, true); if (rc != MPCG_OK) return rc; }
+    if (!std::isfinite(timestep) || !std::isfinite(sim_step)) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": timestep and sim_step must be finite");
+    if (!(sim_step > T(0)) || !(timestep > 0.0)) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": needs sim_step > 0 and timestep > 0");
+    if (batch == 0) return MPCG_OK;
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, std::string(fn) + ": batch exceeds max_batch");
+    HIP_TRY(h, hipSetDevice(h->device));
+    SimClkArgsT<T> a;
+    a.plant = plant->d; a.xs = d_xs; a.xu = d_xu; a.eePos = d_eePos;
+    a.N = (int)h->N; a.batch = (int)batch;
+    a.S = 0; a.ss = (double)sim_step; a.toff = 0.0; a.timestep = timestep; a.rem = 0.0;      // (S, toff, rem: per trajectory, on the device)
+    a.toff_us = d_time_offset_us; a.sim_us = d_sim_time_us; a.done = d_done;
+    const dim3 grid((batch + KKT_ITEMS - 1) / KKT_ITEMS);
+    const bool semi = h->sim_integrator == 1;
+    const bool saturate = plant->has_limits && (plant->lim.flags & MPCG_LIMITS_SIM_SATURATE);
+    void (*const kernel)(SimClkArgsT<T>) = saturate ? (semi ? simulate_kernel<T, 1, 1, 1> : simulate_kernel<T, 0, 1, 1>) : (semi ? simulate_kernel<T, 1, 0, 1> : simulate_kernel<T, 0, 0, 1>);
+    hipLaunchKernelGGL(kernel, grid, dim3(KKT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
+
+template <typename T>
+static int advance_horizon_clk_impl(mpcg_handle* h, const char* fn, uint32_t control_size, T* d_xu, T* d_lambda, T* d_eePos_goal, const T* d_xs, const T* d_eePos,
+                                    const T* d_xu_traj, const T* d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride, uint32_t xu_fill_lead,
+                                    int32_t* d_traj_offset, int32_t* d_done, T* d_tracking_error, double timestep, double shift_threshold_s,
+                                    const double* d_sim_time_us, double* d_prev_sim_us, double* d_since_s, int32_t* d_shifted, int32_t* d_did_shift, uint32_t batch,
+                                    void* stream) {
+    const std::string who(fn);
+    if (!h) return MPCG_ERR_INVALID;
+    if (!d_xu || !d_xs || !d_eePos || !d_lambda || !d_eePos_goal || !d_xu_traj || !d_eePos_traj || !d_traj_offset || !d_done || !d_tracking_error)
+        return fail(h, MPCG_ERR_INVALID, who + ": null device pointer (any trajectory may shift: every array of shift = 1 is needed)");
+    if (!d_sim_time_us || !d_prev_sim_us || !d_since_s || !d_shifted) return fail(h, MPCG_ERR_INVALID, who + ": null time or clock array");
+    if (control_size != (uint32_t)PJ || h->n != 2u * PJ) return fail(h, MPCG_ERR_UNSUPPORTED, who + ": state_size 14 / control_size 7 (IIWA-14) only");
+    if (traj_steps == 0 || xu_fill_lead > h->N - 1 || (traj_batch_stride != 0 && traj_batch_stride < traj_steps))
+        return fail(h, MPCG_ERR_INVALID, who + ": needs traj_steps >= 1, xu_fill_lead <= knot_points - 1 and traj_batch_stride 0 or >= traj_steps");
+    if (!std::isfinite(timestep) || !(timestep > 0.0) || !std::isfinite(shift_threshold_s) || shift_threshold_s < 0.0)
+        return fail(h, MPCG_ERR_INVALID, who + ": needs a finite timestep > 0 and a finite shift_threshold_s >= 0");
+    if (batch == 0) return MPCG_OK;
+    if (batch > h->max_batch) return fail(h, MPCG_ERR_INVALID, who + ": batch exceeds max_batch");
+    HIP_TRY(h, hipSetDevice(h->device));
+    AdvanceClkArgsT<T> a;
+    a.xu = d_xu; a.lambda = d_lambda; a.goal = d_eePos_goal; a.xs = d_xs; a.eePos = d_eePos; a.xu_traj = d_xu_traj; a.goal_traj = d_eePos_traj;
+    a.traj_offset = d_traj_offset; a.done = d_done; a.tracking_error = d_tracking_error;
+    a.n = h->n; a.m = control_size; a.N = h->N; a.traj_steps = traj_steps; a.traj_stride = traj_batch_stride; a.lead = xu_fill_lead; a.shift = 1;
+    a.timestep = timestep; a.threshold = shift_threshold_s;
+    a.sim_us = d_sim_time_us; a.prev_us = d_prev_sim_us; a.since = d_since_s; a.shifted = d_shifted; a.did_shift = d_did_shift;
+    hipLaunchKernelGGL(advance_horizon_clk_kernel<T>, dim3(batch), dim3(ADV_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(h, hipGetLastError());
+    return MPCG_OK;
+}
 }  // extern "C++"
 
 int mpcg_simulate(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float* d_xs, const float* d_xu, double timestep, double time_offset_us,
@@ -717,6 +776,37 @@ int mpcg_advance_horizon_f64(mpcg_handle* h, uint32_t control_size, uint32_t shi
                              uint32_t xu_fill_lead, int32_t* d_traj_offset, int32_t* d_done, double* d_tracking_error, uint32_t batch, void* stream) {
     return advance_horizon_impl<double>(h, "mpcg_advance_horizon_f64", control_size, shift, d_xu, d_lambda, d_eePos_goal, d_xs, d_eePos, d_xu_traj, d_eePos_traj,
                                         traj_steps, traj_batch_stride, xu_fill_lead, d_traj_offset, d_done, d_tracking_error, batch, stream);
+}
+
+int mpcg_simulate_clk(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, float* d_xs, const float* d_xu, double timestep, const double* d_time_offset_us,
+                      const double* d_sim_time_us, float sim_step, float* d_eePos, int32_t* d_done, uint32_t batch, void* stream) {
+    return simulate_clk_impl<float>(h, "mpcg_simulate_clk", plant, control_size, d_xs, d_xu, timestep, d_time_offset_us, d_sim_time_us, sim_step, d_eePos, d_done, batch,
+                                    stream);
+}
+
+int mpcg_simulate_clk_f64(mpcg_handle* h, const mpcg_plant* plant, uint32_t control_size, double* d_xs, const double* d_xu, double timestep,
+                          const double* d_time_offset_us, const double* d_sim_time_us, double sim_step, double* d_eePos, int32_t* d_done, uint32_t batch, void* stream) {
+    return simulate_clk_impl<double>(h, "mpcg_simulate_clk_f64", plant, control_size, d_xs, d_xu, timestep, d_time_offset_us, d_sim_time_us, sim_step, d_eePos, d_done,
+                                     batch, stream);
+}
+
+int mpcg_advance_horizon_clk(mpcg_handle* h, uint32_t control_size, float* d_xu, float* d_lambda, float* d_eePos_goal, const float* d_xs, const float* d_eePos,
+                             const float* d_xu_traj, const float* d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride, uint32_t xu_fill_lead,
+                             int32_t* d_traj_offset, int32_t* d_done, float* d_tracking_error, double timestep, double shift_threshold_s, const double* d_sim_time_us,
+                             double* d_prev_sim_us, double* d_since_s, int32_t* d_shifted, int32_t* d_did_shift, uint32_t batch, void* stream) {
+    return advance_horizon_clk_impl<float>(h, "mpcg_advance_horizon_clk", control_size, d_xu, d_lambda, d_eePos_goal, d_xs, d_eePos, d_xu_traj, d_eePos_traj, traj_steps,
+                                           traj_batch_stride, xu_fill_lead, d_traj_offset, d_done, d_tracking_error, timestep, shift_threshold_s, d_sim_time_us,
+                                           d_prev_sim_us, d_since_s, d_shifted, d_did_shift, batch, stream);
+}
+
+int mpcg_advance_horizon_clk_f64(mpcg_handle* h, uint32_t control_size, double* d_xu, double* d_lambda, double* d_eePos_goal, const double* d_xs, const double* d_eePos,
+                                 const double* d_xu_traj, const double* d_eePos_traj, uint32_t traj_steps, uint32_t traj_batch_stride, uint32_t xu_fill_lead,
+                                 int32_t* d_traj_offset, int32_t* d_done, double* d_tracking_error, double timestep, double shift_threshold_s,
+                                 const double* d_sim_time_us, double* d_prev_sim_us, double* d_since_s, int32_t* d_shifted, int32_t* d_did_shift, uint32_t batch,
+                                 void* stream) {
+    return advance_horizon_clk_impl<double>(h, "mpcg_advance_horizon_clk_f64", control_size, d_xu, d_lambda, d_eePos_goal, d_xs, d_eePos, d_xu_traj, d_eePos_traj,
+                                            traj_steps, traj_batch_stride, xu_fill_lead, d_traj_offset, d_done, d_tracking_error, timestep, shift_threshold_s,
+                                            d_sim_time_us, d_prev_sim_us, d_since_s, d_shifted, d_did_shift, batch, stream);
 }
 
 }  // extern "C"

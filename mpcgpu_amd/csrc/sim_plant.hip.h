@@ -24,6 +24,15 @@
 // advance_horizon_kernel<IO>.  One workgroup per trajectory; every value that moves is LOADED, then a barrier, then stored (the source and destination
 // regions of a shift overlap by one knot).  See include/mpcg.h for the order of operations.
 //
+// CLOCK = 1 (mpcg_simulate_clk, mpcg_simulate_clk_f64): the time offset and the simulated time are device arrays, one pair per trajectory, and the host's
+// part of the schedule — toff = t 1e-6, sim = t 1e-6, S = (uint32)(sim / ss), rem = (double)(IO)fmod(sim, ss) — is evaluated by every group for its own
+// trajectory, one rounding per operation (fmod is exact: the host's bits).  The substep loop has barriers and a wavefront holds four trajectories, so its
+// trip count is the largest of its four groups' round counts (a wave-level maximum; no LDS): A WAVEFRONT TAKES AS LONG AS ITS LONGEST TRAJECTORY.  Each group
+// predicates its own work on its own S, rem, idx and dt: it steps while k < steps, runs the pose sweeps in round k == steps and idles after that, writing
+// nothing to its LDS records, so the pose records survive to the final read.  A trajectory whose done flag is set on entry, or whose times are no schedule
+// (non-finite, negative, sim / ss >= 65537), has no rounds and stores nothing but — the latter — done = MPCG_DONE_BAD_CLOCK.  Read in `if constexpr` only.
+// advance_horizon_clk_kernel<IO> is advance_horizon_kernel with the shift decided per trajectory from clock state in device memory (mpcsim.cuh:294-352).
+//
 // The double twins (mpcg_simulate_f64, mpcg_advance_horizon_f64; linsys_t = double) are the same two templates with IO = double.  simulate_kernel<double> uses
 // d_xs and the controls as they are and stores the float64 state and end-effector position without a rounding; its remainder is fmod(sim, ss) as a double (the host's part of
 // the schedule: mpcg_plant.hip).  advance_horizon_kernel<double> sweeps chunks of the same number of ELEMENTS and forms the tracking error in double.
@@ -107,13 +116,22 @@ template <typename IO> struct SimArgsT {
     double ss, toff, timestep;           // substep, time offset, knot spacing [s]
     double rem;                          // the remainder substep, (double)(IO)fmod(sim, ss): rounded to float, or fmod's value as a double; 0: none
 };
+// CLOCK = 1: S, toff and rem above are not read; every trajectory forms its own from these
+template <typename IO> struct SimClkArgsT : SimArgsT<IO> {
+    const double* toff_us; const double* sim_us;     // [batch]
+    int32_t* done;                       // [batch] in/out or NULL
+};
+template <typename IO, int CLOCK> struct SimArgsOf { typedef SimArgsT<IO> type; };
+template <typename IO> struct SimArgsOf<IO, 1> { typedef SimClkArgsT<IO> type; };
+constexpr int SIM_DONE_BAD_CLOCK = 2;            // MPCG_DONE_BAD_CLOCK
 
 // The arithmetic between load and store is float64 for either IO: only the loads (widened, or used as they are) and the stores (rounded once, or not at all)
 // depend on it.  INTEGRATOR: 0 explicit, 1 semi-implicit Euler ("sim_integrator").  (As for the KKT and merit kernels, a shared __device__ body was tried and changed the code.)
 // SATURATE = 1 (a plant whose limits carry MPCG_LIMITS_SIM_SATURATE): every control applied is clamped to the plant's [u_lo, u_hi] where it is loaded and widened
 // — the actuator saturates; a NaN passes.  Read in `if constexpr` only: SATURATE = 0 is the kernel it was.
-template <typename IO, int INTEGRATOR = 0, int SATURATE = 0>
-__global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgsT<IO> a) {
+// CLOCK = 1: per-trajectory times (the head of this file).  Read in `if constexpr` only: CLOCK = 0 is the kernel it was.
+template <typename IO, int INTEGRATOR = 0, int SATURATE = 0, int CLOCK = 0>
+__global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(typename SimArgsOf<IO, CLOCK>::type a) {
     typedef double R;
     typedef KktLds<R>::vr kkt_lds_vd;
     typedef KktLds<R>::item kkt_lds_item;
@@ -138,13 +156,41 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgsT<IO> a
         return v >= (double)last ? last : (unsigned)v;
     };
     if (l < n) I->Xq[l] = (double)xs[l];
-    unsigned idx = knot_of(a.toff);
-    const unsigned steps = a.S + (a.rem != 0.0 ? 1u : 0u), rounds = steps + (a.eePos ? 1u : 0u);
+    double toff = a.toff, rem = a.rem;                       // CLOCK = 1: this group's own schedule, and `own` rounds of the wavefront's `rounds`
+    unsigned S = a.S, own = 0;
+    bool active = live;                                      // CLOCK = 1: ... and not frozen, and with times that are a schedule
+    if constexpr (CLOCK == 1) {
+#pragma clang fp contract(off)                               // the host's part of the schedule: products the substep loop's sums must not fuse with
+        static_assert(KKT_THREADS == 64 && KKT_GL == 16, "the wave-level maximum below: four groups of 16 lanes");
+        const double tu = a.toff_us[b], su = a.sim_us[b];
+        toff = tu * 1e-6;                                    // (plain operators: the __d*_rn wrappers carry their header's contraction)
+        const double sim = su * 1e-6, full = sim / a.ss;
+        const bool valid = tu >= 0.0 && su >= 0.0 && tu < INFINITY && su < INFINITY && full < (double)SIM_MAX_SUBSTEPS + 1.0;      // (a NaN fails every comparison)
+        const bool frozen = a.done && a.done[b] != 0;
+        active = live && !frozen && valid;
+        S = active ? (unsigned)full : 0u;
+        rem = active ? (double)(IO)fmod(sim, a.ss) : 0.0;
+        if (live && !frozen && !valid && a.done && l == 0) a.done[b] = SIM_DONE_BAD_CLOCK;
+    }
+    unsigned idx = knot_of(toff);
+    const unsigned steps = S + (rem != 0.0 ? 1u : 0u);
+    unsigned rounds = steps + (a.eePos ? 1u : 0u);
+    if constexpr (CLOCK == 1) {
+        own = active ? rounds : 0u;
+        rounds = own;
+        const unsigned r16 = (unsigned)__shfl_xor((int)rounds, 16);
+        rounds = r16 > rounds ? r16 : rounds;
+        const unsigned r32 = (unsigned)__shfl_xor((int)rounds, 32);
+        rounds = r32 > rounds ? r32 : rounds;
+        rounds = (unsigned)__builtin_amdgcn_readfirstlane((int)rounds);
+    }
     for (unsigned k = 0; k < rounds; ++k) {
         const bool step = k < steps;                         // the last round of a call with an end-effector output: the pose sweeps on the final state
-        double dt = a.rem;
-        if (k < a.S) { idx = knot_of(__dadd_rn(a.toff, __dmul_rn((double)k, a.ss))); dt = a.ss; }
-        if (l < m) {
+        bool busy = true;                                    // CLOCK = 1: a group behind its own last round idles and writes nothing to its records
+        if constexpr (CLOCK == 1) busy = k < own;
+        double dt = rem;
+        if (k < S) { idx = knot_of(__dadd_rn(toff, __dmul_rn((double)k, a.ss))); dt = a.ss; }
+        if (l < m && busy) {
             if constexpr (SATURATE == 1) {
                 if (step) {
                     const double u = (double)xu[(size_t)idx * (n + m) + n + l], lo = P.ulo()[l], hi = P.uhi()[l];
@@ -159,7 +205,7 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgsT<IO> a
         }
         __syncthreads();
         // ---- round 0 of the KKT kernel: lanes 0..6 ID(q, 0, e_l), lane 7 ID(q, qd, 0); in the pose round lanes 8..10 instead ----
-        if (l < KKT_R0 && (step ? l <= PJ : l > PJ)) {
+        if (l < KKT_R0 && busy && (step ? l <= PJ : l > PJ)) {
             R a6w[3], a6u[3];
             RneaTask<R> t;
             t.sj = -1; t.pj = -1; t.qdscale = (l == PJ) ? 1.0 : 0.0; t.knot_qdd = false; t.unit = l < PJ ? l : -1; t.base = l > PJ ? l - PJ - 1 : -1;
@@ -182,12 +228,12 @@ __global__ __launch_bounds__(KKT_THREADS, 2) void simulate_kernel(SimArgsT<IO> a
         }
         __syncthreads();
     }
-    if (a.eePos && live && l < 3) {
+    if (a.eePos && active && l < 3) {
         R ee0, ee1, ee2;
         plant_ee_pos(recs, ee0, ee1, ee2);
         a.eePos[b * 3 + l] = (IO)(l == 0 ? ee0 : (l == 1 ? ee1 : ee2));
     }
-    if (live && l < n) xs[l] = (IO)I->Xq[l];                // IO = float: the one rounding of the call; IO = double: the state as it is
+    if (active && l < n) xs[l] = (IO)I->Xq[l];              // IO = float: the one rounding of the call; IO = double: the state as it is
 }
 
 template <typename IO> struct AdvanceArgsT {                // IO = float: mpcg_advance_horizon; IO = double: mpcg_advance_horizon_f64
@@ -265,6 +311,86 @@ __global__ __launch_bounds__(ADV_THREADS) void advance_horizon_kernel(AdvanceArg
         a.tracking_error[b] = err;
         a.traj_offset[b] = (int32_t)off;
         if (off >= a.traj_steps) a.done[b] = 1;              // (:252)
+    }
+}
+
+// mpcg_advance_horizon_clk(_f64): the clock bookkeeping of mpcsim.cuh:294-352 per trajectory, in double with one rounding per operation, around what
+// advance_horizon_kernel does to the trajectory with the shift it decides.  a.shift is not read; a.done is required.  The copies are that kernel's,
+// restated: with the shift lifted into a function of both, advance_horizon_kernel kept its 1,171 / 1,210 instructions but not their order
+// (tools/_prof/diff_kernels.py), and no existing kernel may change.
+template <typename IO> struct AdvanceClkArgsT : AdvanceArgsT<IO> {
+    double timestep, threshold;                             // knot spacing and SHIFT_THRESHOLD [s]
+    const double* sim_us;                                   // [batch]
+    double* prev_us; double* since; int32_t* shifted;       // [batch] in/out: prev_simulation_time [us], time_since_timestep [s], shifted
+    int32_t* did_shift;                                     // [batch] out or NULL
+};
+constexpr int ADV_DONE_BAD_CLOCK = 2;                       // MPCG_DONE_BAD_CLOCK
+
+template <typename IO>
+__global__ __launch_bounds__(ADV_THREADS) void advance_horizon_clk_kernel(AdvanceClkArgsT<IO> a) {
+#pragma clang fp contract(off)                              // since + t 1e-6 is a product rounded, then a sum rounded: under this file's contract(fast) it became one fma
+    const size_t b = blockIdx.x;
+    const uint32_t t = threadIdx.x;
+    // every thread reads the flags and the clock, then a barrier: thread 0 writes them at the end, and no thread may decide on the new values
+    const int32_t done = a.done[b];
+    const double su = a.sim_us[b];
+    const bool bad = !(su >= 0.0 && su < INFINITY);         // negative, infinite or NaN
+    const double su_s = su * 1e-6;
+    double since = a.since[b] + su_s;                       // (:294; plain operators: the __d*_rn wrappers carry their header's contraction)
+    int32_t shifted = a.shifted[b];
+    __syncthreads();
+    if (done != 0) {                                        // frozen: the clock too
+        if (t == 0 && a.did_shift) a.did_shift[b] = 0;
+        return;
+    }
+    if (bad) {
+        if (t == 0) a.done[b] = ADV_DONE_BAD_CLOCK;
+        return;
+    }
+    const bool shift = shifted == 0 && since > a.threshold;             // (:296)
+    const uint32_t n = a.n, m = a.m, N = a.N, nm = n + m;
+    const size_t len = (size_t)nm * N - m;
+    IO* xu = a.xu + b * len;
+    const IO* xs = a.xs + b * n;
+    if (!shift) {                                           // (:348 alone)
+        for (uint32_t e = t; e < n; e += ADV_THREADS) xu[e] = xs[e];
+    } else {                                                // advance_horizon_kernel's shift, restated: shared as a function, that kernel compiled to other code
+        IO* lam = a.lambda + b * (size_t)n * N;
+        IO* goal = a.goal + b * (size_t)6 * N;
+        const IO* xut = a.xu_traj + b * (size_t)a.traj_stride * nm;
+        const IO* gt = a.goal_traj + b * (size_t)a.traj_stride * 6;
+        const uint32_t off = (uint32_t)a.traj_offset[b] + 1;     // (:310; a value that is no row of the plan takes the else branch and reads the plan's last row)
+        const bool inside = off >= 1 && (uint64_t)off + N < a.traj_steps;    // (:314, :327)
+        IO err = 0;
+        if (t == 0) err = tracking_error_of(a.eePos + b * 3, goal);          // (:303-306) against knot 0 of the unshifted goals
+        // xu: x_0 from xs (:348, the last write of the reference); everything else below the last n + m elements from one knot up (just_shift: knots
+        // 0..N-3 whole, x_{N-2} <- x_{N-1} without a control, integrator.cuh:258-263); the last n + m elements u_{N-2}, x_{N-1} from the plan (:316) or
+        // the final plan position with zero velocity and zero control (:320-322).
+        advance_sweep(xu, len, [&](size_t e) -> IO {
+            if (e < n) return xs[e];
+            if (e + nm < len) return xu[e + nm];
+            const uint32_t r = (uint32_t)(e + nm - len);         // 0..m-1: u_{N-2}; m..m+n-1: x_{N-1}
+            if (inside) return xut[(size_t)nm * (off + a.lead) - m + r];
+            return r >= m && r - m < n / 2 ? xut[(size_t)(a.traj_steps - 1) * nm + (r - m)] : IO(0);
+        });
+        advance_sweep(goal, (size_t)6 * N, [&](size_t e) -> IO {         // (:326-334)
+            if (e + 6 < (size_t)6 * N) return goal[e + 6];
+            return gt[(size_t)(inside ? off + N - 1 : a.traj_steps - 1) * 6 + (e + 6 - (size_t)6 * N)];
+        });
+        advance_sweep(lam, (size_t)n * (N - 1), [&](size_t e) -> IO { return lam[e + n]; });         // the last knot of lambda keeps its value (:337-338)
+        if (t == 0) {
+            a.tracking_error[b] = err;
+            a.traj_offset[b] = (int32_t)off;
+            if (off >= a.traj_steps) a.done[b] = 1;              // (:252)
+        }
+    }
+    if (t == 0) {
+        if (shift) shifted = 1;                             // (:340)
+        if (since > a.timestep) { shifted = 0; since = fmod(since, a.timestep); }      // (:343-347; fmod is exact)
+        a.since[b] = since;
+        a.shifted[b] = shifted;
+        a.prev_us[b] = su;                                  // (:352)
+        if (a.did_shift) a.did_shift[b] = shift ? 1 : 0;
     }
 }
 

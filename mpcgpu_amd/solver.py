@@ -171,6 +171,17 @@ class XuRef:
     traj_steps: int | None = None
 
 
+class Clocks:
+    """The clock state of B trajectories of an MPC loop on the device (include/mpcsim.cuh:280-352, per trajectory): prev_sim_us (float64 [B],
+    prev_simulation_time — what simulate_clk takes as its time offsets), since_s (float64 [B], time_since_timestep) and shifted (int32 [B]).
+    A new loop starts from zeros; advance_horizon_clk updates all three in place."""
+
+    def __init__(self, B: int, device="cuda"):
+        self.prev_sim_us = torch.zeros(B, dtype=torch.float64, device=device)
+        self.since_s = torch.zeros(B, dtype=torch.float64, device=device)
+        self.shifted = torch.zeros(B, dtype=torch.int32, device=device)
+
+
 class QdldlSolver:
     """The reference's LINSYS_SOLVE == 0 path (include/qdldl/sqp.cuh) as a selectable solver: CSR lower-triangle pattern
     (include/utils/csr.cuh:40-73) + elimination tree once, then numeric LDL^T factor + solve per call on the HOST
@@ -661,6 +672,56 @@ class PcgSolver:
         self._check(fn(self._h, m, 1 if shift else 0, _ptr(xu), _ptr(lam), _ptr(eePos_goal), _ptr(xs), _ptr(eePos),
                        _ptr(xu_traj), _ptr(eePos_traj), T, stride, int(xu_fill_lead), _ptr(traj_offset), _ptr(done),
                        _ptr(tracking_error), B, _stream()))
+        return xu
+
+    def simulate_clk(self, plant: "Plant", xs, xu, timestep: float, time_offset_us, sim_time_us, sim_step: float = 2e-4, eePos=None, done=None,
+                     control_size: int | None = None):
+        """simulate with the times on the device: time_offset_us and sim_time_us are float64 [B] tensors, and trajectory b gets what simulate gives it
+        with its own pair, bit for bit.  done (optional, int32 [B]): a trajectory with done != 0 is frozen (nothing of it is written); one whose times
+        are no schedule (non-finite, negative, more than MPCG_SIM_MAX_SUBSTEPS substeps) is not simulated and gets done = MPCG_DONE_BAD_CLOCK.
+        A loop passes Clocks.prev_sim_us as time_offset_us.  float32 tensors: mpcg_simulate_clk; float64: mpcg_simulate_clk_f64.  Mixed dtypes raise TypeError."""
+        B = xs.shape[0] if xs.dim() > 1 else 1
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        dt = self._one_dtype("simulate_clk", xs, xu, eePos)
+        self._chk(xs, B * n, dt, "xs")
+        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
+        self._chk(time_offset_us, B, torch.float64, "time_offset_us")
+        self._chk(sim_time_us, B, torch.float64, "sim_time_us")
+        if eePos is not None:
+            self._chk(eePos, B * 3, dt, "eePos")
+        if done is not None:
+            self._chk(done, B, torch.int32, "done")
+        fn = self.lib.mpcg_simulate_clk if dt == torch.float32 else self.lib.mpcg_simulate_clk_f64
+        self._check(fn(self._h, plant._p, m, _ptr(xs), _ptr(xu), float(timestep), _ptr(time_offset_us), _ptr(sim_time_us), float(sim_step), _ptr(eePos),
+                       _ptr(done), B, _stream()))
+        return xs
+
+    def advance_horizon_clk(self, xu, xs, lam, eePos_goal, eePos, xu_traj, eePos_traj, traj_offset, done, tracking_error, timestep: float, sim_time_us,
+                            clocks: Clocks, did_shift=None, shift_threshold_s: float | None = None, xu_fill_lead: int = 0, control_size: int | None = None):
+        """advance_horizon with the shift decided per trajectory on the device from `clocks` (include/mpcsim.cuh:294-352): since += sim_time_us * 1e-6;
+        a trajectory shifts when it has not yet shifted in this timestep and since > shift_threshold_s (default: the reference's, one timestep rounded
+        to the tensors' dtype); since wraps at the timestep; prev_sim_us = sim_time_us.  sim_time_us: float64 [B]; did_shift (optional, int32 [B])
+        receives the decisions.  A frozen trajectory keeps its clock; a non-finite or negative time sets done = MPCG_DONE_BAD_CLOCK.  Every array of
+        advance_horizon(shift=True) is required.  float32 tensors: mpcg_advance_horizon_clk; float64: mpcg_advance_horizon_clk_f64.  Mixed dtypes raise TypeError."""
+        B = xs.shape[0] if xs.dim() > 1 else 1
+        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        dt = self._one_dtype("advance_horizon_clk", xu, xs, lam, eePos_goal, eePos, xu_traj, eePos_traj, tracking_error)
+        per_traj = xu_traj.dim() == 3
+        T = int(xu_traj.shape[-2])
+        for t, count, name in ((xu, B * ((n + m) * N - m), "xu"), (xs, B * n, "xs"), (lam, B * n * N, "lam"), (eePos_goal, B * 6 * N, "eePos_goal"),
+                               (eePos, B * 3, "eePos"), (xu_traj, (B if per_traj else 1) * T * (n + m), "xu_traj"),
+                               (eePos_traj, (B if per_traj else 1) * T * 6, "eePos_traj"), (tracking_error, B, "tracking_error")):
+            self._chk(t, count, dt, name)
+        for t, name in ((traj_offset, "traj_offset"), (done, "done"), (clocks.shifted, "clocks.shifted")) + (((did_shift, "did_shift"),) if did_shift is not None else ()):
+            self._chk(t, B, torch.int32, name)
+        for t, name in ((sim_time_us, "sim_time_us"), (clocks.prev_sim_us, "clocks.prev_sim_us"), (clocks.since_s, "clocks.since_s")):
+            self._chk(t, B, torch.float64, name)
+        if shift_threshold_s is None:
+            shift_threshold_s = float(torch.tensor(1 * timestep, dtype=dt))
+        fn = self.lib.mpcg_advance_horizon_clk if dt == torch.float32 else self.lib.mpcg_advance_horizon_clk_f64
+        self._check(fn(self._h, m, _ptr(xu), _ptr(lam), _ptr(eePos_goal), _ptr(xs), _ptr(eePos), _ptr(xu_traj), _ptr(eePos_traj), T, T if per_traj else 0,
+                       int(xu_fill_lead), _ptr(traj_offset), _ptr(done), _ptr(tracking_error), float(timestep), float(shift_threshold_s), _ptr(sim_time_us),
+                       _ptr(clocks.prev_sim_us), _ptr(clocks.since_s), _ptr(clocks.shifted), _ptr(did_shift), B, _stream()))
         return xu
 
     def csr_nnz(self) -> int:
