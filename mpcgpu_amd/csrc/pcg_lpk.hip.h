@@ -34,8 +34,12 @@
 // both factors of both terms in registers.
 //
 // Reads only the left + diagonal block columns (include/mpcg.h, BLOCK SYMMETRY), like the lane-per-block kernel.
+//
+// What runs BETWEEN the passes — setup, alpha, lambda update, beta, the exit rule, per role — is lxk_role (pcg_lxk_driver.hip.h), shared with the
+// double kernel pcg_lqk_f64_kernel; this file brings the pass (lpk_half), the lane helpers, the barrier and the reduction.
 #pragma once
 #include "pcg_kernels.hip.h"
+#include "pcg_lxk_driver.hip.h"
 
 #ifndef LPK_STAGED_LOAD
 #define LPK_STAGED_LOAD 1      // matrix registers filled through the LDS stage (lpk_load_blocks_lds); 0: lane-private loads (lpk_load_blocks)
@@ -291,6 +295,14 @@ __device__ __forceinline__ float lpk_wave_fold(float part) {
 struct LpkOwn { f2 v[4]; };
 struct LpkVec { LpkOwn k, m; };                                // a lane's copy of a vector: its own row pairs of knot k and of knot k-1
 struct LpkFetch { f2 t[4], z[4], gt[4], gz[4]; };
+struct LpkTypes {                                              // what the shared CG driver (pcg_lxk_driver.hip.h) needs to know about float
+    typedef float real;
+    typedef LpkOwn Own;
+    typedef LpkVec Vec;
+    typedef LpkFetch Fetch;
+    __device__ static __forceinline__ float uniform(float v) { return mpcg::uniform(v); }
+    __device__ static __forceinline__ float abs(float v) { return fabsf(v); }
+};
 // own entries (register slots 0..3) of knot k + dk of the vector at float offset X
 template <int K2>
 __device__ __forceinline__ LpkOwn lpk_load_own(const float* lds, int bA, int b0, int X, int dk) {
@@ -565,8 +577,9 @@ __global__ __launch_bounds__(NWR ? NWR * 256 : 128, 2) void pcg_lpk_kernel(PcgAr
     auto fetch = [&](int T, int Z) -> Fetch { return lpk_fetch<K2>(lds, bA, b0, T, Z); };
     // One half-iteration of this wave's matrix (lpk_half): every lane stores its z to ZOUT and its merged rows to TOUT, the wave's share of
     // x^T M x goes to red[wl].  pb: stamp numbers of the -DMPCG_PROF build.
-    auto half = [&](auto mode_tag, const Fetch& f, const Vec& old, float c, int TOUT, int ZOUT, float* red, auto pb_tag) -> Vec {
-        [[maybe_unused]] constexpr int pb = decltype(pb_tag)::value;
+    auto half = [&](auto mode_tag, auto phase, const Fetch& f, const Vec& old, float c, int TOUT, int ZOUT) -> Vec {
+        [[maybe_unused]] constexpr int pb = decltype(phase)::value ? 8 : 0;
+        float* const red = decltype(phase)::value ? red_e : red_v;
         MPCG_STAMP(pb + 0);
         const Vec x = lpk_half<decltype(mode_tag)::value, L, NTHR, pb>(Md, Ml, park, h, hasL, f, old, c,
             [&](const f2 (&z2)[3], float z6) {                   // z belongs to knot k-1's vector: entries of this lane's columns
@@ -580,80 +593,28 @@ __global__ __launch_bounds__(NWR ? NWR * 256 : 128, 2) void pcg_lpk_kernel(PcgAr
         MPCG_STAMP(pb + 4);
         return x;
     };
-    using Pb0 = std::integral_constant<int, 0>;
-    using Pb8 = std::integral_constant<int, 8>;
-
-    // The S waves and the Pinv waves run the same barrier sequence through two SEPARATE code paths (the role is wave-uniform).
+    // the synchronisation point behind a half and the reduction read behind it (pcg_lxk_driver.hip.h)
+    auto arrive = [&](auto role, auto phase) {
+        MPCG_STAMP(!decltype(phase)::value ? 5 : decltype(role)::value ? 14 : 7);
+        lds_barrier();
+        MPCG_STAMP(decltype(phase)::value ? 15 : 6);
+    };
+    auto value = [&](auto phase) -> float {
+        if constexpr (decltype(phase)::value) return uniform(sum_red(red_e)); else return sum_red(red_v);
+    };
     uint32_t iters = 0;
     uint32_t max_iter_exit = 1;
     float beta = 0.f;                                          // scalar of the NEXT p update (the S half applies it)
     bool p_pending = true;                                     // that update has not been applied to p (write-back of d_p does it)
-    auto run_role = [&](auto role_tag) {
-        constexpr bool P = decltype(role_tag)::value;
-        // ---- setup: r = gamma - S lambda0 ; r~ = Pinv r ; eta = r . r~   (p = r~ is formed by the first S half: beta = 0) ----
-        Fetch f;
-        Vec x;                                                   // S waves: p;  Pinv waves: r
-        x.k = load_own(P ? L::R0 : L::P0, 0);
-        x.m = load_own(P ? L::R0 : L::P0, -1);
-        if constexpr (!P) (void)half(std::integral_constant<int, 0>{}, f, x, 0.f, L::US, L::ZS, red_v, Pb0{});
-        lds_barrier();
-        if constexpr (P) {
-            f = fetch(L::US, L::ZS);
-            x = half(std::integral_constant<int, 1>{}, f, x, 1.f, L::RT, L::ZP, red_e, Pb8{});
-        }
-        lds_barrier();
-        if constexpr (!P) f = fetch(L::RT, L::ZP);
-        float eta = uniform(sum_red(red_e));
-        // every matrix load has been consumed on the waves that ran a setup pass; say so, or the compiler keeps vmcnt waits inside the loop
-        __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0)
-        if (fabsf(eta) < a.exit_tol) {
-            max_iter_exit = 0;
-        } else {
-            for (int it = 0; it < a.max_iter; ++it) {
+    const LxkCg<float> cg{iters, max_iter_exit, beta, p_pending};
+    auto more = [&](int it) {
 #ifdef MPCG_PROF
-                prof_on = b == 0 && it == 20;
+        if (it < a.max_iter) prof_on = b == 0 && it == 20;     // (armed at the top of an iteration that runs, not at the exit check)
 #endif
-                if constexpr (!P) {
-                    // p = r~ + beta p ; upsilon = S p ; v = p . upsilon
-                    x = half(std::integral_constant<int, 2>{}, f, x, beta, L::US, L::ZS, red_v, Pb0{});
-                    MPCG_STAMP(5);
-                    lds_barrier();
-                    MPCG_STAMP(6);
-                    // alpha = eta / v ; lambda += alpha p (own entries) — while the Pinv half runs
-                    const Own cur = load_own(L::LAM, 0);
-                    const float alpha = uniform(eta / sum_red(red_v));
-                    Own nw;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) nw.v[s] = cur.v[s] + alpha * x.k.v[s];
-                    store_own(L::LAM, nw);
-                    MPCG_STAMP(7);
-                    lds_barrier();
-                    MPCG_STAMP(15);
-                    f = fetch(L::RT, L::ZP);                    // the next S half's operand loads fly during the scalar chain below
-                } else {
-                    MPCG_STAMP(5);
-                    lds_barrier();
-                    MPCG_STAMP(6);
-                    // alpha = eta / v ; r -= alpha upsilon ; r~ = Pinv r ; eta' = r . r~
-                    f = fetch(L::US, L::ZS);
-                    const float alpha = uniform(eta / sum_red(red_v));
-                    x = half(std::integral_constant<int, 1>{}, f, x, alpha, L::RT, L::ZP, red_e, Pb8{});
-                    MPCG_STAMP(14);
-                    lds_barrier();
-                    MPCG_STAMP(15);
-                }
-                // eta' ; exit test ; beta
-                const float eta_new = uniform(sum_red(red_e));
-                iters = (uint32_t)(it + 1);
-                if (fabsf(eta_new) < a.exit_tol) { max_iter_exit = 0; p_pending = false; break; }     // (the reference leaves p as it is on this exit)
-                beta = uniform(eta_new / eta);
-                eta = eta_new;
-            }
-        }
-        // the vector this role carries, for d_p / d_r (the staging buffers are free since the setup)
-        store_own(P ? L::R0 : L::P0, x.k);
+        return it < a.max_iter;
     };
-    if (isP) run_role(std::true_type{}); else run_role(std::false_type{});
+    if (isP) lxk_role<true, L, LpkTypes>(a, cg, load_own, store_own, fetch, half, arrive, value, more);
+    else lxk_role<false, L, LpkTypes>(a, cg, load_own, store_own, fetch, half, arrive, value, more);
 
     // ---- write back ----
     lds_barrier();

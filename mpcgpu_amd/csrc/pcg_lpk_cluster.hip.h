@@ -16,6 +16,8 @@
 // matrix that sits the pass out, which therefore starts polling while the pass still runs; it drops the neighbours' vectors into the halo
 // slots of the local T / Z vectors (slot 0 and slot KL + 1), folds the partials, and ONE barrier ends the exchange.  Two hand-offs and two
 // barriers per PCG iteration, nothing else: no part vectors, no element-wise phases (the retired kernel: two hand-offs and four barriers).
+// The recurrence between the passes (run_role) is the single-CU kernels' lxk_role (pcg_lxk_driver.hip.h) with a hand-off where that has a barrier,
+// plus the failure exits; it is this kernel's own copy (profiles/lxk_driver_same_code.txt §3: under the driver, same opcode counts, other text).
 #pragma once
 #include "pcg_lpk.hip.h"
 #include "pcg_cluster.hip.h"
@@ -316,7 +318,7 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lpkc_kernel(ClusterArgs ca) 
         uint32_t max_iter_exit = 1;
         float beta = 0.f;
         bool p_pending = true;
-        // the S waves and the Pinv waves run the same hand-off / barrier sequence through two separate code paths (pcg_lpk_kernel)
+        // the S waves and the Pinv waves run the same hand-off / barrier sequence through two separate code paths (lxk_role's recurrence: file header)
         auto run_role = [&](auto role_tag) {
             constexpr bool P = decltype(role_tag)::value;
             const bool poll_s = P && w == NWM, poll_p = !P && w == 0;      // poller of the S half: first Pinv wave; of the Pinv half: wave 0

@@ -12,6 +12,8 @@
 //     queue, bounded spins + completion counts + a fix-up launch that warm-starts from the handle's copy of lambda0.
 // N = 128: two CUs per trajectory (the clustered row-per-lane kernel needs four, with twice the hand-off partners).  Reads only the left +
 // diagonal block columns: launched when the handle's latch says block-symmetric.
+// The recurrence between the passes (run_role) is the single-CU kernels' lxk_role (pcg_lxk_driver.hip.h) with a hand-off where that has a barrier,
+// plus the failure exits; it is this kernel's own copy (profiles/lxk_driver_same_code.txt §3: under the driver, same opcode counts, other text).
 #pragma once
 #include "pcg_lqk_f64.hip.h"
 #include "pcg_cluster.hip.h"

@@ -19,9 +19,11 @@
 // Reads only the left + diagonal block columns (include/mpcg.h, BLOCK SYMMETRY): launched when the handle's latch says symmetric.
 // Same PCG, same exit rule, same outputs as every other kernel; results agree with the oracle's double instantiation to the round-off of the
 // different summation order (tests: 1e-9 of the iterate after fixed iteration counts).
+// The recurrence between the passes is the float kernel's, literally: lxk_role (pcg_lxk_driver.hip.h).
 #pragma once
 #include "pcg_f64.hip.h"
 #include "pcg_rpl.hip.h"
+#include "pcg_lxk_driver.hip.h"
 
 namespace mpcg {
 
@@ -105,6 +107,14 @@ __device__ __forceinline__ void lqk_load_blocks(rsrc_t M, int k, int h, int g, b
 struct LqkOwn { double v[4]; };
 struct LqkVec { LqkOwn k, m; };                                // a lane's copy of a vector: its own entries of knot k and of knot k-1
 struct LqkFetch { double t[4], z[4], gt[4], gz[4]; };
+struct LqkTypes {                                              // what the shared CG driver (pcg_lxk_driver.hip.h) needs to know about double
+    typedef double real;
+    typedef LqkOwn Own;
+    typedef LqkVec Vec;
+    typedef LqkFetch Fetch;
+    __device__ static __forceinline__ double uniform(double v) { return lqk_uniform(v); }
+    __device__ static __forceinline__ double abs(double v) { return fabs(v); }
+};
 // own entries (register slots 0..3, this lane's row of each pair) of knot k + dk of the vector at double offset X
 template <int K2>
 __device__ __forceinline__ LqkOwn lqk_load_own(const double* lds, int bA, int b0, int X, int dk) {
@@ -340,7 +350,8 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqk_f64_kernel(PcgArgs64 a) 
     auto store_own = [&](int X, const Own& o) { lqk_store_own<K2>(lds, bA, b0, X, o); };
     auto fetch = [&](int T, int Z) -> Fetch { return lqk_fetch<K2>(lds, bA, b0, T, Z); };
     // One half-iteration of this wave's matrix (lqk_half): every lane stores its z and its rows, the wave's partial goes to red[wl]
-    auto half = [&](auto mode_tag, const Fetch& f, const Vec& old, real c, int TOUT, int ZOUT, real* red) -> Vec {
+    auto half = [&](auto mode_tag, auto phase, const Fetch& f, const Vec& old, real c, int TOUT, int ZOUT) -> Vec {
+        real* const red = decltype(phase)::value ? red_e : red_v;
         return lqk_half<decltype(mode_tag)::value, L, NTHR>(Md, Ml, park, h, g, hasL, f, old, c,
             [&](const real (&z)[7]) {                            // column j = (slot j >> 1, element j & 1) — this lane stores element g
                 real* zo = lds + ZOUT;
@@ -351,66 +362,19 @@ __global__ __launch_bounds__(NWR * 256, 2) void pcg_lqk_f64_kernel(PcgArgs64 a) 
             [&](const Own& o) { store_own(TOUT, o); },
             [&](real part) { if (lane == 0) red[wl] = part; });
     };
-
-    // The S waves and the Pinv waves run the same barrier sequence through two SEPARATE code paths (the role is wave-uniform).
+    // the synchronisation point behind a half and the reduction read behind it (pcg_lxk_driver.hip.h)
+    auto arrive = [&](auto, auto) { lds_barrier(); };
+    auto value = [&](auto phase) -> real {
+        if constexpr (decltype(phase)::value) return lqk_uniform(sum_red(red_e)); else return sum_red(red_v);
+    };
     uint32_t iters = 0;
     uint32_t max_iter_exit = 1;
     real beta = real(0);                                       // scalar of the NEXT p update (the S half applies it)
     bool p_pending = true;                                     // that update has not been applied to p (write-back of d_p does it)
-    auto run_role = [&](auto role_tag) {
-        constexpr bool P = decltype(role_tag)::value;
-        // ---- setup: r = gamma - S lambda0 ; r~ = Pinv r ; eta = r . r~   (p = r~ is formed by the first S half: beta = 0) ----
-        Fetch f;
-        Vec x;                                                   // S waves: p;  Pinv waves: r
-        x.k = load_own(P ? L::R0 : L::P0, 0);
-        x.m = load_own(P ? L::R0 : L::P0, -1);
-        if constexpr (!P) (void)half(std::integral_constant<int, 0>{}, f, x, real(0), L::US, L::ZS, red_v);
-        lds_barrier();
-        if constexpr (P) {
-            f = fetch(L::US, L::ZS);
-            x = half(std::integral_constant<int, 1>{}, f, x, real(1), L::RT, L::ZP, red_e);
-        }
-        lds_barrier();
-        if constexpr (!P) f = fetch(L::RT, L::ZP);
-        real eta = lqk_uniform(sum_red(red_e));
-        __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): every matrix load has been consumed
-        if (fabs(eta) < a.exit_tol) {
-            max_iter_exit = 0;
-        } else {
-            for (int it = 0; it < a.max_iter; ++it) {
-                if constexpr (!P) {
-                    // p = r~ + beta p ; upsilon = S p ; v = p . upsilon
-                    x = half(std::integral_constant<int, 2>{}, f, x, beta, L::US, L::ZS, red_v);
-                    lds_barrier();
-                    // alpha = eta / v ; lambda += alpha p (own entries) — while the Pinv half runs
-                    const Own cur = load_own(L::LAM, 0);
-                    const real alpha = lqk_uniform(eta / sum_red(red_v));
-                    Own nw;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) nw.v[s] = cur.v[s] + alpha * x.k.v[s];
-                    store_own(L::LAM, nw);
-                    lds_barrier();
-                    f = fetch(L::RT, L::ZP);                    // the next S half's operand loads fly during the scalar chain below
-                } else {
-                    lds_barrier();
-                    // alpha = eta / v ; r -= alpha upsilon ; r~ = Pinv r ; eta' = r . r~
-                    f = fetch(L::US, L::ZS);
-                    const real alpha = lqk_uniform(eta / sum_red(red_v));
-                    x = half(std::integral_constant<int, 1>{}, f, x, alpha, L::RT, L::ZP, red_e);
-                    lds_barrier();
-                }
-                // eta' ; exit test ; beta
-                const real eta_new = lqk_uniform(sum_red(red_e));
-                iters = (uint32_t)(it + 1);
-                if (fabs(eta_new) < a.exit_tol) { max_iter_exit = 0; p_pending = false; break; }     // (the reference leaves p as it is on this exit)
-                beta = lqk_uniform(eta_new / eta);
-                eta = eta_new;
-            }
-        }
-        // the vector this role carries, for d_p / d_r (the staging buffers are free since the setup)
-        store_own(P ? L::R0 : L::P0, x.k);
-    };
-    if (isP) run_role(std::true_type{}); else run_role(std::false_type{});
+    const LxkCg<real> cg{iters, max_iter_exit, beta, p_pending};
+    auto more = [&](int it) { return it < a.max_iter; };
+    if (isP) lxk_role<true, L, LqkTypes>(a, cg, load_own, store_own, fetch, half, arrive, value, more);
+    else lxk_role<false, L, LqkTypes>(a, cg, load_own, store_own, fetch, half, arrive, value, more);
 
     // ---- write back ----
     lds_barrier();
