@@ -41,107 +41,66 @@ class mpcg_limits(C.Structure):
                 ("q_weight", C.c_double), ("qd_weight", C.c_double), ("u_weight", C.c_double), ("flags", C.c_uint32)]
 
 
-# every symbol include/mpcg.h declares: (name, restype, argtypes)
-_f32p = C.c_void_p   # device pointers travel as integers
+# every symbol include/mpcg.h declares: name -> (restype, argtypes); tests/test_abi.py holds each row against the header's prototype.
+# Device pointers travel as integers (_p).  An entry with an _f64 twin is ONE row of _pair: _T stands for the entry's scalar type (float, and
+# double in the twin) and _TP for a HOST pointer to it; what is double in both twins (timestep, the _us times, mpcg_xuref, mpcg_limits) stays _d.
+_p, _u32, _int, _d, _T, _TP = C.c_void_p, C.c_uint32, C.c_int, C.c_double, "T", "T*"
+
+
+def _pair(name, args):
+    """The rows of the entry `name` and of `name`_f64 (both return int)."""
+    rows = {}
+    for suffix, T in (("", C.c_float), ("_f64", C.c_double)):
+        rows[name + suffix] = (_int, [T if a is _T else C.POINTER(T) if a is _TP else a for a in args])
+    return rows
+
+
 SYMBOLS = {
-    "mpcg_abi_version": (C.c_int, []),
+    "mpcg_abi_version": (_int, []),
     "mpcg_build_info": (C.c_char_p, []),
-    "mpcg_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]),
-    "mpcg_destroy": (C.c_int, [C.c_void_p]),
-    "mpcg_last_error": (C.c_char_p, [C.c_void_p]),
-    "mpcg_pcg_lds_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
-    "mpcg_pcg_lds_bytes_f64": (C.c_size_t, [C.c_uint32, C.c_uint32]),
-    "mpcg_check_pcg_occupancy": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
-    "mpcg_pcg_solve": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, C.c_uint32, C.c_uint32, C.c_float,
-                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mpcg_pcg_solve_ref": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
-                                     C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
-    "mpcg_bt_spmv": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_uint32, C.c_int, C.c_void_p]),
-    "mpcg_probe_hbm_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _f32p, C.c_void_p]),
-    "mpcg_convert_f32_to_f16": (C.c_int, [C.c_void_p, _f32p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "mpcg_pcg_solve_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _f32p, _f32p, C.c_uint32, C.c_uint32, C.c_float,
-                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mpcg_form_schur": (C.c_int, [C.c_void_p, C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float,
-                                  C.c_uint32, C.c_int, C.c_void_p]),
-    "mpcg_form_schur_rhov": (C.c_int, [C.c_void_p, C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
-                                       C.c_uint32, C.c_int, C.c_void_p]),
-    "mpcg_compute_dz": (C.c_int, [C.c_void_p, C.c_uint32, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_uint32, C.c_void_p]),
-    "mpcg_form_schur_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_double, C.c_uint32, C.c_int, C.c_void_p]),
-    "mpcg_form_schur_rhov_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
-    "mpcg_compute_dz_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_prep_csr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mpcg_bd_to_csr_lowertri": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_float, C.c_uint32, C.c_void_p]),
-    "mpcg_pcg_solve_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                     C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mpcg_pcg_solve_ref_f64": (C.c_int, [C.c_void_p] * 11 + [C.c_uint32, C.c_double, C.c_void_p]),
-    "mpcg_block_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_block_solve_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_plant_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
-    "mpcg_plant_create_iiwa14": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
-    "mpcg_plant_clone_gravity": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_double)]),
-    "mpcg_plant_get_gravity": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
-    "mpcg_plant_clone_limits": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(mpcg_limits)]),
-    "mpcg_plant_get_limits": (C.c_int, [C.c_void_p, C.POINTER(mpcg_limits), C.POINTER(C.c_int)]),
-    "mpcg_inverse_dynamics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_inverse_dynamics_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_plant_destroy": (C.c_int, [C.c_void_p]),
-    "mpcg_generate_kkt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_compute_merit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_line_search_step": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_line_search_step_rho": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
-                                            C.c_uint32, C.c_void_p]),
-    "mpcg_generate_kkt_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_compute_merit_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.POINTER(C.c_double), C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_line_search_step_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_line_search_step_rho_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
-                                                C.c_uint32, C.c_void_p]),
-    "mpcg_generate_kkt_xuref": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
-                                          C.POINTER(mpcg_xuref), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_generate_kkt_xuref_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
-                                              C.POINTER(mpcg_xuref), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_compute_merit_xuref": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.POINTER(C.c_float), C.c_uint32, C.c_float, C.c_float, C.c_float, C.POINTER(mpcg_xuref), C.c_void_p, C.c_uint32,
-                                           C.c_void_p]),
-    "mpcg_compute_merit_xuref_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.POINTER(C.c_double), C.c_uint32, C.c_double, C.c_double, C.c_double, C.POINTER(mpcg_xuref), C.c_void_p,
-                                               C.c_uint32, C.c_void_p]),
-    "mpcg_simulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_float,
-                                C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_advance_horizon": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_simulate_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
-                                    C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_advance_horizon_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_simulate_clk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_float,
-                                    C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_simulate_clk_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_double,
-                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_advance_horizon_clk": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_advance_horizon_clk_f64": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    "mpcg_ldl_create":(C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]),
-    "mpcg_ldl_destroy": (C.c_int, [C.c_void_p]),
-    "mpcg_ldl_pattern": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)),
-                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "mpcg_ldl_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mpcg_qdldl_solve_schur": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "mpcg_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
-    "mpcg_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
+    "mpcg_create": (_int, [C.POINTER(_p), _int, _u32, _u32, _u32]),
+    "mpcg_destroy": (_int, [_p]),
+    "mpcg_last_error": (C.c_char_p, [_p]),
+    "mpcg_pcg_lds_bytes": (C.c_size_t, [_u32, _u32]),
+    "mpcg_pcg_lds_bytes_f64": (C.c_size_t, [_u32, _u32]),
+    "mpcg_check_pcg_occupancy": (_int, [_p, C.POINTER(_u32)]),
+    **_pair("mpcg_pcg_solve", [_p, _p, _p, _p, _p, _u32, _u32, _T, _int, _p, _p, _p]),
+    **_pair("mpcg_pcg_solve_ref", [_p] * 11 + [_u32, _T, _p]),
+    "mpcg_pcg_solve_f16": (_int, [_p, _p, _p, _p, _p, _u32, _u32, C.c_float, _int, _p, _p, _p]),
+    "mpcg_bt_spmv": (_int, [_p, _p, _p, _p, _u32, _int, _p]),
+    "mpcg_probe_hbm_read": (_int, [_p, _p, C.c_size_t, _p, _p]),
+    "mpcg_convert_f32_to_f16": (_int, [_p, _p, _p, C.c_size_t, _p]),
+    **_pair("mpcg_form_schur", [_p, _u32, _p, _p, _p, _p, _p, _p, _p, _T, _u32, _int, _p]),
+    **_pair("mpcg_form_schur_rhov", [_p, _u32, _p, _p, _p, _p, _p, _p, _p, _p, _u32, _int, _p]),
+    **_pair("mpcg_compute_dz", [_p, _u32, _p, _p, _p, _p, _p, _u32, _p]),
+    **_pair("mpcg_block_solve", [_p, _p, _p, _p, _u32, _p]),
+    "mpcg_prep_csr": (_int, [_p, _p, _p, _p]),
+    "mpcg_bd_to_csr_lowertri": (_int, [_p, _p, _p, C.c_float, _u32, _p]),
+    "mpcg_plant_create": (_int, [C.POINTER(_p), _int, _u32, _p, _p, _p, _p, _p, _p, _u32, _p, _p, _p, _u32]),
+    "mpcg_plant_create_iiwa14": (_int, [C.POINTER(_p), _int]),
+    "mpcg_plant_clone_gravity": (_int, [C.POINTER(_p), _p, C.POINTER(_d)]),
+    "mpcg_plant_get_gravity": (_int, [_p, C.POINTER(_d)]),
+    "mpcg_plant_clone_limits": (_int, [C.POINTER(_p), _p, C.POINTER(mpcg_limits)]),
+    "mpcg_plant_get_limits": (_int, [_p, C.POINTER(mpcg_limits), C.POINTER(_int)]),
+    "mpcg_plant_destroy": (_int, [_p]),
+    **_pair("mpcg_inverse_dynamics", [_p, _p, _p, _p, _p, _p, _u32, _p]),
+    **_pair("mpcg_generate_kkt", [_p, _p, _u32, _T, _p, _p, _p, _T, _T, _p, _p, _p, _p, _u32, _p]),
+    **_pair("mpcg_generate_kkt_xuref", [_p, _p, _u32, _T, _p, _p, _p, _T, _T, C.POINTER(mpcg_xuref), _p, _p, _p, _p, _u32, _p]),
+    **_pair("mpcg_compute_merit", [_p, _p, _u32, _T, _p, _p, _p, _p, _TP, _u32, _T, _T, _T, _p, _u32, _p]),
+    **_pair("mpcg_compute_merit_xuref", [_p, _p, _u32, _T, _p, _p, _p, _p, _TP, _u32, _T, _T, _T, C.POINTER(mpcg_xuref), _p, _u32, _p]),
+    **_pair("mpcg_line_search_step", [_p, _u32, _p, _TP, _u32, _p, _p, _p, _p, _u32, _p]),
+    **_pair("mpcg_line_search_step_rho", [_p, _u32, _p, _TP, _u32, _p, _p, _p, _p, _p, _p, _p, _T, _T, _T, _T, _u32, _p]),
+    **_pair("mpcg_simulate", [_p, _p, _u32, _p, _p, _d, _d, _d, _T, _p, _u32, _p]),
+    **_pair("mpcg_simulate_clk", [_p, _p, _u32, _p, _p, _d, _p, _p, _T, _p, _p, _u32, _p]),
+    **_pair("mpcg_advance_horizon", [_p, _u32, _u32, _p, _p, _p, _p, _p, _p, _p, _u32, _u32, _u32, _p, _p, _p, _u32, _p]),
+    **_pair("mpcg_advance_horizon_clk", [_p, _u32, _p, _p, _p, _p, _p, _p, _p, _u32, _u32, _u32, _p, _p, _p, _d, _d, _p, _p, _p, _p, _p, _u32, _p]),
+    "mpcg_ldl_create": (_int, [C.POINTER(_p), _u32, _u32]),
+    "mpcg_ldl_destroy": (_int, [_p]),
+    "mpcg_ldl_pattern": (_int, [_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(_u32), C.POINTER(_u32)]),
+    "mpcg_ldl_solve": (_int, [_p, _p, _p, _p]),
+    "mpcg_qdldl_solve_schur": (_int, [_p, _p, _p, _p, _p, _p]),
+    "mpcg_set_option": (_int, [_p, C.c_char_p, _int]),
+    "mpcg_get_option": (_int, [_p, C.c_char_p, C.POINTER(_int)]),
 }
 
 _lib = None

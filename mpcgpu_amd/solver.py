@@ -9,6 +9,7 @@ all arithmetic happens in libmpcg_hip.so.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 
 import torch
@@ -17,6 +18,24 @@ from . import _lib
 from .synth import CONTROL_SIZE, STATE_SIZE, pcg_max_iter
 
 PCG_NUM_THREADS = 128   # include/common/settings.cuh:111-113 (reference launch shape; informational)
+
+# per dtype of a call's tensors: the suffix of its C entry and the ctypes scalar of the HOST arrays it takes
+_PRECISION = {torch.float32: ("", C.c_float), torch.float64: ("_f64", C.c_double)}
+_PRECOND = {"ss": _lib.MPCG_PRECOND_SS, "jacobi": _lib.MPCG_PRECOND_JACOBI, "none": _lib.MPCG_PRECOND_NONE}
+
+
+def layout(n: int, m: int, N: int) -> dict:
+    """Elements per trajectory of the reference's device arrays, by kind (the layouts of synth.py; "csr": include/qdldl/sqp.cuh:148)."""
+    return {"bd": 3 * n * n * N,                               # S, Pinv
+            "state": n * N,                                    # gamma, lambda, c
+            "xu": (n + m) * N - m,                             # xu, g, dz
+            "G_dense": (n * n + m * m) * N - m * m,
+            "C_dense": (n * n + n * m) * (N - 1),
+            "goals": 6 * N,                                    # eePos_traj of a call, eePos_goal
+            "xs": n,
+            "eePos": 3,
+            "csr": (N - 1) * n * n + N * (n * (n + 1)) // 2,   # nnz of the lower triangle
+            "one": 1}
 
 
 @dataclass
@@ -38,6 +57,17 @@ def _ptr(t: torch.Tensor | None):
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _batch(t: torch.Tensor) -> int:
+    """The trajectories of a call, from its leading tensor: [B, ...], or a flat one for a single trajectory."""
+    return t.shape[0] if t.dim() > 1 else 1
+
+
+def _ok(lib, rc, where):
+    """MpcgError unless rc is MPCG_OK.  `where`: the handle whose last error is the text, None for the create-time error, or the text itself."""
+    if rc != _lib.MPCG_OK:
+        raise _lib.MpcgError(rc, where if isinstance(where, str) else lib.mpcg_last_error(where).decode())
 
 
 class Plant:
@@ -62,9 +92,7 @@ class Plant:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         Xc, Hc = np.ascontiguousarray(m.X_const), np.ascontiguousarray(m.Xhom_const)
         h = C.c_void_p()
-        rc = self.lib.mpcg_plant_create(C.byref(h), dev, iiwa.NJ, p(Xc), p(Icol), p(Hc), p(xi), p(xc), p(xj), len(xi), p(hi), p(hc), p(hj), len(hi))
-        if rc != _lib.MPCG_OK:
-            raise _lib.MpcgError(rc, self.lib.mpcg_last_error(None).decode())
+        _ok(self.lib, self.lib.mpcg_plant_create(C.byref(h), dev, iiwa.NJ, p(Xc), p(Icol), p(Hc), p(xi), p(xc), p(xj), len(xi), p(hi), p(hc), p(hj), len(hi)), None)
         self._p = h
         if gravity is not None:
             heavy = self.with_gravity(gravity)
@@ -74,9 +102,7 @@ class Plant:
     def _clone(self, entry, arg) -> "Plant":
         """A new Plant around what the clone entry `entry` (mpcg_plant_clone_gravity / _limits) makes of this one and `arg`; MpcgError if it refuses."""
         h = C.c_void_p()
-        rc = entry(C.byref(h), self._p, arg)
-        if rc != _lib.MPCG_OK:
-            raise _lib.MpcgError(rc, self.lib.mpcg_last_error(None).decode())
+        _ok(self.lib, entry(C.byref(h), self._p, arg), None)
         new = object.__new__(Plant)
         new.lib, new.model, new._p = self.lib, self.model, h
         return new
@@ -91,15 +117,12 @@ class Plant:
     @property
     def gravity(self):
         out = (C.c_double * 3)()
-        rc = self.lib.mpcg_plant_get_gravity(self._p, out)
-        if rc != _lib.MPCG_OK:
-            raise _lib.MpcgError(rc, "mpcg_plant_get_gravity")
+        _ok(self.lib, self.lib.mpcg_plant_get_gravity(self._p, out), "mpcg_plant_get_gravity")
         return tuple(out)
 
     @staticmethod
     def _bounds(name, pair):
         """(lo, hi) -> two lists of 7 floats; None: no bound; a scalar broadcasts.  TypeError on anything that is not a pair of None / scalar / 7 numbers."""
-        import math
         import numpy as np
         if pair is None:
             pair = (None, None)
@@ -137,9 +160,7 @@ class Plant:
     def limits(self):
         """None for a plant without limits; otherwise a dict: q, qd, u = (lo, hi) tuples of 7 floats, q_weight, qd_weight, u_weight, sim_saturate."""
         lim, has = _lib.mpcg_limits(), C.c_int(0)
-        rc = self.lib.mpcg_plant_get_limits(self._p, C.byref(lim), C.byref(has))
-        if rc != _lib.MPCG_OK:
-            raise _lib.MpcgError(rc, "mpcg_plant_get_limits")
+        _ok(self.lib, self.lib.mpcg_plant_get_limits(self._p, C.byref(lim), C.byref(has)), "mpcg_plant_get_limits")
         if not has.value:
             return None
         return {"q": (tuple(lim.q_lo), tuple(lim.q_hi)), "qd": (tuple(lim.qd_lo), tuple(lim.qd_hi)), "u": (tuple(lim.u_lo), tuple(lim.u_hi)),
@@ -192,9 +213,7 @@ class QdldlSolver:
         self.lib = _lib.load()
         self.n, self.N = int(state_size), int(knot_points)
         h = C.c_void_p()
-        rc = self.lib.mpcg_ldl_create(C.byref(h), self.n, self.N)
-        if rc != _lib.MPCG_OK:
-            raise _lib.MpcgError(rc, "mpcg_ldl_create")
+        _ok(self.lib, self.lib.mpcg_ldl_create(C.byref(h), self.n, self.N), "mpcg_ldl_create")
         self._l = h
         cp, ri = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
         nnz, slnz = C.c_uint32(), C.c_uint32()
@@ -217,16 +236,13 @@ class QdldlSolver:
         gamma = np.ascontiguousarray(gamma, np.float32)
         assert val.size == self.nnz and gamma.size == self.n * self.N
         lam = np.empty_like(gamma)
-        rc = self.lib.mpcg_ldl_solve(self._l, val.ctypes.data_as(C.c_void_p), gamma.ctypes.data_as(C.c_void_p), lam.ctypes.data_as(C.c_void_p))
-        if rc != _lib.MPCG_OK:
-            raise _lib.MpcgError(rc, "mpcg_ldl_solve: zero pivot")
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        _ok(self.lib, self.lib.mpcg_ldl_solve(self._l, p(val), p(gamma), p(lam)), "mpcg_ldl_solve: zero pivot")
         return lam
 
     def solve_schur(self, sol: "PcgSolver", d_val, d_gamma, d_lambda):
         """The reference's timed region (include/qdldl/sqp.cuh:268-273): D2H(values, gamma), factor + solve, H2D(lambda)."""
-        rc = self.lib.mpcg_qdldl_solve_schur(sol._h, self._l, _ptr(d_val), _ptr(d_gamma), _ptr(d_lambda), _stream())
-        if rc != _lib.MPCG_OK:
-            raise _lib.MpcgError(rc, self.lib.mpcg_last_error(sol._h).decode())
+        _ok(self.lib, self.lib.mpcg_qdldl_solve_schur(sol._h, self._l, _ptr(d_val), _ptr(d_gamma), _ptr(d_lambda), _stream()), sol._h)
         return d_lambda
 
 
@@ -243,10 +259,9 @@ class PcgSolver:
         self.device = torch.cuda.current_device() if device is None else int(device)
         self.n, self.N, self.max_batch = int(state_size), int(knot_points), int(max_batch)
         self.control_size = CONTROL_SIZE if control_size is None else int(control_size)
+        self._dims_of = (self.control_size, layout(self.n, self.control_size, self.N))
         h = C.c_void_p()
-        rc = self.lib.mpcg_create(C.byref(h), self.device, self.n, self.N, self.max_batch)
-        if rc != _lib.MPCG_OK:
-            raise _lib.MpcgError(rc, self.lib.mpcg_last_error(None).decode())
+        _ok(self.lib, self.lib.mpcg_create(C.byref(h), self.device, self.n, self.N, self.max_batch), None)
         self._h = h
 
     def close(self):
@@ -257,8 +272,7 @@ class PcgSolver:
     __del__ = close
 
     def _check(self, rc):
-        if rc != _lib.MPCG_OK:
-            raise _lib.MpcgError(rc, self.lib.mpcg_last_error(self._h).decode())
+        _ok(self.lib, rc, self._h)
 
     def set_option(self, key: str, value: int):
         self._check(self.lib.mpcg_set_option(self._h, key.encode(), int(value)))
@@ -278,10 +292,34 @@ class PcgSolver:
         self._check(self.lib.mpcg_check_pcg_occupancy(self._h, C.byref(v)))
         return v.value
 
+    def _dims(self, control_size=None):
+        """(m, the array lengths by kind) of a call: the handle's control_size unless the call names one."""
+        m = self.control_size if control_size is None else int(control_size)
+        if m != self._dims_of[0]:
+            self._dims_of = (m, layout(self.n, m, self.N))
+        return self._dims_of
+
+    def _fn(self, base, dt):
+        """The C entry mpcg_`base` for float32 tensors, its _f64 twin for float64 ones."""
+        return getattr(self.lib, "mpcg_" + base + _PRECISION[dt][0])
+
     def _chk(self, t, numel, dtype, name):
         if not (t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() == numel):
             raise ValueError(f"{name}: need contiguous cuda {dtype} tensor with {numel} elements, "
                              f"got {tuple(t.shape)} {t.dtype} {t.device}")
+
+    def _chk_each(self, B, L, dtype, arrays, optional=False):
+        """_chk of B trajectories of each (tensor, kind of L, name); optional: a None among them is an argument left out."""
+        for t, kind, name in arrays:
+            if t is not None or not optional:
+                self._chk(t, B * L[kind], dtype, name)
+
+    def _out(self, t, shape, dtype, like, name):
+        """The caller's output `t`, or a new one of `shape` on the device of `like`; checked either way."""
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=like.device)
+        self._chk(t, math.prod(shape), dtype, name)
+        return t
 
     @staticmethod
     def _one_dtype(name, *tensors):
@@ -295,23 +333,26 @@ class PcgSolver:
               iters: torch.Tensor | None = None, exits: torch.Tensor | None = None):
         """In-place batched solve.  S, Pinv: [B, 3*n*n*N]; gamma, lam: [B, n*N] (lam in/out).
         Returns (iters uint32-as-int32 [B], max_iter_exit uint8 [B]) device tensors; no sync."""
+        return self._solve("mpcg_pcg_solve", torch.float32, torch.float32, ("S", "Pinv"), S, Pinv, gamma, lam, config, precond, iters, exits)
+
+    def _solve(self, entry, mat_dt, vec_dt, names, S, Pinv, gamma, lam, config, precond, iters, exits):
+        """solve, solve_f16 and solve_f64: the C entry `entry` on matrices of mat_dt, called `names` in a refusal, and vectors of vec_dt."""
         cfg = config or pcg_config(pcg_max_iter=pcg_max_iter(self.N))
-        B = lam.shape[0] if lam.dim() > 1 else 1
-        n, N = self.n, self.N
-        self._chk(S, B * 3 * n * n * N, torch.float32, "S")
-        self._chk(Pinv, B * 3 * n * n * N, torch.float32, "Pinv")
-        self._chk(gamma, B * n * N, torch.float32, "gamma")
-        self._chk(lam, B * n * N, torch.float32, "lambda")
+        B = _batch(lam)
+        L = self._dims_of[1]                                   # the hot path: no call for it, and these two kinds are the same for any m
+        self._chk(S, B * L["bd"], mat_dt, names[0])
+        self._chk(Pinv, B * L["bd"], mat_dt, names[1])
+        self._chk(gamma, B * L["state"], vec_dt, "gamma")
+        self._chk(lam, B * L["state"], vec_dt, "lambda")
         if iters is None:
             iters = torch.empty(B, dtype=torch.int32, device=lam.device)
         if exits is None:
             exits = torch.empty(B, dtype=torch.uint8, device=lam.device)
-        pc = _lib.MPCG_PRECOND_SS if precond == "ss" else _lib.MPCG_PRECOND_JACOBI
         if precond not in ("ss", "jacobi"):
             raise ValueError("precond must be 'ss' or 'jacobi'")
-        self._check(self.lib.mpcg_pcg_solve(self._h, _ptr(S), _ptr(Pinv), _ptr(gamma), _ptr(lam), B,
-                                            int(cfg.pcg_max_iter), float(cfg.pcg_exit_tol), pc,
-                                            _ptr(iters), _ptr(exits), _stream()))
+        _ok(self.lib, getattr(self.lib, entry)(self._h, _ptr(S), _ptr(Pinv), _ptr(gamma), _ptr(lam), B,
+                                               int(cfg.pcg_max_iter), float(cfg.pcg_exit_tol), _PRECOND[precond],
+                                               _ptr(iters), _ptr(exits), _stream()), self._h)
         return iters, exits
 
     def to_f16(self, M: torch.Tensor) -> torch.Tensor:
@@ -324,78 +365,40 @@ class PcgSolver:
     def solve_f16(self, S16, Pinv16, gamma, lam, config: pcg_config | None = None, precond: str = "ss",
                   iters: torch.Tensor | None = None, exits: torch.Tensor | None = None):
         """`solve` with S / Pinv stored in half precision (arithmetic stays fp32)."""
-        cfg = config or pcg_config(pcg_max_iter=pcg_max_iter(self.N))
-        B = lam.shape[0] if lam.dim() > 1 else 1
-        n, N = self.n, self.N
-        self._chk(S16, B * 3 * n * n * N, torch.float16, "S16")
-        self._chk(Pinv16, B * 3 * n * n * N, torch.float16, "Pinv16")
-        self._chk(gamma, B * n * N, torch.float32, "gamma")
-        self._chk(lam, B * n * N, torch.float32, "lambda")
-        if iters is None:
-            iters = torch.empty(B, dtype=torch.int32, device=lam.device)
-        if exits is None:
-            exits = torch.empty(B, dtype=torch.uint8, device=lam.device)
-        if precond not in ("ss", "jacobi"):
-            raise ValueError("precond must be 'ss' or 'jacobi'")
-        pc = _lib.MPCG_PRECOND_SS if precond == "ss" else _lib.MPCG_PRECOND_JACOBI
-        self._check(self.lib.mpcg_pcg_solve_f16(self._h, _ptr(S16), _ptr(Pinv16), _ptr(gamma), _ptr(lam), B,
-                                                int(cfg.pcg_max_iter), float(cfg.pcg_exit_tol), pc,
-                                                _ptr(iters), _ptr(exits), _stream()))
-        return iters, exits
+        return self._solve("mpcg_pcg_solve_f16", torch.float16, torch.float32, ("S16", "Pinv16"), S16, Pinv16, gamma, lam, config, precond, iters, exits)
 
     def solve_f64(self, S, Pinv, gamma, lam, config: pcg_config | None = None, precond: str = "ss",
                   iters: torch.Tensor | None = None, exits: torch.Tensor | None = None):
         """`solve` in double precision (linsys_t = double, USE_DOUBLES=1 of include/common/settings.cuh:41-49)."""
-        cfg = config or pcg_config(pcg_max_iter=pcg_max_iter(self.N))
-        B = lam.shape[0] if lam.dim() > 1 else 1
-        n, N = self.n, self.N
-        for t, k, nm in ((S, 3 * n * n, "S"), (Pinv, 3 * n * n, "Pinv"), (gamma, n, "gamma"), (lam, n, "lambda")):
-            self._chk(t, B * k * N, torch.float64, nm)
-        if iters is None:
-            iters = torch.empty(B, dtype=torch.int32, device=lam.device)
-        if exits is None:
-            exits = torch.empty(B, dtype=torch.uint8, device=lam.device)
-        if precond not in ("ss", "jacobi"):
-            raise ValueError("precond must be 'ss' or 'jacobi'")
-        pc = _lib.MPCG_PRECOND_SS if precond == "ss" else _lib.MPCG_PRECOND_JACOBI
-        self._check(self.lib.mpcg_pcg_solve_f64(self._h, _ptr(S), _ptr(Pinv), _ptr(gamma), _ptr(lam), B,
-                                                int(cfg.pcg_max_iter), float(cfg.pcg_exit_tol), pc,
-                                                _ptr(iters), _ptr(exits), _stream()))
-        return iters, exits
+        return self._solve("mpcg_pcg_solve_f64", torch.float64, torch.float64, ("S", "Pinv"), S, Pinv, gamma, lam, config, precond, iters, exits)
 
     def solve_ref(self, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, d_v_temp, d_eta_new_temp,
                   d_pcg_iters, d_pcg_exit, pcg_max_iter: int, pcg_exit_tol: float):
         """The reference kernel's argument list, in order (include/pcg/sqp.cuh:137-150)."""
-        self._check(self.lib.mpcg_pcg_solve_ref(self._h, _ptr(d_S), _ptr(d_Pinv), _ptr(d_gamma), _ptr(d_lambda),
-                                                _ptr(d_r), _ptr(d_p), _ptr(d_v_temp), _ptr(d_eta_new_temp),
-                                                _ptr(d_pcg_iters), _ptr(d_pcg_exit),
-                                                int(pcg_max_iter), float(pcg_exit_tol), _stream()))
+        self._solve_ref("mpcg_pcg_solve_ref", (d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, d_v_temp, d_eta_new_temp, d_pcg_iters, d_pcg_exit),
+                        pcg_max_iter, pcg_exit_tol)
+
+    def _solve_ref(self, entry, arrays, pcg_max_iter, pcg_exit_tol):
+        """solve_ref and solve_ref_f64: the C entry `entry` on the ten arrays of the reference's launch, unchecked as there."""
+        self._check(getattr(self.lib, entry)(self._h, *map(_ptr, arrays), int(pcg_max_iter), float(pcg_exit_tol), _stream()))
 
     def solve_ref_f64(self, d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, d_v_temp, d_eta_new_temp,
                       d_pcg_iters, d_pcg_exit, pcg_max_iter: int, pcg_exit_tol: float):
         """The reference kernel's argument list with linsys_t = double (pcg<double, n, N>; include/pcg/sqp.cuh:137-150)."""
-        self._check(self.lib.mpcg_pcg_solve_ref_f64(self._h, _ptr(d_S), _ptr(d_Pinv), _ptr(d_gamma), _ptr(d_lambda),
-                                                    _ptr(d_r), _ptr(d_p), _ptr(d_v_temp), _ptr(d_eta_new_temp),
-                                                    _ptr(d_pcg_iters), _ptr(d_pcg_exit),
-                                                    int(pcg_max_iter), float(pcg_exit_tol), _stream()))
+        self._solve_ref("mpcg_pcg_solve_ref_f64", (d_S, d_Pinv, d_gamma, d_lambda, d_r, d_p, d_v_temp, d_eta_new_temp, d_pcg_iters, d_pcg_exit),
+                        pcg_max_iter, pcg_exit_tol)
 
     def block_solve(self, S, gamma, lam=None):
         """Batched block-tridiagonal direct solve (the GPU counterpart of qdldl_solve_schur,
         include/qdldl/sqp.cuh:22-49).  S: [B, 3*n*n*N], gamma: [B, n*N]; returns lambda [B, n*N].
         float32 tensors: mpcg_block_solve (option "block_solve_f64" = 1: the sweep in double, float in and out);
         float64 tensors: mpcg_block_solve_f64 (linsys_t = double).  Mixed or other dtypes raise TypeError."""
-        B = gamma.shape[0] if gamma.dim() > 1 else 1
-        n, N = self.n, self.N
-        dt = gamma.dtype
-        if dt not in (torch.float32, torch.float64) or S.dtype != dt or (lam is not None and lam.dtype != dt):
-            raise TypeError("block_solve: S, gamma and lambda must all be float32 or all be float64")
-        self._chk(S, B * 3 * n * n * N, dt, "S")
-        self._chk(gamma, B * n * N, dt, "gamma")
-        if lam is None:
-            lam = torch.empty(B, n * N, device=gamma.device, dtype=dt)
-        self._chk(lam, B * n * N, dt, "lambda")
-        fn = self.lib.mpcg_block_solve if dt == torch.float32 else self.lib.mpcg_block_solve_f64
-        self._check(fn(self._h, _ptr(S), _ptr(gamma), _ptr(lam), B, _stream()))
+        B = _batch(gamma)
+        L = self._dims()[1]
+        dt = self._one_dtype("block_solve", S, gamma, lam)
+        self._chk_each(B, L, dt, ((S, "bd", "S"), (gamma, "state", "gamma")))
+        lam = self._out(lam, (B, L["state"]), dt, gamma, "lambda")
+        self._check(self._fn("block_solve", dt)(self._h, _ptr(S), _ptr(gamma), _ptr(lam), B, _stream()))
         return lam
 
     def form_schur(self, G_dense, C_dense, g, c, rho, precond: str = "ss", S=None, Pinv=None, gamma=None,
@@ -404,31 +407,19 @@ class PcgSolver:
         its block inverses (the reference's side effect).  Returns (S, Pinv, gamma) device tensors.
         rho: a Python float (one value for the call), or a device tensor [B] of the operands' dtype — one value per trajectory, read
         when the kernels run (mpcg_form_schur_rhov; what line_search_step_rho adapts)."""
-        B = c.shape[0] if c.dim() > 1 else 1
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        dt = c.dtype                                           # float32, or float64 = linsys_t double (mpcg_form_schur_f64)
-        if dt not in (torch.float32, torch.float64):
-            raise TypeError("form_schur: float32 or float64 tensors")
-        self._chk(G_dense, B * ((n * n + m * m) * N - m * m), dt, "G_dense")
-        self._chk(C_dense, B * (n * n + n * m) * (N - 1), dt, "C_dense")
-        self._chk(g, B * ((n + m) * N - m), dt, "g")
-        self._chk(c, B * n * N, dt, "c")
-        dev = c.device
-        S = torch.empty(B, 3 * n * n * N, device=dev, dtype=dt) if S is None else S
-        Pinv = torch.empty(B, 3 * n * n * N, device=dev, dtype=dt) if Pinv is None else Pinv
-        gamma = torch.empty(B, n * N, device=dev, dtype=dt) if gamma is None else gamma
-        self._chk(S, B * 3 * n * n * N, dt, "S")
-        self._chk(Pinv, B * 3 * n * n * N, dt, "Pinv")
-        self._chk(gamma, B * n * N, dt, "gamma")
-        pc = {"ss": _lib.MPCG_PRECOND_SS, "jacobi": _lib.MPCG_PRECOND_JACOBI, "none": _lib.MPCG_PRECOND_NONE}[precond]
+        B = _batch(c)
+        m, L = self._dims(control_size)
+        dt = self._one_dtype("form_schur", c)                  # of c alone: another tensor of another dtype is a ValueError below
+        self._chk_each(B, L, dt, ((G_dense, "G_dense", "G_dense"), (C_dense, "C_dense", "C_dense"), (g, "xu", "g"), (c, "state", "c")))
+        S, Pinv, gamma = (self._out(t, (B, L[kind]), dt, c, name) for t, kind, name in ((S, "bd", "S"), (Pinv, "bd", "Pinv"), (gamma, "state", "gamma")))
+        pc = _PRECOND[precond]
         if isinstance(rho, torch.Tensor):
             self._chk(rho, B, dt, "rho")
-            fn = self.lib.mpcg_form_schur_rhov if dt == torch.float32 else self.lib.mpcg_form_schur_rhov_f64
-            rho_arg = _ptr(rho)
+            entry, rho_arg = "form_schur_rhov", _ptr(rho)
         else:
-            fn = self.lib.mpcg_form_schur if dt == torch.float32 else self.lib.mpcg_form_schur_f64
-            rho_arg = float(rho)
-        self._check(fn(self._h, m, _ptr(G_dense), _ptr(C_dense), _ptr(g), _ptr(c), _ptr(S), _ptr(Pinv), _ptr(gamma), rho_arg, B, pc, _stream()))
+            entry, rho_arg = "form_schur", float(rho)
+        self._check(self._fn(entry, dt)(self._h, m, _ptr(G_dense), _ptr(C_dense), _ptr(g), _ptr(c), _ptr(S), _ptr(Pinv), _ptr(gamma), rho_arg, B, pc,
+                                        _stream()))
         return S, Pinv, gamma
 
     def generate_kkt(self, plant: "Plant", eePos_traj, xs, xu, timestep: float, qd_cost: float, r_cost: float,
@@ -442,22 +433,15 @@ class PcgSolver:
     def _generate_kkt(self, xuref: bool, plant, eePos_traj, xs, xu, timestep, qd_cost, r_cost, ref, control_size):
         """generate_kkt (ref = None) and generate_kkt_xuref (xuref): the C entry of that name or its _f64 twin; only the latter may leave eePos_traj out."""
         name = "generate_kkt_xuref" if xuref else "generate_kkt"
-        B = xu.shape[0] if xu.dim() > 1 else 1
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        B = _batch(xu)
+        m, L = self._dims(control_size)
         dt = self._one_dtype(name, eePos_traj, xs, xu, *((ref.xu_traj,) if xuref else ()))
-        if eePos_traj is not None or not xuref:
-            self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
-        self._chk(xs, B * n, dt, "xs")
-        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
-        x = (C.byref(self._xuref(name, ref, dt, B, n, m)),) if xuref else ()
-        dev = xu.device
-        G = torch.empty(B, (n * n + m * m) * N - m * m, device=dev, dtype=dt)
-        Cd = torch.empty(B, (n * n + n * m) * (N - 1), device=dev, dtype=dt)
-        g = torch.empty(B, (n + m) * N - m, device=dev, dtype=dt)
-        c = torch.empty(B, n * N, device=dev, dtype=dt)
-        fn = getattr(self.lib, "mpcg_" + name + ("" if dt == torch.float32 else "_f64"))
-        self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), float(qd_cost), float(r_cost), *x,
-                       _ptr(G), _ptr(Cd), _ptr(g), _ptr(c), B, _stream()))
+        self._chk_each(B, L, dt, ((eePos_traj, "goals", "eePos_traj"),), optional=xuref)
+        self._chk_each(B, L, dt, ((xs, "xs", "xs"), (xu, "xu", "xu")))
+        x = (C.byref(self._xuref(name, ref, dt, B, self.n, m)),) if xuref else ()
+        G, Cd, g, c = (torch.empty(B, L[kind], device=xu.device, dtype=dt) for kind in ("G_dense", "C_dense", "xu", "state"))
+        self._check(self._fn(name, dt)(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), float(qd_cost), float(r_cost), *x,
+                                       _ptr(G), _ptr(Cd), _ptr(g), _ptr(c), B, _stream()))
         return G, Cd, g, c
 
     def _xuref(self, name, ref: "XuRef", dt, B, n, m):
@@ -497,27 +481,19 @@ class PcgSolver:
 
     def compute_dz(self, Ginv_dense, C_dense, g, lam, dz=None, control_size: int | None = None):
         """compute_dz (include/common/dz.cuh:124-136), batched."""
-        B = lam.shape[0] if lam.dim() > 1 else 1
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        dt = lam.dtype                                         # float32, or float64 = linsys_t double (mpcg_compute_dz_f64)
-        if dt not in (torch.float32, torch.float64):
-            raise TypeError("compute_dz: float32 or float64 tensors")
-        self._chk(Ginv_dense, B * ((n * n + m * m) * N - m * m), dt, "Ginv_dense")
-        self._chk(C_dense, B * (n * n + n * m) * (N - 1), dt, "C_dense")
-        self._chk(g, B * ((n + m) * N - m), dt, "g")
-        self._chk(lam, B * n * N, dt, "lam")
-        if dz is None:
-            dz = torch.empty(B, (n + m) * N - m, device=lam.device, dtype=dt)
-        self._chk(dz, B * ((n + m) * N - m), dt, "dz")
-        fn = self.lib.mpcg_compute_dz if dt == torch.float32 else self.lib.mpcg_compute_dz_f64
-        self._check(fn(self._h, m, _ptr(Ginv_dense), _ptr(C_dense), _ptr(g), _ptr(lam), _ptr(dz), B, _stream()))
+        B = _batch(lam)
+        m, L = self._dims(control_size)
+        dt = self._one_dtype("compute_dz", lam)                # of lam alone: another tensor of another dtype is a ValueError below
+        self._chk_each(B, L, dt, ((Ginv_dense, "G_dense", "Ginv_dense"), (C_dense, "C_dense", "C_dense"), (g, "xu", "g"), (lam, "state", "lam")))
+        dz = self._out(dz, (B, L["xu"]), dt, lam, "dz")
+        self._check(self._fn("compute_dz", dt)(self._h, m, _ptr(Ginv_dense), _ptr(C_dense), _ptr(g), _ptr(lam), _ptr(dz), B, _stream()))
         return dz
 
     @staticmethod
     def _steps(step_sizes, dtype=torch.float32):
         """The HOST array of step sizes both line-search calls take (copied into the launch): floats, or doubles for the _f64 entries."""
         vals = [float(v) for v in step_sizes]
-        return ((C.c_float if dtype == torch.float32 else C.c_double) * len(vals))(*vals), len(vals)
+        return (_PRECISION[dtype][1] * len(vals))(*vals), len(vals)
 
     def compute_merit(self, plant: "Plant", eePos_traj, xs, xu, dz, step_sizes, timestep: float, mu: float, qd_cost: float,
                       r_cost: float, merit=None, control_size: int | None = None):
@@ -531,43 +507,39 @@ class PcgSolver:
     def _compute_merit(self, xuref: bool, plant, eePos_traj, xs, xu, dz, step_sizes, timestep, mu, qd_cost, r_cost, ref, merit, control_size):
         """compute_merit (ref = None) and compute_merit_xuref (xuref): the C entry of that name or its _f64 twin; only the latter may leave eePos_traj out."""
         name = "compute_merit_xuref" if xuref else "compute_merit"
-        B = xu.shape[0] if xu.dim() > 1 else 1
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        B = _batch(xu)
+        m, L = self._dims(control_size)
         dt = self._one_dtype(name, eePos_traj, xs, xu, dz, merit, *((ref.xu_traj,) if xuref else ()))
         arr, A = self._steps(step_sizes, dt)
-        if eePos_traj is not None or not xuref:
-            self._chk(eePos_traj, B * 6 * N, dt, "eePos_traj")
-        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
-        if xs is not None:
-            self._chk(xs, B * n, dt, "xs")
-        if dz is not None:
-            self._chk(dz, B * ((n + m) * N - m), dt, "dz")
-        x = (C.byref(self._xuref(name, ref, dt, B, n, m)),) if xuref else ()
-        if merit is None:
-            merit = torch.empty(B, A, device=xu.device, dtype=dt)
-        self._chk(merit, B * A, dt, "merit")
-        fn = getattr(self.lib, "mpcg_" + name + ("" if dt == torch.float32 else "_f64"))
-        self._check(fn(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), _ptr(dz), arr, A,
-                       float(mu), float(qd_cost), float(r_cost), *x, _ptr(merit), B, _stream()))
+        self._chk_each(B, L, dt, ((eePos_traj, "goals", "eePos_traj"),), optional=xuref)
+        self._chk(xu, B * L["xu"], dt, "xu")
+        self._chk_each(B, L, dt, ((xs, "xs", "xs"), (dz, "xu", "dz")), optional=True)
+        x = (C.byref(self._xuref(name, ref, dt, B, self.n, m)),) if xuref else ()
+        merit = self._out(merit, (B, A), dt, xu, "merit")
+        self._check(self._fn(name, dt)(self._h, plant._p, m, float(timestep), _ptr(eePos_traj), _ptr(xs), _ptr(xu), _ptr(dz), arr, A,
+                                       float(mu), float(qd_cost), float(r_cost), *x, _ptr(merit), B, _stream()))
         return merit
 
     def line_search_step(self, merit, step_sizes, merit_ref, dz, xu, step=None, control_size: int | None = None):
         """The step selection and update of include/pcg/sqp.cuh:292-301, 317, 332-338, 352 per trajectory: the first strictly smallest merit below
         merit_ref wins; xu and merit_ref are updated in place.  Returns the chosen index per trajectory (int32 [B], -1: no step).
         float32 tensors: mpcg_line_search_step; float64 tensors: mpcg_line_search_step_f64.  Mixed dtypes raise TypeError."""
+        return self._line_search("line_search_step", merit, step_sizes, merit_ref, dz, xu, step, control_size)
+
+    def _line_search(self, name, merit, step_sizes, merit_ref, dz, xu, step, control_size, rho=(), params=()):
+        """line_search_step, and line_search_step_rho with its device state rho = (rho, drho, done) and its four scalars `params`."""
         B = merit_ref.numel()
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        dt = self._one_dtype("line_search_step", merit, merit_ref, dz, xu)
+        m, L = self._dims(control_size)
+        dt = self._one_dtype(name, merit, merit_ref, dz, xu, *rho[:2])
         arr, A = self._steps(step_sizes, dt)
         self._chk(merit, B * A, dt, "merit")
-        self._chk(merit_ref, B, dt, "merit_ref")
-        self._chk(dz, B * ((n + m) * N - m), dt, "dz")
-        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
-        if step is None:
-            step = torch.empty(B, dtype=torch.int32, device=xu.device)
-        self._chk(step, B, torch.int32, "step")
-        fn = self.lib.mpcg_line_search_step if dt == torch.float32 else self.lib.mpcg_line_search_step_f64
-        self._check(fn(self._h, m, _ptr(merit), arr, A, _ptr(merit_ref), _ptr(dz), _ptr(xu), _ptr(step), B, _stream()))
+        self._chk_each(B, L, dt, ((merit_ref, "one", "merit_ref"), (dz, "xu", "dz"), (xu, "xu", "xu")))
+        if rho:
+            self._chk_each(B, L, dt, ((rho[0], "one", "rho"), (rho[1], "one", "drho")))
+            self._chk(rho[2], B, torch.uint8, "done")
+        step = self._out(step, (B,), torch.int32, xu, "step")
+        self._check(self._fn(name, dt)(self._h, m, _ptr(merit), arr, A, _ptr(merit_ref), _ptr(dz), _ptr(xu), _ptr(step), *map(_ptr, rho),
+                                       *map(float, params), B, _stream()))
         return step
 
     def line_search_step_rho(self, merit, step_sizes, merit_ref, dz, xu, rho, drho, done, rho_factor: float = 1.2, rho_min: float = 1e-3,
@@ -576,25 +548,8 @@ class PcgSolver:
         [B]) and done (uint8 [B]) are updated in place; a trajectory with done != 0 is frozen (step = MPCG_STEP_FROZEN, nothing else written).
         `rho` is the tensor form_schur takes: nothing is read back inside an SQP loop.
         float32 tensors: mpcg_line_search_step_rho; float64 tensors (rho and drho float64 too): mpcg_line_search_step_rho_f64.  Mixed dtypes raise TypeError."""
-        B = merit_ref.numel()
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        dt = self._one_dtype("line_search_step_rho", merit, merit_ref, dz, xu, rho, drho)
-        arr, A = self._steps(step_sizes, dt)
-        self._chk(merit, B * A, dt, "merit")
-        self._chk(merit_ref, B, dt, "merit_ref")
-        self._chk(dz, B * ((n + m) * N - m), dt, "dz")
-        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
-        self._chk(rho, B, dt, "rho")
-        self._chk(drho, B, dt, "drho")
-        self._chk(done, B, torch.uint8, "done")
-        if step is None:
-            step = torch.empty(B, dtype=torch.int32, device=xu.device)
-        self._chk(step, B, torch.int32, "step")
-        fn = self.lib.mpcg_line_search_step_rho if dt == torch.float32 else self.lib.mpcg_line_search_step_rho_f64
-        self._check(fn(self._h, m, _ptr(merit), arr, A, _ptr(merit_ref), _ptr(dz), _ptr(xu), _ptr(step),
-                                                       _ptr(rho), _ptr(drho), _ptr(done), float(rho_factor), float(rho_min), float(rho_max),
-                                                       float(rho_reset), B, _stream()))
-        return step
+        return self._line_search("line_search_step_rho", merit, step_sizes, merit_ref, dz, xu, step, control_size, (rho, drho, done),
+                                 (rho_factor, rho_min, rho_max, rho_reset))
 
     def simulate(self, plant: "Plant", xs, xu, timestep: float, time_offset_us: float, sim_time_us: float, sim_step: float = 2e-4,
                  eePos=None, control_size: int | None = None):
@@ -604,16 +559,21 @@ class PcgSolver:
         float32 tensors: mpcg_simulate (sim_step is rounded to float).  float64 tensors: mpcg_simulate_f64 — the inputs used as they are, the state
         stored without a rounding, sim_step a double: at the default 2e-4 the reference's double schedule runs ten substeps AND a remainder of
         almost a whole one per 2,000 us (include/mpcg.h); pass float(numpy.float32(2e-4)) for the float entry's ten.  Mixed dtypes raise TypeError."""
-        B = xs.shape[0] if xs.dim() > 1 else 1
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        dt = self._one_dtype("simulate", xs, xu, eePos)
-        self._chk(xs, B * n, dt, "xs")
-        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
-        if eePos is not None:
-            self._chk(eePos, B * 3, dt, "eePos")
-        fn = self.lib.mpcg_simulate if dt == torch.float32 else self.lib.mpcg_simulate_f64
-        self._check(fn(self._h, plant._p, m, _ptr(xs), _ptr(xu), float(timestep), float(time_offset_us), float(sim_time_us),
-                       float(sim_step), _ptr(eePos), B, _stream()))
+        return self._simulate("simulate", plant, xs, xu, timestep, (time_offset_us, sim_time_us), sim_step, eePos, (), control_size)
+
+    def _simulate(self, name, plant, xs, xu, timestep, times, sim_step, eePos, done, control_size):
+        """simulate (times: two numbers, done = ()) and simulate_clk (times: two float64 [B] tensors, done = (done,))."""
+        on_device = name == "simulate_clk"
+        B = _batch(xs)
+        m, L = self._dims(control_size)
+        dt = self._one_dtype(name, xs, xu, eePos)
+        self._chk_each(B, L, dt, ((xs, "xs", "xs"), (xu, "xu", "xu")))
+        if on_device:
+            self._chk_each(B, L, torch.float64, ((times[0], "one", "time_offset_us"), (times[1], "one", "sim_time_us")))
+        self._chk_each(B, L, dt, ((eePos, "eePos", "eePos"),), optional=True)
+        self._chk_each(B, L, torch.int32, [(t, "one", "done") for t in done], optional=True)
+        self._check(self._fn(name, dt)(self._h, plant._p, m, _ptr(xs), _ptr(xu), float(timestep), *map(_ptr if on_device else float, times),
+                                       float(sim_step), _ptr(eePos), *map(_ptr, done), B, _stream()))
         return xs
 
     def inverse_dynamics(self, plant: "Plant", q, qd=None, qdd=None, tau=None):
@@ -628,12 +588,27 @@ class PcgSolver:
         for t, name in ((qd, "qd"), (qdd, "qdd")):
             if t is not None:
                 self._chk(t, count * 7, dt, name)
-        if tau is None:
-            tau = torch.empty(count, 7, device=q.device, dtype=dt)
-        self._chk(tau, count * 7, dt, "tau")
-        fn = self.lib.mpcg_inverse_dynamics if dt == torch.float32 else self.lib.mpcg_inverse_dynamics_f64
-        self._check(fn(self._h, plant._p, _ptr(q), _ptr(qd), _ptr(qdd), _ptr(tau), count, _stream()))
+        tau = self._out(tau, (count, 7), dt, q, "tau")
+        self._check(self._fn("inverse_dynamics", dt)(self._h, plant._p, _ptr(q), _ptr(qd), _ptr(qdd), _ptr(tau), count, _stream()))
         return tau
+
+    def _chk_shift(self, name, B, L, dt, m, lam, eePos_goal, eePos, xu_traj, eePos_traj, traj_offset, done, tracking_error, need_eePos):
+        """What a shift reads and writes besides xu and xs: ValueError naming the first array that is missing (eePos only if need_eePos) or is
+        not what B trajectories need; returns the plan's (traj_steps, traj_batch_stride)."""
+        given = {"lam": lam, "eePos_goal": eePos_goal, "xu_traj": xu_traj, "eePos_traj": eePos_traj, "traj_offset": traj_offset, "done": done,
+                 "tracking_error": tracking_error}
+        if need_eePos or eePos is not None:
+            given["eePos"] = eePos
+        for arg, t in given.items():
+            if t is None:
+                raise ValueError(f"{name} needs {arg}")
+        per_traj, T = xu_traj.dim() == 3, int(xu_traj.shape[-2])
+        plans = B if per_traj else 1
+        count = {"lam": B * L["state"], "eePos_goal": B * L["goals"], "eePos": B * L["eePos"], "xu_traj": plans * T * (self.n + m),
+                 "eePos_traj": plans * T * 6}
+        for arg, t in given.items():
+            self._chk(t, count.get(arg, B), torch.int32 if arg in ("traj_offset", "done") else dt, arg)
+        return T, (T if per_traj else 0)
 
     def advance_horizon(self, shift: bool, xu, xs, lam=None, eePos_goal=None, eePos=None, xu_traj=None, eePos_traj=None, traj_offset=None,
                         done=None, tracking_error=None, xu_fill_lead: int = 0, control_size: int | None = None):
@@ -644,34 +619,19 @@ class PcgSolver:
         xu_fill_lead: 0 = the reference's source row of the xu tail, N - 1 = the row its goal fill uses.
         float32 tensors: mpcg_advance_horizon; float64 tensors: mpcg_advance_horizon_f64 (the copies and the tracking error in double).  traj_offset and
         done are int32 for both.  Mixed dtypes raise TypeError."""
-        B = xs.shape[0] if xs.dim() > 1 else 1
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        B = _batch(xs)
+        m, L = self._dims(control_size)
         dt = self._one_dtype("advance_horizon", xu, xs, lam, eePos_goal, eePos, xu_traj, eePos_traj, tracking_error)
-        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
-        self._chk(xs, B * n, dt, "xs")
+        self._chk_each(B, L, dt, ((xu, "xu", "xu"), (xs, "xs", "xs")))
         T = stride = 0
         if shift:
-            for t, name in ((lam, "lam"), (eePos_goal, "eePos_goal"), (xu_traj, "xu_traj"), (eePos_traj, "eePos_traj"), (traj_offset, "traj_offset"),
-                            (done, "done"), (tracking_error, "tracking_error")):
-                if t is None:
-                    raise ValueError(f"advance_horizon(shift=True) needs {name}")
-            per_traj = xu_traj.dim() == 3
-            T = int(xu_traj.shape[-2])
-            stride = T if per_traj else 0
-            self._chk(lam, B * n * N, dt, "lam")
-            self._chk(eePos_goal, B * 6 * N, dt, "eePos_goal")
-            self._chk(xu_traj, (B if per_traj else 1) * T * (n + m), dt, "xu_traj")
-            self._chk(eePos_traj, (B if per_traj else 1) * T * 6, dt, "eePos_traj")
-            self._chk(traj_offset, B, torch.int32, "traj_offset")
-            self._chk(tracking_error, B, dt, "tracking_error")
-            if eePos is not None:
-                self._chk(eePos, B * 3, dt, "eePos")
-        if done is not None:
+            T, stride = self._chk_shift("advance_horizon(shift=True)", B, L, dt, m, lam, eePos_goal, eePos, xu_traj, eePos_traj, traj_offset, done,
+                                        tracking_error, False)
+        elif done is not None:
             self._chk(done, B, torch.int32, "done")
-        fn = self.lib.mpcg_advance_horizon if dt == torch.float32 else self.lib.mpcg_advance_horizon_f64
-        self._check(fn(self._h, m, 1 if shift else 0, _ptr(xu), _ptr(lam), _ptr(eePos_goal), _ptr(xs), _ptr(eePos),
-                       _ptr(xu_traj), _ptr(eePos_traj), T, stride, int(xu_fill_lead), _ptr(traj_offset), _ptr(done),
-                       _ptr(tracking_error), B, _stream()))
+        self._check(self._fn("advance_horizon", dt)(self._h, m, 1 if shift else 0, _ptr(xu), _ptr(lam), _ptr(eePos_goal), _ptr(xs), _ptr(eePos),
+                                                    _ptr(xu_traj), _ptr(eePos_traj), T, stride, int(xu_fill_lead), _ptr(traj_offset), _ptr(done),
+                                                    _ptr(tracking_error), B, _stream()))
         return xu
 
     def simulate_clk(self, plant: "Plant", xs, xu, timestep: float, time_offset_us, sim_time_us, sim_step: float = 2e-4, eePos=None, done=None,
@@ -680,21 +640,7 @@ class PcgSolver:
         with its own pair, bit for bit.  done (optional, int32 [B]): a trajectory with done != 0 is frozen (nothing of it is written); one whose times
         are no schedule (non-finite, negative, more than MPCG_SIM_MAX_SUBSTEPS substeps) is not simulated and gets done = MPCG_DONE_BAD_CLOCK.
         A loop passes Clocks.prev_sim_us as time_offset_us.  float32 tensors: mpcg_simulate_clk; float64: mpcg_simulate_clk_f64.  Mixed dtypes raise TypeError."""
-        B = xs.shape[0] if xs.dim() > 1 else 1
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
-        dt = self._one_dtype("simulate_clk", xs, xu, eePos)
-        self._chk(xs, B * n, dt, "xs")
-        self._chk(xu, B * ((n + m) * N - m), dt, "xu")
-        self._chk(time_offset_us, B, torch.float64, "time_offset_us")
-        self._chk(sim_time_us, B, torch.float64, "sim_time_us")
-        if eePos is not None:
-            self._chk(eePos, B * 3, dt, "eePos")
-        if done is not None:
-            self._chk(done, B, torch.int32, "done")
-        fn = self.lib.mpcg_simulate_clk if dt == torch.float32 else self.lib.mpcg_simulate_clk_f64
-        self._check(fn(self._h, plant._p, m, _ptr(xs), _ptr(xu), float(timestep), _ptr(time_offset_us), _ptr(sim_time_us), float(sim_step), _ptr(eePos),
-                       _ptr(done), B, _stream()))
-        return xs
+        return self._simulate("simulate_clk", plant, xs, xu, timestep, (time_offset_us, sim_time_us), sim_step, eePos, (done,), control_size)
 
     def advance_horizon_clk(self, xu, xs, lam, eePos_goal, eePos, xu_traj, eePos_traj, traj_offset, done, tracking_error, timestep: float, sim_time_us,
                             clocks: Clocks, did_shift=None, shift_threshold_s: float | None = None, xu_fill_lead: int = 0, control_size: int | None = None):
@@ -703,31 +649,26 @@ class PcgSolver:
         to the tensors' dtype); since wraps at the timestep; prev_sim_us = sim_time_us.  sim_time_us: float64 [B]; did_shift (optional, int32 [B])
         receives the decisions.  A frozen trajectory keeps its clock; a non-finite or negative time sets done = MPCG_DONE_BAD_CLOCK.  Every array of
         advance_horizon(shift=True) is required.  float32 tensors: mpcg_advance_horizon_clk; float64: mpcg_advance_horizon_clk_f64.  Mixed dtypes raise TypeError."""
-        B = xs.shape[0] if xs.dim() > 1 else 1
-        n, m, N = self.n, self.control_size if control_size is None else int(control_size), self.N
+        B = _batch(xs)
+        m, L = self._dims(control_size)
         dt = self._one_dtype("advance_horizon_clk", xu, xs, lam, eePos_goal, eePos, xu_traj, eePos_traj, tracking_error)
-        per_traj = xu_traj.dim() == 3
-        T = int(xu_traj.shape[-2])
-        for t, count, name in ((xu, B * ((n + m) * N - m), "xu"), (xs, B * n, "xs"), (lam, B * n * N, "lam"), (eePos_goal, B * 6 * N, "eePos_goal"),
-                               (eePos, B * 3, "eePos"), (xu_traj, (B if per_traj else 1) * T * (n + m), "xu_traj"),
-                               (eePos_traj, (B if per_traj else 1) * T * 6, "eePos_traj"), (tracking_error, B, "tracking_error")):
-            self._chk(t, count, dt, name)
-        for t, name in ((traj_offset, "traj_offset"), (done, "done"), (clocks.shifted, "clocks.shifted")) + (((did_shift, "did_shift"),) if did_shift is not None else ()):
-            self._chk(t, B, torch.int32, name)
-        for t, name in ((sim_time_us, "sim_time_us"), (clocks.prev_sim_us, "clocks.prev_sim_us"), (clocks.since_s, "clocks.since_s")):
-            self._chk(t, B, torch.float64, name)
+        self._chk_each(B, L, dt, ((xu, "xu", "xu"), (xs, "xs", "xs")))
+        T, stride = self._chk_shift("advance_horizon_clk", B, L, dt, m, lam, eePos_goal, eePos, xu_traj, eePos_traj, traj_offset, done, tracking_error, True)
+        self._chk(clocks.shifted, B, torch.int32, "clocks.shifted")
+        self._chk_each(B, L, torch.int32, ((did_shift, "one", "did_shift"),), optional=True)
+        self._chk_each(B, L, torch.float64, ((sim_time_us, "one", "sim_time_us"), (clocks.prev_sim_us, "one", "clocks.prev_sim_us"),
+                                             (clocks.since_s, "one", "clocks.since_s")))
         if shift_threshold_s is None:
             shift_threshold_s = float(torch.tensor(1 * timestep, dtype=dt))
-        fn = self.lib.mpcg_advance_horizon_clk if dt == torch.float32 else self.lib.mpcg_advance_horizon_clk_f64
-        self._check(fn(self._h, m, _ptr(xu), _ptr(lam), _ptr(eePos_goal), _ptr(xs), _ptr(eePos), _ptr(xu_traj), _ptr(eePos_traj), T, T if per_traj else 0,
-                       int(xu_fill_lead), _ptr(traj_offset), _ptr(done), _ptr(tracking_error), float(timestep), float(shift_threshold_s), _ptr(sim_time_us),
-                       _ptr(clocks.prev_sim_us), _ptr(clocks.since_s), _ptr(clocks.shifted), _ptr(did_shift), B, _stream()))
+        self._check(self._fn("advance_horizon_clk", dt)(self._h, m, _ptr(xu), _ptr(lam), _ptr(eePos_goal), _ptr(xs), _ptr(eePos), _ptr(xu_traj),
+                                                        _ptr(eePos_traj), T, stride, int(xu_fill_lead), _ptr(traj_offset), _ptr(done), _ptr(tracking_error),
+                                                        float(timestep), float(shift_threshold_s), _ptr(sim_time_us), _ptr(clocks.prev_sim_us),
+                                                        _ptr(clocks.since_s), _ptr(clocks.shifted), _ptr(did_shift), B, _stream()))
         return xu
 
     def csr_nnz(self) -> int:
         """nnz of the lower triangle (include/qdldl/sqp.cuh:148)."""
-        n, N = self.n, self.N
-        return (N - 1) * n * n + N * (n * (n + 1)) // 2
+        return self._dims()[1]["csr"]
 
     def prep_csr(self):
         """prep_csr (include/utils/csr.cuh:40-73): (col_ptr int32 [nN+1], row_ind int32 [nnz]) on the device."""
@@ -739,8 +680,8 @@ class PcgSolver:
 
     def bd_to_csr_lowertri(self, S, mult: float = 1.0):
         """Values of the QDLDL path's d_val from a bd-layout S, batched: [B, nnz]."""
-        B = S.shape[0] if S.dim() > 1 else 1
-        self._chk(S, B * 3 * self.n * self.n * self.N, torch.float32, "S")
+        B = _batch(S)
+        self._chk(S, B * self._dims()[1]["bd"], torch.float32, "S")
         val = torch.empty(B, self.csr_nnz(), device=S.device)
         self._check(self.lib.mpcg_bd_to_csr_lowertri(self._h, _ptr(S), _ptr(val), float(mult), B, _stream()))
         return val
@@ -754,10 +695,8 @@ class PcgSolver:
         return sink
 
     def bt_spmv(self, M, x, y=None, cols: int = 3):
-        B = x.shape[0] if x.dim() > 1 else 1
-        n, N = self.n, self.N
-        self._chk(M, B * 3 * n * n * N, torch.float32, "M")
-        self._chk(x, B * n * N, torch.float32, "x")
+        B = _batch(x)
+        self._chk_each(B, self._dims()[1], torch.float32, ((M, "bd", "M"), (x, "state", "x")))
         if y is None:
             y = torch.empty_like(x)
         self._check(self.lib.mpcg_bt_spmv(self._h, _ptr(M), _ptr(x), _ptr(y), B, int(cols), _stream()))

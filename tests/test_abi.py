@@ -27,6 +27,47 @@ def test_header_symbols_exported(hiplib):
     assert sorted(_lib.SYMBOLS) == names
 
 
+def _abi_class_c(decl):
+    """The ABI class of a C parameter or return type as include/mpcg.h writes it ("const float *d_S", "double out[3]", "mpcg_precond precond")."""
+    if "*" in decl or "[" in decl:
+        return "pointer"
+    base = [w for w in decl.split() if w != "const"][0]         # the type's name; a parameter's own name follows it
+    return {"int": "i32", "int32_t": "i32", "mpcg_precond": "i32", "uint32_t": "u32", "float": "f32", "double": "f64", "size_t": "size_t"}[base]
+
+
+def _abi_class_ctypes(t):
+    if t in (C.c_void_p, C.c_char_p) or isinstance(t, type(C.POINTER(C.c_int))):
+        return "pointer"
+    return {C.c_int: "i32", C.c_int32: "i32", C.c_uint32: "u32", C.c_float: "f32", C.c_double: "f64", C.c_size_t: "size_t"}[t]
+
+
+def _prototypes():
+    """name -> (return class, [parameter classes]) of every mpcg_* prototype of include/mpcg.h."""
+    src = open(os.path.join(ROOT, "include", "mpcg.h")).read()
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(mpcg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in protos, name
+        params = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+        protos[name] = (_abi_class_c(ret), [_abi_class_c(p) for p in params])
+    return protos
+
+
+def test_signatures_match_the_header():
+    """Every row of _lib.SYMBOLS against the prototype of include/mpcg.h, by ABI class (pointer / i32 / u32 / f32 / f64 / size_t) of the return type
+    and of each argument: a c_float where the header says double would load, run and pass garbage.  Needs neither the library nor a GPU."""
+    from mpcgpu_amd import _lib
+    protos = _prototypes()
+    assert sorted(protos) == _declared(), "a prototype of include/mpcg.h was not parsed"
+    assert sorted(_lib.SYMBOLS) == sorted(protos) and len(protos) == 62
+    bad = []
+    for name, (res, args) in _lib.SYMBOLS.items():
+        have = (_abi_class_ctypes(res), [_abi_class_ctypes(a) for a in args])
+        if have != protos[name]:
+            bad.append(f"{name}: _lib.py {have}, include/mpcg.h {protos[name]}")
+    assert not bad, "\n".join(bad)
+
+
 def test_exports_are_plain_c(hiplib):
     from mpcgpu_amd import _lib
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
