@@ -20,7 +20,6 @@ MU = 10.0
 def dump(root, out):
     import numpy as np
     import torch
-    sys.path.insert(0, root)
     from mpcgpu_amd import PcgSolver, Plant, iiwa
     dev = torch.device("cuda", 0)
     plant = Plant()
@@ -80,12 +79,9 @@ def compare(a, b):
 
 
 if __name__ == "__main__":
+    from ab_timing import select_build
+    root = select_build()
     argv = sys.argv[1:]
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if "--root" in argv:
-        i = argv.index("--root")
-        root = os.path.abspath(argv[i + 1])
-        del argv[i:i + 2]
     if len(argv) == 2 and argv[0] == "dump":
         sys.exit(dump(root, argv[1]))
     if len(argv) == 3 and argv[0] == "compare":

@@ -1,12 +1,10 @@
 """Timing of the clustered lane-pair kernel (pcg_lpk_cluster.hip.h, family 7): fixed iteration counts = the reference's caps, batch 1024 / 64 / 1,
 and the mixed-iteration (warm-start) batch.  (Correctness: tests/test_gpu_cluster.py.)"""
-import os, sys, json
+import json
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from mpcgpu_amd import PcgSolver, pcg_config, synth, _lib as _L
-if os.environ.get("AB_LIB"):
-    _L.LIB_PATH = os.environ["AB_LIB"]
+from ab_timing import select_build
+select_build()
+from mpcgpu_amd import PcgSolver, pcg_config, synth
 dev = torch.device("cuda")
 
 

@@ -11,32 +11,16 @@ traffic.  Needs an MI355X:
     [AB_LIB=<another build's libmpcg_hip.so>] python tools/time_block_solve_f64.py [reps]
 (tools/time_block_solve.py is the older comparison of the float solve against PCG.)"""
 import json
-import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from ab_timing import alternate, select_build, windows_of
+
+select_build()
 import bench  # noqa: E402
-from mpcgpu_amd import PcgSolver, _lib as _L  # noqa: E402
-if os.environ.get("AB_LIB"):                      # A/B against another build of the library
-    _L.LIB_PATH = os.environ["AB_LIB"]
-
-WINDOWS = 7
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3          # microseconds per call
+from mpcgpu_amd import PcgSolver  # noqa: E402
 
 
 def main():
@@ -65,19 +49,11 @@ def main():
             out[w] = (lam64 if w == "f64" else lam).cpu().numpy().astype(np.float64)
         scale = np.abs(out["f64"]).max()
         diff = {w: float(f"{np.abs(out[w] - out['f64']).max() / scale:.3g}") for w in ("float", "option")}
-        t0 = time.time()
-        while time.time() - t0 < 0.05:
-            for w in names:
-                call(w)
-            torch.cuda.synchronize()
-        rounds = []
-        for _ in range(WINDOWS):
-            rounds.append([timed(lambda: call(w), reps) for w in names])
-        med = [statistics.median(r[i] for r in rounds) for i in range(3)]
+        med, rounds = alternate([lambda w=w: call(w) for w in names], reps)
         print(json.dumps({"knots": N, "batch": B, "reps": reps, "float_us": round(med[0], 2), "option_us": round(med[1], 2), "f64_us": round(med[2], 2),
                           "option_over_float": round(med[1] / med[0], 3), "f64_over_float": round(med[2] / med[0], 3),
                           "finite": bool(all(np.isfinite(v).all() for v in out.values())), "float_vs_f64": diff["float"], "option_vs_f64": diff["option"],
-                          "windows": [[round(v, 2) for v in r] for r in rounds]}), flush=True)
+                          "windows": windows_of(rounds)}), flush=True)
     return 0
 
 

@@ -7,29 +7,15 @@ alternated in one process after 50 ms of warm-up, device events around `reps` ba
 window spread (max / min).  Needs an MI355X:  python tools/time_clocks.py [reps]"""
 import ctypes as C
 import json
-import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from ab_timing import alternate, min_max, select_build, windows_of
+
+select_build()
 from mpcgpu_amd import PcgSolver, Plant, iiwa  # noqa: E402
-
-WINDOWS = 7
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3          # microseconds per call
 
 
 def main():
@@ -80,28 +66,15 @@ def main():
             d_xs.copy_(d_xs0)                            # (the plant must not drift away over thousands of timed steps)
 
         fns = (scalar, clk_uniform, clk_mixed, advance, advance_clk)
-        t0 = time.time()
-        while time.time() - t0 < 0.05:
-            for fn in fns:
-                fn()
-            reset()
-            torch.cuda.synchronize()
+        med, rounds = alternate(fns, reps, reset=reset)
         assert int(did.sum()) == B and int(done.sum()) == 0
-        rounds = []
-        for _ in range(WINDOWS):
-            row = []
-            for fn in fns:
-                reset()
-                row.append(timed(fn, reps))
-            rounds.append(row)
-        med = [statistics.median(r[i] for r in rounds) for i in range(len(fns))]
-        spread = [max(r[i] for r in rounds) / min(r[i] for r in rounds) for i in range(len(fns))]
+        spread = [hi / lo for lo, hi in (min_max(rounds, i) for i in range(len(fns)))]
         print(json.dumps({"knots": N, "batch": B, "reps": reps, "simulate_us": round(med[0], 2), "simulate_clk_uniform_us": round(med[1], 2),
                           "simulate_clk_mixed_1000_4000_us": round(med[2], 2), "advance_horizon_shift_us": round(med[3], 2),
                           "advance_horizon_clk_shift_us": round(med[4], 2), "clk_uniform_over_scalar": round(med[1] / med[0], 3),
                           "clk_mixed_over_scalar": round(med[2] / med[0], 3), "advance_clk_over_scalar": round(med[4] / med[3], 3),
                           "window_spread_max_over_min": [round(v, 3) for v in spread],
-                          "windows": [[round(v, 2) for v in r] for r in rounds]}), flush=True)
+                          "windows": windows_of(rounds)}), flush=True)
     return 0
 
 

@@ -10,47 +10,19 @@ the large shape), gravity torques only.  One JSON line per shape and call.
 plant alone: that is how the default is compared with its parent, in the same session on the same box.  Needs an MI355X:
     python tools/time_gravity.py [--root DIR] [reps]"""
 import json
-import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if "--root" in sys.argv:
-    i = sys.argv.index("--root")
-    ROOT = os.path.abspath(sys.argv[i + 1])
-    del sys.argv[i:i + 2]
-sys.path.insert(0, ROOT)
+from ab_timing import alternate, min_max, select_build, windows_of
+
+select_build()
 from mpcgpu_amd import PcgSolver, Plant, iiwa  # noqa: E402
 
-WINDOWS = 7
 STEPS9 = [0.0] + [-1.0 / (1 << p) for p in range(8)]
 MU = 10.0
 GRAVITY = (0.0, 0.0, 9.81)
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3          # microseconds per call
-
-
-def alternate(calls, reps):
-    """Medians of WINDOWS windows per call, after 50 ms of warm-up; the windows alternate between the calls."""
-    t0 = time.time()
-    while time.time() - t0 < 0.05:
-        for call in calls:
-            call()
-        torch.cuda.synchronize()
-    rounds = [[timed(c, reps) for c in calls] for _ in range(WINDOWS)]
-    return [statistics.median(w[i] for w in rounds) for i in range(len(calls))], rounds
 
 
 def main():
@@ -84,9 +56,9 @@ def main():
             finite = all(bool(torch.isfinite(t).all()) for o in outs for t in (o if isinstance(o, tuple) else (o,)) if t is not None)
             del outs
             med, rounds = alternate([(lambda p=p: fn(p)) for p in plants], reps)
-            col0 = [w[0] for w in rounds]
-            rec = {"call": name, "knots": N, "batch": B, "reps": reps, "plain_us": round(med[0], 2), "plain_min_max_us": [round(min(col0), 2), round(max(col0), 2)],
-                   "finite": finite, "windows": [[round(v, 2) for v in w] for w in rounds]}
+            lo, hi = min_max(rounds, 0)
+            rec = {"call": name, "knots": N, "batch": B, "reps": reps, "plain_us": round(med[0], 2), "plain_min_max_us": [round(lo, 2), round(hi, 2)],
+                   "finite": finite, "windows": windows_of(rounds)}
             if len(plants) > 1:
                 rec.update(gravity_us=round(med[1], 2), gravity_over_plain=round(med[1] / med[0], 3))
             else:
@@ -100,9 +72,9 @@ def main():
             q = torch.from_numpy(np.ascontiguousarray(xu.reshape(-1)[:count * 7].reshape(count, 7))).to(dev)      # (any finite angles)
             tau = torch.empty(count, 7, device=dev)
             med, rounds = alternate([lambda: sol.inverse_dynamics(plants[1], q, tau=tau)], reps)
-            col0 = [w[0] for w in rounds]
+            lo, hi = min_max(rounds, 0)
             print(json.dumps({"call": "inverse_dynamics", "states": count, "reps": reps, "gravity_us": round(med[0], 2),
-                              "min_max_us": [round(min(col0), 2), round(max(col0), 2)], "finite": bool(torch.isfinite(tau).all())}), flush=True)
+                              "min_max_us": [round(lo, 2), round(hi, 2)], "finite": bool(torch.isfinite(tau).all())}), flush=True)
     return 0
 
 

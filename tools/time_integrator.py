@@ -10,52 +10,18 @@ One JSON line per shape and call.
 setting: that is how the default is compared with its parent, in the same session on the same box.  Needs an MI355X:
     python tools/time_integrator.py [--root DIR] [reps]"""
 import json
-import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if "--root" in sys.argv:
-    i = sys.argv.index("--root")
-    ROOT = os.path.abspath(sys.argv[i + 1])
-    del sys.argv[i:i + 2]
-sys.path.insert(0, ROOT)
+from ab_timing import alternate, min_max, select_build, windows_of
+
+select_build()
 from mpcgpu_amd import PcgSolver, Plant, iiwa  # noqa: E402
 
-WINDOWS = 7
 STEPS9 = [0.0] + [-1.0 / (1 << p) for p in range(8)]
 MU = 10.0
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3          # microseconds per call
-
-
-def alternate(calls, reps):
-    """calls: (setup, call) pairs.  Medians of WINDOWS windows per call, after 50 ms of warm-up; the windows alternate between the calls, and a window's
-    setup (the option) runs in front of it, outside the timed region: at one trajectory the back-to-back calls are bound by the host's launch rate, where a
-    mpcg_set_option per call would cost the library that has the option 0.7 us a call."""
-    def window(setup, call):
-        setup()
-        return timed(call, reps)
-    t0 = time.time()
-    while time.time() - t0 < 0.05:
-        for setup, call in calls:
-            setup()
-            call()
-        torch.cuda.synchronize()
-    rounds = [[window(*c) for c in calls] for _ in range(WINDOWS)]
-    return [statistics.median(w[i] for w in rounds) for i in range(len(calls))], rounds
 
 
 def main():
@@ -101,11 +67,13 @@ def main():
             torch.cuda.synchronize()
             finite = all(bool(torch.isfinite(t).all()) for o in outs for t in (o if isinstance(o, tuple) else (o,)) if t is not None)
             del outs
-            med, rounds = alternate([(lambda v=v: option(key, v), fn) for v in settings], reps)
+            # (a window's option is set in front of it, outside the timed region: at one trajectory the back-to-back calls are bound by the host's launch rate,
+            # where a mpcg_set_option per call would cost the library that has the option 0.7 us a call)
+            med, rounds = alternate([fn] * len(settings), reps, reset=[lambda v=v: option(key, v) for v in settings])
             option(key, 0)
-            col0 = [w[0] for w in rounds]
-            rec = {"call": name, "knots": N, "batch": B, "reps": reps, "explicit_us": round(med[0], 2), "explicit_min_max_us": [round(min(col0), 2), round(max(col0), 2)],
-                   "finite": finite, "windows": [[round(v, 2) for v in w] for w in rounds]}
+            lo, hi = min_max(rounds, 0)
+            rec = {"call": name, "knots": N, "batch": B, "reps": reps, "explicit_us": round(med[0], 2), "explicit_min_max_us": [round(lo, 2), round(hi, 2)],
+                   "finite": finite, "windows": windows_of(rounds)}
             if len(settings) > 1:
                 rec.update(semi_implicit_us=round(med[1], 2), semi_over_explicit=round(med[1] / med[0], 3))
             else:

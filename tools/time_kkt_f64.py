@@ -8,43 +8,19 @@ outputs rounded to float are compared with the float entry's (the inputs are flo
 entry forms its trial iterate in float).  One JSON line per shape and call.  Needs an MI355X:
     python tools/time_kkt_f64.py [reps]"""
 import json
-import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from ab_timing import alternate, select_build, windows_of
+
+select_build()
 from mpcgpu_amd import PcgSolver, Plant, iiwa  # noqa: E402
 
-WINDOWS = 7
 STEPS9 = [0.0] + [-1.0 / (1 << p) for p in range(8)]
 MU = 10.0
 TORCH = {np.float32: torch.float32, np.float64: torch.float64}
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3          # microseconds per call
-
-
-def alternate(calls, reps):
-    """calls: (float entry, double entry).  Medians of WINDOWS windows each, after 50 ms of warm-up; the windows alternate."""
-    t0 = time.time()
-    while time.time() - t0 < 0.05:
-        for c in calls:
-            c()
-        torch.cuda.synchronize()
-    rounds = [[timed(c, reps) for c in calls] for _ in range(WINDOWS)]
-    return [statistics.median(w[i] for w in rounds) for i in range(2)], rounds
 
 
 def main():
@@ -78,7 +54,7 @@ def main():
         for name, fn in (("generate_kkt", kkt), ("compute_merit", mer)):
             med, rounds = alternate((lambda: fn(np.float32), lambda: fn(np.float64)), reps)
             rec = {"call": name, "knots": N, "batch": B, "reps": reps, "float_us": round(med[0], 2), "f64_us": round(med[1], 2),
-                   "f64_over_float": round(med[1] / med[0], 3), "windows": [[round(v, 2) for v in w] for w in rounds]}
+                   "f64_over_float": round(med[1] / med[0], 3), "windows": windows_of(rounds)}
             if name == "generate_kkt":
                 rec.update(f64_rounded_is_float_bitwise=bool(same), f64_output_bytes=out_bytes)
             else:

@@ -5,28 +5,18 @@ iteration, less its nine device-to-host copies).  1024 x 128 knots and 1 x 32; t
 device events around `reps` back-to-back calls.  Needs an MI355X:  python tools/time_merit.py [reps]"""
 import ctypes as C
 import json
-import os
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from ab_timing import alternate, select_build
+
+select_build()
 from mpcgpu_amd import PcgSolver, Plant, iiwa  # noqa: E402
 
 STEPS = [0.0] + [-1.0 / (1 << p) for p in range(8)]
 ROUNDS = 5
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3          # microseconds per call
 
 
 def main():
@@ -63,14 +53,7 @@ def main():
                 rc = lib.mpcg_generate_kkt(h, pl, 7, iiwa.TIMESTEP, p(dee), p(dxs), p(z), iiwa.QD_COST, iiwa.r_cost(N), p(G), p(Cd), p(g), p(c), B, stream)
                 assert rc == 0
 
-        for _ in range(3):
-            new(); old()
-        torch.cuda.synchronize()
-        rounds = []
-        for _ in range(ROUNDS):
-            a = timed(new, reps)
-            b = timed(old, reps)
-            rounds.append((a, b))
+        _, rounds = alternate((new, old), reps, windows=ROUNDS, warmup_rounds=3)
         res = {"knots": N, "batch": B, "reps": reps, "compute_merit_us": [round(a, 2) for a, _ in rounds], "nine_kkt_calls_us": [round(b, 2) for _, b in rounds],
                "ratio": [round(b / a, 2) for a, b in rounds], "faster_in_every_round": all(a < b for a, b in rounds)}
         print(json.dumps(res), flush=True)

@@ -7,31 +7,18 @@ builds' merits of the timed inputs are compared (relative to max(1, |merit|)).  
     python tools/time_merit_f32.py [reps]
 (tools/time_merit.py is the older comparison of the merit call against nine KKT calls.)"""
 import json
-import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from ab_timing import alternate, select_build, windows_of
+
+select_build()
 from mpcgpu_amd import PcgSolver, Plant, iiwa  # noqa: E402
 
-WINDOWS = 7
 STEPS9 = [0.0] + [-1.0 / (1 << p) for p in range(8)]
 MU = 10.0
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3          # microseconds per call
 
 
 def main():
@@ -58,17 +45,10 @@ def main():
             torch.cuda.synchronize()
             out.append(merit.cpu().numpy().astype(np.float64))
         diff = float((np.abs(out[1] - out[0]) / np.maximum(1.0, np.abs(out[0]))).max())
-        t0 = time.time()
-        while time.time() - t0 < 0.05:
-            call(0); call(1)
-            torch.cuda.synchronize()
-        rounds = []
-        for _ in range(WINDOWS):
-            rounds.append([timed(lambda: call(f32), reps) for f32 in (0, 1)])
-        med = [statistics.median(w[i] for w in rounds) for i in range(2)]
+        med, rounds = alternate([lambda f32=f32: call(f32) for f32 in (0, 1)], reps)
         print(json.dumps({"knots": N, "batch": B, "num_steps": len(steps), "reps": reps, "merit_default_us": round(med[0], 2),
                           "merit_f32_us": round(med[1], 2), "default_over_f32": round(med[0] / med[1], 3), "finite": bool(np.isfinite(out[1]).all()),
-                          "worst_f32_vs_default": float(f"{diff:.3g}"), "windows": [[round(v, 2) for v in w] for w in rounds]}), flush=True)
+                          "worst_f32_vs_default": float(f"{diff:.3g}"), "windows": windows_of(rounds)}), flush=True)
     return 0
 
 

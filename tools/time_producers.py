@@ -7,13 +7,10 @@ schur_generic.hip.h ("producers_generic" = 1) every other shape runs anyway (for
 Every figure is the median of seven timed calls behind 50 ms of back-to-back calls.
 --rho-vector times the formation alone, float and double: mpcg_form_schur(_f64) with a scalar rho against mpcg_form_schur_rhov(_f64) with a device
 vector of the same value, ALTERNATED call by call in one process behind a common warm-up — median and min-max of seven calls each."""
-import argparse, json, os, sys, time
+import argparse, json, sys, time
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from mpcgpu_amd import _lib as _L
-if os.environ.get("AB_LIB"):                      # A/B against another build of the library
-    _L.LIB_PATH = os.environ["AB_LIB"]
+from ab_timing import alternate, min_max, select_build
+select_build()
 from mpcgpu_amd import PcgSolver, synth
 
 ap = argparse.ArgumentParser()
@@ -73,21 +70,11 @@ def rho_vector_ab():
         vec = torch.full((B,), 1e-3, device="cuda", dtype=dt)
         calls = {"scalar": lambda: sol.form_schur(Gd, Cd, gd, cd, 1e-3, "ss", S=Sd, Pinv=Pd, gamma=gmd),
                  "vector": lambda: sol.form_schur(Gd, Cd, gd, cd, vec, "ss", S=Sd, Pinv=Pd, gamma=gmd)}
-        t0 = time.perf_counter()
-        while time.perf_counter() - t0 < 0.1:            # common warm-up, both entries
-            for fn in calls.values():
-                fn()
-            torch.cuda.synchronize()
-        ts = {k: [] for k in calls}
-        for _ in range(7):
-            for k, fn in calls.items():
-                Gd.copy_(G0d)
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); fn(); e1.record(); torch.cuda.synchronize(); ts[k].append(e0.elapsed_time(e1) * 1e3)
-        for k, v in ts.items():
+        med, rounds = alternate(list(calls.values()), 1, reset=lambda: Gd.copy_(G0d), warmup_s=0.1)      # (the formation works on G in place)
+        for i, k in enumerate(calls):
+            lo, hi = min_max(rounds, i)
             rec = {"state": n, "control": m, "knots": N, "batch": B, "dtype": str(dt).split(".")[1], "rho": k, "step": "form_schur", "chunk": sol.get_option("last_schur_chunk"),
-                   "median_us": round(float(np.median(v)), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2)}
+                   "median_us": round(med[i], 2), "min_us": round(lo, 2), "max_us": round(hi, 2)}
             print(json.dumps(rec) if a.json else "(%2d,%2d) %4d x %-4d %-8s rho %-7s form_schur  median %9.1f us  (min %.1f, max %.1f)"
                   % (n, m, B, N, rec["dtype"], k, rec["median_us"], rec["min_us"], rec["max_us"]))
 

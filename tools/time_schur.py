@@ -2,13 +2,10 @@
 """Time mpcg_form_schur / mpcg_compute_dz on B trajectories x N knots (default 1024 x 128):  time_schur.py [N [B]]
 — the register-resident chunk-walking formation at its automatic and at forced chunk lengths, the LDS kernels, both dz kernels, each with
 the rate on its algorithmic-bytes model."""
-import os, sys
+import sys
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from mpcgpu_amd import _lib as _L
-if os.environ.get("AB_LIB"):                      # A/B against another build of the library (tools/_prof/ab/)
-    _L.LIB_PATH = os.environ["AB_LIB"]
+from ab_timing import select_build
+select_build()
 from mpcgpu_amd import PcgSolver, synth
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 1024

@@ -6,29 +6,15 @@ reference's launch structure (simple_simulate launches a kernel per substep), an
 windows.  Needs an MI355X:  python tools/time_simulate.py [reps]"""
 import ctypes as C
 import json
-import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from ab_timing import alternate, select_build, windows_of
+
+select_build()
 from mpcgpu_amd import PcgSolver, Plant, iiwa  # noqa: E402
-
-WINDOWS = 7
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3          # microseconds per call
 
 
 def main():
@@ -64,21 +50,10 @@ def main():
         def reset():
             d_xs.copy_(d_xs0)                            # (the plant must not drift away over thousands of timed steps)
 
-        t0 = time.time()
-        while time.time() - t0 < 0.05:
-            one_call(); eleven_calls(); advance(); reset()
-            torch.cuda.synchronize()
-        rounds = []
-        for _ in range(WINDOWS):
-            row = []
-            for fn in (one_call, eleven_calls, advance):
-                reset()
-                row.append(timed(fn, reps))
-            rounds.append(row)
-        med = [statistics.median(r[i] for r in rounds) for i in range(3)]
+        med, rounds = alternate((one_call, eleven_calls, advance), reps, reset=reset)
         print(json.dumps({"knots": N, "batch": B, "reps": reps, "simulate_one_call_us": round(med[0], 2), "simulate_eleven_calls_us": round(med[1], 2),
                           "advance_horizon_shift_us": round(med[2], 2), "eleven_over_one": round(med[1] / med[0], 2),
-                          "windows": [[round(v, 2) for v in r] for r in rounds]}), flush=True)
+                          "windows": windows_of(rounds)}), flush=True)
     return 0
 
 

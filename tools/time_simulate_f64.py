@@ -9,51 +9,21 @@ timing the double simulate at the substep (double)2e-4f is compared with the flo
 rounding to float only: not bitwise).  One JSON line per shape and call.  Not a gate.  Needs an MI355X:
     python tools/time_simulate_f64.py [reps]"""
 import json
-import os
-import statistics
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from ab_timing import alternate, select_build, windows_of
+
+select_build()
 from mpcgpu_amd import PcgSolver, Plant, iiwa  # noqa: E402
 
-WINDOWS = 7
 WARMUP = 50
 TORCH = {np.float32: torch.float32, np.float64: torch.float64}
 SIM_US = 2000.0
 SS = {np.float32: float(np.float32(2e-4)), np.float64: 2e-4}
 n, m = 14, 7
-
-
-def timed(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps * 1e3          # microseconds per call
-
-
-def alternate(calls, reset, reps):
-    """calls: (float entry, double entry).  Medians of WINDOWS windows each, after WARMUP calls of each; the windows alternate; reset() before every window."""
-    for c in calls:
-        reset()
-        for _ in range(WARMUP):
-            c()
-    torch.cuda.synchronize()
-    rounds = []
-    for _ in range(WINDOWS):
-        row = []
-        for c in calls:
-            reset()
-            torch.cuda.synchronize()
-            row.append(timed(c, reps))
-        rounds.append(row)
-    return [statistics.median(w[i] for w in rounds) for i in range(2)], rounds
 
 
 def main():
@@ -94,10 +64,10 @@ def main():
         torch.cuda.synchronize()
         diff = float(((x64 - x32.double()).abs() / x64.abs().clamp(min=1.0)).max())
         for name, fn in (("simulate", sim), ("advance_horizon", adv)):
-            med, rounds = alternate((lambda: fn(np.float32), lambda: fn(np.float64)), reset, reps)
+            med, rounds = alternate((lambda: fn(np.float32), lambda: fn(np.float64)), reps, reset=reset, warmup_rounds=WARMUP)
             assert int(done.max()) == 0                  # no trajectory used its plan up: every timed shift did the whole work
             rec = {"call": name, "knots": N, "batch": B, "reps": reps, "float_us": round(med[0], 2), "f64_us": round(med[1], 2),
-                   "f64_over_float": round(med[1] / med[0], 3), "windows": [[round(v, 2) for v in w] for w in rounds]}
+                   "f64_over_float": round(med[1] / med[0], 3), "windows": windows_of(rounds)}
             if name == "simulate":
                 rec.update(sim_time_us=SIM_US, substeps_per_call=11, worst_f64_vs_float=float(f"{diff:.3g}"))
             print(json.dumps(rec), flush=True)

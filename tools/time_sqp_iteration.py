@@ -5,10 +5,10 @@ in two builds of the same chain on the same iterate: "scalar" (mpcg_form_schur w
 examples/sqp_batched_iiwa runs without --adapt-rho) and "adaptive" (mpcg_form_schur_rhov reading the rho vector + mpcg_line_search_step_rho).
 Each is captured once after an eager iteration; the replays are ALTERNATED in one process behind a common warm-up, every timed replay starts
 from the same saved state (restored outside the timed region): median and min-max of seven replays each, device events."""
-import argparse, json, os, sys, time
+import argparse, json
 import numpy as np, torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from ab_timing import alternate, min_max, select_build
+select_build()
 from mpcgpu_amd import PcgSolver, Plant, iiwa, pcg_config
 
 ap = argparse.ArgumentParser()
@@ -52,24 +52,14 @@ class Chain:
         else:
             s.line_search_step(merit, STEPS, st["ref"], dz, st["xu"], step=self.step)
 
-    def replay(self):
+    def restore(self):
         for k, v in self.saved.items():
             self.state[k].copy_(v)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); self.graph.replay(); e1.record(); torch.cuda.synchronize()
-        return e0.elapsed_time(e1) * 1e3                     # us
 
 
 chains = {"scalar": Chain(False), "adaptive": Chain(True)}
-t0 = time.perf_counter()
-while time.perf_counter() - t0 < 0.2:                        # common warm-up: the clocks are up before anything is timed
-    for ch in chains.values():
-        ch.replay()
-ts = {k: [] for k in chains}
-for _ in range(7):
-    for k, ch in chains.items():
-        ts[k].append(ch.replay())
-for k, v in ts.items():
-    rec = {"knots": N, "batch": B, "chain": k, "median_us": round(float(np.median(v)), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2)}
+med, rounds = alternate([ch.graph.replay for ch in chains.values()], 1, reset=[ch.restore for ch in chains.values()], warmup_s=0.2)
+for i, k in enumerate(chains):
+    lo, hi = min_max(rounds, i)
+    rec = {"knots": N, "batch": B, "chain": k, "median_us": round(med[i], 2), "min_us": round(lo, 2), "max_us": round(hi, 2)}
     print(json.dumps(rec) if a.json else "%4d x %-4d %-8s iteration (graph replay)  median %9.1f us  (min %.1f, max %.1f)" % (B, N, k, rec["median_us"], rec["min_us"], rec["max_us"]))
