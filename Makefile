@@ -23,7 +23,7 @@ LINKLIB  := -L$(PKG) -lmpcg_hip $(RPATH)
 
 LIB_SRCS := $(wildcard $(CSRC)/*.hip)
 LIB_OBJS := $(patsubst $(CSRC)/%.hip,$(CSRC)/%.o,$(LIB_SRCS))
-LIB_DEPS := $(wildcard $(CSRC)/*.h $(CSRC)/*.hpp $(CSRC)/*.inc) $(INC)/mpcg.h
+LIB_DEPS := $(wildcard $(CSRC)/*.h $(CSRC)/*.hpp $(CSRC)/*.inc) $(INC)/mpcg.h $(INC)/mpcg_riccati.h
 
 SHIM_PCG   := $(INC)/gbd_pcg_compat/gpu_pcg.cuh $(INC)/gbd_pcg_compat/gpuassert.cuh $(INC)/gbd_pcg_compat/utils.cuh
 SHIM_STEPS := $(INC)/mpcgpu_compat/linsys_steps.cuh

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/mpcg.h.
+"""ctypes binding of the C ABI declared in include/mpcg.h and include/mpcg_riccati.h.
 
 The library is the product: if it is missing or does not load, importing fails loudly —
 there is no Python/CPU fallback for any compute entry point.
@@ -103,6 +103,11 @@ SYMBOLS = {
     "mpcg_get_option": (_int, [_p, C.c_char_p, C.POINTER(_int)]),
 }
 
+# the second table, include/mpcg_riccati.h (tests/test_riccati_ref_cpu.py holds each row against that header's prototype)
+SYMBOLS_RICCATI = {
+    **_pair("mpcg_riccati_gains", [_p, _u32, _p, _p, _T, _p, _p, _u32, _p]),
+}
+
 _lib = None
 
 
@@ -114,7 +119,7 @@ def load() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m mpcgpu_amd.build` "
                 "(hipcc --offload-arch=gfx950).  mpcgpu_amd has no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in {**SYMBOLS, **SYMBOLS_RICCATI}.items():
             fn = getattr(lib, name)      # AttributeError if the .so does not export it
             fn.restype = res
             fn.argtypes = args

@@ -37,7 +37,7 @@ def sources():
 
 
 def deps():
-    return sources() + [p for pat in ("*.h", "*.hpp", "*.inc") for p in glob.glob(os.path.join(CSRC, pat))] + [os.path.join(_ROOT, "include", "mpcg.h")]
+    return sources() + [p for pat in ("*.h", "*.hpp", "*.inc") for p in glob.glob(os.path.join(CSRC, pat))] + [os.path.join(_ROOT, "include", h) for h in ("mpcg.h", "mpcg_riccati.h")]
 
 
 # (tools/prof_phases.py builds a -DMPCG_PROF twin of the library in one hipcc call: the Makefile's flags + -shared)

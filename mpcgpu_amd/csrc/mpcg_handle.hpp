@@ -1,5 +1,5 @@
 // mpcg_handle.hpp — what the translation units of libmpcg_hip.so share: the handle behind include/mpcg.h, the error convention, the HIP_TRY
-// macro.  The library is four translation units over this header (Makefile: every csrc/*.hip is compiled on its own and linked once):
+// macro.  The library is five translation units over this header (Makefile: every csrc/*.hip is compiled on its own and linked once):
 //   mpcg_pcg.hip        handle / options / the PCG launch policy and entry points (pcg_*.hip.h kernels): every option is one row of one table
 //                       (kOptions), the five solve entries share one argument check and one argument fill (solve_ends, solve_args), the float and
 //                       double symmetry latches one check launch, one re-open rule and one warning
@@ -9,6 +9,7 @@
 //                       plant simulation + horizon shift (sim_plant.hip.h), inverse dynamics (invdyn_plant.hip.h): one host path per call for float and
 //                       double, each kernel family selected in one place (launch_kkt, launch_merit_points, simulate_impl)
 //   mpcg_ldl.hip        the host LDL^T twin of the reference's QDLDL path (ldl_host.hpp)
+//   mpcg_riccati.hip    the Riccati feedback gains of include/mpcg_riccati.h (riccati.hip.h): one host path for float and double
 // Every kernel header is included by exactly one of them (their non-template kernels have external linkage).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -31,6 +31,7 @@ def layout(n: int, m: int, N: int) -> dict:
             "xu": (n + m) * N - m,                             # xu, g, dz
             "G_dense": (n * n + m * m) * N - m * m,
             "C_dense": (n * n + n * m) * (N - 1),
+            "gains": (N - 1) * m * n,                          # K of riccati_gains
             "goals": 6 * N,                                    # eePos_traj of a call, eePos_goal
             "xs": n,
             "eePos": 3,
@@ -49,6 +50,15 @@ class pcg_config:
 def pcgSharedMemSize(state_size: int, knot_points: int) -> int:
     """Dynamic LDS bytes of one trajectory's workgroup (0 = unsupported shape)."""
     return int(_lib.load().mpcg_pcg_lds_bytes(state_size, knot_points))
+
+
+def gain_blocks(K: torch.Tensor, n: int, m: int) -> torch.Tensor:
+    """The gains of PcgSolver.riccati_gains, flat [B, (N-1) m n] (or [(N-1) m n]) in column-major m x n blocks, as a VIEW [B, N-1, m, n]:
+    gain_blocks(K, n, m)[b, k] @ dx is K_k dx of trajectory b.  No copy: the view is strided."""
+    B = _batch(K)
+    if K.numel() % (B * m * n):
+        raise ValueError(f"gain_blocks: {K.numel()} elements are not {B} trajectories of {m} x {n} blocks")
+    return K.view(B, -1, n, m).transpose(-1, -2)
 
 
 def _ptr(t: torch.Tensor | None):
@@ -400,6 +410,25 @@ class PcgSolver:
         lam = self._out(lam, (B, L["state"]), dt, gamma, "lambda")
         self._check(self._fn("block_solve", dt)(self._h, _ptr(S), _ptr(gamma), _ptr(lam), B, _stream()))
         return lam
+
+    def riccati_gains(self, G, C, rho, control_size: int | None = None, K=None):
+        """The time-varying LQR gains K_k = du_k/dx_k of the regularised LQ subproblem, by a backward Riccati sweep over the KKT blocks
+        (mpcg_riccati_gains, include/mpcg_riccati.h).  CALL IT BEFORE form_schur, which overwrites G with its block inverses.
+        G: [B, (n^2+m^2)N - m^2] and C: [B, (n^2+nm)(N-1)] as generate_kkt returns them; rho: a Python float, or a device tensor [B] of the
+        arrays' dtype (what line_search_step_rho adapts), read when the kernel runs.  Returns K flat [B, (N-1) m n]: `gain_blocks` views it
+        as [B, N-1, m, n].  float32 tensors: mpcg_riccati_gains (float64 inside, K rounded once); float64 tensors: mpcg_riccati_gains_f64.
+        Mixed dtypes raise TypeError."""
+        B = _batch(G)
+        m, L = self._dims(control_size)
+        rho_t = rho if isinstance(rho, torch.Tensor) else None
+        dt = self._one_dtype("riccati_gains", G, C, rho_t, K)
+        self._chk_each(B, L, dt, ((G, "G_dense", "G"), (C, "C_dense", "C")))
+        if rho_t is not None:
+            self._chk(rho_t, B, dt, "rho")
+        K = self._out(K, (B, L["gains"]), dt, G, "K")
+        self._check(self._fn("riccati_gains", dt)(self._h, m, _ptr(G), _ptr(C), 0.0 if rho_t is not None else float(rho), _ptr(rho_t), _ptr(K), B,
+                                                  _stream()))
+        return K
 
     def form_schur(self, G_dense, C_dense, g, c, rho, precond: str = "ss", S=None, Pinv=None, gamma=None,
                    control_size: int | None = None):
