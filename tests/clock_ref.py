@@ -6,13 +6,12 @@ INFRASTRUCTURE.  Python floats are IEEE doubles with one rounding per operation 
     update          the clock bookkeeping of include/mpcsim.cuh:294-352 for ONE trajectory and ONE control update
     Clock           that state carried over updates, counting shifts
     control_update  one control update of one trajectory composed from the restatements: simulate under the previous plan from the clock's
-                    prev_sim_us, then advance with the clock's decision (sim_ref for float32 arrays, sim_ref_f64 for float64)"""
+                    prev_sim_us, then advance with the clock's decision (tests/plant_ref.py in the arrays' precision)"""
 import math
 
 import numpy as np
 
-import sim_ref
-import sim_ref_f64
+import plant_ref
 
 MAX_SUBSTEPS = 65536                     # MPCG_SIM_MAX_SUBSTEPS
 DONE_BAD_CLOCK = 2                       # MPCG_DONE_BAD_CLOCK
@@ -74,9 +73,8 @@ def control_update(model, N, timestep, clock, sim_us, sim_step, xs, xu_old, xu, 
                    dtype=np.float32):
     """One control update of ONE live trajectory.  -> (new xs (float64 values, as the restatement carries them), new (xu, lam, goal, traj_offset,
     done, tracking error or None), shift).  xs_new is rounded to `dtype` before it is handed to advance, as the entry stores it."""
-    ref = sim_ref if np.dtype(dtype) == np.float32 else sim_ref_f64
-    x = ref.simulate(model, xs, xu_old, N, timestep, clock.prev_sim_us, sim_us, sim_step)
+    x = plant_ref.simulate(model, xs, xu_old, N, timestep, clock.prev_sim_us, sim_us, sim_step, double=np.dtype(dtype) == np.float64)
     ee = model.ee_pos(x[:7])
     shift = clock.update(sim_us)
-    out = ref.advance(shift, N, xu, lam, goal, np.asarray(x, dtype), np.asarray(ee, dtype), xu_traj, ee_traj, traj_steps, traj_offset, done, lead)
+    out = plant_ref.advance(shift, N, xu, lam, goal, np.asarray(x, dtype), np.asarray(ee, dtype), xu_traj, ee_traj, traj_steps, traj_offset, done, lead, dtype)
     return x, out, shift

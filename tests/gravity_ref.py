@@ -7,7 +7,7 @@ its negative.
 
     GravityChain    chain_models.Chain whose rnea starts from ap[3:] = base_accel, and whose mass_matrix evaluates its columns WITHOUT it (the inherited
                     one calls self.rnea(q, 0, e_j) and would add the gravity torques to every column).  Every other restatement takes the model as an
-                    argument — iiwa_ref.generate_kkt, merit_ref(_f64).merits, sim_ref(_f64).simulate, integrator_ref.* — and follows with no further code.
+                    argument — iiwa_ref.generate_kkt and every stage of tests/plant_ref.py — and follows with no further code.
     Gravity32       merit_ref_f32.Model32, the separate float model, with the same two changes
     potential       V(q) = sum_i m_i base_accel . c_i(q), the link centres of mass taken through Xhom: independent of the recursion, so
                     dV/dq = ID(q, 0, 0) pins the sign and the axes (tests/test_gravity_ref_cpu.py)

@@ -1,4 +1,4 @@
-"""Float32 restatement of tests/merit_ref.py's merit — TEST INFRASTRUCTURE, the yardstick of the tolerance the tests of `"merit_f32"` = 1
+"""Float32 restatement of tests/plant_ref.py's merit — TEST INFRASTRUCTURE, the yardstick of the tolerance the tests of `"merit_f32"` = 1
 (mpcgpu_amd/csrc/merit_plant_f32.hip.h) use: what plain float arithmetic — the reference's own, include/common/merit.cuh with T = float — makes of the
 same formula on the same inputs.
 
@@ -6,17 +6,17 @@ same formula on the same inputs.
 
 Model tables rounded to float32; sine and cosine in float64, rounded (as the device build does); the recursive Newton-Euler passes, the mass matrix, its
 Cholesky solve, the cost and the L1 defect all in np.float32 with one rounding per operation (numpy does not fuse); the per-knot values are widened and
-summed in float64 (as merit_sum_kernel does).  The trial iterate is merit_ref.trial's float32, used as is.  tests/test_merit_ref_f32_cpu.py pins it
+summed in float64 (as merit_sum_kernel does).  The trial iterate is plant_ref.trial's float32, used as is.  tests/test_merit_ref_f32_cpu.py pins it
 against the float64 restatement."""
 import numpy as np
 
 import iiwa_ref
-import merit_ref
+import plant_ref
 from mpcgpu_amd import iiwa
 
 F = np.float32
 NJ = iiwa_ref.NJ
-n, m = merit_ref.n, merit_ref.m
+n, m = plant_ref.n, plant_ref.m
 STEPS9 = [0.0] + [-1.0 / (1 << p) for p in range(8)]          # tests/test_gpu_merit.py
 STEPS8 = STEPS9[1:]
 MU = 10.0
@@ -141,7 +141,7 @@ class Model32:
 def merit_at(model32, z, goals, xs, N, mu, qd_cost, r_cost, dt=iiwa_ref.TIMESTEP):
     """Merit of ONE trajectory at the float32 iterate z: every knot's value in float32, the knots added in float64."""
     z = np.asarray(z, F)
-    goals = merit_ref.f32(goals).reshape(N, 6)
+    goals = plant_ref.f32(goals).reshape(N, 6)
     mu, qd_cost, r_cost, dt, half = F(mu), F(qd_cost), F(r_cost), F(dt), F(0.5)
     total = 0.0
     for k in range(N):
@@ -157,7 +157,7 @@ def merit_at(model32, z, goals, xs, N, mu, qd_cost, r_cost, dt=iiwa_ref.TIMESTEP
             qdd = model32.forward_dynamics(q, qd, u)
             viol = np.abs(xn - np.concatenate([q + dt * qd, qd + dt * qdd])).sum(dtype=F)
         if k == 0 and xs is not None:
-            viol = viol + np.abs(x - merit_ref.f32(xs)).sum(dtype=F)
+            viol = viol + np.abs(x - plant_ref.f32(xs)).sum(dtype=F)
         point = pm + mu * viol
         assert point.dtype == F
         total += float(point)
@@ -165,12 +165,12 @@ def merit_at(model32, z, goals, xs, N, mu, qd_cost, r_cost, dt=iiwa_ref.TIMESTEP
 
 
 def merits(model32, xu, dz, step_sizes, goals, xs, N, mu, qd_cost, r_cost, dt=iiwa_ref.TIMESTEP):
-    """[B, A] merits of a batch, as merit_ref.merits."""
+    """[B, A] merits of a batch, as plant_ref.merits."""
     B = len(xu)
     out = np.zeros((B, len(step_sizes)))
     for b in range(B):
         for a, alpha in enumerate(step_sizes):
-            z = merit_ref.trial(xu[b], None if dz is None else dz[b], alpha).astype(F)      # (the widening of trial() undone: exact)
+            z = plant_ref.trial(xu[b], None if dz is None else dz[b], alpha).astype(F)      # (the widening of trial() undone: exact)
             out[b, a] = merit_at(model32, z, goals[b], None if xs is None else xs[b], N, mu, qd_cost, r_cost, dt)
     return out
 

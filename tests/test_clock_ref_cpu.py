@@ -1,5 +1,5 @@
 """CPU: tests/clock_ref.py — the restatement that checks mpcg_simulate_clk / mpcg_advance_horizon_clk — pinned on the sequences worked out by hand
-for include/mpcsim.cuh:294-352 (the ShiftClock of examples/mpc_closed_loop.cpp) and on tests/sim_ref.py's schedule."""
+for include/mpcsim.cuh:294-352 (the ShiftClock of examples/mpc_closed_loop.cpp) and on tests/plant_ref.py's schedule."""
 import math
 
 import numpy as np
@@ -7,10 +7,9 @@ import pytest
 
 import clock_ref
 import iiwa_ref
-import sim_ref
-import sim_ref_f64
+import plant_ref as P
 
-n, m = sim_ref.n, sim_ref.m
+n, m = P.n, P.m
 DT = 1.0 / 64
 # the schedules of tests/test_gpu_clocks.py: the five CASES of tests/test_gpu_simulate.py and a zero-time trajectory
 SIX = [(0, 2000), (15000, 2100), (15000, 100), (46000, 2000), (15500, 300), (4000, 0)]
@@ -56,10 +55,10 @@ def test_period_zero_never_shifts_and_keeps_the_clock():
 def test_schedule_agrees_with_sim_ref(toff, sim):
     ss32 = np.float32(2e-4)
     valid, t, S, rem = clock_ref.schedule(toff, sim, ss32, np.float32)
-    S0, _, rem0, _ = sim_ref.schedule(toff, sim, DT, ss32)
+    S0, _, rem0, _ = P.schedule(toff, sim, DT, ss32)
     assert valid and (t, S) == (toff * 1e-6, S0) and rem == float(rem0) and np.float32(rem) == rem0
     valid, t, S, rem = clock_ref.schedule(toff, sim, 2e-4, np.float64)
-    S0, _, rem0, _ = sim_ref_f64.schedule(toff, sim, DT, 2e-4)
+    S0, _, rem0, _ = P.schedule(toff, sim, DT, 2e-4, double=True)
     assert valid and (t, S) == (toff * 1e-6, S0) and rem == rem0
 
 
@@ -73,7 +72,7 @@ def test_schedule_refuses_what_is_no_schedule():
 
 def test_control_update_composes_simulate_and_advance():
     """A zero-time update leaves the state and the clock as they are and copies the start state; an update that crosses the threshold is
-    sim_ref.simulate from prev_sim_us followed by sim_ref.advance(shift = 1)."""
+    plant_ref.simulate from prev_sim_us followed by plant_ref.advance(shift = 1)."""
     M = iiwa_ref.Model()
     rng = np.random.default_rng(5)
     N, T = 4, 10
@@ -85,7 +84,7 @@ def test_control_update_composes_simulate_and_advance():
     assert c.state() == (0.015, 0, 0.0)
     c = clock_ref.Clock(DT, since_s=0.015, prev_sim_us=1500.0)
     x, (xu1, lam1, goal1, off, done, err), shift = clock_ref.control_update(M, N, DT, c, 700.0, np.float32(2e-4), xs, xu, xu, lam, goal, plan, goals, T, 0, 0)
-    want = sim_ref.simulate(M, xs, xu, N, DT, 1500.0, 700.0)
+    want = P.simulate(M, xs, xu, N, DT, 1500.0, 700.0)
     assert shift and off == 1 and np.array_equal(x, want) and c.shifted == 0 and c.prev_sim_us == 700.0
-    ref = sim_ref.advance(True, N, xu, lam, goal, want.astype(np.float32), M.ee_pos(want[:7]).astype(np.float32), plan, goals, T, 0, 0)
+    ref = P.advance(True, N, xu, lam, goal, want.astype(np.float32), M.ee_pos(want[:7]).astype(np.float32), plan, goals, T, 0, 0)
     assert np.array_equal(xu1, ref[0]) and np.array_equal(lam1, ref[1]) and np.array_equal(goal1, ref[2]) and err == ref[5]

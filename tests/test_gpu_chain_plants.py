@@ -1,6 +1,6 @@
 """GPU: the kernels behind mpcg_plant_create on robots OTHER than the KUKA iiwa 14 — mpcg_generate_kkt (double analytic, double difference checker,
 one-knot float, packed two-knot float, the _f64 entry), mpcg_compute_merit (double, packed "merit_f32", the _f64 entry) and mpcg_simulate — against
-the float64 restatements (oracle/iiwa_ref.py, tests/merit_ref.py, tests/merit_ref_f64.py, tests/sim_ref.py) run on the same chain.
+the float64 restatements (oracle/iiwa_ref.py, tests/plant_ref.py) run on the same chain.
 
 Every other GPU test uses Plant() = the iiwa, where about half of the 28 numbers per joint the recursions multiply are zero or below the tolerances
 (tests/chain_models.py).  The chains here (tests/chain_models.py::random_chain, seeds chain_models.SEEDS) have no such entry: a kernel
@@ -20,9 +20,7 @@ import torch
 
 import chain_models as cm
 import iiwa_ref
-import merit_ref
-import merit_ref_f64
-import sim_ref
+import plant_ref as P
 from mpcgpu_amd import iiwa
 from test_gpu_kkt_f64 import LIMIT_C, LIMIT_Ggc
 from test_gpu_merit_f64 import LIMIT as LIMIT_MERIT_F64
@@ -148,8 +146,7 @@ def fig(*a):
 # ---- 0. the control: the iiwa through the export path is Plant(), bit for bit, on every entry ----
 @functools.lru_cache(maxsize=None)
 def merit_inputs(which, N, B, size):
-    """(xu, goals, xs, dz) float32 and the genuinely double (xu, dz) for the _f64 entry (goals and xs stay float-representable: merit_ref.merit_at
-    rounds those two to float32)."""
+    """(xu, goals, xs, dz) float32 and the genuinely double (xu, dz) for the _f64 entry (goals and xs stay float-representable)."""
     xu, goals, xs = inputs32(which, N, B, size)
     rng = np.random.default_rng([9, N, input_seed(which)])
     dz = (0.05 * rng.standard_normal(xu.shape)).astype(f32)
@@ -321,18 +318,18 @@ def test_generate_kkt_f64_rounded_to_float_is_the_float_entry(seed, N, B):
 # ---- 3. mpcg_compute_merit ----
 @functools.lru_cache(maxsize=None)
 def merits_restated(seed, N, B, size, double):
-    """{with_xs: [B, 3]} of the host restatement, float trial iterate (merit_ref) or double (merit_ref_f64)."""
+    """{with_xs: [B, 3]} of the host restatement, float trial iterate or double."""
     xu, goals, xs, dz, xu64, dz64 = merit_inputs(seed, N, B, size)
-    ref, a, d = (merit_ref_f64, xu64, dz64) if double else (merit_ref, xu, dz)
+    a, d = (xu64, dz64) if double else (xu, dz)
     g3 = goals.reshape(B, N, 6)
-    return {w: ref.merits(chain(seed), a, d, STEPS3, g3, xs if w else None, N, MU, iiwa.QD_COST, iiwa.r_cost(N)) for w in (True, False)}
+    return {w: P.merits(chain(seed), a, d, STEPS3, g3, xs if w else None, N, MU, cost=P.Cost.plain(iiwa.QD_COST, iiwa.r_cost(N)), double=double) for w in (True, False)}
 
 
 @pytest.mark.parametrize("N,B", SHAPES)
 @pytest.mark.parametrize("seed", cm.SEEDS)
 def test_merit_vs_host_restatement(seed, N, B):
     """Step sizes 0, -1, -1/2, d_xs given and NULL, both sets.  Default build 1e-6 (test_merit_vs_host_restatement), packed "merit_f32" = 1 1e-5 (the
-    documented limit of include/mpcg.h), the _f64 entry against tests/merit_ref_f64.py at tests/test_gpu_merit_f64.py's limit (1.2e-13).
+    documented limit of include/mpcg.h), the _f64 entry against the double trial iterate at tests/test_gpu_merit_f64.py's limit (1.2e-13).
     Merits here: 120 .. 3700.  Measured worst over the nine cases: default 5.7e-8, "merit_f32" 3.4e-7, _f64 6.8e-16."""
     worst = {"default": 0.0, "merit_f32": 0.0, "f64": 0.0}
     for size in SIZES:
@@ -398,7 +395,7 @@ def test_simulate_vs_host_restatement(seed, toff, sim):
     PcgSolver(N4, max_batch=1).simulate(plant(seed), d_xs, dev(xu), iiwa.TIMESTEP, toff, sim, float(SS), eePos=ee)
     torch.cuda.synchronize()
     got, ee = d_xs.cpu().numpy().astype(f64), ee.cpu().numpy().astype(f64)
-    want = sim_ref.simulate(chain(seed), xs, xu, N4, iiwa.TIMESTEP, toff, sim, SS)
+    want = P.simulate(chain(seed), xs, xu, N4, iiwa.TIMESTEP, toff, sim, SS)
     assert np.isfinite(got).all() and np.isfinite(ee).all()
     err = float((np.abs(got - want) / np.maximum(1.0, np.abs(want))).max())
     ee_want, ee_got = np.abs(ee - chain(seed).ee_pos(want[:7])).max(), np.abs(ee - chain(seed).ee_pos(got[:7])).max()

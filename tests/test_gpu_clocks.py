@@ -15,8 +15,7 @@ import torch
 import arena
 import arena_specs as A
 import clock_ref
-import sim_ref
-import sim_ref_f64
+import plant_ref as P
 import test_gpu_simulate as t32
 import test_gpu_simulate_f64 as t64
 from mpcgpu_amd import Clocks, _lib
@@ -31,7 +30,6 @@ PRECS = ("f32", "f64")
 NP = {"f32": np.float32, "f64": np.float64}
 TD = {"f32": torch.float32, "f64": torch.float64}
 SS = {"f32": float(np.float32(2e-4)), "f64": 2e-4}          # the reference's substep in either type (include/mpcg.h, mpcg_simulate_f64)
-REF = {"f32": sim_ref, "f64": sim_ref_f64}
 MPC = {"f32": t32.Mpc, "f64": t64.Mpc}
 NAN = float("nan")
 # the five schedules of tests/test_gpu_simulate.py and a zero-time trajectory: mixed S in a wavefront, a half-filled last wavefront
@@ -129,7 +127,7 @@ def test_mixed_batch_vs_host_restatement(prec):
     got, ee = clk(prec, order, [SIX[b] for b in order], xu_dev=view)
     assert np.isfinite(got).all() and np.isfinite(ee).all()
     for i, b in enumerate(order):
-        want = REF[prec].simulate(model(), xs[b], xu[b], N4, DT, *SIX[b], NP[prec](SS[prec]))
+        want = P.simulate(model(), xs[b], xu[b], N4, DT, *SIX[b], NP[prec](SS[prec]), double=prec == "f64")
         err = (np.abs(got[i].astype(np.float64) - want) / np.maximum(1.0, np.abs(want))).max()
         ee_err = np.abs(ee[i].astype(np.float64) - model().ee_pos(want[:7])).max()
         print(f"{prec} trajectory {b} {SIX[b]}: worst relative error {err:.3e}, end effector {ee_err:.3e}")

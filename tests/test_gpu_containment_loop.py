@@ -10,7 +10,6 @@ import torch
 
 import containment as ct
 import rho_ref
-import rho_ref_f64
 from mpcgpu_amd import _lib, iiwa
 from test_gpu_rho import MU, STEPS8
 
@@ -73,7 +72,6 @@ def test_three_adaptive_sqp_iterations_with_a_nan_in_one_iterate(dtype):
     xu, goals, xs = windows(dtype)
     bad = ct.poison(xu, (BAD,), lambda a: ct.nan_one(a, (n + m) * 3 + 2))            # q_2 of knot 3
     clean, poisoned = Loop(dtype, xu, goals, xs), Loop(dtype, bad, goals, xs)
-    update = rho_ref.update if dtype == np.float32 else rho_ref_f64.update
     rho, drho, done = dtype(RHO0[BAD]), dtype(1.0), False
     for it in range(3):
         clean.iteration()
@@ -85,7 +83,7 @@ def test_three_adaptive_sqp_iterations_with_a_nan_in_one_iterate(dtype):
             assert got["step"][BAD] == _lib.MPCG_STEP_FROZEN
         else:
             assert got["step"][BAD] == -1, (it, got["step"])
-            rho, drho, done = update(rho, drho, -1, rho_reset=RESET)
+            rho, drho, done = rho_ref.update(rho, drho, -1, rho_reset=RESET, dtype=dtype)
         assert got["rho"][BAD].tobytes() == dtype(rho).tobytes() and got["drho"][BAD].tobytes() == dtype(drho).tobytes(), (it, got["rho"], rho, got["drho"], drho)
         assert int(got["done"][BAD]) == int(done), (it, got["done"])
         assert np.array_equal(got["xu"][BAD].view(np.uint8), bad[BAD].view(np.uint8)) and np.isnan(got["ref"][BAD])

@@ -17,8 +17,7 @@ import torch
 
 import chain_models as cm
 import gravity_ref as gr
-import integrator_ref as ir
-import merit_ref
+import plant_ref as P
 from mpcgpu_amd import _lib, iiwa
 
 pytestmark = pytest.mark.gpu
@@ -104,7 +103,7 @@ def input_seed(which):
 @functools.lru_cache(maxsize=None)
 def inputs(which, N, B, size, dtype):
     """(xu, goals [B, 6N], xs, dz): float32, or (dtype = f64) genuinely double xu, xs, dz — the float32 values times (1 + 1e-12 r) — with goals and (for the
-    merit) an x_s that stay float-representable: merit_ref.merit_at rounds those two."""
+    merit) an x_s that stay float-representable."""
     xu, goals, xs = (np.ascontiguousarray(a, f32) for a in cm.hard_inputs(N, B, input_seed(which), size))
     rng = np.random.default_rng([9, N, input_seed(which)])
     dz = (0.05 * rng.standard_normal(xu.shape)).astype(f32)
@@ -120,14 +119,14 @@ def inputs(which, N, B, size, dtype):
 @functools.lru_cache(maxsize=None)
 def kkt_restated(which, N, B, size, dtype, integrator):
     xu, goals, xs, _ = (np.asarray(a, f64) for a in inputs(which, N, B, size, dtype))
-    return [ir.generate_kkt(model(which), xu[b], goals[b].reshape(N, 6), xs[b], N, DT, integrator) for b in range(B)]
+    return [P.generate_kkt(model(which), xu[b], goals[b].reshape(N, 6), xs[b], N, dt=DT, integrator=integrator) for b in range(B)]
 
 
 @functools.lru_cache(maxsize=None)
 def merits_restated(which, N, B, size, dtype, with_xs, mu=MU):
     xu, goals, xs, dz = inputs(which, N, B, size, dtype)
-    return ir.merits(model(which), xu, dz, STEPS3, goals.reshape(B, N, 6), xs.astype(f32) if with_xs else None, N, mu, iiwa.QD_COST, iiwa.r_cost(N), DT, 0,
-                     double=dtype == f64)
+    return P.merits(model(which), xu, dz, STEPS3, goals.reshape(B, N, 6), xs.astype(f32) if with_xs else None, N, mu, cost=P.Cost.plain(iiwa.QD_COST, iiwa.r_cost(N)),
+                    dt=DT, integrator=0, double=dtype == f64)
 
 
 def solver(N, B, **options):
@@ -431,7 +430,7 @@ def test_simulate_vs_restatement(which, toff, sim, dtype):
     ss = f32(2e-4) if dtype == f32 else float(f32(2e-4))
     for si in (0, 1):
         got, ee = run_simulate(plant(which), N4, xs, xu, dtype, toff, sim, float(ss), sim_integrator=si)
-        want = ir.simulate(model(which), xs[0], xu[0], N4, DT, toff, sim, ss, si, double=dtype == f64)
+        want = P.simulate(model(which), xs[0], xu[0], N4, DT, toff, sim, ss, si, double=dtype == f64)
         assert got.dtype == dtype and np.isfinite(got).all() and np.isfinite(ee).all()
         err = rel(got[0], want)
         ee_want, ee_got = np.abs(ee[0] - model(which).ee_pos(want[:7])).max(), np.abs(ee[0] - model(which).ee_pos(got[0, :7].astype(f64))).max()
@@ -497,11 +496,11 @@ def test_inverse_dynamics_vs_restatement(which, count, dtype):
 
 # ---- 10. the reference's own trajectory stays a solution once compensated ----
 def test_the_reference_trajectory_stays_a_solution_once_compensated():
-    """A window of the reference's trajectory (merit_ref.reference_window(2, 16)), the iiwa with (0, 0, 9.81), in double: u' = u + mpcg_inverse_dynamics_f64(q).
+    """A window of the reference's trajectory (plant_ref.reference_window(2, 16)), the iiwa with (0, 0, 9.81), in double: u' = u + mpcg_inverse_dynamics_f64(q).
     d_c of mpcg_generate_kkt_f64 with (clone, u') equals d_c with (plain plant, u) within LIMIT_Ggc = 8.8e-11 (the rounding of u' ~ 50 Nm: 7e-15, times
     Minv <= 1e3, times dt: 3e-13).  Not in float: rounding a 50 Nm control to float moves c by 5e-5."""
     N = 16
-    xu, goals, xs = (np.asarray(a, f64) for a in merit_ref.reference_window(2, N))
+    xu, goals, xs = (np.asarray(a, f64) for a in P.reference_window(2, N))
     sol = solver(N, 1)
     z = np.concatenate([xu, np.zeros(m)]).reshape(N, n + m)
     tau = sol.inverse_dynamics(plant("iiwa"), dev(z[:, :NJ], f64)).cpu().numpy()

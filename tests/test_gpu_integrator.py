@@ -1,6 +1,6 @@
 """GPU: options "integrator" and "sim_integrator" = 1 — semi-implicit (symplectic) Euler, the reference's INTEGRATOR_TYPE == 1 (include/common/integrator.cuh),
 as a compile-time parameter of the KKT, merit and simulate kernels (mpcgpu_amd/csrc/kkt_plant.hip.h, merit_plant.hip.h, merit_plant_f32.hip.h, sim_plant.hip.h) —
-against the float64 restatement tests/integrator_ref.py (pinned in tests/test_integrator_ref_cpu.py, which also shows that the cases here tell the two
+against the float64 restatement tests/plant_ref.py (pinned in tests/test_integrator_ref_cpu.py, which also shows that the cases here tell the two
 integrators apart by 100 x / 10 x their tolerances), across kernels (the merit measures the map the KKT kernel linearised; one simulated step is that map),
 in a hipGraph and in a closed SQP iteration; and both options at 0 set explicitly give the bits of a handle on which they were never set.
 
@@ -15,7 +15,7 @@ import torch
 
 import chain_models as cm
 import iiwa_ref
-import integrator_ref as ir
+import plant_ref as P
 from mpcgpu_amd import _lib, iiwa
 
 pytestmark = pytest.mark.gpu
@@ -97,7 +97,7 @@ def solver(N, B, **options):
 @functools.lru_cache(maxsize=None)
 def inputs(N, B, dtype):
     """(xu, goals [B, 6N], xs, dz) of mpcgpu_amd.iiwa.random_windows(N, B, 5) and a seeded step: float32, or (dtype = f64) genuinely double xu, xs and
-    dz — the float32 values times (1 + 1e-12 r), as tests/test_gpu_kkt_f64.py::windows64 — with goals that stay floats (merit_ref.merit_at rounds them)."""
+    dz — the float32 values times (1 + 1e-12 r), as tests/test_gpu_kkt_f64.py::windows64 — with goals that stay floats."""
     xu, goals, xs = (np.ascontiguousarray(a, f32) for a in iiwa.random_windows(N, B, 5))
     rng = np.random.default_rng([9, N, B])
     dz = (0.05 * rng.standard_normal(xu.shape)).astype(f32)
@@ -113,16 +113,16 @@ def inputs(N, B, dtype):
 @functools.lru_cache(maxsize=None)
 def kkt_restated(which, N, B, dtype, integrator):
     xu, goals, xs, _ = (np.asarray(a, f64) for a in inputs(N, B, dtype))
-    return [ir.generate_kkt(model(which), xu[b], goals[b].reshape(N, 6), xs[b], N, DT, integrator) for b in range(B)]
+    return [P.generate_kkt(model(which), xu[b], goals[b].reshape(N, 6), xs[b], N, dt=DT, integrator=integrator) for b in range(B)]
 
 
 @functools.lru_cache(maxsize=None)
 def merits_restated(which, N, B, dtype, with_xs, integrator, mu=MU):
     xu, goals, xs, dz = inputs(N, B, dtype)
     if dtype == f64:
-        xs = xs.astype(f32)              # (the merit cases give the _f64 entry a float-representable x_s: merit_ref.merit_at rounds it)
-    return ir.merits(model(which), xu, dz, STEPS3, goals.reshape(B, N, 6), xs if with_xs else None, N, mu, iiwa.QD_COST, iiwa.r_cost(N), DT, integrator,
-                     double=dtype == f64)
+        xs = xs.astype(f32)              # (the merit cases give the _f64 entry a float-representable x_s)
+    return P.merits(model(which), xu, dz, STEPS3, goals.reshape(B, N, 6), xs if with_xs else None, N, mu, cost=P.Cost.plain(iiwa.QD_COST, iiwa.r_cost(N)), dt=DT,
+                    integrator=integrator, double=dtype == f64)
 
 
 def costs(N, dtype):
@@ -329,8 +329,8 @@ def test_simulate_vs_restatement(dtype):
     xu, _, xs, _ = inputs(N, B, dtype)
     ss = f32(2e-3) if dtype == f32 else 2e-3
     got, ee = run_simulate(N, B, dtype, 0, 8000, float(ss), sim_integrator=1)
-    want = np.array([ir.simulate(model("iiwa"), xs[b], xu[b], N, DT, 0, 8000, ss, 1, double=dtype == f64) for b in range(B)])
-    other = np.array([ir.simulate(model("iiwa"), xs[b], xu[b], N, DT, 0, 8000, ss, 0, double=dtype == f64) for b in range(B)])
+    want = np.array([P.simulate(model("iiwa"), xs[b], xu[b], N, DT, 0, 8000, ss, 1, double=dtype == f64) for b in range(B)])
+    other = np.array([P.simulate(model("iiwa"), xs[b], xu[b], N, DT, 0, 8000, ss, 0, double=dtype == f64) for b in range(B)])
     assert got.dtype == dtype and np.isfinite(got).all() and np.isfinite(ee).all()
     err = rel(got, want)
     ee_err = max(rel(ee[b], model("iiwa").ee_pos(want[b, :7])) for b in range(B))

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import large_extents as le
-import limits_ref as L
+import plant_ref as P
 import test_gpu_integrator as ti
 import test_gpu_limits as tl
 from mpcgpu_amd import iiwa
@@ -61,7 +61,6 @@ def test_generate_kkt_with_c_past_2_32(prec, N, opts, xuref):
 
 @pytest.mark.parametrize("prec,N,opts,xuref", XUREF, ids=[ident(c) for c in XUREF])
 def test_generate_kkt_xuref_with_limits_and_a_plan_per_trajectory(prec, N, opts, xuref):
-    import xuref_ref as X
     from mpcgpu_amd import XuRef
     assert prec == "f64" and N == 5
     spec = le.kkt_spec(prec, N, opts, xuref)
@@ -73,7 +72,7 @@ def test_generate_kkt_xuref_with_limits_and_a_plan_per_trajectory(prec, N, opts,
     plan = cs.plan.reshape(spec.D, cs.stride * 21)
 
     def call(a, Bt):
-        ref = XuRef(a["xu_traj"].view(-1, 21), a["traj_offset"].view(-1), cs.stride, co.ee_cost, co.q_cost, bool(co.flags & X.QD_RELATIVE), bool(co.flags & X.U_RELATIVE),
+        ref = XuRef(a["xu_traj"].view(-1, 21), a["traj_offset"].view(-1), cs.stride, co.ee_cost, co.q_cost, bool(co.flags & P.QD_RELATIVE), bool(co.flags & P.U_RELATIVE),
                     traj_steps=cs.T)
         x = sol._xuref("generate_kkt_xuref", ref, torch.float64, Bt, 14, 7)          # (the C entry itself: the wrapper would allocate the outputs)
         sol._check(sol.lib.mpcg_generate_kkt_xuref_f64(sol._h, pl._p, 7, float(DT), ptr(a["goals"]), ptr(a["xs"]), ptr(a["xu"]), float(co.qd_cost), float(co.r_cost),
@@ -82,7 +81,7 @@ def test_generate_kkt_xuref_with_limits_and_a_plan_per_trajectory(prec, N, opts,
     sol.close()
     worst = {"Ggc": 0.0, "C": 0.0}
     for b in range(spec.D):
-        want = L.generate_kkt(model(), cs.xu[b], cs.goals[b], cs.xs[b], N, cs.rows(b), co, lim, DT, integrator, base=cs.dynamics(b, integrator))
+        want = P.generate_kkt(model(), cs.xu[b], cs.goals[b], cs.xs[b], N, rows=cs.rows(b), cost=co, limits=lim, dt=DT, integrator=integrator, base=cs.dynamics(b, integrator))
         for name, w in zip(("G", "C", "g", "c"), want):
             key = "C" if name == "C" else "Ggc"
             worst[key] = max(worst[key], np.abs(out[name][b] - w).max() / max(1.0, np.abs(w).max()))

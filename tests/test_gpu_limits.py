@@ -1,5 +1,5 @@
 """GPU: soft joint, velocity and torque limits as model data of a plant (include/mpcg.h, LIMITS; mpcg_plant_clone_limits) — the COST = 2 instantiations of the
-KKT and merit kernels behind the _xuref entries, and the saturating instantiation of simulate_kernel — against the float64 restatement tests/limits_ref.py,
+KKT and merit kernels behind the _xuref entries, and the saturating instantiation of simulate_kernel — against the float64 restatement tests/plant_ref.py,
 against the _xuref results with the plain plant where nothing is violated, against each other on the device, for independence of the batch and containment of
 a NaN trajectory, inside a hipGraph, and through the error table.  Inputs and shapes: the cases of tests/test_gpu_xuref.py (shared, read-only); the bounds
 come from each case's own values — per kind and joint the lower and upper third, nudged off every value — so that below, inside and above all occur and the
@@ -12,10 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-import limits_ref as L
-import merit_ref
-import merit_ref_f64
-import xuref_ref as X
+import plant_ref as P
 from mpcgpu_amd import XuRef, _lib, iiwa
 from test_gpu_xuref import COSTS, DT, KKT_BUILDS, LIMIT_C, LIMIT_Ggc, MERIT_BUILDS, MU, SHAPES, STEPS8, STEPS9, bits, case, dev, model, plant, solver, want_merits
 
@@ -50,20 +47,19 @@ def limits_of(xs_list, us_list, weights=WEIGHTS):
     (q_lo, q_hi), (qd_lo, qd_hi), (u_lo, u_hi) = bounds_of(x[:, :NJ]), bounds_of(x[:, NJ:]), bounds_of(u)
     for lo in (q_lo, qd_lo, u_lo):
         lo[1] = -np.inf
-    lim = L.Limits(q_lo, q_hi, qd_lo, qd_hi, u_lo, u_hi, *weights)
+    lim = P.Limits(q_lo, q_hi, qd_lo, qd_hi, u_lo, u_hi, *weights)
     for name, vals, lo, hi in (("q", x[:, :NJ], q_lo, q_hi), ("qd", x[:, NJ:], qd_lo, qd_hi), ("u", u, u_lo, u_hi)):
-        s = L.side(vals, lo, hi)
+        s = P.side(vals, lo, hi)
         assert all((s == v).any() for v in (-1, 0, 1)), name
     return lim
 
 
 def states_controls(cs, steps):
     """The states and controls of every trajectory of a case at the trial iterates of `steps` (step size 0: the iterate itself)."""
-    trial = merit_ref_f64.trial if cs.double else merit_ref.trial
     xs, us = [], []
     for b in range(cs.B):
         for a in steps:
-            x, u = X.split(trial(cs.xu[b], cs.dz[b], a), cs.N)
+            x, u = P.split(P.trial(cs.xu[b], cs.dz[b], a, cs.double), cs.N)
             xs.append(x)
             us.append(u)
     return xs, us
@@ -128,7 +124,7 @@ def test_kkt_vs_host_restatement(N, B, build, integrator):
     assert all(np.isfinite(a).all() for a in got)
     worst = 0.0
     for b in range(B):
-        want = L.generate_kkt(model(), cs.xu[b], cs.goals[b], cs.xs[b], N, cs.rows(b), co, lim, DT, integrator, base=cs.dynamics(b, integrator))
+        want = P.generate_kkt(model(), cs.xu[b], cs.goals[b], cs.xs[b], N, rows=cs.rows(b), cost=co, limits=lim, dt=DT, integrator=integrator, base=cs.dynamics(b, integrator))
         for a, w, name in zip(got, want, "GCgc"):
             err = np.abs(a[b] - w).max() / max(1.0, np.abs(w).max())
             worst = max(worst, err)
@@ -152,7 +148,7 @@ def test_double_entry_vs_host_restatement(N, B, analytic, integrator):
     assert all(np.isfinite(a).all() for a in got)
     worst = {"Ggc": 0.0, "C": 0.0}
     for b in range(B):
-        want = L.generate_kkt(model(), cs.xu[b], cs.goals[b], cs.xs[b], N, cs.rows(b), co, lim, DT, integrator, base=cs.dynamics(b, integrator))
+        want = P.generate_kkt(model(), cs.xu[b], cs.goals[b], cs.xs[b], N, rows=cs.rows(b), cost=co, limits=lim, dt=DT, integrator=integrator, base=cs.dynamics(b, integrator))
         for a, w, name in zip(got, want, "GCgc"):
             key = "C" if name == "C" else "Ggc"
             worst[key] = max(worst[key], np.abs(a[b] - w).max() / max(1.0, np.abs(w).max()))
@@ -174,7 +170,7 @@ def test_merit_vs_host_restatement(N, B, build, with_xs):
     cs, co, lim = case(N, B, double), COSTS["all"], merit_limits(N, B, double)
     got = merit(cs, solver(N, B, opts), co, merit_plant(N, B, double), STEPS9, dtype, with_xs).cpu().numpy().astype(np.float64)
     base = want_merits(N, B, "all", with_xs, 0, double)
-    w = L.merits(model(), cs.xu, cs.dz, STEPS9, cs.goals, cs.xs if with_xs else None, N, MU, cs.rows, co, lim, DT, 0, double, base=base)
+    w = P.merits(model(), cs.xu, cs.dz, STEPS9, cs.goals, cs.xs if with_xs else None, N, MU, rows_of=cs.rows, cost=co, limits=lim, dt=DT, integrator=0, double=double, base=base)
     assert got.shape == (B, 9) and np.isfinite(got).all() and (w > base).all()
     err = np.abs(got - w) / np.maximum(1.0, np.abs(w))
     print(f"merit limits N={N} B={B} {build} xs={with_xs}: merits {w.min():.3g} .. {w.max():.3g} (penalty up to {(w - base).max():.3g}), worst {err.max():.2e} (limit {limit:.1e})")
@@ -187,16 +183,16 @@ def test_merit_semi_implicit_integrator(build):
     N, B, double = 3, 2, dtype == np.float64
     cs, co, lim = case(N, B, double), COSTS["all"], merit_limits(N, B, double)
     got = merit(cs, solver(N, B, opts, 1), co, merit_plant(N, B, double), STEPS9, dtype).cpu().numpy().astype(np.float64)
-    w = L.merits(model(), cs.xu, cs.dz, STEPS9, cs.goals, cs.xs, N, MU, cs.rows, co, lim, DT, 1, double, base=want_merits(N, B, "all", True, 1, double))
+    w = P.merits(model(), cs.xu, cs.dz, STEPS9, cs.goals, cs.xs, N, MU, rows_of=cs.rows, cost=co, limits=lim, dt=DT, integrator=1, double=double, base=want_merits(N, B, "all", True, 1, double))
     assert (np.abs(got - w) / np.maximum(1.0, np.abs(w))).max() <= limit
 
 
 # ---- 3. equality with the xu_ref results when nothing is violated ----
 def quiet_plants(N, B):
     lim = merit_limits(N, B)
-    return {"infinite": with_limits(L.Limits(None, None, None, None, None, None, *WEIGHTS)),
-            "wide": with_limits(L.Limits(-64.0, 64.0, -1024.0, None, None, 4096.0, *WEIGHTS)),
-            "zero weights": with_limits(L.Limits(lim.q_lo, lim.q_hi, lim.qd_lo, lim.qd_hi, lim.u_lo, lim.u_hi, 0.0, 0.0, 0.0))}
+    return {"infinite": with_limits(P.Limits(None, None, None, None, None, None, *WEIGHTS)),
+            "wide": with_limits(P.Limits(-64.0, 64.0, -1024.0, None, None, 4096.0, *WEIGHTS)),
+            "zero weights": with_limits(P.Limits(lim.q_lo, lim.q_hi, lim.qd_lo, lim.qd_hi, lim.u_lo, lim.u_hi, 0.0, 0.0, 0.0))}
 
 
 @pytest.mark.parametrize("integrator", [0, 1])
@@ -208,7 +204,7 @@ def test_kkt_equals_the_plain_plants_when_nothing_is_violated(N, B, build, integ
     opts = KKT_BUILDS[build][0] if build != "f64" else ()
     dtype = np.float64 if build == "f64" else np.float32
     cs, co = case(N, B), COSTS["all"]
-    x, u = zip(*[X.split(cs.xu[b], N) for b in range(B)])
+    x, u = zip(*[P.split(cs.xu[b], N) for b in range(B)])
     assert np.abs(np.concatenate(x)[:, :NJ]).max() < 64 and np.abs(np.concatenate(x)[:, NJ:]).max() < 1024 and np.abs(np.concatenate(u)).max() < 4096
     sol = solver(N, B, opts, integrator)
     base = [t.cpu().numpy() for t in kkt(cs, sol, co, plant(), dtype)]
@@ -238,7 +234,7 @@ def test_merit_differences_are_the_kkt_gradient():
     N, Lz, h = 4, 77, 1e-3
     cs = case(8, 3, True)
     xu = cs.xu[0, :Lz].copy()
-    x, u = X.split(xu, N)
+    x, u = P.split(xu, N)
 
     def far_bounds(vals):                                      # per joint: its smallest value below, its largest above, the rest inside
         lo, hi = np.zeros(NJ), np.zeros(NJ)
@@ -249,13 +245,13 @@ def test_merit_differences_are_the_kkt_gradient():
                 lo[i], hi[i] = -np.inf, s[0] - 0.25
         return f32(lo), f32(hi)
     (q_lo, q_hi), (qd_lo, qd_hi), (u_lo, u_hi) = far_bounds(x[:, :NJ]), far_bounds(x[:, NJ:]), far_bounds(u)
-    lim = L.Limits(q_lo, q_hi, qd_lo, qd_hi, u_lo, u_hi, *WEIGHTS)
+    lim = P.Limits(q_lo, q_hi, qd_lo, qd_hi, u_lo, u_hi, *WEIGHTS)
     for vals, lo, hi in ((x[:, :NJ], q_lo, q_hi), (x[:, NJ:], qd_lo, qd_hi), (u, u_lo, u_hi)):
         assert min(np.abs(vals - lo).min(), np.abs(vals - hi).min()) > 2 * h               # further than 2 h from every bound
-        s = L.side(vals, lo, hi)
+        s = P.side(vals, lo, hi)
         assert all((s == v).any() for v in (-1, 0, 1))
     pl = with_limits(lim)
-    co = X.Cost(0.0, 0.5, 2.0 ** -6, 2.0 ** -7, X.QD_RELATIVE | X.U_RELATIVE)
+    co = P.Cost(0.0, 0.5, 2.0 ** -6, 2.0 ** -7, P.QD_RELATIVE | P.U_RELATIVE)
     plan = dev(cs.plan, np.float64)
     sol = PcgSolver(N, max_batch=2 * Lz)
     ref = lambda B: XuRef(plan, torch.full((B,), 2, dtype=torch.int32, device="cuda"), 0, 0.0, co.q_cost, True, True)
@@ -268,10 +264,10 @@ def test_merit_differences_are_the_kkt_gradient():
     err = np.abs(num - g).max() / max(1.0, np.abs(g).max())
     print(f"limits: |g| up to {np.abs(g).max():.3g}, central differences off by {err:.2e}")
     assert err <= 1e-9, err
-    rows = X.plan_rows(cs.plan, 0, 2, N, cs.T)
-    want = L.generate_kkt(model(), xu, None, cs.xs[0], N, rows, co, lim, base=(np.zeros(0), np.zeros(ROW * N - m), np.zeros(0)))[2]
+    rows = P.plan_rows(cs.plan, 0, 2, N, cs.T)
+    want = P.generate_kkt(model(), xu, None, cs.xs[0], N, rows=rows, cost=co, limits=lim, base=(np.zeros(0), np.zeros(ROW * N - m), np.zeros(0)))[2]
     assert np.abs(g - want).max() <= 1e-12
-    assert np.abs(want - X.generate_kkt(model(), xu, None, cs.xs[0], N, rows, co, base=(np.zeros(0), np.zeros(ROW * N - m), np.zeros(0)))[2]).max() > 1e-2
+    assert np.abs(want - P.generate_kkt(model(), xu, None, cs.xs[0], N, rows=rows, cost=co, base=(np.zeros(0), np.zeros(ROW * N - m), np.zeros(0)))[2]).max() > 1e-2
 
 
 # ---- 5. the line search ----

@@ -1,6 +1,6 @@
 """GPU: mpcg_compute_merit and mpcg_line_search_step (mpcgpu_amd/csrc/merit_plant.hip.h) — the merit function of the SQP line search batched over
 trajectories and step sizes, and the reference's step selection + update (include/common/merit.cuh:16-143, include/pcg/sqp.cuh:264-353) — against
-the float64 restatement tests/merit_ref.py (pinned on the reference's own trajectory: tests/test_merit_ref_cpu.py), directly against that trajectory,
+the float64 restatement tests/plant_ref.py (pinned on the reference's own trajectory: tests/test_merit_ref_cpu.py), directly against that trajectory,
 for bit-stability, inside a hipGraph, and closing the loop of a device-side SQP iteration: KKT -> Schur -> PCG -> dz -> merit -> step."""
 import ctypes as C
 import json
@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import iiwa_ref
-import merit_ref
+import plant_ref as P
 from mpcgpu_amd import _lib, iiwa
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +41,7 @@ def case(N, B):
         dz = 0.05 * np.random.default_rng(1000 + N).standard_normal(xu.shape)
         M = iiwa_ref.Model()
         r = iiwa.r_cost(N)
-        want = {with_xs: merit_ref.merits(M, xu, dz, STEPS9, goals, xs if with_xs else None, N, MU, iiwa.QD_COST, r) for with_xs in (True, False)}
+        want = {with_xs: P.merits(M, xu, dz, STEPS9, P.f32(goals), P.f32(xs if with_xs else None), N, MU, cost=P.Cost.plain(iiwa.QD_COST, r)) for with_xs in (True, False)}
         _cases[(N, B)] = (xu, goals, xs, dz, want)
     return _cases[(N, B)]
 
@@ -76,8 +76,8 @@ def test_merit_vanishes_on_the_reference_trajectory(env):
     """The device pin on reference-held data: the windows and the bound of tests/test_merit_ref_cpu.py through mpcg_compute_merit with step size 0 and
     d_dz = NULL.  Measured 1.4e-5 .. 5.0e-5 against 4.3e-4 / 8.8e-4 (the host restatement's figures to three digits)."""
     PcgSolver, plant, _, _ = env
-    for t0, N in merit_ref.WINDOWS:
-        xu, goals, xs = merit_ref.reference_window(t0, N)
+    for t0, N in P.WINDOWS:
+        xu, goals, xs = P.reference_window(t0, N)
         sol = PcgSolver(N, max_batch=1)
         got = float(sol.compute_merit(plant, dev(goals.reshape(1, -1)), dev(xs.reshape(1, -1)), dev(xu.reshape(1, -1)), None, [0.0],
                                       iiwa.TIMESTEP, 1.0, 0.0, 0.0).cpu()[0, 0])
@@ -176,7 +176,7 @@ def test_closed_loop_sqp_on_the_device(env, N, B, seed):
     tail = (iiwa.TIMESTEP, MU, iiwa.QD_COST, r)
     d_ref = sol.compute_merit(plant, d_goals, d_xs, d_xu, None, [0.0], *tail).reshape(B).clone()
     first = d_ref.cpu().numpy().copy()
-    host_ref = merit_ref.merits(M, d_xu.cpu().numpy(), None, [0.0], goals, xs, N, MU, iiwa.QD_COST, r)[:, 0]
+    host_ref = P.merits(M, d_xu.cpu().numpy(), None, [0.0], P.f32(goals), P.f32(xs), N, MU, cost=P.Cost.plain(iiwa.QD_COST, r))[:, 0]
     assert (np.abs(first - host_ref) <= 1e-6 * np.maximum(1.0, np.abs(host_ref))).all()
     compared = skipped = 0
     for it in range(4):
@@ -189,10 +189,10 @@ def test_closed_loop_sqp_on_the_device(env, N, B, seed):
         step = sol.line_search_step(merit, STEPS8, d_ref, dz, d_xu)
         torch.cuda.synchronize()
         step = step.cpu().numpy()
-        host = merit_ref.merits(M, xu_before, dz.cpu().numpy(), STEPS8, goals, xs, N, MU, iiwa.QD_COST, r)
+        host = P.merits(M, xu_before, dz.cpu().numpy(), STEPS8, P.f32(goals), P.f32(xs), N, MU, cost=P.Cost.plain(iiwa.QD_COST, r))
         assert (np.abs(merit.cpu().numpy() - host) <= 1e-6 * np.maximum(1.0, np.abs(host))).all()
         for b in range(B):
-            p, best = merit_ref.select(host[b], host_ref[b])
+            p, best = P.select(host[b], host_ref[b])
             order = np.sort(np.append(host[b], host_ref[b]))
             gap = order[1] - order[0]                          # best against the runner-up, merit_ref among them
             if gap < 1e-5 * max(1.0, abs(order[0])):

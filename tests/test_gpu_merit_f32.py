@@ -1,5 +1,5 @@
 """GPU: mpcg_compute_merit with option "merit_f32" = 1 — the point merits in packed float, two work items per 16-lane group
-(mpcgpu_amd/csrc/merit_plant_f32.hip.h) — against the float64 restatement tests/merit_ref.py within the limit tests/test_merit_ref_f32_cpu.py pins for
+(mpcgpu_amd/csrc/merit_plant_f32.hip.h) — against the float64 restatement tests/plant_ref.py within the limit tests/test_merit_ref_f32_cpu.py pins for
 plain float arithmetic, on the reference's own trajectory, for the bit properties of the pairing, for the decisions the line search takes from it, inside
 a closed device-side SQP iteration and a hipGraph; and the default build untouched by the option."""
 import ctypes as C
@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import iiwa_ref
-import merit_ref
+import plant_ref as P
 import merit_ref_f32 as mf
 from mpcgpu_amd import _lib, iiwa
 
@@ -47,7 +47,7 @@ def want64(N, B, with_xs):
     """The float64 restatement's merits of mf.case_inputs(N, B) at the nine step sizes, computed once per shape."""
     if (N, B, with_xs) not in _want:
         xu, goals, xs, dz = mf.case_inputs(N, B)
-        _want[(N, B, with_xs)] = merit_ref.merits(iiwa_ref.Model(), xu, dz, STEPS9, goals, xs if with_xs else None, N, MU, iiwa.QD_COST, iiwa.r_cost(N))
+        _want[(N, B, with_xs)] = P.merits(iiwa_ref.Model(), xu, dz, STEPS9, P.f32(goals), P.f32(xs if with_xs else None), N, MU, cost=P.Cost.plain(iiwa.QD_COST, iiwa.r_cost(N)))
     return _want[(N, B, with_xs)]
 
 
@@ -85,7 +85,7 @@ def test_float_merit_smallest_and_odd_totals(env, N, B, A):
     steps = STEPS9[:A] if A > 1 else [-0.5]
     sol = solver(PcgSolver, N, B)
     got = call(sol, plant, N, goals, xs, xu, dz, steps).cpu().numpy().astype(np.float64)
-    w = merit_ref.merits(M, xu, dz, steps, goals, xs, N, MU, iiwa.QD_COST, iiwa.r_cost(N))
+    w = P.merits(M, xu, dz, steps, P.f32(goals), P.f32(xs), N, MU, cost=P.Cost.plain(iiwa.QD_COST, iiwa.r_cost(N)))
     err = np.abs(got - w) / np.maximum(1.0, np.abs(w))
     print(f"merit_f32 N={N} B={B} A={A}: worst error {err.max():.2e}")
     assert got.shape == (B, A) and err.max() <= TOL, (err.max(), got, w)
@@ -96,8 +96,8 @@ def test_float_merit_vanishes_on_the_reference_trajectory(env):
     """The windows and the bound of tests/test_merit_ref_cpu.py through the option, step size 0 and d_dz = NULL.  The numpy float32 restatement:
     9.6e-6 .. 5.0e-5 against 4.3e-4 / 8.8e-4."""
     PcgSolver, plant, _, _ = env
-    for t0, N in merit_ref.WINDOWS:
-        xu, goals, xs = merit_ref.reference_window(t0, N)
+    for t0, N in P.WINDOWS:
+        xu, goals, xs = P.reference_window(t0, N)
         sol = solver(PcgSolver, N, 1)
         got = float(sol.compute_merit(plant, dev(goals.reshape(1, -1)), dev(xs.reshape(1, -1)), dev(xu.reshape(1, -1)), None, [0.0],
                                       iiwa.TIMESTEP, 1.0, 0.0, 0.0).cpu()[0, 0])
@@ -175,12 +175,12 @@ def test_accepted_float_merit_is_the_merit_of_the_new_iterate(env):
 # ---- 6. decisions ----
 @pytest.mark.parametrize("N,B,seed", [(8, 3, 19), (32, 2, 43)])
 def test_decisions(env, N, B, seed):
-    """The step mpcg_line_search_step chooses from the FLOAT merits (merit_ref = the float merit at step size 0) is merit_ref.select's on the FLOAT64
+    """The step mpcg_line_search_step chooses from the FLOAT merits (merit_ref = the float merit at step size 0) is plant_ref.select's on the FLOAT64
     merits, for every trajectory whose float64 candidates (merit_ref among them) are separated from the winner by more than 2e-5 max(1, |merit|) —
     twice the limit of test 1.  At most one trajectory per case may be left out; tests/test_merit_ref_f32_cpu.py checks that these seeds leave none."""
     PcgSolver, plant, _, M = env
     xu, goals, xs, dz = mf.decision_inputs(N, B, seed)
-    host = merit_ref.merits(M, xu, dz, [0.0] + STEPS8, goals, xs, N, MU, iiwa.QD_COST, iiwa.r_cost(N))
+    host = P.merits(M, xu, dz, [0.0] + STEPS8, P.f32(goals), P.f32(xs), N, MU, cost=P.Cost.plain(iiwa.QD_COST, iiwa.r_cost(N)))
     sol = solver(PcgSolver, N, B)
     d_xu, d_dz = dev(xu), dev(dz)
     d_ref = call(sol, plant, N, goals, xs, xu, None, [0.0]).reshape(B).clone()
@@ -188,7 +188,7 @@ def test_decisions(env, N, B, seed):
     step = sol.line_search_step(merit, STEPS8, d_ref, d_dz, d_xu).cpu().numpy()
     left_out, chosen = 0, []
     for b in range(B):
-        p, _ = merit_ref.select(host[b, 1:], host[b, 0])
+        p, _ = P.select(host[b, 1:], host[b, 0])
         chosen.append(p)
         if mf.close_tie(host[b, 1:], host[b, 0]):
             left_out += 1

@@ -1,7 +1,7 @@
 """GPU: mpcg_compute_merit_f64, mpcg_line_search_step_f64 and mpcg_line_search_step_rho_f64 (mpcgpu_amd/csrc/merit_plant.hip.h: merit_points_kernel, merit_sum_kernel and line_search_step_kernel in double) — the
 double consumers behind mpcg_compute_dz_f64.  The merit: the float entry's arithmetic bit for bit where the float trial iterate is exact; against
-tests/merit_ref.py::merit_at at the correctly rounded double trial iterate (tests/merit_ref_f64.py); the accepted merit is the merit of the new
-iterate; bit-stability.  The step and the rho rule: tests/rho_ref_f64.py bit for bit.  The closed loop: one whole batched adaptive SQP iteration in
+tests/plant_ref.py::merit_at at the correctly rounded double trial iterate (plant_ref.trial, double); the accepted merit is the merit of the new
+iterate; bit-stability.  The step and the rho rule: tests/rho_ref.py in double, bit for bit.  The closed loop: one whole batched adaptive SQP iteration in
 double — generate_kkt_f64 -> form_schur_rhov_f64 -> block_solve_f64 -> compute_dz_f64 -> compute_merit_f64 -> line_search_step_rho_f64 — against
 single-trajectory loops and as one captured iteration replayed; the -DUSE_DOUBLES build of examples/sqp_batched_iiwa against the same loop in Python."""
 import ctypes as C
@@ -15,8 +15,8 @@ import pytest
 import torch
 
 import iiwa_ref
-import merit_ref_f64
-import rho_ref_f64
+import plant_ref as P
+import rho_ref
 from mpcgpu_amd import _lib, iiwa
 
 pytestmark = pytest.mark.gpu
@@ -92,15 +92,14 @@ LIMIT = 1.2e-13
 
 @functools.lru_cache(maxsize=None)
 def case(N, B):
-    """Genuinely double xu and dz (the float test's windows and step, perturbed by 1e-12 relative), float-representable goals and xs (merit_at rounds those
-    two to float32), and the host's merits for them — computed once per shape."""
+    """Genuinely double xu and dz (the float test's windows and step, perturbed by 1e-12 relative), float-representable goals and xs, and the host's merits for them — computed once per shape."""
     xu, goals, xs = iiwa.random_windows(N, B, 11 + N)
     rng = np.random.default_rng(1000 + N)
     dz = 0.05 * rng.standard_normal(xu.shape)
     xu = xu.astype(np.float32).astype(f64) * (1.0 + 1e-12 * rng.uniform(-1, 1, xu.shape))
     goals, xs = goals.astype(np.float32).astype(f64), xs.astype(np.float32).astype(f64)
     M = iiwa_ref.Model()
-    want = {w: merit_ref_f64.merits(M, xu, dz, STEPS9, goals, xs if w else None, N, MU, iiwa.QD_COST, iiwa.r_cost(N)) for w in (True, False)}
+    want = {w: P.merits(M, xu, dz, STEPS9, goals, xs if w else None, N, MU, cost=P.Cost.plain(iiwa.QD_COST, iiwa.r_cost(N)), double=True) for w in (True, False)}
     return xu, goals, xs, dz, want
 
 
@@ -142,7 +141,7 @@ def test_accepted_merit_is_the_merit_of_the_new_iterate(env):
     assert np.array_equal(bits(again)[:, 0], bits(ref))
     assert np.array_equal(ref.cpu().numpy(), merit.cpu().numpy().min(axis=1))
     for b in range(B):
-        assert np.array_equal(bits(d_xu)[b], bits(rho_ref_f64.fma(steps[p[b]], dz[b], xu[b]))), b
+        assert np.array_equal(bits(d_xu)[b], bits(rho_ref.fma(steps[p[b]], dz[b], xu[b]))), b
 
 
 # ---- 4. bit-stability ----
@@ -194,7 +193,7 @@ def test_line_search_step_on_synthetic_merits(nn, mm):
     step = sol.line_search_step(dev(merit), SYN_STEPS, d_ref, dev(dz), d_xu)
     torch.cuda.synchronize()
     h_xu, h_ref = xu0.copy(), ref0.copy()
-    want = rho_ref_f64.step(merit, SYN_STEPS, h_ref, dz, h_xu)
+    want = rho_ref.step(merit, SYN_STEPS, h_ref, dz, h_xu, dtype=np.float64)
     assert want.tolist() == [-1, 1, -1, 3, -1, 3]
     assert step.dtype == torch.int32 and np.array_equal(step.cpu().numpy(), want)
     assert np.array_equal(bits(d_xu), bits(h_xu)) and np.array_equal(bits(d_ref), bits(h_ref))
@@ -205,7 +204,7 @@ def test_line_search_step_on_synthetic_merits(nn, mm):
 # ---- 6. the rho rule ----
 @pytest.mark.parametrize("nn,mm", [(14, 7), (6, 3)])
 def test_line_search_step_rho_on_synthetic_merits(nn, mm):
-    """14 consecutive calls against tests/rho_ref_f64.py after every one (the scenario of tests/test_gpu_rho.py): rho, drho, merit_ref and xu as integer
+    """14 consecutive calls against tests/rho_ref.py in double after every one (the scenario of tests/test_gpu_rho.py): rho, drho, merit_ref and xu as integer
     views, done and step exact.  Trajectory 0 always fails from rho = 1e-3 and gives up; 1 starts at rho = 5 and gives up at the third call (rho grows
     beyond rho_max: reset, done = 1); 2 always succeeds; 3 alternates; 4 sees NaN rows only; 5 comes frozen by the caller: MPCG_STEP_FROZEN, nothing
     written."""
@@ -230,7 +229,7 @@ def test_line_search_step_rho_on_synthetic_merits(nn, mm):
         merit[5] = 1.0
         sol.line_search_step_rho(dev(merit), SYN_STEPS, d["ref"], dev(dz), d["xu"], d["rho"], d["drho"], d["done"], rho_reset=reset, step=d_step)
         torch.cuda.synchronize()
-        want = rho_ref_f64.step(merit, SYN_STEPS, h["ref"], dz, h["xu"], h["rho"], h["drho"], h["done"], rho_reset=reset)
+        want = rho_ref.step(merit, SYN_STEPS, h["ref"], dz, h["xu"], h["rho"], h["drho"], h["done"], rho_reset=reset, dtype=np.float64)
         got = d_step.cpu().numpy()
         assert np.array_equal(got, want), (t, got, want)
         for k in h:

@@ -1,6 +1,6 @@
 """GPU: the step between two SQP solves on the device — mpcg_simulate (simple_simulate, reference include/common/integrator.cuh:295-325, one launch
 for the batch and all substeps) and mpcg_advance_horizon (tracking error, just_shift, tail fills, start-state copy: include/mpcsim.cuh:300-348).
-Pinned on the reference's own trajectory file, against the float64 restatement tests/sim_ref.py (pinned in tests/test_sim_ref_cpu.py), against the
+Pinned on the reference's own trajectory file, against the float64 restatement tests/plant_ref.py (pinned in tests/test_sim_ref_cpu.py), against the
 KKT kernel's integrator defect, and bit for bit across batch sizes, runs, graph replays and a closed MPC loop."""
 import ctypes as C
 import functools
@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import iiwa_ref
-import sim_ref
+import plant_ref as P
 from conftest import GOLDEN
 from mpcgpu_amd import _lib, iiwa
 
@@ -93,7 +93,7 @@ def plan4():
 
 
 def clamped_schedule(toff, sim, recompute=False, ignore=False):
-    S, idx, rem, ridx = sim_ref.schedule(toff, sim, DT, SS)
+    S, idx, rem, ridx = P.schedule(toff, sim, DT, SS)
     if recompute:
         ridx = int((toff * 1e-6 + S * float(SS)) / DT)
     if ignore:
@@ -114,7 +114,7 @@ def test_simulate_vs_host_restatement(toff, sim):
     d_xs, ee = dev(xs.copy()), torch.zeros(3, device="cuda")
     solver(N4, 1).simulate(plant(), d_xs, view, DT, toff, sim, float(SS), eePos=ee)
     got = d_xs.cpu().numpy().astype(np.float64)
-    want = sim_ref.simulate(model(), xs, xu, N4, DT, toff, sim, SS)
+    want = P.simulate(model(), xs, xu, N4, DT, toff, sim, SS)
     assert np.isfinite(got).all() and np.isfinite(ee.cpu().numpy()).all()
     err = (np.abs(got - want) / np.maximum(1.0, np.abs(want))).max()
     ee_err = np.abs(ee.cpu().numpy() - model().ee_pos(want[:7])).max()
@@ -124,7 +124,7 @@ def test_simulate_vs_host_restatement(toff, sim):
     for flag in ("recompute_remainder_index", "ignore_crossing"):
         kw = {"recompute": flag[0] == "r", "ignore": flag[0] == "i"}
         if clamped_schedule(toff, sim, **kw) != clamped_schedule(toff, sim):
-            other = sim_ref.simulate(model(), xs, xu, N4, DT, toff, sim, SS, **{flag: True})
+            other = P.simulate(model(), xs, xu, N4, DT, toff, sim, SS, **{flag: True})
             assert np.abs(other - want).max() > 1e-4, flag
 
 
@@ -132,7 +132,7 @@ def test_the_cases_tell_both_wrong_schedules_apart():
     right = [clamped_schedule(*c) for c in CASES]
     assert any(clamped_schedule(*c, recompute=True) != r for c, r in zip(CASES, right))
     assert any(clamped_schedule(*c, ignore=True) != r for c, r in zip(CASES, right))
-    assert clamped_schedule(46000, 2000) == ([2] * 10, None if sim_ref.schedule(46000, 2000, DT, SS)[2] == 0 else 2)      # the clamp case
+    assert clamped_schedule(46000, 2000) == ([2] * 10, None if P.schedule(46000, 2000, DT, SS)[2] == 0 else 2)      # the clamp case
 
 
 # ---- 3. against existing device code ----
@@ -265,7 +265,7 @@ def advance_case(N, shared, lead, shift=True):
     torch.cuda.synchronize()
     for b in range(B):
         p, g = (plan, goals) if shared else (plan[b], goals[b])
-        xu, lam, goal, off, done, err = sim_ref.advance(shift, N, h["xu"][b], h["lam"][b], h["goal"][b], h["xs"][b], h["ee"][b], p, g, T, int(off0[b]),
+        xu, lam, goal, off, done, err = P.advance(shift, N, h["xu"][b], h["lam"][b], h["goal"][b], h["xs"][b], h["ee"][b], p, g, T, int(off0[b]),
                                                         int(done0[b]), lead)
         assert same(d["xu"][b], xu) and same(d["lam"][b], lam) and same(d["goal"][b], goal), (b, N, shared, lead)
         assert int(d_off[b]) == off and int(d_done[b]) == done, (b, int(d_off[b]), int(d_done[b]))

@@ -1,7 +1,7 @@
 """GPU: mpcg_simulate_f64 and mpcg_advance_horizon_f64 (mpcgpu_amd/csrc/sim_plant.hip.h: simulate_kernel and advance_horizon_kernel with IO = double) — the step between two SQP
 solves with double arrays in and out, which closes the double MPC loop on the device.  The arithmetic is the float entries' (float64 inside): on
 float-representable inputs and a shared substep schedule the outputs rounded to float ARE the float entry's bits; on genuinely double inputs nothing
-passes through float; against the float64 restatement tests/sim_ref_f64.py (pinned in tests/test_sim_ref_f64_cpu.py) and against the double KKT
+passes through float; against the float64 restatement tests/plant_ref.py in double (pinned in tests/test_sim_ref_f64_cpu.py) and against the double KKT
 kernel's integrator the state agrees far below the float rounding this entry removes.  Bit-stability over the batch, runs and graph replays, the
 horizon shift bit for bit, a chain that is not the iiwa, the closed loop in double, refusals, the Python dispatch on dtype and the -DUSE_DOUBLES example."""
 import ctypes as C
@@ -15,8 +15,7 @@ import torch
 
 import chain_models as cm
 import iiwa_ref
-import sim_ref
-import sim_ref_f64
+import plant_ref as P
 from mpcgpu_amd import _lib, iiwa
 from test_gpu_simulate import CASES, five, plan4
 
@@ -32,7 +31,7 @@ F32_ROUNDING = 2.0 ** -24                # the relative rounding of a float stor
 f32, f64 = np.float32, np.float64
 NAN = float("nan")
 
-# Worst |got - want| / max(1, |want|) of the new state and the end-effector position against tests/sim_ref_f64.py, ten times the worst figure
+# Worst |got - want| / max(1, |want|) of the new state and the end-effector position against tests/plant_ref.py, ten times the worst figure
 # measured over the five schedules of test 3 (the margin covers other seeds, as in tests/test_gpu_kkt_f64.py).  Measured: 5.63e-16 (that test's docstring).
 LIMIT_SIM = 5.7e-15
 # Worst gap of one step to -c_1 of mpcg_generate_kkt_f64, ten times the measured worst (test 4's docstring).  Measured: 0 — all 896 values equal in every
@@ -110,8 +109,8 @@ def test_outputs_rounded_to_float_are_the_float_entry(toff, sim, B):
     """Inputs that are floats widened, the substep (double)2e-4f and the two schedules whose remainder is the same in float and in double: ten full
     substeps and none (with the offset of 15,000 us they cross from knot 0 to knot 1), and no full substep and a remainder of 2^-13 s.  B = 5 is no
     multiple of a wavefront's four trajectories."""
-    S32, idx32, rem32, _ = sim_ref.schedule(toff, sim, DT, f32(2e-4))
-    assert sim_ref_f64.schedule(toff, sim, DT, SS32)[:3] == (S32, idx32, float(rem32))      # the same schedule in both entries
+    S32, idx32, rem32, _ = P.schedule(toff, sim, DT, f32(2e-4))
+    assert P.schedule(toff, sim, DT, SS32, double=True)[:3] == (S32, idx32, float(rem32))      # the same schedule in both entries
     xu, xs = (a[:B] for a in five())
     xs32, ee32 = simulate(B, xs, xu, toff, sim, SS32, f32)
     xs64, ee64 = simulate(B, xs, xu, toff, sim, SS32, f64)
@@ -146,7 +145,7 @@ def plan4_64():
 
 
 def clamped_schedule(toff, sim, recompute=False, ignore=False):
-    S, idx, rem, ridx = sim_ref_f64.schedule(toff, sim, DT, SS)
+    S, idx, rem, ridx = P.schedule(toff, sim, DT, SS, double=True)
     if recompute:
         ridx = int((toff * 1e-6 + S * SS) / DT)
     if ignore:
@@ -171,14 +170,14 @@ def test_simulate_vs_host_restatement(toff, sim):
     solver(N4, 1).simulate(plant(), d_xs, view, DT, toff, sim, SS, eePos=ee)
     torch.cuda.synchronize()
     got, ee = d_xs.cpu().numpy(), ee.cpu().numpy()
-    want = sim_ref_f64.simulate(model(), xs, xu, N4, DT, toff, sim, SS)
+    want = P.simulate(model(), xs, xu, N4, DT, toff, sim, SS, double=True)
     assert np.isfinite(got).all() and np.isfinite(ee).all()
     err, ee_err = rel(got, want), rel(ee, model().ee_pos(want[:7]))
     print(f"SIM64-FIG toff {toff} sim {sim}: worst relative error {err:.3e}, end effector {ee_err:.3e}")
     for flag in ("recompute_remainder_index", "ignore_crossing"):
         kw = {"recompute": flag[0] == "r", "ignore": flag[0] == "i"}
         if clamped_schedule(toff, sim, **kw) != clamped_schedule(toff, sim):
-            other = sim_ref_f64.simulate(model(), xs, xu, N4, DT, toff, sim, SS, **{flag: True})
+            other = P.simulate(model(), xs, xu, N4, DT, toff, sim, SS, double=True, **{flag: True})
             assert np.abs(other - want).max() > 1e-4, flag
     assert max(err, ee_err) < F32_ROUNDING, (err, ee_err)
     assert LIMIT_SIM <= F32_ROUNDING and max(err, ee_err) <= LIMIT_SIM, (err, ee_err)
@@ -310,11 +309,10 @@ def advance_case(N, shared, lead, shift=True, dtype=f64):
     solver(N, B).advance_horizon(shift, d["xu"], d["xs"], d["lam"], d["goal"], d["ee"], dev(plan, dtype), dev(goals, dtype), d_off, d_done, d_err,
                                  xu_fill_lead=lead)
     torch.cuda.synchronize()
-    ref = sim_ref_f64 if dtype == f64 else sim_ref
     for b in range(B):
         p, g = (plan, goals) if shared else (plan[b], goals[b])
-        xu, lam, goal, off, done, err = ref.advance(shift, N, h["xu"][b], h["lam"][b], h["goal"][b], h["xs"][b], h["ee"][b], p, g, T, int(off0[b]),
-                                                    int(done0[b]), lead)
+        xu, lam, goal, off, done, err = P.advance(shift, N, h["xu"][b], h["lam"][b], h["goal"][b], h["xs"][b], h["ee"][b], p, g, T, int(off0[b]),
+                                                  int(done0[b]), lead, dtype)
         assert same(d["xu"][b], xu) and same(d["lam"][b], lam) and same(d["goal"][b], goal), (b, N, shared, lead)
         assert int(d_off[b]) == off and int(d_done[b]) == done, (b, int(d_off[b]), int(d_done[b]))
         if err is None:
@@ -376,7 +374,7 @@ def test_simulate_on_a_random_chain_vs_host_restatement():
         xu, xs = doubles(xu32, 46), doubles(xs32, 47)
         got, ee = simulate(B, xs, xu, 15000, 2100, SS, pl=Plant(cm.tables(chain)))
         for b in range(B):
-            want = sim_ref_f64.simulate(chain, xs[b], xu[b], N4, DT, 15000, 2100, SS)
+            want = P.simulate(chain, xs[b], xu[b], N4, DT, 15000, 2100, SS, double=True)
             assert np.abs(want - xs[b]).max() > 1e-4
             err = max(rel(got[b], want), rel(ee[b], chain.ee_pos(want[:7])))
             print(f"SIM64-FIG random chain {size} trajectory {b}: worst relative error {err:.3e}")
@@ -500,7 +498,7 @@ def test_python_dispatch_on_dtype():
         assert fn(sol._h, plant()._p, 7, p(d_xs), p(d_xu), DT, 15000.0, 2100.0, ss, p(ee), 5, None) == 0
         torch.cuda.synchronize()
         assert got_xs.dtype == dtype and same(got_xs, d_xs) and same(got_ee, ee) and np.isfinite(got_ee).all()
-    d32, _ = advance_case(4, True, 0, dtype=f32)                                # (against tests/sim_ref.py: the float entry's bits)
+    d32, _ = advance_case(4, True, 0, dtype=f32)                                # (against the float restatement: the float entry's bits)
     assert d32["xu"].dtype == torch.float32
     d64, _ = advance_case(4, True, 0, dtype=f64)
     assert d64["xu"].dtype == torch.float64

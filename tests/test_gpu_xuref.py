@@ -1,5 +1,5 @@
 """GPU: mpcg_generate_kkt_xuref(_f64) and mpcg_compute_merit_xuref(_f64) — the generalised running cost over a joint-space plan (include/mpcg.h;
-mpcgpu_amd/csrc/kkt_plant.hip.h, merit_plant.hip.h, merit_plant_f32.hip.h, COST = 1) — against the float64 restatement tests/xuref_ref.py, against the
+mpcgpu_amd/csrc/kkt_plant.hip.h, merit_plant.hip.h, merit_plant_f32.hip.h, COST = 1) — against the float64 restatement tests/plant_ref.py, against the
 existing entries where the cost reduces to theirs, against each other on the device (the merit's central differences are the KKT gradient), for
 independence of the batch, inside a hipGraph that follows d_traj_offset, and through the error table.  Inputs: iiwa.random_windows; the plan is
 random rows of 21."""
@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import iiwa_ref
-import xuref_ref as X
+import plant_ref as X
 from mpcgpu_amd import XuRef, _lib, iiwa
 
 pytestmark = pytest.mark.gpu
@@ -98,7 +98,7 @@ class Case:
         return self._dyn[(b, integrator)]
 
     def want_kkt(self, b, cost, integrator=0):
-        return X.generate_kkt(model(), self.xu[b], None if cost.ee_cost == 0 else self.goals[b], self.xs[b], self.N, self.rows(b), cost, DT, integrator,
+        return X.generate_kkt(model(), self.xu[b], None if cost.ee_cost == 0 else self.goals[b], self.xs[b], self.N, rows=self.rows(b), cost=cost, dt=DT, integrator=integrator,
                               base=self.dynamics(b, integrator))
 
     def xuref(self, cost, dtype, offsets=None, plan=None):
@@ -212,7 +212,7 @@ def test_reduces_to_generate_kkt(N, B, build, integrator):
 @functools.lru_cache(maxsize=None)
 def want_merits(N, B, cost, with_xs, integrator, double):
     cs, co = case(N, B, double), COSTS[cost]
-    return X.merits(model(), cs.xu, cs.dz, STEPS9, None if co.ee_cost == 0 else cs.goals, cs.xs if with_xs else None, N, MU, cs.rows, co, DT, integrator, double)
+    return X.merits(model(), cs.xu, cs.dz, STEPS9, None if co.ee_cost == 0 else cs.goals, cs.xs if with_xs else None, N, MU, rows_of=cs.rows, cost=co, dt=DT, integrator=integrator, double=double)
 
 
 @pytest.mark.parametrize("with_xs", [True, False])
@@ -287,7 +287,7 @@ def test_merit_differences_are_the_kkt_gradient(flags):
     print(f"flags={flags}: |g| up to {np.abs(g).max():.3g}, central differences off by {err:.2e}")
     assert err <= 1e-9, err
     rows = X.plan_rows(cs.plan, 0, 2, N, cs.T)
-    assert np.abs(g - X.generate_kkt(model(), xu, None, cs.xs[0], N, rows, co, base=(np.zeros(0), np.zeros(ROW * N - m), np.zeros(0)))[2]).max() <= 1e-12
+    assert np.abs(g - X.generate_kkt(model(), xu, None, cs.xs[0], N, rows=rows, cost=co, base=(np.zeros(0), np.zeros(ROW * N - m), np.zeros(0)))[2]).max() <= 1e-12
 
 
 # ---- 6. a trajectory's outputs do not depend on the batch ----

@@ -1,4 +1,4 @@
-"""CPU: tests/integrator_ref.py — the restatement of semi-implicit Euler the GPU tests of options "integrator" / "sim_integrator" compare against
+"""CPU: integrator 1 of tests/plant_ref.py — the restatement of semi-implicit Euler the GPU tests of options "integrator" / "sim_integrator" compare against
 (tests/test_gpu_integrator.py) — pinned against the step map itself, and the cases of those GPU tests shown to tell the two integrators apart by far
 more than their tolerances.  No GPU."""
 import functools
@@ -8,8 +8,7 @@ import pytest
 
 import chain_models as cm
 import iiwa_ref
-import integrator_ref as ir
-import sim_ref
+import plant_ref as P
 from mpcgpu_amd import iiwa
 
 n, m = 14, 7
@@ -37,7 +36,7 @@ def windows():
 @functools.lru_cache(maxsize=None)
 def restated(which, integrator):
     xu, goals, xs = windows()
-    return [ir.generate_kkt(model(which), xu[b], goals[b], xs[b], N, DT, integrator) for b in range(B)]
+    return [P.generate_kkt(model(which), xu[b], goals[b], xs[b], N, dt=DT, integrator=integrator) for b in range(B)]
 
 
 def knots(b):
@@ -48,23 +47,23 @@ def knots(b):
 
 @pytest.mark.parametrize("which", MODELS)
 def test_restated_A_and_B_are_the_derivative_of_the_step_map(which):
-    """A and B of integrator_ref.generate_kkt (out of the dense C) against central differences, h = 1e-6, of semi_implicit_step itself, on every knot of
+    """A and B of plant_ref.generate_kkt (out of the dense C) against central differences, h = 1e-6, of step(..., 1) itself, on every knot of
     the windows.  Limit 1e-8: 14 to 30 times the worst measured (3.2e-10 on the iiwa, 7.1e-10 on the chain), to absorb BLAS differences between machines —
     and 1e5 times below what separates the integrators (next test).  The defect is the step map by construction: checked to be exactly x_{k+1} - step."""
     M = model(which)
     h, worst = 1e-6, 0.0
     for b in range(B):
         _, C, _, c = restated(which, 1)[b]
-        A, Bm, cc = ir.blocks(C, c, N)
+        A, Bm, cc = P.blocks(C, c, N)
         for k, x, u, xn in knots(b):
             z = np.concatenate([x, u])
             J = np.zeros((n, n + m))
             for j in range(n + m):
                 e = np.zeros(n + m)
                 e[j] = h
-                J[:, j] = (ir.semi_implicit_step(M, (z + e)[:n], (z + e)[n:], DT) - ir.semi_implicit_step(M, (z - e)[:n], (z - e)[n:], DT)) / (2 * h)
+                J[:, j] = (P.step(M, (z + e)[:n], (z + e)[n:], DT, 1) - P.step(M, (z - e)[:n], (z - e)[n:], DT, 1)) / (2 * h)
             worst = max(worst, np.abs(A[k] - J[:, :n]).max(), np.abs(Bm[k] - J[:, n:]).max())
-            assert np.array_equal(cc[k + 1], xn - ir.semi_implicit_step(M, x, u, DT))
+            assert np.array_equal(cc[k + 1], xn - P.step(M, x, u, DT, 1))
     print(f"INTEGRATOR-FIG {which}: restated A, B against central differences of the step map, worst {worst:.2e}")
     assert worst <= 1e-8, worst
 
@@ -76,8 +75,10 @@ def test_integrator_0_is_the_existing_restatement_exactly(which):
         for a, w in zip(restated(which, 0)[b], iiwa_ref.generate_kkt(model(which), xu[b], goals[b], xs[b], N)):
             assert np.array_equal(a, w)
     x, u = xu[0, :n], xu[0, n:n + m]
-    assert np.array_equal(ir.step(model(which), x, u, DT, 0), sim_ref.euler_step(model(which), x, u, DT))
-    assert np.array_equal(ir.defect(model(which), x, u, xu[0, n + m:2 * n + m], DT, 0), iiwa_ref.euler_defect(model(which), x, u, xu[0, n + m:2 * n + m], DT))
+    assert np.array_equal(P.step(model(which), x, u, DT, 0), -iiwa_ref.euler_defect(model(which), x, u, np.zeros(n), DT))
+    assert np.array_equal(P.defect(model(which), x, u, xu[0, n + m:2 * n + m], DT, 0), iiwa_ref.euler_defect(model(which), x, u, xu[0, n + m:2 * n + m], DT))
+    A, Bm, _ = P.blocks(*restated(which, 0)[0][1::2], N)
+    assert all(np.array_equal(a, w) for a, w in zip(P.AB(model(which), x, u, DT, 0), (A[0], Bm[0])))
 
 
 @pytest.mark.parametrize("which", KKT_MODELS)
@@ -91,7 +92,7 @@ def test_the_kkt_cases_tell_the_integrators_apart(which):
     for b in range(B):
         (G0, C0, g0, c0), (G1, C1, g1, c1) = restated(which, 0)[b], restated(which, 1)[b]
         assert np.array_equal(G0, G1) and np.array_equal(g0, g1) and np.array_equal(c0[:n], c1[:n])
-        (A0, B0, d0), (A1, B1, d1) = ir.blocks(C0, c0, N), ir.blocks(C1, c1, N)
+        (A0, B0, d0), (A1, B1, d1) = P.blocks(C0, c0, N), P.blocks(C1, c1, N)
         assert np.array_equal(A0[:, 7:], A1[:, 7:]) and np.array_equal(B0[:, 7:], B1[:, 7:])         # the lower halves are explicit Euler's
         for k in range(N - 1):
             lo["A"] = min(lo["A"], np.abs(A0[k, :7] - A1[k, :7]).max() / max(1.0, np.abs(A1[k]).max()))
@@ -110,20 +111,20 @@ def test_the_simulate_cases_tell_the_integrators_apart(which="iiwa"):
     rel = lambda a, w: float((np.abs(a - w) / np.maximum(1.0, np.abs(w))).max())
     gaps = {"2e-3 x 4": [], "1/64 x 1": [], "2e-4 x 10": []}
     for b in range(B):
-        gaps["2e-3 x 4"].append(rel(ir.simulate(M, xs[b], xu[b], N, DT, integrator=0, **SIM_CASE), ir.simulate(M, xs[b], xu[b], N, DT, integrator=1, **SIM_CASE)))
-        gaps["1/64 x 1"].append(rel(ir.simulate(M, xs[b], xu[b], N, DT, 0, 15625, 1 / 64, 0), ir.simulate(M, xs[b], xu[b], N, DT, 0, 15625, 1 / 64, 1)))
-        gaps["2e-4 x 10"].append(rel(ir.simulate(M, xs[b], xu[b], N, DT, 0, 2000, sim_ref.SIM_STEP, 0), ir.simulate(M, xs[b], xu[b], N, DT, 0, 2000, sim_ref.SIM_STEP, 1)))
+        gaps["2e-3 x 4"].append(rel(P.simulate(M, xs[b], xu[b], N, DT, integrator=0, **SIM_CASE), P.simulate(M, xs[b], xu[b], N, DT, integrator=1, **SIM_CASE)))
+        gaps["1/64 x 1"].append(rel(P.simulate(M, xs[b], xu[b], N, DT, 0, 15625, 1 / 64, 0), P.simulate(M, xs[b], xu[b], N, DT, 0, 15625, 1 / 64, 1)))
+        gaps["2e-4 x 10"].append(rel(P.simulate(M, xs[b], xu[b], N, DT, 0, 2000, P.SIM_STEP, 0), P.simulate(M, xs[b], xu[b], N, DT, 0, 2000, P.SIM_STEP, 1)))
     print(f"INTEGRATOR-FIG {which}: simulate gaps per trajectory", {k: [f"{g:.1e}" for g in v] for k, v in gaps.items()})
-    assert sim_ref.schedule(SIM_CASE["toff_us"], SIM_CASE["sim_us"], DT, SIM_CASE["sim_step"])[0] in (3, 4)
+    assert P.schedule(SIM_CASE["toff_us"], SIM_CASE["sim_us"], DT, SIM_CASE["sim_step"])[0] in (3, 4)
     assert min(gaps["2e-3 x 4"]) >= 10 * GPU_TOL and min(gaps["1/64 x 1"]) >= 10 * GPU_TOL, gaps
 
 
 def test_merit_restatement_measures_the_kkt_restatements_defect():
-    """merit(mu = 2) - merit(mu = 1) of integrator_ref.merits is the 1-norm of integrator_ref.generate_kkt's c, for either integrator (d_xs given, step 0)."""
+    """merit(mu = 2) - merit(mu = 1) of plant_ref.merits is the 1-norm of plant_ref.generate_kkt's c, for either integrator (d_xs given, step 0)."""
     xu, goals, xs = windows()
     M = model("iiwa")
     for integrator in (0, 1):
-        tail = (N, iiwa.QD_COST, iiwa.r_cost(N), DT, integrator)
-        m2, m1 = (ir.merits(M, xu[:1], None, [0.0], goals[:1], xs[:1], tail[0], mu, *tail[1:])[0, 0] for mu in (2.0, 1.0))
+        tail = dict(cost=P.Cost.plain(iiwa.QD_COST, iiwa.r_cost(N)), dt=DT, integrator=integrator)
+        m2, m1 = (P.merits(M, xu[:1], None, [0.0], goals[:1], xs[:1], N, mu, **tail)[0, 0] for mu in (2.0, 1.0))
         want = np.abs(restated("iiwa", integrator)[0][3]).sum()
         assert abs((m2 - m1) - want) <= 1e-12 * max(1.0, m2), (integrator, m2 - m1, want)

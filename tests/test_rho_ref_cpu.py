@@ -56,7 +56,7 @@ def test_an_alternating_trajectory_stays_bounded():
 
 
 def test_step_freezes_and_follows_the_selection_rule():
-    """rho_ref.step: the selection of merit_ref.select (strict, first of equals, a NaN never wins), the update, and the freeze."""
+    """rho_ref.step: the selection of plant_ref.select (strict, first of equals, a NaN never wins), the update, and the freeze."""
     nan = float("nan")
     merit = np.array([[5, 6], [3, 2], [nan, nan], [1, 1]], f32)
     ref = np.full(4, 4.0, f32)

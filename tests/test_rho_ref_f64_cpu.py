@@ -1,4 +1,4 @@
-"""CPU: the double rho restatement tests/rho_ref_f64.py pinned (a) to the float restatement tests/rho_ref.py on sequences where float and double
+"""CPU: the double setting of the rho restatement tests/rho_ref.py (dtype = np.float64) pinned (a) to its float setting on sequences where float and double
 arithmetic agree exactly — a dyadic factor and dyadic starts: every product and quotient is exact in both — and (b) to a hand-written list for the
 reference's constants (include/pcg/sqp.cuh:304-320: factor 1.2, rho_min 1e-3, rho_max 10).  The decimal strings are the shortest that identify the
 double (repr): equality is exact.  Also the exactly rounded fma the step restatement uses."""
@@ -7,7 +7,6 @@ from fractions import Fraction
 import numpy as np
 
 import rho_ref
-import rho_ref_f64
 
 f64 = np.float64
 
@@ -21,7 +20,7 @@ def test_dyadic_sequences_agree_with_the_float_restatement_exactly():
         gave_up = False
         for p in outcomes:
             ra, da, xa = rho_ref.update(*a, p, **kw)
-            rb, db, xb = rho_ref_f64.update(*b, p, **kw)
+            rb, db, xb = rho_ref.update(*b, p, dtype=np.float64, **kw)
             assert ra.dtype == np.float32 and rb.dtype == f64
             assert (float(ra), float(da), xa) == (float(rb), float(db), xb), (rho0, p)
             a, b = (ra, da), (rb, db)
@@ -38,7 +37,7 @@ def test_the_reference_constants_against_a_hand_written_list():
     seq = []
     rho, drho = 1e-3, 1.0
     for p in [-1, -1, 0] + [-1] * 12:
-        rho, drho, done = rho_ref_f64.update(rho, drho, p)
+        rho, drho, done = rho_ref.update(rho, drho, p, dtype=np.float64)
         seq.append((repr(float(rho)), repr(float(drho)), done))
         if done:
             break
@@ -77,10 +76,10 @@ def test_the_reference_constants_against_a_hand_written_list():
 def test_fma_is_rounded_once():
     """x + a d where the product needs more than 53 bits: the fused result differs from the two-rounding one."""
     a, d, x = 1.0 + 2.0 ** -30, np.array([1.0 + 2.0 ** -30]), np.array([-1.0])
-    got = rho_ref_f64.fma(a, d, x)[0]
+    got = rho_ref.fma(a, d, x)[0]
     assert got == 2.0 ** -29 + 2.0 ** -60                      # exact: (1 + e)^2 - 1 = 2 e + e^2
     assert f64(a) * d[0] + x[0] == 2.0 ** -29                  # the separate product lost e^2
-    nan = rho_ref_f64.fma(-0.5, np.array([np.nan, 1.0]), np.array([1.0, 1.0]))
+    nan = rho_ref.fma(-0.5, np.array([np.nan, 1.0]), np.array([1.0, 1.0]))
     assert np.isnan(nan[0]) and nan[1] == 0.5
 
 
@@ -89,6 +88,6 @@ def test_step_without_rho_is_the_plain_step():
     merit = np.array([[5, 6], [3, 2], [nan, nan]], f64)
     ref = np.full(3, 4.0)
     xu, dz = np.ones((3, 3)), np.full((3, 3), 2.0)
-    got = rho_ref_f64.step(merit, [-1.0, -0.3], ref, dz, xu)
+    got = rho_ref.step(merit, [-1.0, -0.3], ref, dz, xu, dtype=np.float64)
     assert got.tolist() == [-1, 1, -1] and ref.tolist() == [4.0, 2.0, 4.0]
     assert xu[1, 0] == float(Fraction(-0.3) * 2 + 1) and xu[0, 0] == 1.0

@@ -1,4 +1,4 @@
-"""CPU: tests/xuref_ref.py, the float64 restatement of the generalised running cost (mpcg_generate_kkt_xuref / mpcg_compute_merit_xuref), against
+"""CPU: the Cost argument of tests/plant_ref.py, the float64 restatement of the generalised running cost (mpcg_generate_kkt_xuref / mpcg_compute_merit_xuref), against
 itself — its two reductions, the gradient and Hessian of its own cost sum, the row rule — and the four new symbols in the built library and in
 include/mpcg.h."""
 import os
@@ -9,7 +9,7 @@ import pytest
 
 from conftest import ROOT
 import iiwa_ref
-import xuref_ref as X
+import plant_ref as X
 from mpcgpu_amd import iiwa
 
 n, m, NJ, ROW = 14, 7, 7, 21
@@ -35,7 +35,7 @@ def test_reduces_to_the_end_effector_plant(model, N):
     xu, goals, xs = window(N, 5 + N)
     rows = X.plan_rows(plan(9, N), 0, 3, N, 9)
     cost = X.Cost(1.0, 0.0, iiwa_ref.QD_COST, iiwa_ref.r_cost(N), 0)
-    got = X.generate_kkt(model, xu, goals, xs, N, rows, cost)
+    got = X.generate_kkt(model, xu, goals, xs, N, rows=rows, cost=cost)
     want = [a.copy() for a in iiwa_ref.generate_kkt(model, xu, goals, xs, N)]
     last = slice(ROW * (N - 1) + NJ, ROW * (N - 1) + n)
     assert not np.array_equal(got[2][last], want[2][last])
@@ -54,7 +54,7 @@ def test_reduces_to_the_joint_space_plant(model, N):
     P = plan(T, 40 + N)
     rows = X.plan_rows(P, 0, off, N, T)
     cost = X.Cost(0.0, 0.37, 2e-3, 5e-4, X.QD_RELATIVE)
-    G, C, g, c = X.generate_kkt(model, xu, None, xs, N, rows, cost)
+    G, C, g, c = X.generate_kkt(model, xu, None, xs, N, rows=rows, cost=cost)
     _, C0, _, c0 = iiwa_ref.generate_kkt(model, xu, goals, xs, N)
     assert np.array_equal(C, C0) and np.array_equal(c, c0)
     Q = np.diag([0.37] * NJ + [2e-3] * NJ)
@@ -77,7 +77,7 @@ def test_g_is_the_gradient_and_G_the_hessian_of_the_cost_sum(model, flags):
     xu, _, xs = window(N, 23)
     rows = X.plan_rows(plan(T, 7), 0, -1, N, T)
     cost = X.Cost(0.0, 0.8, 0.05, 0.02, flags)
-    G, _, g, _ = X.generate_kkt(model, xu, None, xs, N, rows, cost)
+    G, _, g, _ = X.generate_kkt(model, xu, None, xs, N, rows=rows, cost=cost)
     J = lambda z: X.joint_cost(z, rows, N, cost)
     h = 1e-3
     num = np.zeros_like(g)
@@ -113,17 +113,16 @@ def test_row_rule():
 
 
 def test_merit_is_the_cost_sum_plus_the_violations(model):
-    """mu = 0 leaves sum_k J_k: the joint-space sum plus ee_cost times the end-effector sum; and the violation terms are merit_ref's."""
-    import merit_ref
+    """mu = 0 leaves sum_k J_k: the joint-space sum plus ee_cost times the end-effector sum; and the violation terms are the plain cost's."""
     N, T = 3, 4
     xu, goals, xs = window(N, 31)
     rows = X.plan_rows(plan(T, 3), 0, 1, N, T)
     cost = X.Cost(0.6, 0.3, 0.01, 0.02, X.QD_RELATIVE | X.U_RELATIVE)
-    got = X.merit_at(model, xu, goals, xs, N, 0.0, rows, cost)
+    got = X.merit_at(model, xu, goals, xs, N, 0.0, rows=rows, cost=cost)
     assert got == X.joint_cost(xu, rows, N, cost) + 0.6 * X.ee_cost_sum(model, xu, goals, N)
     plain = X.Cost(1.0, 0.0, iiwa_ref.QD_COST, iiwa_ref.r_cost(N), 0)
-    a = X.merit_at(model, xu, merit_ref.f32(goals).astype(np.float64), merit_ref.f32(xs).astype(np.float64), N, 10.0, rows, plain)
-    b = merit_ref.merit_at(model, xu, goals, xs, N, 10.0, iiwa_ref.QD_COST, iiwa_ref.r_cost(N))
+    a = X.merit_at(model, xu, X.f32(goals).astype(np.float64), X.f32(xs).astype(np.float64), N, 10.0, rows=rows, cost=plain)
+    b = X.merit_at(model, xu, X.f32(goals), X.f32(xs), N, 10.0, cost=X.Cost.plain(iiwa_ref.QD_COST, iiwa_ref.r_cost(N)))
     assert abs(a - b) <= 1e-13 * max(1.0, abs(b))
 
 
