@@ -13,45 +13,12 @@ import pytest
 import torch
 
 import plant_ref as P
+from chain_cost_cases import WEIGHTS, bounds_of, f32, limits_of
 from mpcgpu_amd import XuRef, _lib, iiwa
 from test_gpu_xuref import COSTS, DT, KKT_BUILDS, LIMIT_C, LIMIT_Ggc, MERIT_BUILDS, MU, SHAPES, STEPS8, STEPS9, bits, case, dev, model, plant, solver, want_merits
 
 pytestmark = pytest.mark.gpu
 n, m, NJ, ROW = 14, 7, 7, 21
-WEIGHTS = (3.0, 0.25, 0.125)                                  # q, qd, u: floats
-f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
-
-
-def bounds_of(vals):
-    """(lo, hi) [7] each, float32-representable, for vals [rows, 7]: per joint the lower and upper third of its values, each bound halfway between two
-    neighbours of the sorted values; a joint with fewer than three values lies below (joint % 3 == 0), inside (1) or above (2) its bounds as a whole."""
-    vals = np.asarray(vals, np.float64)
-    lo, hi = np.zeros(NJ), np.zeros(NJ)
-    for i in range(NJ):
-        s = np.sort(vals[:, i])
-        if len(s) >= 3:
-            k = len(s) // 3
-            lo[i], hi[i] = 0.5 * (s[k - 1] + s[k]), 0.5 * (s[-k - 1] + s[-k])
-        else:
-            d = 0.25
-            lo[i], hi[i] = ((s[-1] + d, s[-1] + 2 * d), (s[0] - d, s[-1] + d), (s[0] - 2 * d, s[0] - d))[i % 3]
-    lo, hi = f32(lo), f32(hi)
-    assert (lo <= hi).all() and not (vals == lo).any() and not (vals == hi).any()          # no value ON a bound
-    return lo, hi
-
-
-def limits_of(xs_list, us_list, weights=WEIGHTS):
-    """Limits from all the states [*, 14] and controls [*, 7] given; joint 1's lower bound of every kind is -inf (one-sided).  Valid only if below, inside and
-    above each occur for q, qd and u."""
-    x, u = np.concatenate(xs_list), np.concatenate(us_list)
-    (q_lo, q_hi), (qd_lo, qd_hi), (u_lo, u_hi) = bounds_of(x[:, :NJ]), bounds_of(x[:, NJ:]), bounds_of(u)
-    for lo in (q_lo, qd_lo, u_lo):
-        lo[1] = -np.inf
-    lim = P.Limits(q_lo, q_hi, qd_lo, qd_hi, u_lo, u_hi, *weights)
-    for name, vals, lo, hi in (("q", x[:, :NJ], q_lo, q_hi), ("qd", x[:, NJ:], qd_lo, qd_hi), ("u", u, u_lo, u_hi)):
-        s = P.side(vals, lo, hi)
-        assert all((s == v).any() for v in (-1, 0, 1)), name
-    return lim
 
 
 def states_controls(cs, steps):

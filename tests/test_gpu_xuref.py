@@ -12,6 +12,7 @@ import torch
 
 import iiwa_ref
 import plant_ref as X
+from chain_cost_cases import COSTS                              # "all" (every weight positive, both flags) and "joint" (ee_cost = 0 with a NULL goal pointer)
 from mpcgpu_amd import XuRef, _lib, iiwa
 
 pytestmark = pytest.mark.gpu
@@ -21,9 +22,6 @@ MU = 10.0
 STEPS9 = [0.0] + [-1.0 / (1 << p) for p in range(8)]          # 0, -1, -1/2, ..., -1/128
 STEPS8 = STEPS9[1:]
 SHAPES = ((2, 1), (3, 2), (5, 3), (8, 3))                     # (2, 1): one block that is first and last; B (N - 1) = 1 and 21 are odd: the packed build has an idle half
-# weights that are floats (the float entries take qd_cost and r_cost as floats; the packed build rounds ee_cost and q_cost)
-COSTS = {"all": X.Cost(0.75, 0.5, 2.0 ** -6, 2.0 ** -7, X.QD_RELATIVE | X.U_RELATIVE),          # every weight positive, both flags
-         "joint": X.Cost(0.0, 0.5, 2.0 ** -6, 2.0 ** -7, X.QD_RELATIVE)}                        # ee_cost = 0 with a NULL goal pointer: iiwa_plant.cuh
 # limits of the existing entries' tests: tests/test_gpu_kkt.py (1e-6; 3e-6 with differences; 1e-5 in float arithmetic), tests/test_gpu_kkt_f64.py,
 # tests/test_gpu_merit.py (1e-6), tests/test_gpu_merit_f32.py (1e-5), tests/test_gpu_merit_f64.py (1.2e-13) — all relative to max(1, |reference|)
 KKT_BUILDS = {"default": ((), 1e-6), "difference": ((("kkt_analytic", 0),), 3e-6), "kkt_f32=1": ((("kkt_f32", 1),), 1e-5), "kkt_f32=2": ((("kkt_f32", 2),), 1e-5)}
