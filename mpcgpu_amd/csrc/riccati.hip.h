@@ -27,7 +27,7 @@
 //   5  K_k = -W[:, m:] stored (rounded once to the storage type), P -= Hk^T W[:, m:] on the lower triangle, then the mirror.
 // Float64 inside for both entries, as the plant kernels: IO = float widens on load (exact) and rounds K once.  <IO, 14, 7> has the loop bounds at
 // compile time; <IO, 0, 0> reads (n, m) from the arguments and serves every other shape (its prefetch holds RIC_PF_RT elements per lane, what lies
-// beyond — shapes above about 17 x 17 — is loaded where it is used).  Loop bounds are host arguments only: a trajectory of NaN, Inf or zeros ends
+// beyond — a knot of tot = 2 n^2 + m^2 + n m > 64 RIC_PF_RT = 1280 elements, first at 18 x 18 with 1296 — is loaded where it is used).  Loop bounds are host arguments only: a trajectory of NaN, Inf or zeros ends
 // like any other and, a workgroup of its own, touches nobody else's data.
 #pragma once
 #include <hip/hip_runtime.h>

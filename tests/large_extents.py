@@ -424,6 +424,23 @@ def kkt_specs():
     return [kkt_spec(*c) for c in KKT_CASES]
 
 
+# mpcg_riccati_gains(_f64): 14 x 7 at three knots, the first admissible batch whose G passes 2^32 bytes (686 elements per trajectory: 1,565,222
+# trajectories in float, 782,611 in double; G, C, K and rho together 9.2 GB either way); one rho per trajectory, so rho_v[b] is indexed there too.
+RICCATI_N = 3
+
+
+def riccati_spec(prec):
+    N, dt = RICCATI_N, A.DT[prec]
+    B, D = pick_batch(2 ** 32, A.glen(n14, m7, N) * E[prec])
+    arrays = [arr("G", dt, A.glen(n14, m7, N), "in"), arr("C", dt, A.clen(n14, m7, N), "in"), arr("rho", dt, 1, "in"),
+              arr("K", dt, (N - 1) * m7 * n14, "out")]
+    return Spec(f"riccati_gains {prec} N{N} B{B}", arrays, D, B, 0)                # (pure stream work: the handle owns nothing for it)
+
+
+def riccati_specs():
+    return [riccati_spec(p) for p in ("f32", "f64")]
+
+
 # mpcg_convert_f32_to_f16: the element index passes int, the source 2^33 bytes, the destination 2^32 bytes, the ragged tail at the top.
 CONVERT_COUNT = 2 ** 31 + 13
 
@@ -433,4 +450,4 @@ def convert_need():
 
 
 def all_specs():
-    return form_specs() + dz_specs() + pcg_specs() + linalg_specs() + kkt_specs()
+    return form_specs() + dz_specs() + pcg_specs() + linalg_specs() + kkt_specs() + riccati_specs()

@@ -21,6 +21,14 @@ CASES = {
     "carried P": [(14, 7, 3, 5), (14, 7, 33, 5)],                                                    # mirror, prefetch of knot k-1, odd batch
     "run-time dims": [(1, 1, 3, 5), (6, 3, 5, 5), (13, 5, 4, 5), (17, 17, 3, 5), (32, 8, 3, 2), (32, 32, 2, 2)],
     "foreign m": [(14, 3, 4, 3)],                                                                    # a 14-state handle, not the tuned control size
+    "never computed": [                                    # the smallest shape at which ... (LDS bytes), each with P carried over two knots
+        (3, 2, 4, 3),                                      # odd n, even m: the tile row of phase 3 that straddles A and B feeds a second and a third knot (704)
+        (18, 18, 3, 2),                                    # tot = 1296: the first shape past the 1280-element prefetch, a tail of 16 lanes (23,360)
+        (34, 32, 3, 2),                                    # w = 66: one column on the second trip of the elimination's strided loop; first above 64 KiB (73,984)
+        (40, 30, 3, 2),                                    # w = 70, LM = 32 != m, LD = n (85,760)
+        (64, 1, 3, 2),                                     # the widest P with one control: LM = 4 is three quarters pad (103,456)
+        (64, 28, 3, 2),                                    # the last shape that fits the 160 KiB, on numbers (161,920)
+    ],
 }
 ALL_CASES = [c for group in CASES.values() for c in group]
 
@@ -100,3 +108,51 @@ def e_ref(G, C, n, m, N, rho):
     K64 = gains(G, C, n, m, N, rho, np.float64)
     Kld = gains(G, C, n, m, N, rho, np.longdouble)
     return knot_err(K64.astype(np.longdouble), Kld), K64
+
+
+# ---- the gains as the sensitivity of the QP's solution (tests/test_riccati_ref_cpu.py on the host, tests/test_gpu_riccati.py on the device) ----
+def kkt_cond(k, rho, Cm):
+    """cond_2 of the regularised KKT matrix dense_kkt_solve factors."""
+    N, n, m = k.Q.shape[1], k.Q.shape[2], k.R.shape[-1]
+    nz = (n + m) * N - m
+    Gm = np.zeros((nz, nz))
+    for kk in range(N):
+        o = kk * (n + m)
+        Gm[o:o + n, o:o + n] = k.Q[0, kk] + rho * np.eye(n)
+        if kk < N - 1:
+            Gm[o + n:o + n + m, o + n:o + n + m] = k.R[0, kk] + rho * np.eye(m)
+    return float(np.linalg.cond(np.block([[Gm, Cm.T], [Cm, np.zeros((n * N, n * N))]])))
+
+
+def perturbed(k, seed):
+    """The same QP with another c in knot 1 only."""
+    from mpcgpu_amd import synth
+    c = k.c.copy()
+    c[0, 1] += np.random.default_rng(seed).standard_normal(c.shape[-1])
+    return synth.KKT(k.Q, k.R, k.A, k.Bm, k.q, k.r, c)
+
+
+def feedback_residuals(dz0, dz1, K, k):
+    """The two relative residuals of a solution difference caused in knot 1: du_k - K_k dx_k and dx_{k+1} - A_k dx_k - B_k du_k, k >= 1,
+    against the largest entry of the difference."""
+    N, n, m = k.Q.shape[1], k.Q.shape[2], k.R.shape[-1]
+    d = dz1 - dz0
+    dx = [d[kk * (n + m):kk * (n + m) + n] for kk in range(N)]
+    du = [d[kk * (n + m) + n:(kk + 1) * (n + m)] for kk in range(N - 1)]
+    scale = np.abs(d).max()
+    assert scale > 1e-3, "the perturbation did not reach the solution"
+    assert np.abs(dx[0]).max() <= 1e-9 * scale                 # x_0 is pinned: what hides K_0 from every right-hand side
+    r_fb = max(np.abs(du[kk] - K[kk] @ dx[kk]).max() for kk in range(1, N - 1))
+    r_dyn = max(np.abs(dx[kk + 1] - k.A[0, kk] @ dx[kk] - k.Bm[0, kk] @ du[kk]).max() for kk in range(1, N - 1))
+    return r_fb / scale, r_dyn / scale
+
+
+def kkt_of_packed(G, C, g, c, n, m, N):
+    """One trajectory's packed (G, C, g, c) — what mpcg_generate_kkt_f64 leaves on the device — as a synth.KKT of batch 1 in float64 (exact:
+    synth.pack_kkt_dense of the result gives the same arrays back)."""
+    from mpcgpu_amd import synth
+    Q, R, A, Bm = unpack(G, C, n, m, N, np.float64)
+    gz = np.zeros((n + m) * N)
+    gz[:(n + m) * N - m] = np.asarray(g, np.float64)
+    gz = gz.reshape(N, n + m)
+    return synth.KKT(Q[None], R[None], A[None], Bm[None], gz[None, :, :n].copy(), gz[None, :N - 1, n:].copy(), np.asarray(c, np.float64).reshape(1, N, n).copy())

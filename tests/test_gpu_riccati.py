@@ -1,6 +1,7 @@
 """GPU: mpcg_riccati_gains(_f64) — the Riccati feedback gains of include/mpcg_riccati.h — against the numpy restatement tests/riccati_ref.py on the
 smallest shapes at which each thing can break (riccati_ref.CASES), on blocks mpcg_generate_kkt made for the iiwa, and for what the contract
-promises bit for bit: rho per trajectory, graph replay, batch position, reproducibility, containment, extents, the refusals.
+promises bit for bit: rho per trajectory, graph replay, batch position, reproducibility, containment, extents, the refusals; and against the
+library's own QP solve (Schur formation, block solve, dz in double), whose solution's sensitivity to x_k the gains are.
 
 TOLERANCE.  Per knot ||K_gpu - K64||_max / max(1, ||K64||_max) <= 16 max(e_ref, 2.2e-16), e_ref being float64 against 80-bit arithmetic of the
 restatement ON THE SAME INPUTS, computed here: the kernel sums in another order and fuses multiply-adds, both a multiple of the same amplification
@@ -160,8 +161,9 @@ def test_rho_vector_is_the_scalar_call_bit_for_bit(case, dt):
 
 # ---- 3. independence of the batch position, reproducibility ----
 @pytest.mark.parametrize("dt", DTYPES, ids=["f64", "f32"])
-@pytest.mark.parametrize("case", [(14, 7, 33, 5), (13, 5, 4, 5), (14, 3, 4, 3)], ids=ids)
+@pytest.mark.parametrize("case", [(14, 7, 33, 5), (13, 5, 4, 5), (14, 3, 4, 3), (18, 18, 3, 2)], ids=ids)
 def test_batch_position_and_reproducibility(case, dt):
+    """((18, 18): the 16-lane tail behind the run-time build's prefetch.)"""
     n, m, N, B = case
     _, _, dG, dC = case_arrays(n, m, N, B, dt)
     sol = solver(n, m, N, B)
@@ -203,11 +205,31 @@ def test_a_bad_trajectory_harms_no_neighbour(case, dt):
                     assert not np.isfinite(out["K"][1]).all(), (label, rho)        # (the poison arrived: 0 / 0 at rho = 0)
 
 
+@pytest.mark.parametrize("dt", DTYPES, ids=["f64", "f32"])
+@pytest.mark.parametrize("case", [(14, 7, 4, 6), (13, 5, 4, 6)], ids=ids)
+def test_containment_sweep(case, dt):
+    """tests/containment.py's sweep, as every other entry's: six trajectories, the sets {1}, {5}, {0, 3}; G and C with a
+    NaN and an Inf at the first, the last and a middle element, the whole trajectory NaN, a block of +-3e38 / +-1e308 that overflows inside
+    the kernel, all zeros; one rho[b] NaN.  K of every healthy trajectory carries the bits of the clean call.  Both builds of the kernel."""
+    from test_gpu_containment_linsys import runner
+    n, m, N, B = case
+    assert B == containment.B
+    G, Cd, _, _ = case_arrays(n, m, N, B, dt)
+    sol = solver(n, m, N, B)
+    inputs = {"G": G, "C": Cd, "rho": np.array([1e-3, 0.5, 10.0, 3e-2, 1.7, 1e-3], NPDT[dt])}
+    run = runner(lambda d: sol.riccati_gains(d["G"], d["C"], d["rho"], K=d["K"]), {"K": ((B, (N - 1) * m * n), NPDT[dt])})
+    tag = f"riccati_gains {case} {str(dt)[6:]}"
+    assert np.isfinite(run(inputs)["K"]).all()
+    containment.sweep(tag, inputs, ["G", "C"], run, matrices=("G", "C"), blocks={"G": n * n, "C": n * n})
+    containment.sweep(tag, inputs, ["rho"], run, only=("nan_one@first",))
+
+
 # ---- 5. arena: extents, alignment, const inputs, every element of K written ----
 @pytest.mark.parametrize("mode", arena.MODES)
 @pytest.mark.parametrize("dt", DTYPES, ids=["f64", "f32"])
-@pytest.mark.parametrize("case", [(14, 7, 4, 3), (13, 5, 4, 3), (17, 17, 3, 2)], ids=ids)
+@pytest.mark.parametrize("case", [(14, 7, 4, 3), (13, 5, 4, 3), (17, 17, 3, 2), (34, 32, 3, 2)], ids=ids)
 def test_arena(case, dt, mode):
+    """((34, 32): the first shape above 64 KiB of LDS, through both layouts.)"""
     n, m, N, B = case
     G, Cd, _, _ = case_arrays(n, m, N, B, dt)
     sol = solver(n, m, N, B)
@@ -310,3 +332,70 @@ def test_python_wrapper():
     for b in (0, B - 1):
         for k in (0, N - 2):
             np.testing.assert_allclose((V[b, k] @ dx).cpu().numpy(), Kref[b, k] @ dx.cpu().numpy(), rtol=0, atol=1e-12)
+
+
+# ---- 8. the gains are the sensitivity of the library's own QP solve ----
+def sensitivity_check(tag, k0, n, m, N, rho, max_bound=None):
+    """k0: a synth.KKT of one trajectory in float64.  K from mpcg_riccati_gains_f64 on its packed blocks; dz for c and for c perturbed at knot 1 by
+    mpcg_form_schur_f64 -> mpcg_block_solve_f64 -> mpcg_compute_dz_f64 on clones of G.  Both residuals of riccati_ref.feedback_residuals within
+    64 cond(KKT) 2.2e-16, cond computed here; first for a dense float64 solve on the host, which must be inside the bound by itself.
+    max_bound: the bound must lie below it, else None is returned before anything is asserted (the caller raises rho)."""
+    from mpcgpu_amd import synth
+    from test_generic_producers_cpu import dense_kkt_solve
+    k1 = rr.perturbed(k0, 901)
+    G, Cd, g, c0 = synth.pack_kkt_dense(k0, np.float64)
+    c1 = synth.pack_kkt_dense(k1, np.float64)[3]
+    dz0, _, Cm = dense_kkt_solve(k0, 0, rho)
+    dz1, _, _ = dense_kkt_solve(k1, 0, rho)
+    cond = rr.kkt_cond(k0, rho, Cm)
+    tol = 64 * cond * rr.EPS64
+    print(f"{tag} rho {rho:g}: cond(KKT) {cond:.3g}, bound {tol:.3g}")
+    if max_bound is not None and not tol < max_bound:
+        return None
+    sol = solver(n, m, N, 1)
+    dG, dC, dg = (dev(a, torch.float64) for a in (G, Cd, g))
+    K = sol.riccati_gains(dG, dC, rho, control_size=m)                  # (before the formation overwrites G with its block inverses)
+    torch.cuda.synchronize()
+    K = np.swapaxes(K.cpu().numpy().reshape(N - 1, n, m), -1, -2)
+    res = rr.feedback_residuals(dz0, dz1, K, k0)
+    print(f"{tag} rho {rho:g}: host dense solve, feedback {res[0]:.3g} dynamics {res[1]:.3g}")
+    assert max(res) <= tol, (tag, "the host dense solve", res, tol)
+
+    def device_solve(c):
+        Gc = dG.clone()
+        S, _, gamma = sol.form_schur(Gc, dC, dg, dev(c, torch.float64), rho, "ss", control_size=m)
+        lam = sol.block_solve(S, gamma)
+        dz = sol.compute_dz(Gc, dC, dg, lam, control_size=m)
+        torch.cuda.synchronize()
+        return dz.cpu().numpy()[0]
+    assert torch.equal(dG, dev(G, torch.float64))
+    res = rr.feedback_residuals(device_solve(c0), device_solve(c1), K, k0)
+    print(f"{tag} rho {rho:g}: device solve, feedback {res[0]:.3g} dynamics {res[1]:.3g}")
+    assert max(res) <= tol, (tag, "the device solve", res, tol)
+    return cond, tol, res
+
+
+@pytest.mark.parametrize("n,m,N", [(14, 7, 9), (13, 5, 6), (3, 2, 5), (17, 17, 4)], ids=lambda v: str(v))
+def test_gains_are_the_sensitivity_of_the_device_solve(n, m, N):
+    """K from the device against what the library's own direct path (Schur formation, block solve, dz; all double) does to a perturbation of c
+    in knot 1: du_k = K_k dx_k and the dynamics for every k >= 1.  The two code paths read rho and the packed G and C independently."""
+    from test_generic_producers_cpu import make_kkt_nm
+    assert sensitivity_check(f"({n}, {m}, {N})", make_kkt_nm(N, 1, 900 + N, n, m), n, m, N, rr.RHO) is not None
+
+
+def test_gains_are_the_sensitivity_of_the_device_solve_on_iiwa_blocks():
+    """The same on the blocks mpcg_generate_kkt_f64 makes of one iiwa tracking window at 8 knots.  cond(KKT) comes from those blocks and is not
+    known in advance: rho is raised from 1e-3 by decades, to 1e-1 at most, until 64 cond 2.2e-16 < 1e-6 (DESIGN.md section 3.19 records the
+    value this takes)."""
+    from mpcgpu_amd import Plant
+    N = 8
+    xu, goals, xs = iiwa.random_windows(N, 1, 41)
+    dt = torch.float64
+    G, Cd, g, c = solver(14, 7, N, 1).generate_kkt(Plant(), dev(goals.reshape(1, -1), dt), dev(xs, dt), dev(xu, dt), iiwa.TIMESTEP, iiwa.QD_COST, iiwa.r_cost(N))
+    torch.cuda.synchronize()
+    k0 = rr.kkt_of_packed(*(t.cpu().numpy()[0] for t in (G, Cd, g, c)), 14, 7, N)
+    for rho in (1e-3, 1e-2, 1e-1):
+        out = sensitivity_check("iiwa (14, 7, 8)", k0, 14, 7, N, rho, max_bound=1e-6)
+        if out is not None:
+            return
+    raise AssertionError("no rho up to 1e-1 brings 64 cond(KKT) 2.2e-16 below 1e-6 on the iiwa blocks")

@@ -12,47 +12,13 @@ import pytest
 import riccati_ref as rr
 from conftest import ROOT
 from mpcgpu_amd import synth
+from riccati_ref import feedback_residuals as _feedback_residuals, kkt_cond as _kkt_cond, perturbed as _perturbed
 from test_abi import _abi_class_c, _abi_class_ctypes
 from test_generic_producers_cpu import dense_kkt_solve, make_kkt_nm
 
 HEADER = os.path.join(ROOT, "include", "mpcg_riccati.h")
 ENTRIES = ["mpcg_riccati_gains", "mpcg_riccati_gains_f64"]
 QP_SHAPES = [(14, 7, 9), (6, 3, 5), (17, 17, 4), (1, 1, 3)]
-
-
-def _kkt_cond(k, rho, Cm):
-    """cond_2 of the regularised KKT matrix dense_kkt_solve factors."""
-    N, n, m = k.Q.shape[1], k.Q.shape[2], k.R.shape[-1]
-    nz = (n + m) * N - m
-    Gm = np.zeros((nz, nz))
-    for kk in range(N):
-        o = kk * (n + m)
-        Gm[o:o + n, o:o + n] = k.Q[0, kk] + rho * np.eye(n)
-        if kk < N - 1:
-            Gm[o + n:o + n + m, o + n:o + n + m] = k.R[0, kk] + rho * np.eye(m)
-    return float(np.linalg.cond(np.block([[Gm, Cm.T], [Cm, np.zeros((n * N, n * N))]])))
-
-
-def _perturbed(k, seed):
-    """The same QP with another c in knot 1 only."""
-    c = k.c.copy()
-    c[0, 1] += np.random.default_rng(seed).standard_normal(c.shape[-1])
-    return synth.KKT(k.Q, k.R, k.A, k.Bm, k.q, k.r, c)
-
-
-def _feedback_residuals(dz0, dz1, K, k):
-    """The two relative residuals of a solution difference caused in knot 1: du_k - K_k dx_k and dx_{k+1} - A_k dx_k - B_k du_k, k >= 1,
-    against the largest entry of the difference."""
-    N, n, m = k.Q.shape[1], k.Q.shape[2], k.R.shape[-1]
-    d = dz1 - dz0
-    dx = [d[kk * (n + m):kk * (n + m) + n] for kk in range(N)]
-    du = [d[kk * (n + m) + n:(kk + 1) * (n + m)] for kk in range(N - 1)]
-    scale = np.abs(d).max()
-    assert scale > 1e-3, "the perturbation did not reach the solution"
-    assert np.abs(dx[0]).max() <= 1e-9 * scale                 # x_0 is pinned: what hides K_0 from every right-hand side
-    r_fb = max(np.abs(du[kk] - K[kk] @ dx[kk]).max() for kk in range(1, N - 1))
-    r_dyn = max(np.abs(dx[kk + 1] - k.A[0, kk] @ dx[kk] - k.Bm[0, kk] @ du[kk]).max() for kk in range(1, N - 1))
-    return r_fb / scale, r_dyn / scale
 
 
 @pytest.mark.parametrize("n,m,N", QP_SHAPES)
